@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the draft-verify / accept / stop hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times exactly K steps and prints the line
+(`ms_per_step` = the time of one timed step).  --full adds the measurements of their own that sit beside the headline: the
+kernel-only `roofline` object (with the plain kernel, two batches in flight and the other workloads), the bounded `loop`
+sub-record, `cpu_baseline`, and at N > 1 the `sharded_verify` / `loop` data-path phase; --no-loop, --no-cpu-baseline and
+--no-other-workloads trim that set.  --dump-outputs DIR writes what the last timed step handed its caller (rank 0) as
+DIR/<name>.npy in float32 / float64; the inputs are seeded, so the same arguments give the same inputs on every run.
 
 N > 1 runs one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` the ranks
 come from the launcher (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment); started as a plain process
@@ -23,11 +30,11 @@ Logits buffers rotate through > 600 MB so the figure is HBM, not Infinity Cache.
 Prints ONE JSON line (rank 0; file descriptor 1 is pointed at stderr for everything else, RCCL's warnings included).
 `value` = verified tokens / s = sum_b (n_acc[b] + 1) per second, whole job.  N > 1: one process per GPU, every rank
 verifies its own batch of the same shape (batch-parallel replicas, no data-path collective; "weak" scaling); the barriers
-and the max-over-ranks of the times run over gloo, RCCL carries the one exchange step of the `sharded_verify` sub-record.
+and the max-over-ranks of the times run over gloo, RCCL carries the one exchange step of the `sharded_verify` sub-record (--full).
 Before the W warm-up steps the same step runs untimed for ~120 ms (a fresh box needs that to leave its idle clocks; the
 driver's job is 20 steps), and up to 64 steps are captured per graph (a short job is one replay).
 
-roofline: the ALGORITHMIC bytes (B*K*V*2 + 17*B*K + 4*B, +8*B for the ballot word) of the kernel a TIMED step
+roofline (--full): the ALGORITHMIC bytes (B*K*V*2 + 17*B*K + 4*B, +8*B for the ballot word) of the kernel a TIMED step
 launches -- by default k_verify<..., FUSED = true>, verify + accept + the in-kernel epilogue in one launch -- divided by its mean
 launch duration; `roofline.plain_kernel` repeats the measurement for the plain streaming kernel (FUSED = false: what
 --two-launch runs first), which is NOT what `value` was computed from.  Duration = HIP events recorded on the launch
@@ -36,10 +43,10 @@ right after the timed region in the same process (it includes the inter-kernel g
 slight over-estimate; it agrees with rocprofv3's kernel average within ~1 %, see profiles/).
 Event PAIRS around single launches are not used: on this stack a pair adds 5-15 us of its own to
 a ~16 us kernel (measured in round 1: 19.8 us per pair vs 16.6 us rocprofv3), and recording them
-inside the timed region would slow the very loop `value` is computed from.  cpu_baseline: the C oracle (oracle/,
+inside the timed region would slow the very loop `value` is computed from.  cpu_baseline (--full): the C oracle (oracle/,
 OpenMP over rows) on the host cores, same workload, bounded sample, rank 0 at N = 1 only.
 
-`loop` (N = 1, after the headline measurement): the token-level three-tier loop of BASELINE configs[2] / [3] on synthetic
+`loop` (--full, N = 1, after the headline measurement): the token-level three-tier loop of BASELINE configs[2] / [3] on synthetic
 7B / 32B / 72B-shape models.  Their passes run on the HIP decoder stack (asd_decoder_forward: asd_linear + csrc/decoder.hip,
 DESIGN 4.9) with the projection matrices re-laid tile-major in place; ASD_LOOP_TORCH_MODULES=1 runs the torch modules of rounds
 1-3a instead, ASD_LOOP_PACK_WEIGHTS=0 keeps the [N][D] layout.  `loop.model_execution` says which code ran per tier.
@@ -556,12 +563,14 @@ def main_lm_head(args):
     Cc = torch.tensor(STAGE_COSTS, dtype=torch.float64, device=device)
     p_hist = torch.ones((B, N_STAGES), dtype=torch.float64, device=device)
 
+    last_stop = [None]
+
     def step(i):
         b = bufs[i % nbuf]
         b["out"] = ver(b["h"], b["tok"], b["lp_d"], b["u"], out=b["out"])
         if not args.verify_only:
-            Kmod.predictor_stop(feat, packed, 64, 32, stage_idx=0, L=N_STAGES, lp=b["out"].lp_target, stats_col=5,
-                                risk_adjustment=True, n_obs=100, p_hist=p_hist, Cc=Cc, lam=1.0)
+            last_stop[0] = Kmod.predictor_stop(feat, packed, 64, 32, stage_idx=0, L=N_STAGES, lp=b["out"].lp_target, stats_col=5,
+                                               risk_adjustment=True, n_obs=100, p_hist=p_hist, Cc=Cc, lam=1.0)
 
     for i in range(args.warmup):
         step(i)
@@ -574,19 +583,26 @@ def main_lm_head(args):
     barrier()
     elapsed = time.perf_counter() - t0
     tokens = sum(int(bufs[(args.warmup + i) % nbuf]["out"].n_acc.sum().item()) + B for i in range(args.steps))
-    # kernel-only: back-to-back fused calls (two GEMM launches + the merge launch) between two events
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    runs = []
-    for r in range(4):                                     # run 0 settles clocks / power state and is dropped
-        e0.record()
-        for i in range(30):
-            b = bufs[i % nbuf]
-            ver(b["h"], b["tok"], b["lp_d"], b["u"], out=b["out"])
-        e1.record()
-        torch.cuda.synchronize()
-        if r:
-            runs.append(e0.elapsed_time(e1) / 30)
-    kern_ms = sum(runs) / len(runs)
+    if args.dump_outputs and rank == 0:
+        o = bufs[(args.warmup + args.steps - 1) % nbuf]["out"]
+        outs = {"lp_target": o.lp_target, "accept": o.accept, "n_acc": o.n_acc, "accept_bits": o.accept_bits}
+        if not args.verify_only:
+            outs.update(score=last_stop[0].score, k_star=last_stop[0].k_star, stop=last_stop[0].stop, p_hist=p_hist)
+        _dump_outputs(args.dump_outputs, outs)
+    if args.full:
+        # kernel-only: back-to-back fused calls (two GEMM launches + the merge launch) between two events
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        runs = []
+        for r in range(4):                                     # run 0 settles clocks / power state and is dropped
+            e0.record()
+            for i in range(30):
+                b = bufs[i % nbuf]
+                ver(b["h"], b["tok"], b["lp_d"], b["u"], out=b["out"])
+            e1.record()
+            torch.cuda.synchronize()
+            if r:
+                runs.append(e0.elapsed_time(e1) / 30)
+        kern_ms = sum(runs) / len(runs)
     stats = torch.tensor([elapsed, float(tokens)], dtype=torch.float64, device=red_dev)
     if world > 1:
         tmax = stats[:1].clone()
@@ -607,15 +623,16 @@ def main_lm_head(args):
                        "batch_per_gpu": B, "draft_len": K, "vocab": V, "hidden": D, "accumulate": "f32 MFMA (epilogue f64)",
                        "rotating_buffers": nbuf, "launch_mode": "eager",
                        "parallelism": f"batch-parallel replicas x{world}" if world > 1 else "single GPU"},
-            "roofline": {"bound": "mfma", "achieved": flops / (kern_ms * 1e-3) / 1e12, "peak": MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": flops / (kern_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, "traffic": None,
-                         "kernel": "asd::k_lm_head_tile<4> + <2> + k_accept_from_blocks (lm_head_verify.hip)",
-                         "algorithmic_flops": flops, "algorithmic_bytes": hbm,
-                         "hbm_GBs": hbm / (kern_ms * 1e-3) / 1e9, "hbm_frac": hbm / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_ms_mean": kern_ms, "kernel_ms_runs": runs,
-                         "timing": "HIP events around 3 runs of 30 back-to-back asd_lm_head_verify calls (after one settling run)"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"] = {"bound": "mfma", "achieved": flops / (kern_ms * 1e-3) / 1e12, "peak": MFMA_PEAK_TFLOPS,
+                               "unit": "TFLOP/s", "frac": flops / (kern_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, "traffic": None,
+                               "kernel": "asd::k_lm_head_tile<4> + <2> + k_accept_from_blocks (lm_head_verify.hip)",
+                               "algorithmic_flops": flops, "algorithmic_bytes": hbm,
+                               "hbm_GBs": hbm / (kern_ms * 1e-3) / 1e9, "hbm_frac": hbm / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "kernel_ms_mean": kern_ms, "kernel_ms_runs": runs,
+                               "timing": "HIP events around 3 runs of 30 back-to-back asd_lm_head_verify calls (after one settling run)"}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle as O
             vs = 8192                                           # bounded sample: the first 8192 vocabulary columns
             b = bufs[0]
@@ -643,8 +660,8 @@ def main_lm_head(args):
 def main_tiers(args):
     """`--placement tiers`: the timed step is ONE step of the three-tier loop (draft K tokens, tier-1 verify, stop rule,
     escalated blocks re-verified by tier 2, residual / bonus draw, per-sequence commit) with the tiers placed over the
-    ranks; value = committed tokens per second of the whole job.  The roofline object is still the verify kernel's,
-    measured on rank 0 on a resident c3-shaped buffer."""
+    ranks; value = committed tokens per second of the whole job.  With --full the line also carries the verify kernel's
+    roofline object, measured on rank 0 on a resident c3-shaped buffer."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -665,8 +682,7 @@ def main_tiers(args):
         dist.init_process_group(args.dist_backend, **({"device_id": device} if args.dist_backend == "nccl" else {}))
     B, K, V, desc = WORKLOADS[args.workload]
     B = args.loop_batch
-    steps = args.steps if args.steps != 1000 else 8
-    warmup = args.warmup if args.warmup != 300 else 2
+    steps, warmup = args.steps, args.warmup              # defaults 8 / 2 in this mode (main)
     sharded = args.placement == "sharded-target"
     if sharded:
         if world == 1:                                  # the sharded head talks to a process group even when it is alone
@@ -683,23 +699,6 @@ def main_tiers(args):
         rec = hierarchy_loop(torch, dist, device, rank, world, args.tier_shapes.split(","), B, K, 32, warmup, steps,
                              lam=args.lam, target_stop_rate=args.stop_rate)
     if rank == 0:
-        torch.cuda.empty_cache()
-        nbuf = 3
-        ws, bufs = build_inputs(torch, Kmod, B, K, V, nbuf, device, seed=1234)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-        def verify(buf):
-            Kmod.verify_accept(buf["logits"], buf["tok"], buf["lp_d"], buf["u"], ws, buf["out"])
-        for i in range(600):
-            verify(bufs[i % nbuf])
-        torch.cuda.synchronize()
-        e0.record()
-        for i in range(200):
-            verify(bufs[i % nbuf])
-        e1.record()
-        torch.cuda.synchronize()
-        kern_ms = e0.elapsed_time(e1) / 200
-        nbytes = algorithmic_bytes(B, K, V)
         out = {
             "metric": "verified_tokens_per_s", "value": rec["verified_tokens_per_s"], "unit": "tokens/s", "n_gpus": world,
             "steps": steps, "warmup": warmup, "ms_per_step": rec["ms_per_step"], "higher_is_better": True,
@@ -712,12 +711,31 @@ def main_tiers(args):
                                    "asd_residual_sample_ex + asd_commit_step; synthetic random-weight models",
                        "batch": B, "draft_len": K, "vocab": V, "parallelism": f"{args.placement} over {world} rank(s)",
                        "placement": rec["placement"]},
-            "roofline": {"bound": "hbm", "achieved": nbytes / (kern_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": nbytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
-                         "kernel": "asd::k_verify (verify_accept.hip)", "algorithmic_bytes": nbytes, "kernel_ms_mean": kern_ms,
-                         "timing": "HIP events around 200 back-to-back verify launches on rank 0 after the loop (3 rotating buffers)"},
             "loop": rec,
         }
+        if args.full:
+            # the verify kernel's roofline, measured on its own on a resident c3-shaped buffer (not what `value` times)
+            torch.cuda.empty_cache()
+            nbuf = 3
+            ws, bufs = build_inputs(torch, Kmod, B, K, V, nbuf, device, seed=1234)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+            def verify(buf):
+                Kmod.verify_accept(buf["logits"], buf["tok"], buf["lp_d"], buf["u"], ws, buf["out"])
+            for i in range(600):
+                verify(bufs[i % nbuf])
+            torch.cuda.synchronize()
+            e0.record()
+            for i in range(200):
+                verify(bufs[i % nbuf])
+            e1.record()
+            torch.cuda.synchronize()
+            kern_ms = e0.elapsed_time(e1) / 200
+            nbytes = algorithmic_bytes(B, K, V)
+            out["roofline"] = {"bound": "hbm", "achieved": nbytes / (kern_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": nbytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
+                               "kernel": "asd::k_verify (verify_accept.hip)", "algorithmic_bytes": nbytes, "kernel_ms_mean": kern_ms,
+                               "timing": "HIP events around 200 back-to-back verify launches on rank 0 after the loop (3 rotating buffers)"}
         _emit(out)
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -749,6 +767,27 @@ def _emit(obj):
     else:
         sys.stdout.flush()
         os.write(_RESULT_FD, line)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, one DIR/<name>.npy each, in float32, or in
+    float64 where float32 would not hold every value exactly (f64 outputs, 32- and 64-bit integers)."""
+    import numpy as np
+    import torch
+
+    host = {}
+    for name, t in arrays.items():
+        exact32 = t.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.int8, torch.int16, torch.bool)
+        host[name] = t.detach().to(torch.float32 if exact32 else torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def sharded_verify_step(torch, dist, device, rank, world, B, K, V, D=8192, reps=30, group=None):
@@ -907,8 +946,8 @@ def main_dry(args):
                "vs_baseline": None, "dtype": "bf16", "data": "none (dry run of the launcher: no kernel ran)",
                "dry_run": True, "config": {"workload": f"{args.workload}: {desc}", "parallelism": f"{world} rank(s), gloo, no GPU",
                                            "spawned_by_bench": os.environ.get("ASD_BENCH_SPAWNED") == "1"}}
-    if world > 1 and not args.no_loop:
-        # the data-path phase of the default multi-GPU line (sharded_verify + the bounded loop), as PLUMBING: the same watchdog,
+    if world > 1 and args.full and not args.no_loop:
+        # the data-path phase of the --full multi-GPU line (sharded_verify + the bounded loop), as PLUMBING: the same watchdog,
         # the same sub-record keys (values null), one collective standing in for the exchanges
         plan = multi_gpu_plan(world)
         state = {"out": out, "phase": "loop"}
@@ -1023,8 +1062,14 @@ def _job_store(dist):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
-    ap.add_argument("--warmup", type=int, default=300)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 1000; --placement tiers / sharded-target: 8)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 300; --placement tiers / sharded-target: 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the kernel-only roofline runs, the other workloads, two batches "
+                         "in flight, the bounded 7B/32B/72B loop sub-record, the CPU baseline and (N > 1) the sharded_verify / loop "
+                         "data-path phase.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64; rank 0)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the kernel-only c2/c5 side measurements")
@@ -1076,6 +1121,16 @@ def main():
                     help="--gpus N started without torch.distributed.run: seconds after which the spawned ranks are ended")
     args = ap.parse_args()
     args.fused = not (args.two_launch or args.verify_only)
+    loop_mode = args.placement in ("tiers", "sharded-target") and not args.lm_head
+    if args.steps is None:
+        args.steps = 8 if loop_mode else 1000
+    if args.warmup is None:
+        args.warmup = 2 if loop_mode else 300
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.dry_run or loop_mode):
+        ap.error("--dump-outputs writes the outputs of the kernel step (default placement, or --lm-head); "
+                 "not available with --dry-run or --placement tiers / sharded-target")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher BEFORE anything initialises the GPU (torch is not imported yet)
         sys.exit(_spawn_ranks(args.gpus, sys.argv[1:], args.launch_timeout))
@@ -1263,44 +1318,54 @@ def main():
     # verified tokens: outputs per buffer are deterministic, so count them after the timed region
     per_buf = [int(b["out"].n_acc.sum().item()) + B for b in bufs]
     tokens = sum(per_buf[(args.warmup + (i % G)) % nbuf] for i in range(args.steps))
-    # kernel-only duration: back-to-back verify launches bracketed by two events, best-of-3 + mean
-    reps = max(args.steps, 200)
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran buffer (warmup + G - 1) % nbuf from a graph, (warmup + steps - 1) % nbuf eager; score / k_star /
+        # stop / p_hist are shared by all steps and hold that step's values (nothing has launched since)
+        o = bufs[(args.warmup + (G if graph is not None else args.steps) - 1) % nbuf]["out"]
+        outs = {"lp_target": o.lp_target, "accept": o.accept, "n_acc": o.n_acc, "accept_bits": o.accept_bits}
+        if not args.verify_only:
+            outs.update(score=score, k_star=k_star, stop=stop, p_hist=p_hist)
+        _dump_outputs(args.dump_outputs, outs)
+    # everything below up to the result line runs with --full only: measurements of their own, never `value`
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for i in range(8000):                     # settle (~120 ms): the first launches after an idle gap run 5-15 % slower, and a
-                                              # short job (--steps 20) has not run long enough to reach the steady state
-        verify(bufs[i % nbuf])                # (clock / memory power state ramp; measured: 18.4 -> 16.0 us over 5 runs of 400)
-    torch.cuda.synchronize()
-    runs = []
-    for _ in range(5):
-        barrier()
-        e0.record()
-        for i in range(reps):
-            verify(bufs[i % nbuf])
-        e1.record()
-        torch.cuda.synchronize()
-        runs.append(e0.elapsed_time(e1) / reps)
-    kern_mean_ms = sum(runs) / len(runs)
-    kern_min_ms = min(runs)
-    # the same measurement for the kernel the DEFAULT step launches (the FUSED instantiation: verify + in-kernel epilogue)
     fused_runs = []
-    if args.fused:
-        for i in range(2000):
-            fused_step(bufs[i % nbuf])
+    if args.full:
+        # kernel-only duration: back-to-back verify launches bracketed by two events, best-of-3 + mean
+        reps = max(args.steps, 200)
+        for i in range(8000):                     # settle (~120 ms): the first launches after an idle gap run 5-15 % slower, and a
+                                                  # short job (--steps 20) has not run long enough to reach the steady state
+            verify(bufs[i % nbuf])                # (clock / memory power state ramp; measured: 18.4 -> 16.0 us over 5 runs of 400)
         torch.cuda.synchronize()
+        runs = []
         for _ in range(5):
             barrier()
             e0.record()
             for i in range(reps):
-                fused_step(bufs[i % nbuf])
+                verify(bufs[i % nbuf])
             e1.record()
             torch.cuda.synchronize()
-            fused_runs.append(e0.elapsed_time(e1) / reps)
+            runs.append(e0.elapsed_time(e1) / reps)
+        kern_mean_ms = sum(runs) / len(runs)
+        kern_min_ms = min(runs)
+        # the same measurement for the kernel the DEFAULT step launches (the FUSED instantiation: verify + in-kernel epilogue)
+        if args.fused:
+            for i in range(2000):
+                fused_step(bufs[i % nbuf])
+            torch.cuda.synchronize()
+            for _ in range(5):
+                barrier()
+                e0.record()
+                for i in range(reps):
+                    fused_step(bufs[i % nbuf])
+                e1.record()
+                torch.cuda.synchronize()
+                fused_runs.append(e0.elapsed_time(e1) / reps)
 
     # side measurement (never `value`): TWO independent batches in flight -- the same one-launch step on two streams with their own
     # workspaces and outputs, forked and joined inside one hipGraph.  What separates a serial step from the 9.7 us its bytes take at
     # 8 TB/s is mostly the ramp to the first byte and the tail behind the last one; a second batch hides them.
     two_stream = None
-    if args.fused and world == 1 and not args.no_other_workloads:
+    if args.full and args.fused and world == 1 and not args.no_other_workloads:
         try:
             ws_b = Kmod.VerifyWorkspace(B, K, V, torch.bfloat16, device)
             score_b, k_star_b, stop_b, p_hist_b = torch.empty_like(score), torch.empty_like(k_star), torch.empty_like(stop), p_hist.clone()
@@ -1360,14 +1425,15 @@ def main():
         tk = torch.tensor([tokens], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tk, op=dist.ReduceOp.SUM)
         tokens = int(tk.item())
-        km = torch.tensor([kern_mean_ms], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(km, op=dist.ReduceOp.MAX)
-        kern_mean_ms = float(km.item())
+        if args.full:
+            km = torch.tensor([kern_mean_ms], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(km, op=dist.ReduceOp.MAX)
+            kern_mean_ms = float(km.item())
 
     cpu_buf = bufs[0]
     # kernel-only figures for the other BASELINE shapes (not bench lines: context for the roofline)
     others = {}
-    if rank == 0 and world == 1 and not args.no_other_workloads:
+    if args.full and rank == 0 and world == 1 and not args.no_other_workloads:
         bufs = None
         torch.cuda.empty_cache()
         for name in sorted(WORKLOADS):
@@ -1448,7 +1514,7 @@ def main():
             torch.cuda.empty_cache()
 
     loop_rec = None
-    if world == 1 and not args.no_loop:
+    if args.full and world == 1 and not args.no_loop:
         # bounded sub-record: the full token-level loop around the hot path (7B draft / 32B / 72B on this one GPU,
         # stop rule live), so that "verified tokens/s, 7B-draft/72B-target" has driver-run evidence beside the
         # kernel-step rate.  Never part of `value`.
@@ -1462,14 +1528,6 @@ def main():
         torch.cuda.empty_cache()
 
     if rank == 0:
-        # roofline: the kernel the TIMED step launches (the FUSED instantiation unless --two-launch / --verify-only); the plain
-        # streaming kernel's figures sit beside it as `plain_kernel`
-        step_is_fused = bool(fused_runs)
-        plain_ms, plain_min_ms, plain_runs = kern_mean_ms, kern_min_ms, runs
-        if step_is_fused:
-            kern_mean_ms, kern_min_ms, runs = sum(fused_runs) / len(fused_runs), min(fused_runs), fused_runs
-        achieved = bytes_per_launch / (kern_mean_ms * 1e-3) / 1e9
-        traffic, traffic_src = load_traffic(fused=step_is_fused)
         out = {
             "metric": "verified_tokens_per_s",
             "value": tokens / elapsed,
@@ -1495,38 +1553,47 @@ def main():
                        "parallelism": f"batch-parallel replicas x{world}" if world > 1 else "single GPU",
                        "geometry": {"splits": args.splits, "threads": args.threads, "unroll": args.unroll,
                                     "nontemporal": args.nontemporal}},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": None if traffic is None else traffic.get("hbm_bytes_per_launch"),
-                         "traffic_source": traffic_src,
-                         "kernel": ("asd::k_verify<..., FUSED = true> (verify_accept.hip): verify + accept + the in-kernel statistics / predictor / "
-                                    "Bayes / DP epilogue -- the ONE kernel a timed step launches") if step_is_fused else
-                                   "asd::k_verify<..., FUSED = false> (verify_accept.hip): the step's dominant kernel",
-                         "algorithmic_bytes": bytes_per_launch,
-                         "kernel_ms_mean": kern_mean_ms, "kernel_ms_best_run": kern_min_ms, "kernel_ms_runs": runs,
-                         "timing": f"HIP events on the launch stream around 5 runs of {reps} back-to-back launches of that kernel "
-                                   "(rotating buffers) right after the timed region; includes inter-kernel gaps",
-                         "note": "event PAIRS around single launches add 5-15 us each on this stack (measured in round 1) and are not used"},
         }
-        if step_is_fused:
-            out["roofline"]["plain_kernel"] = {
-                "kernel": "asd::k_verify<..., FUSED = false>: the streaming verify + accept kernel alone (what --two-launch runs as its first launch)",
-                "kernel_ms_mean": plain_ms, "kernel_ms_best_run": plain_min_ms, "kernel_ms_runs": plain_runs,
-                "achieved": bytes_per_launch / (plain_ms * 1e-3) / 1e9,
-                "frac": bytes_per_launch / (plain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "note": "same algorithmic bytes, same measurement; NOT the kernel `value` was computed from"}
-        if two_stream is not None:
-            out["roofline"]["two_batches_in_flight"] = two_stream
-        if others:
-            out["roofline"]["other_workloads_kernel_only"] = others
-        if loop_rec is not None:
-            out["loop"] = loop_rec
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            # roofline: the kernel the TIMED step launches (the FUSED instantiation unless --two-launch / --verify-only); the plain
+            # streaming kernel's figures sit beside it as `plain_kernel`
+            step_is_fused = bool(fused_runs)
+            plain_ms, plain_min_ms, plain_runs = kern_mean_ms, kern_min_ms, runs
+            if step_is_fused:
+                kern_mean_ms, kern_min_ms, runs = sum(fused_runs) / len(fused_runs), min(fused_runs), fused_runs
+            achieved = bytes_per_launch / (kern_mean_ms * 1e-3) / 1e9
+            traffic, traffic_src = load_traffic(fused=step_is_fused)
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": None if traffic is None else traffic.get("hbm_bytes_per_launch"),
+                               "traffic_source": traffic_src,
+                               "kernel": ("asd::k_verify<..., FUSED = true> (verify_accept.hip): verify + accept + the in-kernel statistics / predictor / "
+                                          "Bayes / DP epilogue -- the ONE kernel a timed step launches") if step_is_fused else
+                                         "asd::k_verify<..., FUSED = false> (verify_accept.hip): the step's dominant kernel",
+                               "algorithmic_bytes": bytes_per_launch,
+                               "kernel_ms_mean": kern_mean_ms, "kernel_ms_best_run": kern_min_ms, "kernel_ms_runs": runs,
+                               "timing": f"HIP events on the launch stream around 5 runs of {reps} back-to-back launches of that kernel "
+                                         "(rotating buffers) right after the timed region; includes inter-kernel gaps",
+                               "note": "event PAIRS around single launches add 5-15 us each on this stack (measured in round 1) and are not used"}
+            if step_is_fused:
+                out["roofline"]["plain_kernel"] = {
+                    "kernel": "asd::k_verify<..., FUSED = false>: the streaming verify + accept kernel alone (what --two-launch runs as its first launch)",
+                    "kernel_ms_mean": plain_ms, "kernel_ms_best_run": plain_min_ms, "kernel_ms_runs": plain_runs,
+                    "achieved": bytes_per_launch / (plain_ms * 1e-3) / 1e9,
+                    "frac": bytes_per_launch / (plain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "note": "same algorithmic bytes, same measurement; NOT the kernel `value` was computed from"}
+            if two_stream is not None:
+                out["roofline"]["two_batches_in_flight"] = two_stream
+            if others:
+                out["roofline"]["other_workloads_kernel_only"] = others
+            if loop_rec is not None:
+                out["loop"] = loop_rec
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(np, torch, cpu_buf, B, K, V, weights, feat_np, args.cpu_budget_s)
     else:
         out = None
-    if distributed and not args.no_loop:
-        # N > 1, default arguments: the data path of the multi-GPU configurations, bounded by ONE watchdog (a hang prints the
+    if distributed and args.full and not args.no_loop:
+        # N > 1, --full: the data path of the multi-GPU configurations, bounded by ONE watchdog (a hang prints the
         # headline with the error recorded and exits non-zero):
         #   sharded_verify  the exchange step of a vocab-sharded 72B-shape head over this job's ranks (kernels + one all-gather)
         #   loop            BASELINE configs[3] at N = 2 ... 7 (tiers placed over the ranks), configs[4] at N >= 8 (replicated

@@ -60,7 +60,7 @@ def test_world_size_mismatch_is_an_error():
 def test_two_replica_ranks_on_one_gpu_from_a_plain_process():
     """The real step (asd_verify_accept_fused on resident logits) on two self-spawned ranks sharing cuda:0; control over gloo."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5",
-                        "--no-loop", "--no-cpu-baseline", "--no-other-workloads"], capture_output=True, text=True,
+                        "--full", "--no-loop", "--no-cpu-baseline", "--no-other-workloads"], capture_output=True, text=True,
                        timeout=600, env=_env(ASD_BENCH_ONE_DEVICE="1"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _one_line(r.stdout)
@@ -70,10 +70,10 @@ def test_two_replica_ranks_on_one_gpu_from_a_plain_process():
 
 @pytest.mark.parametrize("n,kind", [(2, "tiers"), (4, "tiers"), (8, "sharded-target")])
 def test_default_multi_gpu_line_carries_the_loop_sub_record_of_its_configuration(n, kind):
-    """the BARE command (`bench.py --gpus N`, what the driver runs) must exercise BASELINE configs[3] at
+    """`bench.py --gpus N --full` must exercise BASELINE configs[3] at
     N = 2 / 4 (tiers placed over the ranks, the reference's configs/qwen3_models.yaml:5-53) and configs[4] at N = 8 (replicated
     drafts + sharded target).  The dry run walks the same branch and prints the sub-record's keys with null values."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--dry-run", "--steps", "5", "--warmup", "1"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--dry-run", "--full", "--steps", "5", "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_line(r.stdout)
@@ -92,7 +92,7 @@ def test_default_multi_gpu_line_carries_the_loop_sub_record_of_its_configuration
 def test_a_rank_that_hangs_in_the_data_path_fails_the_job_but_the_headline_is_printed():
     """A collective that never completes: the watchdog prints the headline with the error recorded in the sub-record that was
     running and EVERY rank exits non-zero (round 3 left with exit code 0)."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--dry-stall-rank", "1", "--multi-gpu-timeout", "4",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--dry-stall-rank", "1", "--multi-gpu-timeout", "4",
                         "--launch-timeout", "90"], capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert r.returncode != 0
     d = _one_line(r.stdout)
@@ -104,7 +104,7 @@ def test_a_rank_whose_sub_record_raises_ends_the_job_in_seconds_not_at_the_time_
     the headline is printed with that rank's error and every rank exits non-zero -- long before --multi-gpu-timeout."""
     import time
     t0 = time.monotonic()
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--dry-raise-rank", "1", "--multi-gpu-timeout", "120",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--dry-raise-rank", "1", "--multi-gpu-timeout", "120",
                         "--launch-timeout", "200"], capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert r.returncode != 0
     assert time.monotonic() - t0 < 60
@@ -113,8 +113,24 @@ def test_a_rank_whose_sub_record_raises_ends_the_job_in_seconds_not_at_the_time_
 
 
 def test_a_sub_record_that_raises_on_every_rank_is_recorded_and_the_job_ends_normally():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--dry-raise-rank", "2", "--multi-gpu-timeout", "120",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--dry-raise-rank", "2", "--multi-gpu-timeout", "120",
                         "--launch-timeout", "200"], capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_line(r.stdout)
     assert "injected" in d["loop"]["error"] and d["loop"]["kind"] == "tiers"
+
+
+def test_plain_multi_gpu_line_carries_no_data_path_phase():
+    """Without --full a run prints the headline only: no sharded_verify / loop phase after the timed steps."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "5", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_line(r.stdout)
+    assert d["n_gpus"] == 2 and d["steps"] == 5 and "loop" not in d and "sharded_verify" not in d
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"], ["--dry-run", "--dump-outputs", "out"],
+                                  ["--placement", "tiers", "--dump-outputs", "out"]])
+def test_bad_arguments_are_refused_before_any_work(argv):
+    r = subprocess.run([sys.executable, BENCH] + argv, capture_output=True, text=True, timeout=120, env=_env(), cwd=ROOT)
+    assert r.returncode == 2 and r.stdout.strip() == "", r.stderr[-2000:]

@@ -8,10 +8,10 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 T=${ROUND:-r03}
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 320 --warmup 32 --no-cpu-baseline --no-other-workloads --no-loop"
+ARGS="--steps 320 --warmup 32 --full --no-cpu-baseline --no-other-workloads --no-loop"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_stats -o b -- python3 $R/bench.py $ARGS > $O/${T}_bench_under_rocprof.json 2> $O/${T}_bench_under_rocprof.err
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${T}_prof_fetch -o b -- python3 $R/bench.py --steps 48 --warmup 8 --no-cpu-baseline --no-other-workloads --no-loop --mode eager > /dev/null 2>&1
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${T}_prof_write -o b -- python3 $R/bench.py --steps 48 --warmup 8 --no-cpu-baseline --no-other-workloads --no-loop --mode eager > /dev/null 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${T}_prof_fetch -o b -- python3 $R/bench.py --steps 48 --warmup 8 --full --no-cpu-baseline --no-other-workloads --no-loop --mode eager > /dev/null 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${T}_prof_write -o b -- python3 $R/bench.py --steps 48 --warmup 8 --full --no-cpu-baseline --no-other-workloads --no-loop --mode eager > /dev/null 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_sampling -o s -- python3 $R/tools/bench_sampling.py --out $O/${T}_sampling_under_rocprof.json > /dev/null 2>&1
 cd $R
 python3 tools/kstats.py $O/${T}_prof_stats --top 8

@@ -10,9 +10,9 @@ set -e -o pipefail
 mkdir -p gpurun_out
 R=${ROUND:-r04}
 T="timeout -k 10 560"
-ASD_BENCH_ONE_DEVICE=1 $T python bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --loop-steps 6 --tier-shapes 7b,14b,32b \
+ASD_BENCH_ONE_DEVICE=1 $T python bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --full --loop-steps 6 --tier-shapes 7b,14b,32b \
   > gpurun_out/${R}_default_n2_gloo.json 2> gpurun_out/${R}_default_n2_gloo.err
-ASD_BENCH_ONE_DEVICE=1 $T python bench.py --gpus 4 --dist-backend gloo --steps 20 --warmup 5 --loop-steps 6 --tier-shapes tiny,tiny,tiny \
+ASD_BENCH_ONE_DEVICE=1 $T python bench.py --gpus 4 --dist-backend gloo --steps 20 --warmup 5 --full --loop-steps 6 --tier-shapes tiny,tiny,tiny \
   > gpurun_out/${R}_default_n4_gloo.json 2> gpurun_out/${R}_default_n4_gloo.err
 $T python bench.py --placement sharded-target --tier-shapes 7b,72b --steps 6 --warmup 2 > gpurun_out/${R}_sharded_real_n1.json 2> gpurun_out/${R}_sharded_real_n1.err
 for N in 2 4; do

@@ -7,7 +7,7 @@ set -e -o pipefail
 mkdir -p gpurun_out
 T="timeout -k 10 420"
 for N in 2 4; do
-  ASD_BENCH_ONE_DEVICE=1 $T python bench.py --gpus $N --dist-backend gloo --steps 20 --warmup 5 \
+  ASD_BENCH_ONE_DEVICE=1 $T python bench.py --gpus $N --dist-backend gloo --steps 20 --warmup 5 --full \
     > gpurun_out/r03_replicas_n${N}_gloo.json 2> gpurun_out/r03_replicas_n${N}_gloo.err
   python - <<PY
 import json
