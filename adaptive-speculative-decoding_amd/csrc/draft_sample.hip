@@ -148,208 +148,26 @@ template <int DT>
 __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
     using E = Elem<DT>;
     constexpr int N = E::kPerVec;
-    __shared__ unsigned long long hist[kDsDigits];
-    __shared__ float tile_mass[kDrMaxTiles];
-    __shared__ float red[kDrWaves][2];
-    __shared__ unsigned long long wave_tot[kDrWaves];
-    __shared__ unsigned long long sel_above, sel_incl;
-    __shared__ int sel_digit;
-    __shared__ uint32_t cand[kDrWaves][kDrSeg];       // per wave: ids of the tokens above the mass floor, tile by tile
-    __shared__ uint32_t tile_span[kDrMaxTiles];       // (first candidate << 16) | candidates of the tile, in its wave's list
-    __shared__ int overflow;
+    __shared__ NucleusLds sh;                          // phases 1-3: sample_device.hpp, nucleus_row_select
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.logits) + static_cast<int64_t>(b) * p.ld * E::kBytes);
-    // fn(v, vector) for this thread's vectors v = t, t + 1024, ... (after the first sweep the row is L2-resident).  The trip
-    // count is the same for all lanes of a wave -- a ragged last tile is padded with -inf vectors, which carry no mass
-    // anywhere -- so the wave reductions inside `fn` always run with every lane active.  Four of a thread's vectors are
-    // loaded before the first is consumed: with one load in flight per thread a sweep is 19 dependent L2 round trips.
-    // (Holding the row in registers instead, 19 x 16 B per lane, was tried: it spills at the 128-VGPR budget of a
-    // 1024-lane workgroup and was slower.)
-    auto for_each = [&](auto&& fn) {
-        constexpr int kAhead = 4;
-        const u32x4 neg = {E::kNegInfWord, E::kNegInfWord, E::kNegInfWord, E::kNegInfWord};
-        for (int v0 = t - lane; v0 < p.nvec; v0 += kAhead * kDrThreads) {
-            u32x4 q[kAhead];
-#pragma unroll
-            for (int j = 0; j < kAhead; ++j) {
-                const int v = v0 + j * kDrThreads + lane;
-                q[j] = v < p.nvec ? row[v] : neg;
-            }
-#pragma unroll
-            for (int j = 0; j < kAhead; ++j)
-                if (v0 + j * kDrThreads < p.nvec) fn(v0 + j * kDrThreads + lane, q[j]);     // wave-uniform guard
-        }
-    };
+    float* const tile_mass = sh.tile_mass;
+    uint32_t* const tile_span = sh.tile_span;
+    auto for_each = [&](auto&& fn) { row_sweep<DT>(row, p.nvec, t, fn); };
+    auto for_cand = [&](int count, auto&& fn) { cand_sweep<DT>(row, sh.cand[wave], count, lane, fn); };
     auto any_at_least = [&](const float (&x)[N], float bound) -> bool {
         bool any = false;
 #pragma unroll
         for (int i = 0; i < N; ++i) any = any || (x[i] >= bound);
         return __ballot(any) != 0ull;
     };
-    float m2, s;
-    ASD_DR_STAMP(0);
-    // Sweep 1 (the only pass that reads HBM) leaves every tile's CANONICAL (max, sum) pair in LDS and folds the pairs in the
-    // fixed order of fold_tile_pairs: L has the same bits as in k_draft_group, whatever the batch (round 2 ran a per-lane
-    // online softmax here when top-p was on: 5 us less for the sweep, but a value only this geometry could reproduce).
-    // Without truncation the tile masses then follow from L without a second exp-per-element sweep of the row.
     const bool tiles_from_sweep1 = p.levels == 0;
-    for_each([&](int v, const u32x4& vec) {
-        float M, sw;
-        tile_pair<DT>(vec, p.c2, M, sw);
-        if (lane == 0) {                                      // nothing is carried from tile to tile: the four tiles of a
-            tile_span[v >> 6] = __float_as_uint(M);           // for_each step reduce side by side
-            tile_mass[v >> 6] = sw;
-        }
-    });
-    __syncthreads();
-    fold_tile_pairs(reinterpret_cast<const float*>(tile_span), tile_mass, p.n_tiles, red, wave, lane, m2, s);
-    ASD_DR_STAMP(1);
-    double L64 = static_cast<double>(m2) + log2_split(s);      // log2 of the normaliser of the distribution drawn from
-    float thr = -INFINITY;
-    bool listed = false;       // the candidates of the row are in `cand`: the remaining phases walk the list, not the row
-    int wcnt = 0;              // candidates in this wave's list (wave-uniform)
-    // fn(slot, x) for this wave's candidates cand[wave][slot], slot in [0, count): 64 per step, four steps' logits gathered
-    // (L2 hits) before the first is used; lanes past the end see slot = -1, x = -inf
-    auto for_cand = [&](int count, auto&& fn) {
-        constexpr int kAhead = 4;
-        for (int e0 = 0; e0 < count; e0 += kAhead * 64) {
-            float x[kAhead];
-#pragma unroll
-            for (int j = 0; j < kAhead; ++j) {
-                const int e = e0 + j * 64 + lane;
-                x[j] = E::scalar(row, e < count ? cand[wave][e] : 0u);
-            }
-#pragma unroll
-            for (int j = 0; j < kAhead; ++j) {
-                const int e = e0 + j * 64 + lane;
-                if (e0 + j * 64 < count) fn(e < count ? e : -1, e < count ? x[j] : -INFINITY);
-            }
-        }
-    };
-    if (p.levels > 0 && s > 0.0f) {
-        const float L = static_cast<float>(L64);
-        const float p_floor = fmaxf((1.0f - p.top_p) / static_cast<float>(p.V), 1.0f / kDsFix);
-        const float x_floor = (L + __builtin_amdgcn_logf(p_floor)) / p.c2;      // p >= p_floor  <=>  x >= x_floor
-        // ---- candidates.  Tokens below p_floor = (1 - top_p) / V carry < 1 - top_p together, so the threshold lies above
-        // all of them and they can never be drawn.  One compare-only sweep lists the others (per-lane counts, DPP prefix
-        // sum, lane-major inside a tile: a fixed order) in the LDS segment of the wave that owns their tile; the histogram
-        // levels, the nucleus normaliser and the tile masses then cost a few candidates per lane instead of a sweep of
-        // divergent per-element work.  A row too flat for the lists (some wave holds more than kDrSeg candidates) keeps
-        // the sweeps.
-        if (t == 0) overflow = 0;
-        __syncthreads();
-        bool over = false;
-        for_each([&](int v, const u32x4& vec) {
-            float x[N];
-            unpack<DT>(vec, x);
-            uint32_t keep = 0u;                           // bit i: element i of this lane's vector is a candidate
-#pragma unroll
-            for (int i = 0; i < N; ++i) keep |= (x[i] >= x_floor ? 1u : 0u) << i;
-            const int first = wcnt;
-            if (__ballot(keep != 0u) != 0ull) {
-                const int cnt = __builtin_popcount(keep);
-                const int incl = wave_incl_scan_i32(cnt);
-                const int n = __builtin_amdgcn_readlane(incl, 63);
-                if (wcnt + n <= kDrSeg) {
-                    int at = wcnt + incl - cnt;           // lane-major inside the tile: a fixed order
-                    while (keep != 0u) {                  // as many rounds as the fullest lane has candidates (1-3, not N)
-                        cand[wave][at++] = static_cast<uint32_t>(v * N + __builtin_ctz(keep));
-                        keep &= keep - 1u;
-                    }
-                    wcnt += n;
-                } else {
-                    over = true;
-                }
-            }
-            if (lane == 0) tile_span[v >> 6] = (static_cast<uint32_t>(first) << 16) | static_cast<uint32_t>(wcnt - first);
-        });
-        if (over && lane == 0) overflow = 1;
-        __syncthreads();
-        listed = overflow == 0;
-        ASD_DR_STAMP(12);
-
-        unsigned long long above = 0ull, target = 0ull;
-        uint32_t prefix = 0u;
-        bool empty = false;
-        const int shifts[3] = {20, 8, 0}, widths[3] = {12, 12, 8};
-        for (int lv = 0; lv < p.levels; ++lv) {
-            const int shift = shifts[lv], digits = 1 << widths[lv], hi_shift = shifts[lv] + widths[lv];
-            for (int i = t; i < digits; i += kDrThreads) hist[i] = 0ull;
-            if (t == 0) sel_digit = -1;
-            __syncthreads();
-            ASD_DR_STAMP(2 + 2 * lv);
-            // every candidate adds its probability, 2^-40 fixed point, to the slot of its digit
-            auto add_mass = [&](int, float x) {
-                if (!(x >= x_floor)) return;
-                const uint32_t key = order_key(x);
-                const bool mine = hi_shift >= 32 || (key >> hi_shift) == (prefix >> hi_shift);
-                if (mine) atomicAdd(&hist[(key >> shift) & (digits - 1)], mass_fixed40(fast_exp2(fmaf(x, p.c2, -L))));
-            };
-            if (listed) {
-                for_cand(wcnt, add_mass);
-            } else {
-                for_each([&](int, const u32x4& vec) {
-                    float x[N];
-                    unpack<DT>(vec, x);
-                    if (!any_at_least(x, x_floor)) return;
-#pragma unroll
-                    for (int i = 0; i < N; ++i) add_mass(0, x[i]);
-                });
-            }
-            __syncthreads();
-            ASD_DR_STAMP(3 + 2 * lv);
-            // thread t owns the t-th chunk of digits counted from the TOP
-            const int per = digits >= kDrThreads ? digits / kDrThreads : 1;
-            const int hi = digits - t * per, lo = hi - per;
-            unsigned long long mine = 0ull;
-            if (lo >= 0)
-                for (int j = lo; j < hi; ++j) mine += hist[j];
-            const unsigned long long incl = wave_incl_scan_u64(mine, lane);
-            if (lane == 63) wave_tot[wave] = incl;
-            __syncthreads();
-            unsigned long long base = 0ull, total = 0ull;
-#pragma unroll
-            for (int w = 0; w < kDrWaves; ++w) {
-                if (w < wave) base += wave_tot[w];
-                total += wave_tot[w];
-            }
-            if (lv == 0) {   // the probabilities sum to 1 = 2^40 fixed point (the histogram only holds the tokens above p_floor)
-                target = static_cast<unsigned long long>(static_cast<double>(p.top_p) * static_cast<double>(kDsFix));
-                if (target > total) target = total;      // fixed-point truncation: never ask for more than is there
-                if (target == 0ull) target = 1ull;
-                empty = total == 0ull;
-            }
-            const unsigned long long before = above + base + incl - mine;
-            if (lo >= 0 && mine > 0ull && before < target && target <= before + mine) {   // exactly one thread
-                unsigned long long acc = before;
-                int pick = lo;
-                for (int j = hi - 1; j >= lo; --j) {
-                    const unsigned long long m = hist[j];
-                    if (m > 0ull && acc + m >= target) { pick = j; break; }
-                    acc += m;
-                }
-                sel_digit = pick;
-                sel_above = acc;
-                sel_incl = acc + hist[pick];
-            }
-            __syncthreads();
-            const int dg = sel_digit;
-            if (dg < 0) empty = true;
-            else {
-                prefix |= static_cast<uint32_t>(dg) << shift;
-                above = sel_above;
-            }
-            __syncthreads();                              // sel_* and hist are rewritten by the next level
-        }
-        // 16-bit logits: the low 8 key bits were never examined because they are constant -- zeros for x >= 0, ones for
-        // x < 0 (the key of a negative float is its complement) -- so the threshold is the logit value itself
-        if (p.levels == 2 && !(prefix & 0x80000000u)) prefix |= 0xffu;
-        thr = empty ? -INFINITY : key_floor_value(prefix);
-        // The nucleus normaliser needs no pass of its own: the last level's scan has summed the masses of exactly the tokens
-        // >= thr (2^-40 fixed point relative to L, an integer sum: reproducible, |error| < candidates * 2^-40).
-        if (!empty) L64 = static_cast<double>(L) + log2_split(static_cast<float>(sel_incl)) - 40.0;
-        ASD_DR_STAMP(8);
-    }
+    const NucleusSel sel = nucleus_row_select<DT>(row, p.V, p.nvec, p.n_tiles, p.c2, p.top_p, p.levels, sh, t,
+                                                  [&](int slot) { ASD_DR_STAMP(slot); });
+    const double L64 = sel.L64;
+    const float thr = sel.thr;
+    const bool listed = sel.listed;
+    const int wcnt = sel.wcnt;
     if (t == 0 && p.thr) p.thr[b] = thr;
 
     // ---- tile masses of the (nucleus-restricted) softmax.  Thread t's j-th vector is v = t + 1024 j = 64 (wave + 16 j) + lane:
@@ -359,7 +177,7 @@ __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
         // every candidate's mass replaces its id (the ids are not needed again); then one lane per tile adds its tile's
         // masses in list order.  All of it is wave-local: a wave lists, weighs and sums its own tiles.
         for_cand(wcnt, [&](int slot, float x) {
-            if (slot >= 0) cand[wave][slot] = __float_as_uint(x >= thr ? fast_exp2(fmaf(x, p.c2, -Lt)) : 0.0f);
+            if (slot >= 0) sh.cand[wave][slot] = __float_as_uint(x >= thr ? fast_exp2(fmaf(x, p.c2, -Lt)) : 0.0f);
         });
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -368,7 +186,7 @@ __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
             const uint32_t span = tile_span[tile];
             const int first = static_cast<int>(span >> 16), last = first + static_cast<int>(span & 0xffffu);
             float z = 0.0f;
-            for (int e = first; e < last; ++e) z += __uint_as_float(cand[wave][e]);
+            for (int e = first; e < last; ++e) z += __uint_as_float(sh.cand[wave][e]);
             tile_mass[tile] = z;
         }
     } else if (tiles_from_sweep1) {

@@ -40,6 +40,8 @@ struct RsParams {
     float2* tiles;            // [B][n_tiles]  (Z, P)
     int32_t* token;
     const float* d_thr;       // [B*K] nucleus thresholds of the draft rows (logit < thr => p_d = 0, renormalised) or nullptr
+    const float* t_thr;       // [B*K] nucleus thresholds of the target rows (asd_verify_accept_top_p's x*) or nullptr
+    const float* b_thr;       // [B] nucleus thresholds of the bonus rows (k_rs_bonus_threshold) or nullptr
 };
 
 template <int DT>
@@ -58,8 +60,10 @@ __device__ __forceinline__ Rows<DT> select_rows(const RsParams& p, int b) {
         r.xt = static_cast<const char*>(p.t_logits) + (static_cast<int64_t>(b) * p.K + j) * p.ld_t * E::kBytes;
         r.xd = static_cast<const char*>(p.d_logits) + (static_cast<int64_t>(b) * p.K + j) * p.ld_d * E::kBytes;
         if (p.d_thr) r.dthr = p.d_thr[static_cast<int64_t>(b) * p.K + j];
+        if (p.t_thr) r.tthr = p.t_thr[static_cast<int64_t>(b) * p.K + j];
     } else if (p.bonus) {
         r.xt = static_cast<const char*>(p.bonus) + static_cast<int64_t>(b) * p.ld_b * E::kBytes;
+        if (p.b_thr) r.tthr = p.b_thr[b];
     }
     return r;
 }
@@ -472,6 +476,22 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
     rs_pick_scan<DT>(p, b, lane, rows, tiles, Lt, Ld, sc);
 }
 
+// ---- asd_residual_sample_top_p: the nucleus threshold x* of every BONUS row (n_acc[b] outside [0, K)), one 1024-lane workgroup
+// per sequence.  The bonus row has no verify output, so its x* is found here -- by the select of asd_draft_sample itself
+// (sample_device.hpp, nucleus_row_select): the same bits as asd_draft_sample's nucleus_logit on that row.  Sequences that
+// draw from a residual (or have no bonus row) leave at once.
+template <int DT>
+__global__ __launch_bounds__(kDrThreads) void k_rs_bonus_threshold(const RsParams p, float top_p, int levels, float* b_thr) {
+    using E = Elem<DT>;
+    __shared__ NucleusLds sh;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int j = p.n_acc[b];
+    if ((j >= 0 && j < p.K) || !p.bonus) return;                        // block-uniform
+    const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.bonus) + static_cast<int64_t>(b) * p.ld_b * E::kBytes);
+    const NucleusSel sel = nucleus_row_select<DT>(row, p.V, p.nvec, p.n_tiles, p.c2, top_p, levels, sh, t, [](int) {});
+    if (t == 0) b_thr[b] = sel.thr;
+}
+
 // sequences from which the one-workgroup-per-sequence form is used (tools/rs_threshold_ab.sh, V = 152064 bf16: three launches
 // 31.6 / 37.8 / 50.1 / 63.9 / 116.4 us at B = 48 / 64 / 96 / 128 / 256, this form 49-55 us at every B)
 constexpr int kRsRowMinBatch = 96;
@@ -536,7 +556,7 @@ namespace {
 int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d, const void* bonus_logits,
                     int64_t ld_b, int dtype, const int32_t* n_acc, const float* r, int B, int K, int V,
                     float inv_temperature, const float* d_threshold, int32_t* token, void* workspace,
-                    size_t workspace_bytes, void* stream) {
+                    size_t workspace_bytes, void* stream, const float* t_threshold = nullptr, float top_p = 1.0f) {
     if (B < 0 || K < 0 || V < 1) return ASD_ERR_INVALID_ARG;
     if (B == 0) return ASD_OK;
     const int esz = dtype_size(dtype);
@@ -564,6 +584,24 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     p.token = token;
     p.d_thr = d_threshold;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (top_p > 0.0f && top_p < 1.0f) {
+        // the target's nucleus: x* of the rejected rows from the verify (t_threshold), of the bonus rows found here first.
+        // Their [B] thresholds live behind the part of the workspace asd_residual_sample_workspace_bytes sizes.
+        if (p.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
+        const size_t base = asd_residual_sample_workspace_bytes(B, V, dtype);
+        float* b_thr = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);
+        p.t_thr = t_threshold;
+        p.b_thr = b_thr;
+        const int levels = dtype == ASD_DTYPE_F32 ? 3 : 2;
+        const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
+        switch (dtype) {
+            case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_BF16>, grid, block, 0, st, p, top_p, levels, b_thr); break;
+            case ASD_DTYPE_F16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F16>, grid, block, 0, st, p, top_p, levels, b_thr); break;
+            default: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F32>, grid, block, 0, st, p, top_p, levels, b_thr); break;
+        }
+        if (launch_status() != ASD_OK) return ASD_ERR_HIP;
+        workspace_bytes = base;                        // the geometry choice below sees the workspace asd_residual_sample_ex would
+    }
     // few sequences: G workgroups per sequence, rows resident in registers, one launch (the mailboxes live behind the legacy
     // part of the workspace and must have been zeroed once: asd_workspace_init)
     {
@@ -637,4 +675,23 @@ ASD_EXPORT int asd_residual_sample_ex(const void* t_logits, int64_t ld_t, const 
                                       void* stream) {
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
                            d_threshold, token, workspace, workspace_bytes, stream);
+}
+
+ASD_EXPORT size_t asd_residual_sample_top_p_workspace_bytes(int B, int V, int dtype) {
+    return asd_residual_sample_workspace_bytes(B, V, dtype) + round_up(static_cast<size_t>(B > 0 ? B : 0) * sizeof(float), 256);
+}
+
+ASD_EXPORT int asd_residual_sample_top_p(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                                         const void* bonus_logits, int64_t ld_b, int dtype, const int32_t* n_acc,
+                                         const float* r, int B, int K, int V, float inv_temperature, float top_p,
+                                         const float* t_threshold, const float* d_threshold, int32_t* token, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    if (top_p != top_p) return ASD_ERR_INVALID_ARG;
+    if (!(top_p > 0.0f && top_p < 1.0f))                 // no truncation: asd_residual_sample_ex itself (the same bits)
+        return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
+                               d_threshold, token, workspace, workspace_bytes, stream);
+    if (B > 0 && K > 0 && !t_threshold) return ASD_ERR_INVALID_ARG;
+    if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
+    return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
+                           d_threshold, token, workspace, workspace_bytes, stream, t_threshold, top_p);
 }

@@ -172,6 +172,239 @@ __device__ __forceinline__ double wave_incl_scan_f64(double v, int lane) {
     return v;
 }
 
+// ---- the nucleus select of ONE row inside ONE 1024-lane workgroup: phases 1-3 of k_draft_row (draft_sample.hip), shared
+// with k_verify_nucleus (verify_nucleus.hip) and the bonus-row threshold of asd_residual_sample_top_p (residual_sample.hip).
+// One body for all three is what makes x* and L_N -- and so log q(tok) / lp_t -- the same bits in every one of them.
+struct NucleusLds {
+    unsigned long long hist[kDsDigits];
+    float tile_mass[kDrMaxTiles];
+    float red[kDrWaves][2];
+    unsigned long long wave_tot[kDrWaves];
+    unsigned long long sel_above, sel_incl;
+    int sel_digit;
+    uint32_t cand[kDrWaves][kDrSeg];       // per wave: ids of the tokens above the mass floor, tile by tile
+    uint32_t tile_span[kDrMaxTiles];       // (first candidate << 16) | candidates of the tile, in its wave's list
+    int overflow;
+};
+
+// fn(v, vector) for thread t's vectors v = t, t + 1024, ... (after the first sweep the row is L2-resident).  The trip count is
+// the same for all lanes of a wave -- a ragged last tile is padded with -inf vectors, which carry no mass anywhere -- so the wave
+// reductions inside `fn` always run with every lane active.  Four of a thread's vectors are loaded before the first is consumed:
+// with one load in flight per thread a sweep is 19 dependent L2 round trips.  (Holding the row in registers instead, 19 x 16 B
+// per lane, was tried: it spills at the 128-VGPR budget of a 1024-lane workgroup and was slower.)
+template <int DT, class Fn>
+__device__ __forceinline__ void row_sweep(const u32x4* row, int nvec, int t, Fn&& fn) {
+    using E = Elem<DT>;
+    constexpr int kAhead = 4;
+    const int lane = t & 63;
+    const u32x4 neg = {E::kNegInfWord, E::kNegInfWord, E::kNegInfWord, E::kNegInfWord};
+    for (int v0 = t - lane; v0 < nvec; v0 += kAhead * kDrThreads) {
+        u32x4 q[kAhead];
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) {
+            const int v = v0 + j * kDrThreads + lane;
+            q[j] = v < nvec ? row[v] : neg;
+        }
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j)
+            if (v0 + j * kDrThreads < nvec) fn(v0 + j * kDrThreads + lane, q[j]);     // wave-uniform guard
+    }
+}
+// fn(slot, x) for this wave's candidates cand[slot], slot in [0, count): 64 per step, four steps' logits gathered (L2 hits)
+// before the first is used; lanes past the end see slot = -1, x = -inf
+template <int DT, class Fn>
+__device__ __forceinline__ void cand_sweep(const u32x4* row, const uint32_t* cand, int count, int lane, Fn&& fn) {
+    using E = Elem<DT>;
+    constexpr int kAhead = 4;
+    for (int e0 = 0; e0 < count; e0 += kAhead * 64) {
+        float x[kAhead];
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) {
+            const int e = e0 + j * 64 + lane;
+            x[j] = E::scalar(row, e < count ? cand[e] : 0u);
+        }
+#pragma unroll
+        for (int j = 0; j < kAhead; ++j) {
+            const int e = e0 + j * 64 + lane;
+            if (e0 + j * 64 < count) fn(e < count ? e : -1, e < count ? x[j] : -INFINITY);
+        }
+    }
+}
+
+struct NucleusSel {
+    float thr;        // x*: the nucleus is { v : x_v >= thr } (-inf: no truncation, an empty select or a row without mass)
+    double L64;       // log2 of the normaliser of the distribution drawn from / scored against (L_N with truncation)
+    bool listed;      // the candidates of the row are in sh.cand: later phases walk the lists, not the row
+    int wcnt;         // candidates in this wave's list (wave-uniform)
+};
+
+//   1. (m2, s) of the row                                   -> L, the softmax normaliser            (sweep, exp per element)
+//   2. top-p only (levels > 0): tokens below the mass floor (1 - top_p) / V cannot be inside the nucleus; a compare-only sweep
+//      lists the rest (the CANDIDATES) in LDS, per wave, tile by tile, in a fixed order             (sweep, compares)
+//   3. radix select on probability MASS over the candidates (2^-40 fixed point, integer adds: reproducible) -> x*, L_N
+// (draft_sample.hip explains each phase.)  Leaves the tile pairs' sums in sh.tile_mass / their maxima in sh.tile_span when
+// levels == 0, the candidate spans in sh.tile_span otherwise.  All 1024 threads call it; `stamp(slot)` marks phase boundaries.
+template <int DT, class Stamp>
+__device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V, int nvec, int n_tiles, float c2, float top_p,
+                                                         int levels, NucleusLds& sh, int t, Stamp&& stamp) {
+    using E = Elem<DT>;
+    constexpr int N = E::kPerVec;
+    const int lane = t & 63, wave = t >> 6;
+    auto any_at_least = [&](const float (&x)[N], float bound) -> bool {
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < N; ++i) any = any || (x[i] >= bound);
+        return __ballot(any) != 0ull;
+    };
+    float m2, s;
+    stamp(0);
+    // Sweep 1 (the only pass that reads HBM) leaves every tile's CANONICAL (max, sum) pair in LDS and folds the pairs in the
+    // fixed order of fold_tile_pairs: L has the same bits as in k_draft_group, whatever the batch (round 2 ran a per-lane
+    // online softmax here when top-p was on: 5 us less for the sweep, but a value only this geometry could reproduce).
+    // Without truncation the tile masses then follow from L without a second exp-per-element sweep of the row.
+    row_sweep<DT>(row, nvec, t, [&](int v, const u32x4& vec) {
+        float M, sw;
+        tile_pair<DT>(vec, c2, M, sw);
+        if (lane == 0) {                                      // nothing is carried from tile to tile: the four tiles of a
+            sh.tile_span[v >> 6] = __float_as_uint(M);        // row_sweep step reduce side by side
+            sh.tile_mass[v >> 6] = sw;
+        }
+    });
+    __syncthreads();
+    fold_tile_pairs(reinterpret_cast<const float*>(sh.tile_span), sh.tile_mass, n_tiles, sh.red, wave, lane, m2, s);
+    stamp(1);
+    NucleusSel r;
+    r.L64 = static_cast<double>(m2) + log2_split(s);
+    r.thr = -INFINITY;
+    r.listed = false;
+    r.wcnt = 0;
+    int& wcnt = r.wcnt;
+    if (levels > 0 && s > 0.0f) {
+        const float L = static_cast<float>(r.L64);
+        const float p_floor = fmaxf((1.0f - top_p) / static_cast<float>(V), 1.0f / kDsFix);
+        const float x_floor = (L + __builtin_amdgcn_logf(p_floor)) / c2;      // p >= p_floor  <=>  x >= x_floor
+        // ---- candidates.  Tokens below p_floor = (1 - top_p) / V carry < 1 - top_p together, so the threshold lies above
+        // all of them.  One compare-only sweep lists the others (per-lane counts, DPP prefix sum, lane-major inside a tile: a
+        // fixed order) in the LDS segment of the wave that owns their tile; the histogram levels, the nucleus normaliser and
+        // the tile masses then cost a few candidates per lane instead of a sweep of divergent per-element work.  A row too
+        // flat for the lists (some wave holds more than kDrSeg candidates) keeps the sweeps.
+        if (t == 0) sh.overflow = 0;
+        __syncthreads();
+        bool over = false;
+        row_sweep<DT>(row, nvec, t, [&](int v, const u32x4& vec) {
+            float x[N];
+            unpack<DT>(vec, x);
+            uint32_t keep = 0u;                           // bit i: element i of this lane's vector is a candidate
+#pragma unroll
+            for (int i = 0; i < N; ++i) keep |= (x[i] >= x_floor ? 1u : 0u) << i;
+            const int first = wcnt;
+            if (__ballot(keep != 0u) != 0ull) {
+                const int cnt = __builtin_popcount(keep);
+                const int incl = wave_incl_scan_i32(cnt);
+                const int n = __builtin_amdgcn_readlane(incl, 63);
+                if (wcnt + n <= kDrSeg) {
+                    int at = wcnt + incl - cnt;           // lane-major inside the tile: a fixed order
+                    while (keep != 0u) {                  // as many rounds as the fullest lane has candidates (1-3, not N)
+                        sh.cand[wave][at++] = static_cast<uint32_t>(v * N + __builtin_ctz(keep));
+                        keep &= keep - 1u;
+                    }
+                    wcnt += n;
+                } else {
+                    over = true;
+                }
+            }
+            if (lane == 0) sh.tile_span[v >> 6] = (static_cast<uint32_t>(first) << 16) | static_cast<uint32_t>(wcnt - first);
+        });
+        if (over && lane == 0) sh.overflow = 1;
+        __syncthreads();
+        r.listed = sh.overflow == 0;
+        stamp(12);
+
+        unsigned long long above = 0ull, target = 0ull;
+        uint32_t prefix = 0u;
+        bool empty = false;
+        const int shifts[3] = {20, 8, 0}, widths[3] = {12, 12, 8};
+        for (int lv = 0; lv < levels; ++lv) {
+            const int shift = shifts[lv], digits = 1 << widths[lv], hi_shift = shifts[lv] + widths[lv];
+            for (int i = t; i < digits; i += kDrThreads) sh.hist[i] = 0ull;
+            if (t == 0) sh.sel_digit = -1;
+            __syncthreads();
+            stamp(2 + 2 * lv);
+            // every candidate adds its probability, 2^-40 fixed point, to the slot of its digit
+            auto add_mass = [&](int, float x) {
+                if (!(x >= x_floor)) return;
+                const uint32_t key = order_key(x);
+                const bool mine = hi_shift >= 32 || (key >> hi_shift) == (prefix >> hi_shift);
+                if (mine) atomicAdd(&sh.hist[(key >> shift) & (digits - 1)], mass_fixed40(fast_exp2(fmaf(x, c2, -L))));
+            };
+            if (r.listed) {
+                cand_sweep<DT>(row, sh.cand[wave], wcnt, lane, add_mass);
+            } else {
+                row_sweep<DT>(row, nvec, t, [&](int, const u32x4& vec) {
+                    float x[N];
+                    unpack<DT>(vec, x);
+                    if (!any_at_least(x, x_floor)) return;
+#pragma unroll
+                    for (int i = 0; i < N; ++i) add_mass(0, x[i]);
+                });
+            }
+            __syncthreads();
+            stamp(3 + 2 * lv);
+            // thread t owns the t-th chunk of digits counted from the TOP
+            const int per = digits >= kDrThreads ? digits / kDrThreads : 1;
+            const int hi = digits - t * per, lo = hi - per;
+            unsigned long long mine = 0ull;
+            if (lo >= 0)
+                for (int j = lo; j < hi; ++j) mine += sh.hist[j];
+            const unsigned long long incl = wave_incl_scan_u64(mine, lane);
+            if (lane == 63) sh.wave_tot[wave] = incl;
+            __syncthreads();
+            unsigned long long base = 0ull, total = 0ull;
+#pragma unroll
+            for (int w = 0; w < kDrWaves; ++w) {
+                if (w < wave) base += sh.wave_tot[w];
+                total += sh.wave_tot[w];
+            }
+            if (lv == 0) {   // the probabilities sum to 1 = 2^40 fixed point (the histogram only holds the tokens above p_floor)
+                target = static_cast<unsigned long long>(static_cast<double>(top_p) * static_cast<double>(kDsFix));
+                if (target > total) target = total;      // fixed-point truncation: never ask for more than is there
+                if (target == 0ull) target = 1ull;
+                empty = total == 0ull;
+            }
+            const unsigned long long before = above + base + incl - mine;
+            if (lo >= 0 && mine > 0ull && before < target && target <= before + mine) {   // exactly one thread
+                unsigned long long acc = before;
+                int pick = lo;
+                for (int j = hi - 1; j >= lo; --j) {
+                    const unsigned long long m = sh.hist[j];
+                    if (m > 0ull && acc + m >= target) { pick = j; break; }
+                    acc += m;
+                }
+                sh.sel_digit = pick;
+                sh.sel_above = acc;
+                sh.sel_incl = acc + sh.hist[pick];
+            }
+            __syncthreads();
+            const int dg = sh.sel_digit;
+            if (dg < 0) empty = true;
+            else {
+                prefix |= static_cast<uint32_t>(dg) << shift;
+                above = sh.sel_above;
+            }
+            __syncthreads();                              // sel_* and hist are rewritten by the next level
+        }
+        // 16-bit logits: the low 8 key bits were never examined because they are constant -- zeros for x >= 0, ones for
+        // x < 0 (the key of a negative float is its complement) -- so the threshold is the logit value itself
+        if (levels == 2 && !(prefix & 0x80000000u)) prefix |= 0xffu;
+        r.thr = empty ? -INFINITY : key_floor_value(prefix);
+        // The nucleus normaliser needs no pass of its own: the last level's scan has summed the masses of exactly the tokens
+        // >= thr (2^-40 fixed point relative to L, an integer sum: reproducible, |error| < candidates * 2^-40).
+        if (!empty) r.L64 = static_cast<double>(L) + log2_split(static_cast<float>(sh.sel_incl)) - 40.0;
+        stamp(8);
+    }
+    return r;
+}
+
 // ---- cross-workgroup mailboxes of the group kernels (k_draft_group, k_residual_group): single writer, single reader,
 // self-tagging words (non-zero = published), handed back empty by the reader
 constexpr int kDgMaxGroups = 32;          // workgroups per row

@@ -127,6 +127,17 @@ class HipOps:
                              lambda: self.K.verify_accept(logits, tok, lp_d, u, ws, inv_temperature=inv_temperature))
         return r.lp_target, r.accept, r.n_acc, r.accept_bits
 
+    @traced("verify_accept_top_p")
+    def verify_accept_top_p(self, logits, tok, lp_d, u, inv_temperature: float = 1.0, top_p: float = 1.0):
+        """Verify against the TARGET's nucleus (asd_verify_accept_top_p) -> (lp_t, accept, n_acc, bits, x* [B,K], n_finite [B]);
+        top_p outside (0, 1) is asd_verify_accept_ex (the same bits)."""
+        B, K = tok.shape
+        ws = None if 0.0 < top_p < 1.0 else self._workspace(B, K, logits.shape[-1], logits.dtype, logits.device)
+        nbytes = B * K * logits.shape[-1] * logits.element_size() + 21 * B * K + 16 * B
+        r = self._timed_step("asd_verify_accept_top_p", nbytes, lambda: self.K.verify_accept_top_p(
+            logits, tok, lp_d, u, ws, inv_temperature=inv_temperature, top_p=top_p))
+        return r.lp_target, r.accept, r.n_acc, r.accept_bits, r.t_nucleus_logit, r.n_finite
+
     @traced("verify_stop")
     def verify_stop(self, logits, tok, lp_d, u, inv_temperature, pred, feat, p_hist, stage_idx, costs, lam,
                     risk_adjustment=True, n_obs=100, alpha=1.0, beta=1.0, stats_col=5):
@@ -205,11 +216,11 @@ class HipOps:
 
     @traced("predictor_stop")
     def predictor_stop(self, pred, lp, feat, p_hist, stage_idx, costs, lam, risk_adjustment=True, n_obs=100, alpha=1.0,
-                       beta=1.0, stats_col=5):
+                       beta=1.0, stats_col=5, n_valid=None):
         """asd_predictor_stop on [n] sequences: p_hist [n,L] f64 is updated in place (column stage_idx) and returned
-        with (score f32 [n], k_star i32 [n])."""
+        with (score f32 [n], k_star i32 [n]).  n_valid [n] i32: leading lp entries the statistics use (None: all K)."""
         packed, in_dim, hidden = pred
-        r = self.K.predictor_stop(feat, packed, in_dim, hidden, stage_idx=stage_idx, L=p_hist.shape[1], lp=lp,
+        r = self.K.predictor_stop(feat, packed, in_dim, hidden, stage_idx=stage_idx, L=p_hist.shape[1], lp=lp, n_valid=n_valid,
                                   stats_col=stats_col, risk_adjustment=risk_adjustment, n_obs=n_obs, alpha=alpha, beta=beta,
                                   p_hist=p_hist, Cc=costs, lam=lam)
         return r.score, r.k_star, p_hist
@@ -229,9 +240,14 @@ class HipOps:
         return d.tok, d.lp, d.thr
 
     @traced("residual_sample")
-    def residual_sample(self, t_logits, d_logits, n_acc, r, bonus, inv_temperature: float = 1.0, d_threshold=None):
-        """t_logits / d_logits [n,K,V], bonus [n,V], n_acc i32 [n], r f32 [n] -> committed token i32 [n]."""
+    def residual_sample(self, t_logits, d_logits, n_acc, r, bonus, inv_temperature: float = 1.0, d_threshold=None,
+                        t_threshold=None, top_p: float = 1.0):
+        """t_logits / d_logits [n,K,V], bonus [n,V], n_acc i32 [n], r f32 [n] -> committed token i32 [n].
+        0 < top_p < 1: against the TARGET's nucleus (asd_residual_sample_top_p; t_threshold [n,K] = the verify's x*)."""
         s = self._sampler("residual", t_logits.shape[0], t_logits.shape[2], t_logits.dtype, t_logits.device)
+        if 0.0 < top_p < 1.0:
+            return s.top_p(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_p=top_p, t_threshold=t_threshold,
+                           d_threshold=d_threshold)
         return s(t_logits, d_logits, n_acc, r, bonus, inv_temperature, d_threshold=d_threshold)
 
     @traced("commit_step")

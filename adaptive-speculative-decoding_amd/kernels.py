@@ -164,6 +164,40 @@ def verify_accept(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tenso
     return out
 
 
+@dataclass
+class NucleusVerifyResult(VerifyResult):
+    t_nucleus_logit: torch.Tensor = None   # [B,K] f32  x* of each target row (raw score units; -inf: no truncation)
+    n_finite: torch.Tensor = None          # [B]   i32  leading positions with a finite lp_target (the stop rule's n_valid)
+
+
+def verify_accept_top_p(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
+                        workspace: Optional[VerifyWorkspace], *, inv_temperature: float = 1.0, top_p: float = 1.0,
+                        out: Optional[NucleusVerifyResult] = None) -> NucleusVerifyResult:
+    """The verify step against the TARGET's nucleus (include/asd_hip.h: asd_verify_accept_top_p): lp_target = log p^N(tok)
+    under softmax(logits / T) restricted to the top-p set of asd_draft_sample's select, -inf outside it.  top_p outside (0, 1)
+    is asd_verify_accept_ex (the same bits; needs `workspace`); otherwise no workspace is used."""
+    Bv, K = tok.shape
+    V, ld, ptr = _logits_2d(logits, Bv, K)
+    dev = logits.device
+    if out is None:
+        out = NucleusVerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
+                                  torch.empty((Bv, K), dtype=torch.uint8, device=dev),
+                                  torch.empty((Bv,), dtype=torch.int32, device=dev),
+                                  torch.empty((Bv,), dtype=torch.int64, device=dev),
+                                  torch.empty((Bv, K), dtype=torch.float32, device=dev),
+                                  torch.empty((Bv,), dtype=torch.int32, device=dev))
+    ws_ptr, ws_bytes = (None, 0) if workspace is None else (workspace.buf.data_ptr(), workspace.bytes)
+    rc = _lib().asd_verify_accept_top_p(
+        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
+        _dev(u, "u", torch.float32), Bv, K, V, float(inv_temperature), float(top_p),
+        _dev(out.lp_target, "lp_target", torch.float32), _dev(out.accept, "accept", torch.uint8),
+        _dev(out.n_acc, "n_acc", torch.int32), _dev(out.accept_bits, "accept_bits", torch.int64),
+        _dev(out.t_nucleus_logit, "t_nucleus_logit", torch.float32), _dev(out.n_finite, "n_finite", torch.int32),
+        ws_ptr, ws_bytes, _stream())
+    B.check("asd_verify_accept_top_p", rc)
+    return out
+
+
 def verify_accept_stats(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
                         workspace: VerifyWorkspace, out: Optional[VerifyResult] = None, *, inv_temperature: float = 1.0,
                         want_entropy: bool = True) -> Tuple[VerifyResult, torch.Tensor, Optional[torch.Tensor]]:
@@ -572,7 +606,8 @@ class ResidualSampler(_StatusWorkspace):
     def __init__(self, B_: int, V: int, dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None):
         self.B, self.V, self.dtype = B_, V, dtype
         # scratch of the multi-launch form + the mailboxes of the group form (B <= 64): zeroed ONCE, handed back empty by every call
-        self.bytes = int(_lib().asd_residual_sample_workspace_bytes(B_, V, _DTYPE_CODE[dtype]))
+        # (+ the bonus rows' nucleus thresholds of asd_residual_sample_top_p, behind the part asd_residual_sample_ex uses)
+        self.bytes = int(_lib().asd_residual_sample_top_p_workspace_bytes(B_, V, _DTYPE_CODE[dtype]))
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device or torch.device("cuda"))
         self.reset()
 
@@ -597,6 +632,31 @@ class ResidualSampler(_StatusWorkspace):
                                            float(inv_temperature), _opt(d_threshold, "d_threshold", torch.float32),
                                            out.data_ptr(), self.buf.data_ptr(), self.bytes, _stream())
         B.check("asd_residual_sample_ex", rc)
+        return out
+
+    def top_p(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
+              bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0, *, top_p: float,
+              t_threshold: Optional[torch.Tensor], d_threshold: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The committed token against the TARGET's nucleus (asd_residual_sample_top_p): t_threshold [B,K] = the verify's
+        t_nucleus_logit; the bonus rows' thresholds are found by the sampler.  top_p outside (0, 1) = __call__ (same bits)."""
+        Bv, K, V = t_logits.shape
+        if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
+            raise ValueError("t_logits and d_logits must have the same shape and dtype")
+        tp, ldt = _rows(t_logits, "t_logits")
+        dp, ldd = _rows(d_logits, "d_logits")
+        bp, ldb = (None, V) if bonus_logits is None else _rows(bonus_logits, "bonus_logits")
+        if out is None:
+            out = torch.empty((Bv,), dtype=torch.int32, device=t_logits.device)
+        for name, t in (("t_threshold", t_threshold), ("d_threshold", d_threshold)):
+            if t is not None and tuple(t.shape) != (Bv, K):
+                raise ValueError(f"{name} must be [B, K]")
+        rc = _lib().asd_residual_sample_top_p(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype],
+                                              _dev(n_acc, "n_acc", torch.int32), _dev(r, "r", torch.float32), Bv, K, V,
+                                              float(inv_temperature), float(top_p), _opt(t_threshold, "t_threshold", torch.float32),
+                                              _opt(d_threshold, "d_threshold", torch.float32), out.data_ptr(),
+                                              self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_residual_sample_top_p", rc)
         return out
 
 

@@ -55,6 +55,9 @@ class HierarchyConfig:
     draft_len: int = 8
     temperature: float = 0.7                 # generate_training_data.py:110-119, pipeline.py:94
     top_p: float = 0.9                       # nucleus of the DRAFT tier (>= 1: off)
+    # nucleus of the VERIFYING tiers: verify and commit against the target's p^N, as HF's assisted generation warps the target's
+    # scores too (generate_training_data.py:110-119; asd_verify_accept_top_p).  >= 1: off, the full softmax(x / T)
+    target_top_p: float = 1.0
     stage_costs: Sequence[float] = (1.0, 4.5, 10.0)   # BASELINE.md cost units 7B / 32B / 72B
     lambda_value: float = 1.0
     risk_adjustment: bool = True             # pipeline.py:234-238
@@ -259,6 +262,12 @@ class LogitsHead:
         K = tok.shape[1]
         return self.ops.verify_stop(self._logits[:, :K].contiguous(), tok, lp_d, u, inv_t, **stop)
 
+    def score_top_p(self, hid, tok, lp_d, u, inv_t, top_p):
+        """Against the target's nucleus (asd_verify_accept_top_p) -> (lp_t, accept, n_acc, bits, x* [n,K], n_finite [n])."""
+        self._logits = self.m.lm_head(hid) * self.m.logit_scale
+        K = tok.shape[1]
+        return self.ops.verify_accept_top_p(self._logits[:, :K].contiguous(), tok, lp_d, u, inv_temperature=inv_t, top_p=top_p)
+
     def draw_rows(self, sel: torch.Tensor, j: torch.Tensor) -> torch.Tensor:
         """Target logits row j[i] of local sequence sel[i] -> [m, V]."""
         return self._logits[sel, j].contiguous()
@@ -355,6 +364,15 @@ class VerifyRole:
         self.pred = ops.pack_predictor(predictor, dev)
         self.feat = prompt_features(prompt_ids) if feat is None else feat
         self.head = head if head is not None else LogitsHead(model, ops)
+        self.t_top_p = float(cfg.target_top_p)
+        self.nucleus = 0.0 < self.t_top_p < 1.0             # verify / commit against the target's nucleus
+        if self.nucleus:
+            if isinstance(self.head, ShardedHead):
+                raise ValueError("target_top_p < 1 is not supported on a vocabulary-sharded head (the nucleus select would "
+                                 "have to run across the shards)")
+            if isinstance(self.head, FusedHead):            # the select needs the rows: materialise them as LogitsHead does
+                self.head = LogitsHead(model, ops)
+        self._t_thr: Optional[torch.Tensor] = None          # [n, K] x* of this step's verified rows (nucleus only)
         self.keep_inputs = keep_inputs
         model.reset()
         model.alloc_ragged(B, self.st.kv_slots)
@@ -413,7 +431,13 @@ class VerifyRole:
         stop_args = dict(pred=self.pred, feat=self.feat[idx].contiguous(), p_hist=ph, stage_idx=self.s, costs=self.costs,
                          lam=cfg.lambda_value, risk_adjustment=cfg.risk_adjustment, n_obs=cfg.n_obs, alpha=cfg.risk_alpha,
                          beta=cfg.risk_beta, stats_col=cfg.stats_col)
-        if hasattr(self.head, "score_and_stop"):            # materialised logits: verify + stop rule in ONE launch
+        n_fin = None
+        if self.nucleus:                                    # the target's nucleus: verify, then the stop rule on the finite lp_t
+            lp_t, accept, n_acc, bits, self._t_thr, n_fin = self.head.score_top_p(hid, tok_i, lp_d, u, self.inv_t, self.t_top_p)
+            score, k_star, ph = self.ops.predictor_stop(self.pred, lp_t.contiguous(), stop_args["feat"], ph, self.s,
+                                                        self.costs, cfg.lambda_value, cfg.risk_adjustment, cfg.n_obs,
+                                                        cfg.risk_alpha, cfg.risk_beta, cfg.stats_col, n_valid=n_fin)
+        elif hasattr(self.head, "score_and_stop"):          # materialised logits: verify + stop rule in ONE launch
             (lp_t, accept, n_acc, bits), (score, k_star, ph) = self.head.score_and_stop(hid, tok_i, lp_d, u, self.inv_t, **stop_args)
         else:                                               # hidden-state heads (fused GEMM, vocabulary shards): two launches
             lp_t, accept, n_acc, bits = self.head.score(hid, tok_i, lp_d, u, self.inv_t)
@@ -430,6 +454,10 @@ class VerifyRole:
                             hidden=hid[:, :K].clone(), feat=self.feat[idx].clone())
             if isinstance(self.head, LogitsHead):
                 v.inputs["logits"] = self.head._logits[:, :K].clone()
+            if self.nucleus:
+                v.inputs["t_nucleus_logit"] = self._t_thr.clone()
+                v.inputs["n_finite"] = n_fin.clone()
+                v.inputs["bonus_logits"] = self.head._logits[:, K].clone()
         out_esc.escalate[idx] = (~stop).to(torch.uint8)
         out_esc.p_prev[idx] = ph[:, :self.s + 1]
         self._fed = idx
@@ -459,9 +487,12 @@ class VerifyRole:
         b_sel = idx[sel]
         j = n_acc.to(torch.int64)[sel]
         t_rows = self.head.draw_rows(sel, j)                # [m, V]: row n_acc (the bonus row when n_acc == K)
+        # the target nucleus of row n_acc (rows < K: the verify's x*; the bonus row's is found by the sampler)
+        t_thr = self._t_thr[sel, j.clamp(max=K - 1)] if self.nucleus else None
         if only is not None:
             mine = (b_sel >= only[0]) & (b_sel < only[1])
             b_sel, j, t_rows = b_sel[mine], j[mine], t_rows[mine].contiguous()
+            t_thr = None if t_thr is None else t_thr[mine]
             m = b_sel.numel()
             if m == 0:
                 return drawn
@@ -476,8 +507,13 @@ class VerifyRole:
             d_full[where] = d_rows
             thr[where] = d_thr
         all_acc = (j >= K).to(torch.int32)                  # K = 1 view: 0 -> residual of the two rows, 1 -> bonus draw
-        tokd = self.ops.residual_sample(t_rows[:, None, :], d_full[:, None, :], all_acc.contiguous(), self._r[b_sel].contiguous(),
-                                        t_rows, self.inv_t, d_threshold=thr[:, None].contiguous())
+        if self.nucleus:
+            tokd = self.ops.residual_sample(t_rows[:, None, :], d_full[:, None, :], all_acc.contiguous(), self._r[b_sel].contiguous(),
+                                            t_rows, self.inv_t, d_threshold=thr[:, None].contiguous(),
+                                            t_threshold=t_thr[:, None].contiguous(), top_p=self.t_top_p)
+        else:
+            tokd = self.ops.residual_sample(t_rows[:, None, :], d_full[:, None, :], all_acc.contiguous(), self._r[b_sel].contiguous(),
+                                            t_rows, self.inv_t, d_threshold=thr[:, None].contiguous())
         drawn[b_sel] = tokd.to(torch.int32)
         return drawn
 
@@ -1014,6 +1050,9 @@ class ShardedTargetRole:
 
     def __init__(self, model, cfg: HierarchyConfig, ops, prompt_local: torch.Tensor, max_new_tokens: int, predictor,
                  head: "ShardedHead", b0: int, batch_total: int, group=None, feat_local: Optional[torch.Tensor] = None):
+        if 0.0 < cfg.target_top_p < 1.0:
+            raise ValueError("target_top_p < 1 is not supported by the vocabulary-sharded target (the nucleus select would "
+                             "have to run across the shards)")
         self.m, self.s, self.cfg, self.ops, self.head, self.group = model, 1, cfg, ops, head, group
         self.b0, self.Bt = int(b0), int(batch_total)
         self.st = _SeqState(prompt_local, max_new_tokens, cfg.draft_len)

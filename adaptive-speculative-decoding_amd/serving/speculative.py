@@ -63,6 +63,7 @@ class SpeculativeVerifier:
         self.sampler = K.ResidualSampler(batch, vocab, logits_dtype, self.device)   # commit step (asd_residual_sample_ex)
         self.draft_sampler = K.DraftSampler(batch, vocab, logits_dtype, self.device)  # proposal step (asd_draft_sample)
         self.top_p = 1.0                  # nucleus of the draft tier (reference: 0.9, generate_training_data.py:110-119)
+        self.target_top_p = 1.0           # nucleus of the TARGET: verify and commit against p^N (asd_verify_accept_top_p); >= 1: off
         self.in_dim = self.hidden = 0
         self.packed = None
         self._lm_head = None              # (key, kernels.LmHeadVerifier) of the last verify_hidden call
@@ -79,8 +80,25 @@ class SpeculativeVerifier:
 
     def verify(self, logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
                out: Optional[K.VerifyResult] = None) -> K.VerifyResult:
-        """`logits` are RAW target logits: 1/temperature is applied inside the kernel (self.inv_temperature)."""
+        """`logits` are RAW target logits: 1/temperature is applied inside the kernel (self.inv_temperature).  With a target
+        nucleus (0 < target_top_p < 1) the result is a kernels.NucleusVerifyResult (lp_t = log p^N(tok), x*, n_finite)."""
+        if self._target_nucleus():
+            return K.verify_accept_top_p(logits, tok, lp_draft, u, None, inv_temperature=self.inv_temperature,
+                                         top_p=self.target_top_p)
         return K.verify_accept(logits, tok, lp_draft, u, self.ws, out, inv_temperature=self.inv_temperature)
+
+    def _target_nucleus(self) -> bool:
+        return 0.0 < self.target_top_p < 1.0
+
+    def draw(self, t_logits: torch.Tensor, d_logits: torch.Tensor, v: K.VerifyResult, r: torch.Tensor,
+             bonus_logits: Optional[torch.Tensor], d_threshold: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The token each sequence commits after its accepted prefix: asd_residual_sample_ex, or -- with a target nucleus --
+        asd_residual_sample_top_p against the verify's thresholds (the bonus rows' are found by the sampler)."""
+        if self._target_nucleus():
+            return self.sampler.top_p(t_logits, d_logits, v.n_acc, r, bonus_logits, self.inv_temperature, top_p=self.target_top_p,
+                                      t_threshold=v.t_nucleus_logit, d_threshold=d_threshold)
+        return self.sampler(t_logits, d_logits, v.n_acc, r, bonus_logits=bonus_logits, inv_temperature=self.inv_temperature,
+                            d_threshold=d_threshold)
 
     def verify_hidden(self, hidden: torch.Tensor, lm_head_weight: torch.Tensor, tok: torch.Tensor,
                       lp_draft: torch.Tensor, u: torch.Tensor, out: Optional[K.VerifyResult] = None,
@@ -88,6 +106,9 @@ class SpeculativeVerifier:
         """N2: verify from the target's final hidden states [B, K, D] and its lm_head matrix [V, D] (bf16);
         the [B, K, V] logits stay in MFMA accumulators (asd_lm_head_verify).  `logit_scale` multiplies the
         logits like SyntheticLM.logit_scale; it rides on the temperature constant."""
+        if self._target_nucleus():
+            raise ValueError("target_top_p < 1 needs materialised logits (verify / step): the nucleus select does not run "
+                             "inside the fused lm_head kernel")
         key = (lm_head_weight.data_ptr(), tok.shape[0], tok.shape[1])
         if self._lm_head is None or self._lm_head[0] != key:
             self._lm_head = (key, K.LmHeadVerifier(lm_head_weight, tok.shape[0], tok.shape[1]))
@@ -103,15 +124,17 @@ class SpeculativeVerifier:
     def _stop(self, v: K.VerifyResult, tok: torch.Tensor, feat: Optional[torch.Tensor], stage_idx: int):
         if self.packed is None or feat is None:
             return None
+        # a target nucleus: the statistics see the leading finite log-probs only (never an out-of-nucleus -inf)
+        n_valid = v.n_finite if isinstance(v, K.NucleusVerifyResult) else None
         return K.predictor_stop(feat, self.packed, self.in_dim, self.hidden, stage_idx=stage_idx, L=self.L,
-                                lp=v.lp_target, stats_col=self.stats_col, risk_adjustment=self.risk, n_obs=self.n_obs,
+                                lp=v.lp_target, n_valid=n_valid, stats_col=self.stats_col, risk_adjustment=self.risk, n_obs=self.n_obs,
                                 alpha=self.alpha, beta=self.beta, p_hist=self.p_hist[: tok.shape[0]], Cc=self.costs,
                                 lam=self.lam, prefix_rule=self.prefix)
 
     def step(self, logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
              feat: Optional[torch.Tensor] = None, stage_idx: int = 0, out: Optional[K.VerifyResult] = None) -> StepResult:
         """One verify + stop decision for the whole batch: ONE launch (two with fused=False), nothing synchronises."""
-        if self.fused and self.packed is not None and feat is not None:
+        if self.fused and self.packed is not None and feat is not None and not self._target_nucleus():
             v, s = K.verify_accept_fused(logits, tok, lp_draft, u, self.ws, feat, self.packed, self.in_dim, self.hidden,
                                          stage_idx=stage_idx, L=self.L, stats_col=self.stats_col,
                                          risk_adjustment=self.risk, n_obs=self.n_obs, alpha=self.alpha, beta=self.beta,
@@ -184,9 +207,8 @@ def speculative_generate(draft, target, prompt_ids: torch.Tensor, max_new_tokens
         # the token every sequence emits after ITS accepted prefix: residual draw at the first rejection,
         # bonus draw from the target's next-token logits when all K passed -- one call, raw logits in
         r = torch.rand((B,), generator=gen, device=dev)
-        drawn = verifier.sampler(score, torch.stack(dls, 1).to(score.dtype).contiguous(), res.verify.n_acc, r,
-                                 bonus_logits=t_new[:, -1].contiguous(), inv_temperature=verifier.inv_temperature,
-                                 d_threshold=d_thr)
+        drawn = verifier.draw(score, torch.stack(dls, 1).to(score.dtype).contiguous(), res.verify, r,
+                              t_new[:, -1].contiguous(), d_threshold=d_thr)
         drawn = drawn.to(torch.int64)
         if m - 1 == Kd:                             # every sequence accepted all K: K drafts + the bonus token
             commit = torch.cat([tok, drawn[:, None]], 1)
@@ -313,9 +335,8 @@ def speculative_generate_ragged(draft, target, prompt_ids: torch.Tensor, max_new
         tok32 = tok.to(torch.int32).contiguous()
         res = verifier.step(score, tok32, lp_d, u, feat)
         r = torch.rand((B,), generator=gen, device=dev)
-        drawn = verifier.sampler(score, torch.stack(dls, 1).to(score.dtype).contiguous(), res.verify.n_acc, r,
-                                 bonus_logits=t_out[:, Kd].contiguous(), inv_temperature=verifier.inv_temperature,
-                                 d_threshold=torch.stack(thrs, 1).contiguous())
+        drawn = verifier.draw(score, torch.stack(dls, 1).to(score.dtype).contiguous(), res.verify, r,
+                              t_out[:, Kd].contiguous(), d_threshold=torch.stack(thrs, 1).contiguous())
         K.commit_step(tok32, res.verify.n_acc, drawn, seq_len, tokens, n_commit, max_len=cap)
         verified += n_commit.sum()
         masks.append(res.verify.accept.clone())

@@ -448,6 +448,48 @@ int asd_draft_sample(const void* logits, int64_t ld, int dtype, const float* r /
                      float inv_temperature, float top_p, int32_t* tok /*[B] out*/, float* lp /*[B] out, may be NULL*/,
                      float* nucleus_logit /*[B] out, may be NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Target-side top-p: verify and commit against the TARGET's nucleus.  The reference samples every model -- the target
+ * included -- with HF generate(do_sample=True, temperature=0.7, top_p=0.9) (src/training/generate_training_data.py:110-119,
+ * src/serving/real_model_pipeline.py:60,326,378, the per-request top_p of src/serving/server.py:45), and HF's assisted
+ * generation applies the same warpers to the target's scores before its speculative test.  For a target row x = logits[b,k]:
+ *   N      = { v : x_v >= x* },  x* = asd_draft_sample's nucleus_logit of that row for the same T and top_p (the same select
+ *            code: bit-identical), HF's TopPLogitsWarper set with every tie at the boundary kept
+ *   p^N    = softmax(x / T) restricted to N, renormalised
+ *   lp_t[b,k]            = log p^N(tok[b,k])  (-inf when x_tok < x* or tok outside [0,V); bit-identical to asd_draft_sample's
+ *                          lp for the token it drew)
+ *   accept / n_acc / accept_bits: the rules of asd_verify_accept (log u <= lp_t - lp_d, the leading run)
+ *   t_nucleus_logit[b,k] = x* (f32, raw score units; -inf without truncation; may be NULL)
+ *   n_finite[b]          = number of leading positions whose lp_t is finite: the n_valid of asd_predictor_stop, so that a
+ *                          token outside the nucleus never reaches the statistics as -inf (may be NULL)
+ * The features the reference's predictor reads are log-probs of the WARPED scores (generate_training_data.py:128-136).
+ * top_p outside (0,1): asd_verify_accept_ex with inv_temperature (the same bits; workspace as for it), x* = -inf.
+ * Otherwise: logits 16-byte aligned, a whole number of 16-byte vectors per row, V*sizeof(elem) <= 2 MiB; no workspace (may be
+ * NULL); two stream-ordered launches (one 1024-lane workgroup per row, then one wave per sequence), nothing crosses workgroups.
+ * ---------------------------------------------------------------------------------------- */
+int asd_verify_accept_top_p(const void* logits, int dtype, int64_t ld_row,
+                            const int32_t* tok /*[B,K]*/, const float* lp_draft /*[B,K]*/, const float* u /*[B,K]*/,
+                            int B, int K, int V, float inv_temperature, float top_p,
+                            float* lp_target /*[B,K] out*/, uint8_t* accept /*[B,K] out*/, int32_t* n_acc /*[B] out*/,
+                            uint64_t* accept_bits /*[B] out, may be NULL*/, float* t_nucleus_logit /*[B,K] out, may be NULL*/,
+                            int32_t* n_finite /*[B] out, may be NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The committed token against the target's nucleus (asd_residual_sample_ex with p_t replaced by p^N):
+ *   j <  K : w = max(0, p_t^N - p_d^N), N of row (b,j) given by t_threshold[b,j] (asd_verify_accept_top_p's t_nucleus_logit),
+ *            p_d^N by d_threshold as in asd_residual_sample_ex; an empty residual falls back to p_t^N
+ *   j >= K : w = p^N of bonus_logits[b]; its x* is computed here by asd_draft_sample's select (the same bits as its
+ *            nucleus_logit on that row)
+ * The draw is the inverse CDF in vocabulary order of asd_residual_sample.  top_p outside (0,1): asd_residual_sample_ex (the
+ * same bits; t_threshold is ignored).  workspace: asd_residual_sample_top_p_workspace_bytes(B,V,dtype) bytes (the residual
+ * workspace + the bonus rows' thresholds), initialised as for asd_residual_sample. */
+size_t asd_residual_sample_top_p_workspace_bytes(int B, int V, int dtype);
+int asd_residual_sample_top_p(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                              const void* bonus_logits, int64_t ld_b, int dtype,
+                              const int32_t* n_acc /*[B]*/, const float* r /*[B]*/, int B, int K, int V,
+                              float inv_temperature, float top_p, const float* t_threshold /*[B,K]*/,
+                              const float* d_threshold /*[B,K] or NULL*/, int32_t* token /*[B] out*/,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* N1, second form: asd_verify_accept with the epilogue of asd_predictor_stop run INSIDE the same
  * launch by the wave that completes each sequence (lp = the kernel's own lp_target, all K
  * positions valid).  ONE launch per tier step instead of two, at every batch size: with one workgroup
