@@ -45,6 +45,7 @@ struct DrParams {
     int B, V, nvec, n_tiles;
     float c2, top_p;
     int levels;              // 0: no truncation; 2: 16-bit logits; 3: f32 logits
+    int top_k;               // k_draft_row<DT, true> only: the top-k bound (1 <= top_k < V)
     int32_t* tok; float* lp; float* thr;
 };
 
@@ -144,7 +145,7 @@ __device__ __forceinline__ void draft_pick_wave(const u32x4* row, int nvec, cons
     }
 }
 
-template <int DT>
+template <int DT, bool kTopK = false>
 __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
     using E = Elem<DT>;
     constexpr int N = E::kPerVec;
@@ -162,8 +163,9 @@ __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
         return __ballot(any) != 0ull;
     };
     const bool tiles_from_sweep1 = p.levels == 0;
-    const NucleusSel sel = nucleus_row_select<DT>(row, p.V, p.nvec, p.n_tiles, p.c2, p.top_p, p.levels, sh, t,
-                                                  [&](int slot) { ASD_DR_STAMP(slot); });
+    // (kTopK: phase 0, the count select of x_k, then phases 1-3 on the top-k set; the tile pairs of phase 1 are K's)
+    const NucleusSel sel = nucleus_row_select<DT, kTopK>(row, p.V, p.nvec, p.n_tiles, p.c2, p.top_p, p.levels, sh, t,
+                                                         [&](int slot) { ASD_DR_STAMP(slot); }, p.top_k);
     const double L64 = sel.L64;
     const float thr = sel.thr;
     const bool listed = sel.listed;
@@ -684,6 +686,44 @@ ASD_EXPORT int asd_draft_sample(const void* logits, int64_t ld, int dtype, const
         case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_draft_row<ASD_DTYPE_BF16>, grid, block, 0, st, p); break;
         case ASD_DTYPE_F16: hipLaunchKernelGGL(k_draft_row<ASD_DTYPE_F16>, grid, block, 0, st, p); break;
         default: hipLaunchKernelGGL(k_draft_row<ASD_DTYPE_F32>, grid, block, 0, st, p); break;
+    }
+    return launch_status();
+}
+
+// Top-k before top-p (HF's TopKLogitsWarper -> TopPLogitsWarper): ONE launch of k_draft_row<DT, true>, one 1024-lane workgroup per
+// row at every batch size.  The group form (k_draft_group) would have to exchange the count histograms of the select through its
+// mailboxes as it does the mass histograms; until it does, top-k rows are not spread over workgroups (the workspace is accepted
+// and left untouched), and the outputs depend on the row alone.
+ASD_EXPORT int asd_draft_sample_top_k(const void* logits, int64_t ld, int dtype, const float* r, int B, int V,
+                                      float inv_temperature, int top_k, float top_p, int32_t* tok, float* lp, float* threshold,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (top_k <= 0 || top_k >= V)                       // no top-k bound: asd_draft_sample itself (the same bits)
+        return asd_draft_sample(logits, ld, dtype, r, B, V, inv_temperature, top_p, tok, lp, threshold, workspace,
+                                workspace_bytes, stream);
+    if (B < 0) return ASD_ERR_INVALID_ARG;
+    if (B == 0) return ASD_OK;
+    const int esz = dtype_size(dtype);
+    if (esz == 0) return ASD_ERR_UNSUPPORTED;
+    if (!logits || !r || !tok || ld < V) return ASD_ERR_INVALID_ARG;
+    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f) || top_p != top_p) return ASD_ERR_INVALID_ARG;
+    if ((static_cast<int64_t>(V) * esz) % 16 || !aligned_to(logits, 16) || (ld * esz) % 16) return ASD_ERR_ALIGNMENT;
+    DrParams p{};
+    p.logits = logits; p.ld = ld; p.r = r; p.B = B; p.V = V;
+    p.nvec = static_cast<int>(static_cast<int64_t>(V) * esz / 16);
+    p.n_tiles = (p.nvec + 63) / 64;
+    if (p.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
+    p.c2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature));
+    p.top_p = top_p;
+    const bool nucleus = top_p > 0.0f && top_p < 1.0f;
+    p.levels = nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
+    p.top_k = top_k;
+    p.tok = tok; p.lp = lp; p.thr = threshold;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
+    switch (dtype) {
+        case ASD_DTYPE_BF16: hipLaunchKernelGGL((k_draft_row<ASD_DTYPE_BF16, true>), grid, block, 0, st, p); break;
+        case ASD_DTYPE_F16: hipLaunchKernelGGL((k_draft_row<ASD_DTYPE_F16, true>), grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL((k_draft_row<ASD_DTYPE_F32, true>), grid, block, 0, st, p); break;
     }
     return launch_status();
 }

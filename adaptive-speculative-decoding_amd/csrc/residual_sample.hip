@@ -480,15 +480,16 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
 // per sequence.  The bonus row has no verify output, so its x* is found here -- by the select of asd_draft_sample itself
 // (sample_device.hpp, nucleus_row_select): the same bits as asd_draft_sample's nucleus_logit on that row.  Sequences that
 // draw from a residual (or have no bonus row) leave at once.
-template <int DT>
-__global__ __launch_bounds__(kDrThreads) void k_rs_bonus_threshold(const RsParams p, float top_p, int levels, float* b_thr) {
+// kTopK (asd_residual_sample_top_k): the top-k + top-p threshold max(x_k, x*_K) of asd_draft_sample_top_k's select instead.
+template <int DT, bool kTopK = false>
+__global__ __launch_bounds__(kDrThreads) void k_rs_bonus_threshold(const RsParams p, float top_p, int levels, float* b_thr, int top_k) {
     using E = Elem<DT>;
     __shared__ NucleusLds sh;
     const int b = blockIdx.x, t = threadIdx.x;
     const int j = p.n_acc[b];
     if ((j >= 0 && j < p.K) || !p.bonus) return;                        // block-uniform
     const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.bonus) + static_cast<int64_t>(b) * p.ld_b * E::kBytes);
-    const NucleusSel sel = nucleus_row_select<DT>(row, p.V, p.nvec, p.n_tiles, p.c2, top_p, levels, sh, t, [](int) {});
+    const NucleusSel sel = nucleus_row_select<DT, kTopK>(row, p.V, p.nvec, p.n_tiles, p.c2, top_p, levels, sh, t, [](int) {}, top_k);
     if (t == 0) b_thr[b] = sel.thr;
 }
 
@@ -556,7 +557,8 @@ namespace {
 int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d, const void* bonus_logits,
                     int64_t ld_b, int dtype, const int32_t* n_acc, const float* r, int B, int K, int V,
                     float inv_temperature, const float* d_threshold, int32_t* token, void* workspace,
-                    size_t workspace_bytes, void* stream, const float* t_threshold = nullptr, float top_p = 1.0f) {
+                    size_t workspace_bytes, void* stream, const float* t_threshold = nullptr, float top_p = 1.0f,
+                    int top_k = 0) {
     if (B < 0 || K < 0 || V < 1) return ASD_ERR_INVALID_ARG;
     if (B == 0) return ASD_OK;
     const int esz = dtype_size(dtype);
@@ -584,20 +586,30 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     p.token = token;
     p.d_thr = d_threshold;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (top_p > 0.0f && top_p < 1.0f) {
+    const bool nucleus = top_p > 0.0f && top_p < 1.0f, topk = top_k > 0 && top_k < V;
+    if (nucleus || topk) {
         // the target's nucleus: x* of the rejected rows from the verify (t_threshold), of the bonus rows found here first.
-        // Their [B] thresholds live behind the part of the workspace asd_residual_sample_workspace_bytes sizes.
+        // Their [B] thresholds live behind the part of the workspace asd_residual_sample_workspace_bytes sizes.  (With top-k
+        // the thresholds are the combined max(x_k, x*_K) of asd_verify_accept_top_k / asd_draft_sample_top_k.)
         if (p.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
         const size_t base = asd_residual_sample_workspace_bytes(B, V, dtype);
         float* b_thr = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);
         p.t_thr = t_threshold;
         p.b_thr = b_thr;
-        const int levels = dtype == ASD_DTYPE_F32 ? 3 : 2;
+        const int levels = nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
         const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
-        switch (dtype) {
-            case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_BF16>, grid, block, 0, st, p, top_p, levels, b_thr); break;
-            case ASD_DTYPE_F16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F16>, grid, block, 0, st, p, top_p, levels, b_thr); break;
-            default: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F32>, grid, block, 0, st, p, top_p, levels, b_thr); break;
+        if (topk) {
+            switch (dtype) {
+                case ASD_DTYPE_BF16: hipLaunchKernelGGL((k_rs_bonus_threshold<ASD_DTYPE_BF16, true>), grid, block, 0, st, p, top_p, levels, b_thr, top_k); break;
+                case ASD_DTYPE_F16: hipLaunchKernelGGL((k_rs_bonus_threshold<ASD_DTYPE_F16, true>), grid, block, 0, st, p, top_p, levels, b_thr, top_k); break;
+                default: hipLaunchKernelGGL((k_rs_bonus_threshold<ASD_DTYPE_F32, true>), grid, block, 0, st, p, top_p, levels, b_thr, top_k); break;
+            }
+        } else {
+            switch (dtype) {
+                case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_BF16>, grid, block, 0, st, p, top_p, levels, b_thr, 0); break;
+                case ASD_DTYPE_F16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F16>, grid, block, 0, st, p, top_p, levels, b_thr, 0); break;
+                default: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F32>, grid, block, 0, st, p, top_p, levels, b_thr, 0); break;
+            }
         }
         if (launch_status() != ASD_OK) return ASD_ERR_HIP;
         workspace_bytes = base;                        // the geometry choice below sees the workspace asd_residual_sample_ex would
@@ -694,4 +706,19 @@ ASD_EXPORT int asd_residual_sample_top_p(const void* t_logits, int64_t ld_t, con
     if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
                            d_threshold, token, workspace, workspace_bytes, stream, t_threshold, top_p);
+}
+
+ASD_EXPORT int asd_residual_sample_top_k(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                                         const void* bonus_logits, int64_t ld_b, int dtype, const int32_t* n_acc,
+                                         const float* r, int B, int K, int V, float inv_temperature, int top_k, float top_p,
+                                         const float* t_threshold, const float* d_threshold, int32_t* token, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    if (top_k <= 0 || top_k >= V)                       // no top-k bound: asd_residual_sample_top_p itself (the same bits)
+        return asd_residual_sample_top_p(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V,
+                                         inv_temperature, top_p, t_threshold, d_threshold, token, workspace, workspace_bytes, stream);
+    if (top_p != top_p) return ASD_ERR_INVALID_ARG;
+    if (B > 0 && K > 0 && !t_threshold) return ASD_ERR_INVALID_ARG;
+    if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
+    return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
+                           d_threshold, token, workspace, workspace_bytes, stream, t_threshold, top_p, top_k);
 }

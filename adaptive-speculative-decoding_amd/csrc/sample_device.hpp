@@ -231,6 +231,81 @@ __device__ __forceinline__ void cand_sweep(const u32x4* row, const uint32_t* can
     }
 }
 
+// ---- top-k: x_k, the k-th largest logit of the row counting multiplicity (HF TopKLogitsWarper keeps { v : x_v >= x_k }, every
+// tie at x_k included), or -inf when fewer than k values are > -inf.  A radix select by COUNT on order_key(x) with the digit
+// schedule of the mass select (12 + 12 bits for 16-bit logits, 12 + 12 + 8 for f32): per level every token of the selected
+// prefix adds 1 to the slot of its digit, the slots are scanned from the top for the digit where above < k <= above + count.
+// Integer counts: the result depends on the row's bytes only, not on the geometry.  The counts live in the first 16 KB of
+// sh.hist (the mass select rewrites it afterwards); sel_digit / sel_above / wave_tot are the mass select's words.  The first
+// level's sweep is the only HBM read of the row; the later levels compare every token against the prefix (L2 hits) and count
+// only the tokens of the selected digit.  All 1024 threads call it.
+template <int DT>
+__device__ __forceinline__ float topk_row_threshold(const u32x4* row, int nvec, int top_k, NucleusLds& sh, int t) {
+    using E = Elem<DT>;
+    constexpr int N = E::kPerVec;
+    constexpr int kLevels = DT == ASD_DTYPE_F32 ? 3 : 2;
+    const int lane = t & 63, wave = t >> 6;
+    uint32_t* const cnt = reinterpret_cast<uint32_t*>(sh.hist);
+    const uint32_t k = static_cast<uint32_t>(top_k);
+    const int shifts[3] = {20, 8, 0}, widths[3] = {12, 12, 8};
+    uint32_t prefix = 0u, above = 0u;
+    bool found = true;
+    for (int lv = 0; lv < kLevels; ++lv) {
+        const int shift = shifts[lv], digits = 1 << widths[lv], hi_shift = shifts[lv] + widths[lv];
+        for (int i = t; i < digits; i += kDrThreads) cnt[i] = 0u;
+        if (t == 0) sh.sel_digit = -1;
+        __syncthreads();
+        row_sweep<DT>(row, nvec, t, [&](int, const u32x4& vec) {
+            float x[N];
+            unpack<DT>(vec, x);
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                if (!(x[i] > -INFINITY)) continue;             // -inf (and the padding of a ragged tile) is never counted
+                const uint32_t key = order_key(x[i]);
+                if (hi_shift >= 32 || (key >> hi_shift) == (prefix >> hi_shift)) atomicAdd(&cnt[(key >> shift) & (digits - 1)], 1u);
+            }
+        });
+        __syncthreads();
+        // thread t owns the t-th chunk of digits counted from the TOP
+        const int per = digits >= kDrThreads ? digits / kDrThreads : 1;
+        const int hi = digits - t * per, lo = hi - per;
+        int mine = 0;
+        if (lo >= 0)
+            for (int j = lo; j < hi; ++j) mine += static_cast<int>(cnt[j]);
+        const int incl = wave_incl_scan_i32(mine);
+        if (lane == 63) sh.wave_tot[wave] = static_cast<unsigned long long>(incl);
+        __syncthreads();
+        uint32_t base = 0u;
+#pragma unroll
+        for (int w = 0; w < kDrWaves; ++w)
+            if (w < wave) base += static_cast<uint32_t>(sh.wave_tot[w]);
+        const uint32_t before = above + base + static_cast<uint32_t>(incl - mine);
+        if (lo >= 0 && mine > 0 && before < k && k <= before + static_cast<uint32_t>(mine)) {   // exactly one thread
+            uint32_t acc = before;
+            int pick = lo;
+            for (int j = hi - 1; j >= lo; --j) {
+                const uint32_t m = cnt[j];
+                if (m > 0u && acc + m >= k) { pick = j; break; }
+                acc += m;
+            }
+            sh.sel_digit = pick;
+            sh.sel_above = acc;
+        }
+        __syncthreads();
+        const int dg = sh.sel_digit;
+        if (dg >= 0) {
+            prefix |= static_cast<uint32_t>(dg) << shift;
+            above = static_cast<uint32_t>(sh.sel_above);
+        }
+        __syncthreads();                                  // sel_* and the counts are rewritten by the next level
+        if (dg < 0) { found = false; break; }             // (block-uniform) fewer than k counted values
+    }
+    if (!found) return -INFINITY;
+    // 16-bit logits: the low 8 key bits are constant (zeros for x >= 0, ones for x < 0), as in the mass select
+    if (kLevels == 2 && !(prefix & 0x80000000u)) prefix |= 0xffu;
+    return key_floor_value(prefix);
+}
+
 struct NucleusSel {
     float thr;        // x*: the nucleus is { v : x_v >= thr } (-inf: no truncation, an empty select or a row without mass)
     double L64;       // log2 of the normaliser of the distribution drawn from / scored against (L_N with truncation)
@@ -244,9 +319,14 @@ struct NucleusSel {
 //   3. radix select on probability MASS over the candidates (2^-40 fixed point, integer adds: reproducible) -> x*, L_N
 // (draft_sample.hip explains each phase.)  Leaves the tile pairs' sums in sh.tile_mass / their maxima in sh.tile_span when
 // levels == 0, the candidate spans in sh.tile_span otherwise.  All 1024 threads call it; `stamp(slot)` marks phase boundaries.
-template <int DT, class Stamp>
+// kTopK (HF's TopKLogitsWarper before its TopPLogitsWarper): phase 0 finds x_k (topk_row_threshold) and every later phase works
+// on the top-k set K = { x >= x_k } only -- the tile pairs are taken with thr = x_k (-> L_K), the candidate floor is
+// max(x_floor, x_k) and the mass target is top_p of K's mass -- so thr = max(x_k, x*_K) and L64 = the normaliser over
+// { x >= thr }; with levels == 0 (top-p off) thr = x_k, L64 = L_K.  kTopK = false is the form without phase 0 (x_lo is the
+// constant -inf, every use of it folds away).
+template <int DT, bool kTopK = false, class Stamp>
 __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V, int nvec, int n_tiles, float c2, float top_p,
-                                                         int levels, NucleusLds& sh, int t, Stamp&& stamp) {
+                                                         int levels, NucleusLds& sh, int t, Stamp&& stamp, int top_k = 0) {
     using E = Elem<DT>;
     constexpr int N = E::kPerVec;
     const int lane = t & 63, wave = t >> 6;
@@ -257,6 +337,8 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
         return __ballot(any) != 0ull;
     };
     float m2, s;
+    float x_lo = -INFINITY;                                   // x_k of a top-k row (kTopK only)
+    if constexpr (kTopK) x_lo = topk_row_threshold<DT>(row, nvec, top_k, sh, t);
     stamp(0);
     // Sweep 1 (the only pass that reads HBM) leaves every tile's CANONICAL (max, sum) pair in LDS and folds the pairs in the
     // fixed order of fold_tile_pairs: L has the same bits as in k_draft_group, whatever the batch (round 2 ran a per-lane
@@ -264,7 +346,8 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
     // Without truncation the tile masses then follow from L without a second exp-per-element sweep of the row.
     row_sweep<DT>(row, nvec, t, [&](int v, const u32x4& vec) {
         float M, sw;
-        tile_pair<DT>(vec, c2, M, sw);
+        if constexpr (kTopK) tile_pair<DT>(vec, c2, M, sw, x_lo);      // the top-k set's pairs -> L_K
+        else tile_pair<DT>(vec, c2, M, sw);
         if (lane == 0) {                                      // nothing is carried from tile to tile: the four tiles of a
             sh.tile_span[v >> 6] = __float_as_uint(M);        // row_sweep step reduce side by side
             sh.tile_mass[v >> 6] = sw;
@@ -282,7 +365,8 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
     if (levels > 0 && s > 0.0f) {
         const float L = static_cast<float>(r.L64);
         const float p_floor = fmaxf((1.0f - top_p) / static_cast<float>(V), 1.0f / kDsFix);
-        const float x_floor = (L + __builtin_amdgcn_logf(p_floor)) / c2;      // p >= p_floor  <=>  x >= x_floor
+        float x_floor = (L + __builtin_amdgcn_logf(p_floor)) / c2;            // p >= p_floor  <=>  x >= x_floor
+        if constexpr (kTopK) x_floor = fmaxf(x_floor, x_lo);                    // only K's tokens are candidates
         // ---- candidates.  Tokens below p_floor = (1 - top_p) / V carry < 1 - top_p together, so the threshold lies above
         // all of them.  One compare-only sweep lists the others (per-lane counts, DPP prefix sum, lane-major inside a tile: a
         // fixed order) in the LDS segment of the wave that owns their tile; the histogram levels, the nucleus normaliser and
@@ -402,6 +486,7 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
         if (!empty) r.L64 = static_cast<double>(L) + log2_split(static_cast<float>(sh.sel_incl)) - 40.0;
         stamp(8);
     }
+    if constexpr (kTopK) r.thr = fmaxf(r.thr, x_lo);          // x*_K >= x_k whenever the mass select found one
     return r;
 }
 

@@ -138,6 +138,19 @@ class HipOps:
             logits, tok, lp_d, u, ws, inv_temperature=inv_temperature, top_p=top_p))
         return r.lp_target, r.accept, r.n_acc, r.accept_bits, r.t_nucleus_logit, r.n_finite
 
+    @traced("verify_accept_top_k")
+    def verify_accept_top_k(self, logits, tok, lp_d, u, inv_temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+        """Verify against the TARGET's Temperature -> TopK -> TopP set (asd_verify_accept_top_k) -> (lp_t, accept, n_acc, bits,
+        thr [B,K], n_finite [B]); top_k <= 0 or >= V is verify_accept_top_p (the same bits)."""
+        B, K = tok.shape
+        V = logits.shape[-1]
+        off = not (0 < top_k < V) and not (0.0 < top_p < 1.0)
+        ws = self._workspace(B, K, V, logits.dtype, logits.device) if off else None
+        nbytes = B * K * V * logits.element_size() + 21 * B * K + 16 * B
+        r = self._timed_step("asd_verify_accept_top_k", nbytes, lambda: self.K.verify_accept_top_k(
+            logits, tok, lp_d, u, ws, inv_temperature=inv_temperature, top_k=top_k, top_p=top_p))
+        return r.lp_target, r.accept, r.n_acc, r.accept_bits, r.t_nucleus_logit, r.n_finite
+
     @traced("verify_stop")
     def verify_stop(self, logits, tok, lp_d, u, inv_temperature, pred, feat, p_hist, stage_idx, costs, lam,
                     risk_adjustment=True, n_obs=100, alpha=1.0, beta=1.0, stats_col=5):
@@ -239,6 +252,14 @@ class HipOps:
         d = self._sampler("draft", logits.shape[0], logits.shape[1], logits.dtype, logits.device)(logits, r, inv_temperature, top_p)
         return d.tok, d.lp, d.thr
 
+    @traced("draft_sample_top_k")
+    def draft_sample_top_k(self, logits, r, inv_temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+        """X1 under Temperature -> TopK -> TopP (asd_draft_sample_top_k): logits [B,V] -> (tok i32 [B], log q(tok) f32 [B],
+        threshold max(x_k, x*_K) f32 [B])."""
+        s = self._sampler("draft", logits.shape[0], logits.shape[1], logits.dtype, logits.device)
+        d = s.top_k(logits, r, inv_temperature, top_k=top_k, top_p=top_p)
+        return d.tok, d.lp, d.thr
+
     @traced("residual_sample")
     def residual_sample(self, t_logits, d_logits, n_acc, r, bonus, inv_temperature: float = 1.0, d_threshold=None,
                         t_threshold=None, top_p: float = 1.0):
@@ -249,6 +270,15 @@ class HipOps:
             return s.top_p(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_p=top_p, t_threshold=t_threshold,
                            d_threshold=d_threshold)
         return s(t_logits, d_logits, n_acc, r, bonus, inv_temperature, d_threshold=d_threshold)
+
+    @traced("residual_sample_top_k")
+    def residual_sample_top_k(self, t_logits, d_logits, n_acc, r, bonus, inv_temperature: float = 1.0, d_threshold=None,
+                              t_threshold=None, top_k: int = 0, top_p: float = 1.0):
+        """The committed token against the TARGET's top-k + top-p set (asd_residual_sample_top_k; t_threshold [n,K] = the
+        thresholds of verify_accept_top_k).  top_k <= 0 or >= V is the top-p route (the same bits)."""
+        s = self._sampler("residual", t_logits.shape[0], t_logits.shape[2], t_logits.dtype, t_logits.device)
+        return s.top_k(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_k=top_k, top_p=top_p, t_threshold=t_threshold,
+                       d_threshold=d_threshold)
 
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):

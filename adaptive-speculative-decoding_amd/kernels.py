@@ -198,6 +198,35 @@ def verify_accept_top_p(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
     return out
 
 
+def verify_accept_top_k(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
+                        workspace: Optional[VerifyWorkspace], *, inv_temperature: float = 1.0, top_k: int = 0,
+                        top_p: float = 1.0, out: Optional[NucleusVerifyResult] = None) -> NucleusVerifyResult:
+    """The verify step against the target's Temperature -> TopK -> TopP set (include/asd_hip.h: asd_verify_accept_top_k):
+    lp_target = log q(tok) over { x >= thr }, thr = max(x_k, x*_K) (t_nucleus_logit), -inf outside it.  HF
+    generate(do_sample=True, ...) applies top_k = 50 unless told otherwise.  top_k <= 0 or >= V is verify_accept_top_p (the
+    same bits; `workspace` only matters when top_p is off too)."""
+    Bv, K = tok.shape
+    V, ld, ptr = _logits_2d(logits, Bv, K)
+    dev = logits.device
+    if out is None:
+        out = NucleusVerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
+                                  torch.empty((Bv, K), dtype=torch.uint8, device=dev),
+                                  torch.empty((Bv,), dtype=torch.int32, device=dev),
+                                  torch.empty((Bv,), dtype=torch.int64, device=dev),
+                                  torch.empty((Bv, K), dtype=torch.float32, device=dev),
+                                  torch.empty((Bv,), dtype=torch.int32, device=dev))
+    ws_ptr, ws_bytes = (None, 0) if workspace is None else (workspace.buf.data_ptr(), workspace.bytes)
+    rc = _lib().asd_verify_accept_top_k(
+        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
+        _dev(u, "u", torch.float32), Bv, K, V, float(inv_temperature), int(top_k), float(top_p),
+        _dev(out.lp_target, "lp_target", torch.float32), _dev(out.accept, "accept", torch.uint8),
+        _dev(out.n_acc, "n_acc", torch.int32), _dev(out.accept_bits, "accept_bits", torch.int64),
+        _dev(out.t_nucleus_logit, "t_nucleus_logit", torch.float32), _dev(out.n_finite, "n_finite", torch.int32),
+        ws_ptr, ws_bytes, _stream())
+    B.check("asd_verify_accept_top_k", rc)
+    return out
+
+
 def verify_accept_stats(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
                         workspace: VerifyWorkspace, out: Optional[VerifyResult] = None, *, inv_temperature: float = 1.0,
                         want_entropy: bool = True) -> Tuple[VerifyResult, torch.Tensor, Optional[torch.Tensor]]:
@@ -659,6 +688,33 @@ class ResidualSampler(_StatusWorkspace):
         B.check("asd_residual_sample_top_p", rc)
         return out
 
+    def top_k(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
+              bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0, *, top_k: int, top_p: float = 1.0,
+              t_threshold: Optional[torch.Tensor], d_threshold: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The committed token against the target's top-k + top-p set (asd_residual_sample_top_k): t_threshold [B,K] = the
+        thresholds of verify_accept_top_k; the bonus rows' are found by the sampler with the same select.  top_k <= 0 or
+        >= V is top_p(...) (the same bits)."""
+        Bv, K, V = t_logits.shape
+        if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
+            raise ValueError("t_logits and d_logits must have the same shape and dtype")
+        tp, ldt = _rows(t_logits, "t_logits")
+        dp, ldd = _rows(d_logits, "d_logits")
+        bp, ldb = (None, V) if bonus_logits is None else _rows(bonus_logits, "bonus_logits")
+        if out is None:
+            out = torch.empty((Bv,), dtype=torch.int32, device=t_logits.device)
+        for name, t in (("t_threshold", t_threshold), ("d_threshold", d_threshold)):
+            if t is not None and tuple(t.shape) != (Bv, K):
+                raise ValueError(f"{name} must be [B, K]")
+        rc = _lib().asd_residual_sample_top_k(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype],
+                                              _dev(n_acc, "n_acc", torch.int32), _dev(r, "r", torch.float32), Bv, K, V,
+                                              float(inv_temperature), int(top_k), float(top_p),
+                                              _opt(t_threshold, "t_threshold", torch.float32),
+                                              _opt(d_threshold, "d_threshold", torch.float32), out.data_ptr(),
+                                              self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_residual_sample_top_k", rc)
+        return out
+
 
 @dataclass
 class DraftDraw:
@@ -696,4 +752,26 @@ class DraftSampler(_StatusWorkspace):
                                      _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
                                      _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
         B.check("asd_draft_sample", rc)
+        return out
+
+    def top_k(self, logits: torch.Tensor, r: torch.Tensor, inv_temperature: float = 1.0, *, top_k: int, top_p: float = 1.0,
+              out: Optional[DraftDraw] = None) -> DraftDraw:
+        """The proposal under HF's Temperature -> TopK -> TopP chain (asd_draft_sample_top_k): thr = max(x_k, x*_K), the
+        threshold of the top-p select taken over the top-k set.  HF generate(do_sample=True, ...) applies top_k = 50 unless
+        told otherwise.  top_k <= 0 or >= V is __call__ (the same bits); otherwise one workgroup per row, the workspace unused."""
+        if logits.dim() != 2 or logits.dtype != self.dtype or not logits.is_cuda or logits.stride(1) != 1:
+            raise ValueError(f"logits must be a [B, V] {self.dtype} CUDA tensor with unit stride along V")
+        Bv, V = logits.shape
+        if Bv > self.B or V != self.V:
+            raise ValueError(f"sampler was sized for B<={self.B}, V={self.V}")
+        dev = logits.device
+        if out is None:
+            out = DraftDraw(torch.empty((Bv,), dtype=torch.int32, device=dev),
+                            torch.empty((Bv,), dtype=torch.float32, device=dev),
+                            torch.empty((Bv,), dtype=torch.float32, device=dev))
+        rc = _lib().asd_draft_sample_top_k(logits.data_ptr(), logits.stride(0) if Bv > 1 else V, _DTYPE_CODE[logits.dtype],
+                                           _dev(r, "r", torch.float32), Bv, V, float(inv_temperature), int(top_k), float(top_p),
+                                           _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
+                                           _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_draft_sample_top_k", rc)
         return out

@@ -58,6 +58,12 @@ class HierarchyConfig:
     # nucleus of the VERIFYING tiers: verify and commit against the target's p^N, as HF's assisted generation warps the target's
     # scores too (generate_training_data.py:110-119; asd_verify_accept_top_p).  >= 1: off, the full softmax(x / T)
     target_top_p: float = 1.0
+    # top-k before top-p (HF's TopKLogitsWarper -> TopPLogitsWarper; asd_draft_sample_top_k / asd_verify_accept_top_k /
+    # asd_residual_sample_top_k): `top_k` for the DRAFT tier, `target_top_k` for the verifying tiers.  <= 0: off.  HF
+    # generate(do_sample=True, ...) applies top_k = 50 unless told otherwise, so the reference's observable sampling is
+    # top_k = 50, top_p = 0.9, temperature = 0.7 here, with target_top_k = 50, target_top_p = 0.9 for the target.
+    top_k: int = 0
+    target_top_k: int = 0
     stage_costs: Sequence[float] = (1.0, 4.5, 10.0)   # BASELINE.md cost units 7B / 32B / 72B
     lambda_value: float = 1.0
     risk_adjustment: bool = True             # pipeline.py:234-238
@@ -202,7 +208,10 @@ class DraftRole:
         for k in range(K):
             self.d_logits[:, k] = dl
             r = torch.rand((self.batch_total,), generator=self.gen, device=dl.device)[self.batch_offset:self.batch_offset + B].contiguous()
-            t, lp, thr = self.ops.draft_sample(self.d_logits[:, k], r, self.inv_t, cfg.top_p)
+            if cfg.top_k > 0:                           # top-k before top-p: thr = max(x_k, x*_K)
+                t, lp, thr = self.ops.draft_sample_top_k(self.d_logits[:, k], r, self.inv_t, cfg.top_k, cfg.top_p)
+            else:
+                t, lp, thr = self.ops.draft_sample(self.d_logits[:, k], r, self.inv_t, cfg.top_p)
             self.tok[:, k], self.lp_d[:, k], self.thr[:, k] = t, lp, thr
             if k + 1 < K:
                 dl = _timed(self, lambda: self.m.forward_ragged(t[:, None].to(torch.int64), L + k, w))[:, -1]
@@ -267,6 +276,14 @@ class LogitsHead:
         self._logits = self.m.lm_head(hid) * self.m.logit_scale
         K = tok.shape[1]
         return self.ops.verify_accept_top_p(self._logits[:, :K].contiguous(), tok, lp_d, u, inv_temperature=inv_t, top_p=top_p)
+
+    def score_top_k(self, hid, tok, lp_d, u, inv_t, top_k, top_p):
+        """Against the target's top-k + top-p set (asd_verify_accept_top_k) -> (lp_t, accept, n_acc, bits, thr [n,K],
+        n_finite [n])."""
+        self._logits = self.m.lm_head(hid) * self.m.logit_scale
+        K = tok.shape[1]
+        return self.ops.verify_accept_top_k(self._logits[:, :K].contiguous(), tok, lp_d, u, inv_temperature=inv_t, top_k=top_k,
+                                            top_p=top_p)
 
     def draw_rows(self, sel: torch.Tensor, j: torch.Tensor) -> torch.Tensor:
         """Target logits row j[i] of local sequence sel[i] -> [m, V]."""
@@ -365,8 +382,13 @@ class VerifyRole:
         self.feat = prompt_features(prompt_ids) if feat is None else feat
         self.head = head if head is not None else LogitsHead(model, ops)
         self.t_top_p = float(cfg.target_top_p)
-        self.nucleus = 0.0 < self.t_top_p < 1.0             # verify / commit against the target's nucleus
+        self.t_top_k = int(cfg.target_top_k)
+        self.topk = self.t_top_k > 0                        # top-k before the target's top-p (asd_verify_accept_top_k)
+        self.nucleus = 0.0 < self.t_top_p < 1.0 or self.topk     # verify / commit against the target's truncated p
         if self.nucleus:
+            if self.topk and isinstance(self.head, ShardedHead):
+                raise ValueError("target_top_k > 0 is not supported on a vocabulary-sharded head (the count select would "
+                                 "have to run across the shards)")
             if isinstance(self.head, ShardedHead):
                 raise ValueError("target_top_p < 1 is not supported on a vocabulary-sharded head (the nucleus select would "
                                  "have to run across the shards)")
@@ -433,7 +455,11 @@ class VerifyRole:
                          beta=cfg.risk_beta, stats_col=cfg.stats_col)
         n_fin = None
         if self.nucleus:                                    # the target's nucleus: verify, then the stop rule on the finite lp_t
-            lp_t, accept, n_acc, bits, self._t_thr, n_fin = self.head.score_top_p(hid, tok_i, lp_d, u, self.inv_t, self.t_top_p)
+            if self.topk:
+                lp_t, accept, n_acc, bits, self._t_thr, n_fin = self.head.score_top_k(hid, tok_i, lp_d, u, self.inv_t, self.t_top_k,
+                                                                                      self.t_top_p)
+            else:
+                lp_t, accept, n_acc, bits, self._t_thr, n_fin = self.head.score_top_p(hid, tok_i, lp_d, u, self.inv_t, self.t_top_p)
             score, k_star, ph = self.ops.predictor_stop(self.pred, lp_t.contiguous(), stop_args["feat"], ph, self.s,
                                                         self.costs, cfg.lambda_value, cfg.risk_adjustment, cfg.n_obs,
                                                         cfg.risk_alpha, cfg.risk_beta, cfg.stats_col, n_valid=n_fin)
@@ -507,7 +533,11 @@ class VerifyRole:
             d_full[where] = d_rows
             thr[where] = d_thr
         all_acc = (j >= K).to(torch.int32)                  # K = 1 view: 0 -> residual of the two rows, 1 -> bonus draw
-        if self.nucleus:
+        if self.topk:
+            tokd = self.ops.residual_sample_top_k(t_rows[:, None, :], d_full[:, None, :], all_acc.contiguous(),
+                                                  self._r[b_sel].contiguous(), t_rows, self.inv_t, d_threshold=thr[:, None].contiguous(),
+                                                  t_threshold=t_thr[:, None].contiguous(), top_k=self.t_top_k, top_p=self.t_top_p)
+        elif self.nucleus:
             tokd = self.ops.residual_sample(t_rows[:, None, :], d_full[:, None, :], all_acc.contiguous(), self._r[b_sel].contiguous(),
                                             t_rows, self.inv_t, d_threshold=thr[:, None].contiguous(),
                                             t_threshold=t_thr[:, None].contiguous(), top_p=self.t_top_p)
@@ -1050,6 +1080,9 @@ class ShardedTargetRole:
 
     def __init__(self, model, cfg: HierarchyConfig, ops, prompt_local: torch.Tensor, max_new_tokens: int, predictor,
                  head: "ShardedHead", b0: int, batch_total: int, group=None, feat_local: Optional[torch.Tensor] = None):
+        if cfg.target_top_k > 0:
+            raise ValueError("target_top_k > 0 is not supported by the vocabulary-sharded target (the count select would "
+                             "have to run across the shards)")
         if 0.0 < cfg.target_top_p < 1.0:
             raise ValueError("target_top_p < 1 is not supported by the vocabulary-sharded target (the nucleus select would "
                              "have to run across the shards)")

@@ -64,6 +64,11 @@ class SpeculativeVerifier:
         self.draft_sampler = K.DraftSampler(batch, vocab, logits_dtype, self.device)  # proposal step (asd_draft_sample)
         self.top_p = 1.0                  # nucleus of the draft tier (reference: 0.9, generate_training_data.py:110-119)
         self.target_top_p = 1.0           # nucleus of the TARGET: verify and commit against p^N (asd_verify_accept_top_p); >= 1: off
+        # top-k before top-p (HF's TopKLogitsWarper; generate(do_sample=True, ...) applies top_k = 50 unless told otherwise):
+        # `top_k` for the draft's proposal (asd_draft_sample_top_k), `target_top_k` for the verify and the commit
+        # (asd_verify_accept_top_k / asd_residual_sample_top_k).  <= 0: off
+        self.top_k = 0
+        self.target_top_k = 0
         self.in_dim = self.hidden = 0
         self.packed = None
         self._lm_head = None              # (key, kernels.LmHeadVerifier) of the last verify_hidden call
@@ -82,18 +87,24 @@ class SpeculativeVerifier:
                out: Optional[K.VerifyResult] = None) -> K.VerifyResult:
         """`logits` are RAW target logits: 1/temperature is applied inside the kernel (self.inv_temperature).  With a target
         nucleus (0 < target_top_p < 1) the result is a kernels.NucleusVerifyResult (lp_t = log p^N(tok), x*, n_finite)."""
+        if self.target_top_k > 0:
+            return K.verify_accept_top_k(logits, tok, lp_draft, u, None, inv_temperature=self.inv_temperature,
+                                         top_k=self.target_top_k, top_p=self.target_top_p)
         if self._target_nucleus():
             return K.verify_accept_top_p(logits, tok, lp_draft, u, None, inv_temperature=self.inv_temperature,
                                          top_p=self.target_top_p)
         return K.verify_accept(logits, tok, lp_draft, u, self.ws, out, inv_temperature=self.inv_temperature)
 
     def _target_nucleus(self) -> bool:
-        return 0.0 < self.target_top_p < 1.0
+        return 0.0 < self.target_top_p < 1.0 or self.target_top_k > 0
 
     def draw(self, t_logits: torch.Tensor, d_logits: torch.Tensor, v: K.VerifyResult, r: torch.Tensor,
              bonus_logits: Optional[torch.Tensor], d_threshold: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The token each sequence commits after its accepted prefix: asd_residual_sample_ex, or -- with a target nucleus --
         asd_residual_sample_top_p against the verify's thresholds (the bonus rows' are found by the sampler)."""
+        if self.target_top_k > 0:
+            return self.sampler.top_k(t_logits, d_logits, v.n_acc, r, bonus_logits, self.inv_temperature, top_k=self.target_top_k,
+                                      top_p=self.target_top_p, t_threshold=v.t_nucleus_logit, d_threshold=d_threshold)
         if self._target_nucleus():
             return self.sampler.top_p(t_logits, d_logits, v.n_acc, r, bonus_logits, self.inv_temperature, top_p=self.target_top_p,
                                       t_threshold=v.t_nucleus_logit, d_threshold=d_threshold)
@@ -107,7 +118,7 @@ class SpeculativeVerifier:
         the [B, K, V] logits stay in MFMA accumulators (asd_lm_head_verify).  `logit_scale` multiplies the
         logits like SyntheticLM.logit_scale; it rides on the temperature constant."""
         if self._target_nucleus():
-            raise ValueError("target_top_p < 1 needs materialised logits (verify / step): the nucleus select does not run "
+            raise ValueError("target_top_p < 1 / target_top_k > 0 need materialised logits (verify / step): the select does not run "
                              "inside the fused lm_head kernel")
         key = (lm_head_weight.data_ptr(), tok.shape[0], tok.shape[1])
         if self._lm_head is None or self._lm_head[0] != key:
@@ -152,7 +163,10 @@ def _propose(verifier: "SpeculativeVerifier", logits: torch.Tensor, gen: torch.G
     HF generate(do_sample=True, temperature=0.7, top_p=0.9), generate_training_data.py:110-119)."""
     logits = logits.contiguous()
     r = torch.rand((logits.shape[0],), generator=gen, device=logits.device)
-    d = verifier.draft_sampler(logits, r, verifier.inv_temperature, verifier.top_p)
+    if verifier.top_k > 0:                          # top-k before top-p: thr = max(x_k, x*_K)
+        d = verifier.draft_sampler.top_k(logits, r, verifier.inv_temperature, top_k=verifier.top_k, top_p=verifier.top_p)
+    else:
+        d = verifier.draft_sampler(logits, r, verifier.inv_temperature, verifier.top_p)
     return d.tok.to(torch.int64), d.lp, d.thr
 
 

@@ -490,6 +490,56 @@ int asd_residual_sample_top_p(const void* t_logits, int64_t ld_t, const void* d_
                               const float* d_threshold /*[B,K] or NULL*/, int32_t* token /*[B] out*/,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Top-k before top-p, on all three sampling steps.  The reference calls HF generate(do_sample=True, temperature=0.7,
+ * top_p=0.9) (src/training/generate_training_data.py:110-119) and passes no top_k, so transformers applies its default
+ * top_k = 50 (GenerationConfig; a checkpoint's generation_config.json may set another value): the warper chain is
+ * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper, on the draft's scores and, in assisted generation, on the
+ * target's.  For a row x (raw logits, T > 0) and 1 <= top_k < V:
+ *   x_k   = the top_k-th largest value of the row counting multiplicity; K = { v : x_v >= x_k } (every tie at x_k kept:
+ *           TopKLogitsWarper removes scores < topk(scores, k).values[-1]).  Fewer than top_k values > -inf: x_k = -inf.
+ *   x*_K  = the nucleus threshold of softmax(x / T) restricted to K and renormalised over K, by the definition of
+ *           asd_draft_sample (the largest value whose upper mass reaches top_p, every tie kept); -inf for top_p outside (0,1)
+ *   thr   = max(x_k, x*_K);  q = softmax(x / T) restricted to { x >= thr } and renormalised
+ * The draw, lp, the accept rule and the residual rule are those of the top-p entry points with this thr, so every
+ * threshold output below is thr and asd_residual_sample_ex / _top_p consume it unchanged.  x_k is found by a radix select by
+ * COUNT (integer counts: no dependence on the geometry); thr, lp and lp_t come from ONE select body shared by the three
+ * entry points (the same bits for the same row).  The sets are defined on raw logits: for bf16 / f16 rows x / T in f32
+ * cannot merge two distinct values, so K and thr's set equal HF's; for f32 rows two logits one ulp apart can round to the
+ * same x / T in HF's scores while the select still tells them apart (a difference at the boundary only).
+ * Off switch: top_k <= 0 or top_k >= V is the corresponding top-p entry point (asd_draft_sample, asd_verify_accept_top_p,
+ * asd_residual_sample_top_p) with the same arguments: the same bits, the same status codes.  Otherwise the argument checks
+ * and status codes are those of that entry point.  Rows: 16-byte aligned, a whole number of 16-byte vectors,
+ * V*sizeof(elem) <= 2 MiB.
+ *
+ * asd_draft_sample_top_k: tok / lp / threshold as asd_draft_sample's tok / lp / nucleus_logit, with thr.  Geometry: ONE
+ *   launch of one 1024-lane workgroup per row at every B (the spread-over-workgroups form of asd_draft_sample does not take
+ *   top-k yet); `workspace` is accepted as for asd_draft_sample (asd_draft_sample_workspace_bytes) and left untouched.
+ * ---------------------------------------------------------------------------------------- */
+int asd_draft_sample_top_k(const void* logits, int64_t ld, int dtype, const float* r /*[B]*/, int B, int V,
+                           float inv_temperature, int top_k, float top_p, int32_t* tok /*[B] out*/,
+                           float* lp /*[B] out, may be NULL*/, float* threshold /*[B] out, may be NULL*/,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* asd_verify_accept_top_k: asd_verify_accept_top_p against thr: lp_t = log q(tok) (-inf when x_tok < thr; bit-identical to
+ *   asd_draft_sample_top_k's lp for the token it drew), accept / n_acc / accept_bits / n_finite as there,
+ *   t_nucleus_logit = thr.  No workspace (may be NULL); two launches (one workgroup per row, one wave per sequence). */
+int asd_verify_accept_top_k(const void* logits, int dtype, int64_t ld_row,
+                            const int32_t* tok /*[B,K]*/, const float* lp_draft /*[B,K]*/, const float* u /*[B,K]*/,
+                            int B, int K, int V, float inv_temperature, int top_k, float top_p,
+                            float* lp_target /*[B,K] out*/, uint8_t* accept /*[B,K] out*/, int32_t* n_acc /*[B] out*/,
+                            uint64_t* accept_bits /*[B] out, may be NULL*/, float* t_nucleus_logit /*[B,K] out, may be NULL*/,
+                            int32_t* n_finite /*[B] out, may be NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+/* asd_residual_sample_top_k: asd_residual_sample_top_p with thr: rows j < K take t_threshold[b,j] (asd_verify_accept_top_k's
+ *   t_nucleus_logit), the bonus row's thr is found here by the same select (bit-identical to asd_draft_sample_top_k's threshold
+ *   on that row), d_threshold = asd_draft_sample_top_k's threshold.  workspace: asd_residual_sample_top_p_workspace_bytes, the
+ *   geometry of asd_residual_sample_top_p. */
+int asd_residual_sample_top_k(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                              const void* bonus_logits, int64_t ld_b, int dtype,
+                              const int32_t* n_acc /*[B]*/, const float* r /*[B]*/, int B, int K, int V,
+                              float inv_temperature, int top_k, float top_p, const float* t_threshold /*[B,K]*/,
+                              const float* d_threshold /*[B,K] or NULL*/, int32_t* token /*[B] out*/,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* N1, second form: asd_verify_accept with the epilogue of asd_predictor_stop run INSIDE the same
  * launch by the wave that completes each sequence (lp = the kernel's own lp_target, all K
  * positions valid).  ONE launch per tier step instead of two, at every batch size: with one workgroup
