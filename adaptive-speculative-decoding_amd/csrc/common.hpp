@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "asd_hip.h"
 
 #define ASD_EXPORT extern "C" __attribute__((visibility("default")))
@@ -31,5 +33,54 @@ inline int dtype_size(int dtype) {
 
 // number of CUs of the CURRENT device (cached per device id; the query is slow)
 int current_device_cus();
+
+// ---- shared by the launchers of the sampling steps (draft_sample.hip, verify_nucleus.hip, residual_sample.hip) ----
+
+// f(std::integral_constant<int, ASD_DTYPE_*>{}): the kernels take the element type as a template argument.  Whatever is not
+// BF16 or F16 takes the F32 branch (the callers have rejected unknown dtypes through dtype_size before).
+template <class F>
+auto dispatch_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case ASD_DTYPE_BF16: return f(std::integral_constant<int, ASD_DTYPE_BF16>{});
+        case ASD_DTYPE_F16: return f(std::integral_constant<int, ASD_DTYPE_F16>{});
+        default: return f(std::integral_constant<int, ASD_DTYPE_F32>{});
+    }
+}
+
+// a logits row as the sampling kernels stream it: 16-byte vectors, tiles of 64 vectors
+struct RowGeom {
+    int esz;              // bytes per element; 0: unknown dtype
+    int nvec, n_tiles;
+    bool whole;           // the row is a whole number of 16-byte vectors
+};
+inline RowGeom row_geom(int V, int dtype) {
+    RowGeom g{};
+    g.esz = dtype_size(dtype);
+    const int64_t bytes = static_cast<int64_t>(V) * g.esz;
+    g.nvec = static_cast<int>(bytes / 16);
+    g.n_tiles = (g.nvec + 63) / 64;
+    g.whole = bytes % 16 == 0;
+    return g;
+}
+// rows of stride ld (elements) from p on start on 16-byte boundaries
+inline bool rows_aligned(const void* p, int64_t ld, int esz) { return aligned_to(p, 16) && (ld * esz) % 16 == 0; }
+
+inline bool valid_inv_temperature(float t) { return t > 0.0f && t < 3.0e38f; }      // (false for NaN)
+// the kernels work in the log2 domain: 2^(x c2) = e^(x / T)
+inline float log2_scale(float inv_temperature) { return static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature)); }
+
+// what a call truncates the distribution to (HF's TopKLogitsWarper -> TopPLogitsWarper)
+struct Truncation {
+    bool nucleus;         // 0 < top_p < 1
+    int top_k;            // the bound where it bounds anything (0 < top_k < V), else 0
+    int levels;           // radix levels of the mass select: 0 without a nucleus, 2 for 16-bit logits, 3 for f32
+};
+inline Truncation truncation(int top_k, float top_p, int V, int dtype) {
+    Truncation t{};
+    t.nucleus = top_p > 0.0f && top_p < 1.0f;
+    t.top_k = (top_k > 0 && top_k < V) ? top_k : 0;
+    t.levels = t.nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
+    return t;
+}
 
 }  // namespace asd

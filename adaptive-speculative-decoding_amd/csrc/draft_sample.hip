@@ -636,32 +636,38 @@ ASD_EXPORT size_t asd_draft_sample_workspace_bytes(int B, int V, int dtype) {
     return kWorkspaceHeaderBytes + round_up(l.hist_bytes + l.small_bytes, 256);
 }
 
-ASD_EXPORT int asd_draft_sample(const void* logits, int64_t ld, int dtype, const float* r, int B, int V,
-                                float inv_temperature, float top_p, int32_t* tok, float* lp, float* nucleus_logit,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+// The launcher behind both entry points.  Without a top-k bound (asd_draft_sample; asd_draft_sample_top_k with top_k <= 0 or
+// >= V: the same call, the same bits) few rows are spread over G workgroups each.  With one (HF's TopKLogitsWarper ->
+// TopPLogitsWarper): ONE launch of k_draft_row<DT, true>, one 1024-lane workgroup per row at every batch size.  The group form
+// (k_draft_group) would have to exchange the count histograms of the select through its mailboxes as it does the mass
+// histograms; until it does, top-k rows are not spread over workgroups (the workspace is accepted and left untouched), and the
+// outputs depend on the row alone.
+int draft_launch(const void* logits, int64_t ld, int dtype, const float* r, int B, int V, float inv_temperature, int top_k,
+                 float top_p, int32_t* tok, float* lp, float* threshold, void* workspace, size_t workspace_bytes, void* stream) {
     if (B < 0 || V < 1) return ASD_ERR_INVALID_ARG;
     if (B == 0) return ASD_OK;
-    const int esz = dtype_size(dtype);
-    if (esz == 0) return ASD_ERR_UNSUPPORTED;
+    const RowGeom g = row_geom(V, dtype);
+    if (g.esz == 0) return ASD_ERR_UNSUPPORTED;
     if (!logits || !r || !tok || ld < V) return ASD_ERR_INVALID_ARG;
-    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f) || top_p != top_p) return ASD_ERR_INVALID_ARG;
-    if ((static_cast<int64_t>(V) * esz) % 16 || !aligned_to(logits, 16) || (ld * esz) % 16) return ASD_ERR_ALIGNMENT;
+    if (!valid_inv_temperature(inv_temperature) || top_p != top_p) return ASD_ERR_INVALID_ARG;
+    if (!g.whole || !rows_aligned(logits, ld, g.esz)) return ASD_ERR_ALIGNMENT;
+    if (g.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
+    const Truncation tr = truncation(top_k, top_p, V, dtype);
     DrParams p{};
     p.logits = logits; p.ld = ld; p.r = r; p.B = B; p.V = V;
-    p.nvec = static_cast<int>(static_cast<int64_t>(V) * esz / 16);
-    p.n_tiles = (p.nvec + 63) / 64;
-    if (p.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
-    p.c2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature));
+    p.nvec = g.nvec; p.n_tiles = g.n_tiles;
+    p.c2 = log2_scale(inv_temperature);
     p.top_p = top_p;
-    const bool nucleus = top_p > 0.0f && top_p < 1.0f;
-    p.levels = nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
-    p.tok = tok; p.lp = lp; p.thr = nucleus_logit;
+    p.levels = tr.levels;
+    p.top_k = tr.top_k;
+    p.tok = tok; p.lp = lp; p.thr = threshold;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // few rows: spread every row over G workgroups (the workspace carries their mailboxes; without one, or with a row too
     // long for the registers of its workgroups, one streaming workgroup per row)
     const DgLayout l = dg_layout(B, p.n_tiles);
     const bool have_ws = workspace && aligned_to(workspace, 256) && workspace_bytes >= kWorkspaceHeaderBytes + l.hist_bytes + l.small_bytes;
-    const int G = g_debug_groups < 0 ? 0 : choose_groups(B, p.n_tiles, current_device_cus(), have_ws);
+    const int G = (tr.top_k > 0 || g_debug_groups < 0) ? 0 : choose_groups(B, p.n_tiles, current_device_cus(), have_ws);
     if (G >= 1) {
         DgParams q{};
         q.d = p;
@@ -674,56 +680,29 @@ ASD_EXPORT int asd_draft_sample(const void* logits, int64_t ld, int dtype, const
         q.withhold1 = g_debug_draft_withhold + 1;
         q.base_shift = dtype == ASD_DTYPE_BF16 ? 16 : (dtype == ASD_DTYPE_F16 ? 13 : 0);
         const int tpw = tiles_per_wave(p.n_tiles, G);
-        switch (dtype) {
-            case ASD_DTYPE_BF16: launch_group<ASD_DTYPE_BF16>(q, tpw, st); break;
-            case ASD_DTYPE_F16: launch_group<ASD_DTYPE_F16>(q, tpw, st); break;
-            default: launch_group<ASD_DTYPE_F32>(q, tpw, st); break;
-        }
+        dispatch_dtype(dtype, [&](auto dt) { launch_group<decltype(dt)::value>(q, tpw, st); });
         return launch_status();
     }
     const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
-    switch (dtype) {
-        case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_draft_row<ASD_DTYPE_BF16>, grid, block, 0, st, p); break;
-        case ASD_DTYPE_F16: hipLaunchKernelGGL(k_draft_row<ASD_DTYPE_F16>, grid, block, 0, st, p); break;
-        default: hipLaunchKernelGGL(k_draft_row<ASD_DTYPE_F32>, grid, block, 0, st, p); break;
-    }
+    dispatch_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (tr.top_k > 0) hipLaunchKernelGGL((k_draft_row<DT, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((k_draft_row<DT, false>), grid, block, 0, st, p);
+    });
     return launch_status();
 }
+}  // namespace
 
-// Top-k before top-p (HF's TopKLogitsWarper -> TopPLogitsWarper): ONE launch of k_draft_row<DT, true>, one 1024-lane workgroup per
-// row at every batch size.  The group form (k_draft_group) would have to exchange the count histograms of the select through its
-// mailboxes as it does the mass histograms; until it does, top-k rows are not spread over workgroups (the workspace is accepted
-// and left untouched), and the outputs depend on the row alone.
+ASD_EXPORT int asd_draft_sample(const void* logits, int64_t ld, int dtype, const float* r, int B, int V,
+                                float inv_temperature, float top_p, int32_t* tok, float* lp, float* nucleus_logit,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    return draft_launch(logits, ld, dtype, r, B, V, inv_temperature, 0, top_p, tok, lp, nucleus_logit, workspace, workspace_bytes,
+                        stream);
+}
+
 ASD_EXPORT int asd_draft_sample_top_k(const void* logits, int64_t ld, int dtype, const float* r, int B, int V,
                                       float inv_temperature, int top_k, float top_p, int32_t* tok, float* lp, float* threshold,
                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (top_k <= 0 || top_k >= V)                       // no top-k bound: asd_draft_sample itself (the same bits)
-        return asd_draft_sample(logits, ld, dtype, r, B, V, inv_temperature, top_p, tok, lp, threshold, workspace,
-                                workspace_bytes, stream);
-    if (B < 0) return ASD_ERR_INVALID_ARG;
-    if (B == 0) return ASD_OK;
-    const int esz = dtype_size(dtype);
-    if (esz == 0) return ASD_ERR_UNSUPPORTED;
-    if (!logits || !r || !tok || ld < V) return ASD_ERR_INVALID_ARG;
-    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f) || top_p != top_p) return ASD_ERR_INVALID_ARG;
-    if ((static_cast<int64_t>(V) * esz) % 16 || !aligned_to(logits, 16) || (ld * esz) % 16) return ASD_ERR_ALIGNMENT;
-    DrParams p{};
-    p.logits = logits; p.ld = ld; p.r = r; p.B = B; p.V = V;
-    p.nvec = static_cast<int>(static_cast<int64_t>(V) * esz / 16);
-    p.n_tiles = (p.nvec + 63) / 64;
-    if (p.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
-    p.c2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature));
-    p.top_p = top_p;
-    const bool nucleus = top_p > 0.0f && top_p < 1.0f;
-    p.levels = nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
-    p.top_k = top_k;
-    p.tok = tok; p.lp = lp; p.thr = threshold;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
-    switch (dtype) {
-        case ASD_DTYPE_BF16: hipLaunchKernelGGL((k_draft_row<ASD_DTYPE_BF16, true>), grid, block, 0, st, p); break;
-        case ASD_DTYPE_F16: hipLaunchKernelGGL((k_draft_row<ASD_DTYPE_F16, true>), grid, block, 0, st, p); break;
-        default: hipLaunchKernelGGL((k_draft_row<ASD_DTYPE_F32, true>), grid, block, 0, st, p); break;
-    }
-    return launch_status();
+    return draft_launch(logits, ld, dtype, r, B, V, inv_temperature, top_k, top_p, tok, lp, threshold, workspace, workspace_bytes,
+                        stream);
 }

@@ -554,31 +554,48 @@ ASD_EXPORT int asd_debug_residual_groups(int groups) {
 #endif
 
 namespace {
+// what the TARGET's distribution is truncated to (asd_residual_sample_top_p / _top_k); {} = not at all
+struct RsTruncate {
+    const float* t_threshold = nullptr;      // [B*K] the verify's thresholds of the target rows
+    float top_p = 1.0f;
+    int top_k = 0;
+};
+
+// The launcher behind the four entry points.  A call that truncates nothing (top_p outside (0, 1) and top_k <= 0 or >= V) is
+// asd_residual_sample_ex's, whichever entry point it came through (the same bits): t_threshold and the larger workspace are
+// not asked for.
 int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d, const void* bonus_logits,
                     int64_t ld_b, int dtype, const int32_t* n_acc, const float* r, int B, int K, int V,
                     float inv_temperature, const float* d_threshold, int32_t* token, void* workspace,
-                    size_t workspace_bytes, void* stream, const float* t_threshold = nullptr, float top_p = 1.0f,
-                    int top_k = 0) {
+                    size_t workspace_bytes, void* stream, const RsTruncate& cut) {
+    // what only a truncating call can fail comes first, before the sizes and the dtype are looked at (asd_residual_sample and
+    // _ex pass top_p = 1)
+    if (cut.top_p != cut.top_p) return ASD_ERR_INVALID_ARG;
+    const Truncation tr = truncation(cut.top_k, cut.top_p, V, dtype);
+    const bool truncated = tr.nucleus || tr.top_k > 0;
+    if (truncated) {
+        if (B > 0 && K > 0 && !cut.t_threshold) return ASD_ERR_INVALID_ARG;
+        if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
+    }
     if (B < 0 || K < 0 || V < 1) return ASD_ERR_INVALID_ARG;
     if (B == 0) return ASD_OK;
-    const int esz = dtype_size(dtype);
-    if (esz == 0) return ASD_ERR_UNSUPPORTED;
+    const RowGeom g = row_geom(V, dtype);
+    if (g.esz == 0) return ASD_ERR_UNSUPPORTED;
     if (!n_acc || !r || !token || !workspace) return ASD_ERR_INVALID_ARG;
     if (K > 0 && (!t_logits || !d_logits || ld_t < V || ld_d < V)) return ASD_ERR_INVALID_ARG;
     if (bonus_logits && ld_b < V) return ASD_ERR_INVALID_ARG;
-    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f)) return ASD_ERR_INVALID_ARG;
+    if (!valid_inv_temperature(inv_temperature)) return ASD_ERR_INVALID_ARG;
     // whole 16-byte vectors, 16-byte aligned rows
-    if ((static_cast<int64_t>(V) * esz) % 16) return ASD_ERR_ALIGNMENT;
-    if ((t_logits && (!aligned_to(t_logits, 16) || (ld_t * esz) % 16)) || (d_logits && (!aligned_to(d_logits, 16) || (ld_d * esz) % 16)) ||
-        (bonus_logits && (!aligned_to(bonus_logits, 16) || (ld_b * esz) % 16)))
+    if (!g.whole) return ASD_ERR_ALIGNMENT;
+    if ((t_logits && !rows_aligned(t_logits, ld_t, g.esz)) || (d_logits && !rows_aligned(d_logits, ld_d, g.esz)) ||
+        (bonus_logits && !rows_aligned(bonus_logits, ld_b, g.esz)))
         return ASD_ERR_ALIGNMENT;
     if (!aligned_to(workspace, 256) || workspace_bytes < asd_residual_sample_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
     RsParams p{};
     p.t_logits = t_logits; p.ld_t = ld_t; p.d_logits = d_logits; p.ld_d = ld_d; p.bonus = bonus_logits; p.ld_b = ld_b;
     p.n_acc = n_acc; p.r = r; p.B = B; p.K = K; p.V = V;
-    p.c2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature));
-    p.nvec = static_cast<int>(static_cast<int64_t>(V) * esz / 16);
-    p.n_tiles = (p.nvec + 63) / 64;
+    p.c2 = log2_scale(inv_temperature);
+    p.nvec = g.nvec; p.n_tiles = g.n_tiles;
     p.S = rs_splits(B, p.n_tiles, current_device_cus());
     char* const body = static_cast<char*>(workspace) + kWorkspaceHeaderBytes;       // (behind the status block)
     p.partial = reinterpret_cast<float4*>(body);
@@ -586,31 +603,21 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     p.token = token;
     p.d_thr = d_threshold;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool nucleus = top_p > 0.0f && top_p < 1.0f, topk = top_k > 0 && top_k < V;
-    if (nucleus || topk) {
+    if (truncated) {
         // the target's nucleus: x* of the rejected rows from the verify (t_threshold), of the bonus rows found here first.
         // Their [B] thresholds live behind the part of the workspace asd_residual_sample_workspace_bytes sizes.  (With top-k
         // the thresholds are the combined max(x_k, x*_K) of asd_verify_accept_top_k / asd_draft_sample_top_k.)
         if (p.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
         const size_t base = asd_residual_sample_workspace_bytes(B, V, dtype);
         float* b_thr = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);
-        p.t_thr = t_threshold;
+        p.t_thr = cut.t_threshold;
         p.b_thr = b_thr;
-        const int levels = nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
         const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
-        if (topk) {
-            switch (dtype) {
-                case ASD_DTYPE_BF16: hipLaunchKernelGGL((k_rs_bonus_threshold<ASD_DTYPE_BF16, true>), grid, block, 0, st, p, top_p, levels, b_thr, top_k); break;
-                case ASD_DTYPE_F16: hipLaunchKernelGGL((k_rs_bonus_threshold<ASD_DTYPE_F16, true>), grid, block, 0, st, p, top_p, levels, b_thr, top_k); break;
-                default: hipLaunchKernelGGL((k_rs_bonus_threshold<ASD_DTYPE_F32, true>), grid, block, 0, st, p, top_p, levels, b_thr, top_k); break;
-            }
-        } else {
-            switch (dtype) {
-                case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_BF16>, grid, block, 0, st, p, top_p, levels, b_thr, 0); break;
-                case ASD_DTYPE_F16: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F16>, grid, block, 0, st, p, top_p, levels, b_thr, 0); break;
-                default: hipLaunchKernelGGL(k_rs_bonus_threshold<ASD_DTYPE_F32>, grid, block, 0, st, p, top_p, levels, b_thr, 0); break;
-            }
-        }
+        dispatch_dtype(dtype, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value;
+            if (tr.top_k > 0) hipLaunchKernelGGL((k_rs_bonus_threshold<DT, true>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, tr.top_k);
+            else hipLaunchKernelGGL((k_rs_bonus_threshold<DT, false>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, 0);
+        });
         if (launch_status() != ASD_OK) return ASD_ERR_HIP;
         workspace_bytes = base;                        // the geometry choice below sees the workspace asd_residual_sample_ex would
     }
@@ -637,37 +644,23 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
                 q.small = reinterpret_cast<unsigned long long*>(body + l.legacy_bytes);
                 q.status = static_cast<uint32_t*>(workspace);
                 const dim3 grid(static_cast<unsigned>(G), static_cast<unsigned>(B)), block(kDrThreads);
-#define ASD_LAUNCH_RG(DT)                                                                                 \
-    do {                                                                                                  \
-        if (tpw <= 3) hipLaunchKernelGGL((k_residual_group<DT, 3>), grid, block, 0, st, q);               \
-        else if (tpw <= 5) hipLaunchKernelGGL((k_residual_group<DT, 5>), grid, block, 0, st, q);          \
-        else if (tpw <= 7) hipLaunchKernelGGL((k_residual_group<DT, 7>), grid, block, 0, st, q);          \
-        else hipLaunchKernelGGL((k_residual_group<DT, 10>), grid, block, 0, st, q);                       \
-    } while (0)
-                switch (dtype) {
-                    case ASD_DTYPE_BF16: ASD_LAUNCH_RG(ASD_DTYPE_BF16); break;
-                    case ASD_DTYPE_F16: ASD_LAUNCH_RG(ASD_DTYPE_F16); break;
-                    default: ASD_LAUNCH_RG(ASD_DTYPE_F32); break;
-                }
-#undef ASD_LAUNCH_RG
+                dispatch_dtype(dtype, [&](auto dt) {
+                    constexpr int DT = decltype(dt)::value;
+                    if (tpw <= 3) hipLaunchKernelGGL((k_residual_group<DT, 3>), grid, block, 0, st, q);
+                    else if (tpw <= 5) hipLaunchKernelGGL((k_residual_group<DT, 5>), grid, block, 0, st, q);
+                    else if (tpw <= 7) hipLaunchKernelGGL((k_residual_group<DT, 7>), grid, block, 0, st, q);
+                    else hipLaunchKernelGGL((k_residual_group<DT, 10>), grid, block, 0, st, q);
+                });
                 return launch_status();
             }
         }
     }
     if (B >= kRsRowMinBatch && p.n_tiles <= kDrMaxTiles) {
         const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
-        switch (dtype) {
-            case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_residual_row<ASD_DTYPE_BF16>, grid, block, 0, st, p); break;
-            case ASD_DTYPE_F16: hipLaunchKernelGGL(k_residual_row<ASD_DTYPE_F16>, grid, block, 0, st, p); break;
-            default: hipLaunchKernelGGL(k_residual_row<ASD_DTYPE_F32>, grid, block, 0, st, p); break;
-        }
+        dispatch_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL(k_residual_row<decltype(dt)::value>, grid, block, 0, st, p); });
         return launch_status();
     }
-    switch (dtype) {
-        case ASD_DTYPE_BF16: return launch_rs<ASD_DTYPE_BF16>(p, st);
-        case ASD_DTYPE_F16: return launch_rs<ASD_DTYPE_F16>(p, st);
-        default: return launch_rs<ASD_DTYPE_F32>(p, st);
-    }
+    return dispatch_dtype(dtype, [&](auto dt) { return launch_rs<decltype(dt)::value>(p, st); });
 }
 
 }  // namespace
@@ -677,7 +670,7 @@ ASD_EXPORT int asd_residual_sample(const void* t_logits, int64_t ld_t, const voi
                                    const float* r, int B, int K, int V, float inv_temperature, int32_t* token,
                                    void* workspace, size_t workspace_bytes, void* stream) {
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
-                           nullptr, token, workspace, workspace_bytes, stream);
+                           nullptr, token, workspace, workspace_bytes, stream, {});
 }
 
 ASD_EXPORT int asd_residual_sample_ex(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
@@ -686,7 +679,7 @@ ASD_EXPORT int asd_residual_sample_ex(const void* t_logits, int64_t ld_t, const 
                                       const float* d_threshold, int32_t* token, void* workspace, size_t workspace_bytes,
                                       void* stream) {
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
-                           d_threshold, token, workspace, workspace_bytes, stream);
+                           d_threshold, token, workspace, workspace_bytes, stream, {});
 }
 
 ASD_EXPORT size_t asd_residual_sample_top_p_workspace_bytes(int B, int V, int dtype) {
@@ -698,14 +691,8 @@ ASD_EXPORT int asd_residual_sample_top_p(const void* t_logits, int64_t ld_t, con
                                          const float* r, int B, int K, int V, float inv_temperature, float top_p,
                                          const float* t_threshold, const float* d_threshold, int32_t* token, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-    if (top_p != top_p) return ASD_ERR_INVALID_ARG;
-    if (!(top_p > 0.0f && top_p < 1.0f))                 // no truncation: asd_residual_sample_ex itself (the same bits)
-        return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
-                               d_threshold, token, workspace, workspace_bytes, stream);
-    if (B > 0 && K > 0 && !t_threshold) return ASD_ERR_INVALID_ARG;
-    if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
-                           d_threshold, token, workspace, workspace_bytes, stream, t_threshold, top_p);
+                           d_threshold, token, workspace, workspace_bytes, stream, {t_threshold, top_p, 0});
 }
 
 ASD_EXPORT int asd_residual_sample_top_k(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
@@ -713,12 +700,6 @@ ASD_EXPORT int asd_residual_sample_top_k(const void* t_logits, int64_t ld_t, con
                                          const float* r, int B, int K, int V, float inv_temperature, int top_k, float top_p,
                                          const float* t_threshold, const float* d_threshold, int32_t* token, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-    if (top_k <= 0 || top_k >= V)                       // no top-k bound: asd_residual_sample_top_p itself (the same bits)
-        return asd_residual_sample_top_p(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V,
-                                         inv_temperature, top_p, t_threshold, d_threshold, token, workspace, workspace_bytes, stream);
-    if (top_p != top_p) return ASD_ERR_INVALID_ARG;
-    if (B > 0 && K > 0 && !t_threshold) return ASD_ERR_INVALID_ARG;
-    if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
-                           d_threshold, token, workspace, workspace_bytes, stream, t_threshold, top_p, top_k);
+                           d_threshold, token, workspace, workspace_bytes, stream, {t_threshold, top_p, top_k});
 }

@@ -89,63 +89,24 @@ __global__ __launch_bounds__(256) void k_fill_f32(float* out, int64_t n, float v
 using namespace asd;
 
 namespace {
-// the launches of asd_verify_accept_top_p (top_k = 0) and asd_verify_accept_top_k (1 <= top_k < V); arguments checked by them
-int verify_nucleus_launch(const void* logits, int dtype, int64_t ld_row, const int32_t* tok, const float* lp_draft, const float* u,
-                          int B, int K, int V, float inv_temperature, int top_k, float top_p, float* lp_target, uint8_t* accept,
-                          int32_t* n_acc, uint64_t* accept_bits, float* t_nucleus_logit, int32_t* n_finite, hipStream_t st) {
-    const int esz = dtype_size(dtype);
-    const int64_t R = static_cast<int64_t>(B) * K;
-    // the nucleus select streams whole 16-byte vectors of 16-byte aligned rows (as asd_draft_sample)
-    if ((static_cast<int64_t>(V) * esz) % 16 || !aligned_to(logits, 16) || (ld_row * esz) % 16) return ASD_ERR_ALIGNMENT;
-    VnParams p{};
-    p.logits = logits; p.ld = ld_row; p.tok = tok; p.lp_d = lp_draft; p.u = u;
-    p.B = B; p.K = K; p.V = V;
-    p.nvec = static_cast<int>(static_cast<int64_t>(V) * esz / 16);
-    p.n_tiles = (p.nvec + 63) / 64;
-    if (p.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
-    p.c2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature));
-    p.top_p = top_p;
-    const bool nucleus = top_p > 0.0f && top_p < 1.0f;          // (always, without top-k)
-    p.levels = nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
-    p.top_k = top_k;
-    p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
-    p.thr = t_nucleus_logit; p.n_finite = n_finite;
-    const dim3 grid(static_cast<unsigned>(R)), block(kDrThreads);
-    if (top_k > 0) {
-        switch (dtype) {
-            case ASD_DTYPE_BF16: hipLaunchKernelGGL((k_verify_nucleus<ASD_DTYPE_BF16, true>), grid, block, 0, st, p); break;
-            case ASD_DTYPE_F16: hipLaunchKernelGGL((k_verify_nucleus<ASD_DTYPE_F16, true>), grid, block, 0, st, p); break;
-            default: hipLaunchKernelGGL((k_verify_nucleus<ASD_DTYPE_F32, true>), grid, block, 0, st, p); break;
-        }
-    } else {
-        switch (dtype) {
-            case ASD_DTYPE_BF16: hipLaunchKernelGGL(k_verify_nucleus<ASD_DTYPE_BF16>, grid, block, 0, st, p); break;
-            case ASD_DTYPE_F16: hipLaunchKernelGGL(k_verify_nucleus<ASD_DTYPE_F16>, grid, block, 0, st, p); break;
-            default: hipLaunchKernelGGL(k_verify_nucleus<ASD_DTYPE_F32>, grid, block, 0, st, p); break;
-        }
-    }
-    hipLaunchKernelGGL(k_nucleus_finish, dim3(static_cast<unsigned>(B)), dim3(64), 0, st, accept, lp_target, K, 1, n_acc,
-                       accept_bits, n_finite);
-    return launch_status();
-}
-}  // namespace
-
-ASD_EXPORT int asd_verify_accept_top_p(const void* logits, int dtype, int64_t ld_row, const int32_t* tok,
-                                       const float* lp_draft, const float* u, int B, int K, int V, float inv_temperature,
-                                       float top_p, float* lp_target, uint8_t* accept, int32_t* n_acc, uint64_t* accept_bits,
-                                       float* t_nucleus_logit, int32_t* n_finite, void* workspace, size_t workspace_bytes,
-                                       void* stream) {
+// asd_verify_accept_top_p (top_k = 0) and asd_verify_accept_top_k; a top_k that bounds nothing (<= 0 or >= V) is the former's
+// call (the same bits)
+int verify_truncated(const void* logits, int dtype, int64_t ld_row, const int32_t* tok, const float* lp_draft, const float* u,
+                     int B, int K, int V, float inv_temperature, int top_k, float top_p, float* lp_target, uint8_t* accept,
+                     int32_t* n_acc, uint64_t* accept_bits, float* t_nucleus_logit, int32_t* n_finite, void* workspace,
+                     size_t workspace_bytes, void* stream) {
     if (B < 0 || K < 0 || V < 1) return ASD_ERR_INVALID_ARG;
     if (B == 0 || K == 0) return ASD_OK;
     if (K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
-    const int esz = dtype_size(dtype);
-    if (esz == 0) return ASD_ERR_UNSUPPORTED;
+    const RowGeom g = row_geom(V, dtype);
+    if (g.esz == 0) return ASD_ERR_UNSUPPORTED;
     if (!logits || !tok || !lp_draft || !u || !lp_target || !accept || !n_acc || ld_row < V) return ASD_ERR_INVALID_ARG;
-    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f) || top_p != top_p) return ASD_ERR_INVALID_ARG;
+    if (!valid_inv_temperature(inv_temperature) || top_p != top_p) return ASD_ERR_INVALID_ARG;
     const int64_t R = static_cast<int64_t>(B) * K;
     if (R > INT32_MAX) return ASD_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!(top_p > 0.0f && top_p < 1.0f)) {
+    const Truncation tr = truncation(top_k, top_p, V, dtype);
+    if (!tr.nucleus && tr.top_k == 0) {
         // no truncation: asd_verify_accept_ex itself (the same bits), then x* = -inf and the leading finite run
         asd_verify_options opt{};
         opt.inv_temperature = inv_temperature;
@@ -159,8 +120,38 @@ ASD_EXPORT int asd_verify_accept_top_p(const void* logits, int dtype, int64_t ld
                                          n_acc, accept_bits, n_finite);
         return launch_status();
     }
-    return verify_nucleus_launch(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, 0, top_p, lp_target, accept,
-                                 n_acc, accept_bits, t_nucleus_logit, n_finite, st);
+    // the nucleus select streams whole 16-byte vectors of 16-byte aligned rows (as asd_draft_sample)
+    if (!g.whole || !rows_aligned(logits, ld_row, g.esz)) return ASD_ERR_ALIGNMENT;
+    if (g.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
+    VnParams p{};
+    p.logits = logits; p.ld = ld_row; p.tok = tok; p.lp_d = lp_draft; p.u = u;
+    p.B = B; p.K = K; p.V = V;
+    p.nvec = g.nvec; p.n_tiles = g.n_tiles;
+    p.c2 = log2_scale(inv_temperature);
+    p.top_p = top_p;
+    p.levels = tr.levels;
+    p.top_k = tr.top_k;
+    p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
+    p.thr = t_nucleus_logit; p.n_finite = n_finite;
+    const dim3 grid(static_cast<unsigned>(R)), block(kDrThreads);
+    dispatch_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (tr.top_k > 0) hipLaunchKernelGGL((k_verify_nucleus<DT, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((k_verify_nucleus<DT, false>), grid, block, 0, st, p);
+    });
+    hipLaunchKernelGGL(k_nucleus_finish, dim3(static_cast<unsigned>(B)), dim3(64), 0, st, accept, lp_target, K, 1, n_acc,
+                       accept_bits, n_finite);
+    return launch_status();
+}
+}  // namespace
+
+ASD_EXPORT int asd_verify_accept_top_p(const void* logits, int dtype, int64_t ld_row, const int32_t* tok,
+                                       const float* lp_draft, const float* u, int B, int K, int V, float inv_temperature,
+                                       float top_p, float* lp_target, uint8_t* accept, int32_t* n_acc, uint64_t* accept_bits,
+                                       float* t_nucleus_logit, int32_t* n_finite, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    return verify_truncated(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, 0, top_p, lp_target, accept, n_acc,
+                            accept_bits, t_nucleus_logit, n_finite, workspace, workspace_bytes, stream);
 }
 
 ASD_EXPORT int asd_verify_accept_top_k(const void* logits, int dtype, int64_t ld_row, const int32_t* tok,
@@ -168,17 +159,6 @@ ASD_EXPORT int asd_verify_accept_top_k(const void* logits, int dtype, int64_t ld
                                        int top_k, float top_p, float* lp_target, uint8_t* accept, int32_t* n_acc,
                                        uint64_t* accept_bits, float* t_nucleus_logit, int32_t* n_finite, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    if (top_k <= 0 || top_k >= V)                       // no top-k bound: asd_verify_accept_top_p itself (the same bits)
-        return asd_verify_accept_top_p(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, top_p, lp_target,
-                                       accept, n_acc, accept_bits, t_nucleus_logit, n_finite, workspace, workspace_bytes, stream);
-    if (B < 0 || K < 0) return ASD_ERR_INVALID_ARG;
-    if (B == 0 || K == 0) return ASD_OK;
-    if (K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
-    const int esz = dtype_size(dtype);
-    if (esz == 0) return ASD_ERR_UNSUPPORTED;
-    if (!logits || !tok || !lp_draft || !u || !lp_target || !accept || !n_acc || ld_row < V) return ASD_ERR_INVALID_ARG;
-    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f) || top_p != top_p) return ASD_ERR_INVALID_ARG;
-    if (static_cast<int64_t>(B) * K > INT32_MAX) return ASD_ERR_UNSUPPORTED;
-    return verify_nucleus_launch(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, top_k, top_p, lp_target, accept,
-                                 n_acc, accept_bits, t_nucleus_logit, n_finite, static_cast<hipStream_t>(stream));
+    return verify_truncated(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, top_k, top_p, lp_target, accept,
+                            n_acc, accept_bits, t_nucleus_logit, n_finite, workspace, workspace_bytes, stream);
 }

@@ -79,7 +79,6 @@ class _StatusWorkspace:
 
     def status(self) -> int:
         """Synchronising read of the status word through the C ABI (asd_workspace_status)."""
-        import ctypes as C
         out = C.c_uint32(0)
         B.check("asd_workspace_status", _lib().asd_workspace_status(self.buf.data_ptr(), C.addressof(out), _stream()))
         return int(out.value)
@@ -120,6 +119,21 @@ class VerifyResult:
     accept_bits: torch.Tensor  # [B]  i64 (bit k = accept[b,k])
 
 
+@dataclass
+class NucleusVerifyResult(VerifyResult):
+    t_nucleus_logit: torch.Tensor = None   # [B,K] f32  x* of each target row (raw score units; -inf: no truncation)
+    n_finite: torch.Tensor = None          # [B]   i32  leading positions with a finite lp_target (the stop rule's n_valid)
+
+
+def _verify_out(Bv: int, K: int, dev, cls=VerifyResult):
+    """Fresh outputs of a verify call: the four tensors of VerifyResult, the six of NucleusVerifyResult."""
+    t = [torch.empty((Bv, K), dtype=torch.float32, device=dev), torch.empty((Bv, K), dtype=torch.uint8, device=dev),
+         torch.empty((Bv,), dtype=torch.int32, device=dev), torch.empty((Bv,), dtype=torch.int64, device=dev)]
+    if cls is NucleusVerifyResult:
+        t += [torch.empty((Bv, K), dtype=torch.float32, device=dev), torch.empty((Bv,), dtype=torch.int32, device=dev)]
+    return cls(*t)
+
+
 def _logits_2d(logits: torch.Tensor, Bv: int, K: int) -> Tuple[int, int, int]:
     if logits.dtype not in _DTYPE_CODE:
         raise ValueError(f"logits dtype {logits.dtype} unsupported (f32 / bf16 / f16)")
@@ -149,10 +163,7 @@ def verify_accept(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tenso
     V, ld, ptr = _logits_2d(logits, Bv, K)
     dev = logits.device
     if out is None:
-        out = VerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                           torch.empty((Bv, K), dtype=torch.uint8, device=dev),
-                           torch.empty((Bv,), dtype=torch.int32, device=dev),
-                           torch.empty((Bv,), dtype=torch.int64, device=dev))
+        out = _verify_out(Bv, K, dev)
     opt = B.verify_options(inv_temperature, splits, threads, unroll, nontemporal)
     rc = _lib().asd_verify_accept_ex(
         ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
@@ -164,10 +175,23 @@ def verify_accept(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tenso
     return out
 
 
-@dataclass
-class NucleusVerifyResult(VerifyResult):
-    t_nucleus_logit: torch.Tensor = None   # [B,K] f32  x* of each target row (raw score units; -inf: no truncation)
-    n_finite: torch.Tensor = None          # [B]   i32  leading positions with a finite lp_target (the stop rule's n_valid)
+def _verify_truncated(entry: str, logits, tok, lp_draft, u, workspace, inv_temperature, truncation: tuple, out):
+    """The body of verify_accept_top_p / verify_accept_top_k: `entry` is the C entry point, `truncation` its arguments between
+    inv_temperature and the outputs."""
+    Bv, K = tok.shape
+    V, ld, ptr = _logits_2d(logits, Bv, K)
+    if out is None:
+        out = _verify_out(Bv, K, logits.device, NucleusVerifyResult)
+    ws_ptr, ws_bytes = (None, 0) if workspace is None else (workspace.buf.data_ptr(), workspace.bytes)
+    rc = getattr(_lib(), entry)(
+        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
+        _dev(u, "u", torch.float32), Bv, K, V, float(inv_temperature), *truncation,
+        _dev(out.lp_target, "lp_target", torch.float32), _dev(out.accept, "accept", torch.uint8),
+        _dev(out.n_acc, "n_acc", torch.int32), _dev(out.accept_bits, "accept_bits", torch.int64),
+        _dev(out.t_nucleus_logit, "t_nucleus_logit", torch.float32), _dev(out.n_finite, "n_finite", torch.int32),
+        ws_ptr, ws_bytes, _stream())
+    B.check(entry, rc)
+    return out
 
 
 def verify_accept_top_p(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
@@ -176,26 +200,7 @@ def verify_accept_top_p(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
     """The verify step against the TARGET's nucleus (include/asd_hip.h: asd_verify_accept_top_p): lp_target = log p^N(tok)
     under softmax(logits / T) restricted to the top-p set of asd_draft_sample's select, -inf outside it.  top_p outside (0, 1)
     is asd_verify_accept_ex (the same bits; needs `workspace`); otherwise no workspace is used."""
-    Bv, K = tok.shape
-    V, ld, ptr = _logits_2d(logits, Bv, K)
-    dev = logits.device
-    if out is None:
-        out = NucleusVerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                                  torch.empty((Bv, K), dtype=torch.uint8, device=dev),
-                                  torch.empty((Bv,), dtype=torch.int32, device=dev),
-                                  torch.empty((Bv,), dtype=torch.int64, device=dev),
-                                  torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                                  torch.empty((Bv,), dtype=torch.int32, device=dev))
-    ws_ptr, ws_bytes = (None, 0) if workspace is None else (workspace.buf.data_ptr(), workspace.bytes)
-    rc = _lib().asd_verify_accept_top_p(
-        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
-        _dev(u, "u", torch.float32), Bv, K, V, float(inv_temperature), float(top_p),
-        _dev(out.lp_target, "lp_target", torch.float32), _dev(out.accept, "accept", torch.uint8),
-        _dev(out.n_acc, "n_acc", torch.int32), _dev(out.accept_bits, "accept_bits", torch.int64),
-        _dev(out.t_nucleus_logit, "t_nucleus_logit", torch.float32), _dev(out.n_finite, "n_finite", torch.int32),
-        ws_ptr, ws_bytes, _stream())
-    B.check("asd_verify_accept_top_p", rc)
-    return out
+    return _verify_truncated("asd_verify_accept_top_p", logits, tok, lp_draft, u, workspace, inv_temperature, (float(top_p),), out)
 
 
 def verify_accept_top_k(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
@@ -205,26 +210,8 @@ def verify_accept_top_k(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
     lp_target = log q(tok) over { x >= thr }, thr = max(x_k, x*_K) (t_nucleus_logit), -inf outside it.  HF
     generate(do_sample=True, ...) applies top_k = 50 unless told otherwise.  top_k <= 0 or >= V is verify_accept_top_p (the
     same bits; `workspace` only matters when top_p is off too)."""
-    Bv, K = tok.shape
-    V, ld, ptr = _logits_2d(logits, Bv, K)
-    dev = logits.device
-    if out is None:
-        out = NucleusVerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                                  torch.empty((Bv, K), dtype=torch.uint8, device=dev),
-                                  torch.empty((Bv,), dtype=torch.int32, device=dev),
-                                  torch.empty((Bv,), dtype=torch.int64, device=dev),
-                                  torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                                  torch.empty((Bv,), dtype=torch.int32, device=dev))
-    ws_ptr, ws_bytes = (None, 0) if workspace is None else (workspace.buf.data_ptr(), workspace.bytes)
-    rc = _lib().asd_verify_accept_top_k(
-        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
-        _dev(u, "u", torch.float32), Bv, K, V, float(inv_temperature), int(top_k), float(top_p),
-        _dev(out.lp_target, "lp_target", torch.float32), _dev(out.accept, "accept", torch.uint8),
-        _dev(out.n_acc, "n_acc", torch.int32), _dev(out.accept_bits, "accept_bits", torch.int64),
-        _dev(out.t_nucleus_logit, "t_nucleus_logit", torch.float32), _dev(out.n_finite, "n_finite", torch.int32),
-        ws_ptr, ws_bytes, _stream())
-    B.check("asd_verify_accept_top_k", rc)
-    return out
+    return _verify_truncated("asd_verify_accept_top_k", logits, tok, lp_draft, u, workspace, inv_temperature,
+                             (int(top_k), float(top_p)), out)
 
 
 def verify_accept_stats(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
@@ -236,10 +223,7 @@ def verify_accept_stats(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
     V, ld, ptr = _logits_2d(logits, Bv, K)
     dev = logits.device
     if out is None:
-        out = VerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                           torch.empty((Bv, K), dtype=torch.uint8, device=dev),
-                           torch.empty((Bv,), dtype=torch.int32, device=dev),
-                           torch.empty((Bv,), dtype=torch.int64, device=dev))
+        out = _verify_out(Bv, K, dev)
     max_lp = torch.empty((Bv, K), dtype=torch.float32, device=dev)
     ent = torch.empty((Bv, K), dtype=torch.float32, device=dev) if want_entropy else None
     rc = _lib().asd_verify_accept_stats(
@@ -272,10 +256,7 @@ def accept_from_partials(msg_all: torch.Tensor, lp_draft: torch.Tensor, u: torch
     assert three == 3
     dev = msg_all.device
     if out is None:
-        out = VerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                           torch.empty((Bv, K), dtype=torch.uint8, device=dev),
-                           torch.empty((Bv,), dtype=torch.int32, device=dev),
-                           torch.empty((Bv,), dtype=torch.int64, device=dev))
+        out = _verify_out(Bv, K, dev)
     rc = _lib().asd_accept_from_partials(_dev(msg_all, "msg_all", torch.float32), n_shards,
                                          _dev(lp_draft, "lp_draft", torch.float32), _dev(u, "u", torch.float32), Bv, K,
                                          float(inv_temperature), out.lp_target.data_ptr(), out.accept.data_ptr(), out.n_acc.data_ptr(),
@@ -335,10 +316,7 @@ class LmHeadVerifier:
             raise ValueError("hidden must be [B*K, D] of the weight's element type with contiguous rows")
         dev = h2.device
         if out is None:
-            out = VerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                               torch.empty((Bv, K), dtype=torch.uint8, device=dev),
-                               torch.empty((Bv,), dtype=torch.int32, device=dev),
-                               torch.empty((Bv,), dtype=torch.int64, device=dev))
+            out = _verify_out(Bv, K, dev)
         rc = _lib().asd_lm_head_verify_ex(h2.data_ptr(), h2.stride(0) if Bv * K > 1 else self.D, self._w_ptr,
                                           self._ld_w, self._dt, self.D, _dev(tok, "tok", torch.int32),
                                           _opt(lp_draft, "lp_draft", torch.float32), _opt(u, "u", torch.float32), Bv, K,
@@ -554,6 +532,18 @@ class StopResult:
     stats: Optional[torch.Tensor]     # [B,5] f64
 
 
+def _stop_out(Bv: int, dev, dp: bool, thr: bool, stats: bool) -> StopResult:
+    """Fresh outputs of the predictor / stop epilogue; only the score is always computed."""
+    u8 = lambda: torch.empty((Bv,), dtype=torch.uint8, device=dev)
+    return StopResult(torch.empty((Bv,), dtype=torch.float32, device=dev),
+                      torch.empty((Bv,), dtype=torch.int32, device=dev) if dp else None, u8() if dp else None,
+                      u8() if thr else None, torch.empty((Bv, 5), dtype=torch.float64, device=dev) if stats else None)
+
+
+def _stop_ptrs(res: StopResult):
+    return [None if t is None else t.data_ptr() for t in (res.score, res.k_star, res.stop, res.thr_stop, res.stats)]
+
+
 def predictor_stop(feat: torch.Tensor, packed_w: torch.Tensor, in_dim: int, hidden: int, *, stage_idx: int, L: int,
                    lp: Optional[torch.Tensor] = None, n_valid: Optional[torch.Tensor] = None, stats_col: int = -1,
                    risk_adjustment: bool = True, n_obs: int = 100, alpha: float = 1.0, beta: float = 1.0,
@@ -563,23 +553,16 @@ def predictor_stop(feat: torch.Tensor, packed_w: torch.Tensor, in_dim: int, hidd
     """Fused post-verify epilogue (asd_predictor_stop): stats -> features -> MLP -> Bayes -> DP / theta."""
     Bv = feat.shape[0]
     dev = feat.device
-    score = torch.empty((Bv,), dtype=torch.float32, device=dev)
-    dp = p_hist is not None and Cc is not None
-    k_star = torch.empty((Bv,), dtype=torch.int32, device=dev) if dp else None
-    stop = torch.empty((Bv,), dtype=torch.uint8, device=dev) if dp else None
-    thr = torch.empty((Bv,), dtype=torch.uint8, device=dev) if theta is not None else None
-    stats = torch.empty((Bv, 5), dtype=torch.float64, device=dev) if want_stats else None
+    res = _stop_out(Bv, dev, p_hist is not None and Cc is not None, theta is not None, want_stats)
     K = 0 if lp is None else lp.shape[1]
     rc = _lib().asd_predictor_stop(
         _opt(lp, "lp", torch.float32), (lp.stride(0) if lp is not None and Bv else K), _opt(n_valid, "n_valid", torch.int32),
         K, _dev(feat, "feat", torch.float32), feat.stride(0) if Bv else in_dim, stats_col,
         _dev(packed_w, "packed_w", torch.float32), in_dim, hidden, int(bool(risk_adjustment)), int(n_obs), float(alpha),
         float(beta), _opt(p_hist, "p_hist", torch.float64), _opt(Cc, "C", torch.float64), float(lam), L, stage_idx,
-        int(bool(prefix_rule)), _opt(theta, "theta", torch.float64), Bv, score.data_ptr(),
-        None if k_star is None else k_star.data_ptr(), None if stop is None else stop.data_ptr(),
-        None if thr is None else thr.data_ptr(), None if stats is None else stats.data_ptr(), _stream())
+        int(bool(prefix_rule)), _opt(theta, "theta", torch.float64), Bv, *_stop_ptrs(res), _stream())
     B.check("asd_predictor_stop", rc)
-    return StopResult(score, k_star, stop, thr, stats)
+    return res
 
 
 def verify_accept_fused(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
@@ -595,16 +578,8 @@ def verify_accept_fused(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
     V, ld, ptr = _logits_2d(logits, Bv, K)
     dev = logits.device
     if out is None:
-        out = VerifyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev),
-                           torch.empty((Bv, K), dtype=torch.uint8, device=dev),
-                           torch.empty((Bv,), dtype=torch.int32, device=dev),
-                           torch.empty((Bv,), dtype=torch.int64, device=dev))
-    score = torch.empty((Bv,), dtype=torch.float32, device=dev)
-    dp = p_hist is not None and Cc is not None
-    k_star = torch.empty((Bv,), dtype=torch.int32, device=dev) if dp else None
-    stop = torch.empty((Bv,), dtype=torch.uint8, device=dev) if dp else None
-    thr = torch.empty((Bv,), dtype=torch.uint8, device=dev) if theta is not None else None
-    stats = torch.empty((Bv, 5), dtype=torch.float64, device=dev) if want_stats else None
+        out = _verify_out(Bv, K, dev)
+    res = _stop_out(Bv, dev, p_hist is not None and Cc is not None, theta is not None, want_stats)
     opt = B.verify_options(inv_temperature)
     rc = _lib().asd_verify_accept_fused_ex(
         ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
@@ -613,11 +588,9 @@ def verify_accept_fused(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
         _dev(feat, "feat", torch.float32), feat.stride(0) if Bv else in_dim, stats_col,
         _dev(packed_w, "packed_w", torch.float32), in_dim, hidden, int(bool(risk_adjustment)), int(n_obs), float(alpha),
         float(beta), _opt(p_hist, "p_hist", torch.float64), _opt(Cc, "C", torch.float64), float(lam), L, stage_idx,
-        int(bool(prefix_rule)), _opt(theta, "theta", torch.float64), score.data_ptr(),
-        None if k_star is None else k_star.data_ptr(), None if stop is None else stop.data_ptr(),
-        None if thr is None else thr.data_ptr(), None if stats is None else stats.data_ptr(), C.addressof(opt), _stream())
+        int(bool(prefix_rule)), _opt(theta, "theta", torch.float64), *_stop_ptrs(res), C.addressof(opt), _stream())
     B.check("asd_verify_accept_fused_ex", rc)
-    return out, StopResult(score, k_star, stop, thr, stats)
+    return out, res
 
 
 def _rows(t: torch.Tensor, name: str) -> Tuple[int, int]:
@@ -640,12 +613,9 @@ class ResidualSampler(_StatusWorkspace):
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device or torch.device("cuda"))
         self.reset()
 
-    def __call__(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
-                 bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0,
-                 out: Optional[torch.Tensor] = None, d_threshold: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """t_logits / d_logits: [B,K,V]; bonus_logits: [B,V] or None; n_acc: [B] i32; r: [B] f32 -> token [B] i32.
-        d_threshold: [B,K] f32 nucleus thresholds of the draft rows (DraftSampler's `thr`) when the drafts were
-        drawn with top-p (asd_residual_sample_ex); None = untruncated drafts."""
+    def _sample(self, entry: str, t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out, scalars=(), **thresholds):
+        """The body of __call__ / top_p / top_k: `entry` is the C entry point; `scalars`, then the optional [B,K] `thresholds`
+        (in the entry point's order), are its arguments between inv_temperature and the token."""
         Bv, K, V = t_logits.shape
         if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
             raise ValueError("t_logits and d_logits must have the same shape and dtype")
@@ -654,14 +624,24 @@ class ResidualSampler(_StatusWorkspace):
         bp, ldb = (None, V) if bonus_logits is None else _rows(bonus_logits, "bonus_logits")
         if out is None:
             out = torch.empty((Bv,), dtype=torch.int32, device=t_logits.device)
-        if d_threshold is not None and tuple(d_threshold.shape) != (Bv, K):
-            raise ValueError("d_threshold must be [B, K]")
-        rc = _lib().asd_residual_sample_ex(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype],
-                                           _dev(n_acc, "n_acc", torch.int32), _dev(r, "r", torch.float32), Bv, K, V,
-                                           float(inv_temperature), _opt(d_threshold, "d_threshold", torch.float32),
-                                           out.data_ptr(), self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_residual_sample_ex", rc)
+        for name, t in thresholds.items():
+            if t is not None and tuple(t.shape) != (Bv, K):
+                raise ValueError(f"{name} must be [B, K]")
+        rc = getattr(_lib(), entry)(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype], _dev(n_acc, "n_acc", torch.int32),
+                                    _dev(r, "r", torch.float32), Bv, K, V, float(inv_temperature), *scalars,
+                                    *[_opt(t, name, torch.float32) for name, t in thresholds.items()], out.data_ptr(),
+                                    self.buf.data_ptr(), self.bytes, _stream())
+        B.check(entry, rc)
         return out
+
+    def __call__(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
+                 bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0,
+                 out: Optional[torch.Tensor] = None, d_threshold: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """t_logits / d_logits: [B,K,V]; bonus_logits: [B,V] or None; n_acc: [B] i32; r: [B] f32 -> token [B] i32.
+        d_threshold: [B,K] f32 nucleus thresholds of the draft rows (DraftSampler's `thr`) when the drafts were
+        drawn with top-p (asd_residual_sample_ex); None = untruncated drafts."""
+        return self._sample("asd_residual_sample_ex", t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out,
+                            d_threshold=d_threshold)
 
     def top_p(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
               bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0, *, top_p: float,
@@ -669,24 +649,8 @@ class ResidualSampler(_StatusWorkspace):
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The committed token against the TARGET's nucleus (asd_residual_sample_top_p): t_threshold [B,K] = the verify's
         t_nucleus_logit; the bonus rows' thresholds are found by the sampler.  top_p outside (0, 1) = __call__ (same bits)."""
-        Bv, K, V = t_logits.shape
-        if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
-            raise ValueError("t_logits and d_logits must have the same shape and dtype")
-        tp, ldt = _rows(t_logits, "t_logits")
-        dp, ldd = _rows(d_logits, "d_logits")
-        bp, ldb = (None, V) if bonus_logits is None else _rows(bonus_logits, "bonus_logits")
-        if out is None:
-            out = torch.empty((Bv,), dtype=torch.int32, device=t_logits.device)
-        for name, t in (("t_threshold", t_threshold), ("d_threshold", d_threshold)):
-            if t is not None and tuple(t.shape) != (Bv, K):
-                raise ValueError(f"{name} must be [B, K]")
-        rc = _lib().asd_residual_sample_top_p(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype],
-                                              _dev(n_acc, "n_acc", torch.int32), _dev(r, "r", torch.float32), Bv, K, V,
-                                              float(inv_temperature), float(top_p), _opt(t_threshold, "t_threshold", torch.float32),
-                                              _opt(d_threshold, "d_threshold", torch.float32), out.data_ptr(),
-                                              self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_residual_sample_top_p", rc)
-        return out
+        return self._sample("asd_residual_sample_top_p", t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out,
+                            (float(top_p),), t_threshold=t_threshold, d_threshold=d_threshold)
 
     def top_k(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
               bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0, *, top_k: int, top_p: float = 1.0,
@@ -695,25 +659,8 @@ class ResidualSampler(_StatusWorkspace):
         """The committed token against the target's top-k + top-p set (asd_residual_sample_top_k): t_threshold [B,K] = the
         thresholds of verify_accept_top_k; the bonus rows' are found by the sampler with the same select.  top_k <= 0 or
         >= V is top_p(...) (the same bits)."""
-        Bv, K, V = t_logits.shape
-        if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
-            raise ValueError("t_logits and d_logits must have the same shape and dtype")
-        tp, ldt = _rows(t_logits, "t_logits")
-        dp, ldd = _rows(d_logits, "d_logits")
-        bp, ldb = (None, V) if bonus_logits is None else _rows(bonus_logits, "bonus_logits")
-        if out is None:
-            out = torch.empty((Bv,), dtype=torch.int32, device=t_logits.device)
-        for name, t in (("t_threshold", t_threshold), ("d_threshold", d_threshold)):
-            if t is not None and tuple(t.shape) != (Bv, K):
-                raise ValueError(f"{name} must be [B, K]")
-        rc = _lib().asd_residual_sample_top_k(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype],
-                                              _dev(n_acc, "n_acc", torch.int32), _dev(r, "r", torch.float32), Bv, K, V,
-                                              float(inv_temperature), int(top_k), float(top_p),
-                                              _opt(t_threshold, "t_threshold", torch.float32),
-                                              _opt(d_threshold, "d_threshold", torch.float32), out.data_ptr(),
-                                              self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_residual_sample_top_k", rc)
-        return out
+        return self._sample("asd_residual_sample_top_k", t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out,
+                            (int(top_k), float(top_p)), t_threshold=t_threshold, d_threshold=d_threshold)
 
 
 @dataclass
@@ -735,8 +682,9 @@ class DraftSampler(_StatusWorkspace):
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device or torch.device("cuda"))
         self.reset()
 
-    def __call__(self, logits: torch.Tensor, r: torch.Tensor, inv_temperature: float = 1.0, top_p: float = 1.0,
-                 out: Optional[DraftDraw] = None) -> DraftDraw:
+    def _draw(self, entry: str, logits, r, inv_temperature, truncation: tuple, out) -> DraftDraw:
+        """The body of __call__ / top_k: `entry` is the C entry point, `truncation` its arguments between inv_temperature and
+        the outputs."""
         if logits.dim() != 2 or logits.dtype != self.dtype or not logits.is_cuda or logits.stride(1) != 1:
             raise ValueError(f"logits must be a [B, V] {self.dtype} CUDA tensor with unit stride along V")
         Bv, V = logits.shape
@@ -747,31 +695,20 @@ class DraftSampler(_StatusWorkspace):
             out = DraftDraw(torch.empty((Bv,), dtype=torch.int32, device=dev),
                             torch.empty((Bv,), dtype=torch.float32, device=dev),
                             torch.empty((Bv,), dtype=torch.float32, device=dev))
-        rc = _lib().asd_draft_sample(logits.data_ptr(), logits.stride(0) if Bv > 1 else V, _DTYPE_CODE[logits.dtype],
-                                     _dev(r, "r", torch.float32), Bv, V, float(inv_temperature), float(top_p),
-                                     _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
-                                     _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_draft_sample", rc)
+        rc = getattr(_lib(), entry)(logits.data_ptr(), logits.stride(0) if Bv > 1 else V, _DTYPE_CODE[logits.dtype],
+                                    _dev(r, "r", torch.float32), Bv, V, float(inv_temperature), *truncation,
+                                    _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
+                                    _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
+        B.check(entry, rc)
         return out
+
+    def __call__(self, logits: torch.Tensor, r: torch.Tensor, inv_temperature: float = 1.0, top_p: float = 1.0,
+                 out: Optional[DraftDraw] = None) -> DraftDraw:
+        return self._draw("asd_draft_sample", logits, r, inv_temperature, (float(top_p),), out)
 
     def top_k(self, logits: torch.Tensor, r: torch.Tensor, inv_temperature: float = 1.0, *, top_k: int, top_p: float = 1.0,
               out: Optional[DraftDraw] = None) -> DraftDraw:
         """The proposal under HF's Temperature -> TopK -> TopP chain (asd_draft_sample_top_k): thr = max(x_k, x*_K), the
         threshold of the top-p select taken over the top-k set.  HF generate(do_sample=True, ...) applies top_k = 50 unless
         told otherwise.  top_k <= 0 or >= V is __call__ (the same bits); otherwise one workgroup per row, the workspace unused."""
-        if logits.dim() != 2 or logits.dtype != self.dtype or not logits.is_cuda or logits.stride(1) != 1:
-            raise ValueError(f"logits must be a [B, V] {self.dtype} CUDA tensor with unit stride along V")
-        Bv, V = logits.shape
-        if Bv > self.B or V != self.V:
-            raise ValueError(f"sampler was sized for B<={self.B}, V={self.V}")
-        dev = logits.device
-        if out is None:
-            out = DraftDraw(torch.empty((Bv,), dtype=torch.int32, device=dev),
-                            torch.empty((Bv,), dtype=torch.float32, device=dev),
-                            torch.empty((Bv,), dtype=torch.float32, device=dev))
-        rc = _lib().asd_draft_sample_top_k(logits.data_ptr(), logits.stride(0) if Bv > 1 else V, _DTYPE_CODE[logits.dtype],
-                                           _dev(r, "r", torch.float32), Bv, V, float(inv_temperature), int(top_k), float(top_p),
-                                           _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
-                                           _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_draft_sample_top_k", rc)
-        return out
+        return self._draw("asd_draft_sample_top_k", logits, r, inv_temperature, (int(top_k), float(top_p)), out)
