@@ -12,13 +12,9 @@
 
 namespace asd {
 
-inline int launch_status() {
-    return hipGetLastError() == hipSuccess ? ASD_OK : ASD_ERR_HIP;
-}
+inline int launch_status() { return hipGetLastError() == hipSuccess ? ASD_OK : ASD_ERR_HIP; }
 
-inline bool aligned_to(const void* p, size_t a) {
-    return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
+inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -34,7 +30,7 @@ inline int dtype_size(int dtype) {
 // number of CUs of the CURRENT device (cached per device id; the query is slow)
 int current_device_cus();
 
-// ---- shared by the launchers of the sampling steps (draft_sample.hip, verify_nucleus.hip, residual_sample.hip) ----
+// ---- shared by the launchers of the sampling steps, the verify step (verify_accept.hip) and the lm_head / linear kernels ----
 
 // f(std::integral_constant<int, ASD_DTYPE_*>{}): the kernels take the element type as a template argument.  Whatever is not
 // BF16 or F16 takes the F32 branch (the callers have rejected unknown dtypes through dtype_size before).
@@ -46,6 +42,9 @@ auto dispatch_dtype(int dtype, F&& f) {
         default: return f(std::integral_constant<int, ASD_DTYPE_F32>{});
     }
 }
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag that the kernels take as a template argument
+template <class F>
+auto dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // a logits row as the sampling kernels stream it: 16-byte vectors, tiles of 64 vectors
 struct RowGeom {

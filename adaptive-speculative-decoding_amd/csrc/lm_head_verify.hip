@@ -1259,16 +1259,14 @@ ASD_EXPORT size_t asd_lm_head_verify_workspace_bytes(int B, int K, int V) {
 }
 
 namespace {
-template <int NTW, bool F16>
-void launch_tile_t(int h_passes, dim3 grid, hipStream_t st, const LmHeadParams& p) {
-    if (h_passes == 1) hipLaunchKernelGGL((k_lm_head_tile<NTW, 1, F16>), grid, dim3(kThreads), 0, st, p);
-    else if (h_passes == 2) hipLaunchKernelGGL((k_lm_head_tile<NTW, 2, F16>), grid, dim3(kThreads), 0, st, p);
-    else hipLaunchKernelGGL((k_lm_head_tile<NTW, 4, F16>), grid, dim3(kThreads), 0, st, p);
-}
 template <int NTW>
 void launch_tile(bool f16, int h_passes, dim3 grid, hipStream_t st, const LmHeadParams& p) {
-    if (f16) launch_tile_t<NTW, true>(h_passes, grid, st, p);
-    else launch_tile_t<NTW, false>(h_passes, grid, st, p);
+    dispatch_bool(f16, [&](auto f) {
+        constexpr bool F16 = decltype(f)::value;
+        if (h_passes == 1) hipLaunchKernelGGL((k_lm_head_tile<NTW, 1, F16>), grid, dim3(kThreads), 0, st, p);
+        else if (h_passes == 2) hipLaunchKernelGGL((k_lm_head_tile<NTW, 2, F16>), grid, dim3(kThreads), 0, st, p);
+        else hipLaunchKernelGGL((k_lm_head_tile<NTW, 4, F16>), grid, dim3(kThreads), 0, st, p);
+    });
 }
 
 struct LmHeadCall {
@@ -1280,7 +1278,7 @@ struct LmHeadCall {
 
 int lm_head_launch(const LmHeadCall& c) {
     if (c.B < 0 || c.K < 0 || c.V < 1 || c.D < 1 || c.v_offset < 0) return ASD_ERR_INVALID_ARG;
-    if (!(c.inv_temperature > 0.0f) || !(c.inv_temperature < 3.0e38f)) return ASD_ERR_INVALID_ARG;
+    if (!valid_inv_temperature(c.inv_temperature)) return ASD_ERR_INVALID_ARG;
     if (c.B == 0 || c.K == 0) return ASD_OK;
     if (c.K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
     if ((c.dtype != ASD_DTYPE_BF16 && c.dtype != ASD_DTYPE_F16) || c.D % kSuper != 0 || c.v_offset + c.V >= (1ll << 31))
@@ -1322,7 +1320,7 @@ int lm_head_launch(const LmHeadCall& c) {
     p.hidden = c.hidden; p.ld_h = c.ld_h; p.weight = c.weight; p.ld_w = c.ld_w;
     p.D = c.D; p.M = static_cast<int>(M); p.V = c.V; p.tok = c.tok;
     p.v_offset = static_cast<int>(c.v_offset);
-    p.c2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(c.inv_temperature));
+    p.c2 = log2_scale(c.inv_temperature);
     p.msg = static_cast<float*>(c.workspace);
     p.m_blocks = static_cast<int>(m_blocks);
     p.packed = packed ? 1 : 0;
@@ -1330,45 +1328,35 @@ int lm_head_launch(const LmHeadCall& c) {
     p.need_argmax = (c.argmax_out != nullptr || c.greedy) ? 1 : 0;
     hipStream_t st = static_cast<hipStream_t>(c.stream);
     const int hp = M <= 64 ? 1 : (M <= 128 ? 2 : 4);
-    if (M <= kSkRows) {   // the stream-shaped kernel: every 256-column block, one record per block
+    // the acceptance tests over the records of the `records` column blocks that wrote one
+    auto accept_from_blocks = [&](int64_t records) {
+        hipLaunchKernelGGL(k_accept_from_blocks, dim3(c.B), dim3(64 * (c.K < 16 ? c.K : 16)), 0, st, p.msg,
+                           static_cast<int>(records), c.lp_draft, c.u, c.tok, c.greedy ? 1 : 0, c.B, c.K, p.c2,
+                           c.lp_target, c.accept, c.n_acc, c.accept_bits, c.argmax_out, c.emit);
+        return launch_status();
+    };
+    // Three forms run over EVERY 256-column block, one record per block:
+    //   skinny  M <= 64         the stream-shaped kernel
+    //   tall    256 < M <= 288  ONE tall row block (1 x 8 waves of 9 x 1 tiles)
+    //   quad    M > 288         several row blocks per weight tile: MFMA-bound, the 4-wave kernel
+    // (Cutting the quad form's tiles of the last, partial round of the CUs into reduction slices -- V = 152064, M = 1024: 2376
+    // tiles = 9.28 rounds -- was built and measured: no gain at D = 8192, +4 % at D = 3584.  The 72 tiles of that round run
+    // faster than a tile of a full round, and a second launch + the slab traffic cost what the slices save.)
+    const bool skinny = M <= kSkRows, tall = M > kBM && M <= 288;
+    if (skinny || tall || m_blocks >= 2) {
         const int64_t blocks = (static_cast<int64_t>(c.V) + 255) / 256;
         p.col0 = 0;
         p.unit0 = 0;
         p.n_blocks = static_cast<int>(blocks);
-        if (f16) hipLaunchKernelGGL(k_lm_head_skinny<true>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL(k_lm_head_skinny<false>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, st, p);
-        hipLaunchKernelGGL(k_accept_from_blocks, dim3(c.B), dim3(64 * (c.K < 16 ? c.K : 16)), 0, st, p.msg,
-                           static_cast<int>(blocks), c.lp_draft, c.u, c.tok, c.greedy ? 1 : 0, c.B, c.K, p.c2,
-                           c.lp_target, c.accept, c.n_acc, c.accept_bits, c.argmax_out, c.emit);
-        return launch_status();
-    }
-    if (M > kBM && M <= 288) {   // ONE tall row block (1 x 8 waves of 9 x 1 tiles) over every 256-column block
-        const int64_t blocks = (static_cast<int64_t>(c.V) + 255) / 256;
-        p.col0 = 0;
-        p.unit0 = 0;
-        p.m_blocks = 1;
-        p.n_blocks = static_cast<int>(blocks);
-        if (f16) hipLaunchKernelGGL((k_lm_head_tall<true, 9>), dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL((k_lm_head_tall<false, 9>), dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, st, p);
-        hipLaunchKernelGGL(k_accept_from_blocks, dim3(c.B), dim3(64 * (c.K < 16 ? c.K : 16)), 0, st, p.msg,
-                           static_cast<int>(blocks), c.lp_draft, c.u, c.tok, c.greedy ? 1 : 0, c.B, c.K, p.c2,
-                           c.lp_target, c.accept, c.n_acc, c.accept_bits, c.argmax_out, c.emit);
-        return launch_status();
-    }
-    if (m_blocks >= 2) {   // several row blocks per weight tile: MFMA-bound, the 4-wave kernel over every 256-column block
-        const int64_t blocks = (static_cast<int64_t>(c.V) + 255) / 256;
-        // (Cutting the tiles of the last, partial round of the CUs into reduction slices -- V = 152064, M = 1024: 2376 tiles =
-        // 9.28 rounds -- was built and measured: no gain at D = 8192, +4 % at D = 3584.  The 72 tiles of that round run
-        // faster than a tile of a full round, and a second launch + the slab traffic cost what the slices save.)
-        p.col0 = 0;
-        p.unit0 = 0;
-        p.n_blocks = static_cast<int>(blocks);
-        if (f16) hipLaunchKernelGGL(k_lm_head_quad<true>, dim3(static_cast<unsigned>(blocks * m_blocks)), dim3(kQThreads), 0, st, p);
-        else hipLaunchKernelGGL(k_lm_head_quad<false>, dim3(static_cast<unsigned>(blocks * m_blocks)), dim3(kQThreads), 0, st, p);
-        hipLaunchKernelGGL(k_accept_from_blocks, dim3(c.B), dim3(64 * (c.K < 16 ? c.K : 16)), 0, st, p.msg,
-                           static_cast<int>(blocks), c.lp_draft, c.u, c.tok, c.greedy ? 1 : 0, c.B, c.K, p.c2,
-                           c.lp_target, c.accept, c.n_acc, c.accept_bits, c.argmax_out, c.emit);
-        return launch_status();
+        if (tall) p.m_blocks = 1;
+        dispatch_bool(f16, [&](auto f) {
+            constexpr bool F16 = decltype(f)::value;
+            const dim3 grid(static_cast<unsigned>(blocks));
+            if (skinny) hipLaunchKernelGGL(k_lm_head_skinny<F16>, grid, dim3(kThreads), 0, st, p);
+            else if (tall) hipLaunchKernelGGL((k_lm_head_tall<F16, 9>), grid, dim3(kThreads), 0, st, p);
+            else hipLaunchKernelGGL(k_lm_head_quad<F16>, dim3(static_cast<unsigned>(blocks * m_blocks)), dim3(kQThreads), 0, st, p);
+        });
+        return accept_from_blocks(blocks);
     }
     if (wide > 0) {
         p.col0 = 0;
@@ -1393,10 +1381,7 @@ int lm_head_launch(const LmHeadCall& c) {
         p.n_blocks = static_cast<int>(narrow);
         launch_tile<2>(f16, hp, dim3(static_cast<unsigned>(narrow * m_blocks)), st, p);
     }
-    hipLaunchKernelGGL(k_accept_from_blocks, dim3(c.B), dim3(64 * (c.K < 16 ? c.K : 16)), 0, st, p.msg,
-                       static_cast<int>(wide + narrow), c.lp_draft, c.u, c.tok, c.greedy ? 1 : 0, c.B, c.K, p.c2,
-                       c.lp_target, c.accept, c.n_acc, c.accept_bits, c.argmax_out, c.emit);
-    return launch_status();
+    return accept_from_blocks(wide + narrow);
 }
 }  // namespace
 
@@ -1597,34 +1582,22 @@ int linear_run(const void* x, int64_t ld_x, const void* w, int64_t ld_w, const v
     p.out = y; p.ld_out = ld_y; p.bias = bias; p.residual = residual; p.ld_res = ld_res;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(static_cast<unsigned>(pl.units * pl.k_slices));
-    if (pl.kind == 0) {
-        if (f16) hipLaunchKernelGGL((k_lm_head_skinny<true, true>), grid, dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL((k_lm_head_skinny<false, true>), grid, dim3(kThreads), 0, st, p);
-    } else if (pl.kind == 1) {
-        if (f16) hipLaunchKernelGGL(k_linear_tile<true>, grid, dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL(k_linear_tile<false>, grid, dim3(kThreads), 0, st, p);
-    } else if (pl.kind == 3) {
-        const int mt = (M + 31) / 32;
-        if (f16) {
-            if (mt <= 7) hipLaunchKernelGGL((k_linear_tall<true, 7>), grid, dim3(kThreads), 0, st, p);
-            else if (mt == 8) hipLaunchKernelGGL((k_linear_tall<true, 8>), grid, dim3(kThreads), 0, st, p);
-            else hipLaunchKernelGGL((k_linear_tall<true, 9>), grid, dim3(kThreads), 0, st, p);
-        } else {
-            if (mt <= 7) hipLaunchKernelGGL((k_linear_tall<false, 7>), grid, dim3(kThreads), 0, st, p);
-            else if (mt == 8) hipLaunchKernelGGL((k_linear_tall<false, 8>), grid, dim3(kThreads), 0, st, p);
-            else hipLaunchKernelGGL((k_linear_tall<false, 9>), grid, dim3(kThreads), 0, st, p);
-        }
-    } else {
-        if (f16) hipLaunchKernelGGL((k_lm_head_quad<true, true>), grid, dim3(kQThreads), 0, st, p);
-        else hipLaunchKernelGGL((k_lm_head_quad<false, true>), grid, dim3(kQThreads), 0, st, p);
-    }
     if (k_slices_out) *k_slices_out = pl.k_slices;
-    if (pl.k_slices > 1 && !k_slices_out) {
-        const int64_t n_threads = static_cast<int64_t>(M) * (N / 4);
-        const dim3 rgrid(static_cast<unsigned>((n_threads + 255) / 256));
-        if (f16) hipLaunchKernelGGL(k_linear_reduce<true>, rgrid, dim3(256), 0, st, p.slabs, pl.k_slices, M, N, bias, residual, ld_res, y, ld_y);
-        else hipLaunchKernelGGL(k_linear_reduce<false>, rgrid, dim3(256), 0, st, p.slabs, pl.k_slices, M, N, bias, residual, ld_res, y, ld_y);
-    }
+    dispatch_bool(f16, [&](auto f) {
+        constexpr bool F16 = decltype(f)::value;
+        const int mt = (M + 31) / 32;     // kind 3: the 32-row tiles of the one tall row block
+        if (pl.kind == 0) hipLaunchKernelGGL((k_lm_head_skinny<F16, true>), grid, dim3(kThreads), 0, st, p);
+        else if (pl.kind == 1) hipLaunchKernelGGL(k_linear_tile<F16>, grid, dim3(kThreads), 0, st, p);
+        else if (pl.kind == 2) hipLaunchKernelGGL((k_lm_head_quad<F16, true>), grid, dim3(kQThreads), 0, st, p);
+        else if (mt <= 7) hipLaunchKernelGGL((k_linear_tall<F16, 7>), grid, dim3(kThreads), 0, st, p);
+        else if (mt == 8) hipLaunchKernelGGL((k_linear_tall<F16, 8>), grid, dim3(kThreads), 0, st, p);
+        else hipLaunchKernelGGL((k_linear_tall<F16, 9>), grid, dim3(kThreads), 0, st, p);
+        if (pl.k_slices > 1 && !k_slices_out) {
+            const int64_t n_threads = static_cast<int64_t>(M) * (N / 4);
+            const dim3 rgrid(static_cast<unsigned>((n_threads + 255) / 256));
+            hipLaunchKernelGGL(k_linear_reduce<F16>, rgrid, dim3(256), 0, st, p.slabs, pl.k_slices, M, N, bias, residual, ld_res, y, ld_y);
+        }
+    });
     return launch_status();
 }
 }  // namespace

@@ -813,35 +813,50 @@ Geometry choose_geometry(int R, int K, int V, int dtype, int cus, bool whole_row
 
 inline int own_row_of(const VerifyParams& p) { return (p.S == 1 && (p.mode == 1 || p.K <= kFastMaxK)) ? 1 : 0; }
 
-template <int DT, int THREADS, int UNROLL>
-void launch_nt(const VerifyParams& p, int64_t grid, hipStream_t st, int nt) {
-    if (nt)
-        hipLaunchKernelGGL((k_verify<DT, THREADS, UNROLL, true, false>), dim3(static_cast<uint32_t>(grid / p.S), static_cast<uint32_t>(p.S)), dim3(THREADS), 0, st,
-                           p.logits, p.tok, p.ld_row, p.V, p.K, p.S, p.scale2, own_row_of(p), p);
-    else
-        hipLaunchKernelGGL((k_verify<DT, THREADS, UNROLL, false, false>), dim3(static_cast<uint32_t>(grid / p.S), static_cast<uint32_t>(p.S)), dim3(THREADS), 0, st,
-                           p.logits, p.tok, p.ld_row, p.V, p.K, p.S, p.scale2, own_row_of(p), p);
+// THE launch of k_verify: one workgroup per (row, slice); the eight leading arguments are the preloaded scalars (see k_verify)
+template <int DT, int THREADS, int UNROLL, bool NT, bool FUSED, bool STATS = false, int EPI = 1>
+void launch_k(const VerifyParams& p, hipStream_t st) {
+    const dim3 grid(static_cast<uint32_t>(static_cast<int64_t>(p.B) * p.K), static_cast<uint32_t>(p.S));
+    hipLaunchKernelGGL((k_verify<DT, THREADS, UNROLL, NT, FUSED, STATS, EPI>), grid, dim3(THREADS), 0, st, p.logits, p.tok,
+                       p.ld_row, p.V, p.K, p.S, p.scale2, own_row_of(p), p);
 }
 
-template <int DT, int THREADS>
-int launch_unroll(const VerifyParams& p, int64_t grid, hipStream_t st, const Geometry& g) {
-    switch (g.unroll) {
-        case 2: launch_nt<DT, THREADS, 2>(p, grid, st, g.nt); return ASD_OK;
-        case 3: launch_nt<DT, THREADS, 3>(p, grid, st, g.nt); return ASD_OK;
-        case 4: launch_nt<DT, THREADS, 4>(p, grid, st, g.nt); return ASD_OK;
-        case 8: launch_nt<DT, THREADS, 8>(p, grid, st, g.nt); return ASD_OK;
-        default: return ASD_ERR_UNSUPPORTED;
-    }
-}
-
+// the plain route: lanes {256, 512, 1024} x KiB per tile {2, 3, 4, 8} x nontemporal loads {no, yes}, forced or the heuristic's
 template <int DT>
-int launch_threads(const VerifyParams& p, int64_t grid, hipStream_t st, const Geometry& g) {
+int launch_plain(const VerifyParams& p, hipStream_t st, const Geometry& g) {
+    auto with_threads = [&](auto threads) -> int {
+        auto with_unroll = [&](auto unroll) -> int {
+            dispatch_bool(g.nt != 0, [&](auto nt) {
+                launch_k<DT, decltype(threads)::value, decltype(unroll)::value, decltype(nt)::value, false>(p, st);
+            });
+            return ASD_OK;
+        };
+        switch (g.unroll) {
+            case 2: return with_unroll(std::integral_constant<int, 2>{});
+            case 3: return with_unroll(std::integral_constant<int, 3>{});
+            case 4: return with_unroll(std::integral_constant<int, 4>{});
+            case 8: return with_unroll(std::integral_constant<int, 8>{});
+            default: return ASD_ERR_UNSUPPORTED;
+        }
+    };
     switch (g.threads) {
-        case 256: return launch_unroll<DT, 256>(p, grid, st, g);
-        case 512: return launch_unroll<DT, 512>(p, grid, st, g);
-        case 1024: return launch_unroll<DT, 1024>(p, grid, st, g);
+        case 256: return with_threads(std::integral_constant<int, 256>{});
+        case 512: return with_threads(std::integral_constant<int, 512>{});
+        case 1024: return with_threads(std::integral_constant<int, 1024>{});
         default: return ASD_ERR_UNSUPPORTED;
     }
+}
+
+// the workspace: the sequences' ticket lines, then per sequence a region of K x splits granules (whole 256-byte blocks)
+struct WorkspaceLayout {
+    size_t ticket_bytes, region_bytes, total;
+};
+inline WorkspaceLayout workspace_layout(int B, int K, int splits) {
+    WorkspaceLayout w{};
+    w.ticket_bytes = round_up(static_cast<size_t>(B) * kTicketStride * sizeof(uint32_t), 256);
+    w.region_bytes = round_up(static_cast<size_t>(K) * splits * sizeof(uint64_t), 256);
+    w.total = w.ticket_bytes + w.region_bytes * static_cast<size_t>(B);
+    return w;
 }
 
 #ifdef ASD_TEST_HOOKS        // (process-global, not thread-safe: the TEST build of the library only)
@@ -882,72 +897,47 @@ int launch_verify(VerifyParams p, int dtype, void* workspace, size_t workspace_b
         return ASD_ERR_UNSUPPORTED;
     }
 
-    const size_t ticket_bytes = round_up(static_cast<size_t>(p.B) * kTicketStride * sizeof(uint32_t), 256);
-    const size_t region_bytes = round_up(static_cast<size_t>(p.K) * g.splits * sizeof(uint64_t), 256);
-    if (workspace_bytes < ticket_bytes + region_bytes * static_cast<size_t>(p.B)) return ASD_ERR_WORKSPACE;
+    const WorkspaceLayout w = workspace_layout(p.B, p.K, g.splits);
+    if (workspace_bytes < w.total) return ASD_ERR_WORKSPACE;
     p.S = g.splits;
     p.tickets = static_cast<uint32_t*>(workspace);
-    p.granules = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + ticket_bytes);
-    p.region = static_cast<uint32_t>(region_bytes / sizeof(uint64_t));
+    p.granules = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + w.ticket_bytes);
+    p.region = static_cast<uint32_t>(w.region_bytes / sizeof(uint64_t));
 
-    const int64_t grid = R * g.splits;
-    if (grid > INT32_MAX || static_cast<int64_t>(p.V) * g.splits > INT32_MAX) return ASD_ERR_UNSUPPORTED;
+    if (R * g.splits > INT32_MAX || static_cast<int64_t>(p.V) * g.splits > INT32_MAX) return ASD_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
     if (p.row_entropy) {   // the (m2, s, t) instantiation exists for one workgroup per row, 512 lanes x 3-KiB tiles
         if (g.splits != 1 || g.threads != 512 || g.unroll != 3 || p.K > kFastMaxK || p.fused || p.mode != 0) return ASD_ERR_UNSUPPORTED;
-        const dim3 gd(static_cast<uint32_t>(grid / p.S), static_cast<uint32_t>(p.S));
-#define ASD_LAUNCH_STATS(DT)                                                                                      \
-    hipLaunchKernelGGL((k_verify<DT, 512, 3, true, false, true>), gd, dim3(512), 0, st, p.logits, p.tok, p.ld_row, p.V, \
-                       p.K, p.S, p.scale2, own_row_of(p), p)
-        switch (dtype) {
-            case ASD_DTYPE_BF16: ASD_LAUNCH_STATS(ASD_DTYPE_BF16); break;
-            case ASD_DTYPE_F16: ASD_LAUNCH_STATS(ASD_DTYPE_F16); break;
-            default: ASD_LAUNCH_STATS(ASD_DTYPE_F32); break;
-        }
-#undef ASD_LAUNCH_STATS
+        dispatch_dtype(dtype, [&](auto dt) { launch_k<decltype(dt)::value, 512, 3, true, false, true>(p, st); });
         return launch_status();
     }
     if (p.fused) {   // the in-kernel epilogue is instantiated for the two geometries the heuristic uses: rows >= CUs
                      // (512 lanes x 3-KiB tiles, one workgroup per row) and rows < CUs (512 x 2 KiB, split rows)
-        const dim3 gd(static_cast<uint32_t>(grid / p.S), static_cast<uint32_t>(p.S));
         const bool wide = (g.threads == 512 && g.unroll == 3);
         if (!wide && !(g.threads == 512 && g.unroll == 2)) return ASD_ERR_UNSUPPORTED;
         if (p.fused == 2) {   // the 256 -> 128 -> 1 epilogue: one workgroup per row, 512 lanes x 3-KiB tiles only
             if (g.splits != 1 || !wide || !own_row_of(p)) return ASD_ERR_UNSUPPORTED;
-#define ASD_LAUNCH_FUSED2(DT)                                                                                     \
-    hipLaunchKernelGGL((k_verify<DT, 512, 3, true, true, false, 2>), gd, dim3(512), 0, st, p.logits, p.tok, p.ld_row, p.V, \
-                       p.K, p.S, p.scale2, own_row_of(p), p)
-            switch (dtype) {
-                case ASD_DTYPE_BF16: ASD_LAUNCH_FUSED2(ASD_DTYPE_BF16); break;
-                case ASD_DTYPE_F16: ASD_LAUNCH_FUSED2(ASD_DTYPE_F16); break;
-                default: ASD_LAUNCH_FUSED2(ASD_DTYPE_F32); break;
-            }
-#undef ASD_LAUNCH_FUSED2
+            dispatch_dtype(dtype, [&](auto dt) { launch_k<decltype(dt)::value, 512, 3, true, true, false, 2>(p, st); });
             return launch_status();
         }
-#define ASD_LAUNCH_FUSED(DT)                                                                                      \
-    do {                                                                                                          \
-        if (wide) hipLaunchKernelGGL((k_verify<DT, 512, 3, true, true>), gd, dim3(512), 0, st, p.logits, p.tok, p.ld_row, \
-                                     p.V, p.K, p.S, p.scale2, own_row_of(p), p);                                  \
-        else hipLaunchKernelGGL((k_verify<DT, 512, 2, true, true>), gd, dim3(512), 0, st, p.logits, p.tok, p.ld_row,  \
-                                p.V, p.K, p.S, p.scale2, own_row_of(p), p);                                       \
-    } while (0)
-        switch (dtype) {
-            case ASD_DTYPE_BF16: ASD_LAUNCH_FUSED(ASD_DTYPE_BF16); break;
-            case ASD_DTYPE_F16: ASD_LAUNCH_FUSED(ASD_DTYPE_F16); break;
-            default: ASD_LAUNCH_FUSED(ASD_DTYPE_F32); break;
-        }
-#undef ASD_LAUNCH_FUSED
+        dispatch_dtype(dtype, [&](auto dt) {
+            if (wide) launch_k<decltype(dt)::value, 512, 3, true, true>(p, st);
+            else launch_k<decltype(dt)::value, 512, 2, true, true>(p, st);
+        });
         return launch_status();
     }
-    switch (dtype) {
-        case ASD_DTYPE_BF16: rc = launch_threads<ASD_DTYPE_BF16>(p, grid, st, g); break;
-        case ASD_DTYPE_F16: rc = launch_threads<ASD_DTYPE_F16>(p, grid, st, g); break;
-        default: rc = launch_threads<ASD_DTYPE_F32>(p, grid, st, g); break;
-    }
+    const int rc = dispatch_dtype(dtype, [&](auto dt) { return launch_plain<decltype(dt)::value>(p, st, g); });
     if (rc != ASD_OK) return rc;
     return launch_status();
+}
+
+// what asd_verify_accept_ex, _stats and _fused_ex fill alike; asd_lse_partial too, which then sets its own v_offset / msg / mode
+void fill_params(VerifyParams& p, const void* logits, int64_t ld_row, const int32_t* tok, const float* lp_draft, const float* u,
+                 int B, int K, int V, float* lp_target, uint8_t* accept, int32_t* n_acc, uint64_t* accept_bits) {
+    p.logits = logits; p.ld_row = ld_row; p.tok = tok; p.lp_d = lp_draft; p.u = u;
+    p.B = B; p.K = K; p.V = V; p.v_offset = 0;
+    p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
+    p.msg = nullptr; p.mode = 0;
 }
 
 }  // namespace
@@ -965,9 +955,7 @@ ASD_EXPORT size_t asd_verify_accept_workspace_bytes(int B, int K, int V, int dty
     (void)V;
     (void)dtype;
     if (B <= 0 || K <= 0) return 256;
-    const size_t ticket_bytes = round_up(static_cast<size_t>(B) * kTicketStride * sizeof(uint32_t), 256);
-    const size_t region_bytes = round_up(static_cast<size_t>(K) * max_splits_for(K) * sizeof(uint64_t), 256);
-    return ticket_bytes + region_bytes * static_cast<size_t>(B);
+    return workspace_layout(B, K, max_splits_for(K)).total;
 }
 
 ASD_EXPORT int asd_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
@@ -989,13 +977,13 @@ namespace {
 // options -> (scale2, geometry); NULL = defaults
 int unpack_options(const asd_verify_options* opt, float& scale2, asd::Geometry& g) {
     g = asd::Geometry{0, 0, 0, -1};
-    double inv_t = 1.0;
+    float inv_t = 1.0f;
     if (opt) {
-        if (!(opt->inv_temperature > 0.0f) || !(opt->inv_temperature < 3.0e38f)) return ASD_ERR_INVALID_ARG;
-        inv_t = static_cast<double>(opt->inv_temperature);
+        if (!valid_inv_temperature(opt->inv_temperature)) return ASD_ERR_INVALID_ARG;
+        inv_t = opt->inv_temperature;
         g = asd::Geometry{opt->splits, opt->threads, opt->unroll, opt->nontemporal};
     }
-    scale2 = static_cast<float>(1.4426950408889634074 * inv_t);
+    scale2 = log2_scale(inv_t);
     return ASD_OK;
 }
 }  // namespace
@@ -1009,10 +997,7 @@ ASD_EXPORT int asd_verify_accept_ex(const void* logits, int dtype, int64_t ld_ro
     Geometry g;
     const int rc = unpack_options(opt, p.scale2, g);
     if (rc != ASD_OK) return rc;
-    p.logits = logits; p.ld_row = ld_row; p.tok = tok; p.lp_d = lp_draft; p.u = u;
-    p.B = B; p.K = K; p.V = V; p.v_offset = 0;
-    p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
-    p.msg = nullptr; p.mode = 0;
+    fill_params(p, logits, ld_row, tok, lp_draft, u, B, K, V, lp_target, accept, n_acc, accept_bits);
     return launch_verify(p, dtype, workspace, workspace_bytes, stream, g);
 }
 
@@ -1028,10 +1013,7 @@ ASD_EXPORT int asd_verify_accept_stats(const void* logits, int dtype, int64_t ld
     const int rc = unpack_options(&opt, p.scale2, g);
     if (rc != ASD_OK) return rc;
     if (row_entropy) g = Geometry{1, 512, 3, 1};   // one workgroup per row whatever the batch: the entropy's third sum is not handed across slices
-    p.logits = logits; p.ld_row = ld_row; p.tok = tok; p.lp_d = lp_draft; p.u = u;
-    p.B = B; p.K = K; p.V = V; p.v_offset = 0;
-    p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
-    p.msg = nullptr; p.mode = 0;
+    fill_params(p, logits, ld_row, tok, lp_draft, u, B, K, V, lp_target, accept, n_acc, accept_bits);
     p.row_max_lp = row_max_lp; p.row_entropy = row_entropy;
     return launch_verify(p, dtype, workspace, workspace_bytes, stream, g);
 }
@@ -1076,10 +1058,8 @@ ASD_EXPORT int asd_verify_accept_fused_ex(const void* logits, int dtype, int64_t
                                   risk_adjustment, n_obs, alpha, beta, p_hist, C, lam, L, stage_idx, prefix_rule, theta, B,
                                   score, k_star, stop, thr_stop, stats, stream);
     }
-    p.logits = logits; p.ld_row = ld_row; p.tok = tok; p.lp_d = lp_draft; p.u = u;
-    p.B = B; p.K = K; p.V = V; p.v_offset = 0;
-    p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
-    p.msg = nullptr; p.mode = 0; p.fused = in_kernel2 ? 2 : 1;
+    fill_params(p, logits, ld_row, tok, lp_draft, u, B, K, V, lp_target, accept, n_acc, accept_bits);
+    p.fused = in_kernel2 ? 2 : 1;
     FusedParams& e = p.epi;
     e.lp = nullptr; e.ld_lp = K; e.n_valid = nullptr; e.K = K;
     e.feat = feat; e.ldf = ldf; e.stats_col = stats_col;
@@ -1126,12 +1106,11 @@ ASD_EXPORT int asd_lse_partial(const void* logits_shard, int dtype, int64_t ld_r
                                int V_shard, int64_t v_offset, float inv_temperature, float* msg, void* workspace,
                                size_t workspace_bytes, void* stream) {
     if (B > 0 && K > 0 && !msg) return ASD_ERR_INVALID_ARG;
-    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f)) return ASD_ERR_INVALID_ARG;
+    if (!valid_inv_temperature(inv_temperature)) return ASD_ERR_INVALID_ARG;
     VerifyParams p{};
-    p.scale2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature));
-    p.logits = logits_shard; p.ld_row = ld_row; p.tok = tok;
-    p.B = B; p.K = K; p.V = V_shard; p.v_offset = v_offset;
-    p.msg = msg; p.mode = 1;
+    p.scale2 = log2_scale(inv_temperature);
+    fill_params(p, logits_shard, ld_row, tok, nullptr, nullptr, B, K, V_shard, nullptr, nullptr, nullptr, nullptr);
+    p.v_offset = v_offset; p.msg = msg; p.mode = 1;
     return launch_verify(p, dtype, workspace, workspace_bytes, stream, Geometry{0, 0, 0, -1});
 }
 
@@ -1139,8 +1118,8 @@ ASD_EXPORT int asd_accept_from_partials(const float* msg_all, int n_shards, cons
                                         int B, int K, float inv_temperature, float* lp_target, uint8_t* accept,
                                         int32_t* n_acc, uint64_t* accept_bits, void* stream) {
     if (B < 0 || K < 0 || n_shards < 1) return ASD_ERR_INVALID_ARG;
-    if (!(inv_temperature > 0.0f) || !(inv_temperature < 3.0e38f)) return ASD_ERR_INVALID_ARG;
-    const float c2 = static_cast<float>(1.4426950408889634074 * static_cast<double>(inv_temperature));
+    if (!valid_inv_temperature(inv_temperature)) return ASD_ERR_INVALID_ARG;
+    const float c2 = log2_scale(inv_temperature);
     if (B == 0 || K == 0) return ASD_OK;
     if (K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
     if (!msg_all || !lp_draft || !u || !lp_target || !accept || !n_acc) return ASD_ERR_INVALID_ARG;

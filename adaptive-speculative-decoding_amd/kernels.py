@@ -154,23 +154,28 @@ def _logits_2d(logits: torch.Tensor, Bv: int, K: int) -> Tuple[int, int, int]:
     raise ValueError("logits must be [B,K,V] or [B*K,V]")
 
 
+def _verify_args(logits, tok, lp_draft, u, out, cls=VerifyResult):
+    """What every verify call starts with: (out -- fresh unless given --, the nine leading arguments logits .. V of the C entry
+    points, the four output pointers lp_target .. accept_bits)."""
+    Bv, K = tok.shape
+    V, ld, ptr = _logits_2d(logits, Bv, K)
+    if out is None:
+        out = _verify_out(Bv, K, logits.device, cls)
+    lead = (ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
+            _dev(u, "u", torch.float32), Bv, K, V)
+    outs = (_dev(out.lp_target, "lp_target", torch.float32), _dev(out.accept, "accept", torch.uint8),
+            _dev(out.n_acc, "n_acc", torch.int32), _dev(out.accept_bits, "accept_bits", torch.int64))
+    return out, lead, outs
+
+
 def verify_accept(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
                   workspace: VerifyWorkspace, out: Optional[VerifyResult] = None, *, inv_temperature: float = 1.0,
                   splits: int = 0, threads: int = 0, unroll: int = 0, nontemporal: int = -1) -> VerifyResult:
     """A5/A6 in one launch (include/asd_hip.h: asd_verify_accept_ex).  tok/lp_draft/u: [B,K].
     inv_temperature scales the logits inside the kernel (the test runs on softmax(logits / T))."""
-    Bv, K = tok.shape
-    V, ld, ptr = _logits_2d(logits, Bv, K)
-    dev = logits.device
-    if out is None:
-        out = _verify_out(Bv, K, dev)
+    out, lead, outs = _verify_args(logits, tok, lp_draft, u, out)
     opt = B.verify_options(inv_temperature, splits, threads, unroll, nontemporal)
-    rc = _lib().asd_verify_accept_ex(
-        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
-        _dev(u, "u", torch.float32), Bv, K, V, _dev(out.lp_target, "lp_target", torch.float32),
-        _dev(out.accept, "accept", torch.uint8), _dev(out.n_acc, "n_acc", torch.int32),
-        _dev(out.accept_bits, "accept_bits", torch.int64), workspace.buf.data_ptr(), workspace.bytes,
-        C.addressof(opt), _stream())
+    rc = _lib().asd_verify_accept_ex(*lead, *outs, workspace.buf.data_ptr(), workspace.bytes, C.addressof(opt), _stream())
     B.check("asd_verify_accept_ex", rc)
     return out
 
@@ -178,16 +183,10 @@ def verify_accept(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tenso
 def _verify_truncated(entry: str, logits, tok, lp_draft, u, workspace, inv_temperature, truncation: tuple, out):
     """The body of verify_accept_top_p / verify_accept_top_k: `entry` is the C entry point, `truncation` its arguments between
     inv_temperature and the outputs."""
-    Bv, K = tok.shape
-    V, ld, ptr = _logits_2d(logits, Bv, K)
-    if out is None:
-        out = _verify_out(Bv, K, logits.device, NucleusVerifyResult)
+    out, lead, outs = _verify_args(logits, tok, lp_draft, u, out, NucleusVerifyResult)
     ws_ptr, ws_bytes = (None, 0) if workspace is None else (workspace.buf.data_ptr(), workspace.bytes)
     rc = getattr(_lib(), entry)(
-        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
-        _dev(u, "u", torch.float32), Bv, K, V, float(inv_temperature), *truncation,
-        _dev(out.lp_target, "lp_target", torch.float32), _dev(out.accept, "accept", torch.uint8),
-        _dev(out.n_acc, "n_acc", torch.int32), _dev(out.accept_bits, "accept_bits", torch.int64),
+        *lead, float(inv_temperature), *truncation, *outs,
         _dev(out.t_nucleus_logit, "t_nucleus_logit", torch.float32), _dev(out.n_finite, "n_finite", torch.int32),
         ws_ptr, ws_bytes, _stream())
     B.check(entry, rc)
@@ -219,17 +218,11 @@ def verify_accept_stats(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
                         want_entropy: bool = True) -> Tuple[VerifyResult, torch.Tensor, Optional[torch.Tensor]]:
     """asd_verify_accept_stats: the verify pass + per position max log-prob [B,K] and (optionally) the entropy of the
     target softmax [B,K] -- the device-side inputs of the doc-only FeatureExtractor (RESEARCH_PROTOCOL.md:378-400)."""
-    Bv, K = tok.shape
-    V, ld, ptr = _logits_2d(logits, Bv, K)
-    dev = logits.device
-    if out is None:
-        out = _verify_out(Bv, K, dev)
-    max_lp = torch.empty((Bv, K), dtype=torch.float32, device=dev)
-    ent = torch.empty((Bv, K), dtype=torch.float32, device=dev) if want_entropy else None
+    out, lead, outs = _verify_args(logits, tok, lp_draft, u, out)
+    max_lp = torch.empty(tuple(tok.shape), dtype=torch.float32, device=logits.device)
+    ent = torch.empty_like(max_lp) if want_entropy else None
     rc = _lib().asd_verify_accept_stats(
-        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
-        _dev(u, "u", torch.float32), Bv, K, V, out.lp_target.data_ptr(), out.accept.data_ptr(), out.n_acc.data_ptr(),
-        out.accept_bits.data_ptr(), max_lp.data_ptr(), None if ent is None else ent.data_ptr(), workspace.buf.data_ptr(),
+        *lead, *outs, max_lp.data_ptr(), None if ent is None else ent.data_ptr(), workspace.buf.data_ptr(),
         workspace.bytes, float(inv_temperature), _stream())
     B.check("asd_verify_accept_stats", rc)
     return out, max_lp, ent
@@ -300,6 +293,13 @@ class LmHeadVerifier:
         n = int(_lib().asd_lm_head_verify_workspace_bytes(self.B, self.K, self.V))
         self.workspace = torch.empty(max(n, 256), dtype=torch.uint8, device=weight.device)
 
+    def _hidden_2d(self, hidden: torch.Tensor, Bv: int, K: int) -> Tuple[torch.Tensor, int]:
+        """(hidden as [B*K, D], its row stride as the C entry points take it)"""
+        h2 = hidden.reshape(Bv * K, hidden.shape[-1]) if hidden.dim() == 3 else hidden
+        if h2.dtype != self.weight.dtype or h2.shape != (Bv * K, self.D) or h2.stride(1) != 1:
+            raise ValueError("hidden must be [B*K, D] of the weight's element type with contiguous rows")
+        return h2, (h2.stride(0) if Bv * K > 1 else self.D)
+
     def __call__(self, hidden: torch.Tensor, tok: torch.Tensor, lp_draft: Optional[torch.Tensor] = None,
                  u: Optional[torch.Tensor] = None, out: Optional[VerifyResult] = None, inv_temperature: float = 1.0,
                  greedy: bool = False, argmax_out: Optional[torch.Tensor] = None) -> VerifyResult:
@@ -311,13 +311,10 @@ class LmHeadVerifier:
             raise ValueError(f"verifier was sized for B<={self.B}, K={self.K}, got {Bv}, {K}")
         if not greedy and (lp_draft is None or u is None):
             raise ValueError("lp_draft and u are required unless greedy=True")
-        h2 = hidden.reshape(Bv * K, hidden.shape[-1]) if hidden.dim() == 3 else hidden
-        if h2.dtype != self.weight.dtype or h2.shape != (Bv * K, self.D) or h2.stride(1) != 1:
-            raise ValueError("hidden must be [B*K, D] of the weight's element type with contiguous rows")
-        dev = h2.device
+        h2, ld_h = self._hidden_2d(hidden, Bv, K)
         if out is None:
-            out = _verify_out(Bv, K, dev)
-        rc = _lib().asd_lm_head_verify_ex(h2.data_ptr(), h2.stride(0) if Bv * K > 1 else self.D, self._w_ptr,
+            out = _verify_out(Bv, K, h2.device)
+        rc = _lib().asd_lm_head_verify_ex(h2.data_ptr(), ld_h, self._w_ptr,
                                           self._ld_w, self._dt, self.D, _dev(tok, "tok", torch.int32),
                                           _opt(lp_draft, "lp_draft", torch.float32), _opt(u, "u", torch.float32), Bv, K,
                                           self.V, float(inv_temperature), 1 if greedy else 0, out.lp_target.data_ptr(),
@@ -335,12 +332,10 @@ class LmHeadVerifier:
         Bv, K = tok.shape
         if Bv > self.B or K != self.K:
             raise ValueError(f"verifier was sized for B<={self.B}, K={self.K}, got {Bv}, {K}")
-        h2 = hidden.reshape(Bv * K, hidden.shape[-1]) if hidden.dim() == 3 else hidden
-        if h2.dtype != self.weight.dtype or h2.shape != (Bv * K, self.D) or h2.stride(1) != 1:
-            raise ValueError("hidden must be [B*K, D] of the weight's element type with contiguous rows")
+        h2, ld_h = self._hidden_2d(hidden, Bv, K)
         if msg is None:
             msg = torch.empty((Bv, K, 3), dtype=torch.float32, device=h2.device)
-        rc = _lib().asd_lm_head_partial(h2.data_ptr(), h2.stride(0) if Bv * K > 1 else self.D, self._w_ptr,
+        rc = _lib().asd_lm_head_partial(h2.data_ptr(), ld_h, self._w_ptr,
                                         self._ld_w, self._dt, self.D, _dev(tok, "tok", torch.int32), Bv, K,
                                         self.V, int(v_offset), float(inv_temperature), _dev(msg, "msg", torch.float32),
                                         self.workspace.data_ptr(), self.workspace.numel(), _stream())
@@ -574,17 +569,12 @@ def verify_accept_fused(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
                         out: Optional[VerifyResult] = None, inv_temperature: float = 1.0) -> Tuple[VerifyResult, StopResult]:
     """N1, second form: verify + accept + predictor/stop epilogue in ONE call (one launch for the reference's
     64->32->1 predictor at any batch size, two for other predictor shapes; asd_verify_accept_fused_ex in include/asd_hip.h)."""
-    Bv, K = tok.shape
-    V, ld, ptr = _logits_2d(logits, Bv, K)
-    dev = logits.device
-    if out is None:
-        out = _verify_out(Bv, K, dev)
-    res = _stop_out(Bv, dev, p_hist is not None and Cc is not None, theta is not None, want_stats)
+    out, lead, outs = _verify_args(logits, tok, lp_draft, u, out)
+    Bv = tok.shape[0]
+    res = _stop_out(Bv, logits.device, p_hist is not None and Cc is not None, theta is not None, want_stats)
     opt = B.verify_options(inv_temperature)
     rc = _lib().asd_verify_accept_fused_ex(
-        ptr, _DTYPE_CODE[logits.dtype], ld, _dev(tok, "tok", torch.int32), _dev(lp_draft, "lp_draft", torch.float32),
-        _dev(u, "u", torch.float32), Bv, K, V, out.lp_target.data_ptr(), out.accept.data_ptr(), out.n_acc.data_ptr(),
-        out.accept_bits.data_ptr(), workspace.buf.data_ptr(), workspace.bytes,
+        *lead, *outs, workspace.buf.data_ptr(), workspace.bytes,
         _dev(feat, "feat", torch.float32), feat.stride(0) if Bv else in_dim, stats_col,
         _dev(packed_w, "packed_w", torch.float32), in_dim, hidden, int(bool(risk_adjustment)), int(n_obs), float(alpha),
         float(beta), _opt(p_hist, "p_hist", torch.float64), _opt(Cc, "C", torch.float64), float(lam), L, stage_idx,
