@@ -13,19 +13,29 @@
 namespace asd {
 namespace {
 
-__global__ __launch_bounds__(64) void k_commit_step(const int32_t* tok, const int32_t* n_acc, const int32_t* drawn, int B,
-                                                    int K, int32_t* seq_len, int32_t* out_tokens, int64_t ld_out,
-                                                    int32_t* n_commit, int32_t max_len) {
+// kLp (asd_commit_step_lp): the log-probs of the committed tokens take the same path into row b of `out_lp` -- lp_tok[b, k]
+// beside draft token k, lp_drawn[b] beside the drawn token -- so a stage that reports per-token log-probs needs no read-back.
+template <bool kLp>
+__global__ __launch_bounds__(64) void k_commit_step(const int32_t* tok, const float* lp_tok, const int32_t* n_acc,
+                                                    const int32_t* drawn, const float* lp_drawn, int B, int K, int32_t* seq_len,
+                                                    int32_t* out_tokens, float* out_lp, int64_t ld_out, int32_t* n_commit,
+                                                    int32_t max_len) {
     const int b = blockIdx.x;
     const int lane = threadIdx.x;
     const int len = seq_len[b];                      // every lane reads the old length before lane 0 rewrites it
     int na = n_acc[b];
     na = na < 0 ? 0 : (na > K ? K : na);
     int32_t* row = out_tokens + static_cast<int64_t>(b) * ld_out;
-    if (lane < na && len + lane < max_len) row[len + lane] = tok[static_cast<int64_t>(b) * K + lane];
+    if (lane < na && len + lane < max_len) {
+        row[len + lane] = tok[static_cast<int64_t>(b) * K + lane];
+        if constexpr (kLp) out_lp[static_cast<int64_t>(b) * ld_out + len + lane] = lp_tok[static_cast<int64_t>(b) * K + lane];
+    }
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
-        if (len + na < max_len) row[len + na] = drawn[b];
+        if (len + na < max_len) {
+            row[len + na] = drawn[b];
+            if constexpr (kLp) out_lp[static_cast<int64_t>(b) * ld_out + len + na] = lp_drawn[b];
+        }
         int appended = max_len - len;
         appended = appended < 0 ? 0 : (appended > na + 1 ? na + 1 : appended);
         seq_len[b] = len + appended;
@@ -46,7 +56,20 @@ ASD_EXPORT int asd_commit_step(const int32_t* tok, const int32_t* n_acc, const i
     if (K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
     if ((K > 0 && !tok) || !n_acc || !drawn || !seq_len || !out_tokens) return ASD_ERR_INVALID_ARG;
     if (ld_out < max_len) return ASD_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(k_commit_step, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, n_acc, drawn, B, K,
-                       seq_len, out_tokens, ld_out, n_commit, max_len);
+    hipLaunchKernelGGL(k_commit_step<false>, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, nullptr, n_acc, drawn,
+                       nullptr, B, K, seq_len, out_tokens, nullptr, ld_out, n_commit, max_len);
+    return launch_status();
+}
+
+ASD_EXPORT int asd_commit_step_lp(const int32_t* tok, const float* lp_tok, const int32_t* n_acc, const int32_t* drawn,
+                                  const float* lp_drawn, int B, int K, int32_t* seq_len, int32_t* out_tokens, float* out_lp,
+                                  int64_t ld_out, int32_t* n_commit, int32_t max_len, void* stream) {
+    if (B < 0 || K < 0 || max_len < 0) return ASD_ERR_INVALID_ARG;
+    if (B == 0) return ASD_OK;
+    if (K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
+    if ((K > 0 && (!tok || !lp_tok)) || !n_acc || !drawn || !lp_drawn || !seq_len || !out_tokens || !out_lp) return ASD_ERR_INVALID_ARG;
+    if (ld_out < max_len) return ASD_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_commit_step<true>, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, lp_tok, n_acc, drawn,
+                       lp_drawn, B, K, seq_len, out_tokens, out_lp, ld_out, n_commit, max_len);
     return launch_status();
 }

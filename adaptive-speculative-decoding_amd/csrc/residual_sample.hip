@@ -42,6 +42,7 @@ struct RsParams {
     const float* d_thr;       // [B*K] nucleus thresholds of the draft rows (logit < thr => p_d = 0, renormalised) or nullptr
     const float* t_thr;       // [B*K] nucleus thresholds of the target rows (asd_verify_accept_top_p's x*) or nullptr
     const float* b_thr;       // [B] nucleus thresholds of the bonus rows (k_rs_bonus_threshold) or nullptr
+    float* lp;                // [B] out: log p_t^N(token) (asd_residual_sample_lp) or nullptr
 };
 
 template <int DT>
@@ -66,6 +67,12 @@ __device__ __forceinline__ Rows<DT> select_rows(const RsParams& p, int b) {
         if (p.b_thr) r.tthr = p.b_thr[b];
     }
     return r;
+}
+
+// a sequence without a token (no row to draw from, an empty row, a poisoned hand-off): token = -1 and, where asked for, lp = NaN
+__device__ __forceinline__ void rs_no_token(const RsParams& p, int b) {
+    p.token[b] = -1;
+    if (p.lp) p.lp[b] = NAN;
 }
 
 __device__ __forceinline__ void slice_tiles(int n_tiles, int s, int S, int& t0, int& t1) {
@@ -185,7 +192,7 @@ __device__ __forceinline__ void rs_pick_scan(const RsParams& p, int b, int lane,
     unsigned long long bal = __ballot(holds);
     if (bal == 0) {                                    // rounding pushed the draw past the end: last chunk with mass
         bal = __ballot(mine > 0.0);
-        if (bal == 0) { if (lane == 0) p.token[b] = -1; return; }
+        if (bal == 0) { if (lane == 0) rs_no_token(p, b); return; }
         bal = 1ull << (63 - __builtin_clzll(bal));
     }
     if (lane == __builtin_ctzll(bal)) {
@@ -214,8 +221,9 @@ __device__ __forceinline__ void rs_pick_scan(const RsParams& p, int b, int lane,
     float w[N], pt[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) { w[i] = 0.0f; pt[i] = 0.0f; }
+    u32x4 a = {0u, 0u, 0u, 0u};
     if (v < p.nvec) {
-        const u32x4 a = vt[v];
+        a = vt[v];
         u32x4 d = {0u, 0u, 0u, 0u};
         if (vd) d = vd[v];
         vector_weights<DT>(a, d, vd != nullptr, p.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
@@ -230,7 +238,7 @@ __device__ __forceinline__ void rs_pick_scan(const RsParams& p, int b, int lane,
     unsigned long long lbal = __ballot(lholds);
     if (lbal == 0) {
         lbal = __ballot(lm > 0.0);
-        if (lbal == 0) { if (lane == 0) p.token[b] = -1; return; }
+        if (lbal == 0) { if (lane == 0) rs_no_token(p, b); return; }
         lbal = 1ull << (63 - __builtin_clzll(lbal));
     }
     if (lane == __builtin_ctzll(lbal)) {
@@ -247,6 +255,15 @@ __device__ __forceinline__ void rs_pick_scan(const RsParams& p, int b, int lane,
         }
         if (pick < 0) pick = last_pos;
         p.token[b] = v * N + pick;
+        if (p.lp) {                                        // (wave-uniform) asd_residual_sample_lp: log p_t^N(token), formed the way
+            float x[N];                                    // the verify forms lp_t -- from the logit and the row's log2 normaliser,
+            unpack<DT>(a, x);                              // never from the f32 probability
+            float x_tok = x[0];
+#pragma unroll
+            for (int i = 1; i < N; ++i) x_tok = pick == i ? x[i] : x_tok;
+            const double L = static_cast<double>(Lt.hi) + static_cast<double>(Lt.lo);
+            p.lp[b] = static_cast<float>(kLn2d * (static_cast<double>(x_tok) * static_cast<double>(p.c2) - L));
+        }
     }
 }
 
@@ -256,7 +273,7 @@ __global__ __launch_bounds__(64) void k_rs_pick(const RsParams p) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const Rows<DT> rows = select_rows<DT>(p, b);
     if (!rows.xt) {
-        if (lane == 0) p.token[b] = -1;
+        if (lane == 0) rs_no_token(p, b);
         return;
     }
     Norm2 Lt, Ld;
@@ -279,7 +296,7 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_row(const RsParams p) {
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const Rows<DT> rows = select_rows<DT>(p, b);        // block-uniform
     if (!rows.xt) {
-        if (t == 0) p.token[b] = -1;
+        if (t == 0) rs_no_token(p, b);
         return;
     }
     const u32x4* vt = reinterpret_cast<const u32x4*>(rows.xt);
@@ -363,7 +380,7 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
     const bool leader = g == 0;
     const Rows<DT> rows = select_rows<DT>(p, b);            // the same for every workgroup of the sequence
     if (!rows.xt) {
-        if (leader && t == 0) p.token[b] = -1;
+        if (leader && t == 0) rs_no_token(p, b);
         return;
     }
     unsigned long long* small = q.small + static_cast<int64_t>(b) * (3 * q.n_pad + kDgMaxGroups * 2);
@@ -470,7 +487,7 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
     __syncthreads();
     if (wave != 0) return;
     if (lost) {
-        if (lane == 0) p.token[b] = -1;                    // a hand-off never arrived: poisoned, not guessed
+        if (lane == 0) rs_no_token(p, b);                  // a hand-off never arrived: poisoned, not guessed
         return;
     }
     rs_pick_scan<DT>(p, b, lane, rows, tiles, Lt, Ld, sc);
@@ -561,13 +578,13 @@ struct RsTruncate {
     int top_k = 0;
 };
 
-// The launcher behind the four entry points.  A call that truncates nothing (top_p outside (0, 1) and top_k <= 0 or >= V) is
+// The launcher behind the five entry points.  A call that truncates nothing (top_p outside (0, 1) and top_k <= 0 or >= V) is
 // asd_residual_sample_ex's, whichever entry point it came through (the same bits): t_threshold and the larger workspace are
 // not asked for.
 int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d, const void* bonus_logits,
                     int64_t ld_b, int dtype, const int32_t* n_acc, const float* r, int B, int K, int V,
                     float inv_temperature, const float* d_threshold, int32_t* token, void* workspace,
-                    size_t workspace_bytes, void* stream, const RsTruncate& cut) {
+                    size_t workspace_bytes, void* stream, const RsTruncate& cut, float* lp = nullptr) {
     // what only a truncating call can fail comes first, before the sizes and the dtype are looked at (asd_residual_sample and
     // _ex pass top_p = 1)
     if (cut.top_p != cut.top_p) return ASD_ERR_INVALID_ARG;
@@ -601,6 +618,7 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     p.partial = reinterpret_cast<float4*>(body);
     p.tiles = reinterpret_cast<float2*>(body + round_up(static_cast<size_t>(B) * 32 * sizeof(float4), 256));
     p.token = token;
+    p.lp = lp;
     p.d_thr = d_threshold;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (truncated) {
@@ -702,4 +720,14 @@ ASD_EXPORT int asd_residual_sample_top_k(const void* t_logits, int64_t ld_t, con
                                          size_t workspace_bytes, void* stream) {
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
                            d_threshold, token, workspace, workspace_bytes, stream, {t_threshold, top_p, top_k});
+}
+
+ASD_EXPORT int asd_residual_sample_lp(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                                      const void* bonus_logits, int64_t ld_b, int dtype, const int32_t* n_acc,
+                                      const float* r, int B, int K, int V, float inv_temperature, int top_k, float top_p,
+                                      const float* t_threshold, const float* d_threshold, int32_t* token, float* lp,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (B > 0 && !lp) return ASD_ERR_INVALID_ARG;
+    return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
+                           d_threshold, token, workspace, workspace_bytes, stream, {t_threshold, top_p, top_k}, lp);
 }

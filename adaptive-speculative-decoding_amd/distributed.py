@@ -280,9 +280,23 @@ class HipOps:
         return s.top_k(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_k=top_k, top_p=top_p, t_threshold=t_threshold,
                        d_threshold=d_threshold)
 
+    @traced("residual_sample_lp")
+    def residual_sample_lp(self, t_logits, d_logits, n_acc, r, bonus, inv_temperature: float = 1.0, d_threshold=None,
+                           t_threshold=None, top_k: int = 0, top_p: float = 1.0):
+        """The committed token and its target log-prob (asd_residual_sample_lp) -> (token i32 [n], lp f32 [n]); the token is
+        residual_sample's / residual_sample_top_k's on the same arguments, lp = log p_t^N(token)."""
+        s = self._sampler("residual", t_logits.shape[0], t_logits.shape[2], t_logits.dtype, t_logits.device)
+        return s.lp(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_k=top_k, top_p=top_p, t_threshold=t_threshold,
+                    d_threshold=d_threshold)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)
+
+    @traced("commit_step_lp")
+    def commit_step_lp(self, tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, max_len):
+        """commit_step with the log-probs scattered beside the tokens (asd_commit_step_lp); tok = lp_tok = None: K = 0."""
+        self.K.commit_step_lp(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, max_len=max_len)
 
     @traced("lambda_sweep")
     def lambda_sweep(self, p_hist, costs, lams):

@@ -408,6 +408,29 @@ def commit_step(tok: torch.Tensor, n_acc: torch.Tensor, drawn: torch.Tensor, seq
     B.check("asd_commit_step", rc)
 
 
+def commit_step_lp(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor], n_acc: torch.Tensor, drawn: torch.Tensor,
+                   lp_drawn: torch.Tensor, seq_len: torch.Tensor, out_tokens: torch.Tensor, out_lp: torch.Tensor,
+                   n_commit: Optional[torch.Tensor] = None, max_len: Optional[int] = None) -> None:
+    """commit_step that also appends the committed tokens' log-probs to `out_lp` (asd_commit_step_lp): lp_tok [B,K] f32 beside
+    tok, lp_drawn [B] f32 beside drawn, out_lp [B, T] f32 with the row stride of out_tokens.  tok = lp_tok = None is K = 0:
+    every sequence appends its drawn token (plain sampled decoding)."""
+    Bv = drawn.shape[0]
+    K = 0 if tok is None else tok.shape[1]
+    if tok is not None and (tok.shape[0] != Bv or lp_tok is None or lp_tok.shape != tok.shape):
+        raise ValueError("tok and lp_tok must both be [B, K]")
+    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
+        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
+    if out_lp.shape != out_tokens.shape or out_lp.stride() != out_tokens.stride():
+        raise ValueError("out_lp must have the shape and strides of out_tokens")
+    cap = out_tokens.shape[1] if max_len is None else int(max_len)
+    rc = _lib().asd_commit_step_lp(_opt(tok, "tok", torch.int32), _opt(lp_tok, "lp_tok", torch.float32),
+                                   _dev(n_acc, "n_acc", torch.int32), _dev(drawn, "drawn", torch.int32),
+                                   _dev(lp_drawn, "lp_drawn", torch.float32), Bv, K, _dev(seq_len, "seq_len", torch.int32),
+                                   _dev(out_tokens, "out_tokens", torch.int32), _dev(out_lp, "out_lp", torch.float32),
+                                   out_tokens.stride(0), _opt(n_commit, "n_commit", torch.int32), cap, _stream())
+    B.check("asd_commit_step_lp", rc)
+
+
 # ------------------------------------------------------------------------------- predictor side
 def logprob_stats(lp: torch.Tensor, n_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A7: [B,K] f32 log-probs -> [B,5] f64 (mean, std, min, q25, median), numpy semantics."""
@@ -603,9 +626,11 @@ class ResidualSampler(_StatusWorkspace):
         self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device or torch.device("cuda"))
         self.reset()
 
-    def _sample(self, entry: str, t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out, scalars=(), **thresholds):
-        """The body of __call__ / top_p / top_k: `entry` is the C entry point; `scalars`, then the optional [B,K] `thresholds`
-        (in the entry point's order), are its arguments between inv_temperature and the token."""
+    def _sample(self, entry: str, t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out, scalars=(), lp_out=None,
+                **thresholds):
+        """The body of __call__ / top_p / top_k / lp: `entry` is the C entry point; `scalars`, then the optional [B,K] `thresholds`
+        (in the entry point's order), are its arguments between inv_temperature and the token; `lp_out` ([B] f32) follows the
+        token where the entry point has it."""
         Bv, K, V = t_logits.shape
         if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
             raise ValueError("t_logits and d_logits must have the same shape and dtype")
@@ -620,6 +645,7 @@ class ResidualSampler(_StatusWorkspace):
         rc = getattr(_lib(), entry)(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype], _dev(n_acc, "n_acc", torch.int32),
                                     _dev(r, "r", torch.float32), Bv, K, V, float(inv_temperature), *scalars,
                                     *[_opt(t, name, torch.float32) for name, t in thresholds.items()], out.data_ptr(),
+                                    *(() if lp_out is None else (_dev(lp_out, "lp", torch.float32),)),
                                     self.buf.data_ptr(), self.bytes, _stream())
         B.check(entry, rc)
         return out
@@ -651,6 +677,19 @@ class ResidualSampler(_StatusWorkspace):
         >= V is top_p(...) (the same bits)."""
         return self._sample("asd_residual_sample_top_k", t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out,
                             (int(top_k), float(top_p)), t_threshold=t_threshold, d_threshold=d_threshold)
+
+    def lp(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
+           bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0, *, top_k: int = 0, top_p: float = 1.0,
+           t_threshold: Optional[torch.Tensor] = None, d_threshold: Optional[torch.Tensor] = None,
+           out: Optional[torch.Tensor] = None, lp_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The committed token AND its target log-prob (asd_residual_sample_lp) -> (token [B] i32, lp [B] f32): the token of
+        __call__ / top_p / top_k on the same arguments (the same bits), lp = log p_t^N(token) under the target row the draw
+        used (NaN where token == -1)."""
+        if lp_out is None:
+            lp_out = torch.empty((t_logits.shape[0],), dtype=torch.float32, device=t_logits.device)
+        tok = self._sample("asd_residual_sample_lp", t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out,
+                           (int(top_k), float(top_p)), lp_out, t_threshold=t_threshold, d_threshold=d_threshold)
+        return tok, lp_out
 
 
 @dataclass

@@ -1,5 +1,6 @@
-"""Serving-side mirror of the reference's src/serving package (pipeline only; the HTTP shell,
-cost optimiser and vLLM stages are out of scope)."""
+"""Serving-side mirror of the reference's src/serving package (the pipeline and the stages behind it; the HTTP
+shell and the cost optimiser are out of scope)."""
 from .cache import RequestCache  # noqa: F401
 from .components import FeatureExtractor, QualityPredictor  # noqa: F401
 from .pipeline import AdaptiveSpeculativePipeline, PipelineConfig, RequestResult  # noqa: F401
+from .stages import Stage, StageConfig, StageManager  # noqa: F401

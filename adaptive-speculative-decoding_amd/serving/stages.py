@@ -1,0 +1,303 @@
+"""Stages behind the pipeline: `StageConfig`, `Stage`, `StageManager` -- the reference's missing src/models/stage.py
+(imported by src/serving/pipeline.py:14, constructed by src/serving/server.py:131-202, sketched in
+docs/guides/RESEARCH_PROTOCOL.md:233-304), with the token-level HIP loop underneath.
+
+`AdaptiveSpeculativePipeline` asks a stage for `generate(prompts=, max_tokens=, temperature=, return_logprobs=True)
+-> (texts, logprobs, stats)` (pipeline.py:204-221) and feeds the per-token log-probs to the quality predictor.  Here a stage
+is a `SyntheticLM` (model execution is plumbing, third party in the reference) and the decoding around it is the kernels':
+
+  stage 0     plain sampled decoding.  Per step: one model pass, one asd_draft_sample[_top_k] call (token + log q(token)),
+              one asd_commit_step_lp call with K = 0 (token and log-prob appended on the device).
+  stage s>0   speculative decoding with stage s-1's model as the draft: the ragged draft -> verify -> commit loop in the
+              step order of serving/speculative.py::speculative_generate_ragged, written on the `ops` abstraction
+              (distributed.HipOps; the CPU tests inject an oracle twin).  The commit draw is asd_residual_sample_lp and the
+              commit is asd_commit_step_lp, so every committed token arrives with its TARGET log-prob: the verify's lp_target
+              for the accepted draft tokens, log p_t^N(drawn) for the token drawn behind them.  The output is distributed as
+              stage s's own model samples (the loop is lossless), and its log-probs are that model's -- what the reference's
+              stage would report.
+
+Nothing synchronises inside a step; the host reads min(seq_len) every `sync_every` steps, and `ops.check_status()` runs before
+results are returned.  There is no EOS in this project: every sequence returns exactly `max_tokens` tokens and log-probs.
+
+PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
+encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
+The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
+the reference's (whose engines mask it).
+"""
+from __future__ import annotations
+
+import time
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ..distributed import HipOps
+from ..minimal_adaptive_decoder import SimpleTokenizer
+from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
+
+# reference stage label -> the Qwen2.5 shape this build runs in its place (configs/models.yaml names the tiers by size)
+_DEFAULT_SHAPES = {"8b": "7b", "13b": "14b", "34b": "32b", "70b": "72b"}
+
+
+@dataclass
+class StageConfig:
+    # -- the reference's fields (server.py:151-158)
+    model_name: str = "synthetic"
+    model_size: str = "8b"                   # the stage's name: StageManager.get_stage(model_size)
+    tensor_parallel_size: int = 1            # recorded only (multi-rank stages are out of scope)
+    gpu_memory_utilization: float = 0.8      # recorded only
+    quantized: bool = False                  # recorded only
+    cost_per_token: float = 1.0
+    # -- build extensions
+    shape: Optional[LMShape] = None          # None: QWEN25_SHAPES by model_size
+    dtype: torch.dtype = torch.bfloat16
+    model_seed: int = 0
+    logit_scale: float = 1.0
+    max_prompt_tokens: int = 256
+    # sampling: the reference's settings for the DRAFT side (temperature comes with the call), off for the TARGET side, as in
+    # serving/hierarchy.py HierarchyConfig.  Stage 0 draws with (top_k, top_p); a verifying stage drafts with the stage
+    # below's model under ITS OWN (top_k, top_p) and verifies / commits against (target_top_k, target_top_p).
+    top_p: float = 0.9
+    top_k: int = 0
+    target_top_p: float = 1.0
+    target_top_k: int = 0
+    draft_len: int = 8
+    seed: int = 0
+    sync_every: int = 4
+
+
+def _shape_of(cfg: StageConfig) -> LMShape:
+    if cfg.shape is not None:
+        return cfg.shape
+    key = _DEFAULT_SHAPES.get(cfg.model_size, cfg.model_size)
+    if key not in QWEN25_SHAPES:
+        raise ValueError(f"no model shape for stage {cfg.model_size!r}: set StageConfig.shape")
+    return QWEN25_SHAPES[key]
+
+
+class Stage:
+    def __init__(self, config: StageConfig, index: int, draft: Optional["Stage"], ops, device):
+        self.config = config
+        self.index = index
+        self.name = config.model_size
+        self.model_size = config.model_size
+        self.model_name = config.model_name
+        self.cost_per_token = float(config.cost_per_token)
+        self.draft = draft                               # the stage below (its model drafts for this one); None for stage 0
+        self.ops = ops
+        self.device = torch.device(device)
+        self.shape = _shape_of(config)
+        if draft is not None and draft.shape.vocab != self.shape.vocab:
+            raise ValueError("a stage and the stage below it must share the vocabulary")
+        if not 1 <= config.draft_len <= 64:
+            raise ValueError("draft_len must be in [1, 64]")
+        self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
+                                 logit_scale=config.logit_scale)
+        self.tokenizer = SimpleTokenizer()
+        self.gen = torch.Generator(device=self.device).manual_seed(int(config.seed))
+        self.keep_inputs = False                         # tests: keep every step's inputs and draws in `step_inputs`
+        self.step_inputs: List[dict] = []
+        self.last_steps = 0
+
+    def get_model_info(self) -> Dict[str, object]:
+        c = self.config
+        return {"name": self.model_name, "size": self.model_size, "stage": self.index, "shape": self.shape.name,
+                "parameters": self.shape.param_count(), "vocab": self.shape.vocab, "cost_per_token": self.cost_per_token,
+                "draft": None if self.draft is None else self.draft.model_size, "draft_len": c.draft_len,
+                "tensor_parallel_size": c.tensor_parallel_size, "quantized": c.quantized, "device": str(self.device)}
+
+    # ------------------------------------------------------------------------------------------ prompts / text
+    def encode_prompts(self, prompts: Sequence[str]) -> torch.Tensor:
+        """[B, P] int64 on the stage's device: the last P ids of every prompt, left-padded with id 0 (module docstring)."""
+        V = self.shape.vocab
+        rows = [[i % V for i in self.tokenizer.encode(p, return_tensors=None)] for p in prompts]
+        P = max(2, min(max((len(r) for r in rows), default=0), int(self.config.max_prompt_tokens)))
+        ids = torch.zeros((len(rows), P), dtype=torch.int64)
+        for b, r in enumerate(rows):
+            r = r[-P:]
+            if r:
+                ids[b, P - len(r):] = torch.tensor(r, dtype=torch.int64)
+        return ids.to(self.device)
+
+    @staticmethod
+    def decode_tokens(ids: Sequence[int]) -> str:
+        return " ".join(f"t{int(i)}" for i in ids)
+
+    # ------------------------------------------------------------------------------------------ generate
+    @torch.no_grad()
+    def generate(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7, return_logprobs: bool = True,
+                 top_p: Optional[float] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, float]]:
+        """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
+        ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [max_tokens],
+        log-prob of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the
+        nucleus of that distribution for the call: StageConfig.top_p at stage 0, StageConfig.target_top_p at a verifying stage."""
+        t0 = time.perf_counter()
+        prompts = list(prompts)
+        self.step_inputs = []
+        if not prompts or max_tokens <= 0:
+            return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
+                {"generation_time_ms": 0.0}
+        if not temperature > 0.0:
+            raise ValueError("temperature must be > 0 (sampled decoding)")
+        ids = self.encode_prompts(prompts)
+        inv_t = float(np.float32(1.0 / temperature))
+        if self.draft is None:
+            tokens, lps = self._decode_plain(ids, int(max_tokens), inv_t, self.config.top_p if top_p is None else float(top_p))
+        else:
+            tokens, lps = self._decode_speculative(ids, int(max_tokens), inv_t,
+                                                   self.config.target_top_p if top_p is None else float(top_p))
+        self.ops.check_status()
+        P = ids.shape[1]
+        tok_h = tokens[:, P:].cpu().numpy()
+        lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
+        texts = [self.decode_tokens(row) for row in tok_h]
+        stats = {"generation_time_ms": (time.perf_counter() - t0) * 1000.0, "steps": float(self.last_steps)}
+        return texts, ([np.ascontiguousarray(r) for r in lp_h] if return_logprobs else None), stats
+
+    def _buffers(self, ids: torch.Tensor, cap: int):
+        B, P = ids.shape
+        dev = ids.device
+        tokens = torch.zeros((B, cap), dtype=torch.int32, device=dev)
+        tokens[:, :P] = ids.to(torch.int32)
+        lps = torch.zeros((B, cap), dtype=torch.float32, device=dev)
+        seq_len = torch.full((B,), P, dtype=torch.int32, device=dev)
+        n_commit = torch.zeros((B,), dtype=torch.int32, device=dev)
+        return tokens, lps, seq_len, n_commit
+
+    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float):
+        """One proposal per sequence from next-token logits [B, V] under Temperature -> (TopK ->) TopP: (tok i32, log q(tok),
+        threshold)."""
+        logits = logits.contiguous()
+        r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device)
+        if cfg.top_k > 0:
+            return self.ops.draft_sample_top_k(logits, r, inv_t, top_k=cfg.top_k, top_p=top_p)
+        return self.ops.draft_sample(logits, r, inv_t, top_p)
+
+    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float):
+        """Stage 0.  Every sequence appends exactly one token per step, so all positions are known on the host."""
+        B, P = ids.shape
+        dev = ids.device
+        cap = P + max_tokens
+        tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
+        m = self.model
+        m.reset()
+        m.alloc_ragged(B, cap + 1)
+        none_accepted = torch.zeros((B,), dtype=torch.int32, device=dev)
+        logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
+        for step in range(max_tokens):
+            logits = logits.contiguous()
+            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p)
+            self.ops.commit_step_lp(None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
+            if self.keep_inputs:
+                self.step_inputs.append(dict(logits=logits.clone(), drawn=tok.clone(), lp_drawn=lp.clone(), thr=thr.clone()))
+            if step + 1 < max_tokens:
+                pos = torch.full((B,), P + step, dtype=torch.int64, device=dev)
+                logits = m.forward_ragged(tok.to(torch.int64)[:, None], pos, P + step + 1)[:, -1]
+        self.last_steps = max_tokens
+        return tokens, lps
+
+    def _verify(self, score, tok32, lp_d, u, inv_t, top_k, top_p):
+        """-> (lp_t, n_acc, t_threshold or None) against the target's Temperature -> (TopK ->) (TopP) distribution."""
+        if top_k > 0:
+            lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_top_k(score, tok32, lp_d, u, inv_t, top_k=top_k, top_p=top_p)
+            return lp_t, n_acc, t_thr
+        if 0.0 < top_p < 1.0:
+            lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_top_p(score, tok32, lp_d, u, inv_t, top_p=top_p)
+            return lp_t, n_acc, t_thr
+        lp_t, _, n_acc, _ = self.ops.verify_accept(score, tok32, lp_d, u, inv_t)
+        return lp_t, n_acc, None
+
+    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float):
+        """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
+
+        Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
+        < L - 1 and the draft's for positions < L - 2, so the target is fed [t_{L-1}, d_0 .. d_{K-1}] at position L - 1 (row i
+        scores d_i, row K is the bonus row) and the draft first re-feeds the last two committed tokens."""
+        cfg, dcfg = self.config, self.draft.config
+        draft, target = self.draft.model, self.model
+        B, P = ids.shape
+        dev = ids.device
+        Kd = cfg.draft_len
+        cap = P + max_tokens
+        tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
+        for m in (draft, target):
+            m.reset()
+            m.alloc_ragged(B, cap + Kd + 2)
+        zero = torch.zeros((B,), dtype=torch.int64, device=dev)
+        target.forward_ragged(ids[:, :P - 1], zero, P)                  # prefill: everything but the last prompt token
+        if P > 2:
+            draft.forward_ragged(ids[:, :P - 2], zero, P)
+        rows = torch.arange(B, device=dev)
+        steps = 0
+        while True:
+            L = seq_len.to(torch.int64)
+            window = min(P + steps * (Kd + 1) + Kd + 1, cap + Kd + 2)   # host-side bound on every position touched this step
+            last2 = torch.stack([tokens[rows, L - 2], tokens[rows, L - 1]], 1).to(torch.int64)
+            dl = draft.forward_ragged(last2, L - 2, window)[:, -1]
+            toks, lpd, dls, thrs = [], [], [], []
+            for k in range(Kd):
+                dl = dl.contiguous()
+                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p)
+                toks.append(t)
+                lpd.append(lp)
+                thrs.append(thr)
+                dls.append(dl)                                          # kept for the residual distribution at a rejection
+                if k + 1 < Kd:
+                    dl = draft.forward_ragged(t.to(torch.int64)[:, None], L + k, window)[:, -1]
+            tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
+            lp_d = torch.stack(lpd, 1).contiguous()
+            d_thr = torch.stack(thrs, 1).contiguous()
+            t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
+            score = t_out[:, :Kd].contiguous()
+            bonus = t_out[:, Kd].contiguous()
+            u = torch.rand((B, Kd), generator=self.gen, device=dev)
+            lp_t, n_acc, t_thr = self._verify(score, tok32, lp_d, u, inv_t, cfg.target_top_k, target_top_p)
+            r = torch.rand((B,), generator=self.gen, device=dev)
+            drawn, lp_drawn = self.ops.residual_sample_lp(score, torch.stack(dls, 1).to(score.dtype).contiguous(), n_acc, r, bonus,
+                                                          inv_t, d_threshold=d_thr, t_threshold=t_thr, top_k=cfg.target_top_k,
+                                                          top_p=target_top_p)
+            if self.keep_inputs:
+                self.step_inputs.append(dict(logits=score.clone(), bonus=bonus.clone(), tok=tok32.clone(), lp_d=lp_d.clone(),
+                                             u=u.clone(), lp_t=lp_t.clone(), n_acc=n_acc.clone(), drawn=drawn.clone(),
+                                             lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone(),
+                                             t_thr=None if t_thr is None else t_thr.clone()))
+            self.ops.commit_step_lp(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            steps += 1
+            if steps % cfg.sync_every == 0 and int(seq_len.min().item()) >= cap:
+                break
+            if steps > max_tokens + cfg.sync_every:      # cannot happen: every step appends >= 1 token per unfinished row
+                raise RuntimeError("stage loop did not terminate")
+        self.last_steps = steps
+        return tokens, lps
+
+
+class StageManager:
+    """The reference's StageManager(stage_configs, gpu_allocation) (server.py:163): stages in the order of `stage_configs`,
+    stage i drafting for stage i + 1.  `ops`: the arithmetic behind every step (default distributed.HipOps -> libasd_hip.so on
+    the current GPU); a CPU ops object makes every stage run on CPU tensors, as in serving/hierarchy.py.  `gpu_allocation`
+    ({size: [gpu ids]}) is accepted and reported by get_model_info(); multi-rank stages are not built, all stages share the
+    ops' device."""
+
+    def __init__(self, stage_configs: Sequence[StageConfig], gpu_allocation: Optional[Dict[str, List[int]]] = None, ops=None):
+        self.ops = ops if ops is not None else HipOps()
+        self.gpu_allocation = dict(gpu_allocation or {})
+        self.device = torch.device("cuda", torch.cuda.current_device()) if isinstance(self.ops, HipOps) else torch.device("cpu")
+        self.stages: Dict[str, Stage] = {}
+        below: Optional[Stage] = None
+        for i, cfg in enumerate(stage_configs):
+            if cfg.model_size in self.stages:
+                raise ValueError(f"duplicate stage {cfg.model_size!r}")
+            below = self.stages[cfg.model_size] = Stage(cfg, i, below, self.ops, self.device)
+        self.names = tuple(self.stages)
+
+    def get_stage(self, name: str) -> Stage:
+        return self.stages[name]
+
+    def warmup_all(self, max_tokens: int = 2) -> None:
+        for s in self.stages.values():
+            s.generate(["warm up"], max_tokens=max_tokens)
+
+    def get_model_info(self) -> Dict[str, Dict[str, object]]:
+        return {n: dict(s.get_model_info(), gpus=self.gpu_allocation.get(n)) for n, s in self.stages.items()}

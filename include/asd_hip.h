@@ -299,6 +299,15 @@ int asd_decoder_forward(const asd_layer_t* layers, int n_layers, const asd_decod
 int asd_commit_step(const int32_t* tok /*[B,K]*/, const int32_t* n_acc /*[B]*/, const int32_t* drawn /*[B]*/,
                     int B, int K, int32_t* seq_len /*[B] in/out*/, int32_t* out_tokens /*[B][ld_out]*/,
                     int64_t ld_out, int32_t* n_commit /*[B] out, may be NULL*/, int32_t max_len, void* stream);
+/* asd_commit_step with a second scatter: the per-token log-probs a stage returns (stage.generate(..., return_logprobs=True),
+ * src/serving/pipeline.py:204-231) follow the tokens into out_lp ([B][ld_out] f32, the geometry of out_tokens):
+ * out_lp[b, len + k] = lp_tok[b, k] for k < n_acc[b] (the verify's lp_target), out_lp[b, len + n_acc[b]] = lp_drawn[b]
+ * (asd_residual_sample_lp), under the same clamp to max_len; the bits are copied.  K = 0 (tok and lp_tok may be NULL): every
+ * sequence appends drawn / lp_drawn -- plain sampled decoding.  Status codes: those of asd_commit_step. */
+int asd_commit_step_lp(const int32_t* tok /*[B,K]*/, const float* lp_tok /*[B,K]*/, const int32_t* n_acc /*[B]*/,
+                       const int32_t* drawn /*[B]*/, const float* lp_drawn /*[B]*/, int B, int K,
+                       int32_t* seq_len /*[B] in/out*/, int32_t* out_tokens /*[B][ld_out]*/, float* out_lp /*[B][ld_out]*/,
+                       int64_t ld_out, int32_t* n_commit /*[B] out, may be NULL*/, int32_t max_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,
@@ -539,6 +548,20 @@ int asd_residual_sample_top_k(const void* t_logits, int64_t ld_t, const void* d_
                               float inv_temperature, int top_k, float top_p, const float* t_threshold /*[B,K]*/,
                               const float* d_threshold /*[B,K] or NULL*/, int32_t* token /*[B] out*/,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* asd_residual_sample_lp: asd_residual_sample_top_k that also reports the committed token's TARGET log-prob -- the per-token
+ *   log-prob the reference's stages hand to the quality predictor (stage.generate(..., return_logprobs=True),
+ *   src/serving/pipeline.py:204-231); the verify gives lp_target for the accepted tokens, this call for the one drawn after them.
+ *   lp[b] = log p_t^N(token[b]): p_t^N = softmax(x / T) over the target row the draw used (t_logits[b, n_acc[b]], or the bonus
+ *   row) restricted to that row's threshold and renormalised -- the distribution the step is lossless against, NOT the residual
+ *   weight.  Formed like lp_target: ln 2 * (x_tok * c2 - log2 normaliser).  token[b] == -1 => lp[b] = NaN.  lp must not be NULL.
+ *   Arguments that truncate nothing make it asd_residual_sample_ex (t_threshold ignored); the tokens are those of the
+ *   corresponding existing entry point, bit for bit.  workspace: asd_residual_sample_top_p_workspace_bytes when truncating. */
+int asd_residual_sample_lp(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                           const void* bonus_logits, int64_t ld_b, int dtype,
+                           const int32_t* n_acc /*[B]*/, const float* r /*[B]*/, int B, int K, int V,
+                           float inv_temperature, int top_k, float top_p, const float* t_threshold /*[B,K] or NULL*/,
+                           const float* d_threshold /*[B,K] or NULL*/, int32_t* token /*[B] out*/, float* lp /*[B] out*/,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* N1, second form: asd_verify_accept with the epilogue of asd_predictor_stop run INSIDE the same
  * launch by the wave that completes each sequence (lp = the kernel's own lp_target, all K

@@ -1,0 +1,73 @@
+// Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp and
+// asd_commit_step_lp in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+
+#include "asd_hip.h"
+
+static int failures = 0;
+#define EXPECT(call, want)                                                                 \
+    do {                                                                                   \
+        const int rc_ = (call);                                                            \
+        if (rc_ != (want)) { std::printf("FAIL %s:%d  %s -> %d, want %d\n", __FILE__, __LINE__, #call, rc_, (want)); ++failures; } \
+    } while (0)
+
+int main() {
+    const int B = 4, K = 8, V = 1024, BF16 = 1;
+    alignas(256) static unsigned char rows[16];          // stands for every device buffer: aligned, never read
+    void* p = rows;
+    int32_t* i32 = reinterpret_cast<int32_t*>(rows);
+    float* f32 = reinterpret_cast<float*>(rows);
+    const size_t plain = asd_residual_sample_workspace_bytes(B, V, BF16);
+    const size_t cut = asd_residual_sample_top_p_workspace_bytes(B, V, BF16);
+    if (cut < plain || plain % 256 != 0) { std::printf("FAIL workspace sizes %zu %zu\n", plain, cut); ++failures; }
+
+    // ---- asd_residual_sample_lp
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, nullptr, p, cut, nullptr), ASD_ERR_INVALID_ARG);   // lp
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, 0, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, nullptr, p, cut, nullptr), ASD_OK);                // B == 0
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, NAN, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);        // top_p NaN
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 0.9f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);       // t_threshold
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 50, 0.9f, f32, nullptr, i32, f32, p, plain, nullptr), ASD_ERR_WORKSPACE);                      // truncating call, plain workspace
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, -1, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, -1, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, 0, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, 99, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_UNSUPPORTED);         // dtype
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, nullptr, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);   // n_acc
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, nullptr, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);   // r
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, nullptr, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);   // token
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, nullptr, cut, nullptr), ASD_ERR_INVALID_ARG); // workspace
+    EXPECT(asd_residual_sample_lp(nullptr, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_residual_sample_lp(p, V - 1, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);  // ld_t < V
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V - 1, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);  // ld_b < V
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, -1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_INVALID_ARG);     // temperature
+    EXPECT(asd_residual_sample_lp(p, 1001, p, 1001, p, 1001, BF16, i32, f32, B, K, 1001, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_ALIGNMENT);   // not whole vectors
+    EXPECT(asd_residual_sample_lp(rows + 2, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, cut, nullptr), ASD_ERR_ALIGNMENT);  // misaligned rows
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, rows + 16, cut, nullptr), ASD_ERR_WORKSPACE); // misaligned workspace
+    EXPECT(asd_residual_sample_lp(p, V, p, V, p, V, BF16, i32, f32, B, K, V, 1.0f, 0, 1.0f, nullptr, nullptr, i32, f32, p, plain - 1, nullptr), ASD_ERR_WORKSPACE);   // too small
+
+    // ---- asd_commit_step_lp (the checks of asd_commit_step, plus the three new pointers)
+    const int64_t ld = 64;
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, -1, K, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, -1, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, i32, i32, f32, ld, i32, -1, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(nullptr, nullptr, nullptr, nullptr, nullptr, 0, K, nullptr, nullptr, nullptr, ld, nullptr, 32, nullptr), ASD_OK);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, ASD_MAX_DRAFT_LEN + 1, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_UNSUPPORTED);
+    EXPECT(asd_commit_step_lp(nullptr, f32, i32, i32, f32, B, K, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, nullptr, i32, i32, f32, B, K, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, nullptr, i32, f32, B, K, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, nullptr, f32, B, K, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, nullptr, B, K, i32, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, nullptr, i32, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, i32, nullptr, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, i32, i32, nullptr, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+    EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, i32, i32, f32, 31, i32, 32, nullptr), ASD_ERR_INVALID_ARG);       // ld_out < max_len
+    // the same rejections from the entry point it extends
+    EXPECT(asd_commit_step(i32, i32, i32, B, ASD_MAX_DRAFT_LEN + 1, i32, i32, ld, i32, 32, nullptr), ASD_ERR_UNSUPPORTED);
+    EXPECT(asd_commit_step(i32, i32, i32, B, K, i32, i32, 31, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+
+    std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
+    return failures ? EXIT_FAILURE : EXIT_SUCCESS;
+}

@@ -3,6 +3,7 @@
 they replace (log_softmax + multinomial + gather per drafted token, serving/speculative.py of round 1).
 
     python tools/bench_sampling.py [--out gpurun_out/sampling.json]
+    python tools/bench_sampling.py --lp [--out FILE]     # the log-prob forms beside their parents
 """
 import argparse
 import json
@@ -30,6 +31,61 @@ def timed(fn, reps=200, settle=50):
     return 1e3 * e0.elapsed_time(e1) / reps      # us per call
 
 
+def interleaved(fns, reps, rounds=11):
+    """A/B/A/B ... in one process: `rounds` timings of every candidate, taken in turn so that clock and cache drift hit all of
+    them alike -> {name: {"median_us", "min_us", "max_us"}}; max - min over the rounds is the run-to-run noise."""
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, reps, settle=20))
+    return {k: {"median_us": sorted(v)[len(v) // 2], "min_us": min(v), "max_us": max(v)} for k, v in times.items()}
+
+
+def bench_lp(a, dev):
+    """asd_residual_sample_lp beside asd_residual_sample_ex (B = 32: group form, B = 128: one workgroup per sequence; V = 152064,
+    bf16) and asd_commit_step_lp beside asd_commit_step (B = 32, K = 8)."""
+    V, Kd = 152064, 8
+    res = {}
+    for B in (32, 128):
+        g = torch.Generator(device=dev).manual_seed(B)
+        rows = [(torch.randn((B, V), generator=g, device=dev) * a.scale).to(torch.bfloat16) for _ in range(4)]
+        t3 = torch.stack([rows[j % 4] for j in range(Kd)], 1).contiguous()
+        d3 = torch.stack([rows[(j + 1) % 4] for j in range(Kd)], 1).contiguous()
+        n_acc = torch.randint(0, Kd + 1, (B,), generator=g, device=dev, dtype=torch.int32)
+        r = torch.rand((B,), generator=g, device=dev)
+        rs = K.ResidualSampler(B, V, torch.bfloat16, dev)
+        tok_out = torch.empty((B,), dtype=torch.int32, device=dev)
+        lp_out = torch.empty((B,), dtype=torch.float32, device=dev)
+        res[f"residual_B{B}"] = interleaved({
+            "asd_residual_sample_ex": lambda: rs(t3, d3, n_acc, r, rows[0], 1 / 0.7, out=tok_out),
+            "asd_residual_sample_lp": lambda: rs.lp(t3, d3, n_acc, r, rows[0], 1 / 0.7, out=tok_out, lp_out=lp_out),
+        }, a.reps)
+        print(B, res[f"residual_B{B}"], flush=True)
+    B = 32
+    g = torch.Generator(device=dev).manual_seed(7)
+    tok = torch.randint(0, V, (B, Kd), generator=g, device=dev, dtype=torch.int32)
+    lp_tok = -torch.rand((B, Kd), generator=g, device=dev)
+    n_acc = torch.randint(0, Kd + 1, (B,), generator=g, device=dev, dtype=torch.int32)
+    drawn = torch.randint(0, V, (B,), generator=g, device=dev, dtype=torch.int32)
+    lp_drawn = -torch.rand((B,), generator=g, device=dev)
+    seq_len = torch.zeros((B,), dtype=torch.int32, device=dev)
+    out_tok = torch.zeros((B, 4096), dtype=torch.int32, device=dev)
+    out_lp = torch.zeros((B, 4096), dtype=torch.float32, device=dev)
+    nc = torch.zeros((B,), dtype=torch.int32, device=dev)
+
+    def commit():
+        seq_len.zero_()                             # (the length-reset fill of tools/bench_aux.py: both candidates pay it)
+        K.commit_step(tok, n_acc, drawn, seq_len, out_tok, nc)
+
+    def commit_lp():
+        seq_len.zero_()
+        K.commit_step_lp(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, out_tok, out_lp, nc)
+
+    res["commit_B32_K8"] = interleaved({"asd_commit_step": commit, "asd_commit_step_lp": commit_lp}, a.reps)
+    print("commit", res["commit_B32_K8"], flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "sampling.json"))
@@ -37,8 +93,15 @@ def main():
     ap.add_argument("--batches", default="8,32,128")
     ap.add_argument("--scale", type=float, default=3.0, help="logits = scale * N(0,1): 3 = a wide nucleus (hundreds of tokens at "
                     "T = 0.7, top-p 0.9), 8 = a peaked row (a handful of tokens), closer to a confident LLM step")
+    ap.add_argument("--lp", action="store_true", help="time asd_residual_sample_lp / asd_commit_step_lp beside their parents, interleaved")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.lp:
+        res = bench_lp(a, dev)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     V = 152064
     res = {}
     for B in [int(x) for x in a.batches.split(",")]:
