@@ -43,6 +43,59 @@ __global__ __launch_bounds__(64) void k_commit_step(const int32_t* tok, const fl
     }
 }
 
+// asd_commit_step_stop: k_commit_step<true> with a stop set.  The wave finds the first committed candidate that is a stop id with
+// one ballot (lane k tests draft token k; the drawn token, candidate n_acc, is tested by every lane alike, so K = 64 needs no
+// 65th lane), cuts the append behind it, and lane 0 records why the row ended: finished[b] = 1 (stop) / 2 (length) and one
+// ordinary atomic add on *n_finished at the 0 -> non-zero transition.  A row that enters finished is left as it is.
+__global__ __launch_bounds__(64) void k_commit_step_stop(const int32_t* tok, const float* lp_tok, const int32_t* n_acc,
+                                                         const int32_t* drawn, const float* lp_drawn, int B, int K,
+                                                         const int32_t* stop_ids, int n_stop, int32_t* seq_len, int32_t* out_tokens,
+                                                         float* out_lp, int64_t ld_out, int32_t* n_commit, int32_t* finished,
+                                                         int32_t* n_finished, int32_t max_len) {
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int len = seq_len[b];                      // every lane reads the old length and flag before lane 0 rewrites them
+    if (finished[b] != 0) {                          // wave-uniform
+        if (lane == 0 && n_commit) n_commit[b] = 0;
+        return;
+    }
+    int na = n_acc[b];
+    na = na < 0 ? 0 : (na > K ? K : na);
+    int fit = max_len - len;
+    fit = fit < 0 ? 0 : (fit > na + 1 ? na + 1 : fit);
+    const int32_t d = drawn[b];
+    const int32_t c = lane < na ? tok[static_cast<int64_t>(b) * K + lane] : d;
+    bool c_stops = false, d_stops = false;
+    for (int s = 0; s < n_stop; ++s) {
+        const int32_t id = stop_ids[s];
+        c_stops |= c == id;
+        d_stops |= d == id;
+    }
+    // rejected draft tokens (lane >= na) and candidates cut off by max_len (index >= fit) never stop a row
+    const unsigned long long hits = __ballot(c_stops && lane < na && lane < fit);
+    int j = hits ? __ffsll(hits) - 1 : ((d_stops && na < fit) ? na : -1);
+    const int appended = j >= 0 ? j + 1 : fit;
+    int32_t* row = out_tokens + static_cast<int64_t>(b) * ld_out;
+    if (lane < na && lane < appended) {
+        row[len + lane] = c;
+        out_lp[static_cast<int64_t>(b) * ld_out + len + lane] = lp_tok[static_cast<int64_t>(b) * K + lane];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) {
+        if (na < appended) {
+            row[len + na] = d;
+            out_lp[static_cast<int64_t>(b) * ld_out + len + na] = lp_drawn[b];
+        }
+        seq_len[b] = len + appended;
+        if (n_commit) n_commit[b] = appended;
+        const int32_t reason = j >= 0 ? 1 : (len + appended >= max_len ? 2 : 0);     // stop wins on the last free slot
+        if (reason) {
+            finished[b] = reason;
+            if (n_finished) atomicAdd(n_finished, 1);
+        }
+    }
+}
+
 }  // namespace
 }  // namespace asd
 
@@ -71,5 +124,20 @@ ASD_EXPORT int asd_commit_step_lp(const int32_t* tok, const float* lp_tok, const
     if (ld_out < max_len) return ASD_ERR_INVALID_ARG;
     hipLaunchKernelGGL(k_commit_step<true>, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, lp_tok, n_acc, drawn,
                        lp_drawn, B, K, seq_len, out_tokens, out_lp, ld_out, n_commit, max_len);
+    return launch_status();
+}
+
+ASD_EXPORT int asd_commit_step_stop(const int32_t* tok, const float* lp_tok, const int32_t* n_acc, const int32_t* drawn,
+                                    const float* lp_drawn, int B, int K, const int32_t* stop_ids, int n_stop, int32_t* seq_len,
+                                    int32_t* out_tokens, float* out_lp, int64_t ld_out, int32_t* n_commit, int32_t* finished,
+                                    int32_t* n_finished, int32_t max_len, void* stream) {
+    if (B < 0 || K < 0 || max_len < 0 || n_stop < 0) return ASD_ERR_INVALID_ARG;
+    if (B == 0) return ASD_OK;
+    if (K > ASD_MAX_DRAFT_LEN || n_stop > ASD_MAX_STOP_IDS) return ASD_ERR_UNSUPPORTED;
+    if ((K > 0 && (!tok || !lp_tok)) || !n_acc || !drawn || !lp_drawn || !seq_len || !out_tokens || !out_lp) return ASD_ERR_INVALID_ARG;
+    if (!finished || (n_stop > 0 && !stop_ids)) return ASD_ERR_INVALID_ARG;
+    if (ld_out < max_len) return ASD_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_commit_step_stop, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, lp_tok, n_acc, drawn,
+                       lp_drawn, B, K, stop_ids, n_stop, seq_len, out_tokens, out_lp, ld_out, n_commit, finished, n_finished, max_len);
     return launch_status();
 }

@@ -298,6 +298,14 @@ class HipOps:
         """commit_step with the log-probs scattered beside the tokens (asd_commit_step_lp); tok = lp_tok = None: K = 0."""
         self.K.commit_step_lp(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, max_len=max_len)
 
+    @traced("commit_step_stop")
+    def commit_step_stop(self, tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, max_len, stop_ids, finished,
+                         n_finished):
+        """commit_step_lp that ends a row at a stop token (asd_commit_step_stop): stop_ids i32 [S], finished i32 [B] (0 / 1 stop /
+        2 length), n_finished i32 [1] -- the counter the stage loop reads every few steps."""
+        self.K.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, finished, stop_ids=stop_ids,
+                                n_finished=n_finished, n_commit=n_commit, max_len=max_len)
+
     @traced("lambda_sweep")
     def lambda_sweep(self, p_hist, costs, lams):
         """N4: the DP rule for every (lambda, sequence) pair in one launch -> k_star [G, n] i32."""

@@ -431,6 +431,41 @@ def commit_step_lp(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor], 
     B.check("asd_commit_step_lp", rc)
 
 
+def commit_step_stop(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor], n_acc: torch.Tensor, drawn: torch.Tensor,
+                     lp_drawn: torch.Tensor, seq_len: torch.Tensor, out_tokens: torch.Tensor, out_lp: torch.Tensor,
+                     finished: torch.Tensor, stop_ids: Optional[torch.Tensor] = None, n_finished: Optional[torch.Tensor] = None,
+                     n_commit: Optional[torch.Tensor] = None, max_len: Optional[int] = None) -> None:
+    """commit_step_lp that ends a sequence at a stop token (asd_commit_step_stop): the append is cut behind the first committed
+    token that is in `stop_ids` (device int32 [S], S <= 8; None: no stop set) and that token is kept.  finished [B] i32 in/out:
+    0 running, 1 stopped, 2 reached max_len; a row that enters non-zero is left alone (n_commit 0).  n_finished [1] i32 in/out:
+    rows that finished so far -- the one value a host loop reads."""
+    Bv = drawn.shape[0]
+    K = 0 if tok is None else tok.shape[1]
+    if tok is not None and (tok.shape[0] != Bv or lp_tok is None or lp_tok.shape != tok.shape):
+        raise ValueError("tok and lp_tok must both be [B, K]")
+    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
+        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
+    if out_lp.shape != out_tokens.shape or out_lp.stride() != out_tokens.stride():
+        raise ValueError("out_lp must have the shape and strides of out_tokens")
+    if finished.shape != (Bv,):
+        raise ValueError("finished must be [B] int32")
+    if stop_ids is not None and stop_ids.dim() != 1:
+        raise ValueError("stop_ids must be [S] int32")
+    if n_finished is not None and n_finished.numel() != 1:
+        raise ValueError("n_finished must hold one int32")
+    n_stop = 0 if stop_ids is None else stop_ids.shape[0]
+    cap = out_tokens.shape[1] if max_len is None else int(max_len)
+    rc = _lib().asd_commit_step_stop(_opt(tok, "tok", torch.int32), _opt(lp_tok, "lp_tok", torch.float32),
+                                     _dev(n_acc, "n_acc", torch.int32), _dev(drawn, "drawn", torch.int32),
+                                     _dev(lp_drawn, "lp_drawn", torch.float32), Bv, K,
+                                     _opt(stop_ids, "stop_ids", torch.int32) if n_stop else None, n_stop,
+                                     _dev(seq_len, "seq_len", torch.int32), _dev(out_tokens, "out_tokens", torch.int32),
+                                     _dev(out_lp, "out_lp", torch.float32), out_tokens.stride(0),
+                                     _opt(n_commit, "n_commit", torch.int32), _dev(finished, "finished", torch.int32),
+                                     _opt(n_finished, "n_finished", torch.int32), cap, _stream())
+    B.check("asd_commit_step_stop", rc)
+
+
 # ------------------------------------------------------------------------------- predictor side
 def logprob_stats(lp: torch.Tensor, n_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A7: [B,K] f32 log-probs -> [B,5] f64 (mean, std, min, q25, median), numpy semantics."""

@@ -1,7 +1,7 @@
 """Adaptive cascade pipeline -- API of the reference's src/serving/pipeline.py, with the decision
 arithmetic of the stage loop (Bayes adjustment, DP stop rule) done by batched kernels.
 
-    PipelineConfig                  pipeline.py:22-31   (+ stop_rule, stage_names: build extensions)
+    PipelineConfig                  pipeline.py:22-31   (+ stop_rule, stage_names, stop_token_ids: build extensions)
     RequestResult                   pipeline.py:34-45
     AdaptiveSpeculativePipeline     pipeline.py:48-423
         process_request / process_request_async / batch_process / update_lambda / get_stats /
@@ -68,6 +68,7 @@ class PipelineConfig:
     stage_names: Sequence[str] = DEFAULT_STAGE_NAMES
     stage_priors: Optional[Sequence[float]] = None          # prior p for not-yet-run stages ("full")
     batch_grouping: str = "none"                            # batch_process: "none" (one batch, the reference's shape) | "predicted_stage"
+    stop_token_ids: Optional[Sequence[int]] = None          # EOS ids handed to stage.generate(stop_token_ids=); None: the keyword is not passed
 
     @classmethod
     def from_yaml(cls, path: str) -> "PipelineConfig":
@@ -93,6 +94,8 @@ class PipelineConfig:
             kw["stage_priors"] = tuple(float(x) for x in sec["stage_priors"])
         if "batch_grouping" in sec:
             kw["batch_grouping"] = str(sec["batch_grouping"])
+        if sec.get("stop_token_ids") is not None:
+            kw["stop_token_ids"] = tuple(int(x) for x in sec["stop_token_ids"])
         return cls(**kw)
 
 
@@ -313,9 +316,10 @@ class AdaptiveSpeculativePipeline:
                     todo.append(r)
             gen_out: Dict[str, Any] = {}
             if todo:
+                stop_kw = {} if cfg.stop_token_ids is None else {"stop_token_ids": tuple(cfg.stop_token_ids)}
                 texts, logprobs, stage_stats = stage.generate(prompts=[r.current_prompt for r in todo],
                                                               max_tokens=max_tokens, temperature=temperature,
-                                                              return_logprobs=True)
+                                                              return_logprobs=True, **stop_kw)
                 for j, r in enumerate(todo):
                     lp = logprobs[j] if logprobs is not None and len(logprobs) > j else np.array([])
                     gen_out[r.request_id] = (texts[j], lp)

@@ -17,7 +17,17 @@ is a `SyntheticLM` (model execution is plumbing, third party in the reference) a
               stage would report.
 
 Nothing synchronises inside a step; the host reads min(seq_len) every `sync_every` steps, and `ops.check_status()` runs before
-results are returned.  There is no EOS in this project: every sequence returns exactly `max_tokens` tokens and log-probs.
+results are returned.
+
+STOP TOKENS (EOS).  With a stop set (`StageConfig.stop_token_ids`, or `generate(stop_token_ids=...)`; at most 8 distinct ids) both
+loops commit through asd_commit_step_stop: a sequence ends behind the first COMMITTED token that is a stop id -- the token is kept,
+with its log-prob; a rejected draft token never ends anything -- or at `max_tokens`.  The kernel keeps a per-sequence flag
+(1 stop, 2 length) and a counter of finished sequences; the host reads that ONE int32 every `sync_every` steps (in place of
+min(seq_len); the plain loop gains the same read) and leaves the loop when it equals the batch size.  A finished sequence stays in
+the batch: its length, and so every position it is fed at, is frozen, its draws are discarded by the commit and its model work is
+wasted -- compacting the batch is not done here.  texts[i] / logprobs[i] then hold n_i tokens, 1 <= n_i <= max_tokens, and `stats`
+says why each sequence ended.  Without a stop set a stage runs the asd_commit_step_lp path and every sequence returns exactly
+`max_tokens` tokens and log-probs.
 
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
@@ -66,6 +76,22 @@ class StageConfig:
     draft_len: int = 8
     seed: int = 0
     sync_every: int = 4
+    stop_token_ids: Sequence[int] = ()       # EOS ids: a sequence ends behind the first committed one (module docstring)
+
+
+MAX_STOP_IDS = 8                             # ASD_MAX_STOP_IDS of include/asd_hip.h
+_REASONS = {1: "stop", 2: "length"}
+
+
+def _check_stop_ids(ids: Sequence[int], vocab: int) -> Tuple[int, ...]:
+    ids = tuple(int(i) for i in ids)
+    if len(ids) > MAX_STOP_IDS:
+        raise ValueError(f"at most {MAX_STOP_IDS} stop token ids, got {len(ids)}")
+    if len(set(ids)) != len(ids):
+        raise ValueError("stop token ids must be distinct")
+    if any(not 0 <= i < vocab for i in ids):
+        raise ValueError(f"stop token ids must lie in [0, {vocab})")
+    return ids
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -75,6 +101,20 @@ def _shape_of(cfg: StageConfig) -> LMShape:
     if key not in QWEN25_SHAPES:
         raise ValueError(f"no model shape for stage {cfg.model_size!r}: set StageConfig.shape")
     return QWEN25_SHAPES[key]
+
+
+class _StopState:
+    """What a generate call with a stop set keeps beside seq_len: the ids on the device (uploaded once), the per-sequence
+    finished flag and the counter asd_commit_step_stop maintains."""
+
+    def __init__(self, stop_ids: Sequence[int], B: int, device):
+        self.B = B
+        self.stop_ids = torch.tensor(list(stop_ids), dtype=torch.int32, device=device)
+        self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.n_finished = torch.zeros((1,), dtype=torch.int32, device=device)
+
+    def all_finished(self) -> bool:
+        return int(self.n_finished.item()) == self.B         # the loop's one host read
 
 
 class Stage:
@@ -128,14 +168,19 @@ class Stage:
     # ------------------------------------------------------------------------------------------ generate
     @torch.no_grad()
     def generate(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7, return_logprobs: bool = True,
-                 top_p: Optional[float] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, float]]:
+                 top_p: Optional[float] = None, stop_token_ids: Optional[Sequence[int]] = None
+                 ) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
-        ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [max_tokens],
-        log-prob of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the
-        nucleus of that distribution for the call: StageConfig.top_p at stage 0, StageConfig.target_top_p at a verifying stage."""
+        ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
+        of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
+        distribution for the call: StageConfig.top_p at stage 0, StageConfig.target_top_p at a verifying stage.
+        `stop_token_ids`: None = StageConfig.stop_token_ids, an empty sequence = no stop set.  n_i = max_tokens without a stop set;
+        with one, the tokens up to and including the first stop id (module docstring).  stats["n_tokens"][i] = n_i and
+        stats["finish_reasons"][i] = "stop" | "length"."""
         t0 = time.perf_counter()
         prompts = list(prompts)
         self.step_inputs = []
+        stop = _check_stop_ids(self.config.stop_token_ids if stop_token_ids is None else stop_token_ids, self.shape.vocab)
         if not prompts or max_tokens <= 0:
             return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -143,18 +188,29 @@ class Stage:
             raise ValueError("temperature must be > 0 (sampled decoding)")
         ids = self.encode_prompts(prompts)
         inv_t = float(np.float32(1.0 / temperature))
+        B, P = ids.shape
+        end = _StopState(stop, B, ids.device) if stop else None
         if self.draft is None:
-            tokens, lps = self._decode_plain(ids, int(max_tokens), inv_t, self.config.top_p if top_p is None else float(top_p))
+            tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
+                                                      self.config.top_p if top_p is None else float(top_p), end)
         else:
-            tokens, lps = self._decode_speculative(ids, int(max_tokens), inv_t,
-                                                   self.config.target_top_p if top_p is None else float(top_p))
+            tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
+                                                            self.config.target_top_p if top_p is None else float(top_p), end)
         self.ops.check_status()
-        P = ids.shape[1]
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
-        texts = [self.decode_tokens(row) for row in tok_h]
-        stats = {"generation_time_ms": (time.perf_counter() - t0) * 1000.0, "steps": float(self.last_steps)}
-        return texts, ([np.ascontiguousarray(r) for r in lp_h] if return_logprobs else None), stats
+        if end is None:
+            n_tok, reasons = [int(max_tokens)] * B, ["length"] * B
+        else:
+            n_tok = [int(n) - P for n in seq_len.cpu().tolist()]
+            flags = end.finished.cpu().tolist()
+            if any(f not in _REASONS for f in flags) or any(not 1 <= n <= max_tokens for n in n_tok):
+                raise RuntimeError("stage loop ended with an unfinished sequence")
+            reasons = [_REASONS[f] for f in flags]
+        texts = [self.decode_tokens(row[:n]) for row, n in zip(tok_h, n_tok)]
+        stats = {"generation_time_ms": (time.perf_counter() - t0) * 1000.0, "steps": float(self.last_steps),
+                 "n_tokens": n_tok, "finish_reasons": reasons}
+        return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -175,8 +231,17 @@ class Stage:
             return self.ops.draft_sample_top_k(logits, r, inv_t, top_k=cfg.top_k, top_p=top_p)
         return self.ops.draft_sample(logits, r, inv_t, top_p)
 
-    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float):
-        """Stage 0.  Every sequence appends exactly one token per step, so all positions are known on the host."""
+    def _commit(self, end, tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap):
+        if end is None:
+            self.ops.commit_step_lp(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+        else:
+            self.ops.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap, end.stop_ids,
+                                      end.finished, end.n_finished)
+
+    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None):
+        """Stage 0.  Without a stop set every sequence appends exactly one token per step, so all positions are known on the
+        host; with one (`end`), a sequence is fed its last committed token at seq_len - 1, which is the same for a running
+        sequence and stays put for a finished one."""
         B, P = ids.shape
         dev = ids.device
         cap = P + max_tokens
@@ -189,14 +254,21 @@ class Stage:
         for step in range(max_tokens):
             logits = logits.contiguous()
             tok, lp, thr = self._propose(self.config, logits, inv_t, top_p)
-            self.ops.commit_step_lp(None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
+            self._commit(end, None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
             if self.keep_inputs:
                 self.step_inputs.append(dict(logits=logits.clone(), drawn=tok.clone(), lp_drawn=lp.clone(), thr=thr.clone()))
+            self.last_steps = step + 1
+            if end is not None and (step + 1) % self.config.sync_every == 0 and end.all_finished():
+                break
             if step + 1 < max_tokens:
-                pos = torch.full((B,), P + step, dtype=torch.int64, device=dev)
-                logits = m.forward_ragged(tok.to(torch.int64)[:, None], pos, P + step + 1)[:, -1]
-        self.last_steps = max_tokens
-        return tokens, lps
+                if end is None:
+                    pos = torch.full((B,), P + step, dtype=torch.int64, device=dev)
+                    last = tok.to(torch.int64)[:, None]
+                else:
+                    pos = seq_len.to(torch.int64) - 1
+                    last = tokens.gather(1, pos[:, None]).to(torch.int64)
+                logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
+        return tokens, lps, seq_len
 
     def _verify(self, score, tok32, lp_d, u, inv_t, top_k, top_p):
         """-> (lp_t, n_acc, t_threshold or None) against the target's Temperature -> (TopK ->) (TopP) distribution."""
@@ -209,7 +281,7 @@ class Stage:
         lp_t, _, n_acc, _ = self.ops.verify_accept(score, tok32, lp_d, u, inv_t)
         return lp_t, n_acc, None
 
-    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float):
+    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None):
         """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
 
         Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
@@ -263,14 +335,14 @@ class Stage:
                                              u=u.clone(), lp_t=lp_t.clone(), n_acc=n_acc.clone(), drawn=drawn.clone(),
                                              lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone(),
                                              t_thr=None if t_thr is None else t_thr.clone()))
-            self.ops.commit_step_lp(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            self._commit(end, tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
             steps += 1
-            if steps % cfg.sync_every == 0 and int(seq_len.min().item()) >= cap:
+            if steps % cfg.sync_every == 0 and (int(seq_len.min().item()) >= cap if end is None else end.all_finished()):
                 break
             if steps > max_tokens + cfg.sync_every:      # cannot happen: every step appends >= 1 token per unfinished row
                 raise RuntimeError("stage loop did not terminate")
         self.last_steps = steps
-        return tokens, lps
+        return tokens, lps, seq_len
 
 
 class StageManager:

@@ -47,6 +47,7 @@ typedef enum asd_dtype {
 
 /* limits enforced by the launchers */
 #define ASD_MAX_DRAFT_LEN 64   /* K: one ballot word per sequence */
+#define ASD_MAX_STOP_IDS 8     /* stop (EOS) token ids of asd_commit_step_stop */
 #define ASD_MAX_STAGES 16      /* L: tiers in the DP rule */
 #define ASD_MAX_SPLITS 64      /* vocab splits per row inside one launch */
 #define ASD_MAX_MLP_DIM 1024   /* predictor input / hidden width */
@@ -308,6 +309,26 @@ int asd_commit_step_lp(const int32_t* tok /*[B,K]*/, const float* lp_tok /*[B,K]
                        const int32_t* drawn /*[B]*/, const float* lp_drawn /*[B]*/, int B, int K,
                        int32_t* seq_len /*[B] in/out*/, int32_t* out_tokens /*[B][ld_out]*/, float* out_lp /*[B][ld_out]*/,
                        int64_t ld_out, int32_t* n_commit /*[B] out, may be NULL*/, int32_t max_len, void* stream);
+/* asd_commit_step_lp that ends a sequence at a stop (EOS) token: what HF `generate`'s EOS handling does behind the reference's
+ * stage.generate (src/serving/pipeline.py:204-209), decided on the device so that a step still reads nothing back.
+ * Row b, na = clamp(n_acc[b], 0, K), len = seq_len[b], candidates c_0..c_na = tok[b, 0..na) ++ drawn[b]:
+ *   finished[b] != 0 on entry: the row is left alone (seq_len, finished, *n_finished unchanged), n_commit[b] = 0.
+ *   otherwise fit = min(na + 1, max(max_len - len, 0)); j* = the smallest j < fit with c_j in stop_ids[0..n_stop);
+ *   appended = j* + 1 if j* exists, else fit.  The first `appended` candidates and their log-probs go to index len.. as in
+ *   asd_commit_step_lp (bits copied), seq_len[b] = len + appended, n_commit[b] = appended.  The stop token itself is committed;
+ *   a rejected draft token (index >= na) and a stop token cut off by max_len never stop a row.
+ *   finished[b] = 1 (stop) if j* exists -- also when it lands on the last free slot --, else 2 (length) if
+ *   len + appended >= max_len (a row that enters full included), else it stays 0.  A row going 0 -> non-zero adds 1 to
+ *   *n_finished (may be NULL) with a global atomic: the host reads that one counter to leave its loop.
+ * n_stop == 0 (stop_ids may be NULL) with all flags zero: tokens, log-probs, seq_len and n_commit are asd_commit_step_lp's.
+ * Status codes: those of asd_commit_step_lp; finished == NULL, n_stop < 0, n_stop > 0 with stop_ids == NULL: invalid argument;
+ * n_stop > ASD_MAX_STOP_IDS: unsupported. */
+int asd_commit_step_stop(const int32_t* tok /*[B,K]*/, const float* lp_tok /*[B,K]*/, const int32_t* n_acc /*[B]*/,
+                         const int32_t* drawn /*[B]*/, const float* lp_drawn /*[B]*/, int B, int K,
+                         const int32_t* stop_ids /*[n_stop]*/, int n_stop, int32_t* seq_len /*[B] in/out*/,
+                         int32_t* out_tokens /*[B][ld_out]*/, float* out_lp /*[B][ld_out]*/, int64_t ld_out,
+                         int32_t* n_commit /*[B] out, may be NULL*/, int32_t* finished /*[B] in/out: 0, 1 stop, 2 length*/,
+                         int32_t* n_finished /*[1] in/out, may be NULL*/, int32_t max_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,

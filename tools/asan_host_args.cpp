@@ -1,5 +1,5 @@
-// Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp and
-// asd_commit_step_lp in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
+// asd_commit_step_lp and asd_commit_step_stop in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -64,6 +64,29 @@ int main() {
     EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, i32, nullptr, f32, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
     EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, i32, i32, nullptr, ld, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
     EXPECT(asd_commit_step_lp(i32, f32, i32, i32, f32, B, K, i32, i32, f32, 31, i32, 32, nullptr), ASD_ERR_INVALID_ARG);       // ld_out < max_len
+    // ---- asd_commit_step_stop (the checks of asd_commit_step_lp, plus the stop set and the finished flag)
+#define STOP(tok_, lp_tok_, n_acc_, drawn_, lp_drawn_, B_, K_, stops_, n_stop_, seq_, out_, out_lp_, ld_, fin_, max_len_) \
+    asd_commit_step_stop(tok_, lp_tok_, n_acc_, drawn_, lp_drawn_, B_, K_, stops_, n_stop_, seq_, out_, out_lp_, ld_, i32, fin_, i32, max_len_, nullptr)
+    EXPECT(STOP(i32, f32, i32, i32, f32, -1, K, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, -1, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, 2, i32, i32, f32, ld, i32, -1), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(nullptr, nullptr, nullptr, nullptr, nullptr, 0, K, nullptr, 0, nullptr, nullptr, nullptr, ld, nullptr, 32), ASD_OK);
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, ASD_MAX_DRAFT_LEN + 1, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_UNSUPPORTED);
+    EXPECT(STOP(nullptr, f32, i32, i32, f32, B, K, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, nullptr, i32, i32, f32, B, K, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, nullptr, i32, f32, B, K, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, nullptr, f32, B, K, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, i32, nullptr, B, K, i32, 2, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, 2, nullptr, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, 2, i32, nullptr, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, 2, i32, i32, nullptr, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, 2, i32, i32, f32, 31, i32, 32), ASD_ERR_INVALID_ARG);                  // ld_out < max_len
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, 2, i32, i32, f32, ld, nullptr, 32), ASD_ERR_INVALID_ARG);              // finished
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, -1, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);                 // n_stop < 0
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, nullptr, 1, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);              // ids missing
+    EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, ASD_MAX_STOP_IDS + 1, i32, i32, f32, ld, i32, 32), ASD_ERR_UNSUPPORTED);
+    EXPECT(STOP(i32, f32, i32, i32, f32, -1, K, nullptr, 0, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);             // no stop set: B is still checked
+#undef STOP
     // the same rejections from the entry point it extends
     EXPECT(asd_commit_step(i32, i32, i32, B, ASD_MAX_DRAFT_LEN + 1, i32, i32, ld, i32, 32, nullptr), ASD_ERR_UNSUPPORTED);
     EXPECT(asd_commit_step(i32, i32, i32, B, K, i32, i32, 31, i32, 32, nullptr), ASD_ERR_INVALID_ARG);

@@ -43,7 +43,7 @@ def interleaved(fns, reps, rounds=11):
 
 def bench_lp(a, dev):
     """asd_residual_sample_lp beside asd_residual_sample_ex (B = 32: group form, B = 128: one workgroup per sequence; V = 152064,
-    bf16) and asd_commit_step_lp beside asd_commit_step (B = 32, K = 8)."""
+    bf16) and asd_commit_step_lp / asd_commit_step_stop beside asd_commit_step (B = 32, K = 8)."""
     V, Kd = 152064, 8
     res = {}
     for B in (32, 128):
@@ -81,7 +81,22 @@ def bench_lp(a, dev):
         seq_len.zero_()
         K.commit_step_lp(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, out_tok, out_lp, nc)
 
-    res["commit_B32_K8"] = interleaved({"asd_commit_step": commit, "asd_commit_step_lp": commit_lp}, a.reps)
+    # asd_commit_step_stop on the same inputs with a two-id stop set that no input token hits: no row ever finishes (the length
+    # is reset every call, the rows are 4096 wide), so every call does the whole commit, like the two beside it
+    present = set(tok.flatten().tolist()) | set(drawn.tolist())
+    stop_ids = torch.tensor([i for i in range(V - 1, 0, -1) if i not in present][:2], dtype=torch.int32, device=dev)
+    finished = torch.zeros((B,), dtype=torch.int32, device=dev)
+    n_finished = torch.zeros((1,), dtype=torch.int32, device=dev)
+
+    def commit_stop():
+        seq_len.zero_()
+        K.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, out_tok, out_lp, finished, stop_ids=stop_ids,
+                           n_finished=n_finished, n_commit=nc)
+
+    res["commit_B32_K8"] = interleaved({"asd_commit_step": commit, "asd_commit_step_lp": commit_lp,
+                                        "asd_commit_step_stop": commit_stop}, a.reps)
+    if int(n_finished.item()) != 0:
+        raise RuntimeError("a row finished during the timing: the three candidates did not do the same work")
     print("commit", res["commit_B32_K8"], flush=True)
     return res
 
@@ -93,7 +108,7 @@ def main():
     ap.add_argument("--batches", default="8,32,128")
     ap.add_argument("--scale", type=float, default=3.0, help="logits = scale * N(0,1): 3 = a wide nucleus (hundreds of tokens at "
                     "T = 0.7, top-p 0.9), 8 = a peaked row (a handful of tokens), closer to a confident LLM step")
-    ap.add_argument("--lp", action="store_true", help="time asd_residual_sample_lp / asd_commit_step_lp beside their parents, interleaved")
+    ap.add_argument("--lp", action="store_true", help="time asd_residual_sample_lp / asd_commit_step_lp / asd_commit_step_stop beside their parents, interleaved")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     if a.lp:
