@@ -32,6 +32,7 @@ SOURCES = {
     "verify_nucleus.hip": [],     # shares draft_sample.hip's select (sample_device.hpp) and its flags: the same bits
     "decoder.hip": [],
     "commit.hip": [],
+    "greedy.hip": ["-ffp-contract=off"],          # lp_argmax / lp_target end in finish_row's arithmetic, as verify_accept.hip's do
     "lm_head_verify.hip": ["-ffp-contract=off"],  # ends in the same finish_row arithmetic as verify_accept.hip
     "decision.hip": ["-ffp-contract=off"],
     "predictor.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=11"],   # k_predictor_stop_w64x32's leading arguments

@@ -289,6 +289,20 @@ class HipOps:
         return s.lp(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_k=top_k, top_p=top_p, t_threshold=t_threshold,
                     d_threshold=d_threshold)
 
+    @traced("verify_greedy")
+    def verify_greedy(self, logits, tok=None, inv_temperature: float = 1.0, splits: int = 0):
+        """Greedy decoding's step (asd_verify_greedy): logits [B,K+1,V] read in place (or [B,V] with tok = None: K = 0), tok i32
+        [B,K] -> (lp_t [B,K], n_acc [B], drawn [B], lp_drawn [B], argmax [B,K+1], lp_argmax [B,K+1]).  One verifier (workspace)
+        per shape and calling thread, like `_sampler`."""
+        K = 0 if tok is None else tok.shape[1]
+        Bv, V = logits.shape[0], logits.shape[-1]
+        key = ("greedy", K, V, str(logits.dtype), str(logits.device))
+        g = self._ws.get(key)
+        if g is None or g.B < Bv:
+            g = self._ws[key] = self.K.GreedyVerifier(Bv, K, V, logits.dtype, logits.device)
+        r = g(logits, tok, inv_temperature, splits)
+        return r.lp_target, r.n_acc, r.drawn, r.lp_drawn, r.argmax, r.lp_argmax
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

@@ -776,3 +776,72 @@ class DraftSampler(_StatusWorkspace):
         threshold of the top-p select taken over the top-k set.  HF generate(do_sample=True, ...) applies top_k = 50 unless
         told otherwise.  top_k <= 0 or >= V is __call__ (the same bits); otherwise one workgroup per row, the workspace unused."""
         return self._draw("asd_draft_sample_top_k", logits, r, inv_temperature, (int(top_k), float(top_p)), out)
+
+
+# ------------------------------------------------------------------------------- greedy decoding (temperature 0)
+@dataclass
+class GreedyResult:
+    lp_target: torch.Tensor   # [B,K]   f32  log p_target(tok) (-inf: tok outside the vocabulary)
+    accept: torch.Tensor      # [B,K]   u8   tok == argmax of its row
+    n_acc: torch.Tensor       # [B]     i32  accepted-prefix length
+    drawn: torch.Tensor       # [B]     i32  argmax[b, n_acc[b]]: the token committed behind the prefix (-1: no finite logit)
+    lp_drawn: torch.Tensor    # [B]     f32  its log-prob
+    argmax: torch.Tensor      # [B,K+1] i32  the lowest id among each row's maxima
+    lp_argmax: torch.Tensor   # [B,K+1] f32
+
+
+class GreedyVerifier:
+    """asd_verify_greedy with its workspace and outputs: arg-max, accepted prefix and commit token of every sequence from the
+    target's [B, K+1, V] logits in ONE launch, read in place (any sequence / row stride, unit stride along V); K = 0 takes
+    [B, V] -- the plain greedy step.  The workspace is zeroed by every call itself (no asd_workspace_init, no status word).
+    `out` holds the outputs of a full-size call; a call writes there with `out=verifier.out`, into fresh tensors otherwise
+    (the stage loop keeps the K draft steps' tokens side by side)."""
+
+    def __init__(self, B_: int, K: int, V: int, dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None):
+        self.B, self.K, self.V, self.dtype = B_, K, V, dtype
+        self.device = device or torch.device("cuda")
+        self.bytes = int(_lib().asd_verify_greedy_workspace_bytes(B_, K, V, _DTYPE_CODE[dtype]))
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+        self.out = self.new_out(B_)
+
+    def new_out(self, Bv: int) -> GreedyResult:
+        K, dev = self.K, self.device
+        return GreedyResult(torch.empty((Bv, K), dtype=torch.float32, device=dev), torch.empty((Bv, K), dtype=torch.uint8, device=dev),
+                            torch.empty((Bv,), dtype=torch.int32, device=dev), torch.empty((Bv,), dtype=torch.int32, device=dev),
+                            torch.empty((Bv,), dtype=torch.float32, device=dev),
+                            torch.empty((Bv, K + 1), dtype=torch.int32, device=dev),
+                            torch.empty((Bv, K + 1), dtype=torch.float32, device=dev))
+
+    def __call__(self, logits: torch.Tensor, tok: Optional[torch.Tensor] = None, inv_temperature: float = 1.0, splits: int = 0,
+                 out: Optional[GreedyResult] = None) -> GreedyResult:
+        K, V = self.K, self.V
+        if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != self.dtype:
+            raise ValueError(f"logits must be a {self.dtype} CUDA (HIP) tensor; this package has no CPU path")
+        if logits.dim() == 2 and K == 0:
+            logits = logits[:, None]
+        if logits.dim() != 3 or logits.shape[1] != K + 1 or logits.shape[2] != V or logits.stride(2) != 1:
+            raise ValueError(f"logits must be [B, {K + 1}, {V}]" + (f" or [B, {V}]" if K == 0 else "") + " with unit stride along V")
+        Bv = logits.shape[0]
+        if Bv > self.B:
+            raise ValueError(f"verifier was sized for B <= {self.B}")
+        # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
+        ld_row = logits.stride(1) if K > 0 else V
+        ld_seq = logits.stride(0) if Bv > 1 else (K + 1) * ld_row
+        if ld_row < V or ld_seq < (K + 1) * ld_row:
+            raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= (K + 1) row strides")
+        if K > 0:
+            if tok is None or tuple(tok.shape) != (Bv, K):
+                raise ValueError("tok must be [B, K]")
+            tok_p = _dev(tok, "tok", torch.int32)
+        else:
+            tok_p = None
+        if out is None:
+            out = self.new_out(Bv)
+        rc = _lib().asd_verify_greedy(logits.data_ptr(), _DTYPE_CODE[logits.dtype], ld_seq, ld_row, tok_p, Bv, K, V,
+                                      float(inv_temperature), int(splits), _dev(out.argmax, "argmax", torch.int32),
+                                      _dev(out.lp_argmax, "lp_argmax", torch.float32), _dev(out.lp_target, "lp_target", torch.float32),
+                                      _dev(out.accept, "accept", torch.uint8), _dev(out.n_acc, "n_acc", torch.int32),
+                                      _dev(out.drawn, "drawn", torch.int32), _dev(out.lp_drawn, "lp_drawn", torch.float32),
+                                      self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_verify_greedy", rc)
+        return out

@@ -29,6 +29,13 @@ wasted -- compacting the batch is not done here.  texts[i] / logprobs[i] then ho
 says why each sequence ended.  Without a stop set a stage runs the asd_commit_step_lp path and every sequence returns exactly
 `max_tokens` tokens and log-probs.
 
+GREEDY DECODING.  `temperature == 0.0` (the reference's server and core types allow it; it is the setting of reproducible
+evaluation runs) selects arg-max decoding on ops.verify_greedy (asd_verify_greedy): stage 0 makes one K = 0 call per step, a
+verifying stage drafts with K = 0 calls on the draft's logits and makes ONE call on the target's [B, K+1, V] output, in place.
+The generator is not consumed (the result does not depend on StageConfig.seed), top_p / top_k / target_top_p / target_top_k are
+ignored (the arg-max is in every nucleus), and the log-probs are the model's at temperature 1 (what vLLM returns for
+temperature 0).  Ties go to the lowest id.  Stop tokens work as above.  Negative temperatures raise.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -184,17 +191,19 @@ class Stage:
         if not prompts or max_tokens <= 0:
             return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
-        if not temperature > 0.0:
-            raise ValueError("temperature must be > 0 (sampled decoding)")
+        if not temperature >= 0.0:                       # (NaN included)
+            raise ValueError("temperature must be >= 0 (0: greedy decoding)")
         ids = self.encode_prompts(prompts)
-        inv_t = float(np.float32(1.0 / temperature))
         B, P = ids.shape
         end = _StopState(stop, B, ids.device) if stop else None
-        if self.draft is None:
-            tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
+        if temperature == 0.0:                           # greedy: no draws, no truncation (module docstring)
+            decode = self._decode_plain_greedy if self.draft is None else self._decode_speculative_greedy
+            tokens, lps, seq_len = decode(ids, int(max_tokens), end)
+        elif self.draft is None:
+            tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), float(np.float32(1.0 / temperature)),
                                                       self.config.top_p if top_p is None else float(top_p), end)
         else:
-            tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
+            tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), float(np.float32(1.0 / temperature)),
                                                             self.config.target_top_p if top_p is None else float(top_p), end)
         self.ops.check_status()
         tok_h = tokens[:, P:].cpu().numpy()
@@ -268,6 +277,86 @@ class Stage:
                     pos = seq_len.to(torch.int64) - 1
                     last = tokens.gather(1, pos[:, None]).to(torch.int64)
                 logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
+        return tokens, lps, seq_len
+
+    def _decode_plain_greedy(self, ids: torch.Tensor, max_tokens: int, end=None):
+        """Stage 0 at temperature 0: _decode_plain with one verify_greedy call (K = 0) per step in place of the draw; the logits
+        are read where the model left them."""
+        B, P = ids.shape
+        dev = ids.device
+        cap = P + max_tokens
+        tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
+        m = self.model
+        m.reset()
+        m.alloc_ragged(B, cap + 1)
+        logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
+        for step in range(max_tokens):
+            lp_t, n_acc, tok, lp, argmax, lp_argmax = self.ops.verify_greedy(logits, None, 1.0)
+            if self.keep_inputs:
+                self.step_inputs.append(dict(logits=logits.clone(), tok=None, n_acc=n_acc.clone(), argmax=argmax.clone(),
+                                             lp_argmax=lp_argmax.clone(), lp_t=lp_t.clone(), drawn=tok.clone(),
+                                             lp_drawn=lp.clone(), seq_len=seq_len.clone()))
+            self._commit(end, None, None, n_acc, tok, lp, seq_len, tokens, lps, n_commit, cap)
+            self.last_steps = step + 1
+            if end is not None and (step + 1) % self.config.sync_every == 0 and end.all_finished():
+                break
+            if step + 1 < max_tokens:
+                if end is None:
+                    pos = torch.full((B,), P + step, dtype=torch.int64, device=dev)
+                    last = tok.to(torch.int64)[:, None]
+                else:
+                    pos = seq_len.to(torch.int64) - 1
+                    last = tokens.gather(1, pos[:, None]).to(torch.int64)
+                logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
+        return tokens, lps, seq_len
+
+    def _decode_speculative_greedy(self, ids: torch.Tensor, max_tokens: int, end=None):
+        """Stage s > 0 at temperature 0: _decode_speculative's step with the draft's arg-max as the proposal (K = 0 calls on the
+        draft logits) and ONE verify_greedy call on the target's [B, K+1, V] output as returned -- no copies of the score and
+        bonus rows, no kept draft logits, no uniforms.  A draft token is accepted iff it is the target row's arg-max, the token
+        behind the accepted prefix is the arg-max of the next row (row K: the bonus row), so the text is the target's own greedy
+        continuation.  Log-probs are the target's at temperature 1."""
+        cfg = self.config
+        draft, target = self.draft.model, self.model
+        B, P = ids.shape
+        dev = ids.device
+        Kd = cfg.draft_len
+        cap = P + max_tokens
+        tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
+        for m in (draft, target):
+            m.reset()
+            m.alloc_ragged(B, cap + Kd + 2)
+        zero = torch.zeros((B,), dtype=torch.int64, device=dev)
+        target.forward_ragged(ids[:, :P - 1], zero, P)
+        if P > 2:
+            draft.forward_ragged(ids[:, :P - 2], zero, P)
+        rows = torch.arange(B, device=dev)
+        steps = 0
+        while True:
+            L = seq_len.to(torch.int64)
+            window = min(P + steps * (Kd + 1) + Kd + 1, cap + Kd + 2)
+            last2 = torch.stack([tokens[rows, L - 2], tokens[rows, L - 1]], 1).to(torch.int64)
+            dl = draft.forward_ragged(last2, L - 2, window)[:, -1]
+            toks = []
+            for k in range(Kd):
+                t = self.ops.verify_greedy(dl, None, 1.0)[2]
+                toks.append(t)
+                if k + 1 < Kd:
+                    dl = draft.forward_ragged(t.to(torch.int64)[:, None], L + k, window)[:, -1]
+            tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
+            t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
+            lp_t, n_acc, drawn, lp_drawn, argmax, lp_argmax = self.ops.verify_greedy(t_out, tok32, 1.0)
+            if self.keep_inputs:
+                self.step_inputs.append(dict(logits=t_out.clone(), tok=tok32.clone(), n_acc=n_acc.clone(), argmax=argmax.clone(),
+                                             lp_argmax=lp_argmax.clone(), lp_t=lp_t.clone(), drawn=drawn.clone(),
+                                             lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone()))
+            self._commit(end, tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            steps += 1
+            if steps % cfg.sync_every == 0 and (int(seq_len.min().item()) >= cap if end is None else end.all_finished()):
+                break
+            if steps > max_tokens + cfg.sync_every:
+                raise RuntimeError("stage loop did not terminate")
+        self.last_steps = steps
         return tokens, lps, seq_len
 
     def _verify(self, score, tok32, lp_d, u, inv_t, top_k, top_p):

@@ -331,6 +331,36 @@ int asd_commit_step_stop(const int32_t* tok /*[B,K]*/, const float* lp_tok /*[B,
                          int32_t* n_finished /*[1] in/out, may be NULL*/, int32_t max_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Greedy decoding (temperature 0): arg-max verify and commit token in one launch, no random numbers.
+ * The reference accepts temperature 0 (src/serving/server.py:44,67; src/core/types.py:240,267).
+ * logits: sequence b owns K + 1 rows, row (b, k) starts at element b*ld_seq + k*ld_row: rows 0..K-1 score the draft tokens
+ * tok[b, k], row K is the bonus row (the row convention of asd_lm_head_verify_ex; a target's [B, K+1, V] output is read in
+ * place).  K == 0: one row per sequence, the plain greedy step.  Any V >= 1 and any element-aligned row base (16-byte loads
+ * where the address allows, scalar head and tail); ld_row >= V, ld_seq >= (K+1)*ld_row; the padding is never read.
+ * Per row: argmax = the lowest id among the maxima; a NaN logit never wins; -1 if the row has no logit above -inf.
+ *   lp_argmax = x[argmax]*inv_temperature - lse(x*inv_temperature), NaN where argmax == -1.
+ * Per sequence: accept[b,k] = (argmax[b,k] >= 0 && tok[b,k] == argmax[b,k]); n_acc[b] = length of the accepted prefix;
+ *   drawn[b] = argmax[b, n_acc[b]], lp_drawn[b] = that row's lp_argmax; lp_target[b,k] = x[tok]*inv_temperature - lse (what
+ *   asd_verify_accept reports), -inf for tok outside [0,V); on an accepted position it has the bits of lp_argmax[b,k].
+ * splits: workgroups per row in [1, ASD_MAX_SPLITS], 0 = heuristic (asd_device_cu_count).  A geometry gives the same bits on
+ * every run.  Nothing in the kernel waits, so there is no status word; the launcher zeroes the tickets (hipMemsetAsync) ahead
+ * of every launch: the workspace needs no asd_workspace_init, calls in stream order may share one, calls in flight together
+ * need one each.
+ * Status: NULL n_acc / drawn / lp_drawn, inv_temperature not > 0 (both before the empty-batch return), negative sizes, V == 0,
+ * NULL logits / workspace, tok == NULL with K > 0, ld_row < V, ld_seq < (K+1)*ld_row: invalid argument; K > ASD_MAX_DRAFT_LEN,
+ * unknown dtype, splits outside [0, ASD_MAX_SPLITS], a row of 2 GiB or more: unsupported; workspace misaligned (256) or too
+ * small: workspace; B == 0: ASD_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+size_t asd_verify_greedy_workspace_bytes(int B, int K, int V, int dtype);   /* sized for ASD_MAX_SPLITS; a multiple of 256 */
+int asd_verify_greedy(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row,
+                      const int32_t* tok /*[B,K]; may be NULL when K == 0*/, int B, int K, int V,
+                      float inv_temperature, int splits /*workgroups per row, 0 = heuristic*/,
+                      int32_t* argmax_out /*[B,K+1] out, may be NULL*/, float* lp_argmax /*[B,K+1] out, may be NULL*/,
+                      float* lp_target /*[B,K] out, may be NULL*/, uint8_t* accept /*[B,K] out, may be NULL*/,
+                      int32_t* n_acc /*[B] out*/, int32_t* drawn /*[B] out*/, float* lp_drawn /*[B] out*/,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,
  * src/training/generate_training_data.py:166-175 -- np.mean, np.std (population), np.min,
  * np.percentile(.,25) (linear interpolation), np.median, all in float64 like numpy.

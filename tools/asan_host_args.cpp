@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp and asd_commit_step_stop in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop and asd_verify_greedy in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -90,6 +90,48 @@ int main() {
     // the same rejections from the entry point it extends
     EXPECT(asd_commit_step(i32, i32, i32, B, ASD_MAX_DRAFT_LEN + 1, i32, i32, ld, i32, 32, nullptr), ASD_ERR_UNSUPPORTED);
     EXPECT(asd_commit_step(i32, i32, i32, B, K, i32, i32, 31, i32, 32, nullptr), ASD_ERR_INVALID_ARG);
+
+    // ---- asd_verify_greedy: NULL outputs and the temperature first (both ahead of the empty-batch return), then sizes, the empty batch,
+    // K / dtype / splits, pointers, strides, alignment, the workspace
+    {
+        const int KG = 4, VG = 1000;
+        const int64_t ldr = VG, lds = static_cast<int64_t>(KG + 1) * VG;
+        uint8_t* u8 = rows;
+        const size_t ws = asd_verify_greedy_workspace_bytes(B, KG, VG, BF16);
+        if (ws % 256 != 0 || ws < asd_verify_greedy_workspace_bytes(B, 0, VG, BF16) || asd_verify_greedy_workspace_bytes(0, KG, VG, BF16) != 256) {
+            std::printf("FAIL greedy workspace size %zu\n", ws);
+            ++failures;
+        }
+#define GREEDY(logits_, dtype_, lds_, ldr_, tok_, B_, K_, V_, inv_t_, splits_, n_acc_, drawn_, lp_drawn_, ws_, ws_bytes_) \
+    asd_verify_greedy(logits_, dtype_, lds_, ldr_, tok_, B_, K_, V_, inv_t_, splits_, i32, f32, f32, u8, n_acc_, drawn_, lp_drawn_, ws_, ws_bytes_, nullptr)
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 0, nullptr, i32, f32, p, ws), ASD_ERR_INVALID_ARG);           // n_acc
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 0, i32, nullptr, f32, p, ws), ASD_ERR_INVALID_ARG);           // drawn
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 0, i32, i32, nullptr, p, ws), ASD_ERR_INVALID_ARG);           // lp_drawn
+        EXPECT(GREEDY(nullptr, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);         // logits
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 0, i32, i32, f32, nullptr, ws), ASD_ERR_INVALID_ARG);         // workspace
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 0.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);               // temperature
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, -1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, NAN, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, INFINITY, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, 0, KG, VG, 0.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);               // ... before the empty batch
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, -1, KG, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, -1, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(GREEDY(p, BF16, 0, 0, i32, B, KG, 0, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                    // V == 0
+        EXPECT(GREEDY(p, BF16, lds, ldr, nullptr, B, KG, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);           // tok == NULL, K > 0
+        EXPECT(GREEDY(p, BF16, ldr, ldr, nullptr, B, 0, VG, 1.0f, 0, i32, i32, f32, p, 0), ASD_ERR_WORKSPACE);               // K == 0 needs no tok
+        EXPECT(GREEDY(p, BF16, lds, ldr - 1, i32, B, KG, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);           // ld_row < V
+        EXPECT(GREEDY(p, BF16, lds - 1, ldr, i32, B, KG, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_INVALID_ARG);           // ld_seq < (K+1) ld_row
+        EXPECT(GREEDY(p, BF16, 66 * ldr, ldr, i32, B, ASD_MAX_DRAFT_LEN + 1, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);
+        EXPECT(GREEDY(p, 99, lds, ldr, i32, B, KG, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);                 // dtype
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, -1, i32, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);              // splits
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, ASD_MAX_SPLITS + 1, i32, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);
+        EXPECT(GREEDY(rows + 1, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 0, i32, i32, f32, p, ws), ASD_ERR_ALIGNMENT);          // below the element size
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 0, i32, i32, f32, rows + 16, ws), ASD_ERR_WORKSPACE);         // misaligned workspace
+        EXPECT(GREEDY(p, BF16, lds, ldr, i32, B, KG, VG, 1.0f, ASD_MAX_SPLITS, i32, i32, f32, p, ws - 1), ASD_ERR_WORKSPACE); // too small
+        EXPECT(GREEDY(rows + 2, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 1, i32, i32, f32, p, 0), ASD_ERR_WORKSPACE);           // (an element-aligned base is valid)
+        EXPECT(GREEDY(nullptr, 99, 0, 0, nullptr, 0, KG, VG, 1.0f, 0, nullptr, nullptr, nullptr, nullptr, 0), ASD_OK);       // B == 0: nothing launched
+#undef GREEDY
+    }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
     return failures ? EXIT_FAILURE : EXIT_SUCCESS;
