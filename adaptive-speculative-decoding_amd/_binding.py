@@ -20,6 +20,7 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 MAX_DRAFT_LEN = 64
 MAX_STAGES = 16
 MAX_SPLITS = 64
+MAX_TOP_LOGPROBS = 8
 MAX_MLP_DIM = 1024
 NUM_LP_STATS = 5
 WS_LOST_HANDOFF = 0x1
@@ -86,6 +87,9 @@ SIGNATURES = {
     "asd_commit_step_stop": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _vp]),
     "asd_verify_greedy_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "asd_verify_greedy": (_i, [_vp, _i, _i64, _i64, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "asd_top_logprobs_workspace_bytes": (_sz, [_i, _i, _i]),
+    "asd_top_logprobs": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "asd_commit_top_logprobs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "asd_logprob_stats": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     "asd_mlp_packed_floats": (_sz, [_i, _i]),
     "asd_mlp_pack_weights": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),

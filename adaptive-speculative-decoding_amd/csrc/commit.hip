@@ -96,6 +96,30 @@ __global__ __launch_bounds__(64) void k_commit_step_stop(const int32_t* tok, con
     }
 }
 
+// asd_commit_top_logprobs: the top-N table of a step follows the step's commit.  It runs BEHIND asd_commit_step_lp /
+// asd_commit_step_stop and reads what they left: seq_len[b] (already advanced) and n_commit[b].  Row j < n_commit[b] of
+// top[b] -- the distribution the step's j-th committed token came from -- goes to position seq_len[b] - n_commit[b] + j of
+// out[b].  One wave per sequence walks the n_commit * N entries; bits are copied.
+__global__ __launch_bounds__(64) void k_commit_top_logprobs(const int32_t* top_id, const float* top_lp, const int32_t* seq_len,
+                                                            const int32_t* n_commit, int B, int K1, int N, int32_t* out_id,
+                                                            float* out_lp, int max_len) {
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int nc = n_commit[b];
+    const int64_t first = static_cast<int64_t>(seq_len[b]) - nc;
+    const int rows = nc < 0 ? 0 : (nc > K1 ? K1 : nc);
+    const int32_t* const src_id = top_id + static_cast<int64_t>(b) * K1 * N;
+    const float* const src_lp = top_lp + static_cast<int64_t>(b) * K1 * N;
+    for (int e = lane; e < rows * N; e += 64) {
+        const int j = e / N;
+        const int64_t pos = first + j;
+        if (pos < 0 || pos >= max_len) continue;
+        const int64_t at = (static_cast<int64_t>(b) * max_len + pos) * N + (e - j * N);
+        out_id[at] = src_id[e];
+        out_lp[at] = src_lp[e];
+    }
+}
+
 }  // namespace
 }  // namespace asd
 
@@ -139,5 +163,17 @@ ASD_EXPORT int asd_commit_step_stop(const int32_t* tok, const float* lp_tok, con
     if (ld_out < max_len) return ASD_ERR_INVALID_ARG;
     hipLaunchKernelGGL(k_commit_step_stop, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, lp_tok, n_acc, drawn,
                        lp_drawn, B, K, stop_ids, n_stop, seq_len, out_tokens, out_lp, ld_out, n_commit, finished, n_finished, max_len);
+    return launch_status();
+}
+
+ASD_EXPORT int asd_commit_top_logprobs(const int32_t* top_id, const float* top_lp, const int32_t* seq_len, const int32_t* n_commit,
+                                       int B, int K1, int N, int32_t* out_id, float* out_lp, int max_len, void* stream) {
+    if (B < 0 || K1 < 0 || N < 0 || max_len < 0) return ASD_ERR_INVALID_ARG;
+    if (B == 0) return ASD_OK;
+    if (K1 > ASD_MAX_DRAFT_LEN + 1 || N > ASD_MAX_TOP_LOGPROBS) return ASD_ERR_UNSUPPORTED;
+    if (K1 < 1 || N < 1) return ASD_ERR_INVALID_ARG;
+    if (!top_id || !top_lp || !seq_len || !n_commit || !out_id || !out_lp) return ASD_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_commit_top_logprobs, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), top_id, top_lp, seq_len,
+                       n_commit, B, K1, N, out_id, out_lp, max_len);
     return launch_status();
 }

@@ -30,6 +30,10 @@ inline int dtype_size(int dtype) {
 // number of CUs of the CURRENT device (cached per device id; the query is slow)
 int current_device_cus();
 
+// workgroups per row of the row-streaming kernels that cut a row into vocabulary slices (greedy.hip, which defines it, and
+// top_logprobs.hip): R rows of V elements of esz bytes on `cus` compute units
+int choose_splits(int64_t R, int V, int esz, int cus);
+
 // ---- shared by the launchers of the sampling steps, the verify step (verify_accept.hip) and the lm_head / linear kernels ----
 
 // f(std::integral_constant<int, ASD_DTYPE_*>{}): the kernels take the element type as a template argument.  Whatever is not

@@ -340,9 +340,11 @@ inline Layout layout(int B, int K, int splits) {
     return w;
 }
 
+}  // namespace
+
 // Workgroups per row.  Whole rows where they fill the CUs evenly; otherwise the estimate verify_accept.hip fitted to its slice
 // sweeps (bytes of the fullest CU, floored by the chip-wide stream, plus a fixed cost per workgroup), which this kernel has not
-// been swept against.  A slice is never cut below 16 KiB.
+// been swept against.  A slice is never cut below 16 KiB.  (Declared in common.hpp: top_logprobs.hip streams the same geometry.)
 int choose_splits(int64_t R, int V, int esz, int cus) {
     if (R <= 0 || cus <= 0) return 1;
     if (R >= cus && (R % cus == 0 || 10 * (R % cus) >= 6 * cus || R / cus >= 6)) return 1;
@@ -363,7 +365,6 @@ int choose_splits(int64_t R, int V, int esz, int cus) {
     return best;
 }
 
-}  // namespace
 }  // namespace asd
 
 using namespace asd;

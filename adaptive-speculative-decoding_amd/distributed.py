@@ -303,6 +303,26 @@ class HipOps:
         r = g(logits, tok, inv_temperature, splits)
         return r.lp_target, r.n_acc, r.drawn, r.lp_drawn, r.argmax, r.lp_argmax
 
+    @traced("top_logprobs")
+    def top_logprobs(self, logits, n, inv_temperature: float = 1.0, splits: int = 0):
+        """The `n` most likely tokens of every row and their log-probs over the whole vocabulary (asd_top_logprobs): logits
+        [B,K1,V] -- a strided view is read in place, nothing is copied -- or [B,V] -> (top_id i32 [B,K1,n], top_lp f32 [B,K1,n]),
+        value descending then id ascending, (-1, -inf) in slots that cannot be filled.  One workspace per shape and calling
+        thread, like `verify_greedy`."""
+        K1 = 1 if logits.dim() == 2 else logits.shape[1]
+        Bv, V = logits.shape[0], logits.shape[-1]
+        key = ("top_logprobs", K1, V, int(n), str(logits.dtype), str(logits.device))
+        t = self._ws.get(key)
+        if t is None or t.B < Bv:
+            t = self._ws[key] = self.K.TopLogprobs(Bv, K1, V, logits.dtype, int(n), logits.device)
+        return t(logits, inv_temperature, splits)
+
+    @traced("commit_top_logprobs")
+    def commit_top_logprobs(self, top_id, top_lp, seq_len, n_commit, out_id, out_lp, max_len):
+        """The step's top-N rows follow its commit (asd_commit_top_logprobs); runs behind commit_step_lp / commit_step_stop and
+        reads the seq_len / n_commit they left."""
+        self.K.commit_top_logprobs(top_id, top_lp, seq_len, n_commit, out_id, out_lp, max_len=max_len)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

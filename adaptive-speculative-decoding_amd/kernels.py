@@ -845,3 +845,76 @@ class GreedyVerifier:
                                       self.buf.data_ptr(), self.bytes, _stream())
         B.check("asd_verify_greedy", rc)
         return out
+
+
+# ------------------------------------------------------------------------------- top-N log-probs (SamplingParams(logprobs=N))
+MAX_TOP_LOGPROBS = B.MAX_TOP_LOGPROBS
+
+
+class TopLogprobs:
+    """asd_top_logprobs with its workspace and outputs: the `n` most likely tokens of every row of [B, K1, V] logits and their
+    log-probs over the whole vocabulary, read in place (any sequence / row stride, unit stride along V); K1 = 1 also takes
+    [B, V].  Order: value descending, then id ascending; slots that cannot be filled hold (-1, -inf).  The workspace is zeroed
+    by every call itself.  `out` = (top_id i32 [B,K1,n], top_lp f32 [B,K1,n]) holds the outputs of a full-size call; a call
+    writes there with `out=obj.out`, into fresh tensors otherwise."""
+
+    def __init__(self, B_: int, K1: int, V: int, dtype: torch.dtype = torch.bfloat16, n: int = 5,
+                 device: Optional[torch.device] = None):
+        if not 1 <= int(n) <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"n must be in [1, {MAX_TOP_LOGPROBS}]")
+        self.B, self.K1, self.V, self.dtype, self.n = B_, K1, V, dtype, int(n)
+        self.device = device or torch.device("cuda")
+        self.bytes = int(_lib().asd_top_logprobs_workspace_bytes(B_, K1, self.n))
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+        self.out = self.new_out(B_)
+
+    def new_out(self, Bv: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return (torch.empty((Bv, self.K1, self.n), dtype=torch.int32, device=self.device),
+                torch.empty((Bv, self.K1, self.n), dtype=torch.float32, device=self.device))
+
+    def __call__(self, logits: torch.Tensor, inv_temperature: float = 1.0, splits: int = 0,
+                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        K1, V = self.K1, self.V
+        if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != self.dtype:
+            raise ValueError(f"logits must be a {self.dtype} CUDA (HIP) tensor; this package has no CPU path")
+        if logits.dim() == 2 and K1 == 1:
+            logits = logits[:, None]
+        if logits.dim() != 3 or logits.shape[1] != K1 or logits.shape[2] != V or logits.stride(2) != 1:
+            raise ValueError(f"logits must be [B, {K1}, {V}]" + (f" or [B, {V}]" if K1 == 1 else "") + " with unit stride along V")
+        Bv = logits.shape[0]
+        if Bv > self.B:
+            raise ValueError(f"sized for B <= {self.B}")
+        # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
+        ld_row = logits.stride(1) if K1 > 1 else V
+        ld_seq = logits.stride(0) if Bv > 1 else K1 * ld_row
+        if ld_row < V or ld_seq < K1 * ld_row:
+            raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= K1 row strides")
+        if out is None:
+            out = self.new_out(Bv)
+        top_id, top_lp = out
+        if tuple(top_id.shape) != (Bv, K1, self.n) or tuple(top_lp.shape) != (Bv, K1, self.n):
+            raise ValueError("out must be (int32 [B, K1, n], float32 [B, K1, n])")
+        rc = _lib().asd_top_logprobs(logits.data_ptr(), _DTYPE_CODE[logits.dtype], ld_seq, ld_row, Bv, K1, V,
+                                     float(inv_temperature), self.n, int(splits), _dev(top_id, "top_id", torch.int32),
+                                     _dev(top_lp, "top_lp", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_top_logprobs", rc)
+        return out
+
+
+def commit_top_logprobs(top_id: torch.Tensor, top_lp: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor,
+                        out_id: torch.Tensor, out_lp: torch.Tensor, max_len: Optional[int] = None) -> None:
+    """The top-N rows of a step follow its commit (asd_commit_top_logprobs): out[b, seq_len[b] - n_commit[b] + j] = top[b, j]
+    for j < n_commit[b], with seq_len / n_commit as asd_commit_step_lp / asd_commit_step_stop left them.  top_id i32 / top_lp
+    f32 [B, K1, N]; out_id i32 / out_lp f32 [B, max_len, N], contiguous; bits are copied."""
+    if top_id.dim() != 3 or top_lp.shape != top_id.shape:
+        raise ValueError("top_id and top_lp must both be [B, K1, N]")
+    Bv, K1, N = top_id.shape
+    cap = out_id.shape[1] if max_len is None else int(max_len)
+    if tuple(out_id.shape) != (Bv, cap, N) or out_lp.shape != out_id.shape:
+        raise ValueError("out_id and out_lp must both be [B, max_len, N]")
+    if seq_len.shape != (Bv,) or n_commit.shape != (Bv,):
+        raise ValueError("seq_len and n_commit must be [B] int32")
+    rc = _lib().asd_commit_top_logprobs(_dev(top_id, "top_id", torch.int32), _dev(top_lp, "top_lp", torch.float32),
+                                        _dev(seq_len, "seq_len", torch.int32), _dev(n_commit, "n_commit", torch.int32), Bv, K1, N,
+                                        _dev(out_id, "out_id", torch.int32), _dev(out_lp, "out_lp", torch.float32), cap, _stream())
+    B.check("asd_commit_top_logprobs", rc)

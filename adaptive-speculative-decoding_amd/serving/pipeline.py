@@ -1,7 +1,7 @@
 """Adaptive cascade pipeline -- API of the reference's src/serving/pipeline.py, with the decision
 arithmetic of the stage loop (Bayes adjustment, DP stop rule) done by batched kernels.
 
-    PipelineConfig                  pipeline.py:22-31   (+ stop_rule, stage_names, stop_token_ids: build extensions)
+    PipelineConfig                  pipeline.py:22-31   (+ stop_rule, stage_names, stop_token_ids, logprobs: build extensions)
     RequestResult                   pipeline.py:34-45
     AdaptiveSpeculativePipeline     pipeline.py:48-423
         process_request / process_request_async / batch_process / update_lambda / get_stats /
@@ -69,6 +69,10 @@ class PipelineConfig:
     stage_priors: Optional[Sequence[float]] = None          # prior p for not-yet-run stages ("full")
     batch_grouping: str = "none"                            # batch_process: "none" (one batch, the reference's shape) | "predicted_stage"
     stop_token_ids: Optional[Sequence[int]] = None          # EOS ids handed to stage.generate(stop_token_ids=); None: the keyword is not passed
+    # top-N log-probs (the specification's SamplingParams(logprobs=5), RESEARCH_PROTOCOL.md:272-277): handed to
+    # stage.generate(logprobs=); the predictor then receives the [n_tokens, N] table as `draft_logprobs` (what
+    # FeatureExtractor.extract is written for) in place of the 1-D vector.  None: the keyword is not passed
+    logprobs: Optional[int] = None
 
     @classmethod
     def from_yaml(cls, path: str) -> "PipelineConfig":
@@ -96,6 +100,8 @@ class PipelineConfig:
             kw["batch_grouping"] = str(sec["batch_grouping"])
         if sec.get("stop_token_ids") is not None:
             kw["stop_token_ids"] = tuple(int(x) for x in sec["stop_token_ids"])
+        if sec.get("logprobs") is not None:
+            kw["logprobs"] = int(sec["logprobs"])
         return cls(**kw)
 
 
@@ -317,14 +323,20 @@ class AdaptiveSpeculativePipeline:
             gen_out: Dict[str, Any] = {}
             if todo:
                 stop_kw = {} if cfg.stop_token_ids is None else {"stop_token_ids": tuple(cfg.stop_token_ids)}
+                if cfg.logprobs is not None:
+                    stop_kw["logprobs"] = int(cfg.logprobs)
                 texts, logprobs, stage_stats = stage.generate(prompts=[r.current_prompt for r in todo],
                                                               max_tokens=max_tokens, temperature=temperature,
                                                               return_logprobs=True, **stop_kw)
+                tables = (stage_stats or {}).get("top_logprobs") if cfg.logprobs else None
                 for j, r in enumerate(todo):
                     lp = logprobs[j] if logprobs is not None and len(logprobs) > j else np.array([])
+                    entry = {"output": texts[j], "logprobs": lp}
+                    if tables is not None:                              # the [n_j, N] table takes the vector's place at the predictor
+                        entry["top_logprobs"] = lp = tables[j]
                     gen_out[r.request_id] = (texts[j], lp)
                     if self.cache_manager:
-                        self.cache_manager.allocate(r.request_id, i, {"output": texts[j], "logprobs": lp})
+                        self.cache_manager.allocate(r.request_id, i, entry)
                 logger.debug("Stage %d: %d generated, time=%.1fms", i, len(todo),
                              float(stage_stats.get("generation_time_ms", 0.0)) if stage_stats else 0.0)
             # -- predictor (host objects, per request as in the reference) ...

@@ -36,6 +36,20 @@ The generator is not consumed (the result does not depend on StageConfig.seed), 
 ignored (the arg-max is in every nucleus), and the log-probs are the model's at temperature 1 (what vLLM returns for
 temperature 0).  Ties go to the lowest id.  Stop tokens work as above.  Negative temperatures raise.
 
+TOP-N LOG-PROBS.  `generate(logprobs=N)` (or `StageConfig.logprobs`), 1 <= N <= 8, is the specification's
+`SamplingParams(logprobs=N)` (RESEARCH_PROTOCOL.md:272-277): for every committed token, the N most likely tokens of the
+distribution it came from and their log-probs, in `stats["top_token_ids"]` / `stats["top_logprobs"]`.  Every loop adds one
+ops.top_logprobs call per step (asd_top_logprobs) -- a verifying stage on the target's [B, K+1, V] output as returned, stage 0
+on its [B, V] logits -- and one ops.commit_top_logprobs call behind the step's commit, which moves row j of the step to the
+position of the step's j-th committed token on the device (accepted draft token j was scored by row j, the token drawn behind
+the prefix by row n_acc).  The draft model's proposal rows get no table.  Nothing is read back inside a step, the generator is
+not consumed, and tokens and log-probs are the same bits with and without the table.  The table is the UNTRUNCATED
+temperature-scaled distribution (temperature 1 when greedy): with top-k / top-p active the committed token's own log-prob is
+renormalised over the nucleus and so is not less than its table entry, and a committed token always lies inside the nucleus.
+COST: a sampled verifying step then reads the target rows three times (verify, residual draw, top-N), about one more verify
+kernel's time in a step dominated by the model passes; with `logprobs` off (0, the default) a stage runs exactly the launches
+it ran before.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -84,9 +98,11 @@ class StageConfig:
     seed: int = 0
     sync_every: int = 4
     stop_token_ids: Sequence[int] = ()       # EOS ids: a sequence ends behind the first committed one (module docstring)
+    logprobs: int = 0                        # top-N log-probs per committed token, 0..8 (0: off; module docstring)
 
 
 MAX_STOP_IDS = 8                             # ASD_MAX_STOP_IDS of include/asd_hip.h
+MAX_TOP_LOGPROBS = 8                         # ASD_MAX_TOP_LOGPROBS
 _REASONS = {1: "stop", 2: "length"}
 
 
@@ -99,6 +115,12 @@ def _check_stop_ids(ids: Sequence[int], vocab: int) -> Tuple[int, ...]:
     if any(not 0 <= i < vocab for i in ids):
         raise ValueError(f"stop token ids must lie in [0, {vocab})")
     return ids
+
+
+def _check_logprobs(n) -> int:
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs must be an integer in [0, {MAX_TOP_LOGPROBS}], got {n!r}")
+    return int(n)
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -122,6 +144,28 @@ class _StopState:
 
     def all_finished(self) -> bool:
         return int(self.n_finished.item()) == self.B         # the loop's one host read
+
+
+class _TopState:
+    """What a generate call with logprobs = n > 0 keeps beside the token buffer: the [B, cap, n] tables the commit fills
+    (positions count from the start of the row, prompt included, like `tokens`) and the step's two calls."""
+
+    def __init__(self, ops, n: int, inv_t: float, B: int, cap: int, device):
+        self.ops, self.n, self.inv_t, self.cap = ops, n, inv_t, cap
+        self.ids = torch.full((B, cap, n), -1, dtype=torch.int32, device=device)
+        self.lps = torch.full((B, cap, n), float("-inf"), dtype=torch.float32, device=device)
+        self.step = None
+
+    def score(self, logits: torch.Tensor) -> None:
+        """logits: the rows the step commits from, [B, V] or [B, K+1, V], read where they are."""
+        self.step = self.ops.top_logprobs(logits, self.n, self.inv_t)
+
+    def commit(self, seq_len: torch.Tensor, n_commit: torch.Tensor) -> None:
+        """Behind the step's commit, which left seq_len and n_commit."""
+        self.ops.commit_top_logprobs(self.step[0], self.step[1], seq_len, n_commit, self.ids, self.lps, self.cap)
+
+    def record(self) -> dict:
+        return dict(top_id=self.step[0].clone(), top_lp=self.step[1].clone())
 
 
 class Stage:
@@ -175,19 +219,25 @@ class Stage:
     # ------------------------------------------------------------------------------------------ generate
     @torch.no_grad()
     def generate(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7, return_logprobs: bool = True,
-                 top_p: Optional[float] = None, stop_token_ids: Optional[Sequence[int]] = None
-                 ) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 top_p: Optional[float] = None, stop_token_ids: Optional[Sequence[int]] = None,
+                 logprobs: Optional[int] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
         distribution for the call: StageConfig.top_p at stage 0, StageConfig.target_top_p at a verifying stage.
         `stop_token_ids`: None = StageConfig.stop_token_ids, an empty sequence = no stop set.  n_i = max_tokens without a stop set;
         with one, the tokens up to and including the first stop id (module docstring).  stats["n_tokens"][i] = n_i and
-        stats["finish_reasons"][i] = "stop" | "length"."""
+        stats["finish_reasons"][i] = "stop" | "length".
+        `logprobs`: None = StageConfig.logprobs; N in 1..8 adds stats["top_token_ids"][i] (int32 [n_i, N]) and
+        stats["top_logprobs"][i] (float32 [n_i, N]): per committed token the N most likely tokens of the UNTRUNCATED
+        temperature-scaled distribution it came from, most likely first (ties: lowest id), ragged like logprobs[i]; 0 = off.
+        With top-k / top-p active the token's own (renormalised) log-prob is not less than its table entry, and the token is
+        always inside the nucleus (module docstring).  Anything outside 0..8 raises ValueError."""
         t0 = time.perf_counter()
         prompts = list(prompts)
         self.step_inputs = []
         stop = _check_stop_ids(self.config.stop_token_ids if stop_token_ids is None else stop_token_ids, self.shape.vocab)
+        n_top = _check_logprobs(self.config.logprobs if logprobs is None else logprobs)
         if not prompts or max_tokens <= 0:
             return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -196,15 +246,17 @@ class Stage:
         ids = self.encode_prompts(prompts)
         B, P = ids.shape
         end = _StopState(stop, B, ids.device) if stop else None
+        inv_t = 1.0 if temperature == 0.0 else float(np.float32(1.0 / temperature))
+        top = _TopState(self.ops, n_top, inv_t, B, P + int(max_tokens), ids.device) if n_top else None
         if temperature == 0.0:                           # greedy: no draws, no truncation (module docstring)
             decode = self._decode_plain_greedy if self.draft is None else self._decode_speculative_greedy
-            tokens, lps, seq_len = decode(ids, int(max_tokens), end)
+            tokens, lps, seq_len = decode(ids, int(max_tokens), end, top)
         elif self.draft is None:
-            tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), float(np.float32(1.0 / temperature)),
-                                                      self.config.top_p if top_p is None else float(top_p), end)
+            tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
+                                                      self.config.top_p if top_p is None else float(top_p), end, top)
         else:
-            tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), float(np.float32(1.0 / temperature)),
-                                                            self.config.target_top_p if top_p is None else float(top_p), end)
+            tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
+                                                            self.config.target_top_p if top_p is None else float(top_p), end, top)
         self.ops.check_status()
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
@@ -219,6 +271,10 @@ class Stage:
         texts = [self.decode_tokens(row[:n]) for row, n in zip(tok_h, n_tok)]
         stats = {"generation_time_ms": (time.perf_counter() - t0) * 1000.0, "steps": float(self.last_steps),
                  "n_tokens": n_tok, "finish_reasons": reasons}
+        if top is not None:
+            id_h, tlp_h = top.ids[:, P:].cpu().numpy(), top.lps[:, P:].cpu().numpy()
+            stats["top_token_ids"] = [np.ascontiguousarray(r[:n]) for r, n in zip(id_h, n_tok)]
+            stats["top_logprobs"] = [np.ascontiguousarray(r[:n]) for r, n in zip(tlp_h, n_tok)]
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     def _buffers(self, ids: torch.Tensor, cap: int):
@@ -247,7 +303,7 @@ class Stage:
             self.ops.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap, end.stop_ids,
                                       end.finished, end.n_finished)
 
-    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None):
+    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None, top=None):
         """Stage 0.  Without a stop set every sequence appends exactly one token per step, so all positions are known on the
         host; with one (`end`), a sequence is fed its last committed token at seq_len - 1, which is the same for a running
         sequence and stays put for a finished one."""
@@ -263,9 +319,15 @@ class Stage:
         for step in range(max_tokens):
             logits = logits.contiguous()
             tok, lp, thr = self._propose(self.config, logits, inv_t, top_p)
+            if top is not None:
+                top.score(logits)
             self._commit(end, None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
+            if top is not None:
+                top.commit(seq_len, n_commit)
             if self.keep_inputs:
                 self.step_inputs.append(dict(logits=logits.clone(), drawn=tok.clone(), lp_drawn=lp.clone(), thr=thr.clone()))
+                if top is not None:
+                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
             self.last_steps = step + 1
             if end is not None and (step + 1) % self.config.sync_every == 0 and end.all_finished():
                 break
@@ -279,7 +341,7 @@ class Stage:
                 logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
         return tokens, lps, seq_len
 
-    def _decode_plain_greedy(self, ids: torch.Tensor, max_tokens: int, end=None):
+    def _decode_plain_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None):
         """Stage 0 at temperature 0: _decode_plain with one verify_greedy call (K = 0) per step in place of the draw; the logits
         are read where the model left them."""
         B, P = ids.shape
@@ -296,7 +358,13 @@ class Stage:
                 self.step_inputs.append(dict(logits=logits.clone(), tok=None, n_acc=n_acc.clone(), argmax=argmax.clone(),
                                              lp_argmax=lp_argmax.clone(), lp_t=lp_t.clone(), drawn=tok.clone(),
                                              lp_drawn=lp.clone(), seq_len=seq_len.clone()))
+            if top is not None:
+                top.score(logits)
             self._commit(end, None, None, n_acc, tok, lp, seq_len, tokens, lps, n_commit, cap)
+            if top is not None:
+                top.commit(seq_len, n_commit)
+                if self.keep_inputs:
+                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
             self.last_steps = step + 1
             if end is not None and (step + 1) % self.config.sync_every == 0 and end.all_finished():
                 break
@@ -310,7 +378,7 @@ class Stage:
                 logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
         return tokens, lps, seq_len
 
-    def _decode_speculative_greedy(self, ids: torch.Tensor, max_tokens: int, end=None):
+    def _decode_speculative_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None):
         """Stage s > 0 at temperature 0: _decode_speculative's step with the draft's arg-max as the proposal (K = 0 calls on the
         draft logits) and ONE verify_greedy call on the target's [B, K+1, V] output as returned -- no copies of the score and
         bonus rows, no kept draft logits, no uniforms.  A draft token is accepted iff it is the target row's arg-max, the token
@@ -350,7 +418,13 @@ class Stage:
                 self.step_inputs.append(dict(logits=t_out.clone(), tok=tok32.clone(), n_acc=n_acc.clone(), argmax=argmax.clone(),
                                              lp_argmax=lp_argmax.clone(), lp_t=lp_t.clone(), drawn=drawn.clone(),
                                              lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone()))
+            if top is not None:
+                top.score(t_out)
             self._commit(end, tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            if top is not None:
+                top.commit(seq_len, n_commit)
+                if self.keep_inputs:
+                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
             steps += 1
             if steps % cfg.sync_every == 0 and (int(seq_len.min().item()) >= cap if end is None else end.all_finished()):
                 break
@@ -370,7 +444,7 @@ class Stage:
         lp_t, _, n_acc, _ = self.ops.verify_accept(score, tok32, lp_d, u, inv_t)
         return lp_t, n_acc, None
 
-    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None):
+    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None, top=None):
         """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
 
         Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
@@ -424,7 +498,13 @@ class Stage:
                                              u=u.clone(), lp_t=lp_t.clone(), n_acc=n_acc.clone(), drawn=drawn.clone(),
                                              lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone(),
                                              t_thr=None if t_thr is None else t_thr.clone()))
+            if top is not None:
+                top.score(t_out)                                        # the [B, K+1, V] output as returned, not the copies
             self._commit(end, tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            if top is not None:
+                top.commit(seq_len, n_commit)
+                if self.keep_inputs:
+                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
             steps += 1
             if steps % cfg.sync_every == 0 and (int(seq_len.min().item()) >= cap if end is None else end.all_finished()):
                 break

@@ -48,6 +48,7 @@ typedef enum asd_dtype {
 /* limits enforced by the launchers */
 #define ASD_MAX_DRAFT_LEN 64   /* K: one ballot word per sequence */
 #define ASD_MAX_STOP_IDS 8     /* stop (EOS) token ids of asd_commit_step_stop */
+#define ASD_MAX_TOP_LOGPROBS 8 /* N of asd_top_logprobs: the most likely tokens listed per row */
 #define ASD_MAX_STAGES 16      /* L: tiers in the DP rule */
 #define ASD_MAX_SPLITS 64      /* vocab splits per row inside one launch */
 #define ASD_MAX_MLP_DIM 1024   /* predictor input / hidden width */
@@ -359,6 +360,45 @@ int asd_verify_greedy(const void* logits, int dtype, int64_t ld_seq, int64_t ld_
                       float* lp_target /*[B,K] out, may be NULL*/, uint8_t* accept /*[B,K] out, may be NULL*/,
                       int32_t* n_acc /*[B] out*/, int32_t* drawn /*[B] out*/, float* lp_drawn /*[B] out*/,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Top-N log-probs per row: the table behind SamplingParams(logprobs=N) of the stage specification
+ * (docs/guides/RESEARCH_PROTOCOL.md:272-277), which its FeatureExtractor consumes (:366-409).
+ * logits: B sequences of K1 rows, row (b, j) starts at element b*ld_seq + j*ld_row and is read in place (asd_verify_greedy's
+ * addressing with K1 = K + 1; K1 == 1 is a [B, V] matrix).  Any V >= 1 and any element-aligned row base; ld_row >= V,
+ * ld_seq >= K1*ld_row; the padding is never read.
+ * Per row, the N entries with the largest logits, 1 <= N <= ASD_MAX_TOP_LOGPROBS, as pairs (top_id, top_lp):
+ *   order: value descending, then id ascending -- a total order, so the ids do not depend on the launch geometry, and slot 0
+ *   is asd_verify_greedy's argmax.  A NaN logit is never listed; a logit of -inf is never listed.
+ *   top_lp = x[id]*inv_temperature - lse(x*inv_temperature) over the WHOLE vocabulary (asd_verify_greedy's lp_argmax
+ *   arithmetic; slot 0 has its bits).  A row that holds a NaN has NaN log-probs; its ids are listed all the same.
+ *   A slot that cannot be filled (V < N, or fewer than N logits above -inf) holds id -1 and lp -inf.
+ * splits: workgroups per row in [1, ASD_MAX_SPLITS], 0 = heuristic (asd_verify_greedy's).  Nothing in the kernel waits, so
+ * there is no status word; the launcher zeroes the tickets (hipMemsetAsync) ahead of every launch: the workspace needs no
+ * asd_workspace_init, calls in stream order may share one, calls in flight together need one each.
+ * Status, in this order: NULL top_id / top_lp, inv_temperature not > 0 (both before the empty-batch return), negative sizes:
+ * invalid argument; B == 0: ASD_OK, nothing launched; V == 0, K1 < 1, N < 1: invalid argument; K1 > ASD_MAX_DRAFT_LEN + 1,
+ * N > ASD_MAX_TOP_LOGPROBS, unknown dtype, splits outside [0, ASD_MAX_SPLITS]: unsupported; NULL logits / workspace,
+ * ld_row < V, ld_seq < K1*ld_row: invalid argument; logits not aligned to the element size: alignment; workspace misaligned
+ * (256): workspace; a row of 2 GiB or more: unsupported; workspace too small: workspace.
+ * ---------------------------------------------------------------------------------------- */
+size_t asd_top_logprobs_workspace_bytes(int B, int K1, int N);   /* sized for ASD_MAX_SPLITS; a multiple of 256; 256 when B <= 0 */
+int asd_top_logprobs(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                     float inv_temperature, int N, int splits /*workgroups per row, 0 = heuristic*/,
+                     int32_t* top_id /*[B,K1,N] out*/, float* top_lp /*[B,K1,N] out*/,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* The table of a step follows the step's commit (RESEARCH_PROTOCOL.md:272-277: one [N] row per GENERATED token).  Runs behind
+ * asd_commit_step_lp / asd_commit_step_stop of the same step and reads their outputs: seq_len[b] AFTER the commit and
+ * n_commit[b].  For j < min(n_commit[b], K1):  out[b, seq_len[b] - n_commit[b] + j, :] = top[b, j, :]  (ids and log-probs;
+ * bits are copied; positions outside [0, max_len) are not written).  Row j of a step is the distribution its j-th committed
+ * token came from: accepted draft token j comes from score row j, the token drawn behind the prefix from row n_acc (the bonus
+ * row when n_acc == K).  A finished sequence (n_commit == 0) appends nothing.  out_id / out_lp: [B][max_len][N], contiguous.
+ * Status: negative sizes: invalid argument; B == 0: ASD_OK; K1 > ASD_MAX_DRAFT_LEN + 1, N > ASD_MAX_TOP_LOGPROBS: unsupported;
+ * K1 < 1, N < 1, any NULL pointer: invalid argument. */
+int asd_commit_top_logprobs(const int32_t* top_id /*[B,K1,N]*/, const float* top_lp /*[B,K1,N]*/,
+                            const int32_t* seq_len /*[B]: AFTER the step's commit*/, const int32_t* n_commit /*[B]*/,
+                            int B, int K1, int N, int32_t* out_id /*[B,max_len,N]*/, float* out_lp /*[B,max_len,N]*/,
+                            int max_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop and asd_verify_greedy in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_verify_greedy, asd_top_logprobs and asd_commit_top_logprobs in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -131,6 +131,67 @@ int main() {
         EXPECT(GREEDY(rows + 2, BF16, lds, ldr, i32, B, KG, VG, 1.0f, 1, i32, i32, f32, p, 0), ASD_ERR_WORKSPACE);           // (an element-aligned base is valid)
         EXPECT(GREEDY(nullptr, 99, 0, 0, nullptr, 0, KG, VG, 1.0f, 0, nullptr, nullptr, nullptr, nullptr, 0), ASD_OK);       // B == 0: nothing launched
 #undef GREEDY
+    }
+
+    // ---- asd_top_logprobs: asd_verify_greedy's order (NULL outputs and the temperature ahead of the empty-batch return, sizes, the
+    // empty batch, N / K1 / dtype / splits, pointers, strides, alignment, the workspace), then asd_commit_top_logprobs
+    {
+        const int K1 = 5, VT = 1000, NT = 5;
+        const int64_t ldr = VT, lds = static_cast<int64_t>(K1) * VT;
+        const size_t ws = asd_top_logprobs_workspace_bytes(B, K1, NT);
+        if (ws % 256 != 0 || ws <= asd_top_logprobs_workspace_bytes(B, 1, NT) || asd_top_logprobs_workspace_bytes(0, K1, NT) != 256 ||
+            asd_top_logprobs_workspace_bytes(B, 0, NT) != 256) {
+            std::printf("FAIL top_logprobs workspace size %zu\n", ws);
+            ++failures;
+        }
+#define TOP(logits_, dtype_, lds_, ldr_, B_, K1_, V_, inv_t_, N_, splits_, id_, lp_, ws_, ws_bytes_) \
+    asd_top_logprobs(logits_, dtype_, lds_, ldr_, B_, K1_, V_, inv_t_, N_, splits_, id_, lp_, ws_, ws_bytes_, nullptr)
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, NT, 0, nullptr, f32, p, ws), ASD_ERR_INVALID_ARG);                   // top_id
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, NT, 0, i32, nullptr, p, ws), ASD_ERR_INVALID_ARG);                   // top_lp
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 0.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                       // temperature
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, NAN, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, INFINITY, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(TOP(p, BF16, lds, ldr, 0, K1, VT, -1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                      // ... before the empty batch
+        EXPECT(TOP(p, BF16, lds, ldr, -1, K1, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(TOP(p, BF16, lds, ldr, B, -1, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, -1, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, -1, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);
+        EXPECT(TOP(nullptr, 99, 0, 0, 0, 99, VT, 1.0f, 99, 99, nullptr, nullptr, nullptr, 0), ASD_OK);                      // B == 0: nothing launched
+        EXPECT(TOP(p, BF16, 0, 0, B, K1, 0, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                            // V == 0
+        EXPECT(TOP(p, BF16, 0, ldr, B, 0, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                          // K1 < 1
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, 0, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                        // N < 1
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, ASD_MAX_TOP_LOGPROBS + 1, 0, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);
+        EXPECT(TOP(p, BF16, 66 * ldr, ldr, B, ASD_MAX_DRAFT_LEN + 2, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);
+        EXPECT(TOP(p, 99, lds, ldr, B, K1, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);                         // dtype
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, NT, -1, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);                      // splits
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, NT, ASD_MAX_SPLITS + 1, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);
+        EXPECT(TOP(nullptr, BF16, lds, ldr, B, K1, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                 // logits
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, NT, 0, i32, f32, nullptr, ws), ASD_ERR_INVALID_ARG);                 // workspace
+        EXPECT(TOP(p, BF16, lds, ldr - 1, B, K1, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                   // ld_row < V
+        EXPECT(TOP(p, BF16, lds - 1, ldr, B, K1, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_INVALID_ARG);                   // ld_seq < K1 ld_row
+        EXPECT(TOP(p, BF16, int64_t{5} << 30, int64_t{1} << 30, B, K1, 1 << 30, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_UNSUPPORTED);   // a 2 GiB row
+        EXPECT(TOP(rows + 1, BF16, lds, ldr, B, K1, VT, 1.0f, NT, 0, i32, f32, p, ws), ASD_ERR_ALIGNMENT);                  // below the element size
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, NT, 0, i32, f32, rows + 16, ws), ASD_ERR_WORKSPACE);                 // misaligned workspace
+        EXPECT(TOP(p, BF16, lds, ldr, B, K1, VT, 1.0f, NT, ASD_MAX_SPLITS, i32, f32, p, ws - 1), ASD_ERR_WORKSPACE);        // too small
+        EXPECT(TOP(rows + 2, BF16, lds, ldr, B, K1, VT, 1.0f, NT, 1, i32, f32, p, 0), ASD_ERR_WORKSPACE);                   // (an element-aligned base is valid)
+#undef TOP
+#define CTOP(id_, lp_, seq_, nc_, B_, K1_, N_, oid_, olp_, max_len_) asd_commit_top_logprobs(id_, lp_, seq_, nc_, B_, K1_, N_, oid_, olp_, max_len_, nullptr)
+        EXPECT(CTOP(i32, f32, i32, i32, -1, K1, NT, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, i32, i32, B, -1, NT, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, i32, i32, B, K1, -1, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, i32, i32, B, K1, NT, i32, f32, -1), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(nullptr, nullptr, nullptr, nullptr, 0, 99, 99, nullptr, nullptr, 32), ASD_OK);                          // B == 0
+        EXPECT(CTOP(i32, f32, i32, i32, B, ASD_MAX_DRAFT_LEN + 2, NT, i32, f32, 32), ASD_ERR_UNSUPPORTED);
+        EXPECT(CTOP(i32, f32, i32, i32, B, K1, ASD_MAX_TOP_LOGPROBS + 1, i32, f32, 32), ASD_ERR_UNSUPPORTED);
+        EXPECT(CTOP(i32, f32, i32, i32, B, 0, NT, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, i32, i32, B, K1, 0, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(nullptr, f32, i32, i32, B, K1, NT, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, nullptr, i32, i32, B, K1, NT, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, nullptr, i32, B, K1, NT, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, i32, nullptr, B, K1, NT, i32, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, i32, i32, B, K1, NT, nullptr, f32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(CTOP(i32, f32, i32, i32, B, K1, NT, i32, nullptr, 32), ASD_ERR_INVALID_ARG);
+#undef CTOP
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
