@@ -61,6 +61,11 @@ SIGNATURES = {
                                        _vp, _sz, _vp]),
     "asd_residual_sample_lp": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp,
                                     _vp, _vp, _sz, _vp]),
+    "asd_draft_sample_min_p": (_i, [_vp, _i64, _i, _vp, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "asd_verify_accept_min_p": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _sz, _vp]),
+    "asd_residual_sample_lp_min_p": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _f, _i, _f, _f, _vp, _vp,
+                                          _vp, _vp, _vp, _sz, _vp]),
     "asd_lse_partial": (_i, [_vp, _i, _i64, _vp, _i, _i, _i, _i64, _f, _vp, _vp, _sz, _vp]),
     "asd_accept_from_partials": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "asd_lm_head_verify_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -84,6 +85,15 @@ inline Truncation truncation(int top_k, float top_p, int V, int dtype) {
     t.top_k = (top_k > 0 && top_k < V) ? top_k : 0;
     t.levels = t.nucleus ? (dtype == ASD_DTYPE_F32 ? 3 : 2) : 0;
     return t;
+}
+
+
+// min-p (HF's MinPLogitsWarper, behind top-k and top-p): <= 0 is the off switch, (0, 1] a bound, anything else (NaN included)
+// an argument error
+inline bool valid_min_p(float min_p) { return min_p <= 1.0f; }
+// x_max + this is min-p's threshold on the raw logits: p_v >= min_p p_max  <=>  x_v >= x_max + T ln(min_p)
+inline float min_p_delta(float min_p, float inv_temperature) {
+    return static_cast<float>(log(static_cast<double>(min_p)) / static_cast<double>(inv_temperature));
 }
 
 }  // namespace asd

@@ -46,6 +46,7 @@ struct DrParams {
     float c2, top_p;
     int levels;              // 0: no truncation; 2: 16-bit logits; 3: f32 logits
     int top_k;               // k_draft_row<DT, true> only: the top-k bound (1 <= top_k < V)
+    float mp_delta;          // k_draft_row<DT, *, true> only: T ln(min_p) <= 0 (asd_draft_sample_min_p)
     int32_t* tok; float* lp; float* thr;
 };
 
@@ -57,7 +58,9 @@ struct DraftPickScratch {
     int tile;
     double rest;
 };
-template <int DT>
+// kClampLp (the min-p kernels): a kept set of ONE token has q = 1, and the f32 normaliser can leave log q a rounding ABOVE 0; there
+// the log-prob is reported as 0.
+template <int DT, bool kClampLp = false>
 __device__ __forceinline__ void draft_pick_wave(const u32x4* row, int nvec, const float* tile_mass, int n_tiles, float r, float c2,
                                                 float Lt, double L64, float thr, int lane, DraftPickScratch& sc, int32_t* tok,
                                                 float* lp) {
@@ -140,12 +143,14 @@ __device__ __forceinline__ void draft_pick_wave(const u32x4* row, int nvec, cons
         *tok = v * N + pick;
         if (lp) {
             const double x = static_cast<double>(E::scalar(row, static_cast<int64_t>(v) * N + pick));
-            *lp = static_cast<float>(kLn2d * (x * static_cast<double>(c2) - L64));
+            double lq = kLn2d * (x * static_cast<double>(c2) - L64);
+            if constexpr (kClampLp) { if (lq > 0.0) lq = 0.0; }
+            *lp = static_cast<float>(lq);
         }
     }
 }
 
-template <int DT, bool kTopK = false>
+template <int DT, bool kTopK = false, bool kMinP = false>
 __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
     using E = Elem<DT>;
     constexpr int N = E::kPerVec;
@@ -162,10 +167,11 @@ __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
         for (int i = 0; i < N; ++i) any = any || (x[i] >= bound);
         return __ballot(any) != 0ull;
     };
-    const bool tiles_from_sweep1 = p.levels == 0;
     // (kTopK: phase 0, the count select of x_k, then phases 1-3 on the top-k set; the tile pairs of phase 1 are K's)
-    const NucleusSel sel = nucleus_row_select<DT, kTopK>(row, p.V, p.nvec, p.n_tiles, p.c2, p.top_p, p.levels, sh, t,
-                                                         [&](int slot) { ASD_DR_STAMP(slot); }, p.top_k);
+    // (kMinP: thr = max(thr_kp, x_max + mp_delta); where min-p's bound won, the select left the tile pairs of { x >= thr })
+    const NucleusSel sel = nucleus_row_select<DT, kTopK, kMinP>(row, p.V, p.nvec, p.n_tiles, p.c2, p.top_p, p.levels, sh, t,
+                                                                [&](int slot) { ASD_DR_STAMP(slot); }, p.top_k, p.mp_delta);
+    const bool tiles_from_sweep1 = p.levels == 0 || (kMinP && sel.pairs);
     const double L64 = sel.L64;
     const float thr = sel.thr;
     const bool listed = sel.listed;
@@ -216,7 +222,8 @@ __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
 
     // ---- inverse CDF by one wave
     __shared__ DraftPickScratch pick;
-    draft_pick_wave<DT>(row, p.nvec, tile_mass, p.n_tiles, p.r[b], p.c2, Lt, L64, thr, lane, pick, p.tok + b, p.lp ? p.lp + b : nullptr);
+    draft_pick_wave<DT, kMinP>(row, p.nvec, tile_mass, p.n_tiles, p.r[b], p.c2, Lt, L64, thr, lane, pick, p.tok + b,
+                               p.lp ? p.lp + b : nullptr);
     if (lane == 0) ASD_DR_STAMP(11);
 }
 
@@ -643,8 +650,10 @@ namespace {
 // (k_draft_group) would have to exchange the count histograms of the select through its mailboxes as it does the mass
 // histograms; until it does, top-k rows are not spread over workgroups (the workspace is accepted and left untouched), and the
 // outputs depend on the row alone.
+// With a min-p bound (asd_draft_sample_min_p, 0 < min_p <= 1; 0 = none): k_draft_row<DT, *, true>, the same geometry.
 int draft_launch(const void* logits, int64_t ld, int dtype, const float* r, int B, int V, float inv_temperature, int top_k,
-                 float top_p, int32_t* tok, float* lp, float* threshold, void* workspace, size_t workspace_bytes, void* stream) {
+                 float top_p, int32_t* tok, float* lp, float* threshold, void* workspace, size_t workspace_bytes, void* stream,
+                 float min_p = 0.0f) {
     if (B < 0 || V < 1) return ASD_ERR_INVALID_ARG;
     if (B == 0) return ASD_OK;
     const RowGeom g = row_geom(V, dtype);
@@ -661,13 +670,14 @@ int draft_launch(const void* logits, int64_t ld, int dtype, const float* r, int 
     p.top_p = top_p;
     p.levels = tr.levels;
     p.top_k = tr.top_k;
+    p.mp_delta = min_p > 0.0f ? min_p_delta(min_p, inv_temperature) : 0.0f;
     p.tok = tok; p.lp = lp; p.thr = threshold;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // few rows: spread every row over G workgroups (the workspace carries their mailboxes; without one, or with a row too
     // long for the registers of its workgroups, one streaming workgroup per row)
     const DgLayout l = dg_layout(B, p.n_tiles);
     const bool have_ws = workspace && aligned_to(workspace, 256) && workspace_bytes >= kWorkspaceHeaderBytes + l.hist_bytes + l.small_bytes;
-    const int G = (tr.top_k > 0 || g_debug_groups < 0) ? 0 : choose_groups(B, p.n_tiles, current_device_cus(), have_ws);
+    const int G = (tr.top_k > 0 || min_p > 0.0f || g_debug_groups < 0) ? 0 : choose_groups(B, p.n_tiles, current_device_cus(), have_ws);
     if (G >= 1) {
         DgParams q{};
         q.d = p;
@@ -686,7 +696,10 @@ int draft_launch(const void* logits, int64_t ld, int dtype, const float* r, int 
     const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
     dispatch_dtype(dtype, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
-        if (tr.top_k > 0) hipLaunchKernelGGL((k_draft_row<DT, true>), grid, block, 0, st, p);
+        if (min_p > 0.0f) {
+            if (tr.top_k > 0) hipLaunchKernelGGL((k_draft_row<DT, true, true>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((k_draft_row<DT, false, true>), grid, block, 0, st, p);
+        } else if (tr.top_k > 0) hipLaunchKernelGGL((k_draft_row<DT, true>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((k_draft_row<DT, false>), grid, block, 0, st, p);
     });
     return launch_status();
@@ -705,4 +718,12 @@ ASD_EXPORT int asd_draft_sample_top_k(const void* logits, int64_t ld, int dtype,
                                       void* workspace, size_t workspace_bytes, void* stream) {
     return draft_launch(logits, ld, dtype, r, B, V, inv_temperature, top_k, top_p, tok, lp, threshold, workspace, workspace_bytes,
                         stream);
+}
+
+ASD_EXPORT int asd_draft_sample_min_p(const void* logits, int64_t ld, int dtype, const float* r, int B, int V,
+                                      float inv_temperature, int top_k, float top_p, float min_p, int32_t* tok, float* lp,
+                                      float* threshold, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!valid_min_p(min_p)) return ASD_ERR_INVALID_ARG;
+    return draft_launch(logits, ld, dtype, r, B, V, inv_temperature, top_k, top_p, tok, lp, threshold, workspace, workspace_bytes,
+                        stream, min_p > 0.0f ? min_p : 0.0f);
 }

@@ -43,6 +43,7 @@ struct RsParams {
     const float* t_thr;       // [B*K] nucleus thresholds of the target rows (asd_verify_accept_top_p's x*) or nullptr
     const float* b_thr;       // [B] nucleus thresholds of the bonus rows (k_rs_bonus_threshold) or nullptr
     float* lp;                // [B] out: log p_t^N(token) (asd_residual_sample_lp) or nullptr
+    int clamp_lp;             // asd_residual_sample_lp_min_p: an lp a rounding above 0 (a kept set of one token) is reported as 0
 };
 
 template <int DT>
@@ -262,7 +263,9 @@ __device__ __forceinline__ void rs_pick_scan(const RsParams& p, int b, int lane,
 #pragma unroll
             for (int i = 1; i < N; ++i) x_tok = pick == i ? x[i] : x_tok;
             const double L = static_cast<double>(Lt.hi) + static_cast<double>(Lt.lo);
-            p.lp[b] = static_cast<float>(kLn2d * (static_cast<double>(x_tok) * static_cast<double>(p.c2) - L));
+            double lq = kLn2d * (static_cast<double>(x_tok) * static_cast<double>(p.c2) - L);
+            if (p.clamp_lp && lq > 0.0) lq = 0.0;
+            p.lp[b] = static_cast<float>(lq);
         }
     }
 }
@@ -498,15 +501,18 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
 // (sample_device.hpp, nucleus_row_select): the same bits as asd_draft_sample's nucleus_logit on that row.  Sequences that
 // draw from a residual (or have no bonus row) leave at once.
 // kTopK (asd_residual_sample_top_k): the top-k + top-p threshold max(x_k, x*_K) of asd_draft_sample_top_k's select instead.
-template <int DT, bool kTopK = false>
-__global__ __launch_bounds__(kDrThreads) void k_rs_bonus_threshold(const RsParams p, float top_p, int levels, float* b_thr, int top_k) {
+// kMinP (asd_residual_sample_lp_min_p): max(that, x_max + mp_delta), asd_draft_sample_min_p's.
+template <int DT, bool kTopK = false, bool kMinP = false>
+__global__ __launch_bounds__(kDrThreads) void k_rs_bonus_threshold(const RsParams p, float top_p, int levels, float* b_thr, int top_k,
+                                                                   float mp_delta = 0.0f) {
     using E = Elem<DT>;
     __shared__ NucleusLds sh;
     const int b = blockIdx.x, t = threadIdx.x;
     const int j = p.n_acc[b];
     if ((j >= 0 && j < p.K) || !p.bonus) return;                        // block-uniform
     const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.bonus) + static_cast<int64_t>(b) * p.ld_b * E::kBytes);
-    const NucleusSel sel = nucleus_row_select<DT, kTopK>(row, p.V, p.nvec, p.n_tiles, p.c2, top_p, levels, sh, t, [](int) {}, top_k);
+    const NucleusSel sel = nucleus_row_select<DT, kTopK, kMinP>(row, p.V, p.nvec, p.n_tiles, p.c2, top_p, levels, sh, t, [](int) {},
+                                                                top_k, mp_delta);
     if (t == 0) b_thr[b] = sel.thr;
 }
 
@@ -576,6 +582,7 @@ struct RsTruncate {
     const float* t_threshold = nullptr;      // [B*K] the verify's thresholds of the target rows
     float top_p = 1.0f;
     int top_k = 0;
+    float min_p = 0.0f;                      // (0, 1]: asd_residual_sample_lp_min_p; 0 = none
 };
 
 // The launcher behind the five entry points.  A call that truncates nothing (top_p outside (0, 1) and top_k <= 0 or >= V) is
@@ -589,7 +596,7 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     // _ex pass top_p = 1)
     if (cut.top_p != cut.top_p) return ASD_ERR_INVALID_ARG;
     const Truncation tr = truncation(cut.top_k, cut.top_p, V, dtype);
-    const bool truncated = tr.nucleus || tr.top_k > 0;
+    const bool truncated = tr.nucleus || tr.top_k > 0 || cut.min_p > 0.0f;
     if (truncated) {
         if (B > 0 && K > 0 && !cut.t_threshold) return ASD_ERR_INVALID_ARG;
         if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
@@ -619,6 +626,7 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     p.tiles = reinterpret_cast<float2*>(body + round_up(static_cast<size_t>(B) * 32 * sizeof(float4), 256));
     p.token = token;
     p.lp = lp;
+    p.clamp_lp = cut.min_p > 0.0f ? 1 : 0;
     p.d_thr = d_threshold;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (truncated) {
@@ -633,8 +641,12 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
         const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
         dispatch_dtype(dtype, [&](auto dt) {
             constexpr int DT = decltype(dt)::value;
-            if (tr.top_k > 0) hipLaunchKernelGGL((k_rs_bonus_threshold<DT, true>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, tr.top_k);
-            else hipLaunchKernelGGL((k_rs_bonus_threshold<DT, false>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, 0);
+            if (cut.min_p > 0.0f) {
+                const float mp_delta = min_p_delta(cut.min_p, inv_temperature);
+                if (tr.top_k > 0) hipLaunchKernelGGL((k_rs_bonus_threshold<DT, true, true>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, tr.top_k, mp_delta);
+                else hipLaunchKernelGGL((k_rs_bonus_threshold<DT, false, true>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, 0, mp_delta);
+            } else if (tr.top_k > 0) hipLaunchKernelGGL((k_rs_bonus_threshold<DT, true>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, tr.top_k, 0.0f);
+            else hipLaunchKernelGGL((k_rs_bonus_threshold<DT, false>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, 0, 0.0f);
         });
         if (launch_status() != ASD_OK) return ASD_ERR_HIP;
         workspace_bytes = base;                        // the geometry choice below sees the workspace asd_residual_sample_ex would
@@ -730,4 +742,16 @@ ASD_EXPORT int asd_residual_sample_lp(const void* t_logits, int64_t ld_t, const 
     if (B > 0 && !lp) return ASD_ERR_INVALID_ARG;
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
                            d_threshold, token, workspace, workspace_bytes, stream, {t_threshold, top_p, top_k}, lp);
+}
+
+ASD_EXPORT int asd_residual_sample_lp_min_p(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                                            const void* bonus_logits, int64_t ld_b, int dtype, const int32_t* n_acc,
+                                            const float* r, int B, int K, int V, float inv_temperature, int top_k, float top_p,
+                                            float min_p, const float* t_threshold, const float* d_threshold, int32_t* token,
+                                            float* lp, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!valid_min_p(min_p)) return ASD_ERR_INVALID_ARG;
+    if (B > 0 && !lp) return ASD_ERR_INVALID_ARG;
+    return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
+                           d_threshold, token, workspace, workspace_bytes, stream,
+                           {t_threshold, top_p, top_k, min_p > 0.0f ? min_p : 0.0f}, lp);
 }

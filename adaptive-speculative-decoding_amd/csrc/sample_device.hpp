@@ -311,6 +311,7 @@ struct NucleusSel {
     double L64;       // log2 of the normaliser of the distribution drawn from / scored against (L_N with truncation)
     bool listed;      // the candidates of the row are in sh.cand: later phases walk the lists, not the row
     int wcnt;         // candidates in this wave's list (wave-uniform)
+    bool pairs;       // kMinP, x_mp won: sh.tile_span / sh.tile_mass hold the tile pairs of { x >= thr } (as with levels == 0)
 };
 
 //   1. (m2, s) of the row                                   -> L, the softmax normaliser            (sweep, exp per element)
@@ -324,9 +325,17 @@ struct NucleusSel {
 // max(x_floor, x_k) and the mass target is top_p of K's mass -- so thr = max(x_k, x*_K) and L64 = the normaliser over
 // { x >= thr }; with levels == 0 (top-p off) thr = x_k, L64 = L_K.  kTopK = false is the form without phase 0 (x_lo is the
 // constant -inf, every use of it folds away).
-template <int DT, bool kTopK = false, class Stamp>
+// kMinP (HF's MinPLogitsWarper behind the two, include/asd_hip.h "Min-p"): sweep 1 also takes the EXACT maximum x_max of the raw
+// logits (a float max per lane, the lanes, the 16 waves: no rounding, no dependence on the order), and behind the select
+// x_mp = x_max + mp_delta (mp_delta = T ln(min_p) <= 0, the launcher's) is compared with thr_kp = max(x_k, x*_K).  Where x_mp
+// is larger it is the threshold, and one more sweep (L2 hits) takes the tile pairs of { x >= x_mp } and folds them into its
+// normaliser -- the pairs stay in sh.tile_span / sh.tile_mass as with levels == 0 (`pairs`), the candidate lists are dropped.
+// With levels == 0 and no top-k there is no select at all: the row costs sweep 1, that sweep and the draw.  kMinP = false
+// compiles none of it.
+template <int DT, bool kTopK = false, bool kMinP = false, class Stamp>
 __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V, int nvec, int n_tiles, float c2, float top_p,
-                                                         int levels, NucleusLds& sh, int t, Stamp&& stamp, int top_k = 0) {
+                                                         int levels, NucleusLds& sh, int t, Stamp&& stamp, int top_k = 0,
+                                                         float mp_delta = 0.0f) {
     using E = Elem<DT>;
     constexpr int N = E::kPerVec;
     const int lane = t & 63, wave = t >> 6;
@@ -344,6 +353,7 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
     // fixed order of fold_tile_pairs: L has the same bits as in k_draft_group, whatever the batch (round 2 ran a per-lane
     // online softmax here when top-p was on: 5 us less for the sweep, but a value only this geometry could reproduce).
     // Without truncation the tile masses then follow from L without a second exp-per-element sweep of the row.
+    float x_max = -INFINITY;                                  // kMinP only: this lane's, then the row's, largest raw logit
     row_sweep<DT>(row, nvec, t, [&](int v, const u32x4& vec) {
         float M, sw;
         if constexpr (kTopK) tile_pair<DT>(vec, c2, M, sw, x_lo);      // the top-k set's pairs -> L_K
@@ -352,11 +362,26 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
             sh.tile_span[v >> 6] = __float_as_uint(M);        // row_sweep step reduce side by side
             sh.tile_mass[v >> 6] = sw;
         }
+        if constexpr (kMinP) {
+            float x[N];
+            unpack<DT>(vec, x);
+#pragma unroll
+            for (int i = 0; i < N; ++i) x_max = fmaxf(x_max, x[i]);
+        }
     });
     __syncthreads();
     fold_tile_pairs(reinterpret_cast<const float*>(sh.tile_span), sh.tile_mass, n_tiles, sh.red, wave, lane, m2, s);
+    if constexpr (kMinP) {
+        // the 16 waves' maxima through sh.wave_tot (idle here: phase 0 is over, the mass select writes it behind two barriers)
+        x_max = wave_max(x_max);
+        if (lane == 0) sh.wave_tot[wave] = __float_as_uint(x_max);
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < kDrWaves; ++w) x_max = fmaxf(x_max, __uint_as_float(static_cast<uint32_t>(sh.wave_tot[w])));
+    }
     stamp(1);
     NucleusSel r;
+    r.pairs = false;
     r.L64 = static_cast<double>(m2) + log2_split(s);
     r.thr = -INFINITY;
     r.listed = false;
@@ -487,6 +512,26 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
         stamp(8);
     }
     if constexpr (kTopK) r.thr = fmaxf(r.thr, x_lo);          // x*_K >= x_k whenever the mass select found one
+    if constexpr (kMinP) {
+        const float x_mp = x_max + mp_delta;                  // p_v >= min_p p_max  <=>  x_v >= x_max + T ln(min_p)
+        if (x_mp > r.thr) {                                   // (block-uniform; never for a row of -inf)
+            __syncthreads();                                  // the select's readers of tile_span / tile_mass are done
+            row_sweep<DT>(row, nvec, t, [&](int v, const u32x4& vec) {
+                float M, sw;
+                tile_pair<DT>(vec, c2, M, sw, x_mp);
+                if (lane == 0) {
+                    sh.tile_span[v >> 6] = __float_as_uint(M);
+                    sh.tile_mass[v >> 6] = sw;
+                }
+            });
+            __syncthreads();
+            fold_tile_pairs(reinterpret_cast<const float*>(sh.tile_span), sh.tile_mass, n_tiles, sh.red, wave, lane, m2, s);
+            r.L64 = static_cast<double>(m2) + log2_split(s);
+            r.thr = x_mp;
+            r.listed = false;
+            r.pairs = true;
+        }
+    }
     return r;
 }
 

@@ -34,23 +34,26 @@ struct VnParams {
     float* thr;               // [B*K] x* per row, or nullptr
     int32_t* n_finite;        // [B], or nullptr
     int top_k;                // k_verify_nucleus<DT, true> only (asd_verify_accept_top_k): 1 <= top_k < V; levels may then be 0
+    float mp_delta;           // k_verify_nucleus<DT, *, true> only (asd_verify_accept_min_p): T ln(min_p) <= 0
 };
 
-template <int DT, bool kTopK = false>
+template <int DT, bool kTopK = false, bool kMinP = false>
 __global__ __launch_bounds__(kDrThreads) void k_verify_nucleus(const VnParams p) {
     using E = Elem<DT>;
     __shared__ NucleusLds sh;
     const int r = blockIdx.x, t = threadIdx.x;
     const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.logits) + static_cast<int64_t>(r) * p.ld * E::kBytes);
-    // (kTopK: thr = max(x_k, x*_K) and L64 its normaliser -- the select of asd_draft_sample_top_k)
-    const NucleusSel sel = nucleus_row_select<DT, kTopK>(row, p.V, p.nvec, p.n_tiles, p.c2, p.top_p, p.levels, sh, t, [](int) {},
-                                                         p.top_k);
+    // (kTopK: thr = max(x_k, x*_K) and L64 its normaliser -- the select of asd_draft_sample_top_k; kMinP: that of
+    // asd_draft_sample_min_p, thr = max(thr_kp, x_max + mp_delta))
+    const NucleusSel sel = nucleus_row_select<DT, kTopK, kMinP>(row, p.V, p.nvec, p.n_tiles, p.c2, p.top_p, p.levels, sh, t,
+                                                                [](int) {}, p.top_k, p.mp_delta);
     if (t != 0) return;
     const int32_t tok = p.tok[r];
     const float x_tok = (tok >= 0 && tok < p.V) ? E::scalar(row, tok) : -INFINITY;
     // log p^N(tok) with the arithmetic of draft_pick_wave's log q(tok): the same bits for the token the draft sampler drew
     double lp = -INFINITY;
     if (!(x_tok < sel.thr)) lp = kLn2d * (static_cast<double>(x_tok) * static_cast<double>(p.c2) - sel.L64);   // (NaN stays NaN)
+    if constexpr (kMinP) { if (lp > 0.0) lp = 0.0; }          // (draft_pick_wave's kClampLp: q = 1 never reads as log q > 0)
     const float lpf = static_cast<float>(lp);
     // finish_row's rule: p^N(tok) == 0 never accepts, not even at u == 0; NaN rejects by comparison
     const bool flag = lp > -INFINITY && log_u(p.u[r]) <= lp - static_cast<double>(p.lp_d[r]);
@@ -90,11 +93,11 @@ using namespace asd;
 
 namespace {
 // asd_verify_accept_top_p (top_k = 0) and asd_verify_accept_top_k; a top_k that bounds nothing (<= 0 or >= V) is the former's
-// call (the same bits)
+// call (the same bits).  min_p in (0, 1] (asd_verify_accept_min_p; 0 = none) always takes the select's route.
 int verify_truncated(const void* logits, int dtype, int64_t ld_row, const int32_t* tok, const float* lp_draft, const float* u,
                      int B, int K, int V, float inv_temperature, int top_k, float top_p, float* lp_target, uint8_t* accept,
                      int32_t* n_acc, uint64_t* accept_bits, float* t_nucleus_logit, int32_t* n_finite, void* workspace,
-                     size_t workspace_bytes, void* stream) {
+                     size_t workspace_bytes, void* stream, float min_p = 0.0f) {
     if (B < 0 || K < 0 || V < 1) return ASD_ERR_INVALID_ARG;
     if (B == 0 || K == 0) return ASD_OK;
     if (K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
@@ -106,7 +109,7 @@ int verify_truncated(const void* logits, int dtype, int64_t ld_row, const int32_
     if (R > INT32_MAX) return ASD_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Truncation tr = truncation(top_k, top_p, V, dtype);
-    if (!tr.nucleus && tr.top_k == 0) {
+    if (!tr.nucleus && tr.top_k == 0 && !(min_p > 0.0f)) {
         // no truncation: asd_verify_accept_ex itself (the same bits), then x* = -inf and the leading finite run
         asd_verify_options opt{};
         opt.inv_temperature = inv_temperature;
@@ -131,12 +134,16 @@ int verify_truncated(const void* logits, int dtype, int64_t ld_row, const int32_
     p.top_p = top_p;
     p.levels = tr.levels;
     p.top_k = tr.top_k;
+    p.mp_delta = min_p > 0.0f ? min_p_delta(min_p, inv_temperature) : 0.0f;
     p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
     p.thr = t_nucleus_logit; p.n_finite = n_finite;
     const dim3 grid(static_cast<unsigned>(R)), block(kDrThreads);
     dispatch_dtype(dtype, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
-        if (tr.top_k > 0) hipLaunchKernelGGL((k_verify_nucleus<DT, true>), grid, block, 0, st, p);
+        if (min_p > 0.0f) {
+            if (tr.top_k > 0) hipLaunchKernelGGL((k_verify_nucleus<DT, true, true>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((k_verify_nucleus<DT, false, true>), grid, block, 0, st, p);
+        } else if (tr.top_k > 0) hipLaunchKernelGGL((k_verify_nucleus<DT, true>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((k_verify_nucleus<DT, false>), grid, block, 0, st, p);
     });
     hipLaunchKernelGGL(k_nucleus_finish, dim3(static_cast<unsigned>(B)), dim3(64), 0, st, accept, lp_target, K, 1, n_acc,
@@ -161,4 +168,15 @@ ASD_EXPORT int asd_verify_accept_top_k(const void* logits, int dtype, int64_t ld
                                        size_t workspace_bytes, void* stream) {
     return verify_truncated(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, top_k, top_p, lp_target, accept,
                             n_acc, accept_bits, t_nucleus_logit, n_finite, workspace, workspace_bytes, stream);
+}
+
+ASD_EXPORT int asd_verify_accept_min_p(const void* logits, int dtype, int64_t ld_row, const int32_t* tok,
+                                       const float* lp_draft, const float* u, int B, int K, int V, float inv_temperature,
+                                       int top_k, float top_p, float min_p, float* lp_target, uint8_t* accept, int32_t* n_acc,
+                                       uint64_t* accept_bits, float* t_nucleus_logit, int32_t* n_finite, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    if (!valid_min_p(min_p)) return ASD_ERR_INVALID_ARG;
+    return verify_truncated(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, top_k, top_p, lp_target, accept,
+                            n_acc, accept_bits, t_nucleus_logit, n_finite, workspace, workspace_bytes, stream,
+                            min_p > 0.0f ? min_p : 0.0f);
 }

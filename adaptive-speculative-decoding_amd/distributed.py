@@ -151,6 +151,20 @@ class HipOps:
             logits, tok, lp_d, u, ws, inv_temperature=inv_temperature, top_k=top_k, top_p=top_p))
         return r.lp_target, r.accept, r.n_acc, r.accept_bits, r.t_nucleus_logit, r.n_finite
 
+    @traced("verify_accept_min_p")
+    def verify_accept_min_p(self, logits, tok, lp_d, u, inv_temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                            min_p: float = 0.0):
+        """Verify against the TARGET's Temperature -> TopK -> TopP -> MinP set (asd_verify_accept_min_p) -> (lp_t, accept,
+        n_acc, bits, thr [B,K], n_finite [B]); min_p <= 0 is verify_accept_top_k (the same bits)."""
+        B, K = tok.shape
+        V = logits.shape[-1]
+        off = not (0 < top_k < V) and not (0.0 < top_p < 1.0) and not min_p > 0.0
+        ws = self._workspace(B, K, V, logits.dtype, logits.device) if off else None
+        nbytes = B * K * V * logits.element_size() + 21 * B * K + 16 * B
+        r = self._timed_step("asd_verify_accept_min_p", nbytes, lambda: self.K.verify_accept_min_p(
+            logits, tok, lp_d, u, ws, inv_temperature=inv_temperature, top_k=top_k, top_p=top_p, min_p=min_p))
+        return r.lp_target, r.accept, r.n_acc, r.accept_bits, r.t_nucleus_logit, r.n_finite
+
     @traced("verify_stop")
     def verify_stop(self, logits, tok, lp_d, u, inv_temperature, pred, feat, p_hist, stage_idx, costs, lam,
                     risk_adjustment=True, n_obs=100, alpha=1.0, beta=1.0, stats_col=5):
@@ -260,6 +274,15 @@ class HipOps:
         d = s.top_k(logits, r, inv_temperature, top_k=top_k, top_p=top_p)
         return d.tok, d.lp, d.thr
 
+    @traced("draft_sample_min_p")
+    def draft_sample_min_p(self, logits, r, inv_temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                           min_p: float = 0.0):
+        """X1 under Temperature -> TopK -> TopP -> MinP (asd_draft_sample_min_p): logits [B,V] -> (tok i32 [B], log q(tok)
+        f32 [B], threshold max(thr_kp, x_max + T ln(min_p)) f32 [B])."""
+        s = self._sampler("draft", logits.shape[0], logits.shape[1], logits.dtype, logits.device)
+        d = s.min_p(logits, r, inv_temperature, min_p=min_p, top_k=top_k, top_p=top_p)
+        return d.tok, d.lp, d.thr
+
     @traced("residual_sample")
     def residual_sample(self, t_logits, d_logits, n_acc, r, bonus, inv_temperature: float = 1.0, d_threshold=None,
                         t_threshold=None, top_p: float = 1.0):
@@ -282,10 +305,14 @@ class HipOps:
 
     @traced("residual_sample_lp")
     def residual_sample_lp(self, t_logits, d_logits, n_acc, r, bonus, inv_temperature: float = 1.0, d_threshold=None,
-                           t_threshold=None, top_k: int = 0, top_p: float = 1.0):
+                           t_threshold=None, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """The committed token and its target log-prob (asd_residual_sample_lp) -> (token i32 [n], lp f32 [n]); the token is
-        residual_sample's / residual_sample_top_k's on the same arguments, lp = log p_t^N(token)."""
+        residual_sample's / residual_sample_top_k's on the same arguments, lp = log p_t^N(token).  min_p > 0: against the
+        target's min-p set as well (asd_residual_sample_lp_min_p; t_threshold = the thresholds of verify_accept_min_p)."""
         s = self._sampler("residual", t_logits.shape[0], t_logits.shape[2], t_logits.dtype, t_logits.device)
+        if min_p > 0.0:
+            return s.lp_min_p(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                              t_threshold=t_threshold, d_threshold=d_threshold)
         return s.lp(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_k=top_k, top_p=top_p, t_threshold=t_threshold,
                     d_threshold=d_threshold)
 

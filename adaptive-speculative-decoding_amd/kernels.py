@@ -213,6 +213,17 @@ def verify_accept_top_k(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
                              (int(top_k), float(top_p)), out)
 
 
+def verify_accept_min_p(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
+                        workspace: Optional[VerifyWorkspace], *, inv_temperature: float = 1.0, top_k: int = 0,
+                        top_p: float = 1.0, min_p: float = 0.0,
+                        out: Optional[NucleusVerifyResult] = None) -> NucleusVerifyResult:
+    """The verify step against the target's Temperature -> TopK -> TopP -> MinP set (include/asd_hip.h:
+    asd_verify_accept_min_p): thr = max(thr_kp, x_max + T ln(min_p)) (t_nucleus_logit).  min_p <= 0 is verify_accept_top_k (the
+    same bits); min_p > 1 or NaN is an argument error."""
+    return _verify_truncated("asd_verify_accept_min_p", logits, tok, lp_draft, u, workspace, inv_temperature,
+                             (int(top_k), float(top_p), float(min_p)), out)
+
+
 def verify_accept_stats(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
                         workspace: VerifyWorkspace, out: Optional[VerifyResult] = None, *, inv_temperature: float = 1.0,
                         want_entropy: bool = True) -> Tuple[VerifyResult, torch.Tensor, Optional[torch.Tensor]]:
@@ -726,6 +737,19 @@ class ResidualSampler(_StatusWorkspace):
                            (int(top_k), float(top_p)), lp_out, t_threshold=t_threshold, d_threshold=d_threshold)
         return tok, lp_out
 
+    def lp_min_p(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
+                 bonus_logits: Optional[torch.Tensor] = None, inv_temperature: float = 1.0, *, top_k: int = 0, top_p: float = 1.0,
+                 min_p: float = 0.0, t_threshold: Optional[torch.Tensor] = None, d_threshold: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, lp_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """lp(...) against the target's top-k + top-p + min-p set (asd_residual_sample_lp_min_p): t_threshold [B,K] = the
+        thresholds of verify_accept_min_p; the bonus rows' are found by the sampler with the same select.  min_p <= 0 is
+        lp(...) (the same bits)."""
+        if lp_out is None:
+            lp_out = torch.empty((t_logits.shape[0],), dtype=torch.float32, device=t_logits.device)
+        tok = self._sample("asd_residual_sample_lp_min_p", t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out,
+                           (int(top_k), float(top_p), float(min_p)), lp_out, t_threshold=t_threshold, d_threshold=d_threshold)
+        return tok, lp_out
+
 
 @dataclass
 class DraftDraw:
@@ -776,6 +800,13 @@ class DraftSampler(_StatusWorkspace):
         threshold of the top-p select taken over the top-k set.  HF generate(do_sample=True, ...) applies top_k = 50 unless
         told otherwise.  top_k <= 0 or >= V is __call__ (the same bits); otherwise one workgroup per row, the workspace unused."""
         return self._draw("asd_draft_sample_top_k", logits, r, inv_temperature, (int(top_k), float(top_p)), out)
+
+    def min_p(self, logits: torch.Tensor, r: torch.Tensor, inv_temperature: float = 1.0, *, min_p: float, top_k: int = 0,
+              top_p: float = 1.0, out: Optional[DraftDraw] = None) -> DraftDraw:
+        """The proposal under Temperature -> TopK -> TopP -> MinP (asd_draft_sample_min_p; HF's MinPLogitsWarper, vLLM's
+        min_p): thr = max(thr_kp, x_max + T ln(min_p)).  min_p <= 0 is top_k(...) (the same bits); otherwise one workgroup
+        per row, the workspace unused."""
+        return self._draw("asd_draft_sample_min_p", logits, r, inv_temperature, (int(top_k), float(top_p), float(min_p)), out)
 
 
 # ------------------------------------------------------------------------------- greedy decoding (temperature 0)

@@ -50,6 +50,15 @@ COST: a sampled verifying step then reads the target rows three times (verify, r
 kernel's time in a step dominated by the model passes; with `logprobs` off (0, the default) a stage runs exactly the launches
 it ran before.
 
+MIN-P.  `StageConfig.min_p` (the stage's own draws: stage 0, and the proposals its model makes for the stage above) and
+`StageConfig.target_min_p` (a verifying stage's own distribution), or `generate(min_p=...)` for the call, are HF's
+MinPLogitsWarper / vLLM's `min_p`, last in the chain Temperature -> TopK -> TopP -> MinP: a token is kept when its probability is
+at least min_p times the row's largest.  On raw logits that is one more threshold, x_max + T ln(min_p), so the draw, the verify
+and the commit draw take max(top-k / top-p threshold, that) from one select (asd_draft_sample_min_p, asd_verify_accept_min_p,
+asd_residual_sample_lp_min_p) and the loop stays lossless.  0 (the default) is off: a stage then makes exactly the calls it
+made before.  Values outside [0, 1] raise ValueError.  Greedy decoding ignores min-p, and the top-N table stays the
+untruncated distribution.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -94,6 +103,8 @@ class StageConfig:
     top_k: int = 0
     target_top_p: float = 1.0
     target_top_k: int = 0
+    min_p: float = 0.0                       # min-p of the stage's own draws, behind (top_k, top_p); 0: off (module docstring)
+    target_min_p: float = 0.0                # min-p of a verifying stage's own distribution, behind (target_top_k, target_top_p)
     draft_len: int = 8
     seed: int = 0
     sync_every: int = 4
@@ -121,6 +132,12 @@ def _check_logprobs(n) -> int:
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
         raise ValueError(f"logprobs must be an integer in [0, {MAX_TOP_LOGPROBS}], got {n!r}")
     return int(n)
+
+
+def _check_min_p(v, name: str = "min_p") -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+        raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")           # (NaN included)
+    return float(v)
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -184,6 +201,8 @@ class Stage:
             raise ValueError("a stage and the stage below it must share the vocabulary")
         if not 1 <= config.draft_len <= 64:
             raise ValueError("draft_len must be in [1, 64]")
+        _check_min_p(config.min_p, "min_p")
+        _check_min_p(config.target_min_p, "target_min_p")
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -220,7 +239,8 @@ class Stage:
     @torch.no_grad()
     def generate(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7, return_logprobs: bool = True,
                  top_p: Optional[float] = None, stop_token_ids: Optional[Sequence[int]] = None,
-                 logprobs: Optional[int] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 logprobs: Optional[int] = None,
+                 min_p: Optional[float] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -232,12 +252,16 @@ class Stage:
         stats["top_logprobs"][i] (float32 [n_i, N]): per committed token the N most likely tokens of the UNTRUNCATED
         temperature-scaled distribution it came from, most likely first (ties: lowest id), ragged like logprobs[i]; 0 = off.
         With top-k / top-p active the token's own (renormalised) log-prob is not less than its table entry, and the token is
-        always inside the nucleus (module docstring).  Anything outside 0..8 raises ValueError."""
+        always inside the nucleus (module docstring).  Anything outside 0..8 raises ValueError.
+        `min_p` overrides min-p for the call by the rule of `top_p`: StageConfig.min_p at stage 0, StageConfig.target_min_p at a
+        verifying stage; None = the configuration's, 0 = off, outside [0, 1] raises ValueError (module docstring, MIN-P)."""
         t0 = time.perf_counter()
         prompts = list(prompts)
         self.step_inputs = []
         stop = _check_stop_ids(self.config.stop_token_ids if stop_token_ids is None else stop_token_ids, self.shape.vocab)
         n_top = _check_logprobs(self.config.logprobs if logprobs is None else logprobs)
+        own_min_p = self.config.min_p if self.draft is None else self.config.target_min_p
+        min_p = _check_min_p(own_min_p if min_p is None else min_p)
         if not prompts or max_tokens <= 0:
             return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -253,10 +277,11 @@ class Stage:
             tokens, lps, seq_len = decode(ids, int(max_tokens), end, top)
         elif self.draft is None:
             tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
-                                                      self.config.top_p if top_p is None else float(top_p), end, top)
+                                                      self.config.top_p if top_p is None else float(top_p), end, top, min_p)
         else:
             tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
-                                                            self.config.target_top_p if top_p is None else float(top_p), end, top)
+                                                            self.config.target_top_p if top_p is None else float(top_p), end, top,
+                                                            min_p)
         self.ops.check_status()
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
@@ -287,11 +312,13 @@ class Stage:
         n_commit = torch.zeros((B,), dtype=torch.int32, device=dev)
         return tokens, lps, seq_len, n_commit
 
-    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float):
-        """One proposal per sequence from next-token logits [B, V] under Temperature -> (TopK ->) TopP: (tok i32, log q(tok),
-        threshold)."""
+    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float, min_p: float = 0.0):
+        """One proposal per sequence from next-token logits [B, V] under Temperature -> (TopK ->) TopP (-> MinP): (tok i32,
+        log q(tok), threshold)."""
         logits = logits.contiguous()
         r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device)
+        if min_p > 0.0:
+            return self.ops.draft_sample_min_p(logits, r, inv_t, top_k=cfg.top_k, top_p=top_p, min_p=min_p)
         if cfg.top_k > 0:
             return self.ops.draft_sample_top_k(logits, r, inv_t, top_k=cfg.top_k, top_p=top_p)
         return self.ops.draft_sample(logits, r, inv_t, top_p)
@@ -303,7 +330,8 @@ class Stage:
             self.ops.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap, end.stop_ids,
                                       end.finished, end.n_finished)
 
-    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None, top=None):
+    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None, top=None,
+                      min_p: float = 0.0):
         """Stage 0.  Without a stop set every sequence appends exactly one token per step, so all positions are known on the
         host; with one (`end`), a sequence is fed its last committed token at seq_len - 1, which is the same for a running
         sequence and stays put for a finished one."""
@@ -318,7 +346,7 @@ class Stage:
         logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
         for step in range(max_tokens):
             logits = logits.contiguous()
-            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p)
+            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p, min_p)
             if top is not None:
                 top.score(logits)
             self._commit(end, None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
@@ -433,8 +461,12 @@ class Stage:
         self.last_steps = steps
         return tokens, lps, seq_len
 
-    def _verify(self, score, tok32, lp_d, u, inv_t, top_k, top_p):
-        """-> (lp_t, n_acc, t_threshold or None) against the target's Temperature -> (TopK ->) (TopP) distribution."""
+    def _verify(self, score, tok32, lp_d, u, inv_t, top_k, top_p, min_p=0.0):
+        """-> (lp_t, n_acc, t_threshold or None) against the target's Temperature -> (TopK ->) (TopP) (-> MinP) distribution."""
+        if min_p > 0.0:
+            lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_min_p(score, tok32, lp_d, u, inv_t, top_k=top_k, top_p=top_p,
+                                                                       min_p=min_p)
+            return lp_t, n_acc, t_thr
         if top_k > 0:
             lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_top_k(score, tok32, lp_d, u, inv_t, top_k=top_k, top_p=top_p)
             return lp_t, n_acc, t_thr
@@ -444,7 +476,8 @@ class Stage:
         lp_t, _, n_acc, _ = self.ops.verify_accept(score, tok32, lp_d, u, inv_t)
         return lp_t, n_acc, None
 
-    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None, top=None):
+    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None, top=None,
+                            target_min_p: float = 0.0):
         """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
 
         Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
@@ -474,7 +507,7 @@ class Stage:
             toks, lpd, dls, thrs = [], [], [], []
             for k in range(Kd):
                 dl = dl.contiguous()
-                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p)
+                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p, dcfg.min_p)
                 toks.append(t)
                 lpd.append(lp)
                 thrs.append(thr)
@@ -488,11 +521,13 @@ class Stage:
             score = t_out[:, :Kd].contiguous()
             bonus = t_out[:, Kd].contiguous()
             u = torch.rand((B, Kd), generator=self.gen, device=dev)
-            lp_t, n_acc, t_thr = self._verify(score, tok32, lp_d, u, inv_t, cfg.target_top_k, target_top_p)
+            lp_t, n_acc, t_thr = self._verify(score, tok32, lp_d, u, inv_t, cfg.target_top_k, target_top_p, target_min_p)
             r = torch.rand((B,), generator=self.gen, device=dev)
+            # (the min_p keyword only where it is on: with it off the call is the one made before)
+            mp = dict(min_p=target_min_p) if target_min_p > 0.0 else {}
             drawn, lp_drawn = self.ops.residual_sample_lp(score, torch.stack(dls, 1).to(score.dtype).contiguous(), n_acc, r, bonus,
                                                           inv_t, d_threshold=d_thr, t_threshold=t_thr, top_k=cfg.target_top_k,
-                                                          top_p=target_top_p)
+                                                          top_p=target_top_p, **mp)
             if self.keep_inputs:
                 self.step_inputs.append(dict(logits=score.clone(), bonus=bonus.clone(), tok=tok32.clone(), lp_d=lp_d.clone(),
                                              u=u.clone(), lp_t=lp_t.clone(), n_acc=n_acc.clone(), drawn=drawn.clone(),

@@ -654,6 +654,62 @@ int asd_residual_sample_lp(const void* t_logits, int64_t ld_t, const void* d_log
                            const float* d_threshold /*[B,K] or NULL*/, int32_t* token /*[B] out*/, float* lp /*[B] out*/,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Min-p behind top-k and top-p, on all three sampling steps: HF's MinPLogitsWarper (generate(min_p=...)), vLLM's
+ * SamplingParams.min_p -- what is set in place of top-p at temperatures of 0.7 and above.  The warper keeps the tokens with
+ * p_v >= min_p * p_max, and at least one.  For a row x (raw logits, T > 0, c = inv_temperature) and 0 < min_p <= 1:
+ *   thr_kp = the threshold of Temperature -> TopK -> TopP: max(x_k, x*_K), computed exactly as asd_draft_sample_top_k computes
+ *            it for the same (top_k, top_p); -inf when both are off
+ *   x_max  = the largest value of the row, exactly (a float max over the raw logits, not the streaming pair's scaled
+ *            maximum).  x_max lies inside every top-k and every top-p set.
+ *   delta  = (float)(log((double)min_p) / (double)inv_temperature) <= 0, formed once on the host by the launcher
+ *   x_mp   = x_max + delta, ONE f32 addition on the device.  This is the warper's rule on raw logits, with min-p LAST in
+ *            the chain: p_v / p_max = exp((x_v - x_max) c) does not change under the renormalisation of top-k or top-p, so the
+ *            kept set is { x_v >= thr_kp } n { x_v >= x_mp }
+ *   thr    = max(thr_kp, x_mp);  q = softmax(x / T) restricted to { x >= thr } and renormalised.  Every tie at thr is kept and
+ *            the maximum is always kept (HF's min_tokens_to_keep = 1).
+ * The draw, lp, the accept rule, n_finite, the residual rule and the -1 / NaN poisoning are those of the top-k entry points
+ * with this thr; every threshold output below is thr.  One addition: min-p often keeps a single token, q = 1, and the f32
+ * normaliser can leave its log-prob a rounding above 0 -- the min-p entry points report such an lp / lp_target as 0 (the draft
+ * and the verify alike: still the same bits).  Where x_mp > thr_kp the normaliser is taken over { x >= x_mp } by one
+ * more sweep of the (L2-resident) row: canonical tile pairs folded in the fixed order, inside the ONE select body the three
+ * entry points share (the same bits for the same row).  With top-k and top-p both off no select runs at all.  The set is
+ * defined on raw logits in f32: against HF, which compares softmax probabilities, it can differ only for tokens whose logit
+ * lies within one f32 rounding of x_mp (for 16-bit and f32 rows alike: the boundary is a sum, not a value of the row).
+ * Off switch: min_p <= 0 is the corresponding top-k entry point (asd_draft_sample_top_k, asd_verify_accept_top_k,
+ * asd_residual_sample_lp) with the same arguments: the same bits, the same status codes.  min_p > 1 or NaN:
+ * ASD_ERR_INVALID_ARG, reported before anything else (the empty-batch return included).  Otherwise the argument checks and
+ * status codes are those of the top-k entry point with a live bound.  Rows: 16-byte aligned, a whole number of 16-byte
+ * vectors, V*sizeof(elem) <= 2 MiB, no NaN / +inf.
+ *
+ * asd_draft_sample_min_p: tok / lp / threshold as asd_draft_sample_top_k's, with thr.  ONE launch of one 1024-lane workgroup
+ *   per row at every B (the spread-over-workgroups form does not take min-p); `workspace` is accepted and left untouched.
+ * ---------------------------------------------------------------------------------------- */
+int asd_draft_sample_min_p(const void* logits, int64_t ld, int dtype, const float* r /*[B]*/, int B, int V,
+                           float inv_temperature, int top_k, float top_p, float min_p, int32_t* tok /*[B] out*/,
+                           float* lp /*[B] out, may be NULL*/, float* threshold /*[B] out, may be NULL*/,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* asd_verify_accept_min_p: asd_verify_accept_top_k against thr: lp_t = log q(tok) (-inf when x_tok < thr; bit-identical to
+ *   asd_draft_sample_min_p's lp for the token it drew), accept / n_acc / accept_bits / n_finite as there,
+ *   t_nucleus_logit = thr.  No workspace (may be NULL); two launches (one workgroup per row, one wave per sequence). */
+int asd_verify_accept_min_p(const void* logits, int dtype, int64_t ld_row,
+                            const int32_t* tok /*[B,K]*/, const float* lp_draft /*[B,K]*/, const float* u /*[B,K]*/,
+                            int B, int K, int V, float inv_temperature, int top_k, float top_p, float min_p,
+                            float* lp_target /*[B,K] out*/, uint8_t* accept /*[B,K] out*/, int32_t* n_acc /*[B] out*/,
+                            uint64_t* accept_bits /*[B] out, may be NULL*/, float* t_nucleus_logit /*[B,K] out, may be NULL*/,
+                            int32_t* n_finite /*[B] out, may be NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+/* asd_residual_sample_lp_min_p: asd_residual_sample_lp with thr: rows j < K take t_threshold[b,j] (asd_verify_accept_min_p's
+ *   t_nucleus_logit), the bonus row's thr is found here by the same select (bit-identical to asd_draft_sample_min_p's
+ *   threshold on that row), d_threshold = the draft draw's threshold.  workspace:
+ *   asd_residual_sample_top_p_workspace_bytes, the geometry of asd_residual_sample_top_p. */
+int asd_residual_sample_lp_min_p(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                                 const void* bonus_logits, int64_t ld_b, int dtype,
+                                 const int32_t* n_acc /*[B]*/, const float* r /*[B]*/, int B, int K, int V,
+                                 float inv_temperature, int top_k, float top_p, float min_p,
+                                 const float* t_threshold /*[B,K]*/, const float* d_threshold /*[B,K] or NULL*/,
+                                 int32_t* token /*[B] out*/, float* lp /*[B] out*/,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* N1, second form: asd_verify_accept with the epilogue of asd_predictor_stop run INSIDE the same
  * launch by the wave that completes each sequence (lp = the kernel's own lp_target, all K
  * positions valid).  ONE launch per tier step instead of two, at every batch size: with one workgroup
