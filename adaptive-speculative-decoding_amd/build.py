@@ -34,6 +34,7 @@ SOURCES = {
     "commit.hip": [],
     "greedy.hip": ["-ffp-contract=off"],          # lp_argmax / lp_target end in finish_row's arithmetic, as verify_accept.hip's do
     "top_logprobs.hip": ["-ffp-contract=off"],    # greedy.hip's (m2, s) stream and row_logprob: slot 0 has lp_argmax's bits
+    "philox.hip": [],                             # integer arithmetic and one exact conversion: no flag changes its bits
     "lm_head_verify.hip": ["-ffp-contract=off"],  # ends in the same finish_row arithmetic as verify_accept.hip
     "decision.hip": ["-ffp-contract=off"],
     "predictor.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=11"],   # k_predictor_stop_w64x32's leading arguments

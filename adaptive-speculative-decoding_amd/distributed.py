@@ -350,6 +350,27 @@ class HipOps:
         reads the seq_len / n_commit they left."""
         self.K.commit_top_logprobs(top_id, top_lp, seq_len, n_commit, out_id, out_lp, max_len=max_len)
 
+    @traced("step_uniforms")
+    def step_uniforms(self, seeds, step, stage, K_draft, K_accept, commit: bool = True, out=None):
+        """Every uniform of a seeded decoding step in ONE launch (asd_step_uniforms; Philox4x32-10 keyed by seeds[b] i64 [B],
+        counter (step, k, stage, 0)) -> (r_draft f32 [K_draft, B] | None, u f32 [B, K_accept] | None, r_commit f32 [B] | None):
+        r_draft[k] is the proposal uniform of slot k, u[:, k] the accept uniform of slot k.  An output whose K is 0 (and
+        r_commit with commit=False) is None and not written.  The three are views of `out`, one f32 buffer of at least
+        (K_draft + K_accept + 1) * B elements that a stage loop allocates once per generate call (None: a fresh one), so a
+        step's uniforms are valid until the next call on the same buffer (stream order)."""
+        Bv = seeds.shape[0]
+        Kd, Ka = int(K_draft), int(K_accept)
+        need = (Kd + Ka + 1) * Bv
+        if out is None:
+            out = torch.empty((need,), dtype=torch.float32, device=seeds.device)
+        if out.dim() != 1 or out.numel() < need:
+            raise ValueError(f"out must be a float32 vector of at least {need} elements")
+        r_draft = out[:Kd * Bv].view(Kd, Bv) if Kd > 0 else None
+        u = out[Kd * Bv:(Kd + Ka) * Bv].view(Bv, Ka) if Ka > 0 else None
+        r_commit = out[(Kd + Ka) * Bv:need] if commit else None
+        self.K.step_uniforms(seeds, step, stage, r_draft, u, r_commit)
+        return r_draft, u, r_commit
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

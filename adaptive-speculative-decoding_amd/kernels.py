@@ -949,3 +949,28 @@ def commit_top_logprobs(top_id: torch.Tensor, top_lp: torch.Tensor, seq_len: tor
                                         _dev(seq_len, "seq_len", torch.int32), _dev(n_commit, "n_commit", torch.int32), Bv, K1, N,
                                         _dev(out_id, "out_id", torch.int32), _dev(out_lp, "out_lp", torch.float32), cap, _stream())
     B.check("asd_commit_top_logprobs", rc)
+
+
+# ------------------------------------------------------------------------------- per-request seeds (SamplingParams(seed=...))
+def step_uniforms(seeds: torch.Tensor, step: int, stage: int, r_draft: Optional[torch.Tensor] = None,
+                  u: Optional[torch.Tensor] = None, r_commit: Optional[torch.Tensor] = None) -> None:
+    """Every uniform of a decoding step in one launch (asd_step_uniforms): Philox4x32-10 with key seeds[b] (int64 [B], read as
+    uint64) and counter (step, k, stage, 0).  r_draft f32 [K_draft, B]: the proposal uniform of slot k; u f32 [B, K_accept]: the
+    accept uniform of slot k; r_commit f32 [B]: the commit uniform.  An output left None is not written; at least one is
+    given.  Values lie in [0, 1) and depend on (seeds[b], step, stage, k) alone."""
+    if seeds.dim() != 1:
+        raise ValueError("seeds must be int64 [B]")
+    Bv = seeds.shape[0]
+    if not 0 <= int(step) < 2 ** 32 or not 0 <= int(stage) < 2 ** 32:
+        raise ValueError("step and stage must lie in [0, 2^32)")
+    if r_draft is not None and (r_draft.dim() != 2 or r_draft.shape[1] != Bv):
+        raise ValueError("r_draft must be float32 [K_draft, B]")
+    if u is not None and (u.dim() != 2 or u.shape[0] != Bv):
+        raise ValueError("u must be float32 [B, K_accept]")
+    if r_commit is not None and tuple(r_commit.shape) != (Bv,):
+        raise ValueError("r_commit must be float32 [B]")
+    rc = _lib().asd_step_uniforms(_dev(seeds, "seeds", torch.int64), int(step), int(stage), Bv,
+                                  0 if r_draft is None else r_draft.shape[0], 0 if u is None else u.shape[1],
+                                  _opt(r_draft, "r_draft", torch.float32), _opt(u, "u", torch.float32),
+                                  _opt(r_commit, "r_commit", torch.float32), _stream())
+    B.check("asd_step_uniforms", rc)

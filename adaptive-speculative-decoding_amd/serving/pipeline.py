@@ -7,6 +7,12 @@ arithmetic of the stage loop (Bayes adjustment, DP stop rule) done by batched ke
         process_request / process_request_async / batch_process / update_lambda / get_stats /
         reset_stats / warmup / shutdown
 
+Per-request seeds (build extension; SamplingParams(seed=...)): `process_request(..., seed=)` and `batch_process(..., seeds=)`
+take ints in [0, 2^64) (serving/stages.py, SEEDS; a batch passes a seed for every request or none).  A request's seed travels
+with it through every regrouping -- the `predicted_stage` groups, the cache split, the requests that leave the cascade -- and
+reaches every stage as `stage.generate(seed=[...])`, so its draws do not depend on the requests it happens to be batched with.
+Without seeds the keyword is not passed.
+
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
                      p_i = predictor.predict(...)  (1.0 at the last stage)        :225-241
@@ -48,6 +54,7 @@ import numpy as np
 
 from ..backend import get_backend
 from .cache import RequestCache
+from .stages import check_seeds
 
 logger = logging.getLogger(__name__)
 
@@ -136,6 +143,7 @@ class _Active:
     total_tokens: int = 0
     k_star: int = -1
     predicted_stage: int = -1
+    seed: Optional[int] = None                              # the request's sampling seed (None: the stage's own generator)
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -166,25 +174,32 @@ class AdaptiveSpeculativePipeline:
 
     # ------------------------------------------------------------------ public API
     def process_request(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
-                        request_id: Optional[str] = None) -> RequestResult:
-        return self._run_batch([prompt], max_tokens, temperature, [request_id])[0]
+                        request_id: Optional[str] = None, seed: Optional[int] = None) -> RequestResult:
+        """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring)."""
+        if seed is not None and not isinstance(seed, (int, np.integer)):
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1))[0]
 
     async def process_request_async(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
-                                    request_id: Optional[str] = None) -> RequestResult:
+                                    request_id: Optional[str] = None, seed: Optional[int] = None) -> RequestResult:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.executor, self.process_request, prompt, max_tokens, temperature,
-                                          request_id)
+                                          request_id, seed)
 
-    def batch_process(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7) -> List[RequestResult]:
+    def batch_process(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7,
+                      seeds=None) -> List[RequestResult]:
+        """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
+        raises ValueError); request i keeps seeds[i] through every regrouping (module docstring)."""
         prompts = list(prompts)
+        seeds = check_seeds(seeds, len(prompts))
         if self.config.batch_grouping != "predicted_stage" or len(prompts) < 2 or self.config.stop_rule == "prefix":
-            return self._run_batch(prompts, max_tokens, temperature, [None] * len(prompts))
+            return self._run_batch(prompts, max_tokens, temperature, [None] * len(prompts), seeds=seeds)
         pred = self.predict_stop_stages(prompts)
         results: List[Optional[RequestResult]] = [None] * len(prompts)
         for stage in sorted(set(pred.tolist())):                       # shallowest group first
             idx = [i for i, s in enumerate(pred) if s == stage]
             out = self._run_batch([prompts[i] for i in idx], max_tokens, temperature, [None] * len(idx),
-                                  predicted=[int(stage)] * len(idx))
+                                  predicted=[int(stage)] * len(idx), seeds=None if seeds is None else [seeds[i] for i in idx])
             for i, r in zip(idx, out):
                 results[i] = r
         return results  # type: ignore[return-value]
@@ -268,13 +283,17 @@ class AdaptiveSpeculativePipeline:
 
     # ------------------------------------------------------------------ the stage loop, batched
     def _run_batch(self, prompts: List[str], max_tokens: int, temperature: float,
-                   request_ids: List[Optional[str]], predicted: Optional[List[int]] = None) -> List[RequestResult]:
+                   request_ids: List[Optional[str]], predicted: Optional[List[int]] = None,
+                   seeds: Optional[List[int]] = None) -> List[RequestResult]:
         now = time.time()
         reqs = [_Active(request_id=rid or str(uuid.uuid4()), prompt=p, current_prompt=p, start_time=now)
                 for p, rid in zip(prompts, request_ids)]
         if predicted is not None:
             for r, s in zip(reqs, predicted):
                 r.predicted_stage = s
+        if seeds is not None:
+            for r, s in zip(reqs, seeds):
+                r.seed = s
         for r in reqs:
             self.active_requests[r.request_id] = {"start_time": r.start_time,
                                                   "prompt": r.prompt[:100] + "..." if len(r.prompt) > 100 else r.prompt}
@@ -325,6 +344,8 @@ class AdaptiveSpeculativePipeline:
                 stop_kw = {} if cfg.stop_token_ids is None else {"stop_token_ids": tuple(cfg.stop_token_ids)}
                 if cfg.logprobs is not None:
                     stop_kw["logprobs"] = int(cfg.logprobs)
+                if todo[0].seed is not None:                            # (a batch carries seeds for all of its requests or for none)
+                    stop_kw["seed"] = [r.seed for r in todo]
                 texts, logprobs, stage_stats = stage.generate(prompts=[r.current_prompt for r in todo],
                                                               max_tokens=max_tokens, temperature=temperature,
                                                               return_logprobs=True, **stop_kw)

@@ -59,6 +59,21 @@ asd_residual_sample_lp_min_p) and the loop stays lossless.  0 (the default) is o
 made before.  Values outside [0, 1] raise ValueError.  Greedy decoding ignores min-p, and the top-N table stays the
 untruncated distribution.
 
+SEEDS.  `generate(seed=...)` is the serving parameter `SamplingParams(seed=...)`: one int in [0, 2^64) for every prompt of the
+call, or one per prompt.  A seeded call draws nothing from the stage's torch.Generator and launches no torch.rand: every step
+makes ONE ops.step_uniforms call (asd_step_uniforms, Philox4x32-10 keyed by the row's seed, counter (step, slot, stage, 0)) that
+writes all the uniforms of the step -- stage 0 its one proposal uniform, a verifying stage the draft_len proposal uniforms, the
+[B, draft_len] accept uniforms and the commit uniform -- where a sampled verifying step of an unseeded call launches
+draft_len + 2 torch.rand kernels.  `step` is the loop's own 0-based step index (a finished sequence keeps stepping with the
+batch, so it is every sequence's own step count) and `stage` is the stage's index; every draw has its own counter and output
+word, so the loop stays lossless.  What a seed guarantees: a row's uniforms depend only on its seed, the stage index and the
+step -- not on its row index, the batch size, the other requests, earlier calls, StageConfig.seed or draft_len.  What it does
+not: left-padding still makes a row's LOGITS depend on the longest prompt of the call, and the model kernels may pick other
+tilings at another batch size.  So bit-equal text is promised for the same call repeated, and for a permuted batch of
+equal-length prompts (seeds permuted with them); it is not promised across batch sizes.  `seed=None` (the default) is the
+behaviour described above, with exactly the ops calls and generator use it had; greedy decoding makes no call and ignores the
+seed.  A bool, a float, a negative value, a value >= 2^64, a sequence of the wrong length or one that holds None raise ValueError.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -140,6 +155,24 @@ def _check_min_p(v, name: str = "min_p") -> float:
     return float(v)
 
 
+def _check_seed(v) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {v!r}")
+    return int(v)
+
+
+def check_seeds(seed, n: int) -> Optional[List[int]]:
+    """generate's `seed`: None, one int in [0, 2^64) for all `n` prompts, or a sequence of n such ints -> None or n ints."""
+    if seed is None:
+        return None
+    if isinstance(seed, (str, bytes)) or not isinstance(seed, (Sequence, np.ndarray)):
+        return [_check_seed(seed)] * n
+    seeds = [_check_seed(v) for v in seed]
+    if len(seeds) != n:
+        raise ValueError(f"{len(seeds)} seeds for {n} prompts")
+    return seeds
+
+
 def _shape_of(cfg: StageConfig) -> LMShape:
     if cfg.shape is not None:
         return cfg.shape
@@ -183,6 +216,20 @@ class _TopState:
 
     def record(self) -> dict:
         return dict(top_id=self.step[0].clone(), top_lp=self.step[1].clone())
+
+
+class _SeedState:
+    """What a seeded generate call keeps: the seeds on the device (uploaded once, two's-complement wrap above 2^63 - 1), the one
+    buffer every step's uniforms are written to, and the step's single ops.step_uniforms call."""
+
+    def __init__(self, ops, seeds: Sequence[int], stage: int, k_max: int, device):
+        self.ops, self.stage = ops, int(stage)
+        self.seeds = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device=device)
+        self.buf = torch.empty(((2 * k_max + 1) * len(seeds),), dtype=torch.float32, device=device)
+
+    def step(self, step: int, k_draft: int, k_accept: int, commit: bool):
+        """-> (r_draft [k_draft, B] | None, u [B, k_accept] | None, r_commit [B] | None), valid until the next step."""
+        return self.ops.step_uniforms(self.seeds, step, self.stage, k_draft, k_accept, commit=commit, out=self.buf)
 
 
 class Stage:
@@ -240,7 +287,8 @@ class Stage:
     def generate(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7, return_logprobs: bool = True,
                  top_p: Optional[float] = None, stop_token_ids: Optional[Sequence[int]] = None,
                  logprobs: Optional[int] = None,
-                 min_p: Optional[float] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 min_p: Optional[float] = None,
+                 seed=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -254,7 +302,14 @@ class Stage:
         With top-k / top-p active the token's own (renormalised) log-prob is not less than its table entry, and the token is
         always inside the nucleus (module docstring).  Anything outside 0..8 raises ValueError.
         `min_p` overrides min-p for the call by the rule of `top_p`: StageConfig.min_p at stage 0, StageConfig.target_min_p at a
-        verifying stage; None = the configuration's, 0 = off, outside [0, 1] raises ValueError (module docstring, MIN-P)."""
+        verifying stage; None = the configuration's, 0 = off, outside [0, 1] raises ValueError (module docstring, MIN-P).
+        `seed`: None = the stage's own generator (StageConfig.seed), as before; an int in [0, 2^64) for every prompt, or a
+        sequence of len(prompts) such ints, makes row i's uniforms a function of (seed_i, this stage's index, the step) alone
+        -- not of the row index, the batch size, the other requests, earlier calls, StageConfig.seed or draft_len -- through one
+        ops.step_uniforms call per step and no torch.rand.  The same call repeated, and a permuted batch of equal-length prompts
+        with the seeds permuted alike, return bit-equal texts and log-probs; another batch size may not (left-padding and the
+        model kernels' tilings change the logits).  Greedy decoding ignores it.  Anything else raises ValueError (module
+        docstring, SEEDS)."""
         t0 = time.perf_counter()
         prompts = list(prompts)
         self.step_inputs = []
@@ -262,6 +317,7 @@ class Stage:
         n_top = _check_logprobs(self.config.logprobs if logprobs is None else logprobs)
         own_min_p = self.config.min_p if self.draft is None else self.config.target_min_p
         min_p = _check_min_p(own_min_p if min_p is None else min_p)
+        seeds = check_seeds(seed, len(prompts))
         if not prompts or max_tokens <= 0:
             return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -272,16 +328,20 @@ class Stage:
         end = _StopState(stop, B, ids.device) if stop else None
         inv_t = 1.0 if temperature == 0.0 else float(np.float32(1.0 / temperature))
         top = _TopState(self.ops, n_top, inv_t, B, P + int(max_tokens), ids.device) if n_top else None
+        rng = None
+        if seeds is not None and temperature != 0.0:
+            rng = _SeedState(self.ops, seeds, self.index, 1 if self.draft is None else self.config.draft_len, ids.device)
         if temperature == 0.0:                           # greedy: no draws, no truncation (module docstring)
             decode = self._decode_plain_greedy if self.draft is None else self._decode_speculative_greedy
             tokens, lps, seq_len = decode(ids, int(max_tokens), end, top)
         elif self.draft is None:
             tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
-                                                      self.config.top_p if top_p is None else float(top_p), end, top, min_p)
+                                                      self.config.top_p if top_p is None else float(top_p), end, top, min_p,
+                                                      rng)
         else:
             tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
                                                             self.config.target_top_p if top_p is None else float(top_p), end, top,
-                                                            min_p)
+                                                            min_p, rng)
         self.ops.check_status()
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
@@ -312,11 +372,12 @@ class Stage:
         n_commit = torch.zeros((B,), dtype=torch.int32, device=dev)
         return tokens, lps, seq_len, n_commit
 
-    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float, min_p: float = 0.0):
+    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float, min_p: float = 0.0, r=None):
         """One proposal per sequence from next-token logits [B, V] under Temperature -> (TopK ->) TopP (-> MinP): (tok i32,
-        log q(tok), threshold)."""
+        log q(tok), threshold).  r: the [B] uniforms of a seeded call; None: drawn from the stage's generator."""
         logits = logits.contiguous()
-        r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device)
+        if r is None:
+            r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device)
         if min_p > 0.0:
             return self.ops.draft_sample_min_p(logits, r, inv_t, top_k=cfg.top_k, top_p=top_p, min_p=min_p)
         if cfg.top_k > 0:
@@ -331,7 +392,7 @@ class Stage:
                                       end.finished, end.n_finished)
 
     def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None, top=None,
-                      min_p: float = 0.0):
+                      min_p: float = 0.0, rng=None):
         """Stage 0.  Without a stop set every sequence appends exactly one token per step, so all positions are known on the
         host; with one (`end`), a sequence is fed its last committed token at seq_len - 1, which is the same for a running
         sequence and stays put for a finished one."""
@@ -346,7 +407,8 @@ class Stage:
         logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
         for step in range(max_tokens):
             logits = logits.contiguous()
-            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p, min_p)
+            r = None if rng is None else rng.step(step, 1, 0, False)[0][0]      # seeded: the step's one launch
+            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p, min_p, r)
             if top is not None:
                 top.score(logits)
             self._commit(end, None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
@@ -354,6 +416,8 @@ class Stage:
                 top.commit(seq_len, n_commit)
             if self.keep_inputs:
                 self.step_inputs.append(dict(logits=logits.clone(), drawn=tok.clone(), lp_drawn=lp.clone(), thr=thr.clone()))
+                if r is not None:
+                    self.step_inputs[-1].update(r_draft=r[None].clone())
                 if top is not None:
                     self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
             self.last_steps = step + 1
@@ -477,7 +541,7 @@ class Stage:
         return lp_t, n_acc, None
 
     def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None, top=None,
-                            target_min_p: float = 0.0):
+                            target_min_p: float = 0.0, rng=None):
         """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
 
         Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
@@ -504,10 +568,12 @@ class Stage:
             window = min(P + steps * (Kd + 1) + Kd + 1, cap + Kd + 2)   # host-side bound on every position touched this step
             last2 = torch.stack([tokens[rows, L - 2], tokens[rows, L - 1]], 1).to(torch.int64)
             dl = draft.forward_ragged(last2, L - 2, window)[:, -1]
+            # seeded: ONE launch for every uniform of the step (proposal k takes rd[k], the verify u, the commit draw r)
+            rd, u, r = (None, None, None) if rng is None else rng.step(steps, Kd, Kd, True)
             toks, lpd, dls, thrs = [], [], [], []
             for k in range(Kd):
                 dl = dl.contiguous()
-                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p, dcfg.min_p)
+                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p, dcfg.min_p, None if rd is None else rd[k])
                 toks.append(t)
                 lpd.append(lp)
                 thrs.append(thr)
@@ -520,9 +586,11 @@ class Stage:
             t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
             score = t_out[:, :Kd].contiguous()
             bonus = t_out[:, Kd].contiguous()
-            u = torch.rand((B, Kd), generator=self.gen, device=dev)
+            if rng is None:
+                u = torch.rand((B, Kd), generator=self.gen, device=dev)
             lp_t, n_acc, t_thr = self._verify(score, tok32, lp_d, u, inv_t, cfg.target_top_k, target_top_p, target_min_p)
-            r = torch.rand((B,), generator=self.gen, device=dev)
+            if rng is None:
+                r = torch.rand((B,), generator=self.gen, device=dev)
             # (the min_p keyword only where it is on: with it off the call is the one made before)
             mp = dict(min_p=target_min_p) if target_min_p > 0.0 else {}
             drawn, lp_drawn = self.ops.residual_sample_lp(score, torch.stack(dls, 1).to(score.dtype).contiguous(), n_acc, r, bonus,
@@ -533,6 +601,8 @@ class Stage:
                                              u=u.clone(), lp_t=lp_t.clone(), n_acc=n_acc.clone(), drawn=drawn.clone(),
                                              lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone(),
                                              t_thr=None if t_thr is None else t_thr.clone()))
+                if rd is not None:
+                    self.step_inputs[-1].update(r_draft=rd.clone(), r_commit=r.clone())
             if top is not None:
                 top.score(t_out)                                        # the [B, K+1, V] output as returned, not the copies
             self._commit(end, tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)

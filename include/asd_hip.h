@@ -401,6 +401,27 @@ int asd_commit_top_logprobs(const int32_t* top_id /*[B,K1,N]*/, const float* top
                             int max_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-request seeds (SamplingParams(seed=...); the reference's evaluation runs `random_seeds: [42, 123, 456, 789, 999]`):
+ * every uniform a decoding step consumes, in ONE launch, from a counter-based generator keyed by the request's seed.
+ * Generator: Philox4x32-10 (Random123), multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85.
+ *   key     = (seed_lo, seed_hi) of seeds[b], the 64 bits read as unsigned
+ *   counter = (step, k, stage, 0): the caller's step index, the draft slot k, the stage's index
+ *   word 0 of counter (step, k, stage, 0): the proposal uniform of slot k   -> r_draft[k*B + b]   (k < K_draft)
+ *   word 1:                                the accept uniform of slot k     -> u[b*K_accept + k]  (k < K_accept)
+ *   word 2, from k == 0 only:              the commit uniform               -> r_commit[b]
+ *   word 3: unused
+ *   float = (float)(x >> 8) * 2^-24: exact, in [0, 1) (torch.rand's range; 0 is possible, 1 is not)
+ * A row's uniforms depend on (seeds[b], step, stage) alone: not on b, B, the other rows, K_draft / K_accept or earlier calls.
+ * A NULL output is skipped.  One thread per (b, k), k < max(K_draft, K_accept, 1); no workspace, nothing waits.
+ * Status: B < 1, K_draft or K_accept outside [0, ASD_MAX_DRAFT_LEN], NULL seeds, all three outputs NULL, r_draft with
+ * K_draft < 1, u with K_accept < 1: invalid argument, nothing launched; seeds not 8-byte or an output not 4-byte aligned:
+ * alignment.
+ * ---------------------------------------------------------------------------------------- */
+int asd_step_uniforms(const int64_t* seeds /*[B], read as uint64*/, uint32_t step, uint32_t stage, int B, int K_draft,
+                      int K_accept, float* r_draft /*[K_draft,B] out, may be NULL*/,
+                      float* u /*[B,K_accept] out, may be NULL*/, float* r_commit /*[B] out, may be NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,
  * src/training/generate_training_data.py:166-175 -- np.mean, np.std (population), np.min,
  * np.percentile(.,25) (linear interpolation), np.median, all in float64 like numpy.

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_verify_greedy, asd_top_logprobs and asd_commit_top_logprobs in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs and asd_step_uniforms in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -192,6 +192,27 @@ int main() {
         EXPECT(CTOP(i32, f32, i32, i32, B, K1, NT, nullptr, f32, 32), ASD_ERR_INVALID_ARG);
         EXPECT(CTOP(i32, f32, i32, i32, B, K1, NT, i32, nullptr, 32), ASD_ERR_INVALID_ARG);
 #undef CTOP
+    }
+
+    // ---- asd_step_uniforms: every rejection is ASD_ERR_INVALID_ARG and comes before the launch
+    {
+        const int64_t* seeds = reinterpret_cast<const int64_t*>(rows);
+#define UNI(seeds_, B_, Kd_, Ka_, rd_, u_, rc_) asd_step_uniforms(seeds_, 0u, 0u, B_, Kd_, Ka_, rd_, u_, rc_, nullptr)
+        EXPECT(UNI(seeds, 0, 2, 2, f32, f32, f32), ASD_ERR_INVALID_ARG);                                    // B < 1
+        EXPECT(UNI(seeds, -1, 2, 2, f32, f32, f32), ASD_ERR_INVALID_ARG);
+        EXPECT(UNI(seeds, B, -1, 2, f32, f32, f32), ASD_ERR_INVALID_ARG);
+        EXPECT(UNI(seeds, B, 2, -1, f32, f32, f32), ASD_ERR_INVALID_ARG);
+        EXPECT(UNI(seeds, B, ASD_MAX_DRAFT_LEN + 1, 2, f32, f32, f32), ASD_ERR_INVALID_ARG);
+        EXPECT(UNI(seeds, B, 2, ASD_MAX_DRAFT_LEN + 1, f32, f32, f32), ASD_ERR_INVALID_ARG);
+        EXPECT(UNI(nullptr, B, 2, 2, f32, f32, f32), ASD_ERR_INVALID_ARG);                                  // seeds
+        EXPECT(UNI(seeds, B, 2, 2, nullptr, nullptr, nullptr), ASD_ERR_INVALID_ARG);                        // no output at all
+        EXPECT(UNI(seeds, B, 0, 0, nullptr, nullptr, nullptr), ASD_ERR_INVALID_ARG);
+        EXPECT(UNI(seeds, B, 0, 2, f32, f32, f32), ASD_ERR_INVALID_ARG);                                    // r_draft without a slot
+        EXPECT(UNI(seeds, B, 2, 0, f32, f32, f32), ASD_ERR_INVALID_ARG);                                    // u without a slot
+        EXPECT(UNI(seeds, INT32_MAX, ASD_MAX_DRAFT_LEN, ASD_MAX_DRAFT_LEN, nullptr, nullptr, nullptr), ASD_ERR_INVALID_ARG);   // (the largest grid the launcher would size)
+        EXPECT(UNI(reinterpret_cast<const int64_t*>(rows + 4), B, 2, 2, f32, f32, f32), ASD_ERR_ALIGNMENT);
+        EXPECT(UNI(seeds, B, 2, 2, reinterpret_cast<float*>(rows + 2), f32, f32), ASD_ERR_ALIGNMENT);
+#undef UNI
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
