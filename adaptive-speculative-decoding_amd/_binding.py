@@ -21,6 +21,7 @@ MAX_DRAFT_LEN = 64
 MAX_STAGES = 16
 MAX_SPLITS = 64
 MAX_TOP_LOGPROBS = 8
+MAX_STOP_SEQS, MAX_STOP_SEQ_LEN = 16, 8
 MAX_MLP_DIM = 1024
 NUM_LP_STATS = 5
 WS_LOST_HANDOFF = 0x1
@@ -94,6 +95,8 @@ SIGNATURES = {
     "asd_verify_greedy": (_i, [_vp, _i, _i64, _i64, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "asd_top_logprobs_workspace_bytes": (_sz, [_i, _i, _i]),
     "asd_top_logprobs": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "asd_commit_step_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i,
+                                    _vp]),
     "asd_commit_top_logprobs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "asd_step_uniforms": (_i, [_vp, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "asd_logprob_stats": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),

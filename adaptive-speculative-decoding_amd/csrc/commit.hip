@@ -7,6 +7,8 @@
 //   row b of the token buffer receives tok[b, 0 .. n_acc[b]) followed by drawn[b] at seq_len[b],
 //   seq_len[b] += n_acc[b] + 1  (clamped to max_len; tokens past max_len are dropped),
 //   n_commit[b] = number of tokens actually appended.
+// asd_commit_step_stop ends a row at a stop id, asd_commit_step_finish at a multi-token stop sequence of the row's own list or at
+// the row's own length limit.
 // One wave per sequence (K <= 64): lane k moves draft token k.  Integer work: bit-exact vs the oracle.
 #include "common.hpp"
 
@@ -120,6 +122,109 @@ __global__ __launch_bounds__(64) void k_commit_top_logprobs(const int32_t* top_i
     }
 }
 
+// asd_commit_step_finish: k_commit_step_stop with multi-token stop sequences, per-row sequence lists and a per-row length limit.
+// The wave keeps the row's window in LDS: kHist = ASD_MAX_STOP_SEQ_LEN - 1 history tokens (stream positions len - kHist .. len - 1;
+// read only inside [max(start, 0), len), anything else holds 0 and is never compared: a match that would begin in front of
+// `start` is refused by its position) followed by the up to 65 candidates.  Lane j asks "does an owned sequence end at candidate
+// j" by comparing backwards from slot kHist + j; candidate 64 (K = 64 with every draft token accepted: the drawn token) has no
+// lane of its own and is tested by all lanes alike, only when no earlier candidate matched.  One ballot and a find-first-set give
+// j*; a shuffle brings the matched sequence's index from lane j*.  Slots behind the drawn token are never read (a window ends
+// at its own candidate and j < fit <= na + 1), so rejected draft tokens take no part.
+constexpr int kHist = ASD_MAX_STOP_SEQ_LEN - 1;
+
+// -> index (within the row's list) of the first owned sequence that ends at candidate j, or -1
+__device__ __forceinline__ int first_seq_ending_at(const int32_t* win, int j, int len, int32_t start, const int32_t* seq_tok,
+                                                   const int32_t* seq_n, int first, int n_own) {
+    for (int s = 0; s < n_own; ++s) {
+        const int m = seq_n[first + s];
+        if (m < 1 || m > ASD_MAX_STOP_SEQ_LEN) continue;
+        if (len + j - m + 1 < start) continue;                    // no token of a match lies in the prompt
+        const int32_t* const want = seq_tok + static_cast<int64_t>(first + s) * ASD_MAX_STOP_SEQ_LEN;
+        const int32_t* const have = win + kHist + j - m + 1;     // >= win: m <= kHist + 1
+        bool same = true;
+        for (int i = 0; i < m; ++i) same &= have[i] == want[i];
+        if (same) return s;
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(64) void k_commit_step_finish(const int32_t* tok, const float* lp_tok, const int32_t* n_acc,
+                                                           const int32_t* drawn, const float* lp_drawn, int B, int K,
+                                                           const int32_t* seq_tok, const int32_t* seq_n, int n_seq,
+                                                           const int32_t* row_first, const int32_t* row_max_len, int32_t start,
+                                                           int32_t* seq_len, int32_t* out_tokens, float* out_lp, int64_t ld_out,
+                                                           int32_t* n_commit, int32_t* finished, int32_t* n_finished,
+                                                           int32_t* matched, int32_t max_len) {
+    __shared__ int32_t win[kHist + ASD_MAX_DRAFT_LEN + 1];
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int len = seq_len[b];                      // every lane reads the old length and flag before lane 0 rewrites them
+    if (finished[b] != 0) {                          // wave-uniform
+        if (lane == 0 && n_commit) n_commit[b] = 0;
+        return;
+    }
+    int limit = max_len;
+    if (row_max_len) {
+        const int own = row_max_len[b] < 0 ? 0 : row_max_len[b];
+        limit = own < max_len ? own : max_len;
+    }
+    int na = n_acc[b];
+    na = na < 0 ? 0 : (na > K ? K : na);
+    int fit = limit - len;
+    fit = fit < 0 ? 0 : (fit > na + 1 ? na + 1 : fit);
+    // the row's sequences: [first, first + n_own) of the n_seq uploaded ones, at most ASD_MAX_STOP_SEQS, never outside the arrays
+    int first = 0, n_own = n_seq;
+    if (row_first) {
+        first = row_first[b];
+        n_own = row_first[b + 1] - first;
+    }
+    if (first < 0 || first > n_seq) n_own = 0;
+    n_own = n_own > n_seq - first ? n_seq - first : n_own;
+    n_own = n_own < 0 ? 0 : (n_own > ASD_MAX_STOP_SEQS ? ASD_MAX_STOP_SEQS : n_own);
+    const int32_t d = drawn[b];
+    const int32_t c = lane < na ? tok[static_cast<int64_t>(b) * K + lane] : d;
+    int32_t* row = out_tokens + static_cast<int64_t>(b) * ld_out;
+    int j = -1, which = -1;
+    if (n_own > 0 && fit > 0) {                      // wave-uniform
+        if (lane < kHist) {
+            const int64_t pos = static_cast<int64_t>(len) - kHist + lane;
+            win[lane] = (pos >= start && pos >= 0) ? row[pos] : 0;           // pos < len < limit <= ld_out
+        }
+        if (lane <= na) win[kHist + lane] = c;       // slot na holds the drawn token (lane na == 64 does not exist: below)
+        if (lane == 0 && na == 64) win[kHist + 64] = d;
+        __syncthreads();
+        const int mine = lane < fit ? first_seq_ending_at(win, lane, len, start, seq_tok, seq_n, first, n_own) : -1;
+        const unsigned long long hits = __ballot(mine >= 0);
+        if (hits) {
+            j = __ffsll(hits) - 1;
+            which = __shfl(mine, j);
+        } else if (fit > 64) {                       // candidate 64, by every lane alike
+            which = first_seq_ending_at(win, 64, len, start, seq_tok, seq_n, first, n_own);
+            j = which >= 0 ? 64 : -1;
+        }
+    }
+    const int appended = j >= 0 ? j + 1 : fit;
+    if (lane < na && lane < appended) {
+        row[len + lane] = c;
+        out_lp[static_cast<int64_t>(b) * ld_out + len + lane] = lp_tok[static_cast<int64_t>(b) * K + lane];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) {
+        if (na < appended) {
+            row[len + na] = d;
+            out_lp[static_cast<int64_t>(b) * ld_out + len + na] = lp_drawn[b];
+        }
+        seq_len[b] = len + appended;
+        if (n_commit) n_commit[b] = appended;
+        const int32_t reason = j >= 0 ? 1 : (len + appended >= limit ? 2 : 0);       // stop wins on the last free slot
+        if (reason) {
+            finished[b] = reason;
+            if (n_finished) atomicAdd(n_finished, 1);
+        }
+        if (j >= 0 && matched) matched[b] = which;
+    }
+}
+
 }  // namespace
 }  // namespace asd
 
@@ -163,6 +268,23 @@ ASD_EXPORT int asd_commit_step_stop(const int32_t* tok, const float* lp_tok, con
     if (ld_out < max_len) return ASD_ERR_INVALID_ARG;
     hipLaunchKernelGGL(k_commit_step_stop, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, lp_tok, n_acc, drawn,
                        lp_drawn, B, K, stop_ids, n_stop, seq_len, out_tokens, out_lp, ld_out, n_commit, finished, n_finished, max_len);
+    return launch_status();
+}
+
+ASD_EXPORT int asd_commit_step_finish(const int32_t* tok, const float* lp_tok, const int32_t* n_acc, const int32_t* drawn,
+                                      const float* lp_drawn, int B, int K, const int32_t* seq_tok, const int32_t* seq_n, int n_seq,
+                                      const int32_t* row_first, const int32_t* row_max_len, int32_t start, int32_t* seq_len,
+                                      int32_t* out_tokens, float* out_lp, int64_t ld_out, int32_t* n_commit, int32_t* finished,
+                                      int32_t* n_finished, int32_t* matched, int32_t max_len, void* stream) {
+    if (B < 0 || K < 0 || max_len < 0 || n_seq < 0 || start < 0) return ASD_ERR_INVALID_ARG;
+    if (B == 0) return ASD_OK;
+    if (K > ASD_MAX_DRAFT_LEN || (!row_first && n_seq > ASD_MAX_STOP_SEQS)) return ASD_ERR_UNSUPPORTED;
+    if ((K > 0 && (!tok || !lp_tok)) || !n_acc || !drawn || !lp_drawn || !seq_len || !out_tokens || !out_lp) return ASD_ERR_INVALID_ARG;
+    if (!finished || (n_seq > 0 && (!seq_tok || !seq_n))) return ASD_ERR_INVALID_ARG;
+    if (ld_out < max_len) return ASD_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_commit_step_finish, dim3(B), dim3(64), 0, static_cast<hipStream_t>(stream), tok, lp_tok, n_acc, drawn,
+                       lp_drawn, B, K, seq_tok, seq_n, n_seq, row_first, row_max_len, start, seq_len, out_tokens, out_lp, ld_out,
+                       n_commit, finished, n_finished, matched, max_len);
     return launch_status();
 }
 

@@ -388,6 +388,16 @@ class HipOps:
         self.K.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, finished, stop_ids=stop_ids,
                                 n_finished=n_finished, n_commit=n_commit, max_len=max_len)
 
+    @traced("commit_step_finish")
+    def commit_step_finish(self, tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, max_len, start, seq_tok, seq_n,
+                           row_first, row_max_len, finished, n_finished, matched):
+        """commit_step_stop with multi-token stop sequences, per-row lists and per-row limits (asd_commit_step_finish): seq_tok
+        i32 [n, 8] / seq_n i32 [n] / row_first i32 [B+1] (kernels.pack_stop_sequences; None where a call has no sequences),
+        row_max_len i32 [B] or None, start = the prompt length, matched i32 [B]: which of its sequences ended a row."""
+        self.K.commit_step_finish(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, finished, start, seq_tok=seq_tok,
+                                  seq_n=seq_n, row_first=row_first, row_max_len=row_max_len, n_finished=n_finished,
+                                  matched=matched, n_commit=n_commit, max_len=max_len)
+
     @traced("lambda_sweep")
     def lambda_sweep(self, p_hist, costs, lams):
         """N4: the DP rule for every (lambda, sequence) pair in one launch -> k_star [G, n] i32."""

@@ -477,6 +477,86 @@ def commit_step_stop(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor]
     B.check("asd_commit_step_stop", rc)
 
 
+def pack_stop_sequences(rows, device, shared: bool = False):
+    """The stop-sequence tables of commit_step_finish from host lists, checked BEFORE anything is uploaded.
+    shared=False: `rows` holds one list of sequences per batch row (each sequence 1..8 token ids, at most 16 per row, a row's
+    list may be empty) -> (seq_tok i32 [n, 8], seq_n i32 [n], row_first i32 [B+1]) on `device`.  shared=True: `rows` is ONE such
+    list, owned by every row -> (seq_tok, seq_n, None)."""
+    lists = [list(rows)] if shared else [list(r) for r in rows]
+    flat, first = [], [0]
+    for r, seqs in enumerate(lists):
+        if len(seqs) > B.MAX_STOP_SEQS:
+            raise ValueError(f"row {r} owns {len(seqs)} stop sequences, at most {B.MAX_STOP_SEQS}")
+        for s in seqs:
+            s = [int(t) for t in s]
+            if not 1 <= len(s) <= B.MAX_STOP_SEQ_LEN:
+                raise ValueError(f"a stop sequence holds 1..{B.MAX_STOP_SEQ_LEN} token ids, got {len(s)}")
+            if any(not -2 ** 31 <= t < 2 ** 31 for t in s):
+                raise ValueError("stop sequence token ids must fit int32")
+            flat.append(s)
+        first.append(len(flat))
+    tok = torch.zeros((len(flat), B.MAX_STOP_SEQ_LEN), dtype=torch.int32)
+    for i, s in enumerate(flat):
+        tok[i, :len(s)] = torch.tensor(s, dtype=torch.int32)
+    n = torch.tensor([len(s) for s in flat], dtype=torch.int32)
+    return tok.to(device), n.to(device), None if shared else torch.tensor(first, dtype=torch.int32).to(device)
+
+
+def commit_step_finish(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor], n_acc: torch.Tensor, drawn: torch.Tensor,
+                       lp_drawn: torch.Tensor, seq_len: torch.Tensor, out_tokens: torch.Tensor, out_lp: torch.Tensor,
+                       finished: torch.Tensor, start: int, seq_tok: Optional[torch.Tensor] = None,
+                       seq_n: Optional[torch.Tensor] = None, row_first: Optional[torch.Tensor] = None,
+                       row_max_len: Optional[torch.Tensor] = None, n_finished: Optional[torch.Tensor] = None,
+                       matched: Optional[torch.Tensor] = None, n_commit: Optional[torch.Tensor] = None,
+                       max_len: Optional[int] = None) -> None:
+    """commit_step_stop with multi-token stop sequences, per-row lists and per-row limits (asd_commit_step_finish): the append
+    is cut behind the first committed token at which a sequence the row owns ENDS (the match may begin in earlier steps' tokens,
+    never in front of position `start`, the prompt length) or at min(max_len, row_max_len[b]).  seq_tok i32 [n, 8] / seq_n i32
+    [n] / row_first i32 [B+1] or None (every row owns all n <= 16): the tables of pack_stop_sequences, which checks that no row
+    owns more than 16 on the host lists.  row_max_len i32 [B] or None.  finished / n_finished: as commit_step_stop.  matched
+    i32 [B] in/out or None: the index, within the row's list, of the sequence that ended it."""
+    Bv = drawn.shape[0]
+    K = 0 if tok is None else tok.shape[1]
+    if tok is not None and (tok.shape[0] != Bv or lp_tok is None or lp_tok.shape != tok.shape):
+        raise ValueError("tok and lp_tok must both be [B, K]")
+    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
+        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
+    if out_lp.shape != out_tokens.shape or out_lp.stride() != out_tokens.stride():
+        raise ValueError("out_lp must have the shape and strides of out_tokens")
+    if finished.shape != (Bv,):
+        raise ValueError("finished must be [B] int32")
+    if (seq_tok is None) != (seq_n is None):
+        raise ValueError("seq_tok and seq_n come together")
+    n_seq = 0 if seq_tok is None else seq_tok.shape[0]
+    if seq_tok is not None and (seq_tok.dim() != 2 or seq_tok.shape[1] != B.MAX_STOP_SEQ_LEN or seq_n.shape != (n_seq,)):
+        raise ValueError(f"seq_tok must be [n, {B.MAX_STOP_SEQ_LEN}] int32 and seq_n [n] int32")
+    if row_first is not None and row_first.shape != (Bv + 1,):
+        raise ValueError("row_first must be [B + 1] int32")
+    if row_first is None and n_seq > B.MAX_STOP_SEQS:
+        raise ValueError(f"at most {B.MAX_STOP_SEQS} stop sequences per row")
+    if row_max_len is not None and row_max_len.shape != (Bv,):
+        raise ValueError("row_max_len must be [B] int32")
+    if n_finished is not None and n_finished.numel() != 1:
+        raise ValueError("n_finished must hold one int32")
+    if matched is not None and matched.shape != (Bv,):
+        raise ValueError("matched must be [B] int32")
+    if int(start) < 0:
+        raise ValueError("start must be >= 0")
+    cap = out_tokens.shape[1] if max_len is None else int(max_len)
+    rc = _lib().asd_commit_step_finish(_opt(tok, "tok", torch.int32), _opt(lp_tok, "lp_tok", torch.float32),
+                                       _dev(n_acc, "n_acc", torch.int32), _dev(drawn, "drawn", torch.int32),
+                                       _dev(lp_drawn, "lp_drawn", torch.float32), Bv, K,
+                                       _opt(seq_tok, "seq_tok", torch.int32) if n_seq else None,
+                                       _opt(seq_n, "seq_n", torch.int32) if n_seq else None, n_seq,
+                                       _opt(row_first, "row_first", torch.int32), _opt(row_max_len, "row_max_len", torch.int32),
+                                       int(start), _dev(seq_len, "seq_len", torch.int32),
+                                       _dev(out_tokens, "out_tokens", torch.int32), _dev(out_lp, "out_lp", torch.float32),
+                                       out_tokens.stride(0), _opt(n_commit, "n_commit", torch.int32),
+                                       _dev(finished, "finished", torch.int32), _opt(n_finished, "n_finished", torch.int32),
+                                       _opt(matched, "matched", torch.int32), cap, _stream())
+    B.check("asd_commit_step_finish", rc)
+
+
 # ------------------------------------------------------------------------------- predictor side
 def logprob_stats(lp: torch.Tensor, n_valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A7: [B,K] f32 log-probs -> [B,5] f64 (mean, std, min, q25, median), numpy semantics."""

@@ -1,7 +1,8 @@
 """Adaptive cascade pipeline -- API of the reference's src/serving/pipeline.py, with the decision
 arithmetic of the stage loop (Bayes adjustment, DP stop rule) done by batched kernels.
 
-    PipelineConfig                  pipeline.py:22-31   (+ stop_rule, stage_names, stop_token_ids, logprobs: build extensions)
+    PipelineConfig                  pipeline.py:22-31   (+ stop_rule, stage_names, stop_token_ids, stop_sequences, logprobs: build
+                                                         extensions)
     RequestResult                   pipeline.py:34-45
     AdaptiveSpeculativePipeline     pipeline.py:48-423
         process_request / process_request_async / batch_process / update_lambda / get_stats /
@@ -12,6 +13,12 @@ take ints in [0, 2^64) (serving/stages.py, SEEDS; a batch passes a seed for ever
 with it through every regrouping -- the `predicted_stage` groups, the cache split, the requests that leave the cascade -- and
 reaches every stage as `stage.generate(seed=[...])`, so its draws do not depend on the requests it happens to be batched with.
 Without seeds the keyword is not passed.
+
+Per-request length limits (the reference's GenerationRequest.max_tokens, src/serving/server.py:43): `batch_process(max_tokens=)`
+takes an int or one int >= 1 per request.  A request keeps its own limit (`_Active.max_tokens`) through the same regroupings and
+every stage sees `stage.generate(max_tokens=[...])` with the values of that call's rows; with an int the stage sees the int, as
+before.  `PipelineConfig.stop_sequences` (also read from the YAML `pipeline:` section) is handed to every stage.generate call as
+`stop_sequences=`, only when set (serving/stages.py, HOW A ROW ENDS).
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -54,7 +61,7 @@ import numpy as np
 
 from ..backend import get_backend
 from .cache import RequestCache
-from .stages import check_seeds
+from .stages import check_max_tokens, check_seeds
 
 logger = logging.getLogger(__name__)
 
@@ -80,6 +87,8 @@ class PipelineConfig:
     # stage.generate(logprobs=); the predictor then receives the [n_tokens, N] table as `draft_logprobs` (what
     # FeatureExtractor.extract is written for) in place of the 1-D vector.  None: the keyword is not passed
     logprobs: Optional[int] = None
+    # stop strings / token-id sequences handed to stage.generate(stop_sequences=); None: the keyword is not passed
+    stop_sequences: Optional[Sequence] = None
 
     @classmethod
     def from_yaml(cls, path: str) -> "PipelineConfig":
@@ -109,6 +118,8 @@ class PipelineConfig:
             kw["stop_token_ids"] = tuple(int(x) for x in sec["stop_token_ids"])
         if sec.get("logprobs") is not None:
             kw["logprobs"] = int(sec["logprobs"])
+        if sec.get("stop_sequences") is not None:
+            kw["stop_sequences"] = tuple(e if isinstance(e, str) else tuple(int(t) for t in e) for e in sec["stop_sequences"])
         return cls(**kw)
 
 
@@ -144,6 +155,7 @@ class _Active:
     k_star: int = -1
     predicted_stage: int = -1
     seed: Optional[int] = None                              # the request's sampling seed (None: the stage's own generator)
+    max_tokens: Optional[int] = None                        # the request's own length limit (None: the batch's one int)
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -186,19 +198,23 @@ class AdaptiveSpeculativePipeline:
         return await loop.run_in_executor(self.executor, self.process_request, prompt, max_tokens, temperature,
                                           request_id, seed)
 
-    def batch_process(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7,
+    def batch_process(self, prompts: List[str], max_tokens=512, temperature: float = 0.7,
                       seeds=None) -> List[RequestResult]:
         """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
-        raises ValueError); request i keeps seeds[i] through every regrouping (module docstring)."""
+        raises ValueError); request i keeps seeds[i] through every regrouping (module docstring).  max_tokens: an int, or one
+        int >= 1 per request, kept by the request in the same way."""
         prompts = list(prompts)
         seeds = check_seeds(seeds, len(prompts))
+        max_tokens = check_max_tokens(max_tokens, len(prompts))
         if self.config.batch_grouping != "predicted_stage" or len(prompts) < 2 or self.config.stop_rule == "prefix":
             return self._run_batch(prompts, max_tokens, temperature, [None] * len(prompts), seeds=seeds)
         pred = self.predict_stop_stages(prompts)
         results: List[Optional[RequestResult]] = [None] * len(prompts)
         for stage in sorted(set(pred.tolist())):                       # shallowest group first
             idx = [i for i, s in enumerate(pred) if s == stage]
-            out = self._run_batch([prompts[i] for i in idx], max_tokens, temperature, [None] * len(idx),
+            out = self._run_batch([prompts[i] for i in idx],
+                                  [max_tokens[i] for i in idx] if isinstance(max_tokens, list) else max_tokens, temperature,
+                                  [None] * len(idx),
                                   predicted=[int(stage)] * len(idx), seeds=None if seeds is None else [seeds[i] for i in idx])
             for i, r in zip(idx, out):
                 results[i] = r
@@ -282,7 +298,7 @@ class AdaptiveSpeculativePipeline:
         logger.info("Pipeline shutdown completed")
 
     # ------------------------------------------------------------------ the stage loop, batched
-    def _run_batch(self, prompts: List[str], max_tokens: int, temperature: float,
+    def _run_batch(self, prompts: List[str], max_tokens, temperature: float,
                    request_ids: List[Optional[str]], predicted: Optional[List[int]] = None,
                    seeds: Optional[List[int]] = None) -> List[RequestResult]:
         now = time.time()
@@ -294,6 +310,9 @@ class AdaptiveSpeculativePipeline:
         if seeds is not None:
             for r, s in zip(reqs, seeds):
                 r.seed = s
+        if isinstance(max_tokens, list):
+            for r, n in zip(reqs, max_tokens):
+                r.max_tokens = n
         for r in reqs:
             self.active_requests[r.request_id] = {"start_time": r.start_time,
                                                   "prompt": r.prompt[:100] + "..." if len(r.prompt) > 100 else r.prompt}
@@ -318,7 +337,7 @@ class AdaptiveSpeculativePipeline:
         return float(self.predictor.predict(prompt=r.current_prompt, draft_output=output, draft_logprobs=logprobs,
                                             stage_id=stage_idx, feature_extractor=self.feature_extractor))
 
-    def _process_stages(self, reqs: List[_Active], max_tokens: int, temperature: float) -> None:
+    def _process_stages(self, reqs: List[_Active], max_tokens, temperature: float) -> None:
         cfg = self.config
         names = list(cfg.stage_names)
         L = len(names)
@@ -346,8 +365,12 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["logprobs"] = int(cfg.logprobs)
                 if todo[0].seed is not None:                            # (a batch carries seeds for all of its requests or for none)
                     stop_kw["seed"] = [r.seed for r in todo]
+                if cfg.stop_sequences is not None:
+                    stop_kw["stop_sequences"] = list(cfg.stop_sequences)
+                # (limits likewise: one per request of the batch, or the batch's one int)
+                limit = [r.max_tokens for r in todo] if isinstance(max_tokens, list) else max_tokens
                 texts, logprobs, stage_stats = stage.generate(prompts=[r.current_prompt for r in todo],
-                                                              max_tokens=max_tokens, temperature=temperature,
+                                                              max_tokens=limit, temperature=temperature,
                                                               return_logprobs=True, **stop_kw)
                 tables = (stage_stats or {}).get("top_logprobs") if cfg.logprobs else None
                 for j, r in enumerate(todo):

@@ -29,6 +29,20 @@ wasted -- compacting the batch is not done here.  texts[i] / logprobs[i] then ho
 says why each sequence ended.  Without a stop set a stage runs the asd_commit_step_lp path and every sequence returns exactly
 `max_tokens` tokens and log-probs.
 
+HOW A ROW ENDS (per request).  `generate(max_tokens=[...])` gives every prompt its own limit (buffers are sized by the largest),
+`generate(stop_sequences=[...])` / `StageConfig.stop_sequences` adds stop strings or token-id sequences of 1..8 ids for every
+prompt, and `generate(stop_sequences_per_prompt=[[...], ...])` adds a list for each prompt alone.  A string is encoded by the
+stage's tokenizer and folded into the vocabulary like a prompt.  A row's list is its stop ids (as length-1 sequences), then the
+common sequences, then its own: at most 16 distinct entries.  With unequal limits or any sequence, both loops commit through
+asd_commit_step_finish in place of asd_commit_step_stop: a step commits up to draft_len + 1 tokens, so a sequence may end inside
+the accepted prefix, on the drawn token, or begin in tokens an earlier step committed; the kernel matches over the row's
+committed stream and the step's committed candidates only -- never a rejected draft token, never a prompt token, never a token
+the row's limit cuts off -- and keeps the matched tokens, with their log-probs.  The loop ends on the same one-counter read.
+stats["stop_matches"][i] names the sequence that ended row i ((id,) for a stop id, None for "length"), so a caller can trim it.
+With one limit and no sequence a stage makes exactly the calls described above.  Not built: `min_new_tokens` (the stop ids would
+have to be masked out of the draft, verify and commit DISTRIBUTIONS, not out of the commit), removing finished rows from the
+batch, and serving/hierarchy.py's loop.  Bad values raise ValueError before any launch.
+
 GREEDY DECODING.  `temperature == 0.0` (the reference's server and core types allow it; it is the setting of reproducible
 evaluation runs) selects arg-max decoding on ops.verify_greedy (asd_verify_greedy): stage 0 makes one K = 0 call per step, a
 verifying stage drafts with K = 0 calls on the draft's logits and makes ONE call on the target's [B, K+1, V] output, in place.
@@ -89,6 +103,7 @@ import numpy as np
 import torch
 
 from ..distributed import HipOps
+from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -125,9 +140,12 @@ class StageConfig:
     sync_every: int = 4
     stop_token_ids: Sequence[int] = ()       # EOS ids: a sequence ends behind the first committed one (module docstring)
     logprobs: int = 0                        # top-N log-probs per committed token, 0..8 (0: off; module docstring)
+    stop_sequences: Sequence = ()            # stop strings / token-id sequences of every prompt (module docstring, HOW A ROW ENDS)
 
 
 MAX_STOP_IDS = 8                             # ASD_MAX_STOP_IDS of include/asd_hip.h
+MAX_STOP_SEQS = 16                           # ASD_MAX_STOP_SEQS: entries of one row's list (stop ids included)
+MAX_STOP_SEQ_LEN = 8                         # ASD_MAX_STOP_SEQ_LEN
 MAX_TOP_LOGPROBS = 8                         # ASD_MAX_TOP_LOGPROBS
 _REASONS = {1: "stop", 2: "length"}
 
@@ -141,6 +159,45 @@ def _check_stop_ids(ids: Sequence[int], vocab: int) -> Tuple[int, ...]:
     if any(not 0 <= i < vocab for i in ids):
         raise ValueError(f"stop token ids must lie in [0, {vocab})")
     return ids
+
+
+def check_max_tokens(max_tokens, n: int):
+    """generate's `max_tokens`: an int (returned as it is), or a sequence of n ints >= 1 -> a list of n ints."""
+    if isinstance(max_tokens, (int, np.integer)) and not isinstance(max_tokens, bool):
+        return int(max_tokens)
+    if isinstance(max_tokens, (str, bytes)) or not isinstance(max_tokens, (Sequence, np.ndarray)):
+        raise ValueError(f"max_tokens must be an integer or one integer per prompt, got {max_tokens!r}")
+    limits = list(max_tokens)
+    if len(limits) != n:
+        raise ValueError(f"{len(limits)} max_tokens values for {n} prompts")
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in limits):
+        raise ValueError(f"every per-prompt max_tokens must be an integer >= 1, got {max_tokens!r}")
+    return [int(v) for v in limits]
+
+
+def _check_stop_sequences(entries, vocab: int, tokenizer) -> List[Tuple[int, ...]]:
+    """One list of stop sequences: each entry a str (encoded by the stage's tokenizer, ids folded into the vocabulary as
+    encode_prompts folds prompt ids) or a sequence of token ids; every entry must come to 1..8 ids in [0, vocab)."""
+    if entries is None:
+        return []
+    if isinstance(entries, (str, bytes)) or not isinstance(entries, (Sequence, np.ndarray)):
+        raise ValueError(f"stop sequences must be a list of strings or token-id sequences, got {entries!r}")
+    out = []
+    for e in entries:
+        if isinstance(e, str):
+            ids = [int(i) % vocab for i in tokenizer.encode(e, return_tensors=None)]
+        elif isinstance(e, bytes) or not isinstance(e, (Sequence, np.ndarray)):
+            raise ValueError(f"a stop sequence is a string or a sequence of token ids, got {e!r}")
+        else:
+            if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in e):
+                raise ValueError(f"stop sequence token ids must be integers, got {e!r}")
+            ids = [int(t) for t in e]
+            if any(not 0 <= t < vocab for t in ids):
+                raise ValueError(f"stop sequence token ids must lie in [0, {vocab})")
+        if not 1 <= len(ids) <= MAX_STOP_SEQ_LEN:
+            raise ValueError(f"a stop sequence must come to 1..{MAX_STOP_SEQ_LEN} token ids, {e!r} gives {len(ids)}")
+        out.append(tuple(ids))
+    return out
 
 
 def _check_logprobs(n) -> int:
@@ -191,6 +248,30 @@ class _StopState:
         self.stop_ids = torch.tensor(list(stop_ids), dtype=torch.int32, device=device)
         self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
         self.n_finished = torch.zeros((1,), dtype=torch.int32, device=device)
+
+    def all_finished(self) -> bool:
+        return int(self.n_finished.item()) == self.B         # the loop's one host read
+
+
+class _FinishState:
+    """What a generate call on the asd_commit_step_finish route keeps beside seq_len: every row's list of stop sequences (the
+    stop ids as length-1 sequences first) and its own length limit on the device, uploaded once, with the finished flag, the
+    counter and the index of the sequence that ended each row."""
+
+    def __init__(self, row_seqs: List[List[Tuple[int, ...]]], limits: Sequence[int], P: int, device):
+        B = self.B = len(row_seqs)
+        self.rows = row_seqs
+        self.start = int(P)
+        self.seq_tok = self.seq_n = self.row_first = None
+        if any(row_seqs):
+            shared = all(r == row_seqs[0] for r in row_seqs)             # one list for every row: no row_first
+            self.seq_tok, self.seq_n, self.row_first = pack_stop_sequences(row_seqs[0] if shared else row_seqs, device, shared)
+        self.row_max_len = None
+        if len(set(limits)) > 1:
+            self.row_max_len = torch.tensor([P + int(n) for n in limits], dtype=torch.int32, device=device)
+        self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.n_finished = torch.zeros((1,), dtype=torch.int32, device=device)
+        self.matched = torch.full((B,), -1, dtype=torch.int32, device=device)
 
     def all_finished(self) -> bool:
         return int(self.n_finished.item()) == self.B         # the loop's one host read
@@ -284,11 +365,12 @@ class Stage:
 
     # ------------------------------------------------------------------------------------------ generate
     @torch.no_grad()
-    def generate(self, prompts: List[str], max_tokens: int = 512, temperature: float = 0.7, return_logprobs: bool = True,
+    def generate(self, prompts: List[str], max_tokens=512, temperature: float = 0.7, return_logprobs: bool = True,
                  top_p: Optional[float] = None, stop_token_ids: Optional[Sequence[int]] = None,
                  logprobs: Optional[int] = None,
                  min_p: Optional[float] = None,
-                 seed=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 seed=None, stop_sequences=None,
+                 stop_sequences_per_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -309,7 +391,14 @@ class Stage:
         ops.step_uniforms call per step and no torch.rand.  The same call repeated, and a permuted batch of equal-length prompts
         with the seeds permuted alike, return bit-equal texts and log-probs; another batch size may not (left-padding and the
         model kernels' tilings change the logits).  Greedy decoding ignores it.  Anything else raises ValueError (module
-        docstring, SEEDS)."""
+        docstring, SEEDS).
+        `max_tokens`: an int, or one int >= 1 per prompt (row i then returns at most max_tokens[i] tokens).  `stop_sequences`:
+        None = StageConfig.stop_sequences; strings or sequences of 1..8 token ids that end EVERY prompt's row;
+        `stop_sequences_per_prompt`: len(prompts) such lists (possibly empty), each for its own row.  A row ends behind the first
+        committed token at which one of its sequences is complete in the GENERATED tokens; the matched tokens are kept.
+        stats["stop_matches"][i] is the tuple of token ids that ended row i ((id,) for a stop id), or None for "length".
+        A row's list -- stop ids, common sequences, its own -- holds at most 16 distinct entries (module docstring, HOW A ROW
+        ENDS)."""
         t0 = time.perf_counter()
         prompts = list(prompts)
         self.step_inputs = []
@@ -318,6 +407,24 @@ class Stage:
         own_min_p = self.config.min_p if self.draft is None else self.config.target_min_p
         min_p = _check_min_p(own_min_p if min_p is None else min_p)
         seeds = check_seeds(seed, len(prompts))
+        max_tokens = check_max_tokens(max_tokens, len(prompts))
+        common = _check_stop_sequences(self.config.stop_sequences if stop_sequences is None else stop_sequences,
+                                       self.shape.vocab, self.tokenizer)
+        own = [[] for _ in prompts]
+        if stop_sequences_per_prompt is not None:
+            if isinstance(stop_sequences_per_prompt, (str, bytes)) or len(stop_sequences_per_prompt) != len(prompts):
+                raise ValueError(f"stop_sequences_per_prompt must hold one list per prompt ({len(prompts)})")
+            own = [_check_stop_sequences(e, self.shape.vocab, self.tokenizer) for e in stop_sequences_per_prompt]
+        row_seqs = [[(i,) for i in stop] + common + o for o in own]
+        for r in row_seqs:
+            if len(r) > MAX_STOP_SEQS:
+                raise ValueError(f"a prompt's stop list (stop ids included) holds at most {MAX_STOP_SEQS} entries, got {len(r)}")
+            if len(set(r)) != len(r):
+                raise ValueError("the stop sequences of a prompt must be distinct")
+        limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * len(prompts)
+        # the asd_commit_step_finish route: only for what the stop-id route cannot do (module docstring, HOW A ROW ENDS)
+        finish_route = len(set(limits)) > 1 or bool(common) or any(own)
+        max_tokens = max(limits, default=0)
         if not prompts or max_tokens <= 0:
             return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -325,7 +432,10 @@ class Stage:
             raise ValueError("temperature must be >= 0 (0: greedy decoding)")
         ids = self.encode_prompts(prompts)
         B, P = ids.shape
-        end = _StopState(stop, B, ids.device) if stop else None
+        if finish_route:
+            end = _FinishState(row_seqs, limits, P, ids.device)
+        else:
+            end = _StopState(stop, B, ids.device) if stop else None
         inv_t = 1.0 if temperature == 0.0 else float(np.float32(1.0 / temperature))
         top = _TopState(self.ops, n_top, inv_t, B, P + int(max_tokens), ids.device) if n_top else None
         rng = None
@@ -346,16 +456,21 @@ class Stage:
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
         if end is None:
-            n_tok, reasons = [int(max_tokens)] * B, ["length"] * B
+            n_tok, reasons, matches = [int(max_tokens)] * B, ["length"] * B, [None] * B
         else:
             n_tok = [int(n) - P for n in seq_len.cpu().tolist()]
             flags = end.finished.cpu().tolist()
-            if any(f not in _REASONS for f in flags) or any(not 1 <= n <= max_tokens for n in n_tok):
+            if any(f not in _REASONS for f in flags) or any(not 1 <= n <= lim for n, lim in zip(n_tok, limits)):
                 raise RuntimeError("stage loop ended with an unfinished sequence")
             reasons = [_REASONS[f] for f in flags]
+            if finish_route:
+                which = end.matched.cpu().tolist()
+                matches = [end.rows[b][which[b]] if f == 1 else None for b, f in enumerate(flags)]
+            else:
+                matches = [(int(tok_h[b, n_tok[b] - 1]),) if f == 1 else None for b, f in enumerate(flags)]
         texts = [self.decode_tokens(row[:n]) for row, n in zip(tok_h, n_tok)]
         stats = {"generation_time_ms": (time.perf_counter() - t0) * 1000.0, "steps": float(self.last_steps),
-                 "n_tokens": n_tok, "finish_reasons": reasons}
+                 "n_tokens": n_tok, "finish_reasons": reasons, "stop_matches": matches}
         if top is not None:
             id_h, tlp_h = top.ids[:, P:].cpu().numpy(), top.lps[:, P:].cpu().numpy()
             stats["top_token_ids"] = [np.ascontiguousarray(r[:n]) for r, n in zip(id_h, n_tok)]
@@ -387,6 +502,10 @@ class Stage:
     def _commit(self, end, tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap):
         if end is None:
             self.ops.commit_step_lp(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+        elif isinstance(end, _FinishState):
+            self.ops.commit_step_finish(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap, end.start,
+                                        end.seq_tok, end.seq_n, end.row_first, end.row_max_len, end.finished, end.n_finished,
+                                        end.matched)
         else:
             self.ops.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap, end.stop_ids,
                                       end.finished, end.n_finished)

@@ -48,6 +48,8 @@ typedef enum asd_dtype {
 /* limits enforced by the launchers */
 #define ASD_MAX_DRAFT_LEN 64   /* K: one ballot word per sequence */
 #define ASD_MAX_STOP_IDS 8     /* stop (EOS) token ids of asd_commit_step_stop */
+#define ASD_MAX_STOP_SEQS 16   /* stop sequences one row may own in asd_commit_step_finish */
+#define ASD_MAX_STOP_SEQ_LEN 8 /* tokens per stop sequence of asd_commit_step_finish */
 #define ASD_MAX_TOP_LOGPROBS 8 /* N of asd_top_logprobs: the most likely tokens listed per row */
 #define ASD_MAX_STAGES 16      /* L: tiers in the DP rule */
 #define ASD_MAX_SPLITS 64      /* vocab splits per row inside one launch */
@@ -330,6 +332,43 @@ int asd_commit_step_stop(const int32_t* tok /*[B,K]*/, const float* lp_tok /*[B,
                          int32_t* out_tokens /*[B][ld_out]*/, float* out_lp /*[B][ld_out]*/, int64_t ld_out,
                          int32_t* n_commit /*[B] out, may be NULL*/, int32_t* finished /*[B] in/out: 0, 1 stop, 2 length*/,
                          int32_t* n_finished /*[1] in/out, may be NULL*/, int32_t max_len, void* stream);
+/* asd_commit_step_stop with multi-token stop sequences, a list of sequences per row and a length limit per row: how a serving
+ * request ends (stop strings, the reference's per-request GenerationRequest.max_tokens, src/serving/server.py:43), decided on the
+ * device inside the step's commit.  A step commits up to K + 1 tokens, so a sequence may end in the middle of the accepted
+ * prefix, on the drawn token, or begin in tokens an earlier step committed.
+ * seq_tok [n_seq][ASD_MAX_STOP_SEQ_LEN] holds the sequences, seq_n [n_seq] their lengths; slots behind a sequence's length are
+ * ignored, a sequence whose length lies outside [1, ASD_MAX_STOP_SEQ_LEN] never matches.  Row b owns sequences
+ * row_first[b] .. row_first[b+1] - 1 (row_first [B+1], non-decreasing, inside [0, n_seq]); row_first == NULL: every row owns all
+ * n_seq.  A row owns at most ASD_MAX_STOP_SEQS sequences: the kernel IGNORES the ones behind the first ASD_MAX_STOP_SEQS of a
+ * row's list (and any part of a list that lies outside [0, n_seq)); the caller checks its lists.
+ * Row b, na = clamp(n_acc[b], 0, K), len = seq_len[b], candidates c_0..c_na = tok[b, 0..na) ++ drawn[b]:
+ *   finished[b] != 0 on entry: the row is left alone (seq_len, finished, *n_finished, matched[b] unchanged), n_commit[b] = 0.
+ *   otherwise limit = max_len when row_max_len == NULL, else min(max_len, max(row_max_len[b], 0)) (a position, prompt included,
+ *   like max_len); fit = min(na + 1, max(limit - len, 0)).  The row's stream is out_tokens[b, 0..len) followed by
+ *   c_0..c_{fit-1}.  Sequence s of length m ENDS AT candidate j < fit when stream positions len + j - m + 1 .. len + j equal
+ *   s[0..m) and len + j - m + 1 >= start (`start`: the first generated position, the prompt length -- no token of a match lies
+ *   in the prompt; positions in front of `start` are never read).  j* = the smallest j at which any owned sequence ends;
+ *   appended = j* + 1 if j* exists, else fit.  The first `appended` candidates and their log-probs go to index len.. as in
+ *   asd_commit_step_lp (bits copied), seq_len[b] = len + appended, n_commit[b] = appended: the matched tokens are committed.
+ *   A rejected draft token (index >= na, other than drawn) and anything cut off by `limit` never take part in a match.
+ *   finished[b] = 1 (stop) if j* exists -- also when it lands on the last free slot --, else 2 (length) if
+ *   len + appended >= limit, else it stays 0.  A row going 0 -> non-zero adds 1 to *n_finished (may be NULL) with a global atomic.
+ *   matched[b] (may be NULL) = the index, within the row's own list, of the first owned sequence that ends at j*; written only
+ *   when j* exists.
+ * row_first == NULL, row_max_len == NULL and every sequence of length 1: every output is asd_commit_step_stop's with those ids,
+ * byte for byte, for any start <= every seq_len.
+ * Status codes: those of asd_commit_step_stop (negative B / K / max_len / n_seq: invalid argument; B == 0: ASD_OK;
+ * K > ASD_MAX_DRAFT_LEN: unsupported; NULL operands, finished == NULL, ld_out < max_len: invalid argument); start < 0, n_seq > 0
+ * with seq_tok == NULL or seq_n == NULL: invalid argument; row_first == NULL with n_seq > ASD_MAX_STOP_SEQS: unsupported. */
+int asd_commit_step_finish(const int32_t* tok /*[B,K]*/, const float* lp_tok /*[B,K]*/, const int32_t* n_acc /*[B]*/,
+                           const int32_t* drawn /*[B]*/, const float* lp_drawn /*[B]*/, int B, int K,
+                           const int32_t* seq_tok /*[n_seq][ASD_MAX_STOP_SEQ_LEN]*/, const int32_t* seq_n /*[n_seq]*/, int n_seq,
+                           const int32_t* row_first /*[B+1] or NULL*/, const int32_t* row_max_len /*[B] or NULL*/,
+                           int32_t start /*first generated position*/, int32_t* seq_len /*[B] in/out*/,
+                           int32_t* out_tokens /*[B][ld_out]*/, float* out_lp /*[B][ld_out]*/, int64_t ld_out,
+                           int32_t* n_commit /*[B] out, may be NULL*/, int32_t* finished /*[B] in/out: 0, 1 stop, 2 length*/,
+                           int32_t* n_finished /*[1] in/out, may be NULL*/, int32_t* matched /*[B] in/out, may be NULL*/,
+                           int32_t max_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Greedy decoding (temperature 0): arg-max verify and commit token in one launch, no random numbers.

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs and asd_step_uniforms in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs and asd_step_uniforms in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -87,6 +87,33 @@ int main() {
     EXPECT(STOP(i32, f32, i32, i32, f32, B, K, i32, ASD_MAX_STOP_IDS + 1, i32, i32, f32, ld, i32, 32), ASD_ERR_UNSUPPORTED);
     EXPECT(STOP(i32, f32, i32, i32, f32, -1, K, nullptr, 0, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);             // no stop set: B is still checked
 #undef STOP
+    // ---- asd_commit_step_finish (the checks of asd_commit_step_stop, plus the sequence tables, the row lists and `start`)
+#define FINISH(tok_, lp_tok_, n_acc_, drawn_, lp_drawn_, B_, K_, seq_tok_, seq_n_, n_seq_, first_, start_, seq_, out_, out_lp_, ld_, fin_, max_len_) \
+    asd_commit_step_finish(tok_, lp_tok_, n_acc_, drawn_, lp_drawn_, B_, K_, seq_tok_, seq_n_, n_seq_, first_, i32, start_, seq_, out_, out_lp_, ld_, i32, fin_, i32, i32, max_len_, nullptr)
+    EXPECT(FINISH(i32, f32, i32, i32, f32, -1, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, -1, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, -1), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, -1, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);               // n_seq < 0
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, 2, i32, -1, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);               // start < 0
+    EXPECT(FINISH(i32, f32, i32, i32, f32, 0, K, i32, i32, 2, i32, -1, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);               // ... before the empty batch
+    EXPECT(FINISH(nullptr, nullptr, nullptr, nullptr, nullptr, 0, K, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, ld, nullptr, 32), ASD_OK);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, ASD_MAX_DRAFT_LEN + 1, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_UNSUPPORTED);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, ASD_MAX_STOP_SEQS + 1, nullptr, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_UNSUPPORTED);   // no row lists: all of them are every row's
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, ASD_MAX_STOP_SEQS + 1, i32, 4, i32, i32, f32, ld, nullptr, 32), ASD_ERR_INVALID_ARG);   // with row lists the total is free: on to the pointers
+    EXPECT(FINISH(nullptr, f32, i32, i32, f32, B, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, nullptr, i32, i32, f32, B, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, nullptr, i32, f32, B, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, nullptr, f32, B, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, nullptr, B, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, nullptr, i32, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);            // seq_tok missing
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, nullptr, 2, i32, 4, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);            // seq_n missing
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, 2, i32, 4, nullptr, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, 2, i32, 4, i32, nullptr, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, 2, i32, 4, i32, i32, nullptr, ld, i32, 32), ASD_ERR_INVALID_ARG);
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, 2, i32, 4, i32, i32, f32, 31, i32, 32), ASD_ERR_INVALID_ARG);                // ld_out < max_len
+    EXPECT(FINISH(i32, f32, i32, i32, f32, B, K, i32, i32, 2, i32, 4, i32, i32, f32, ld, nullptr, 32), ASD_ERR_INVALID_ARG);            // finished
+    EXPECT(FINISH(i32, f32, i32, i32, f32, -1, K, nullptr, nullptr, 0, nullptr, 0, i32, i32, f32, ld, i32, 32), ASD_ERR_INVALID_ARG);   // no sequences: B is still checked
+#undef FINISH
     // the same rejections from the entry point it extends
     EXPECT(asd_commit_step(i32, i32, i32, B, ASD_MAX_DRAFT_LEN + 1, i32, i32, ld, i32, 32, nullptr), ASD_ERR_UNSUPPORTED);
     EXPECT(asd_commit_step(i32, i32, i32, B, K, i32, i32, 31, i32, 32, nullptr), ASD_ERR_INVALID_ARG);

@@ -43,10 +43,10 @@ def interleaved(fns, reps, rounds=11):
 
 def bench_lp(a, dev):
     """asd_residual_sample_lp beside asd_residual_sample_ex (B = 32: group form, B = 128: one workgroup per sequence; V = 152064,
-    bf16) and asd_commit_step_lp / asd_commit_step_stop beside asd_commit_step (B = 32, K = 8)."""
+    bf16) and asd_commit_step_lp / asd_commit_step_stop / asd_commit_step_finish beside asd_commit_step (B = 32, K = 8)."""
     V, Kd = 152064, 8
     res = {}
-    for B in (32, 128):
+    for B in (() if a.commit_only else (32, 128)):
         g = torch.Generator(device=dev).manual_seed(B)
         rows = [(torch.randn((B, V), generator=g, device=dev) * a.scale).to(torch.bfloat16) for _ in range(4)]
         t3 = torch.stack([rows[j % 4] for j in range(Kd)], 1).contiguous()
@@ -93,10 +93,23 @@ def bench_lp(a, dev):
         K.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, out_tok, out_lp, finished, stop_ids=stop_ids,
                            n_finished=n_finished, n_commit=nc)
 
+    # asd_commit_step_finish on the same inputs with 8 two-token sequences, owned by every row, that no input hits (their tokens
+    # are absent from the inputs); its own flag and counter, so that neither kernel sees a row the other finished
+    absent = [i for i in range(V - 3, 0, -1) if i not in present][:16]
+    seq_tok, seq_n, _ = K.pack_stop_sequences([absent[2 * i:2 * i + 2] for i in range(8)], dev, shared=True)
+    finished2 = torch.zeros((B,), dtype=torch.int32, device=dev)
+    n_finished2 = torch.zeros((1,), dtype=torch.int32, device=dev)
+    matched = torch.full((B,), -1, dtype=torch.int32, device=dev)
+
+    def commit_finish():
+        seq_len.zero_()
+        K.commit_step_finish(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, out_tok, out_lp, finished2, 0, seq_tok=seq_tok,
+                             seq_n=seq_n, n_finished=n_finished2, matched=matched, n_commit=nc)
+
     res["commit_B32_K8"] = interleaved({"asd_commit_step": commit, "asd_commit_step_lp": commit_lp,
-                                        "asd_commit_step_stop": commit_stop}, a.reps)
-    if int(n_finished.item()) != 0:
-        raise RuntimeError("a row finished during the timing: the three candidates did not do the same work")
+                                        "asd_commit_step_stop": commit_stop, "asd_commit_step_finish": commit_finish}, a.reps)
+    if int(n_finished.item()) != 0 or int(n_finished2.item()) != 0:
+        raise RuntimeError("a row finished during the timing: the candidates did not do the same work")
     print("commit", res["commit_B32_K8"], flush=True)
     return res
 
@@ -108,7 +121,8 @@ def main():
     ap.add_argument("--batches", default="8,32,128")
     ap.add_argument("--scale", type=float, default=3.0, help="logits = scale * N(0,1): 3 = a wide nucleus (hundreds of tokens at "
                     "T = 0.7, top-p 0.9), 8 = a peaked row (a handful of tokens), closer to a confident LLM step")
-    ap.add_argument("--lp", action="store_true", help="time asd_residual_sample_lp / asd_commit_step_lp / asd_commit_step_stop beside their parents, interleaved")
+    ap.add_argument("--lp", action="store_true", help="time asd_residual_sample_lp / asd_commit_step_lp / asd_commit_step_stop / asd_commit_step_finish beside their parents, interleaved")
+    ap.add_argument("--commit-only", action="store_true", help="with --lp: the commit kernels only")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     if a.lp:
