@@ -23,6 +23,7 @@ MAX_SPLITS = 64
 MAX_TOP_LOGPROBS = 8
 MAX_STOP_SEQS, MAX_STOP_SEQ_LEN = 16, 8
 MAX_MLP_DIM = 1024
+SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
 WS_LOST_HANDOFF = 0x1
 
@@ -67,6 +68,12 @@ SIGNATURES = {
                                      _vp, _sz, _vp]),
     "asd_residual_sample_lp_min_p": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _f, _i, _f, _f, _vp, _vp,
                                           _vp, _vp, _vp, _sz, _vp]),
+    "asd_sampling_rows_bytes": (_sz, [_i]),
+    "asd_sampling_rows_pack": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "asd_draft_sample_rows": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "asd_verify_accept_rows": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "asd_residual_sample_lp_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _sz, _vp]),
     "asd_lse_partial": (_i, [_vp, _i, _i64, _vp, _i, _i, _i, _i64, _f, _vp, _vp, _sz, _vp]),
     "asd_accept_from_partials": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "asd_lm_head_verify_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -95,6 +102,7 @@ SIGNATURES = {
     "asd_verify_greedy": (_i, [_vp, _i, _i64, _i64, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "asd_top_logprobs_workspace_bytes": (_sz, [_i, _i, _i]),
     "asd_top_logprobs": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "asd_top_logprobs_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "asd_commit_step_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i,
                                     _vp]),
     "asd_commit_top_logprobs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -96,4 +96,18 @@ inline float min_p_delta(float min_p, float inv_temperature) {
     return static_cast<float>(log(static_cast<double>(min_p)) / static_cast<double>(inv_temperature));
 }
 
+// One sequence of the packed sampling table (asd_sampling_rows_pack, include/asd_hip.h "Per-sequence sampling parameters"):
+// what a scalar launch with the sequence's (inv_temperature, top_k, top_p, min_p) puts into its parameter block, formed on
+// the host by the functions above -- so row b of a *_rows launch works on the bits a scalar launch with its values would.
+struct SamplingRow {
+    float c2;             // log2_scale(inv_temperature)
+    float top_p;          // as given (1 when the caller passed none); read by the mass select only when levels > 0
+    int32_t levels;       // truncation(...).levels
+    int32_t top_k;        // truncation(...).top_k: the bound where it bounds anything, else 0
+    float mp_delta;       // min_p_delta(min_p, inv_temperature) where min_p > 0, else -inf
+    uint32_t clamp;       // 1 where min_p > 0: the row takes the kMinP select and the "lp above 0 reads as 0" rule
+    uint32_t reserved[2];
+};
+static_assert(sizeof(SamplingRow) == ASD_SAMPLING_ROW_BYTES, "SamplingRow");
+
 }  // namespace asd

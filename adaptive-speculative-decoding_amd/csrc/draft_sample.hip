@@ -150,11 +150,12 @@ __device__ __forceinline__ void draft_pick_wave(const u32x4* row, int nvec, cons
     }
 }
 
-template <int DT, bool kTopK = false, bool kMinP = false>
-__global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
+// The body of k_draft_row and of k_draft_row_rows (one instantiation per mode, the LDS declared ONCE by the kernel: NucleusLds
+// is ~115 KB of the CU's 160 KB).  sh: phases 1-3 (sample_device.hpp, nucleus_row_select); pick: the draw's scratch.
+template <int DT, bool kTopK, bool kMinP>
+__device__ __forceinline__ void draft_row_body(const DrParams& p, NucleusLds& sh, DraftPickScratch& pick) {
     using E = Elem<DT>;
     constexpr int N = E::kPerVec;
-    __shared__ NucleusLds sh;                          // phases 1-3: sample_device.hpp, nucleus_row_select
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.logits) + static_cast<int64_t>(b) * p.ld * E::kBytes);
     float* const tile_mass = sh.tile_mass;
@@ -221,10 +222,32 @@ __global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
     if (wave != 0) return;
 
     // ---- inverse CDF by one wave
-    __shared__ DraftPickScratch pick;
     draft_pick_wave<DT, kMinP>(row, p.nvec, tile_mass, p.n_tiles, p.r[b], p.c2, Lt, L64, thr, lane, pick, p.tok + b,
                                p.lp ? p.lp + b : nullptr);
     if (lane == 0) ASD_DR_STAMP(11);
+}
+
+template <int DT, bool kTopK = false, bool kMinP = false>
+__global__ __launch_bounds__(kDrThreads) void k_draft_row(const DrParams p) {
+    __shared__ NucleusLds sh;
+    __shared__ DraftPickScratch pick;
+    draft_row_body<DT, kTopK, kMinP>(p, sh, pick);
+}
+
+// asd_draft_sample_rows: k_draft_row with the parameters of the workgroup's own sequence (rows[b], asd_sampling_rows_pack) and
+// a workgroup-uniform branch on its mode into the body the scalar kernel of that mode runs: the same bits.
+template <int DT>
+__global__ __launch_bounds__(kDrThreads) void k_draft_row_rows(const DrParams p0, const SamplingRow* rows) {
+    __shared__ NucleusLds sh;
+    __shared__ DraftPickScratch pick;
+    DrParams p = p0;
+    const SamplingRow q = load_sampling_row(rows, blockIdx.x);
+    p.c2 = q.c2; p.top_p = q.top_p; p.levels = q.levels; p.top_k = q.top_k; p.mp_delta = q.mp_delta;
+    if (q.clamp != 0u) {
+        if (q.top_k > 0) draft_row_body<DT, true, true>(p, sh, pick);
+        else draft_row_body<DT, false, true>(p, sh, pick);
+    } else if (q.top_k > 0) draft_row_body<DT, true, false>(p, sh, pick);
+    else draft_row_body<DT, false, false>(p, sh, pick);
 }
 
 // =====================================================================================================================
@@ -726,4 +749,27 @@ ASD_EXPORT int asd_draft_sample_min_p(const void* logits, int64_t ld, int dtype,
     if (!valid_min_p(min_p)) return ASD_ERR_INVALID_ARG;
     return draft_launch(logits, ld, dtype, r, B, V, inv_temperature, top_k, top_p, tok, lp, threshold, workspace, workspace_bytes,
                         stream, min_p > 0.0f ? min_p : 0.0f);
+}
+
+ASD_EXPORT int asd_draft_sample_rows(const void* logits, int64_t ld, int dtype, const float* r, int B, int V, const void* rows,
+                                     int32_t* tok, float* lp, float* threshold, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    (void)workspace; (void)workspace_bytes;                 // one workgroup per row at every B: nothing is handed across workgroups
+    if (B < 0 || V < 1) return ASD_ERR_INVALID_ARG;
+    if (B == 0) return ASD_OK;
+    const RowGeom g = row_geom(V, dtype);
+    if (g.esz == 0) return ASD_ERR_UNSUPPORTED;
+    if (!logits || !r || !tok || ld < V || !rows) return ASD_ERR_INVALID_ARG;
+    if (!g.whole || !rows_aligned(logits, ld, g.esz)) return ASD_ERR_ALIGNMENT;
+    if (g.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
+    DrParams p{};
+    p.logits = logits; p.ld = ld; p.r = r; p.B = B; p.V = V;
+    p.nvec = g.nvec; p.n_tiles = g.n_tiles;
+    p.tok = tok; p.lp = lp; p.thr = threshold;
+    const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
+    dispatch_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_draft_row_rows<decltype(dt)::value>), grid, block, 0, static_cast<hipStream_t>(stream), p,
+                           static_cast<const SamplingRow*>(rows));
+    });
+    return launch_status();
 }

@@ -44,6 +44,7 @@ struct RsParams {
     const float* b_thr;       // [B] nucleus thresholds of the bonus rows (k_rs_bonus_threshold) or nullptr
     float* lp;                // [B] out: log p_t^N(token) (asd_residual_sample_lp) or nullptr
     int clamp_lp;             // asd_residual_sample_lp_min_p: an lp a rounding above 0 (a kept set of one token) is reported as 0
+    const SamplingRow* rows;  // asd_residual_sample_lp_rows: sequence b takes c2 and the clamp flag from rows[b] (c2 / clamp_lp unused)
 };
 
 template <int DT>
@@ -51,13 +52,20 @@ struct Rows {
     const char* xt;   // target row (or the bonus row), nullptr => nothing to sample from
     const char* xd;   // draft row, nullptr => p_d == 0 (bonus draw)
     float tthr, dthr; // nucleus thresholds of the two rows (-inf: the whole vocabulary)
+    float c2;         // the sequence's log2-domain scale: the launch's, or its own (RsParams::rows)
+    int clamp;        // the sequence's "lp above 0 reads as 0" flag, likewise
 };
 
 template <int DT>
 __device__ __forceinline__ Rows<DT> select_rows(const RsParams& p, int b) {
     using E = Elem<DT>;
     const int j = p.n_acc[b];
-    Rows<DT> r{nullptr, nullptr, -INFINITY, -INFINITY};
+    Rows<DT> r{nullptr, nullptr, -INFINITY, -INFINITY, p.c2, p.clamp_lp};
+    if (p.rows) {                                          // (uniform: one table row per sequence)
+        const SamplingRow q = load_sampling_row(p.rows, b);
+        r.c2 = q.c2;
+        r.clamp = static_cast<int>(q.clamp);
+    }
     if (j >= 0 && j < p.K) {
         r.xt = static_cast<const char*>(p.t_logits) + (static_cast<int64_t>(b) * p.K + j) * p.ld_t * E::kBytes;
         r.xd = static_cast<const char*>(p.d_logits) + (static_cast<int64_t>(b) * p.K + j) * p.ld_d * E::kBytes;
@@ -99,8 +107,8 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_lse(const RsParams p) {
         for (int t = t0 + wave; t < t1; t += kRsWaves) {
             const int v = t * 64 + lane;
             if (v < p.nvec) {
-                accum_nucleus<DT>(vt[v], rows.tthr, p.c2, mt, st);
-                if (vd) accum_nucleus<DT>(vd[v], rows.dthr, p.c2, md, sd);
+                accum_nucleus<DT>(vt[v], rows.tthr, rows.c2, mt, st);
+                if (vd) accum_nucleus<DT>(vd[v], rows.dthr, rows.c2, md, sd);
             }
         }
     }
@@ -152,7 +160,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_mass(const RsParams p) {
             const u32x4 a = vt[v];
             u32x4 d = {0u, 0u, 0u, 0u};
             if (vd) d = vd[v];
-            vector_weights<DT>(a, d, vd != nullptr, p.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
+            vector_weights<DT>(a, d, vd != nullptr, rows.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
 #pragma unroll
             for (int i = 0; i < N; ++i) { z += w[i]; q += pt[i]; }
         }
@@ -227,7 +235,7 @@ __device__ __forceinline__ void rs_pick_scan(const RsParams& p, int b, int lane,
         a = vt[v];
         u32x4 d = {0u, 0u, 0u, 0u};
         if (vd) d = vd[v];
-        vector_weights<DT>(a, d, vd != nullptr, p.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
+        vector_weights<DT>(a, d, vd != nullptr, rows.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
     }
     double lm = 0.0;
 #pragma unroll
@@ -263,8 +271,8 @@ __device__ __forceinline__ void rs_pick_scan(const RsParams& p, int b, int lane,
 #pragma unroll
             for (int i = 1; i < N; ++i) x_tok = pick == i ? x[i] : x_tok;
             const double L = static_cast<double>(Lt.hi) + static_cast<double>(Lt.lo);
-            double lq = kLn2d * (static_cast<double>(x_tok) * static_cast<double>(p.c2) - L);
-            if (p.clamp_lp && lq > 0.0) lq = 0.0;
+            double lq = kLn2d * (static_cast<double>(x_tok) * static_cast<double>(rows.c2) - L);
+            if (rows.clamp && lq > 0.0) lq = 0.0;
             p.lp[b] = static_cast<float>(lq);
         }
     }
@@ -324,8 +332,8 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_row(const RsParams p) {
     };
     float mt = kSentinel, st = 0.0f, md = kSentinel, sd = 0.0f;
     for_each([&](int, const u32x4& a, const u32x4& d) {
-        accum_nucleus<DT>(a, rows.tthr, p.c2, mt, st);
-        if (vd) accum_nucleus<DT>(d, rows.dthr, p.c2, md, sd);
+        accum_nucleus<DT>(a, rows.tthr, rows.c2, mt, st);
+        if (vd) accum_nucleus<DT>(d, rows.dthr, rows.c2, md, sd);
     });
     wave_merge(mt, st);
     wave_merge(md, sd);
@@ -340,7 +348,7 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_row(const RsParams p) {
     const Norm2 Lt = norm2_of(mt, st), Ld = norm2_of(md, sd);
     for_each([&](int v, const u32x4& a, const u32x4& d) {
         float w[N], pt[N];
-        vector_weights<DT>(a, d, vd != nullptr, p.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
+        vector_weights<DT>(a, d, vd != nullptr, rows.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
         float z = 0.0f, q = 0.0f;
 #pragma unroll
         for (int i = 0; i < N; ++i) { z += w[i]; q += pt[i]; }
@@ -417,8 +425,8 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
         const int tile = t0 + wave + kDrWaves * j;
         if (tile < t1) {                                   // wave-uniform
             float Mt, St, Md = kSentinel, Sd = 0.0f;
-            tile_pair<DT>(qa[j], p.c2, Mt, St, rows.tthr);
-            if (has_d) tile_pair<DT>(qb[j], p.c2, Md, Sd, rows.dthr);
+            tile_pair<DT>(qa[j], rows.c2, Mt, St, rows.tthr);
+            if (has_d) tile_pair<DT>(qb[j], rows.c2, Md, Sd, rows.dthr);
             if (lane == 0) {
                 if (leader) { tm[tile] = Mt; ts[tile] = St; dm[tile] = Md; dsum[tile] = Sd; }
                 else {
@@ -469,7 +477,7 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
         const int tile = t0 + wave + kDrWaves * j;
         if (tile < t1) {                                   // wave-uniform
             float w[N], pt[N];
-            vector_weights<DT>(qa[j], qb[j], has_d, p.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
+            vector_weights<DT>(qa[j], qb[j], has_d, rows.c2, Lt, Ld, rows.tthr, rows.dthr, w, pt);
             float z = 0.0f, pm = 0.0f;
 #pragma unroll
             for (int i = 0; i < N; ++i) { z += w[i]; pm += pt[i]; }
@@ -502,18 +510,41 @@ __global__ __launch_bounds__(kDrThreads) void k_residual_group(const RgParams q)
 // draw from a residual (or have no bonus row) leave at once.
 // kTopK (asd_residual_sample_top_k): the top-k + top-p threshold max(x_k, x*_K) of asd_draft_sample_top_k's select instead.
 // kMinP (asd_residual_sample_lp_min_p): max(that, x_max + mp_delta), asd_draft_sample_min_p's.
+// (the body of k_rs_bonus_threshold and of k_rs_bonus_threshold_rows; the LDS is declared once, by the kernel)
+template <int DT, bool kTopK, bool kMinP>
+__device__ __forceinline__ void rs_bonus_threshold_body(const RsParams& p, float c2, float top_p, int levels, float* b_thr, int top_k,
+                                                        float mp_delta, NucleusLds& sh) {
+    using E = Elem<DT>;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.bonus) + static_cast<int64_t>(b) * p.ld_b * E::kBytes);
+    const NucleusSel sel = nucleus_row_select<DT, kTopK, kMinP>(row, p.V, p.nvec, p.n_tiles, c2, top_p, levels, sh, t, [](int) {},
+                                                                top_k, mp_delta);
+    if (t == 0) b_thr[b] = sel.thr;
+}
+
 template <int DT, bool kTopK = false, bool kMinP = false>
 __global__ __launch_bounds__(kDrThreads) void k_rs_bonus_threshold(const RsParams p, float top_p, int levels, float* b_thr, int top_k,
                                                                    float mp_delta = 0.0f) {
-    using E = Elem<DT>;
     __shared__ NucleusLds sh;
-    const int b = blockIdx.x, t = threadIdx.x;
-    const int j = p.n_acc[b];
+    const int j = p.n_acc[blockIdx.x];
     if ((j >= 0 && j < p.K) || !p.bonus) return;                        // block-uniform
-    const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.bonus) + static_cast<int64_t>(b) * p.ld_b * E::kBytes);
-    const NucleusSel sel = nucleus_row_select<DT, kTopK, kMinP>(row, p.V, p.nvec, p.n_tiles, p.c2, top_p, levels, sh, t, [](int) {},
-                                                                top_k, mp_delta);
-    if (t == 0) b_thr[b] = sel.thr;
+    rs_bonus_threshold_body<DT, kTopK, kMinP>(p, p.c2, top_p, levels, b_thr, top_k, mp_delta, sh);
+}
+
+// asd_residual_sample_lp_rows: the select parameters of the workgroup's own sequence (p.rows[b]) and a workgroup-uniform branch on
+// its mode into the body the scalar kernel of that mode runs.  A sequence that truncates nothing runs the <false, false> body
+// with levels = 0: sweep 1 alone, thr = -inf.
+template <int DT>
+__global__ __launch_bounds__(kDrThreads) void k_rs_bonus_threshold_rows(const RsParams p, float* b_thr) {
+    __shared__ NucleusLds sh;
+    const int j = p.n_acc[blockIdx.x];
+    if ((j >= 0 && j < p.K) || !p.bonus) return;                        // block-uniform
+    const SamplingRow q = load_sampling_row(p.rows, blockIdx.x);
+    if (q.clamp != 0u) {
+        if (q.top_k > 0) rs_bonus_threshold_body<DT, true, true>(p, q.c2, q.top_p, q.levels, b_thr, q.top_k, q.mp_delta, sh);
+        else rs_bonus_threshold_body<DT, false, true>(p, q.c2, q.top_p, q.levels, b_thr, 0, q.mp_delta, sh);
+    } else if (q.top_k > 0) rs_bonus_threshold_body<DT, true, false>(p, q.c2, q.top_p, q.levels, b_thr, q.top_k, 0.0f, sh);
+    else rs_bonus_threshold_body<DT, false, false>(p, q.c2, q.top_p, q.levels, b_thr, 0, 0.0f, sh);
 }
 
 // sequences from which the one-workgroup-per-sequence form is used (tools/rs_threshold_ab.sh, V = 152064 bf16: three launches
@@ -583,6 +614,7 @@ struct RsTruncate {
     float top_p = 1.0f;
     int top_k = 0;
     float min_p = 0.0f;                      // (0, 1]: asd_residual_sample_lp_min_p; 0 = none
+    const void* rows = nullptr;              // asd_residual_sample_lp_rows: the packed per-sequence table (device); the three above unused
 };
 
 // The launcher behind the five entry points.  A call that truncates nothing (top_p outside (0, 1) and top_k <= 0 or >= V) is
@@ -596,7 +628,8 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     // _ex pass top_p = 1)
     if (cut.top_p != cut.top_p) return ASD_ERR_INVALID_ARG;
     const Truncation tr = truncation(cut.top_k, cut.top_p, V, dtype);
-    const bool truncated = tr.nucleus || tr.top_k > 0 || cut.min_p > 0.0f;
+    // (a per-sequence table always takes the truncating route: the thresholds decide per row, -inf = the whole vocabulary)
+    const bool truncated = tr.nucleus || tr.top_k > 0 || cut.min_p > 0.0f || cut.rows;
     if (truncated) {
         if (B > 0 && K > 0 && !cut.t_threshold) return ASD_ERR_INVALID_ARG;
         if (B > 0 && workspace && workspace_bytes < asd_residual_sample_top_p_workspace_bytes(B, V, dtype)) return ASD_ERR_WORKSPACE;
@@ -608,7 +641,7 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     if (!n_acc || !r || !token || !workspace) return ASD_ERR_INVALID_ARG;
     if (K > 0 && (!t_logits || !d_logits || ld_t < V || ld_d < V)) return ASD_ERR_INVALID_ARG;
     if (bonus_logits && ld_b < V) return ASD_ERR_INVALID_ARG;
-    if (!valid_inv_temperature(inv_temperature)) return ASD_ERR_INVALID_ARG;
+    if (!cut.rows && !valid_inv_temperature(inv_temperature)) return ASD_ERR_INVALID_ARG;
     // whole 16-byte vectors, 16-byte aligned rows
     if (!g.whole) return ASD_ERR_ALIGNMENT;
     if ((t_logits && !rows_aligned(t_logits, ld_t, g.esz)) || (d_logits && !rows_aligned(d_logits, ld_d, g.esz)) ||
@@ -618,7 +651,8 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
     RsParams p{};
     p.t_logits = t_logits; p.ld_t = ld_t; p.d_logits = d_logits; p.ld_d = ld_d; p.bonus = bonus_logits; p.ld_b = ld_b;
     p.n_acc = n_acc; p.r = r; p.B = B; p.K = K; p.V = V;
-    p.c2 = log2_scale(inv_temperature);
+    p.c2 = cut.rows ? 0.0f : log2_scale(inv_temperature);
+    p.rows = static_cast<const SamplingRow*>(cut.rows);
     p.nvec = g.nvec; p.n_tiles = g.n_tiles;
     p.S = rs_splits(B, p.n_tiles, current_device_cus());
     char* const body = static_cast<char*>(workspace) + kWorkspaceHeaderBytes;       // (behind the status block)
@@ -641,7 +675,8 @@ int residual_launch(const void* t_logits, int64_t ld_t, const void* d_logits, in
         const dim3 grid(static_cast<unsigned>(B)), block(kDrThreads);
         dispatch_dtype(dtype, [&](auto dt) {
             constexpr int DT = decltype(dt)::value;
-            if (cut.min_p > 0.0f) {
+            if (cut.rows) hipLaunchKernelGGL((k_rs_bonus_threshold_rows<DT>), grid, block, 0, st, p, b_thr);
+            else if (cut.min_p > 0.0f) {
                 const float mp_delta = min_p_delta(cut.min_p, inv_temperature);
                 if (tr.top_k > 0) hipLaunchKernelGGL((k_rs_bonus_threshold<DT, true, true>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, tr.top_k, mp_delta);
                 else hipLaunchKernelGGL((k_rs_bonus_threshold<DT, false, true>), grid, block, 0, st, p, cut.top_p, tr.levels, b_thr, 0, mp_delta);
@@ -754,4 +789,17 @@ ASD_EXPORT int asd_residual_sample_lp_min_p(const void* t_logits, int64_t ld_t, 
     return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, inv_temperature,
                            d_threshold, token, workspace, workspace_bytes, stream,
                            {t_threshold, top_p, top_k, min_p > 0.0f ? min_p : 0.0f}, lp);
+}
+
+ASD_EXPORT int asd_residual_sample_lp_rows(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                                           const void* bonus_logits, int64_t ld_b, int dtype, const int32_t* n_acc,
+                                           const float* r, int B, int K, int V, const void* rows, const float* t_threshold,
+                                           const float* d_threshold, int32_t* token, float* lp, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    if (B > 0 && (!lp || !rows)) return ASD_ERR_INVALID_ARG;
+    RsTruncate cut{};
+    cut.t_threshold = t_threshold;
+    cut.rows = rows;
+    return residual_launch(t_logits, ld_t, d_logits, ld_d, bonus_logits, ld_b, dtype, n_acc, r, B, K, V, 1.0f, d_threshold, token,
+                           workspace, workspace_bytes, stream, cut, lp);
 }

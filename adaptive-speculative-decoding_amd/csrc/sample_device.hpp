@@ -535,6 +535,20 @@ __device__ __forceinline__ NucleusSel nucleus_row_select(const u32x4* row, int V
     return r;
 }
 
+// rows[b] of the packed sampling table (common.hpp, SamplingRow) as workgroup-uniform values: b is uniform, and every field goes
+// through readfirstlane so that the mode branches and the select's parameters live in scalar registers as a kernel argument would
+__device__ __forceinline__ SamplingRow load_sampling_row(const SamplingRow* rows, int b) {
+    const SamplingRow q = rows[b];
+    SamplingRow r{};
+    r.c2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.c2)));
+    r.top_p = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.top_p)));
+    r.levels = __builtin_amdgcn_readfirstlane(q.levels);
+    r.top_k = __builtin_amdgcn_readfirstlane(q.top_k);
+    r.mp_delta = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q.mp_delta)));
+    r.clamp = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(q.clamp)));
+    return r;
+}
+
 // ---- cross-workgroup mailboxes of the group kernels (k_draft_group, k_residual_group): single writer, single reader,
 // self-tagging words (non-zero = published), handed back empty by the reader
 constexpr int kDgMaxGroups = 32;          // workgroups per row

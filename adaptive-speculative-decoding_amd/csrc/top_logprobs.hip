@@ -63,6 +63,7 @@ struct TopParams {
     int64_t ld_seq, ld_row;
     int K1, V, S, N;
     float c2;
+    const float* inv_t;       // k_top_logprobs<DT, true> (asd_top_logprobs_rows): [B] per-sequence 1 / T; c2 unused
     int32_t* top_id;
     float* top_lp;
     uint32_t* row_tickets;
@@ -219,7 +220,8 @@ __device__ __forceinline__ void merge_in_lane_order(float m2, float s, int n, fl
                  __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l)));
 }
 
-template <int DT>
+// kRows (asd_top_logprobs_rows): the scale of sequence b is formed from inv_t[b] by log2_scale's own f64 product
+template <int DT, bool kRows = false>
 __global__ __launch_bounds__(kThreads) void k_top_logprobs(const TopParams p) {
     using E = Elem<DT>;
     __shared__ float meet_v[kWaves][kTop];
@@ -232,10 +234,13 @@ __global__ __launch_bounds__(kThreads) void k_top_logprobs(const TopParams p) {
     const int wave = tid >> 6;
     const int S = p.S;
     const int K1 = p.K1;
-    const float c2 = p.c2;
     const int row = static_cast<int>(blockIdx.x);
     const int split = static_cast<int>(blockIdx.y);
     const int b = static_cast<int>(static_cast<uint32_t>(row) / static_cast<uint32_t>(K1));
+    float c2 = p.c2;
+    if constexpr (kRows)
+        c2 = __int_as_float(__builtin_amdgcn_readfirstlane(
+            __float_as_int(static_cast<float>(1.4426950408889634074 * static_cast<double>(p.inv_t[b])))));
     const int k = row - b * K1;
 
     const char* rowp = static_cast<const char*>(p.logits) + (static_cast<int64_t>(b) * p.ld_seq + static_cast<int64_t>(k) * p.ld_row) * E::kBytes;
@@ -389,11 +394,13 @@ ASD_EXPORT size_t asd_top_logprobs_workspace_bytes(int B, int K1, int N) {
     return layout(B, K1, ASD_MAX_SPLITS).total;
 }
 
-ASD_EXPORT int asd_top_logprobs(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
-                                float inv_temperature, int N, int splits, int32_t* top_id, float* top_lp, void* workspace,
-                                size_t workspace_bytes, void* stream) {
+namespace {
+// asd_top_logprobs (inv_t_rows == nullptr) and asd_top_logprobs_rows (the scalar unused)
+int top_logprobs_launch(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V, float inv_temperature,
+                        const float* inv_t_rows, bool per_row, int N, int splits, int32_t* top_id, float* top_lp, void* workspace,
+                        size_t workspace_bytes, void* stream) {
     if (B > 0 && (!top_id || !top_lp)) return ASD_ERR_INVALID_ARG;
-    if (!valid_inv_temperature(inv_temperature)) return ASD_ERR_INVALID_ARG;
+    if (per_row ? (B > 0 && !inv_t_rows) : !valid_inv_temperature(inv_temperature)) return ASD_ERR_INVALID_ARG;
     if (B < 0 || K1 < 0 || V < 0 || N < 0) return ASD_ERR_INVALID_ARG;
     if (B == 0) return ASD_OK;
     if (V == 0 || K1 < 1 || N < 1) return ASD_ERR_INVALID_ARG;
@@ -415,7 +422,8 @@ ASD_EXPORT int asd_top_logprobs(const void* logits, int dtype, int64_t ld_seq, i
     TopParams p{};
     p.logits = logits; p.ld_seq = ld_seq; p.ld_row = ld_row;
     p.K1 = K1; p.V = V; p.S = S; p.N = N;
-    p.c2 = log2_scale(inv_temperature);
+    p.c2 = per_row ? 0.0f : log2_scale(inv_temperature);
+    p.inv_t = inv_t_rows;
     p.top_id = top_id; p.top_lp = top_lp;
     char* const ws = static_cast<char*>(workspace);
     p.row_tickets = reinterpret_cast<uint32_t*>(ws);
@@ -427,7 +435,23 @@ ASD_EXPORT int asd_top_logprobs(const void* logits, int dtype, int64_t ld_seq, i
     }
     const dim3 grid(static_cast<uint32_t>(R), static_cast<uint32_t>(S));
     dispatch_dtype(dtype, [&](auto dt) {
-        hipLaunchKernelGGL((k_top_logprobs<decltype(dt)::value>), grid, dim3(kThreads), 0, st, p);
+        if (per_row) hipLaunchKernelGGL((k_top_logprobs<decltype(dt)::value, true>), grid, dim3(kThreads), 0, st, p);
+        else hipLaunchKernelGGL((k_top_logprobs<decltype(dt)::value>), grid, dim3(kThreads), 0, st, p);
     });
     return launch_status();
+}
+}  // namespace
+
+ASD_EXPORT int asd_top_logprobs(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                                float inv_temperature, int N, int splits, int32_t* top_id, float* top_lp, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    return top_logprobs_launch(logits, dtype, ld_seq, ld_row, B, K1, V, inv_temperature, nullptr, false, N, splits, top_id, top_lp,
+                               workspace, workspace_bytes, stream);
+}
+
+ASD_EXPORT int asd_top_logprobs_rows(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                                     const float* inv_temperature, int N, int splits, int32_t* top_id, float* top_lp,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    return top_logprobs_launch(logits, dtype, ld_seq, ld_row, B, K1, V, 1.0f, inv_temperature, true, N, splits, top_id, top_lp,
+                               workspace, workspace_bytes, stream);
 }

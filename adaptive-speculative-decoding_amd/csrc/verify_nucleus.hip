@@ -37,10 +37,10 @@ struct VnParams {
     float mp_delta;           // k_verify_nucleus<DT, *, true> only (asd_verify_accept_min_p): T ln(min_p) <= 0
 };
 
-template <int DT, bool kTopK = false, bool kMinP = false>
-__global__ __launch_bounds__(kDrThreads) void k_verify_nucleus(const VnParams p) {
+// The body of k_verify_nucleus and of k_verify_nucleus_rows (the LDS is declared once, by the kernel)
+template <int DT, bool kTopK, bool kMinP>
+__device__ __forceinline__ void verify_nucleus_body(const VnParams& p, NucleusLds& sh) {
     using E = Elem<DT>;
-    __shared__ NucleusLds sh;
     const int r = blockIdx.x, t = threadIdx.x;
     const u32x4* row = reinterpret_cast<const u32x4*>(static_cast<const char*>(p.logits) + static_cast<int64_t>(r) * p.ld * E::kBytes);
     // (kTopK: thr = max(x_k, x*_K) and L64 its normaliser -- the select of asd_draft_sample_top_k; kMinP: that of
@@ -60,6 +60,28 @@ __global__ __launch_bounds__(kDrThreads) void k_verify_nucleus(const VnParams p)
     p.lp_t[r] = lpf;
     p.accept[r] = flag ? 1 : 0;
     if (p.thr) p.thr[r] = sel.thr;
+}
+
+template <int DT, bool kTopK = false, bool kMinP = false>
+__global__ __launch_bounds__(kDrThreads) void k_verify_nucleus(const VnParams p) {
+    __shared__ NucleusLds sh;
+    verify_nucleus_body<DT, kTopK, kMinP>(p, sh);
+}
+
+// asd_verify_accept_rows: row r = b*K + k takes the parameters of sequence b (rows[b], asd_sampling_rows_pack) and a
+// workgroup-uniform branch on its mode into the body the scalar kernel of that mode runs.  A sequence that truncates nothing
+// runs the <false, false> body with levels = 0: thr = -inf, lp_t from the sweep-1 normaliser (asd_draft_sample's lp bits).
+template <int DT>
+__global__ __launch_bounds__(kDrThreads) void k_verify_nucleus_rows(const VnParams p0, const SamplingRow* rows) {
+    __shared__ NucleusLds sh;
+    VnParams p = p0;
+    const SamplingRow q = load_sampling_row(rows, static_cast<int>(blockIdx.x / static_cast<unsigned>(p0.K)));
+    p.c2 = q.c2; p.top_p = q.top_p; p.levels = q.levels; p.top_k = q.top_k; p.mp_delta = q.mp_delta;
+    if (q.clamp != 0u) {
+        if (q.top_k > 0) verify_nucleus_body<DT, true, true>(p, sh);
+        else verify_nucleus_body<DT, false, true>(p, sh);
+    } else if (q.top_k > 0) verify_nucleus_body<DT, true, false>(p, sh);
+    else verify_nucleus_body<DT, false, false>(p, sh);
 }
 
 // one wave per sequence: lane k < K reads row (b, k)'s flag and lp_t.  all_rows = 0: only n_finite (and nothing else) is written
@@ -179,4 +201,35 @@ ASD_EXPORT int asd_verify_accept_min_p(const void* logits, int dtype, int64_t ld
     return verify_truncated(logits, dtype, ld_row, tok, lp_draft, u, B, K, V, inv_temperature, top_k, top_p, lp_target, accept,
                             n_acc, accept_bits, t_nucleus_logit, n_finite, workspace, workspace_bytes, stream,
                             min_p > 0.0f ? min_p : 0.0f);
+}
+
+ASD_EXPORT int asd_verify_accept_rows(const void* logits, int dtype, int64_t ld_row, const int32_t* tok, const float* lp_draft,
+                                      const float* u, int B, int K, int V, const void* rows, float* lp_target, uint8_t* accept,
+                                      int32_t* n_acc, uint64_t* accept_bits, float* t_nucleus_logit, int32_t* n_finite,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    (void)workspace; (void)workspace_bytes;                 // the select's two launches: nothing is handed across workgroups
+    if (B < 0 || K < 0 || V < 1) return ASD_ERR_INVALID_ARG;
+    if (B == 0 || K == 0) return ASD_OK;
+    if (K > ASD_MAX_DRAFT_LEN) return ASD_ERR_UNSUPPORTED;
+    const RowGeom g = row_geom(V, dtype);
+    if (g.esz == 0) return ASD_ERR_UNSUPPORTED;
+    if (!logits || !tok || !lp_draft || !u || !lp_target || !accept || !n_acc || ld_row < V || !rows) return ASD_ERR_INVALID_ARG;
+    const int64_t R = static_cast<int64_t>(B) * K;
+    if (R > INT32_MAX) return ASD_ERR_UNSUPPORTED;
+    if (!g.whole || !rows_aligned(logits, ld_row, g.esz)) return ASD_ERR_ALIGNMENT;
+    if (g.n_tiles > kDrMaxTiles) return ASD_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    VnParams p{};
+    p.logits = logits; p.ld = ld_row; p.tok = tok; p.lp_d = lp_draft; p.u = u;
+    p.B = B; p.K = K; p.V = V;
+    p.nvec = g.nvec; p.n_tiles = g.n_tiles;
+    p.lp_t = lp_target; p.accept = accept; p.n_acc = n_acc; p.bits = accept_bits;
+    p.thr = t_nucleus_logit; p.n_finite = n_finite;
+    dispatch_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_verify_nucleus_rows<decltype(dt)::value>), dim3(static_cast<unsigned>(R)), dim3(kDrThreads), 0, st, p,
+                           static_cast<const SamplingRow*>(rows));
+    });
+    hipLaunchKernelGGL(k_nucleus_finish, dim3(static_cast<unsigned>(B)), dim3(64), 0, st, accept, lp_target, K, 1, n_acc,
+                       accept_bits, n_finite);
+    return launch_status();
 }

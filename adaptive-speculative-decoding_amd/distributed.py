@@ -316,6 +316,40 @@ class HipOps:
         return s.lp(t_logits, d_logits, n_acc, r, bonus, inv_temperature, top_k=top_k, top_p=top_p, t_threshold=t_threshold,
                     d_threshold=d_threshold)
 
+    # -- per-request sampling parameters (serving/stages.py, PER-REQUEST SAMPLING): one packed table per generate call
+    def pack_sampling_rows(self, inv_temperature, top_k, top_p, min_p, V, dtype, device):
+        """The packed per-sequence table of the *_rows ops (asd_sampling_rows_pack), uploaded once: inv_temperature / top_k /
+        top_p / min_p hold one value per sequence (top_k / top_p / min_p may be None = off) -> opaque handle."""
+        return self.K.SamplingRows(inv_temperature, top_k, top_p, min_p, V=V, dtype=dtype, device=device)
+
+    @traced("draft_sample_rows")
+    def draft_sample_rows(self, logits, r, rows):
+        """X1 with every sequence's own Temperature -> TopK -> TopP -> MinP (asd_draft_sample_rows): logits [B,V] -> (tok i32
+        [B], log q(tok) f32 [B], threshold f32 [B]); sequence b has the bits of draft_sample_min_p with its values."""
+        d = self._sampler("draft", logits.shape[0], logits.shape[1], logits.dtype, logits.device).rows(logits, r, rows)
+        return d.tok, d.lp, d.thr
+
+    @traced("verify_accept_rows")
+    def verify_accept_rows(self, logits, tok, lp_d, u, rows):
+        """Verify against every sequence's own target distribution (asd_verify_accept_rows) -> (lp_t, accept, n_acc, bits,
+        thr [B,K], n_finite [B]); a sequence that truncates nothing is scored by the same select kernel (thr = -inf)."""
+        B, K = tok.shape
+        nbytes = B * K * logits.shape[-1] * logits.element_size() + 21 * B * K + 16 * B + 32 * B
+        r = self._timed_step("asd_verify_accept_rows", nbytes, lambda: self.K.verify_accept_rows(logits, tok, lp_d, u, rows))
+        return r.lp_target, r.accept, r.n_acc, r.accept_bits, r.t_nucleus_logit, r.n_finite
+
+    @traced("residual_sample_lp_rows")
+    def residual_sample_lp_rows(self, t_logits, d_logits, n_acc, r, bonus, rows, d_threshold=None, t_threshold=None):
+        """The committed token and its target log-prob with every sequence's own parameters (asd_residual_sample_lp_rows) ->
+        (token i32 [n], lp f32 [n]); t_threshold = the thresholds of verify_accept_rows."""
+        s = self._sampler("residual", t_logits.shape[0], t_logits.shape[2], t_logits.dtype, t_logits.device)
+        return s.lp_rows(t_logits, d_logits, n_acc, r, bonus, rows=rows, t_threshold=t_threshold, d_threshold=d_threshold)
+
+    @traced("top_logprobs_rows")
+    def top_logprobs_rows(self, logits, n, rows, splits: int = 0):
+        """top_logprobs with every sequence's own temperature (asd_top_logprobs_rows; rows: the pack_sampling_rows handle)."""
+        return self._top_logprobs(logits, n, rows.inv_t, splits)
+
     @traced("verify_greedy")
     def verify_greedy(self, logits, tok=None, inv_temperature: float = 1.0, splits: int = 0):
         """Greedy decoding's step (asd_verify_greedy): logits [B,K+1,V] read in place (or [B,V] with tok = None: K = 0), tok i32
@@ -336,6 +370,9 @@ class HipOps:
         [B,K1,V] -- a strided view is read in place, nothing is copied -- or [B,V] -> (top_id i32 [B,K1,n], top_lp f32 [B,K1,n]),
         value descending then id ascending, (-1, -inf) in slots that cannot be filled.  One workspace per shape and calling
         thread, like `verify_greedy`."""
+        return self._top_logprobs(logits, n, inv_temperature, splits)
+
+    def _top_logprobs(self, logits, n, inv_temperature, splits):
         K1 = 1 if logits.dim() == 2 else logits.shape[1]
         Bv, V = logits.shape[0], logits.shape[-1]
         key = ("top_logprobs", K1, V, int(n), str(logits.dtype), str(logits.device))

@@ -224,6 +224,58 @@ def verify_accept_min_p(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch
                              (int(top_k), float(top_p), float(min_p)), out)
 
 
+# ------------------------------------------------------------------------------- per-sequence sampling parameters
+class SamplingRows:
+    """The packed per-sequence sampling table of the *_rows entry points (include/asd_hip.h: asd_sampling_rows_pack) on the
+    device: one row of 32 bytes per sequence with what a scalar launch with that sequence's (inv_temperature, top_k, top_p,
+    min_p) would use.  Packed on the host by the library, uploaded once; `inv_t` is the f32 [B] device copy of the
+    temperatures (asd_top_logprobs_rows).  The table depends on V and the logits dtype (top_k >= V is off; the select's radix
+    levels).  top_k / top_p / min_p: None = off for every sequence, else one value per sequence."""
+
+    def __init__(self, inv_temperature, top_k=None, top_p=None, min_p=None, *, V: int, dtype: torch.dtype = torch.bfloat16,
+                 device: Optional[torch.device] = None):
+        if dtype not in _DTYPE_CODE:
+            raise ValueError(f"logits dtype {dtype} unsupported (f32 / bf16 / f16)")
+        inv = np.ascontiguousarray(inv_temperature, dtype=np.float32).reshape(-1)
+        n = inv.shape[0]
+
+        def arr(v, dt, name):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(v, dtype=dt).reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError(f"{name} must hold one value per sequence ({n})")
+            return a
+        tk, tp, mp = arr(top_k, np.int32, "top_k"), arr(top_p, np.float32, "top_p"), arr(min_p, np.float32, "min_p")
+        self.B, self.V, self.dtype = n, int(V), dtype
+        self.host = np.zeros(int(_lib().asd_sampling_rows_bytes(n)), np.uint8)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        B.check("asd_sampling_rows_pack", _lib().asd_sampling_rows_pack(vp(inv), vp(tk), vp(tp), vp(mp), n, int(V),
+                                                                        _DTYPE_CODE[dtype], vp(self.host)))
+        dev = device or torch.device("cuda")
+        self.buf = torch.from_numpy(self.host).to(dev)
+        self.inv_t = torch.from_numpy(inv).to(dev)
+
+    def ptr(self, Bv: int, V: int, dtype) -> int:
+        """The device table for a call on Bv sequences of [.., V] `dtype` logits."""
+        if Bv != self.B or V != self.V or dtype != self.dtype:
+            raise ValueError(f"the sampling table was packed for B={self.B}, V={self.V}, {self.dtype}")
+        return self.buf.data_ptr()
+
+
+def verify_accept_rows(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor, rows: SamplingRows,
+                       out: Optional[NucleusVerifyResult] = None) -> NucleusVerifyResult:
+    """The verify step with every sequence's own temperature / top-k / top-p / min-p (include/asd_hip.h:
+    asd_verify_accept_rows): sequence b returns the bits verify_accept_min_p returns for it with its values; a sequence that
+    truncates nothing is scored by the same select (t_nucleus_logit = -inf).  No workspace."""
+    out, lead, outs = _verify_args(logits, tok, lp_draft, u, out, NucleusVerifyResult)
+    rc = _lib().asd_verify_accept_rows(*lead, rows.ptr(lead[6], lead[8], logits.dtype), *outs,
+                                       _dev(out.t_nucleus_logit, "t_nucleus_logit", torch.float32),
+                                       _dev(out.n_finite, "n_finite", torch.int32), None, 0, _stream())
+    B.check("asd_verify_accept_rows", rc)
+    return out
+
+
 def verify_accept_stats(logits: torch.Tensor, tok: torch.Tensor, lp_draft: torch.Tensor, u: torch.Tensor,
                         workspace: VerifyWorkspace, out: Optional[VerifyResult] = None, *, inv_temperature: float = 1.0,
                         want_entropy: bool = True) -> Tuple[VerifyResult, torch.Tensor, Optional[torch.Tensor]]:
@@ -831,6 +883,34 @@ class ResidualSampler(_StatusWorkspace):
         return tok, lp_out
 
 
+    def lp_rows(self, t_logits: torch.Tensor, d_logits: torch.Tensor, n_acc: torch.Tensor, r: torch.Tensor,
+                bonus_logits: Optional[torch.Tensor] = None, *, rows: "SamplingRows", t_threshold: torch.Tensor,
+                d_threshold: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                lp_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """lp_min_p(...) with every sequence's own parameters (asd_residual_sample_lp_rows): t_threshold [B,K] = the thresholds
+        of verify_accept_rows; the bonus rows' are found by the sampler with the sequence's select."""
+        Bv, K, V = t_logits.shape
+        if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
+            raise ValueError("t_logits and d_logits must have the same shape and dtype")
+        tp, ldt = _rows(t_logits, "t_logits")
+        dp, ldd = _rows(d_logits, "d_logits")
+        bp, ldb = (None, V) if bonus_logits is None else _rows(bonus_logits, "bonus_logits")
+        if out is None:
+            out = torch.empty((Bv,), dtype=torch.int32, device=t_logits.device)
+        if lp_out is None:
+            lp_out = torch.empty((Bv,), dtype=torch.float32, device=t_logits.device)
+        for name, t in (("t_threshold", t_threshold), ("d_threshold", d_threshold)):
+            if t is not None and tuple(t.shape) != (Bv, K):
+                raise ValueError(f"{name} must be [B, K]")
+        rc = _lib().asd_residual_sample_lp_rows(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype],
+                                                _dev(n_acc, "n_acc", torch.int32), _dev(r, "r", torch.float32), Bv, K, V,
+                                                rows.ptr(Bv, V, t_logits.dtype), _opt(t_threshold, "t_threshold", torch.float32),
+                                                _opt(d_threshold, "d_threshold", torch.float32), out.data_ptr(),
+                                                _dev(lp_out, "lp", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_residual_sample_lp_rows", rc)
+        return out, lp_out
+
+
 @dataclass
 class DraftDraw:
     tok: torch.Tensor   # [B] i32  the proposed token
@@ -887,6 +967,27 @@ class DraftSampler(_StatusWorkspace):
         min_p): thr = max(thr_kp, x_max + T ln(min_p)).  min_p <= 0 is top_k(...) (the same bits); otherwise one workgroup
         per row, the workspace unused."""
         return self._draw("asd_draft_sample_min_p", logits, r, inv_temperature, (int(top_k), float(top_p), float(min_p)), out)
+
+
+    def rows(self, logits: torch.Tensor, r: torch.Tensor, rows: "SamplingRows", out: Optional[DraftDraw] = None) -> DraftDraw:
+        """The proposal with every sequence's own temperature / top-k / top-p / min-p (asd_draft_sample_rows): one workgroup
+        per row at every batch size, the workspace unused; sequence b returns the bits min_p(...) returns for it."""
+        if logits.dim() != 2 or logits.dtype != self.dtype or not logits.is_cuda or logits.stride(1) != 1:
+            raise ValueError(f"logits must be a [B, V] {self.dtype} CUDA tensor with unit stride along V")
+        Bv, V = logits.shape
+        if Bv > self.B or V != self.V:
+            raise ValueError(f"sampler was sized for B<={self.B}, V={self.V}")
+        dev = logits.device
+        if out is None:
+            out = DraftDraw(torch.empty((Bv,), dtype=torch.int32, device=dev),
+                            torch.empty((Bv,), dtype=torch.float32, device=dev),
+                            torch.empty((Bv,), dtype=torch.float32, device=dev))
+        rc = _lib().asd_draft_sample_rows(logits.data_ptr(), logits.stride(0) if Bv > 1 else V, _DTYPE_CODE[logits.dtype],
+                                          _dev(r, "r", torch.float32), Bv, V, rows.ptr(Bv, V, logits.dtype),
+                                          _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
+                                          _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_draft_sample_rows", rc)
+        return out
 
 
 # ------------------------------------------------------------------------------- greedy decoding (temperature 0)
@@ -983,8 +1084,9 @@ class TopLogprobs:
         return (torch.empty((Bv, self.K1, self.n), dtype=torch.int32, device=self.device),
                 torch.empty((Bv, self.K1, self.n), dtype=torch.float32, device=self.device))
 
-    def __call__(self, logits: torch.Tensor, inv_temperature: float = 1.0, splits: int = 0,
+    def __call__(self, logits: torch.Tensor, inv_temperature=1.0, splits: int = 0,
                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """inv_temperature: a number, or a float32 [B] device tensor with one value per sequence (asd_top_logprobs_rows)."""
         K1, V = self.K1, self.V
         if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != self.dtype:
             raise ValueError(f"logits must be a {self.dtype} CUDA (HIP) tensor; this package has no CPU path")
@@ -1005,10 +1107,16 @@ class TopLogprobs:
         top_id, top_lp = out
         if tuple(top_id.shape) != (Bv, K1, self.n) or tuple(top_lp.shape) != (Bv, K1, self.n):
             raise ValueError("out must be (int32 [B, K1, n], float32 [B, K1, n])")
-        rc = _lib().asd_top_logprobs(logits.data_ptr(), _DTYPE_CODE[logits.dtype], ld_seq, ld_row, Bv, K1, V,
-                                     float(inv_temperature), self.n, int(splits), _dev(top_id, "top_id", torch.int32),
-                                     _dev(top_lp, "top_lp", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_top_logprobs", rc)
+        if isinstance(inv_temperature, torch.Tensor):
+            if tuple(inv_temperature.shape) != (Bv,):
+                raise ValueError("a per-sequence inv_temperature must be float32 [B]")
+            entry, scale = "asd_top_logprobs_rows", _dev(inv_temperature, "inv_temperature", torch.float32)
+        else:
+            entry, scale = "asd_top_logprobs", float(inv_temperature)
+        rc = getattr(_lib(), entry)(logits.data_ptr(), _DTYPE_CODE[logits.dtype], ld_seq, ld_row, Bv, K1, V,
+                                    scale, self.n, int(splits), _dev(top_id, "top_id", torch.int32),
+                                    _dev(top_lp, "top_lp", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
+        B.check(entry, rc)
         return out
 
 

@@ -20,6 +20,14 @@ every stage sees `stage.generate(max_tokens=[...])` with the values of that call
 before.  `PipelineConfig.stop_sequences` (also read from the YAML `pipeline:` section) is handed to every stage.generate call as
 `stop_sequences=`, only when set (serving/stages.py, HOW A ROW ENDS).
 
+Per-request sampling parameters (the reference's GenerationRequest.temperature / top_p, src/serving/server.py:44-45,67; top_k and
+min_p as in vLLM's SamplingParams): `batch_process(temperature=, top_p=, top_k=, min_p=)` take one value or one per request, and
+`process_request` takes `top_p=`, `top_k=`, `min_p=`.  A request keeps its values (`_Active`) through the same regroupings and
+across stages; a stage sees lists only where the batch carries lists, and one value given for the whole batch as that value, so
+calls without them are the calls made before (serving/stages.py, PER-REQUEST SAMPLING).  A stage call cannot mix greedy
+(temperature 0) and sampled rows: `batch_process` runs such a batch as a greedy and a sampled sub-batch -- the one place mixing
+is handled -- and returns the results in request order.
+
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
                      p_i = predictor.predict(...)  (1.0 at the last stage)        :225-241
@@ -61,7 +69,7 @@ import numpy as np
 
 from ..backend import get_backend
 from .cache import RequestCache
-from .stages import check_max_tokens, check_seeds
+from .stages import check_max_tokens, check_per_prompt, check_seeds
 
 logger = logging.getLogger(__name__)
 
@@ -156,6 +164,11 @@ class _Active:
     predicted_stage: int = -1
     seed: Optional[int] = None                              # the request's sampling seed (None: the stage's own generator)
     max_tokens: Optional[int] = None                        # the request's own length limit (None: the batch's one int)
+    # the request's own sampling parameters (None: the batch's one value, or the stage's configuration)
+    temperature: Optional[float] = None
+    top_p: Optional[float] = None
+    top_k: Optional[int] = None
+    min_p: Optional[float] = None
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -186,11 +199,15 @@ class AdaptiveSpeculativePipeline:
 
     # ------------------------------------------------------------------ public API
     def process_request(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
-                        request_id: Optional[str] = None, seed: Optional[int] = None) -> RequestResult:
-        """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring)."""
+                        request_id: Optional[str] = None, seed: Optional[int] = None, top_p: Optional[float] = None,
+                        top_k: Optional[int] = None, min_p: Optional[float] = None) -> RequestResult:
+        """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring).
+        top_p / top_k / min_p: None = every stage's configuration, else the request's own value at every stage
+        (stage.generate(top_p=, top_k=, min_p=))."""
         if seed is not None and not isinstance(seed, (int, np.integer)):
             raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
-        return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1))[0]
+        sampling = {k: check_per_prompt(v, 1, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
+        return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1), sampling=sampling)[0]
 
     async def process_request_async(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
                                     request_id: Optional[str] = None, seed: Optional[int] = None) -> RequestResult:
@@ -198,24 +215,44 @@ class AdaptiveSpeculativePipeline:
         return await loop.run_in_executor(self.executor, self.process_request, prompt, max_tokens, temperature,
                                           request_id, seed)
 
-    def batch_process(self, prompts: List[str], max_tokens=512, temperature: float = 0.7,
-                      seeds=None) -> List[RequestResult]:
+    def batch_process(self, prompts: List[str], max_tokens=512, temperature=0.7,
+                      seeds=None, top_p=None, top_k=None, min_p=None) -> List[RequestResult]:
         """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
         raises ValueError); request i keeps seeds[i] through every regrouping (module docstring).  max_tokens: an int, or one
-        int >= 1 per request, kept by the request in the same way."""
+        int >= 1 per request, kept by the request in the same way.
+        temperature, top_p, top_k, min_p: one value for the batch (None: every stage's configuration), or one per request,
+        kept by the request through every regrouping and handed to stage.generate as a list only where the batch has one
+        (serving/stages.py, PER-REQUEST SAMPLING).  A stage call cannot mix greedy (temperature 0) and sampled rows: a batch
+        whose temperatures do is run as a greedy and a sampled sub-batch here, and the results come back in request order."""
         prompts = list(prompts)
-        seeds = check_seeds(seeds, len(prompts))
-        max_tokens = check_max_tokens(max_tokens, len(prompts))
-        if self.config.batch_grouping != "predicted_stage" or len(prompts) < 2 or self.config.stop_rule == "prefix":
-            return self._run_batch(prompts, max_tokens, temperature, [None] * len(prompts), seeds=seeds)
+        n = len(prompts)
+        seeds = check_seeds(seeds, n)
+        max_tokens = check_max_tokens(max_tokens, n)
+        sampling = {k: check_per_prompt(v, n, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
+        if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
+            temperature = check_per_prompt(temperature, n, "temperature")
+        if isinstance(temperature, list) and any(t == 0.0 for t in temperature):
+            # the one place greedy and sampled requests are mixed: two sub-batches, results in request order
+            results: List[Optional[RequestResult]] = [None] * n
+            for greedy in (True, False):
+                idx = [i for i, t in enumerate(temperature) if (t == 0.0) == greedy]
+                pick = lambda v: [v[i] for i in idx] if isinstance(v, list) else v      # noqa: E731
+                out = self.batch_process([prompts[i] for i in idx], pick(max_tokens), pick(temperature), pick(seeds),
+                                         **{k: pick(v) for k, v in sampling.items()})
+                for i, r in zip(idx, out):
+                    results[i] = r
+            return results  # type: ignore[return-value]
+        if self.config.batch_grouping != "predicted_stage" or n < 2 or self.config.stop_rule == "prefix":
+            return self._run_batch(prompts, max_tokens, temperature, [None] * n, seeds=seeds, sampling=sampling)
         pred = self.predict_stop_stages(prompts)
-        results: List[Optional[RequestResult]] = [None] * len(prompts)
+        results = [None] * n
         for stage in sorted(set(pred.tolist())):                       # shallowest group first
             idx = [i for i, s in enumerate(pred) if s == stage]
-            out = self._run_batch([prompts[i] for i in idx],
-                                  [max_tokens[i] for i in idx] if isinstance(max_tokens, list) else max_tokens, temperature,
+            pick = lambda v: [v[i] for i in idx] if isinstance(v, list) else v          # noqa: E731
+            out = self._run_batch([prompts[i] for i in idx], pick(max_tokens), pick(temperature),
                                   [None] * len(idx),
-                                  predicted=[int(stage)] * len(idx), seeds=None if seeds is None else [seeds[i] for i in idx])
+                                  predicted=[int(stage)] * len(idx), seeds=None if seeds is None else [seeds[i] for i in idx],
+                                  sampling={k: pick(v) for k, v in sampling.items()})
             for i, r in zip(idx, out):
                 results[i] = r
         return results  # type: ignore[return-value]
@@ -298,9 +335,9 @@ class AdaptiveSpeculativePipeline:
         logger.info("Pipeline shutdown completed")
 
     # ------------------------------------------------------------------ the stage loop, batched
-    def _run_batch(self, prompts: List[str], max_tokens, temperature: float,
+    def _run_batch(self, prompts: List[str], max_tokens, temperature,
                    request_ids: List[Optional[str]], predicted: Optional[List[int]] = None,
-                   seeds: Optional[List[int]] = None) -> List[RequestResult]:
+                   seeds: Optional[List[int]] = None, sampling: Optional[Dict[str, Any]] = None) -> List[RequestResult]:
         now = time.time()
         reqs = [_Active(request_id=rid or str(uuid.uuid4()), prompt=p, current_prompt=p, start_time=now)
                 for p, rid in zip(prompts, request_ids)]
@@ -313,11 +350,18 @@ class AdaptiveSpeculativePipeline:
         if isinstance(max_tokens, list):
             for r, n in zip(reqs, max_tokens):
                 r.max_tokens = n
+        # per-request sampling parameters: kept by the request where the batch has a list; a batch-wide value stays batch-wide
+        sampling = dict(sampling or {})
+        shared = {k: v for k, v in sampling.items() if v is not None and not isinstance(v, list)}
+        for name, v in list(sampling.items()) + [("temperature", temperature)]:
+            if isinstance(v, list):
+                for r, x in zip(reqs, v):
+                    setattr(r, name, x)
         for r in reqs:
             self.active_requests[r.request_id] = {"start_time": r.start_time,
                                                   "prompt": r.prompt[:100] + "..." if len(r.prompt) > 100 else r.prompt}
         try:
-            self._process_stages(reqs, max_tokens, temperature)
+            self._process_stages(reqs, max_tokens, temperature, shared)
             results = [self._finish(r) for r in reqs]
             for res in results:
                 self._update_stats(res)
@@ -337,7 +381,7 @@ class AdaptiveSpeculativePipeline:
         return float(self.predictor.predict(prompt=r.current_prompt, draft_output=output, draft_logprobs=logprobs,
                                             stage_id=stage_idx, feature_extractor=self.feature_extractor))
 
-    def _process_stages(self, reqs: List[_Active], max_tokens, temperature: float) -> None:
+    def _process_stages(self, reqs: List[_Active], max_tokens, temperature, shared: Optional[Dict[str, Any]] = None) -> None:
         cfg = self.config
         names = list(cfg.stage_names)
         L = len(names)
@@ -369,8 +413,14 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["stop_sequences"] = list(cfg.stop_sequences)
                 # (limits likewise: one per request of the batch, or the batch's one int)
                 limit = [r.max_tokens for r in todo] if isinstance(max_tokens, list) else max_tokens
+                # (sampling parameters likewise: a list only where the batch carries one, so other calls are unchanged)
+                stop_kw.update(shared or {})
+                for name in ("top_p", "top_k", "min_p"):
+                    if getattr(todo[0], name) is not None:
+                        stop_kw[name] = [getattr(r, name) for r in todo]
+                temp = [r.temperature for r in todo] if isinstance(temperature, list) else temperature
                 texts, logprobs, stage_stats = stage.generate(prompts=[r.current_prompt for r in todo],
-                                                              max_tokens=limit, temperature=temperature,
+                                                              max_tokens=limit, temperature=temp,
                                                               return_logprobs=True, **stop_kw)
                 tables = (stage_stats or {}).get("top_logprobs") if cfg.logprobs else None
                 for j, r in enumerate(todo):

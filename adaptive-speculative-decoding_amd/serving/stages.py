@@ -88,6 +88,27 @@ equal-length prompts (seeds permuted with them); it is not promised across batch
 behaviour described above, with exactly the ops calls and generator use it had; greedy decoding makes no call and ignores the
 seed.  A bool, a float, a negative value, a value >= 2^64, a sequence of the wrong length or one that holds None raise ValueError.
 
+PER-REQUEST SAMPLING.  `generate(temperature=, top_p=, top_k=, min_p=)` each take one value for the call, as before, or one
+value per prompt: a batch is a set of independent requests (the reference's GenerationRequest carries temperature and top_p
+per request, src/serving/server.py:44-45,67; vLLM's SamplingParams and HF generate add top_k and min_p).  `top_k` (None = the
+configuration's) overrides StageConfig.top_k at stage 0 and target_top_k at a verifying stage, the rule top_p and min_p
+follow.  Off, per prompt: top_k <= 0 or >= vocabulary, top_p outside (0, 1), min_p == 0.  A sequence whose values are all equal
+is that one value, and a call without an unequal sequence makes exactly the ops calls it made before.  With any unequal
+sequence the call takes the ROWS route: the stage packs, once, a table `own` (each row's temperature with its own top-k / top-p
+/ min-p) and, at a verifying stage, a table `draft` (each row's temperature with the DRAFT stage's configured top_k / top_p /
+min_p), through ops.pack_sampling_rows (asd_sampling_rows_pack); per step it then calls ops.draft_sample_rows for every
+proposal (stage 0 with `own`, a verifying stage with `draft`), ops.verify_accept_rows(score, tok, lp_d, u, own),
+ops.residual_sample_lp_rows(..., own, d_threshold, t_threshold) and, with logprobs = N, ops.top_logprobs_rows with the rows'
+own temperatures.  Row b of such a call is computed as the call with row b's four values computes it (the kernels branch per
+workgroup into the select of the row's mode: the same bits), except that the verify of a row that truncates nothing runs the
+select kernel too and agrees with the plain verify kernel to 1e-5, not bit for bit.  Commits, stop handling, seeds, the kept
+step records and the host reads are unchanged; nothing new is read back inside a step.  A temperature sequence of zeros is the
+greedy call.  NOT BUILT: greedy and sampled rows in one call (a temperature sequence that mixes 0 with positive values raises
+ValueError; AdaptiveSpeculativePipeline.batch_process splits such a batch in two), per-request truncation of the DRAFT side
+(the proposals of a verifying stage use the draft stage's configuration), and serving/hierarchy.py's loop.  A bool, a NaN, a
+negative temperature, a min_p outside [0, 1], a non-integer top_k, a sequence of the wrong length or one that holds None raise
+ValueError before any launch.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -212,6 +233,60 @@ def _check_min_p(v, name: str = "min_p") -> float:
     return float(v)
 
 
+_NUMBER = (int, float, np.integer, np.floating)
+
+
+def _check_sampling_value(v, name: str):
+    """One temperature / top_p / top_k / min_p value of generate (module docstring, PER-REQUEST SAMPLING)."""
+    if name == "top_k":
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"top_k must be an integer, got {v!r}")
+        return int(v)
+    if name == "min_p":
+        return _check_min_p(v)
+    if isinstance(v, bool) or not isinstance(v, _NUMBER) or float(v) != float(v):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+    v = float(v)
+    if name == "temperature" and not v >= 0.0:
+        raise ValueError("temperature must be >= 0 (0: greedy decoding)")
+    return v
+
+
+def check_per_prompt(value, n: int, name: str):
+    """generate's `temperature` / `top_p` / `top_k` / `min_p`: None (returned as it is), one value for all `n` prompts, or a
+    sequence of n values.  -> the checked value, or a list of n checked values; a sequence whose values are all equal
+    collapses to that value."""
+    if value is None:
+        return None
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+    if isinstance(value, (Sequence, np.ndarray)):
+        vals = list(value)
+        if len(vals) != n:
+            raise ValueError(f"{len(vals)} {name} values for {n} prompts")
+        vals = [_check_sampling_value(v, name) for v in vals]          # (None inside a sequence raises here)
+        if vals and all(v == vals[0] for v in vals):
+            return vals[0]
+        return vals
+    return _check_sampling_value(value, name)
+
+
+class _RowsState:
+    """What a generate call on the rows route keeps (module docstring, PER-REQUEST SAMPLING): the packed tables, uploaded once.
+    `own`: each row's temperature with its own top-k / top-p / min-p; `draft` (verifying stages): each row's temperature with
+    the draft stage's configured truncation.  inv_t / top_k / top_p / min_p: the rows' values as lists."""
+
+    def __init__(self, ops, inv_t, top_k, top_p, min_p, draft_cfg, V: int, dtype, device):
+        # (a table is packed for the dtype of the logits it is used on: `draft` for the draft stage's)
+        n = len(inv_t)
+        self.inv_t, self.top_k, self.top_p, self.min_p = list(inv_t), list(top_k), list(top_p), list(min_p)
+        self.own = ops.pack_sampling_rows(self.inv_t, self.top_k, self.top_p, self.min_p, V, dtype, device)
+        self.draft = None
+        if draft_cfg is not None:
+            self.draft = ops.pack_sampling_rows(self.inv_t, [int(draft_cfg.top_k)] * n, [float(draft_cfg.top_p)] * n,
+                                                [float(draft_cfg.min_p)] * n, V, draft_cfg.dtype, device)
+
+
 def _check_seed(v) -> int:
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 64:
         raise ValueError(f"seed must be an integer in [0, 2^64), got {v!r}")
@@ -281,15 +356,19 @@ class _TopState:
     """What a generate call with logprobs = n > 0 keeps beside the token buffer: the [B, cap, n] tables the commit fills
     (positions count from the start of the row, prompt included, like `tokens`) and the step's two calls."""
 
-    def __init__(self, ops, n: int, inv_t: float, B: int, cap: int, device):
+    def __init__(self, ops, n: int, inv_t: float, B: int, cap: int, device, rows=None):
         self.ops, self.n, self.inv_t, self.cap = ops, n, inv_t, cap
+        self.rows = rows                                 # the rows route: the `own` table (every row's own temperature)
         self.ids = torch.full((B, cap, n), -1, dtype=torch.int32, device=device)
         self.lps = torch.full((B, cap, n), float("-inf"), dtype=torch.float32, device=device)
         self.step = None
 
     def score(self, logits: torch.Tensor) -> None:
         """logits: the rows the step commits from, [B, V] or [B, K+1, V], read where they are."""
-        self.step = self.ops.top_logprobs(logits, self.n, self.inv_t)
+        if self.rows is not None:
+            self.step = self.ops.top_logprobs_rows(logits, self.n, self.rows)
+        else:
+            self.step = self.ops.top_logprobs(logits, self.n, self.inv_t)
 
     def commit(self, seq_len: torch.Tensor, n_commit: torch.Tensor) -> None:
         """Behind the step's commit, which left seq_len and n_commit."""
@@ -365,12 +444,12 @@ class Stage:
 
     # ------------------------------------------------------------------------------------------ generate
     @torch.no_grad()
-    def generate(self, prompts: List[str], max_tokens=512, temperature: float = 0.7, return_logprobs: bool = True,
-                 top_p: Optional[float] = None, stop_token_ids: Optional[Sequence[int]] = None,
+    def generate(self, prompts: List[str], max_tokens=512, temperature=0.7, return_logprobs: bool = True,
+                 top_p=None, stop_token_ids: Optional[Sequence[int]] = None,
                  logprobs: Optional[int] = None,
-                 min_p: Optional[float] = None,
+                 min_p=None,
                  seed=None, stop_sequences=None,
-                 stop_sequences_per_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 stop_sequences_per_prompt=None, top_k=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -398,14 +477,29 @@ class Stage:
         committed token at which one of its sequences is complete in the GENERATED tokens; the matched tokens are kept.
         stats["stop_matches"][i] is the tuple of token ids that ended row i ((id,) for a stop id), or None for "length".
         A row's list -- stop ids, common sequences, its own -- holds at most 16 distinct entries (module docstring, HOW A ROW
-        ENDS)."""
+        ENDS).
+        `temperature`, `top_p`, `min_p` and `top_k` (None = the configuration's: StageConfig.top_k at stage 0, target_top_k at a
+        verifying stage) each take one value or one per prompt; unequal values select the rows route, where row i is sampled
+        with its own four values; a temperature sequence may not mix 0 with positive values (module docstring, PER-REQUEST
+        SAMPLING)."""
         t0 = time.perf_counter()
         prompts = list(prompts)
         self.step_inputs = []
         stop = _check_stop_ids(self.config.stop_token_ids if stop_token_ids is None else stop_token_ids, self.shape.vocab)
         n_top = _check_logprobs(self.config.logprobs if logprobs is None else logprobs)
+        n_prompts = len(prompts)
         own_min_p = self.config.min_p if self.draft is None else self.config.target_min_p
-        min_p = _check_min_p(own_min_p if min_p is None else min_p)
+        own_top_p = self.config.top_p if self.draft is None else self.config.target_top_p
+        own_top_k = self.config.top_k if self.draft is None else self.config.target_top_k
+        min_p = check_per_prompt(own_min_p if min_p is None else min_p, n_prompts, "min_p")
+        top_p = check_per_prompt(top_p, n_prompts, "top_p")
+        top_k = check_per_prompt(top_k, n_prompts, "top_k")
+        if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
+            temperature = check_per_prompt(temperature, n_prompts, "temperature")
+            if isinstance(temperature, list) and any(t == 0.0 for t in temperature):
+                raise ValueError("greedy (temperature 0) and sampled rows cannot share one generate call: split the batch")
+        elif isinstance(temperature, bool):
+            raise ValueError(f"temperature must be a number, got {temperature!r}")
         seeds = check_seeds(seed, len(prompts))
         max_tokens = check_max_tokens(max_tokens, len(prompts))
         common = _check_stop_sequences(self.config.stop_sequences if stop_sequences is None else stop_sequences,
@@ -428,7 +522,7 @@ class Stage:
         if not prompts or max_tokens <= 0:
             return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
-        if not temperature >= 0.0:                       # (NaN included)
+        if not isinstance(temperature, list) and not temperature >= 0.0:     # (NaN included; a list was checked above)
             raise ValueError("temperature must be >= 0 (0: greedy decoding)")
         ids = self.encode_prompts(prompts)
         B, P = ids.shape
@@ -436,8 +530,20 @@ class Stage:
             end = _FinishState(row_seqs, limits, P, ids.device)
         else:
             end = _StopState(stop, B, ids.device) if stop else None
+        rows = None
+        if not isinstance(temperature, list) and temperature == 0.0:
+            pass                                         # greedy: no draws, no truncation, no table
+        elif any(isinstance(v, list) for v in (temperature, top_p, top_k, min_p)):
+            # the rows route (module docstring, PER-REQUEST SAMPLING): every row's four values, the tables packed once
+            per_row = lambda v, default: list(v) if isinstance(v, list) else [default if v is None else v] * B   # noqa: E731
+            temps = per_row(temperature, None)
+            rows = _RowsState(self.ops, [float(np.float32(1.0 / t)) for t in temps], per_row(top_k, int(own_top_k)),
+                              per_row(top_p, float(own_top_p)), per_row(min_p, 0.0),
+                              None if self.draft is None else self.draft.config, self.shape.vocab, self.config.dtype, ids.device)
+            temperature = temps[0]                       # (positive: the scalar below only selects the sampled loops)
         inv_t = 1.0 if temperature == 0.0 else float(np.float32(1.0 / temperature))
-        top = _TopState(self.ops, n_top, inv_t, B, P + int(max_tokens), ids.device) if n_top else None
+        top = _TopState(self.ops, n_top, inv_t, B, P + int(max_tokens), ids.device,
+                        None if rows is None else rows.own) if n_top else None
         rng = None
         if seeds is not None and temperature != 0.0:
             rng = _SeedState(self.ops, seeds, self.index, 1 if self.draft is None else self.config.draft_len, ids.device)
@@ -446,12 +552,12 @@ class Stage:
             tokens, lps, seq_len = decode(ids, int(max_tokens), end, top)
         elif self.draft is None:
             tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
-                                                      self.config.top_p if top_p is None else float(top_p), end, top, min_p,
-                                                      rng)
+                                                      self.config.top_p if top_p is None or rows else float(top_p), end, top,
+                                                      0.0 if rows else min_p, rng, None if rows else top_k, rows)
         else:
             tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
-                                                            self.config.target_top_p if top_p is None else float(top_p), end, top,
-                                                            min_p, rng)
+                                                            self.config.target_top_p if top_p is None or rows else float(top_p),
+                                                            end, top, 0.0 if rows else min_p, rng, None if rows else top_k, rows)
         self.ops.check_status()
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
@@ -487,16 +593,21 @@ class Stage:
         n_commit = torch.zeros((B,), dtype=torch.int32, device=dev)
         return tokens, lps, seq_len, n_commit
 
-    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float, min_p: float = 0.0, r=None):
+    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float, min_p: float = 0.0, r=None,
+                 top_k: Optional[int] = None, table=None):
         """One proposal per sequence from next-token logits [B, V] under Temperature -> (TopK ->) TopP (-> MinP): (tok i32,
-        log q(tok), threshold).  r: the [B] uniforms of a seeded call; None: drawn from the stage's generator."""
+        log q(tok), threshold).  r: the [B] uniforms of a seeded call; None: drawn from the stage's generator.  top_k: None =
+        cfg.top_k.  table: the rows route's packed table -- every row under its own parameters, the scalars unused."""
         logits = logits.contiguous()
         if r is None:
             r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device)
+        if table is not None:
+            return self.ops.draft_sample_rows(logits, r, table)
+        top_k = cfg.top_k if top_k is None else top_k
         if min_p > 0.0:
-            return self.ops.draft_sample_min_p(logits, r, inv_t, top_k=cfg.top_k, top_p=top_p, min_p=min_p)
-        if cfg.top_k > 0:
-            return self.ops.draft_sample_top_k(logits, r, inv_t, top_k=cfg.top_k, top_p=top_p)
+            return self.ops.draft_sample_min_p(logits, r, inv_t, top_k=top_k, top_p=top_p, min_p=min_p)
+        if top_k > 0:
+            return self.ops.draft_sample_top_k(logits, r, inv_t, top_k=top_k, top_p=top_p)
         return self.ops.draft_sample(logits, r, inv_t, top_p)
 
     def _commit(self, end, tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap):
@@ -511,7 +622,7 @@ class Stage:
                                       end.finished, end.n_finished)
 
     def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None, top=None,
-                      min_p: float = 0.0, rng=None):
+                      min_p: float = 0.0, rng=None, top_k: Optional[int] = None, per_row=None):
         """Stage 0.  Without a stop set every sequence appends exactly one token per step, so all positions are known on the
         host; with one (`end`), a sequence is fed its last committed token at seq_len - 1, which is the same for a running
         sequence and stays put for a finished one."""
@@ -527,7 +638,7 @@ class Stage:
         for step in range(max_tokens):
             logits = logits.contiguous()
             r = None if rng is None else rng.step(step, 1, 0, False)[0][0]      # seeded: the step's one launch
-            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p, min_p, r)
+            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p, min_p, r, top_k, None if per_row is None else per_row.own)
             if top is not None:
                 top.score(logits)
             self._commit(end, None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
@@ -660,7 +771,7 @@ class Stage:
         return lp_t, n_acc, None
 
     def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None, top=None,
-                            target_min_p: float = 0.0, rng=None):
+                            target_min_p: float = 0.0, rng=None, target_top_k: Optional[int] = None, per_row=None):
         """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
 
         Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
@@ -671,6 +782,8 @@ class Stage:
         B, P = ids.shape
         dev = ids.device
         Kd = cfg.draft_len
+        if target_top_k is None:
+            target_top_k = cfg.target_top_k
         cap = P + max_tokens
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -692,7 +805,8 @@ class Stage:
             toks, lpd, dls, thrs = [], [], [], []
             for k in range(Kd):
                 dl = dl.contiguous()
-                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p, dcfg.min_p, None if rd is None else rd[k])
+                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p, dcfg.min_p, None if rd is None else rd[k],
+                                           table=None if per_row is None else per_row.draft)
                 toks.append(t)
                 lpd.append(lp)
                 thrs.append(thr)
@@ -707,14 +821,21 @@ class Stage:
             bonus = t_out[:, Kd].contiguous()
             if rng is None:
                 u = torch.rand((B, Kd), generator=self.gen, device=dev)
-            lp_t, n_acc, t_thr = self._verify(score, tok32, lp_d, u, inv_t, cfg.target_top_k, target_top_p, target_min_p)
+            if per_row is not None:                         # every row against its own target distribution
+                lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_rows(score, tok32, lp_d, u, per_row.own)
+            else:
+                lp_t, n_acc, t_thr = self._verify(score, tok32, lp_d, u, inv_t, target_top_k, target_top_p, target_min_p)
             if rng is None:
                 r = torch.rand((B,), generator=self.gen, device=dev)
-            # (the min_p keyword only where it is on: with it off the call is the one made before)
-            mp = dict(min_p=target_min_p) if target_min_p > 0.0 else {}
-            drawn, lp_drawn = self.ops.residual_sample_lp(score, torch.stack(dls, 1).to(score.dtype).contiguous(), n_acc, r, bonus,
-                                                          inv_t, d_threshold=d_thr, t_threshold=t_thr, top_k=cfg.target_top_k,
-                                                          top_p=target_top_p, **mp)
+            d_rows = torch.stack(dls, 1).to(score.dtype).contiguous()
+            if per_row is not None:
+                drawn, lp_drawn = self.ops.residual_sample_lp_rows(score, d_rows, n_acc, r, bonus, per_row.own, d_threshold=d_thr,
+                                                                   t_threshold=t_thr)
+            else:
+                # (the min_p keyword only where it is on: with it off the call is the one made before)
+                mp = dict(min_p=target_min_p) if target_min_p > 0.0 else {}
+                drawn, lp_drawn = self.ops.residual_sample_lp(score, d_rows, n_acc, r, bonus, inv_t, d_threshold=d_thr,
+                                                              t_threshold=t_thr, top_k=target_top_k, top_p=target_top_p, **mp)
             if self.keep_inputs:
                 self.step_inputs.append(dict(logits=score.clone(), bonus=bonus.clone(), tok=tok32.clone(), lp_d=lp_d.clone(),
                                              u=u.clone(), lp_t=lp_t.clone(), n_acc=n_acc.clone(), drawn=drawn.clone(),

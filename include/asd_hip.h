@@ -426,6 +426,16 @@ int asd_top_logprobs(const void* logits, int dtype, int64_t ld_seq, int64_t ld_r
                      float inv_temperature, int N, int splits /*workgroups per row, 0 = heuristic*/,
                      int32_t* top_id /*[B,K1,N] out*/, float* top_lp /*[B,K1,N] out*/,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* asd_top_logprobs_rows: asd_top_logprobs with one temperature per SEQUENCE (per-request sampling parameters, below):
+ * inv_temperature is a DEVICE array [B]; the rows of sequence b are scaled by c2 = (float)(log2(e) * (double)inv_temperature[b]),
+ * formed on the device by the one f64 product the host forms it with, so a sequence returns the bits asd_top_logprobs returns
+ * for it with that scalar at the same `splits`.  The values cannot be checked by the launcher: every one must be finite and
+ * > 0.  NULL inv_temperature (with B > 0): invalid argument, reported where asd_top_logprobs reports a bad scalar; every other
+ * argument, status code and the workspace are asd_top_logprobs'. */
+int asd_top_logprobs_rows(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                          const float* inv_temperature /*[B], device*/, int N, int splits,
+                          int32_t* top_id /*[B,K1,N] out*/, float* top_lp /*[B,K1,N] out*/,
+                          void* workspace, size_t workspace_bytes, void* stream);
 /* The table of a step follows the step's commit (RESEARCH_PROTOCOL.md:272-277: one [N] row per GENERATED token).  Runs behind
  * asd_commit_step_lp / asd_commit_step_stop of the same step and reads their outputs: seq_len[b] AFTER the commit and
  * n_commit[b].  For j < min(n_commit[b], K1):  out[b, seq_len[b] - n_commit[b] + j, :] = top[b, j, :]  (ids and log-probs;
@@ -769,6 +779,69 @@ int asd_residual_sample_lp_min_p(const void* t_logits, int64_t ld_t, const void*
                                  const float* t_threshold /*[B,K]*/, const float* d_threshold /*[B,K] or NULL*/,
                                  int32_t* token /*[B] out*/, float* lp /*[B] out*/,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-sequence sampling parameters: a batch is a set of independent requests, each with its own temperature, top-k, top-p
+ * and min-p (the reference's GenerationRequest carries temperature and top_p per request, src/serving/server.py:44-45,67;
+ * vLLM's SamplingParams and HF generate add top_k and min_p).  The scalar entry points above bake c2, levels, top_k and
+ * delta into one parameter block per launch; the *_rows entry points below read them per SEQUENCE from a packed table.
+ *
+ * asd_sampling_rows_pack (host pointers, like asd_mlp_pack_weights) writes B rows of ASD_SAMPLING_ROW_BYTES:
+ *   +0  f32 c2        (float)(log2(e) * (double)inv_temperature[b])
+ *   +4  f32 top_p     top_p[b] (1 without the array); used by the mass select where levels > 0
+ *   +8  i32 levels    0 when top_p[b] is outside (0, 1), else 2 (16-bit logits) or 3 (f32): why the table is per dtype
+ *   +12 i32 top_k     top_k[b] where 0 < top_k[b] < V, else 0: why it is per V
+ *   +16 f32 delta     (float)(log((double)min_p[b]) / (double)inv_temperature[b]) where min_p[b] > 0, else -inf
+ *   +20 u32 clamp     1 where min_p[b] > 0 (the row takes the min-p select and its "lp a rounding above 0 reads as 0" rule)
+ *   +24 8 bytes reserved (zero)
+ * formed by the very host functions the scalar launchers call: a row holds the bits a scalar launch with its four values
+ * would use.  NULL top_k / top_p / min_p = off for every sequence.  Status: B < 0, V < 1, NULL inv_temperature or packed (with
+ * B > 0), an inv_temperature that is not finite and > 0, a NaN top_p, a min_p that is NaN or > 1: invalid argument; an unknown
+ * dtype: unsupported.  The caller copies the table to the device once (per generate call) and hands that copy to the kernels,
+ * which index it by sequence b (the verify by b = row / K); it must stay alive and unchanged until they have run.
+ *
+ * Semantics: sequence b of a *_rows call is the scalar min-p entry point called with b's four values -- through the off
+ * switches (top_k <= 0 or >= V; top_p outside (0, 1); min_p <= 0) the top-k, top-p or plain entry point -- and returns its
+ * bits: thresholds, lp / lp_target, n_finite, the commit draw's lp and the tokens (the draft's token: that of the
+ * one-workgroup form, which the scalar call takes by itself whenever top-k or min-p is on).  Every kernel takes a
+ * workgroup-uniform branch on the sequence's mode into the instantiation of the ONE select body the scalar kernel of that mode
+ * runs.  One exception: a sequence that truncates nothing is verified by the same select kernel with levels = 0 -- not by
+ * asd_verify_accept_ex's streaming kernel -- so its lp_target is the select's sweep-1 normaliser (the bits asd_draft_sample
+ * reports as lp for that token), its t_nucleus_logit is -inf, and it agrees with asd_verify_accept_ex to 1e-5 against f64,
+ * not bit for bit.  Mixing is per sequence, never per row of a sequence.
+ * Status: a NULL table (with rows to process) is an invalid argument; everything else is checked as by the min-p entry point
+ * with a live bound (whole 16-byte vectors, 16-byte aligned rows, V*sizeof(elem) <= 2 MiB at every B).  The table's contents
+ * are not checked by the device entry points.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_SAMPLING_ROW_BYTES 32
+size_t asd_sampling_rows_bytes(int B);     /* B * ASD_SAMPLING_ROW_BYTES; 0 when B <= 0 */
+int asd_sampling_rows_pack(const float* inv_temperature /*host [B]*/, const int32_t* top_k /*host [B] or NULL = off*/,
+                           const float* top_p /*host [B] or NULL = off*/, const float* min_p /*host [B] or NULL = off*/,
+                           int B, int V, int dtype, void* packed /*host out*/);
+/* asd_draft_sample_rows: asd_draft_sample_min_p with sequence b's parameters from rows[b].  ONE launch of one 1024-lane
+ *   workgroup per row at every B; `workspace` is accepted and left untouched. */
+int asd_draft_sample_rows(const void* logits, int64_t ld, int dtype, const float* r /*[B]*/, int B, int V,
+                          const void* rows /*device, asd_sampling_rows_pack*/, int32_t* tok /*[B] out*/,
+                          float* lp /*[B] out, may be NULL*/, float* threshold /*[B] out, may be NULL*/,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* asd_verify_accept_rows: asd_verify_accept_min_p with the parameters of rows[b] for the K rows of sequence b.  The two
+ *   launches of the truncated verify at every B, for every row (the untruncated-sequence exception above); no workspace. */
+int asd_verify_accept_rows(const void* logits, int dtype, int64_t ld_row,
+                           const int32_t* tok /*[B,K]*/, const float* lp_draft /*[B,K]*/, const float* u /*[B,K]*/,
+                           int B, int K, int V, const void* rows /*device*/,
+                           float* lp_target /*[B,K] out*/, uint8_t* accept /*[B,K] out*/, int32_t* n_acc /*[B] out*/,
+                           uint64_t* accept_bits /*[B] out, may be NULL*/, float* t_nucleus_logit /*[B,K] out, may be NULL*/,
+                           int32_t* n_finite /*[B] out, may be NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+/* asd_residual_sample_lp_rows: asd_residual_sample_lp_min_p with the parameters of rows[b]: t_threshold =
+ *   asd_verify_accept_rows' t_nucleus_logit (-inf on an untruncated sequence: the whole row), d_threshold = the draft draws',
+ *   the bonus row's threshold found here by the select of rows[b].  workspace: asd_residual_sample_top_p_workspace_bytes,
+ *   always; the geometry choice of asd_residual_sample_lp_min_p. */
+int asd_residual_sample_lp_rows(const void* t_logits, int64_t ld_t, const void* d_logits, int64_t ld_d,
+                                const void* bonus_logits, int64_t ld_b, int dtype,
+                                const int32_t* n_acc /*[B]*/, const float* r /*[B]*/, int B, int K, int V,
+                                const void* rows /*device*/, const float* t_threshold /*[B,K]*/,
+                                const float* d_threshold /*[B,K] or NULL*/, int32_t* token /*[B] out*/, float* lp /*[B] out*/,
+                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* N1, second form: asd_verify_accept with the epilogue of asd_predictor_stop run INSIDE the same
  * launch by the wave that completes each sequence (lp = the kernel's own lp_target, all K
