@@ -195,21 +195,25 @@ def test_hip_decoder_matches_torch_modules_and_fp32():
         assert eh <= max(2.0 * et, 0.02 * scale), (eh, et, scale)
 
 
-def test_decoder_forward_equals_the_composition_of_its_parts():
+@pytest.mark.parametrize("Bn,T", [(3, 5), (13, 5), (32, 9), (33, 9)],
+                         ids=["M15-skinny", "M65-tile", "M288-tall", "M297-two_row_blocks"])
+def test_decoder_forward_equals_the_composition_of_its_parts(Bn, T):
     """asd_decoder_forward lets the kernel after a sliced projection add the f32 partials itself; the exported parts, called
-    one by one with asd_linear_ex's own reduce kernel in between, must give the same bits."""
+    one by one with asd_linear_ex's own reduce kernel in between, must give the same bits -- at one row count per form of the
+    linear launcher (M <= 64, <= 256, <= 288, more)."""
     SL = import_module("adaptive-speculative-decoding_amd.serving.synthetic_lm")
     K_ = import_module("adaptive-speculative-decoding_amd.kernels")
     lib, Bd = _lib(), _B()
     shape = _small_shape()
     lm = SL.SyntheticLM(shape, dtype=BF, device="cuda", seed=6)
     lm.enable_hip_layers()
-    Bn, T, t_max = 3, 5, 64
+    t_max = 64
     lm.alloc_ragged(Bn, t_max)
     hd = lm._hip
     g = _gen(2)
     ids = torch.randint(0, shape.vocab, (Bn, T), generator=g, device="cuda")
-    pos0 = torch.tensor([0, 7, 30], device="cuda")
+    pos0 = torch.randint(0, t_max - T, (Bn,), generator=g, device="cuda")             # <= t_max - T - 1: the trash slot stays out
+    pos0[0] = 0
     # the composition, on its own caches
     M = Bn * T
     x = lm.embed(ids).view(M, shape.hidden).clone()
@@ -235,8 +239,11 @@ def test_decoder_forward_equals_the_composition_of_its_parts():
         K_.linear(act, blk.down.weight, workspace=ws, out=x, residual=x)
     want = torch.empty_like(x)
     _check(lib.asd_rmsnorm(x.data_ptr(), shape.hidden, lm.norm.weight.data_ptr(), shape.rms_eps, Bd.DTYPE_BF16, M, shape.hidden, want.data_ptr(), shape.hidden, None), "asd_rmsnorm")
-    got = lm.forward_ragged(ids, pos0, 40, return_hidden=True)
-    assert lib.asd_linear_slices(M, shape.hidden, shape.hidden) > 1           # the fused consumers really ran
+    got = lm.forward_ragged(ids, pos0, t_max, return_hidden=True)
+    plans = [lib.asd_linear_slices(M, N, D) for N, D in ((shape.hidden + 2 * kv, shape.hidden), (shape.hidden, shape.hidden),
+                                                         (2 * shape.intermediate, shape.hidden), (shape.hidden, shape.intermediate))]
+    print(f"M = {M}: slices of q|k|v, o, gate|up, down = {plans}")
+    assert max(plans) > 1                                                      # fused consumers really ran
     assert torch.equal(got.view(M, shape.hidden), want)
 
 
