@@ -21,6 +21,7 @@ MAX_DRAFT_LEN = 64
 MAX_STAGES = 16
 MAX_SPLITS = 64
 MAX_TOP_LOGPROBS = 8
+MAX_LOGIT_EDITS = 1024
 MAX_STOP_SEQS, MAX_STOP_SEQ_LEN = 16, 8
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
@@ -107,6 +108,7 @@ SIGNATURES = {
                                     _vp]),
     "asd_commit_top_logprobs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "asd_step_uniforms": (_i, [_vp, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "asd_logit_edit_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "asd_logprob_stats": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     "asd_mlp_packed_floats": (_sz, [_i, _i]),
     "asd_mlp_pack_weights": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -408,6 +408,19 @@ class HipOps:
         self.K.step_uniforms(seeds, step, stage, r_draft, u, r_commit)
         return r_draft, u, r_commit
 
+    def pack_logit_edits(self, rows, device):
+        """One list of (id, bias, until) per batch row -> the device arrays of logit_edit_rows (kernels.pack_logit_edits: checked
+        on the host, uploaded once per generate call; equal lists are uploaded once, without row_first)."""
+        return self.K.pack_logit_edits(rows, device)
+
+    @traced("logit_edit_rows")
+    def logit_edit_rows(self, logits, edits, seq_len, start, offset: int = 0):
+        """The sparse in-place logit edit ahead of the samplers (asd_logit_edit_rows): logits [B, V] or [B, K1, V] (any strides
+        with a unit last stride) -> the same tensor, edited: for every entry (id, bias, until) of row b at position j, with
+        g = seq_len[b] - start + offset + j, element id is -inf while g < until and x + bias (one rounding) afterwards.  One
+        launch, no workspace; a stage loop makes the call once per logits tensor and only when the call has an entry."""
+        return self.K.logit_edit_rows(logits, edits, seq_len, start, offset)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

@@ -1162,3 +1162,81 @@ def step_uniforms(seeds: torch.Tensor, step: int, stage: int, r_draft: Optional[
                                   _opt(r_draft, "r_draft", torch.float32), _opt(u, "u", torch.float32),
                                   _opt(r_commit, "r_commit", torch.float32), _stream())
     B.check("asd_step_uniforms", rc)
+
+
+# ------------------------------------------------------------------------------- logit edits (logit_bias, banned ids, min_tokens)
+MAX_LOGIT_EDITS = B.MAX_LOGIT_EDITS
+EDIT_FOREVER = 2 ** 31 - 1                   # `until` of a permanent ban
+
+
+@dataclass
+class LogitEdits:
+    """The entry arrays of asd_logit_edit_rows on the device (pack_logit_edits): edit_id i32 [n], edit_bias f32 [n],
+    edit_until i32 [n]; row_first i32 [B+1], or None when every row owns the entries [0, n) (n_shared = n)."""
+    edit_id: torch.Tensor
+    edit_bias: torch.Tensor
+    edit_until: torch.Tensor
+    row_first: Optional[torch.Tensor]
+    n: int                                   # entries uploaded
+    B: int                                   # rows the lists were packed for
+
+
+def check_logit_edit_rows(rows):
+    """The host side of pack_logit_edits: `rows` = one list of (id, bias, until) per batch row -> (flat entries, row_first list
+    or None when all rows hold equal lists).  Inside a row the ids must be distinct
+    (the kernel's packing contract), at most MAX_LOGIT_EDITS of them; a bias is finite; 0 <= until <= INT32_MAX."""
+    lists = [[(int(i), float(b), int(u)) for i, b, u in r] for r in rows]
+    for r, entries in enumerate(lists):
+        if len(entries) > MAX_LOGIT_EDITS:
+            raise ValueError(f"row {r} owns {len(entries)} logit edits, at most {MAX_LOGIT_EDITS}")
+        if len({e[0] for e in entries}) != len(entries):
+            raise ValueError(f"the logit edits of row {r} name a token id twice")
+        for i, b, u in entries:
+            if not -2 ** 31 <= i < 2 ** 31 or not 0 <= u <= EDIT_FOREVER:
+                raise ValueError("logit edit ids must fit int32 and `until` must lie in [0, 2^31)")
+            if b != b or b in (float("inf"), float("-inf")):
+                raise ValueError("a logit bias must be finite")
+    if lists and all(r == lists[0] for r in lists):
+        return lists[0], None
+    first = [0]
+    for entries in lists:
+        first.append(first[-1] + len(entries))
+    return [e for entries in lists for e in entries], first
+
+
+def pack_logit_edits(rows, device) -> LogitEdits:
+    """The entry arrays of logit_edit_rows from host lists, checked BEFORE anything is uploaded: `rows` holds one list of
+    (id, bias, until) per batch row (a row's list may be empty).  When all rows hold equal lists one copy is uploaded and
+    row_first is None (the way pack_stop_sequences treats a shared list)."""
+    rows = list(rows)
+    flat, first = check_logit_edit_rows(rows)
+    return LogitEdits(torch.tensor([e[0] for e in flat], dtype=torch.int32).to(device),
+                      torch.tensor([e[1] for e in flat], dtype=torch.float32).to(device),
+                      torch.tensor([e[2] for e in flat], dtype=torch.int32).to(device),
+                      None if first is None else torch.tensor(first, dtype=torch.int32).to(device), len(flat), len(rows))
+
+
+def logit_edit_rows(logits: torch.Tensor, edits: LogitEdits, seq_len: torch.Tensor, start: int, offset: int = 0) -> torch.Tensor:
+    """Edit `logits` in place (asd_logit_edit_rows) and return it: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  For every entry (id, bias, until) of row b and every position j, with
+    g = seq_len[b] - start + offset + j: logits[b, j, id] = -inf while g < until, else += bias (one rounding; bias 0 stores
+    nothing).  seq_len i32 [B]: the step's lengths BEFORE its commit; start: the prompt length."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if edits.B != Bv or tuple(seq_len.shape) != (Bv,):
+        raise ValueError(f"the edits were packed for {edits.B} rows and seq_len must be int32 [B]; logits have {Bv} rows")
+    # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
+    ld_row = view.stride(1) if K1 > 1 else V
+    ld_seq = view.stride(0) if Bv > 1 else K1 * ld_row
+    if ld_row < V or ld_seq < K1 * ld_row:
+        raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= K1 row strides")
+    rc = _lib().asd_logit_edit_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
+                                    _dev(edits.edit_id, "edit_id", torch.int32), _dev(edits.edit_bias, "edit_bias", torch.float32),
+                                    _dev(edits.edit_until, "edit_until", torch.int32), _opt(edits.row_first, "row_first", torch.int32),
+                                    edits.n, _dev(seq_len, "seq_len", torch.int32), int(start), int(offset), _stream())
+    B.check("asd_logit_edit_rows", rc)
+    return logits

@@ -28,6 +28,12 @@ calls without them are the calls made before (serving/stages.py, PER-REQUEST SAM
 (temperature 0) and sampled rows: `batch_process` runs such a batch as a greedy and a sampled sub-batch -- the one place mixing
 is handled -- and returns the results in request order.
 
+Logit edits (OpenAI's `logit_bias`, vLLM's `bad_words` / `min_tokens`; serving/stages.py, LOGIT EDITS): `batch_process(logit_bias=,
+banned_token_ids=, min_tokens=)` take one value for the batch -- a dict, a sequence of token ids, an int -- or one per request
+(a sequence of dicts / Nones, a sequence of id sequences, a sequence of ints), and `process_request` takes the same three for its
+one request.  A per-request value travels with the request like its `top_p`; a keyword reaches `stage.generate` only when it was
+given.  The values are checked by the stage (which knows the vocabulary); only the per-request lengths are checked here.
+
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
                      p_i = predictor.predict(...)  (1.0 at the last stage)        :225-241
@@ -69,9 +75,43 @@ import numpy as np
 
 from ..backend import get_backend
 from .cache import RequestCache
-from .stages import check_max_tokens, check_per_prompt, check_seeds
+from .stages import _is_seq, check_max_tokens, check_per_prompt, check_seeds
 
 logger = logging.getLogger(__name__)
+
+_EDIT_KEYS = ("logit_bias", "banned_token_ids", "min_tokens")
+
+
+def check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n: int) -> Dict[str, Any]:
+    """The three logit-edit keywords of batch_process -> {name: value} of those that were given: a `list` of n values where
+    the batch carries one per request, anything else (a dict, a tuple of ids, an int) is one value for the batch.  Only the
+    shapes are looked at here; stage.generate checks the values."""
+    out: Dict[str, Any] = {}
+    if logit_bias is not None:
+        if _is_seq(logit_bias):
+            if len(logit_bias) != n:
+                raise ValueError(f"{len(logit_bias)} logit_bias dicts for {n} requests")
+            out["logit_bias"] = list(logit_bias)
+        else:
+            out["logit_bias"] = logit_bias
+    if banned_token_ids is not None:
+        if not _is_seq(banned_token_ids):
+            raise ValueError(f"banned_token_ids must be a sequence of token ids or one sequence per request, got {banned_token_ids!r}")
+        vals = list(banned_token_ids)
+        if any(_is_seq(v) or v is None for v in vals):
+            if len(vals) != n:
+                raise ValueError(f"{len(vals)} banned_token_ids lists for {n} requests")
+            out["banned_token_ids"] = vals
+        else:
+            out["banned_token_ids"] = tuple(vals)
+    if min_tokens is not None:
+        if _is_seq(min_tokens):
+            if len(min_tokens) != n:
+                raise ValueError(f"{len(min_tokens)} min_tokens values for {n} requests")
+            out["min_tokens"] = list(min_tokens)
+        else:
+            out["min_tokens"] = min_tokens
+    return out
 
 DEFAULT_STAGE_NAMES = ("8b", "13b", "34b", "70b")          # pipeline.py:175
 
@@ -169,6 +209,7 @@ class _Active:
     top_p: Optional[float] = None
     top_k: Optional[int] = None
     min_p: Optional[float] = None
+    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -200,14 +241,22 @@ class AdaptiveSpeculativePipeline:
     # ------------------------------------------------------------------ public API
     def process_request(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
                         request_id: Optional[str] = None, seed: Optional[int] = None, top_p: Optional[float] = None,
-                        top_k: Optional[int] = None, min_p: Optional[float] = None) -> RequestResult:
+                        top_k: Optional[int] = None, min_p: Optional[float] = None, logit_bias=None, banned_token_ids=None,
+                        min_tokens=None) -> RequestResult:
         """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring).
         top_p / top_k / min_p: None = every stage's configuration, else the request's own value at every stage
-        (stage.generate(top_p=, top_k=, min_p=))."""
+        (stage.generate(top_p=, top_k=, min_p=)).  logit_bias (a dict) / banned_token_ids (token ids) / min_tokens (an int):
+        None = every stage's configuration, else handed to every stage.generate call (module docstring, Logit edits)."""
         if seed is not None and not isinstance(seed, (int, np.integer)):
             raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
         sampling = {k: check_per_prompt(v, 1, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
-        return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1), sampling=sampling)[0]
+        edits = {k: v for k, v in zip(_EDIT_KEYS, (logit_bias, banned_token_ids, min_tokens)) if v is not None}
+        if _is_seq(edits.get("banned_token_ids")):
+            edits["banned_token_ids"] = tuple(edits["banned_token_ids"])         # (one value for the batch of one, never a list)
+        if _is_seq(edits.get("logit_bias")) or _is_seq(edits.get("min_tokens")):
+            raise ValueError("process_request takes one logit_bias dict and one min_tokens int")
+        return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1), sampling=sampling,
+                               edits=edits)[0]
 
     async def process_request_async(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
                                     request_id: Optional[str] = None, seed: Optional[int] = None) -> RequestResult:
@@ -216,19 +265,23 @@ class AdaptiveSpeculativePipeline:
                                           request_id, seed)
 
     def batch_process(self, prompts: List[str], max_tokens=512, temperature=0.7,
-                      seeds=None, top_p=None, top_k=None, min_p=None) -> List[RequestResult]:
+                      seeds=None, top_p=None, top_k=None, min_p=None, logit_bias=None, banned_token_ids=None,
+                      min_tokens=None) -> List[RequestResult]:
         """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
         raises ValueError); request i keeps seeds[i] through every regrouping (module docstring).  max_tokens: an int, or one
         int >= 1 per request, kept by the request in the same way.
         temperature, top_p, top_k, min_p: one value for the batch (None: every stage's configuration), or one per request,
         kept by the request through every regrouping and handed to stage.generate as a list only where the batch has one
         (serving/stages.py, PER-REQUEST SAMPLING).  A stage call cannot mix greedy (temperature 0) and sampled rows: a batch
-        whose temperatures do is run as a greedy and a sampled sub-batch here, and the results come back in request order."""
+        whose temperatures do is run as a greedy and a sampled sub-batch here, and the results come back in request order.
+        logit_bias, banned_token_ids, min_tokens: None (the keyword is not handed to the stages), one value for the batch, or
+        one per request, kept by the request through every regrouping (module docstring, Logit edits)."""
         prompts = list(prompts)
         n = len(prompts)
         seeds = check_seeds(seeds, n)
         max_tokens = check_max_tokens(max_tokens, n)
         sampling = {k: check_per_prompt(v, n, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
+        edits = check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n)
         if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
             temperature = check_per_prompt(temperature, n, "temperature")
         if isinstance(temperature, list) and any(t == 0.0 for t in temperature):
@@ -238,12 +291,12 @@ class AdaptiveSpeculativePipeline:
                 idx = [i for i, t in enumerate(temperature) if (t == 0.0) == greedy]
                 pick = lambda v: [v[i] for i in idx] if isinstance(v, list) else v      # noqa: E731
                 out = self.batch_process([prompts[i] for i in idx], pick(max_tokens), pick(temperature), pick(seeds),
-                                         **{k: pick(v) for k, v in sampling.items()})
+                                         **{k: pick(v) for k, v in sampling.items()}, **{k: pick(v) for k, v in edits.items()})
                 for i, r in zip(idx, out):
                     results[i] = r
             return results  # type: ignore[return-value]
         if self.config.batch_grouping != "predicted_stage" or n < 2 or self.config.stop_rule == "prefix":
-            return self._run_batch(prompts, max_tokens, temperature, [None] * n, seeds=seeds, sampling=sampling)
+            return self._run_batch(prompts, max_tokens, temperature, [None] * n, seeds=seeds, sampling=sampling, edits=edits)
         pred = self.predict_stop_stages(prompts)
         results = [None] * n
         for stage in sorted(set(pred.tolist())):                       # shallowest group first
@@ -252,7 +305,8 @@ class AdaptiveSpeculativePipeline:
             out = self._run_batch([prompts[i] for i in idx], pick(max_tokens), pick(temperature),
                                   [None] * len(idx),
                                   predicted=[int(stage)] * len(idx), seeds=None if seeds is None else [seeds[i] for i in idx],
-                                  sampling={k: pick(v) for k, v in sampling.items()})
+                                  sampling={k: pick(v) for k, v in sampling.items()},
+                                  edits={k: pick(v) for k, v in edits.items()})
             for i, r in zip(idx, out):
                 results[i] = r
         return results  # type: ignore[return-value]
@@ -337,7 +391,8 @@ class AdaptiveSpeculativePipeline:
     # ------------------------------------------------------------------ the stage loop, batched
     def _run_batch(self, prompts: List[str], max_tokens, temperature,
                    request_ids: List[Optional[str]], predicted: Optional[List[int]] = None,
-                   seeds: Optional[List[int]] = None, sampling: Optional[Dict[str, Any]] = None) -> List[RequestResult]:
+                   seeds: Optional[List[int]] = None, sampling: Optional[Dict[str, Any]] = None,
+                   edits: Optional[Dict[str, Any]] = None) -> List[RequestResult]:
         now = time.time()
         reqs = [_Active(request_id=rid or str(uuid.uuid4()), prompt=p, current_prompt=p, start_time=now)
                 for p, rid in zip(prompts, request_ids)]
@@ -357,6 +412,13 @@ class AdaptiveSpeculativePipeline:
             if isinstance(v, list):
                 for r, x in zip(reqs, v):
                     setattr(r, name, x)
+        # logit edits likewise: a list is one value per request, anything else is the batch's one value
+        for name, v in (edits or {}).items():
+            if isinstance(v, list):
+                for r, x in zip(reqs, v):
+                    r.edits[name] = x
+            else:
+                shared[name] = v
         for r in reqs:
             self.active_requests[r.request_id] = {"start_time": r.start_time,
                                                   "prompt": r.prompt[:100] + "..." if len(r.prompt) > 100 else r.prompt}
@@ -418,6 +480,8 @@ class AdaptiveSpeculativePipeline:
                 for name in ("top_p", "top_k", "min_p"):
                     if getattr(todo[0], name) is not None:
                         stop_kw[name] = [getattr(r, name) for r in todo]
+                for name in todo[0].edits:                              # (a batch carries a per-request edit for all requests or none)
+                    stop_kw[name] = [r.edits[name] for r in todo]
                 temp = [r.temperature for r in todo] if isinstance(temperature, list) else temperature
                 texts, logprobs, stage_stats = stage.generate(prompts=[r.current_prompt for r in todo],
                                                               max_tokens=limit, temperature=temp,

@@ -39,9 +39,8 @@ the accepted prefix, on the drawn token, or begin in tokens an earlier step comm
 committed stream and the step's committed candidates only -- never a rejected draft token, never a prompt token, never a token
 the row's limit cuts off -- and keeps the matched tokens, with their log-probs.  The loop ends on the same one-counter read.
 stats["stop_matches"][i] names the sequence that ended row i ((id,) for a stop id, None for "length"), so a caller can trim it.
-With one limit and no sequence a stage makes exactly the calls described above.  Not built: `min_new_tokens` (the stop ids would
-have to be masked out of the draft, verify and commit DISTRIBUTIONS, not out of the commit), removing finished rows from the
-batch, and serving/hierarchy.py's loop.  Bad values raise ValueError before any launch.
+With one limit and no sequence a stage makes exactly the calls described above.  Not built: removing finished rows from the
+batch, and serving/hierarchy.py's loop (`min_tokens` is built: LOGIT EDITS below).  Bad values raise ValueError before any launch.
 
 GREEDY DECODING.  `temperature == 0.0` (the reference's server and core types allow it; it is the setting of reproducible
 evaluation runs) selects arg-max decoding on ops.verify_greedy (asd_verify_greedy): stage 0 makes one K = 0 call per step, a
@@ -109,6 +108,34 @@ ValueError; AdaptiveSpeculativePipeline.batch_process splits such a batch in two
 negative temperature, a min_p outside [0, 1], a non-integer top_k, a sequence of the wrong length or one that holds None raise
 ValueError before any launch.
 
+LOGIT EDITS.  `generate(logit_bias=, banned_token_ids=, min_tokens=)` (or the StageConfig fields of those names; a keyword of
+None takes the configuration's value) change the distribution itself, ahead of every sampler: the order is edit -> temperature
+-> top-k -> top-p -> min-p.  `logit_bias` is OpenAI's / vLLM's: {token id: bias} for every prompt, or one dict (or None) per
+prompt; the bias is in RAW logit units, added before the temperature, a finite number in [-100, 100] (the range OpenAI
+documents; inside it an f16 logit cannot be pushed to +inf, which the samplers forbid).  `banned_token_ids` (vLLM's `bad_words`
+for single tokens) is a sequence of ids for every prompt, or one sequence per prompt: the logit becomes -inf; a banned id wins
+over a bias on the same id.  `min_tokens` (vLLM's) is an int >= 0, or one per prompt: while row i has generated fewer than
+min_tokens[i] tokens, every length-1 entry of its stop list -- the stop ids and the one-token stop sequences -- is banned, so
+such a row ends by "stop" with n_i >= min_tokens[i] + 1, or by "length".  All three are ONE operation, a sparse edit of a few
+logits per row: the host merges them per row into distinct (id, bias, until) entries -- a banned id gets until = INT32_MAX, a
+stop id under min_tokens gets until = min_tokens and keeps its bias for afterwards, a plain bias has until = 0; at most
+MAX_LOGIT_EDITS = 1024 per row -- uploads them once (ops.pack_logit_edits; equal rows share one list), and every loop calls
+ops.logit_edit_rows (asd_logit_edit_rows, in place) once per logits tensor: stage 0 on the step's [B, V] logits before the
+draw and the top-N pass; a verifying stage on every proposal's draft logits (offset = the draft slot k; the copy kept for
+the residual is the edited one) and on the target's [B, K+1, V] output before anything is sliced from or scored on it.  The
+edit sees seq_len as it is before the step's commit, so row j of a step knows which generated token it decides.  Draft and
+target receive the SAME edit, so the draft -> verify -> residual chain stays lossless against the edited target distribution.
+Consequences: the returned log-probs and the top-N tables are those of the EDITED distribution; a banned token is never
+listed; a banned token is never proposed, accepted or drawn.  The rows route, seeds, the stop and finish routes, greedy decoding
+and `logprobs = N` are untouched and compose with the edit.  A call whose merged lists are all empty (no keyword, an empty
+dict or list, min_tokens 0, biases of 0) makes exactly the ops calls it made before.  ValueError before any launch: a bool,
+non-integer or out-of-vocabulary id, a bias that is no number, NaN or outside [-100, 100], a negative or non-integer
+min_tokens, a sequence of the wrong length, more than 1024 entries in one row after merging, a row whose banned ids (for ever
+or at its first token) would leave no token.  NOT BUILT: `min_tokens` > 0 on a row whose stop list holds a MULTI-token
+sequence raises ValueError (the match would have to be suppressed in the commit kernels, which stay as they are); allow-lists
+(`allowed_token_ids`: a dense mask, not a sparse edit); multi-token `bad_words`; stateful penalties (repetition, presence,
+frequency), which need per-token state on top of this operation; and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -162,12 +189,18 @@ class StageConfig:
     stop_token_ids: Sequence[int] = ()       # EOS ids: a sequence ends behind the first committed one (module docstring)
     logprobs: int = 0                        # top-N log-probs per committed token, 0..8 (0: off; module docstring)
     stop_sequences: Sequence = ()            # stop strings / token-id sequences of every prompt (module docstring, HOW A ROW ENDS)
+    logit_bias: Optional[Dict[int, float]] = None    # {token id: bias in raw logit units} (module docstring, LOGIT EDITS)
+    banned_token_ids: Sequence[int] = ()     # token ids that are never proposed, accepted or drawn
+    min_tokens: int = 0                      # the stop ids are banned until a row has generated this many tokens
 
 
 MAX_STOP_IDS = 8                             # ASD_MAX_STOP_IDS of include/asd_hip.h
 MAX_STOP_SEQS = 16                           # ASD_MAX_STOP_SEQS: entries of one row's list (stop ids included)
 MAX_STOP_SEQ_LEN = 8                         # ASD_MAX_STOP_SEQ_LEN
 MAX_TOP_LOGPROBS = 8                         # ASD_MAX_TOP_LOGPROBS
+MAX_LOGIT_EDITS = 1024                       # ASD_MAX_LOGIT_EDITS: (id, bias, until) entries of one row after merging
+MAX_LOGIT_BIAS = 100.0                       # |bias| <= 100, the range OpenAI documents
+_EDIT_FOREVER = 2 ** 31 - 1                  # `until` of a permanent ban
 _REASONS = {1: "stop", 2: "length"}
 
 
@@ -269,6 +302,110 @@ def check_per_prompt(value, n: int, name: str):
             return vals[0]
         return vals
     return _check_sampling_value(value, name)
+
+
+def _is_seq(v) -> bool:
+    return isinstance(v, (Sequence, np.ndarray)) and not isinstance(v, (str, bytes))
+
+
+def _check_token_id(t, vocab: int, what: str) -> int:
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < vocab:
+        raise ValueError(f"{what} token ids must be integers in [0, {vocab}), got {t!r}")
+    return int(t)
+
+
+def _check_bias_dict(d, vocab: int) -> Dict[int, float]:
+    if d is None:
+        return {}
+    if not isinstance(d, dict):
+        raise ValueError(f"logit_bias must be a dict {{token id: bias}}, got {d!r}")
+    out = {}
+    for t, b in d.items():
+        t = _check_token_id(t, vocab, "logit_bias")
+        if isinstance(b, bool) or not isinstance(b, _NUMBER) or not abs(float(b)) <= MAX_LOGIT_BIAS:      # (NaN included)
+            raise ValueError(f"a logit bias must be a number in [-{MAX_LOGIT_BIAS:g}, {MAX_LOGIT_BIAS:g}], got {b!r}")
+        out[t] = float(b)
+    return out
+
+
+def check_logit_bias(value, n: int, vocab: int) -> List[Dict[int, float]]:
+    """generate's `logit_bias`: None, one dict for all `n` prompts, or a sequence of n dicts / Nones -> n dicts."""
+    if value is None or isinstance(value, dict):
+        d = _check_bias_dict(value, vocab)
+        return [d] * n
+    if not _is_seq(value):
+        raise ValueError(f"logit_bias must be a dict or one dict per prompt, got {value!r}")
+    if len(value) != n:
+        raise ValueError(f"{len(value)} logit_bias dicts for {n} prompts")
+    return [_check_bias_dict(d, vocab) for d in value]
+
+
+def check_banned_token_ids(value, n: int, vocab: int) -> List[Tuple[int, ...]]:
+    """generate's `banned_token_ids`: None, a sequence of ids for all `n` prompts, or a sequence of n such sequences -> n sorted
+    tuples of distinct ids."""
+    if value is None:
+        return [()] * n
+    if not _is_seq(value):
+        raise ValueError(f"banned_token_ids must be a sequence of token ids or one sequence per prompt, got {value!r}")
+    value = list(value)
+    if any(_is_seq(v) or v is None for v in value):
+        if not all(_is_seq(v) or v is None for v in value):
+            raise ValueError("banned_token_ids mixes token ids and per-prompt lists")
+        if len(value) != n:
+            raise ValueError(f"{len(value)} banned_token_ids lists for {n} prompts")
+        return [tuple(sorted({_check_token_id(t, vocab, "banned") for t in (v if v is not None else ())})) for v in value]
+    ids = tuple(sorted({_check_token_id(t, vocab, "banned") for t in value}))
+    return [ids] * n
+
+
+def check_min_tokens(value, n: int) -> List[int]:
+    """generate's `min_tokens`: an int >= 0 for all `n` prompts, or a sequence of n such ints -> n ints."""
+    def one(v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+            raise ValueError(f"min_tokens must be an integer >= 0, got {v!r}")
+        return min(int(v), _EDIT_FOREVER - 1)
+    if _is_seq(value):
+        if len(value) != n:
+            raise ValueError(f"{len(value)} min_tokens values for {n} prompts")
+        return [one(v) for v in value]
+    return [one(value)] * n
+
+
+def merge_logit_edits(bias: List[Dict[int, float]], banned: List[Tuple[int, ...]], min_tokens: List[int],
+                      row_seqs: List[List[Tuple[int, ...]]], vocab: int) -> List[List[Tuple[int, float, int]]]:
+    """Per row, the distinct (id, bias, until) entries of asd_logit_edit_rows (module docstring, LOGIT EDITS), sorted by id: a
+    bias has until 0, a length-1 stop entry of a row with min_tokens > 0 has until = min_tokens (and keeps its bias), a banned
+    id has until = INT32_MAX.  An entry that would do nothing (bias 0, until 0) is dropped."""
+    rows = []
+    for b, (d, ban, m, seqs) in enumerate(zip(bias, banned, min_tokens, row_seqs)):
+        entries = {t: [v, 0] for t, v in d.items()}
+        if m > 0:
+            if any(len(s) > 1 for s in seqs):
+                raise ValueError(f"prompt {b}: min_tokens > 0 is not built for a stop list that holds a multi-token stop sequence")
+            for (t,) in seqs:
+                entries.setdefault(t, [0.0, 0])[1] = m
+        for t in ban:
+            entries[t] = [0.0, _EDIT_FOREVER]
+        row = [(t, v, u) for t, (v, u) in sorted(entries.items()) if v != 0.0 or u > 0]
+        if len(row) > MAX_LOGIT_EDITS:
+            raise ValueError(f"prompt {b}: {len(row)} logit edits after merging, at most {MAX_LOGIT_EDITS}")
+        if sum(u > 0 for _, _, u in row) >= vocab:
+            raise ValueError(f"prompt {b}: the banned token ids leave no token of the vocabulary ({vocab})")
+        rows.append(row)
+    return rows
+
+
+class _EditState:
+    """What a generate call with logit edits keeps: the merged entries on the device (uploaded once) and the prompt length;
+    `apply` is the loops' one call per logits tensor (module docstring, LOGIT EDITS)."""
+
+    def __init__(self, ops, rows, P: int, device):
+        self.ops, self.start = ops, int(P)
+        self.packed = ops.pack_logit_edits(rows, device)
+
+    def apply(self, logits: torch.Tensor, seq_len: torch.Tensor, offset: int = 0) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], edited in place; seq_len: the step's lengths before its commit."""
+        return self.ops.logit_edit_rows(logits, self.packed, seq_len, self.start, offset)
 
 
 class _RowsState:
@@ -449,7 +586,8 @@ class Stage:
                  logprobs: Optional[int] = None,
                  min_p=None,
                  seed=None, stop_sequences=None,
-                 stop_sequences_per_prompt=None, top_k=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 stop_sequences_per_prompt=None, top_k=None, logit_bias=None, banned_token_ids=None,
+                 min_tokens=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -481,7 +619,12 @@ class Stage:
         `temperature`, `top_p`, `min_p` and `top_k` (None = the configuration's: StageConfig.top_k at stage 0, target_top_k at a
         verifying stage) each take one value or one per prompt; unequal values select the rows route, where row i is sampled
         with its own four values; a temperature sequence may not mix 0 with positive values (module docstring, PER-REQUEST
-        SAMPLING)."""
+        SAMPLING).
+        `logit_bias` ({token id: bias in [-100, 100]}, raw logit units, added before the temperature), `banned_token_ids` (ids
+        whose logit becomes -inf; a ban wins over a bias) and `min_tokens` (the row's stop ids and one-token stop sequences are
+        banned until it has generated that many tokens): None = the configuration's; one value for every prompt or one per
+        prompt.  Draft and target logits receive the same edit, so log-probs and top-N tables are those of the edited
+        distribution and a banned token is never proposed, accepted, drawn or listed (module docstring, LOGIT EDITS)."""
         t0 = time.perf_counter()
         prompts = list(prompts)
         self.step_inputs = []
@@ -515,6 +658,11 @@ class Stage:
                 raise ValueError(f"a prompt's stop list (stop ids included) holds at most {MAX_STOP_SEQS} entries, got {len(r)}")
             if len(set(r)) != len(r):
                 raise ValueError("the stop sequences of a prompt must be distinct")
+        edit_rows = merge_logit_edits(
+            check_logit_bias(self.config.logit_bias if logit_bias is None else logit_bias, n_prompts, self.shape.vocab),
+            check_banned_token_ids(self.config.banned_token_ids if banned_token_ids is None else banned_token_ids, n_prompts,
+                                   self.shape.vocab),
+            check_min_tokens(self.config.min_tokens if min_tokens is None else min_tokens, n_prompts), row_seqs, self.shape.vocab)
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * len(prompts)
         # the asd_commit_step_finish route: only for what the stop-id route cannot do (module docstring, HOW A ROW ENDS)
         finish_route = len(set(limits)) > 1 or bool(common) or any(own)
@@ -530,6 +678,8 @@ class Stage:
             end = _FinishState(row_seqs, limits, P, ids.device)
         else:
             end = _StopState(stop, B, ids.device) if stop else None
+        # logit edits: only where the call has an entry -- without one the ops calls are the ones made before
+        edit = _EditState(self.ops, edit_rows, P, ids.device) if any(edit_rows) else None
         rows = None
         if not isinstance(temperature, list) and temperature == 0.0:
             pass                                         # greedy: no draws, no truncation, no table
@@ -549,15 +699,16 @@ class Stage:
             rng = _SeedState(self.ops, seeds, self.index, 1 if self.draft is None else self.config.draft_len, ids.device)
         if temperature == 0.0:                           # greedy: no draws, no truncation (module docstring)
             decode = self._decode_plain_greedy if self.draft is None else self._decode_speculative_greedy
-            tokens, lps, seq_len = decode(ids, int(max_tokens), end, top)
+            tokens, lps, seq_len = decode(ids, int(max_tokens), end, top, edit)
         elif self.draft is None:
             tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
                                                       self.config.top_p if top_p is None or rows else float(top_p), end, top,
-                                                      0.0 if rows else min_p, rng, None if rows else top_k, rows)
+                                                      0.0 if rows else min_p, rng, None if rows else top_k, rows, edit)
         else:
             tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
                                                             self.config.target_top_p if top_p is None or rows else float(top_p),
-                                                            end, top, 0.0 if rows else min_p, rng, None if rows else top_k, rows)
+                                                            end, top, 0.0 if rows else min_p, rng, None if rows else top_k, rows,
+                                                            edit)
         self.ops.check_status()
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
@@ -622,7 +773,7 @@ class Stage:
                                       end.finished, end.n_finished)
 
     def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None, top=None,
-                      min_p: float = 0.0, rng=None, top_k: Optional[int] = None, per_row=None):
+                      min_p: float = 0.0, rng=None, top_k: Optional[int] = None, per_row=None, edit=None):
         """Stage 0.  Without a stop set every sequence appends exactly one token per step, so all positions are known on the
         host; with one (`end`), a sequence is fed its last committed token at seq_len - 1, which is the same for a running
         sequence and stays put for a finished one."""
@@ -637,6 +788,8 @@ class Stage:
         logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
         for step in range(max_tokens):
             logits = logits.contiguous()
+            if edit is not None:
+                edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
             r = None if rng is None else rng.step(step, 1, 0, False)[0][0]      # seeded: the step's one launch
             tok, lp, thr = self._propose(self.config, logits, inv_t, top_p, min_p, r, top_k, None if per_row is None else per_row.own)
             if top is not None:
@@ -663,7 +816,7 @@ class Stage:
                 logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
         return tokens, lps, seq_len
 
-    def _decode_plain_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None):
+    def _decode_plain_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None, edit=None):
         """Stage 0 at temperature 0: _decode_plain with one verify_greedy call (K = 0) per step in place of the draw; the logits
         are read where the model left them."""
         B, P = ids.shape
@@ -675,6 +828,8 @@ class Stage:
         m.alloc_ragged(B, cap + 1)
         logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
         for step in range(max_tokens):
+            if edit is not None:
+                edit.apply(logits, seq_len)                              # in place, where the model left the logits
             lp_t, n_acc, tok, lp, argmax, lp_argmax = self.ops.verify_greedy(logits, None, 1.0)
             if self.keep_inputs:
                 self.step_inputs.append(dict(logits=logits.clone(), tok=None, n_acc=n_acc.clone(), argmax=argmax.clone(),
@@ -700,7 +855,7 @@ class Stage:
                 logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
         return tokens, lps, seq_len
 
-    def _decode_speculative_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None):
+    def _decode_speculative_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None, edit=None):
         """Stage s > 0 at temperature 0: _decode_speculative's step with the draft's arg-max as the proposal (K = 0 calls on the
         draft logits) and ONE verify_greedy call on the target's [B, K+1, V] output as returned -- no copies of the score and
         bonus rows, no kept draft logits, no uniforms.  A draft token is accepted iff it is the target row's arg-max, the token
@@ -729,12 +884,16 @@ class Stage:
             dl = draft.forward_ragged(last2, L - 2, window)[:, -1]
             toks = []
             for k in range(Kd):
+                if edit is not None:
+                    edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
                 t = self.ops.verify_greedy(dl, None, 1.0)[2]
                 toks.append(t)
                 if k + 1 < Kd:
                     dl = draft.forward_ragged(t.to(torch.int64)[:, None], L + k, window)[:, -1]
             tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
             t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
+            if edit is not None:
+                edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows
             lp_t, n_acc, drawn, lp_drawn, argmax, lp_argmax = self.ops.verify_greedy(t_out, tok32, 1.0)
             if self.keep_inputs:
                 self.step_inputs.append(dict(logits=t_out.clone(), tok=tok32.clone(), n_acc=n_acc.clone(), argmax=argmax.clone(),
@@ -771,7 +930,7 @@ class Stage:
         return lp_t, n_acc, None
 
     def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None, top=None,
-                            target_min_p: float = 0.0, rng=None, target_top_k: Optional[int] = None, per_row=None):
+                            target_min_p: float = 0.0, rng=None, target_top_k: Optional[int] = None, per_row=None, edit=None):
         """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
 
         Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
@@ -805,18 +964,22 @@ class Stage:
             toks, lpd, dls, thrs = [], [], [], []
             for k in range(Kd):
                 dl = dl.contiguous()
+                if edit is not None:
+                    edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
                 t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p, dcfg.min_p, None if rd is None else rd[k],
                                            table=None if per_row is None else per_row.draft)
                 toks.append(t)
                 lpd.append(lp)
                 thrs.append(thr)
-                dls.append(dl)                                          # kept for the residual distribution at a rejection
+                dls.append(dl)                                          # kept (edited) for the residual distribution at a rejection
                 if k + 1 < Kd:
                     dl = draft.forward_ragged(t.to(torch.int64)[:, None], L + k, window)[:, -1]
             tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
             lp_d = torch.stack(lpd, 1).contiguous()
             d_thr = torch.stack(thrs, 1).contiguous()
             t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
+            if edit is not None:
+                edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any copy
             score = t_out[:, :Kd].contiguous()
             bonus = t_out[:, Kd].contiguous()
             if rng is None:

@@ -51,6 +51,7 @@ typedef enum asd_dtype {
 #define ASD_MAX_STOP_SEQS 16   /* stop sequences one row may own in asd_commit_step_finish */
 #define ASD_MAX_STOP_SEQ_LEN 8 /* tokens per stop sequence of asd_commit_step_finish */
 #define ASD_MAX_TOP_LOGPROBS 8 /* N of asd_top_logprobs: the most likely tokens listed per row */
+#define ASD_MAX_LOGIT_EDITS 1024 /* entries one row may own in asd_logit_edit_rows */
 #define ASD_MAX_STAGES 16      /* L: tiers in the DP rule */
 #define ASD_MAX_SPLITS 64      /* vocab splits per row inside one launch */
 #define ASD_MAX_MLP_DIM 1024   /* predictor input / hidden width */
@@ -469,6 +470,42 @@ int asd_commit_top_logprobs(const int32_t* top_id /*[B,K1,N]*/, const float* top
 int asd_step_uniforms(const int64_t* seeds /*[B], read as uint64*/, uint32_t step, uint32_t stage, int B, int K_draft,
                       int K_accept, float* r_draft /*[K_draft,B] out, may be NULL*/,
                       float* u /*[B,K_accept] out, may be NULL*/, float* r_commit /*[B] out, may be NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Logit edits: a sparse in-place edit of a few logits per row AHEAD of the samplers -- OpenAI's `logit_bias`, vLLM's
+ * `bad_words` / `logit_bias` (a ban, a push) and vLLM's `min_tokens` (the stop ids banned until a row has generated enough).
+ * Every sampler above and below admits -inf logits ("no logit > -inf", "a logit of -inf is never listed"), so an edited row is
+ * an ordinary input of theirs; applied alike to the draft's proposal rows and the target's K+1 rows, the draft -> verify ->
+ * residual chain stays lossless against the EDITED target distribution.
+ * logits: B sequences of K1 rows, element (b, j, v) at b*ld_seq + j*ld_row + v (asd_top_logprobs' addressing; K1 == 1 is a
+ * [B, V] matrix), bf16 / f16 / f32, edited in place.  ld_row >= V, ld_seq >= K1*ld_row; the padding is never touched.
+ * Entries: three parallel DEVICE arrays edit_id / edit_bias / edit_until of n entries.  row_first != NULL: int32 [B+1], row b
+ * owns the entries [row_first[b], row_first[b+1]) and n_shared is n, the length of the arrays (indices are clamped into it,
+ * so a damaged row_first never leaves them).  row_first == NULL: every row owns the entries [0, n_shared).  At most
+ * ASD_MAX_LOGIT_EDITS entries of a row are honoured.
+ * One entry (id, bias, until) at position j of row b, with
+ *     g = seq_len[b] - start + offset + j
+ * the 0-based index, among the row's generated tokens, of the token that logits row decides (start: the prompt length;
+ * offset: the draft slot of a proposal row, 0 for the target's rows):
+ *     g < until           element id becomes -inf
+ *     else, bias != 0     element id becomes round_to_dtype((float)x + bias): one f32 addition, one rounding, to nearest even
+ *     else                nothing is stored (the bits stay)
+ * until == 0 is a plain bias, until == INT32_MAX a permanent ban, a value between them the min_tokens ban of a stop id (which
+ * keeps its bias for afterwards).
+ * THE PACKING CONTRACT: inside one row the ids are distinct.  The launcher cannot check device data, so it does not; the
+ * kernel relies on it (no two lanes write one element: no atomics) and writes nothing but the named elements, with ordinary
+ * per-lane stores.  Likewise the ids themselves cannot be checked by the launcher: an id outside [0, V) is skipped by the
+ * kernel, never written.  A bias must be finite; the caller keeps x + bias away from +inf, which the samplers forbid.
+ * One launch, one workgroup per (b, j); no workspace, nothing waits.
+ * Status, in this order: negative B / K1 / V / n_shared: invalid argument; B == 0, K1 == 0 or n_shared == 0: ASD_OK, nothing
+ * launched; unknown dtype, row_first == NULL with n_shared > ASD_MAX_LOGIT_EDITS, B*K1 > INT32_MAX: unsupported; NULL logits /
+ * edit_id / edit_bias / edit_until / seq_len, ld_row < V, ld_seq < K1*ld_row: invalid argument; logits not aligned to the
+ * element size: alignment.
+ * ---------------------------------------------------------------------------------------- */
+int asd_logit_edit_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                        const int32_t* edit_id /*[n]*/, const float* edit_bias /*[n]*/, const int32_t* edit_until /*[n]*/,
+                        const int32_t* row_first /*[B+1], or NULL: entries [0, n_shared) for every row*/, int n_shared,
+                        const int32_t* seq_len /*[B]*/, int start, int offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs and asd_step_uniforms in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms and asd_logit_edit_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -240,6 +240,33 @@ int main() {
         EXPECT(UNI(reinterpret_cast<const int64_t*>(rows + 4), B, 2, 2, f32, f32, f32), ASD_ERR_ALIGNMENT);
         EXPECT(UNI(seeds, B, 2, 2, reinterpret_cast<float*>(rows + 2), f32, f32), ASD_ERR_ALIGNMENT);
 #undef UNI
+    }
+
+    // ---- asd_logit_edit_rows: every rejection, and every "nothing to do", comes before the launch
+    {
+#define EDIT(x_, dt_, lds_, ldr_, B_, K1_, V_, id_, bias_, until_, first_, n_, seq_) \
+    asd_logit_edit_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, id_, bias_, until_, first_, n_, seq_, 5, 0, nullptr)
+        const int K1 = 5;
+        EXPECT(EDIT(p, BF16, K1 * V, V, -1, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, -1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, K1, -1, i32, f32, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, K1, V, i32, f32, i32, nullptr, -1, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(nullptr, 99, 0, 0, 0, K1, V, nullptr, nullptr, nullptr, nullptr, 4, nullptr), ASD_OK);          // B == 0
+        EXPECT(EDIT(nullptr, 99, 0, 0, B, 0, V, nullptr, nullptr, nullptr, nullptr, 4, nullptr), ASD_OK);           // K1 == 0
+        EXPECT(EDIT(nullptr, 99, 0, 0, B, K1, V, nullptr, nullptr, nullptr, nullptr, 0, nullptr), ASD_OK);          // no entries
+        EXPECT(EDIT(p, 99, K1 * V, V, B, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_UNSUPPORTED);              // dtype
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, K1, V, i32, f32, i32, nullptr, ASD_MAX_LOGIT_EDITS + 1, i32), ASD_ERR_UNSUPPORTED);
+        EXPECT(EDIT(p, BF16, int64_t{1} << 40, V, INT32_MAX, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_UNSUPPORTED);   // grid
+        EXPECT(EDIT(nullptr, BF16, K1 * V, V, B, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, K1, V, nullptr, f32, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, K1, V, i32, nullptr, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, K1, V, i32, f32, nullptr, nullptr, 4, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(EDIT(p, BF16, K1 * V, V, B, K1, V, i32, f32, i32, nullptr, 4, nullptr), ASD_ERR_INVALID_ARG);        // seq_len
+        EXPECT(EDIT(p, BF16, K1 * V, V - 1, B, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);        // ld_row < V
+        EXPECT(EDIT(p, BF16, K1 * V - 1, V, B, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_INVALID_ARG);        // ld_seq < K1 ld_row
+        EXPECT(EDIT(rows + 1, BF16, K1 * V, V, B, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_ALIGNMENT);
+        EXPECT(EDIT(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, i32, f32, i32, i32, 4, i32), ASD_ERR_ALIGNMENT);
+#undef EDIT
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
