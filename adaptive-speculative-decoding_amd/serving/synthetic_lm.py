@@ -62,18 +62,26 @@ class RMSNorm(nn.Module):
         self.eps = eps
 
     def forward(self, x):
-        v = x.float()
+        ct = _compute_dtype(x)
+        v = x.to(ct)
         v = v * torch.rsqrt(v.pow(2).mean(-1, keepdim=True) + self.eps)
-        return (v * self.weight.float()).to(x.dtype)
+        return (v * self.weight.to(ct)).to(x.dtype)
+
+
+def _compute_dtype(x: torch.Tensor) -> torch.dtype:
+    """f32 for bf16 / f16 / f32 states; a .double() model (the f64 reference of the tests) keeps f64 through norm and rope."""
+    return torch.float64 if x.dtype == torch.float64 else torch.float32
 
 
 def _rope(x: torch.Tensor, pos: torch.Tensor, theta: float) -> torch.Tensor:
-    """x: [B, H, T, D]; pos: [T] absolute positions shared by the batch, or [B, T] per sequence."""
+    """x: [B, H, T, D]; pos: [T] absolute positions shared by the batch, or [B, T] per sequence.  The angle is the f32 product
+    f32(pos) * f32(inv_freq) for every dtype (the kernel's); its cosine and sine are taken in the compute dtype."""
     d = x.shape[-1]
+    ct = _compute_dtype(x)
     inv = 1.0 / (theta ** (torch.arange(0, d, 2, device=x.device, dtype=torch.float32) / d))
-    ang = pos.float()[..., None] * inv
+    ang = (pos.float()[..., None] * inv).to(ct)
     cos, sin = (ang.cos()[None, None], ang.sin()[None, None]) if pos.dim() == 1 else (ang.cos()[:, None], ang.sin()[:, None])
-    x1, x2 = x.float()[..., : d // 2], x.float()[..., d // 2:]
+    x1, x2 = x.to(ct)[..., : d // 2], x.to(ct)[..., d // 2:]
     return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1).to(x.dtype)
 
 

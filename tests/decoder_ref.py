@@ -1,8 +1,11 @@
-"""References, bounds and input builders for the decoder-stack edge tests (CPU only: torch on the host, no kernels, no package).
+"""References, bounds and input builders for the decoder-stack tests (plain torch: no kernels, no package; every function works on
+the device of the tensors it is given, and the module itself needs none).
 
 tests/test_decoder_refs.py shows on the CPU that the assertions below pass a faithful restatement of k_attn_ragged's algorithm
 and fail six single defects of it; tests/test_gpu_decoder_edges.py holds the kernel itself to the same assertions on the same
-cases (the builders are pure functions of the case, so both see the same bits)."""
+cases (the builders are pure functions of the case, so both see the same bits).  The f64 references of the single ops at the end
+(rmsnorm_ref, linear_ref, rope_ref, attn_ref, silu_mul_ref) are chained over a model by tests/test_decoder_refs.py, which holds the
+chain to SyntheticLM's own f64 forward; tests/test_gpu_decoder_widths.py holds every kernel of the stack to them."""
 import math
 from collections import namedtuple
 from functools import lru_cache
@@ -34,10 +37,11 @@ def attn_ref(q, k, v, pos, row_of=None):
     KVH, t_max = k.shape[1], k.shape[2]
     rep = H // KVH
     rows = _row_of(M, k.shape[0], row_of)
+    pos = torch.as_tensor(pos).tolist()
     q64 = q.double().view(M, KVH, rep, HD)
-    ref = torch.empty(M, H, HD, dtype=torch.float64)
+    ref = torch.empty(M, H, HD, dtype=torch.float64, device=q.device)
     A = torch.empty_like(ref)
-    j = torch.arange(t_max)
+    j = torch.arange(t_max, device=q.device)
     for m in range(M):
         kk, vv = k[rows[m]].double(), v[rows[m]].double()                       # [KVH, t_max, 128]
         sc = torch.matmul(q64[m], kk.transpose(1, 2)) / math.sqrt(float(HD))     # [KVH, rep, t_max]
@@ -272,3 +276,54 @@ def rope_ref(x, pos, inv_freq):
 def rope_bound(ref):
     """2^-8 |ref| + 1e-5 (tests/test_gpu_decoder.py::test_rope_kv_store): one bf16 rounding plus the cosf / sinf error."""
     return 2.0 ** -8 * ref.abs() + 1.0e-5
+
+
+# ---- the other ops of a decoder layer, and inputs that are not the special case bias = 0, norm weight = 1
+
+def rmsnorm_ref(x, w, eps):
+    """x [M, D], w [D] (any float type) -> f64 x * rsqrt(mean(x^2) + eps) * w."""
+    v = x.double()
+    return v * torch.rsqrt(v.pow(2).mean(-1, keepdim=True) + eps) * w.double()
+
+
+def silu_mul_ref(gu):
+    """gu [M, 2 I] = gate | up (any float type) -> f64 [M, I] silu(gate) * up."""
+    I = gu.shape[-1] // 2
+    g, u = gu[..., :I].double(), gu[..., I:].double()
+    return g / (1.0 + torch.exp(-g)) * u
+
+
+def linear_ref(x, w, bias=None, residual=None):
+    """x [M, D], w [N, D] (nn.Linear layout), bias [N] or None, residual [M, N] or None -> f64 x . w^T + bias + residual."""
+    r = x.double() @ w.double().T
+    if bias is not None:
+        r = r + bias.double()
+    if residual is not None:
+        r = r + residual.double()
+    return r
+
+
+def elementwise_bound(ref):
+    """2^-8 |ref| + 1e-6 (tests/test_gpu_decoder.py::test_rmsnorm, test_silu_mul): f32 arithmetic and one bf16 rounding."""
+    return 2.0 ** -8 * ref.abs() + 1.0e-6
+
+
+def linear_bound(ref):
+    """2^-8 |ref| + 2e-4 (tests/test_gpu_linear.py::_check for bf16): f32 accumulation in MFMA order and one bf16 rounding."""
+    return 2.0 ** -8 * ref.abs() + 2.0e-4
+
+
+def randomize_affine(lm, seed):
+    """Every `*.bias` of the model becomes N(0, 1) and every norm weight 1 + 0.25 N(0, 1), in place and in the model's dtype
+    (SyntheticLM initialises them to 0 and 1, where a wrong bias or weight index changes nothing).  The values are drawn on the
+    CPU in f32, in named_parameters order, and then copied to the parameter's device: one seed gives the same values to a CPU and a
+    GPU model.  Call it before enable_hip_layers (which re-points q|k|v biases at a fused buffer)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in lm.named_parameters():
+            if p.dim() != 1:
+                continue
+            z = torch.randn(p.shape, generator=g, dtype=torch.float32)
+            if not name.endswith(".bias"):
+                z = 1.0 + 0.25 * z
+            p.copy_(z.to(p.dtype))

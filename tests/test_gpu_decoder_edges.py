@@ -126,6 +126,7 @@ def test_kv_rollback_is_exact():
     outs, caches = [], []
     for feed in (X, Xp):
         lm = SL.SyntheticLM(shape, dtype=BF, device="cuda", seed=4)
+        R.randomize_affine(lm, 21)
         lm.enable_hip_layers()
         lm.alloc_ragged(3, 96)
         length = torch.zeros(3, dtype=torch.int64, device="cuda")

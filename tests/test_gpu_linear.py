@@ -100,6 +100,94 @@ def test_linear_slice_counts_agree(M):
             lib.asd_debug_force_linear_slices(0)
 
 
+def _pack(w):
+    """The tile-major image of w [N, D] in a new buffer, as HipDecoder(pack_weights=True) makes it (asd_lm_head_pack_weights)."""
+    from importlib import import_module
+    K_ = import_module("adaptive-speculative-decoding_amd.kernels")
+    B_ = import_module("adaptive-speculative-decoding_amd._binding")
+    N, D = w.shape
+    nbytes = int(K_._lib().asd_lm_head_packed_bytes(N, D))
+    assert nbytes == (N + 255) // 256 * 256 * D * 2
+    image = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    B_.check("asd_lm_head_pack_weights", K_._lib().asd_lm_head_pack_weights(
+        w.data_ptr(), w.stride(0), K_._DTYPE_CODE[w.dtype], N, D, image.data_ptr(), nbytes, K_._stream()))
+    return image
+
+
+def _linear_ex(x, w, N, b, res, ws, packed):
+    """asd_linear_ex through the library handle of the moment (inside test_hooks(): the TEST build), out = residual in place.
+    w: the [N, D] matrix, or with packed=True its tile-major image (passed with ld_w = 0)."""
+    from importlib import import_module
+    K_ = import_module("adaptive-speculative-decoding_amd.kernels")
+    B_ = import_module("adaptive-speculative-decoding_amd._binding")
+    M, D = x.shape
+    out = res.clone()
+    rc = K_._lib().asd_linear_ex(x.data_ptr(), x.stride(0), w.data_ptr(), 0 if packed else w.stride(0), b.data_ptr(), out.data_ptr(),
+                                 out.stride(0), K_._DTYPE_CODE[x.dtype], M, N, D, out.data_ptr(), out.stride(0), ws.data_ptr(),
+                                 ws.numel(), K_._stream())
+    B_.check("asd_linear_ex", rc)
+    return out
+
+
+def _mk_res(M, N, dtype):
+    g = torch.Generator(device="cuda").manual_seed(9)
+    return torch.randn(M, N, generator=g, device="cuda").to(dtype)
+
+
+PACKED_FORMS = [
+    # form, M, N, D, dtype: one (M, N, D) per form of the launcher at the benchmarked widths
+    ("skinny", 1, 3584, 18944, torch.bfloat16), ("skinny", 32, 3584, 18944, torch.bfloat16), ("tile", 65, 10240, 8192, torch.bfloat16),
+    ("tile", 200, 5120, 5120, torch.bfloat16), ("tile", 200, 5120, 5120, torch.float16), ("tall", 288, 5120, 27648, torch.bfloat16),
+    ("two_row_blocks", 297, 3584, 18944, torch.bfloat16), ("quad", 520, 55296, 5120, torch.bfloat16),
+]
+
+
+@pytest.mark.parametrize("form,M,N,D,dtype", PACKED_FORMS,
+                         ids=[f"{f}-{M}x{N}x{D}-{'f16' if t == torch.float16 else 'bf16'}" for f, M, N, D, t in PACKED_FORMS])
+def test_linear_packed_image_through_the_store_epilogue(form, M, N, D, dtype):
+    """The tile-major image (ld_w = 0) through asd_linear_ex's STORE epilogue with bias and in-place residual: the bits of the
+    row-major call, and within _check of the f64 product."""
+    from importlib import import_module
+    K_ = import_module("adaptive-speculative-decoding_amd.kernels")
+    x, w, b = _mk(M, N, D, dtype, True, seed=M * 7 + N)
+    res = _mk_res(M, N, dtype)
+    slices = K_._lib().asd_linear_slices(M, N, D)
+    print(f"{form} {M} x {N} x {D}: {slices} slices")
+    if form == "quad":               # linear_plan: two or more 256-row blocks whose unsliced grid fills the CUs twice over
+        units = (N + 255) // 256 * ((M + 255) // 256)
+        assert M > 288 and units >= 2 * K_.device_cu_count(), (units, K_.device_cu_count())
+    ws = torch.empty(int(K_._lib().asd_linear_workspace_bytes(M, N, D)), dtype=torch.uint8, device="cuda")
+    y_rows = _linear_ex(x, w, N, b, res, ws, packed=False)
+    y_packed = _linear_ex(x, _pack(w), N, b, res, ws, packed=True)
+    assert torch.equal(y_packed, y_rows)
+    _check(y_packed, _ref(x, w, b) + res.double(), dtype)
+
+
+@pytest.mark.parametrize("M,N,D", [(32, 3584, 18944), (288, 5120, 27648)])
+def test_linear_forced_slice_counts_on_the_packed_image(M, N, D):
+    """296 and 432 superstages cut 1, 3, 5 and 18 ways on the packed layout (5 divides neither and 18 does not divide 296: the
+    uneven s_begin / n_super split; 432 = 24 x 18 is the even one): every count within _check, and the bits of the row-major call
+    at the same count."""
+    from importlib import import_module
+    K_ = import_module("adaptive-speculative-decoding_amd.kernels")
+    x, w, b = _mk(M, N, D, torch.bfloat16, True, seed=13)
+    res = _mk_res(M, N, torch.bfloat16)
+    ref = _ref(x, w, b) + res.double()
+    image = _pack(w)
+    assert (D // 64) % 5 != 0 and ((D // 64) % 18 != 0) == (D == 18944)
+    with K_.test_hooks() as lib:                # the TEST build of the library: the product one has no asd_debug_* switches
+        try:
+            for k in (1, 3, 5, 18):
+                lib.asd_debug_force_linear_slices(k)
+                ws = torch.empty(k * M * N * 4 + 512, dtype=torch.uint8, device="cuda")
+                y_packed = _linear_ex(x, image, N, b, res, ws, packed=True)
+                y_rows = _linear_ex(x, w, N, b, res, ws, packed=False)
+                _check(y_packed, ref, torch.bfloat16)
+                assert torch.equal(y_packed, y_rows), k
+        finally:
+            lib.asd_debug_force_linear_slices(0)
+
+
 def test_linear_argument_checks():
     from importlib import import_module
     K_ = import_module("adaptive-speculative-decoding_amd.kernels")
