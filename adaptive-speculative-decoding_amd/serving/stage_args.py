@@ -1,0 +1,205 @@
+"""The argument checks of Stage.generate (serving/stages.py, whose module docstring states every rule): host-side, before any
+launch.  Every "one value, or one per prompt" argument goes through `_per_prompt`; a bad value raises ValueError."""
+from __future__ import annotations
+
+from collections.abc import Sequence          # (isinstance against this one, not typing's alias: several times cheaper)
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+MAX_STOP_IDS = 8                             # ASD_MAX_STOP_IDS of include/asd_hip.h
+MAX_STOP_SEQS = 16                           # ASD_MAX_STOP_SEQS: entries of one row's list (stop ids included)
+MAX_STOP_SEQ_LEN = 8                         # ASD_MAX_STOP_SEQ_LEN
+MAX_TOP_LOGPROBS = 8                         # ASD_MAX_TOP_LOGPROBS
+MAX_LOGIT_EDITS = 1024                       # ASD_MAX_LOGIT_EDITS: (id, bias, until) entries of one row after merging
+MAX_LOGIT_BIAS = 100.0                       # |bias| <= 100, the range OpenAI documents
+_EDIT_FOREVER = 2 ** 31 - 1                  # `until` of a permanent ban
+_NUMBER = (int, float, np.integer, np.floating)
+
+
+def _is_seq(v) -> bool:
+    return isinstance(v, (Sequence, np.ndarray)) and not isinstance(v, (str, bytes))
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _per_prompt(value, n: int, one, what: str) -> list:
+    """One value for all `n` prompts, or a sequence of n values, each passed through `one(v)` -> a list of n checked values."""
+    if not _is_seq(value):
+        return [one(value)] * n
+    if len(value) != n:
+        raise ValueError(f"{len(value)} {what} for {n} prompts")
+    return [one(v) for v in value]
+
+
+def _check_stop_ids(ids: Sequence[int], vocab: int) -> Tuple[int, ...]:
+    ids = tuple(int(i) for i in ids)
+    if len(ids) > MAX_STOP_IDS:
+        raise ValueError(f"at most {MAX_STOP_IDS} stop token ids, got {len(ids)}")
+    if len(set(ids)) != len(ids):
+        raise ValueError("stop token ids must be distinct")
+    if any(not 0 <= i < vocab for i in ids):
+        raise ValueError(f"stop token ids must lie in [0, {vocab})")
+    return ids
+
+
+def check_max_tokens(max_tokens, n: int):
+    """generate's `max_tokens`: an int (returned as it is), or a sequence of n ints >= 1 -> a list of n ints."""
+    def one(v):
+        if not _is_int(v) or int(v) < 1:
+            raise ValueError(f"every per-prompt max_tokens must be an integer >= 1, got {max_tokens!r}")
+        return int(v)
+    if _is_int(max_tokens):
+        return int(max_tokens)
+    if not _is_seq(max_tokens):
+        raise ValueError(f"max_tokens must be an integer or one integer per prompt, got {max_tokens!r}")
+    return _per_prompt(max_tokens, n, one, "max_tokens values")
+
+
+def _check_stop_sequences(entries, vocab: int, tokenizer) -> List[Tuple[int, ...]]:
+    """One list of stop sequences: each entry a str (encoded by the stage's tokenizer, ids folded into the vocabulary as
+    encode_prompts folds prompt ids) or a sequence of token ids; every entry must come to 1..8 ids in [0, vocab)."""
+    if entries is None:
+        return []
+    if not _is_seq(entries):
+        raise ValueError(f"stop sequences must be a list of strings or token-id sequences, got {entries!r}")
+    out = []
+    for e in entries:
+        if isinstance(e, str):
+            ids = [int(i) % vocab for i in tokenizer.encode(e, return_tensors=None)]
+        elif not _is_seq(e):
+            raise ValueError(f"a stop sequence is a string or a sequence of token ids, got {e!r}")
+        else:
+            if not all(_is_int(t) for t in e):
+                raise ValueError(f"stop sequence token ids must be integers, got {e!r}")
+            ids = [int(t) for t in e]
+            if any(not 0 <= t < vocab for t in ids):
+                raise ValueError(f"stop sequence token ids must lie in [0, {vocab})")
+        if not 1 <= len(ids) <= MAX_STOP_SEQ_LEN:
+            raise ValueError(f"a stop sequence must come to 1..{MAX_STOP_SEQ_LEN} token ids, {e!r} gives {len(ids)}")
+        out.append(tuple(ids))
+    return out
+
+
+def _check_logprobs(n) -> int:
+    if not _is_int(n) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs must be an integer in [0, {MAX_TOP_LOGPROBS}], got {n!r}")
+    return int(n)
+
+
+def _check_min_p(v, name: str = "min_p") -> float:
+    if isinstance(v, bool) or not isinstance(v, _NUMBER) or not 0.0 <= float(v) <= 1.0:
+        raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")           # (NaN included)
+    return float(v)
+
+
+def _check_sampling_value(v, name: str):
+    """One temperature / top_p / top_k / min_p value of generate (PER-REQUEST SAMPLING)."""
+    if name == "top_k":
+        if not _is_int(v):
+            raise ValueError(f"top_k must be an integer, got {v!r}")
+        return int(v)
+    if name == "min_p":
+        return _check_min_p(v)
+    if isinstance(v, bool) or not isinstance(v, _NUMBER) or float(v) != float(v):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+    v = float(v)
+    if name == "temperature" and not v >= 0.0:
+        raise ValueError("temperature must be >= 0 (0: greedy decoding)")
+    return v
+
+
+def check_per_prompt(value, n: int, name: str):
+    """generate's `temperature` / `top_p` / `top_k` / `min_p`: None (returned as it is), one value for all `n` prompts, or a
+    sequence of n values.  -> the checked value, or a list of n checked values; a sequence whose values are all equal
+    collapses to that value."""
+    if value is None:
+        return None
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+    if not _is_seq(value):
+        return _check_sampling_value(value, name)
+    vals = _per_prompt(value, n, lambda v: _check_sampling_value(v, name), f"{name} values")   # (None inside a sequence raises)
+    return vals[0] if vals and all(v == vals[0] for v in vals) else vals
+
+
+def _check_token_id(t, vocab: int, what: str) -> int:
+    if not _is_int(t) or not 0 <= int(t) < vocab:
+        raise ValueError(f"{what} token ids must be integers in [0, {vocab}), got {t!r}")
+    return int(t)
+
+
+def check_logit_bias(value, n: int, vocab: int) -> List[Dict[int, float]]:
+    """generate's `logit_bias`: None, one dict for all `n` prompts, or a sequence of n dicts / Nones -> n dicts."""
+    def one(d):
+        if d is None:
+            return {}
+        if not isinstance(d, dict):
+            raise ValueError(f"logit_bias must be a dict {{token id: bias}} or one dict per prompt, got {d!r}")
+        out = {}
+        for t, b in d.items():
+            t = _check_token_id(t, vocab, "logit_bias")
+            if isinstance(b, bool) or not isinstance(b, _NUMBER) or not abs(float(b)) <= MAX_LOGIT_BIAS:      # (NaN included)
+                raise ValueError(f"a logit bias must be a number in [-{MAX_LOGIT_BIAS:g}, {MAX_LOGIT_BIAS:g}], got {b!r}")
+            out[t] = float(b)
+        return out
+    return _per_prompt(value, n, one, "logit_bias dicts")
+
+
+def check_banned_token_ids(value, n: int, vocab: int) -> List[Tuple[int, ...]]:
+    """generate's `banned_token_ids`: None, a sequence of ids for all `n` prompts, or a sequence of n such sequences -> n sorted
+    tuples of distinct ids."""
+    def one(ids):
+        return tuple(sorted({_check_token_id(t, vocab, "banned") for t in (ids if ids is not None else ())}))
+    if value is not None and not _is_seq(value):
+        raise ValueError(f"banned_token_ids must be a sequence of token ids or one sequence per prompt, got {value!r}")
+    per_prompt = [_is_seq(v) or v is None for v in (value if value is not None else ())]
+    if not any(per_prompt):                              # a flat id list (or None): the same ban for every prompt
+        return [one(value)] * n
+    if not all(per_prompt):
+        raise ValueError("banned_token_ids mixes token ids and per-prompt lists")
+    return _per_prompt(list(value), n, one, "banned_token_ids lists")
+
+
+def check_min_tokens(value, n: int) -> List[int]:
+    """generate's `min_tokens`: an int >= 0 for all `n` prompts, or a sequence of n such ints -> n ints."""
+    def one(v):
+        if not _is_int(v) or int(v) < 0:
+            raise ValueError(f"min_tokens must be an integer >= 0, got {v!r}")
+        return min(int(v), _EDIT_FOREVER - 1)
+    return _per_prompt(value, n, one, "min_tokens values")
+
+
+def check_seeds(seed, n: int) -> Optional[List[int]]:
+    """generate's `seed`: None, one int in [0, 2^64) for all `n` prompts, or a sequence of n such ints -> None or n ints."""
+    def one(v):
+        if not _is_int(v) or not 0 <= int(v) < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {v!r}")
+        return int(v)
+    return None if seed is None else _per_prompt(seed, n, one, "seeds")
+
+
+def merge_logit_edits(bias: List[Dict[int, float]], banned: List[Tuple[int, ...]], min_tokens: List[int],
+                      row_seqs: List[List[Tuple[int, ...]]], vocab: int) -> List[List[Tuple[int, float, int]]]:
+    """Per row, the distinct (id, bias, until) entries of asd_logit_edit_rows (LOGIT EDITS), sorted by id: a bias has until 0, a
+    length-1 stop entry of a row with min_tokens > 0 has until = min_tokens (and keeps its bias), a banned id has
+    until = INT32_MAX.  An entry that would do nothing (bias 0, until 0) is dropped."""
+    rows = []
+    for b, (d, ban, m, seqs) in enumerate(zip(bias, banned, min_tokens, row_seqs)):
+        entries = {t: [v, 0] for t, v in d.items()}
+        if m > 0:
+            if any(len(s) > 1 for s in seqs):
+                raise ValueError(f"prompt {b}: min_tokens > 0 is not built for a stop list that holds a multi-token stop sequence")
+            for (t,) in seqs:
+                entries.setdefault(t, [0.0, 0])[1] = m
+        for t in ban:
+            entries[t] = [0.0, _EDIT_FOREVER]
+        row = [(t, v, u) for t, (v, u) in sorted(entries.items()) if v != 0.0 or u > 0]
+        if len(row) > MAX_LOGIT_EDITS:
+            raise ValueError(f"prompt {b}: {len(row)} logit edits after merging, at most {MAX_LOGIT_EDITS}")
+        if sum(u > 0 for _, _, u in row) >= vocab:
+            raise ValueError(f"prompt {b}: the banned token ids leave no token of the vocabulary ({vocab})")
+        rows.append(row)
+    return rows

@@ -145,7 +145,7 @@ from __future__ import annotations
 
 import time
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -153,6 +153,9 @@ import torch
 from ..distributed import HipOps
 from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
+from .stage_args import (MAX_LOGIT_EDITS, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS, _check_logprobs, _check_min_p,  # noqa: F401
+                         _check_stop_ids, _check_stop_sequences, _is_seq, check_banned_token_ids, check_logit_bias,
+                         check_max_tokens, check_min_tokens, check_per_prompt, check_seeds, merge_logit_edits)
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
 # reference stage label -> the Qwen2.5 shape this build runs in its place (configs/models.yaml names the tiers by size)
@@ -194,205 +197,25 @@ class StageConfig:
     min_tokens: int = 0                      # the stop ids are banned until a row has generated this many tokens
 
 
-MAX_STOP_IDS = 8                             # ASD_MAX_STOP_IDS of include/asd_hip.h
-MAX_STOP_SEQS = 16                           # ASD_MAX_STOP_SEQS: entries of one row's list (stop ids included)
-MAX_STOP_SEQ_LEN = 8                         # ASD_MAX_STOP_SEQ_LEN
-MAX_TOP_LOGPROBS = 8                         # ASD_MAX_TOP_LOGPROBS
-MAX_LOGIT_EDITS = 1024                       # ASD_MAX_LOGIT_EDITS: (id, bias, until) entries of one row after merging
-MAX_LOGIT_BIAS = 100.0                       # |bias| <= 100, the range OpenAI documents
-_EDIT_FOREVER = 2 ** 31 - 1                  # `until` of a permanent ban
 _REASONS = {1: "stop", 2: "length"}
 
 
-def _check_stop_ids(ids: Sequence[int], vocab: int) -> Tuple[int, ...]:
-    ids = tuple(int(i) for i in ids)
-    if len(ids) > MAX_STOP_IDS:
-        raise ValueError(f"at most {MAX_STOP_IDS} stop token ids, got {len(ids)}")
-    if len(set(ids)) != len(ids):
-        raise ValueError("stop token ids must be distinct")
-    if any(not 0 <= i < vocab for i in ids):
-        raise ValueError(f"stop token ids must lie in [0, {vocab})")
-    return ids
-
-
-def check_max_tokens(max_tokens, n: int):
-    """generate's `max_tokens`: an int (returned as it is), or a sequence of n ints >= 1 -> a list of n ints."""
-    if isinstance(max_tokens, (int, np.integer)) and not isinstance(max_tokens, bool):
-        return int(max_tokens)
-    if isinstance(max_tokens, (str, bytes)) or not isinstance(max_tokens, (Sequence, np.ndarray)):
-        raise ValueError(f"max_tokens must be an integer or one integer per prompt, got {max_tokens!r}")
-    limits = list(max_tokens)
-    if len(limits) != n:
-        raise ValueError(f"{len(limits)} max_tokens values for {n} prompts")
-    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in limits):
-        raise ValueError(f"every per-prompt max_tokens must be an integer >= 1, got {max_tokens!r}")
-    return [int(v) for v in limits]
-
-
-def _check_stop_sequences(entries, vocab: int, tokenizer) -> List[Tuple[int, ...]]:
-    """One list of stop sequences: each entry a str (encoded by the stage's tokenizer, ids folded into the vocabulary as
-    encode_prompts folds prompt ids) or a sequence of token ids; every entry must come to 1..8 ids in [0, vocab)."""
-    if entries is None:
-        return []
-    if isinstance(entries, (str, bytes)) or not isinstance(entries, (Sequence, np.ndarray)):
-        raise ValueError(f"stop sequences must be a list of strings or token-id sequences, got {entries!r}")
-    out = []
-    for e in entries:
-        if isinstance(e, str):
-            ids = [int(i) % vocab for i in tokenizer.encode(e, return_tensors=None)]
-        elif isinstance(e, bytes) or not isinstance(e, (Sequence, np.ndarray)):
-            raise ValueError(f"a stop sequence is a string or a sequence of token ids, got {e!r}")
-        else:
-            if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in e):
-                raise ValueError(f"stop sequence token ids must be integers, got {e!r}")
-            ids = [int(t) for t in e]
-            if any(not 0 <= t < vocab for t in ids):
-                raise ValueError(f"stop sequence token ids must lie in [0, {vocab})")
-        if not 1 <= len(ids) <= MAX_STOP_SEQ_LEN:
-            raise ValueError(f"a stop sequence must come to 1..{MAX_STOP_SEQ_LEN} token ids, {e!r} gives {len(ids)}")
-        out.append(tuple(ids))
-    return out
-
-
-def _check_logprobs(n) -> int:
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
-        raise ValueError(f"logprobs must be an integer in [0, {MAX_TOP_LOGPROBS}], got {n!r}")
-    return int(n)
-
-
-def _check_min_p(v, name: str = "min_p") -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
-        raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")           # (NaN included)
-    return float(v)
-
-
-_NUMBER = (int, float, np.integer, np.floating)
-
-
-def _check_sampling_value(v, name: str):
-    """One temperature / top_p / top_k / min_p value of generate (module docstring, PER-REQUEST SAMPLING)."""
-    if name == "top_k":
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"top_k must be an integer, got {v!r}")
-        return int(v)
-    if name == "min_p":
-        return _check_min_p(v)
-    if isinstance(v, bool) or not isinstance(v, _NUMBER) or float(v) != float(v):
-        raise ValueError(f"{name} must be a number, got {v!r}")
-    v = float(v)
-    if name == "temperature" and not v >= 0.0:
-        raise ValueError("temperature must be >= 0 (0: greedy decoding)")
-    return v
-
-
-def check_per_prompt(value, n: int, name: str):
-    """generate's `temperature` / `top_p` / `top_k` / `min_p`: None (returned as it is), one value for all `n` prompts, or a
-    sequence of n values.  -> the checked value, or a list of n checked values; a sequence whose values are all equal
-    collapses to that value."""
-    if value is None:
-        return None
-    if isinstance(value, (str, bytes)):
-        raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
-    if isinstance(value, (Sequence, np.ndarray)):
-        vals = list(value)
-        if len(vals) != n:
-            raise ValueError(f"{len(vals)} {name} values for {n} prompts")
-        vals = [_check_sampling_value(v, name) for v in vals]          # (None inside a sequence raises here)
-        if vals and all(v == vals[0] for v in vals):
-            return vals[0]
-        return vals
-    return _check_sampling_value(value, name)
-
-
-def _is_seq(v) -> bool:
-    return isinstance(v, (Sequence, np.ndarray)) and not isinstance(v, (str, bytes))
-
-
-def _check_token_id(t, vocab: int, what: str) -> int:
-    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < vocab:
-        raise ValueError(f"{what} token ids must be integers in [0, {vocab}), got {t!r}")
-    return int(t)
-
-
-def _check_bias_dict(d, vocab: int) -> Dict[int, float]:
-    if d is None:
-        return {}
-    if not isinstance(d, dict):
-        raise ValueError(f"logit_bias must be a dict {{token id: bias}}, got {d!r}")
-    out = {}
-    for t, b in d.items():
-        t = _check_token_id(t, vocab, "logit_bias")
-        if isinstance(b, bool) or not isinstance(b, _NUMBER) or not abs(float(b)) <= MAX_LOGIT_BIAS:      # (NaN included)
-            raise ValueError(f"a logit bias must be a number in [-{MAX_LOGIT_BIAS:g}, {MAX_LOGIT_BIAS:g}], got {b!r}")
-        out[t] = float(b)
-    return out
-
-
-def check_logit_bias(value, n: int, vocab: int) -> List[Dict[int, float]]:
-    """generate's `logit_bias`: None, one dict for all `n` prompts, or a sequence of n dicts / Nones -> n dicts."""
-    if value is None or isinstance(value, dict):
-        d = _check_bias_dict(value, vocab)
-        return [d] * n
-    if not _is_seq(value):
-        raise ValueError(f"logit_bias must be a dict or one dict per prompt, got {value!r}")
-    if len(value) != n:
-        raise ValueError(f"{len(value)} logit_bias dicts for {n} prompts")
-    return [_check_bias_dict(d, vocab) for d in value]
-
-
-def check_banned_token_ids(value, n: int, vocab: int) -> List[Tuple[int, ...]]:
-    """generate's `banned_token_ids`: None, a sequence of ids for all `n` prompts, or a sequence of n such sequences -> n sorted
-    tuples of distinct ids."""
-    if value is None:
-        return [()] * n
-    if not _is_seq(value):
-        raise ValueError(f"banned_token_ids must be a sequence of token ids or one sequence per prompt, got {value!r}")
-    value = list(value)
-    if any(_is_seq(v) or v is None for v in value):
-        if not all(_is_seq(v) or v is None for v in value):
-            raise ValueError("banned_token_ids mixes token ids and per-prompt lists")
-        if len(value) != n:
-            raise ValueError(f"{len(value)} banned_token_ids lists for {n} prompts")
-        return [tuple(sorted({_check_token_id(t, vocab, "banned") for t in (v if v is not None else ())})) for v in value]
-    ids = tuple(sorted({_check_token_id(t, vocab, "banned") for t in value}))
-    return [ids] * n
-
-
-def check_min_tokens(value, n: int) -> List[int]:
-    """generate's `min_tokens`: an int >= 0 for all `n` prompts, or a sequence of n such ints -> n ints."""
-    def one(v):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
-            raise ValueError(f"min_tokens must be an integer >= 0, got {v!r}")
-        return min(int(v), _EDIT_FOREVER - 1)
-    if _is_seq(value):
-        if len(value) != n:
-            raise ValueError(f"{len(value)} min_tokens values for {n} prompts")
-        return [one(v) for v in value]
-    return [one(value)] * n
-
-
-def merge_logit_edits(bias: List[Dict[int, float]], banned: List[Tuple[int, ...]], min_tokens: List[int],
-                      row_seqs: List[List[Tuple[int, ...]]], vocab: int) -> List[List[Tuple[int, float, int]]]:
-    """Per row, the distinct (id, bias, until) entries of asd_logit_edit_rows (module docstring, LOGIT EDITS), sorted by id: a
-    bias has until 0, a length-1 stop entry of a row with min_tokens > 0 has until = min_tokens (and keeps its bias), a banned
-    id has until = INT32_MAX.  An entry that would do nothing (bias 0, until 0) is dropped."""
-    rows = []
-    for b, (d, ban, m, seqs) in enumerate(zip(bias, banned, min_tokens, row_seqs)):
-        entries = {t: [v, 0] for t, v in d.items()}
-        if m > 0:
-            if any(len(s) > 1 for s in seqs):
-                raise ValueError(f"prompt {b}: min_tokens > 0 is not built for a stop list that holds a multi-token stop sequence")
-            for (t,) in seqs:
-                entries.setdefault(t, [0.0, 0])[1] = m
-        for t in ban:
-            entries[t] = [0.0, _EDIT_FOREVER]
-        row = [(t, v, u) for t, (v, u) in sorted(entries.items()) if v != 0.0 or u > 0]
-        if len(row) > MAX_LOGIT_EDITS:
-            raise ValueError(f"prompt {b}: {len(row)} logit edits after merging, at most {MAX_LOGIT_EDITS}")
-        if sum(u > 0 for _, _, u in row) >= vocab:
-            raise ValueError(f"prompt {b}: the banned token ids leave no token of the vocabulary ({vocab})")
-        rows.append(row)
-    return rows
+class _Plan(NamedTuple):
+    """One generate call, checked and defaulted by Stage._plan before anything is launched or encoded: what _CallState and the
+    two loops are built from.  Nothing here lives on the device."""
+    prompts: Tuple[str, ...]
+    limits: Tuple[int, ...]                  # every row's max_tokens
+    max_tokens: int                          # the largest of them: the size of the buffers
+    greedy: bool
+    inv_t: float                             # float32(1 / temperature); 1 when greedy; the first row's on the rows route
+    scalars: Optional[Tuple[int, float, float]]     # the stage's own (top_k, top_p, min_p); None: greedy, or the rows route
+    rows: Optional[Tuple[list, list, list, list]]   # the rows route: every row's inv_t, top_k, top_p, min_p
+    stop: Tuple[int, ...]                    # the stop ids
+    row_seqs: List[list]                     # every row's stop list: the stop ids as length-1 sequences, the common ones, its own
+    finish_route: bool                       # asd_commit_step_finish: only for what the stop-id route cannot do
+    edit_rows: list                          # every row's merged (id, bias, until) entries
+    seeds: Optional[List[int]]
+    n_top: int
 
 
 class _EditState:
@@ -408,85 +231,82 @@ class _EditState:
         return self.ops.logit_edit_rows(logits, self.packed, seq_len, self.start, offset)
 
 
-class _RowsState:
-    """What a generate call on the rows route keeps (module docstring, PER-REQUEST SAMPLING): the packed tables, uploaded once.
-    `own`: each row's temperature with its own top-k / top-p / min-p; `draft` (verifying stages): each row's temperature with
-    the draft stage's configured truncation.  inv_t / top_k / top_p / min_p: the rows' values as lists."""
+# ---------------------------------------------------------------------------------------------- how a call's rows end
+# One interface for the three commit kernels: commit(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+# is the step's commit, done(seq_len, cap) makes the loop's ONE host read, outcome(...) names every row's end for `stats`.
+class _RunToLimit:
+    """No stop set: asd_commit_step_lp; every row returns exactly max_tokens tokens.  `stops` is False: stage 0 then never
+    calls done() -- it knows every position on the host -- and a verifying stage reads min(seq_len)."""
+    stops = False
 
-    def __init__(self, ops, inv_t, top_k, top_p, min_p, draft_cfg, V: int, dtype, device):
-        # (a table is packed for the dtype of the logits it is used on: `draft` for the draft stage's)
-        n = len(inv_t)
-        self.inv_t, self.top_k, self.top_p, self.min_p = list(inv_t), list(top_k), list(top_p), list(min_p)
-        self.own = ops.pack_sampling_rows(self.inv_t, self.top_k, self.top_p, self.min_p, V, dtype, device)
-        self.draft = None
-        if draft_cfg is not None:
-            self.draft = ops.pack_sampling_rows(self.inv_t, [int(draft_cfg.top_k)] * n, [float(draft_cfg.top_p)] * n,
-                                                [float(draft_cfg.min_p)] * n, V, draft_cfg.dtype, device)
+    def __init__(self, ops):
+        self.commit = ops.commit_step_lp
 
+    def done(self, seq_len: torch.Tensor, cap: int) -> bool:
+        return int(seq_len.min().item()) >= cap
 
-def _check_seed(v) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 64:
-        raise ValueError(f"seed must be an integer in [0, 2^64), got {v!r}")
-    return int(v)
+    def outcome(self, seq_len, tok_h, P: int, limits):
+        return list(limits), ["length"] * len(limits), [None] * len(limits)
 
 
-def check_seeds(seed, n: int) -> Optional[List[int]]:
-    """generate's `seed`: None, one int in [0, 2^64) for all `n` prompts, or a sequence of n such ints -> None or n ints."""
-    if seed is None:
-        return None
-    if isinstance(seed, (str, bytes)) or not isinstance(seed, (Sequence, np.ndarray)):
-        return [_check_seed(seed)] * n
-    seeds = [_check_seed(v) for v in seed]
-    if len(seeds) != n:
-        raise ValueError(f"{len(seeds)} seeds for {n} prompts")
-    return seeds
+class _Stops:
+    """What the two stopping routes keep beside seq_len: the per-sequence finished flag (1 stop, 2 length) and the counter of
+    finished sequences their commit kernels maintain -- the ONE int32 the host reads."""
+    stops = True
 
-
-def _shape_of(cfg: StageConfig) -> LMShape:
-    if cfg.shape is not None:
-        return cfg.shape
-    key = _DEFAULT_SHAPES.get(cfg.model_size, cfg.model_size)
-    if key not in QWEN25_SHAPES:
-        raise ValueError(f"no model shape for stage {cfg.model_size!r}: set StageConfig.shape")
-    return QWEN25_SHAPES[key]
-
-
-class _StopState:
-    """What a generate call with a stop set keeps beside seq_len: the ids on the device (uploaded once), the per-sequence
-    finished flag and the counter asd_commit_step_stop maintains."""
-
-    def __init__(self, stop_ids: Sequence[int], B: int, device):
-        self.B = B
-        self.stop_ids = torch.tensor(list(stop_ids), dtype=torch.int32, device=device)
+    def __init__(self, ops, B: int, device):
+        self.ops, self.B = ops, B
         self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
         self.n_finished = torch.zeros((1,), dtype=torch.int32, device=device)
 
-    def all_finished(self) -> bool:
-        return int(self.n_finished.item()) == self.B         # the loop's one host read
+    def done(self, seq_len: torch.Tensor, cap: int) -> bool:
+        return int(self.n_finished.item()) == self.B
+
+    def outcome(self, seq_len, tok_h, P: int, limits):
+        n_tok = [int(n) - P for n in seq_len.cpu().tolist()]
+        flags = self.finished.cpu().tolist()
+        if any(f not in _REASONS for f in flags) or any(not 1 <= n <= lim for n, lim in zip(n_tok, limits)):
+            raise RuntimeError("stage loop ended with an unfinished sequence")
+        return n_tok, [_REASONS[f] for f in flags], self._matches(flags, tok_h, n_tok)
 
 
-class _FinishState:
-    """What a generate call on the asd_commit_step_finish route keeps beside seq_len: every row's list of stop sequences (the
-    stop ids as length-1 sequences first) and its own length limit on the device, uploaded once, with the finished flag, the
-    counter and the index of the sequence that ended each row."""
+class _StopIds(_Stops):
+    """A stop set: asd_commit_step_stop, the ids on the device (uploaded once)."""
 
-    def __init__(self, row_seqs: List[List[Tuple[int, ...]]], limits: Sequence[int], P: int, device):
-        B = self.B = len(row_seqs)
-        self.rows = row_seqs
-        self.start = int(P)
-        self.seq_tok = self.seq_n = self.row_first = None
+    def __init__(self, ops, stop_ids: Sequence[int], B: int, device):
+        super().__init__(ops, B, device)
+        self.stop_ids = torch.tensor(list(stop_ids), dtype=torch.int32, device=device)
+
+    def commit(self, *step) -> None:
+        self.ops.commit_step_stop(*step, self.stop_ids, self.finished, self.n_finished)
+
+    def _matches(self, flags, tok_h, n_tok):
+        return [(int(tok_h[b, n_tok[b] - 1]),) if f == 1 else None for b, f in enumerate(flags)]
+
+
+class _StopSequences(_Stops):
+    """Unequal limits or multi-token stop sequences: asd_commit_step_finish.  Every row's list of stop sequences (the stop ids
+    as length-1 sequences first) and its own length limit on the device, uploaded once, and beside the flag and the counter
+    the index of the sequence that ended each row."""
+
+    def __init__(self, ops, row_seqs: List[List[Tuple[int, ...]]], limits: Sequence[int], P: int, device):
+        super().__init__(ops, len(row_seqs), device)
+        self.rows, self.start = row_seqs, int(P)
+        self.seq_tok = self.seq_n = self.row_first = self.row_max_len = None
         if any(row_seqs):
             shared = all(r == row_seqs[0] for r in row_seqs)             # one list for every row: no row_first
             self.seq_tok, self.seq_n, self.row_first = pack_stop_sequences(row_seqs[0] if shared else row_seqs, device, shared)
-        self.row_max_len = None
         if len(set(limits)) > 1:
             self.row_max_len = torch.tensor([P + int(n) for n in limits], dtype=torch.int32, device=device)
-        self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
-        self.n_finished = torch.zeros((1,), dtype=torch.int32, device=device)
-        self.matched = torch.full((B,), -1, dtype=torch.int32, device=device)
+        self.matched = torch.full((self.B,), -1, dtype=torch.int32, device=device)
 
-    def all_finished(self) -> bool:
-        return int(self.n_finished.item()) == self.B         # the loop's one host read
+    def commit(self, *step) -> None:
+        self.ops.commit_step_finish(*step, self.start, self.seq_tok, self.seq_n, self.row_first, self.row_max_len, self.finished,
+                                    self.n_finished, self.matched)
+
+    def _matches(self, flags, tok_h, n_tok):
+        which = self.matched.cpu().tolist()
+        return [self.rows[b][which[b]] if f == 1 else None for b, f in enumerate(flags)]
 
 
 class _TopState:
@@ -502,10 +322,8 @@ class _TopState:
 
     def score(self, logits: torch.Tensor) -> None:
         """logits: the rows the step commits from, [B, V] or [B, K+1, V], read where they are."""
-        if self.rows is not None:
-            self.step = self.ops.top_logprobs_rows(logits, self.n, self.rows)
-        else:
-            self.step = self.ops.top_logprobs(logits, self.n, self.inv_t)
+        self.step = self.ops.top_logprobs(logits, self.n, self.inv_t) if self.rows is None else \
+            self.ops.top_logprobs_rows(logits, self.n, self.rows)
 
     def commit(self, seq_len: torch.Tensor, n_commit: torch.Tensor) -> None:
         """Behind the step's commit, which left seq_len and n_commit."""
@@ -515,18 +333,202 @@ class _TopState:
         return dict(top_id=self.step[0].clone(), top_lp=self.step[1].clone())
 
 
-class _SeedState:
-    """What a seeded generate call keeps: the seeds on the device (uploaded once, two's-complement wrap above 2^63 - 1), the one
-    buffer every step's uniforms are written to, and the step's single ops.step_uniforms call."""
+# ---------------------------------------------------------------------------------------------- what a step draws with
+# What differs between greedy and sampled decoding, behind one interface; the loops hold everything else.
+#   draw(logits, step)   stage 0's step -> (n_acc, tok, lp) for the commit
+#   start(step)          the top of a verifying step: a seeded call's one step_uniforms launch
+#   propose(dl, k)       proposal k of a verifying step from the draft's logits -> tok
+#   settle(t_out, tok32) the target's [B, K+1, V] output against the K proposals -> (lp_t, n_acc, drawn, lp_drawn)
+# `dense`: the step reads (and edits) a contiguous copy of the logits, not the tensor the model left; kept(seq_len): the step's
+# record for Stage.step_inputs, taken before the commit and only when the stage keeps them.
+def _clones(**kept) -> dict:
+    return {k: None if v is None else v.clone() for k, v in kept.items()}
 
-    def __init__(self, ops, seeds: Sequence[int], stage: int, k_max: int, device):
-        self.ops, self.stage = ops, int(stage)
-        self.seeds = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device=device)
-        self.buf = torch.empty(((2 * k_max + 1) * len(seeds),), dtype=torch.float32, device=device)
 
-    def step(self, step: int, k_draft: int, k_accept: int, commit: bool):
+class _Greedy:
+    """temperature 0: ops.verify_greedy (K = 0 on [B, V] logits, one call on the target's output) on the tensors WHERE THEY LIE
+    -- no uniforms, no generator use, no score / bonus / draft-row copies, no kept draft logits.  A draft token is accepted iff
+    it is the target row's arg-max and the token behind the accepted prefix is the arg-max of the next row, so the text is the
+    target's own greedy continuation; log-probs are the model's at temperature 1."""
+    dense = False
+
+    def __init__(self, ops):
+        self.ops = ops
+
+    def start(self, step: int) -> None:
+        pass
+
+    def draw(self, logits, step: int):
+        self.read = logits, None
+        out = self.out = self.ops.verify_greedy(logits, None, 1.0)
+        return out[1], out[2], out[3]
+
+    def propose(self, dl, k: int):
+        return self.ops.verify_greedy(dl, None, 1.0)[2]
+
+    def settle(self, t_out, tok32):
+        self.read = t_out, tok32
+        out = self.out = self.ops.verify_greedy(t_out, tok32, 1.0)
+        return out[:4]
+
+    def kept(self, seq_len) -> dict:
+        names = ("logits", "tok", "lp_t", "n_acc", "drawn", "lp_drawn", "argmax", "lp_argmax")
+        return _clones(**dict(zip(names, (*self.read, *self.out))), seq_len=seq_len)
+
+
+class _Sampled:
+    """temperature > 0 with one (top_k, top_p, min_p) for the call.  Owns the uniforms -- torch.rand on the stage's generator:
+    stage 0 once per step; a verifying step draft_len times (B,), then (B, draft_len), then (B,), in that order; or, seeded, the
+    slots of the step's ONE ops.step_uniforms launch and no torch.rand -- the dispatch over the draft_sample* / verify_accept*
+    ops, the residual draw and the dense copies it needs (score, bonus, the K edited draft rows)."""
+    dense = True
+
+    def __init__(self, stage: "Stage", plan: _Plan, B: int, device):
+        self.ops, self.gen, self.inv_t, self.stage = stage.ops, stage.gen, plan.inv_t, stage.index
+        self.K = 0 if stage.draft is None else stage.config.draft_len
+        self.seeds = None
+        if plan.seeds is not None:               # uploaded once (two's-complement wrap above 2^63 - 1), with the one buffer every
+            wrapped = [s - 2 ** 64 if s >= 2 ** 63 else s for s in plan.seeds]           # step's uniforms are written to
+            self.seeds = torch.tensor(wrapped, dtype=torch.int64, device=device)
+            self.buf = torch.empty(((2 * max(self.K, 1) + 1) * B,), dtype=torch.float32, device=device)
+        self.own = plan.scalars
+        # the proposals: stage 0's are its own draws; a verifying stage's come from the DRAFT stage's configured truncation
+        dcfg = None if stage.draft is None else stage.draft.config
+        self.prop = plan.scalars if dcfg is None else (dcfg.top_k, dcfg.top_p, dcfg.min_p)
+        self.none_accepted = torch.zeros((B,), dtype=torch.int32, device=device) if dcfg is None else None
+        self.rd = self.u = self.r = None         # a seeded call: the step's uniforms (start)
+
+    def _uniforms(self, step: int, k_draft: int, k_accept: int, commit: bool):
         """-> (r_draft [k_draft, B] | None, u [B, k_accept] | None, r_commit [B] | None), valid until the next step."""
         return self.ops.step_uniforms(self.seeds, step, self.stage, k_draft, k_accept, commit=commit, out=self.buf)
+
+    def start(self, step: int) -> None:
+        if self.seeds is not None:               # ONE launch for every uniform of the step
+            self.rd, self.u, self.r = self._uniforms(step, self.K, self.K, True)
+        self.lpd, self.thrs, self.dls = [], [], []
+
+    def draw(self, logits, step: int):
+        if self.seeds is not None:               # stage 0's one uniform, behind the edit as it always was
+            self.rd = self._uniforms(step, 1, 0, False)[0]
+        r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device) if self.rd is None else self.rd[0]
+        tok, lp, thr = self._draft_op(logits, r)         # (tok i32, log q(tok), threshold)
+        self.last = (logits, tok, lp, thr, r)
+        return self.none_accepted, tok, lp
+
+    def propose(self, dl, k: int):
+        r = torch.rand((dl.shape[0],), generator=self.gen, device=dl.device) if self.rd is None else self.rd[k]
+        tok, lp, thr = self._draft_op(dl, r)
+        self.lpd.append(lp)
+        self.thrs.append(thr)
+        self.dls.append(dl)                      # kept (edited) for the residual distribution at a rejection
+        return tok
+
+    def settle(self, t_out, tok32):
+        B, Kd = tok32.shape
+        lp_d = torch.stack(self.lpd, 1).contiguous()
+        d_thr = torch.stack(self.thrs, 1).contiguous()
+        score = t_out[:, :Kd].contiguous()
+        bonus = t_out[:, Kd].contiguous()
+        u = torch.rand((B, Kd), generator=self.gen, device=t_out.device) if self.seeds is None else self.u
+        lp_t, n_acc, t_thr = self._verify_op(score, tok32, lp_d, u)
+        r = torch.rand((B,), generator=self.gen, device=t_out.device) if self.seeds is None else self.r
+        d_rows = torch.stack(self.dls, 1).to(score.dtype).contiguous()
+        drawn, lp_drawn = self._residual_op(score, d_rows, n_acc, r, bonus, d_thr, t_thr)
+        self.last = (score, bonus, tok32, lp_d, u, lp_t, n_acc, drawn, lp_drawn, t_thr)
+        return lp_t, n_acc, drawn, lp_drawn
+
+    def kept(self, seq_len) -> dict:
+        seeded = self.rd is not None             # only a seeded call records the uniforms it was handed
+        if self.K:
+            names = ("logits", "bonus", "tok", "lp_d", "u", "lp_t", "n_acc", "drawn", "lp_drawn", "t_thr")
+            last = dict(zip(names, self.last), seq_len=seq_len)
+            if seeded:
+                last.update(r_draft=self.rd, r_commit=self.r)
+        else:
+            last = dict(zip(("logits", "drawn", "lp_drawn", "thr"), self.last))
+            if seeded:
+                last.update(r_draft=self.last[-1][None])
+        return _clones(**last)
+
+    # ---- the ops of the call's one (top_k, top_p, min_p); positional and keyword arguments exactly as the ops' twins and
+    # recorders expect them (the uniforms by position, `min_p` only where min-p is on)
+    def _draft_op(self, logits, r):
+        top_k, top_p, min_p = self.prop
+        if min_p > 0.0:
+            return self.ops.draft_sample_min_p(logits, r, self.inv_t, top_k=top_k, top_p=top_p, min_p=min_p)
+        if top_k > 0:
+            return self.ops.draft_sample_top_k(logits, r, self.inv_t, top_k=top_k, top_p=top_p)
+        return self.ops.draft_sample(logits, r, self.inv_t, top_p)
+
+    def _verify_op(self, score, tok32, lp_d, u):
+        """-> (lp_t, n_acc, t_threshold or None) against the target's Temperature -> (TopK ->) (TopP) (-> MinP) distribution."""
+        top_k, top_p, min_p = self.own
+        if min_p > 0.0:
+            out = self.ops.verify_accept_min_p(score, tok32, lp_d, u, self.inv_t, top_k=top_k, top_p=top_p, min_p=min_p)
+        elif top_k > 0:
+            out = self.ops.verify_accept_top_k(score, tok32, lp_d, u, self.inv_t, top_k=top_k, top_p=top_p)
+        elif 0.0 < top_p < 1.0:
+            out = self.ops.verify_accept_top_p(score, tok32, lp_d, u, self.inv_t, top_p=top_p)
+        else:                                    # (nothing truncates: no threshold)
+            out = (*self.ops.verify_accept(score, tok32, lp_d, u, self.inv_t), None)
+        return out[0], out[2], out[4]
+
+    def _residual_op(self, score, d_rows, n_acc, r, bonus, d_thr, t_thr):
+        top_k, top_p, min_p = self.own
+        mp = dict(min_p=min_p) if min_p > 0.0 else {}    # (with min-p off the call is the one made before min-p existed)
+        return self.ops.residual_sample_lp(score, d_rows, n_acc, r, bonus, self.inv_t, d_threshold=d_thr, t_threshold=t_thr,
+                                           top_k=top_k, top_p=top_p, **mp)
+
+
+class _SampledRows(_Sampled):
+    """The rows route (module docstring, PER-REQUEST SAMPLING): _Sampled with every row under its own values, through the
+    packed tables, uploaded once.  `table`: each row's temperature with its own top-k / top-p / min-p; `draft` (verifying
+    stages): each row's temperature with the draft stage's configured truncation -- what the proposals are drawn with."""
+
+    def __init__(self, stage: "Stage", plan: _Plan, B: int, device):
+        super().__init__(stage, plan, B, device)
+        inv_t, top_k, top_p, min_p = plan.rows
+        V, pack = stage.shape.vocab, stage.ops.pack_sampling_rows
+        # (a table is packed for the dtype of the logits it is used on: `draft` for the draft stage's)
+        self.table = self.draft = pack(inv_t, top_k, top_p, min_p, V, stage.config.dtype, device)
+        if stage.draft is not None:
+            dcfg = stage.draft.config
+            self.draft = pack(inv_t, [int(dcfg.top_k)] * B, [float(dcfg.top_p)] * B, [float(dcfg.min_p)] * B, V, dcfg.dtype, device)
+
+    def _draft_op(self, logits, r):
+        return self.ops.draft_sample_rows(logits, r, self.draft)
+
+    def _verify_op(self, score, tok32, lp_d, u):
+        lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_rows(score, tok32, lp_d, u, self.table)
+        return lp_t, n_acc, t_thr
+
+    def _residual_op(self, score, d_rows, n_acc, r, bonus, d_thr, t_thr):
+        return self.ops.residual_sample_lp_rows(score, d_rows, n_acc, r, bonus, self.table, d_threshold=d_thr, t_threshold=t_thr)
+
+
+class _CallState:
+    """The device side of one generate call, built in this one place from the plan and the encoded prompts and handed to the
+    loop: how rows end (`end`), the logit edit (`edit`, None without an entry), the sampler and the top-N tables (`top`, None
+    when off).  Uploads happen here, once; a part that is off costs no launch."""
+
+    def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor):
+        (B, P), dev, ops = ids.shape, ids.device, stage.ops
+        self.end = _StopSequences(ops, plan.row_seqs, plan.limits, P, dev) if plan.finish_route else \
+            _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
+        self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
+        # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
+        self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
+        self.top = _TopState(ops, plan.n_top, plan.inv_t, B, P + plan.max_tokens, dev,
+                             self.sampler.table if plan.rows else None) if plan.n_top else None
+
+
+def _shape_of(cfg: StageConfig) -> LMShape:
+    if cfg.shape is not None:
+        return cfg.shape
+    key = _DEFAULT_SHAPES.get(cfg.model_size, cfg.model_size)
+    if key not in QWEN25_SHAPES:
+        raise ValueError(f"no model shape for stage {cfg.model_size!r}: set StageConfig.shape")
+    return QWEN25_SHAPES[key]
 
 
 class Stage:
@@ -568,12 +570,8 @@ class Stage:
         V = self.shape.vocab
         rows = [[i % V for i in self.tokenizer.encode(p, return_tensors=None)] for p in prompts]
         P = max(2, min(max((len(r) for r in rows), default=0), int(self.config.max_prompt_tokens)))
-        ids = torch.zeros((len(rows), P), dtype=torch.int64)
-        for b, r in enumerate(rows):
-            r = r[-P:]
-            if r:
-                ids[b, P - len(r):] = torch.tensor(r, dtype=torch.int64)
-        return ids.to(self.device)
+        rows = [[0] * (P - len(r)) + r[-P:] for r in rows]
+        return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), P).to(self.device)
 
     @staticmethod
     def decode_tokens(ids: Sequence[int]) -> str:
@@ -626,113 +624,86 @@ class Stage:
         prompt.  Draft and target logits receive the same edit, so log-probs and top-N tables are those of the edited
         distribution and a banned token is never proposed, accepted, drawn or listed (module docstring, LOGIT EDITS)."""
         t0 = time.perf_counter()
-        prompts = list(prompts)
         self.step_inputs = []
-        stop = _check_stop_ids(self.config.stop_token_ids if stop_token_ids is None else stop_token_ids, self.shape.vocab)
-        n_top = _check_logprobs(self.config.logprobs if logprobs is None else logprobs)
-        n_prompts = len(prompts)
-        own_min_p = self.config.min_p if self.draft is None else self.config.target_min_p
-        own_top_p = self.config.top_p if self.draft is None else self.config.target_top_p
-        own_top_k = self.config.top_k if self.draft is None else self.config.target_top_k
-        min_p = check_per_prompt(own_min_p if min_p is None else min_p, n_prompts, "min_p")
-        top_p = check_per_prompt(top_p, n_prompts, "top_p")
-        top_k = check_per_prompt(top_k, n_prompts, "top_k")
-        if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
-            temperature = check_per_prompt(temperature, n_prompts, "temperature")
+        plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
+                          stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens)
+        if not plan.prompts or plan.max_tokens <= 0:
+            return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
+                {"generation_time_ms": 0.0}
+        ids = self.encode_prompts(plan.prompts)
+        P = ids.shape[1]
+        state = _CallState(self, plan, ids)
+        decode = self._decode_plain if self.draft is None else self._decode_speculative
+        tokens, lps, seq_len = decode(ids, plan.max_tokens, state)
+        self.ops.check_status()
+        tok_h = tokens[:, P:].cpu().numpy()
+        lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
+        n_tok, reasons, matches = state.end.outcome(seq_len, tok_h, P, plan.limits)
+        texts = [self.decode_tokens(row[:n]) for row, n in zip(tok_h, n_tok)]
+        stats = {"generation_time_ms": (time.perf_counter() - t0) * 1000.0, "steps": float(self.last_steps),
+                 "n_tokens": n_tok, "finish_reasons": reasons, "stop_matches": matches}
+        if state.top is not None:
+            id_h, tlp_h = state.top.ids[:, P:].cpu().numpy(), state.top.lps[:, P:].cpu().numpy()
+            stats["top_token_ids"] = [np.ascontiguousarray(r[:n]) for r, n in zip(id_h, n_tok)]
+            stats["top_logprobs"] = [np.ascontiguousarray(r[:n]) for r, n in zip(tlp_h, n_tok)]
+        return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
+
+    def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
+              stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens) -> _Plan:
+        """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
+        `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
+        target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
+        cfg, V, prompts = self.config, self.shape.vocab, tuple(prompts)
+        n = len(prompts)
+        given = lambda v, default: default if v is None else v                       # noqa: E731
+        stop = _check_stop_ids(given(stop_token_ids, cfg.stop_token_ids), V)
+        n_top = _check_logprobs(given(logprobs, cfg.logprobs))
+        own_top_k, own_top_p, own_min_p = (cfg.top_k, cfg.top_p, cfg.min_p) if self.draft is None else \
+            (cfg.target_top_k, cfg.target_top_p, cfg.target_min_p)
+        min_p = check_per_prompt(given(min_p, own_min_p), n, "min_p")
+        top_p = given(check_per_prompt(top_p, n, "top_p"), float(own_top_p))
+        top_k = given(check_per_prompt(top_k, n, "top_k"), int(own_top_k))
+        if _is_seq(temperature):
+            temperature = check_per_prompt(temperature, n, "temperature")
             if isinstance(temperature, list) and any(t == 0.0 for t in temperature):
                 raise ValueError("greedy (temperature 0) and sampled rows cannot share one generate call: split the batch")
         elif isinstance(temperature, bool):
             raise ValueError(f"temperature must be a number, got {temperature!r}")
-        seeds = check_seeds(seed, len(prompts))
-        max_tokens = check_max_tokens(max_tokens, len(prompts))
-        common = _check_stop_sequences(self.config.stop_sequences if stop_sequences is None else stop_sequences,
-                                       self.shape.vocab, self.tokenizer)
+        seeds = check_seeds(seed, n)
+        max_tokens = check_max_tokens(max_tokens, n)
+        common = _check_stop_sequences(given(stop_sequences, cfg.stop_sequences), V, self.tokenizer)
         own = [[] for _ in prompts]
         if stop_sequences_per_prompt is not None:
-            if isinstance(stop_sequences_per_prompt, (str, bytes)) or len(stop_sequences_per_prompt) != len(prompts):
-                raise ValueError(f"stop_sequences_per_prompt must hold one list per prompt ({len(prompts)})")
-            own = [_check_stop_sequences(e, self.shape.vocab, self.tokenizer) for e in stop_sequences_per_prompt]
+            if isinstance(stop_sequences_per_prompt, (str, bytes)) or len(stop_sequences_per_prompt) != n:
+                raise ValueError(f"stop_sequences_per_prompt must hold one list per prompt ({n})")
+            own = [_check_stop_sequences(e, V, self.tokenizer) for e in stop_sequences_per_prompt]
         row_seqs = [[(i,) for i in stop] + common + o for o in own]
         for r in row_seqs:
             if len(r) > MAX_STOP_SEQS:
                 raise ValueError(f"a prompt's stop list (stop ids included) holds at most {MAX_STOP_SEQS} entries, got {len(r)}")
             if len(set(r)) != len(r):
                 raise ValueError("the stop sequences of a prompt must be distinct")
-        edit_rows = merge_logit_edits(
-            check_logit_bias(self.config.logit_bias if logit_bias is None else logit_bias, n_prompts, self.shape.vocab),
-            check_banned_token_ids(self.config.banned_token_ids if banned_token_ids is None else banned_token_ids, n_prompts,
-                                   self.shape.vocab),
-            check_min_tokens(self.config.min_tokens if min_tokens is None else min_tokens, n_prompts), row_seqs, self.shape.vocab)
-        limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * len(prompts)
-        # the asd_commit_step_finish route: only for what the stop-id route cannot do (module docstring, HOW A ROW ENDS)
-        finish_route = len(set(limits)) > 1 or bool(common) or any(own)
-        max_tokens = max(limits, default=0)
-        if not prompts or max_tokens <= 0:
-            return ["" for _ in prompts], ([np.zeros(0, np.float32) for _ in prompts] if return_logprobs else None), \
-                {"generation_time_ms": 0.0}
-        if not isinstance(temperature, list) and not temperature >= 0.0:     # (NaN included; a list was checked above)
+        edit_rows = merge_logit_edits(check_logit_bias(given(logit_bias, cfg.logit_bias), n, V),
+                                      check_banned_token_ids(given(banned_token_ids, cfg.banned_token_ids), n, V),
+                                      check_min_tokens(given(min_tokens, cfg.min_tokens), n), row_seqs, V)
+        limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
+        limit = max(limits, default=0)
+        live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
+        if live and not isinstance(temperature, list) and not temperature >= 0.0:     # (NaN included)
             raise ValueError("temperature must be >= 0 (0: greedy decoding)")
-        ids = self.encode_prompts(prompts)
-        B, P = ids.shape
-        if finish_route:
-            end = _FinishState(row_seqs, limits, P, ids.device)
-        else:
-            end = _StopState(stop, B, ids.device) if stop else None
-        # logit edits: only where the call has an entry -- without one the ops calls are the ones made before
-        edit = _EditState(self.ops, edit_rows, P, ids.device) if any(edit_rows) else None
-        rows = None
-        if not isinstance(temperature, list) and temperature == 0.0:
-            pass                                         # greedy: no draws, no truncation, no table
-        elif any(isinstance(v, list) for v in (temperature, top_p, top_k, min_p)):
-            # the rows route (module docstring, PER-REQUEST SAMPLING): every row's four values, the tables packed once
-            per_row = lambda v, default: list(v) if isinstance(v, list) else [default if v is None else v] * B   # noqa: E731
-            temps = per_row(temperature, None)
-            rows = _RowsState(self.ops, [float(np.float32(1.0 / t)) for t in temps], per_row(top_k, int(own_top_k)),
-                              per_row(top_p, float(own_top_p)), per_row(min_p, 0.0),
-                              None if self.draft is None else self.draft.config, self.shape.vocab, self.config.dtype, ids.device)
-            temperature = temps[0]                       # (positive: the scalar below only selects the sampled loops)
-        inv_t = 1.0 if temperature == 0.0 else float(np.float32(1.0 / temperature))
-        top = _TopState(self.ops, n_top, inv_t, B, P + int(max_tokens), ids.device,
-                        None if rows is None else rows.own) if n_top else None
-        rng = None
-        if seeds is not None and temperature != 0.0:
-            rng = _SeedState(self.ops, seeds, self.index, 1 if self.draft is None else self.config.draft_len, ids.device)
-        if temperature == 0.0:                           # greedy: no draws, no truncation (module docstring)
-            decode = self._decode_plain_greedy if self.draft is None else self._decode_speculative_greedy
-            tokens, lps, seq_len = decode(ids, int(max_tokens), end, top, edit)
-        elif self.draft is None:
-            tokens, lps, seq_len = self._decode_plain(ids, int(max_tokens), inv_t,
-                                                      self.config.top_p if top_p is None or rows else float(top_p), end, top,
-                                                      0.0 if rows else min_p, rng, None if rows else top_k, rows, edit)
-        else:
-            tokens, lps, seq_len = self._decode_speculative(ids, int(max_tokens), inv_t,
-                                                            self.config.target_top_p if top_p is None or rows else float(top_p),
-                                                            end, top, 0.0 if rows else min_p, rng, None if rows else top_k, rows,
-                                                            edit)
-        self.ops.check_status()
-        tok_h = tokens[:, P:].cpu().numpy()
-        lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
-        if end is None:
-            n_tok, reasons, matches = [int(max_tokens)] * B, ["length"] * B, [None] * B
-        else:
-            n_tok = [int(n) - P for n in seq_len.cpu().tolist()]
-            flags = end.finished.cpu().tolist()
-            if any(f not in _REASONS for f in flags) or any(not 1 <= n <= lim for n, lim in zip(n_tok, limits)):
-                raise RuntimeError("stage loop ended with an unfinished sequence")
-            reasons = [_REASONS[f] for f in flags]
-            if finish_route:
-                which = end.matched.cpu().tolist()
-                matches = [end.rows[b][which[b]] if f == 1 else None for b, f in enumerate(flags)]
-            else:
-                matches = [(int(tok_h[b, n_tok[b] - 1]),) if f == 1 else None for b, f in enumerate(flags)]
-        texts = [self.decode_tokens(row[:n]) for row, n in zip(tok_h, n_tok)]
-        stats = {"generation_time_ms": (time.perf_counter() - t0) * 1000.0, "steps": float(self.last_steps),
-                 "n_tokens": n_tok, "finish_reasons": reasons, "stop_matches": matches}
-        if top is not None:
-            id_h, tlp_h = top.ids[:, P:].cpu().numpy(), top.lps[:, P:].cpu().numpy()
-            stats["top_token_ids"] = [np.ascontiguousarray(r[:n]) for r, n in zip(id_h, n_tok)]
-            stats["top_logprobs"] = [np.ascontiguousarray(r[:n]) for r, n in zip(tlp_h, n_tok)]
-        return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
+        greedy = not live or (not isinstance(temperature, list) and temperature == 0.0)
+        scalars = rows = None
+        if not greedy and any(isinstance(v, list) for v in (temperature, top_p, top_k, min_p)):
+            # the rows route (module docstring, PER-REQUEST SAMPLING): every row's four values
+            temps, top_k, top_p, min_p = (v if isinstance(v, list) else [v] * n for v in (temperature, top_k, top_p, min_p))
+            rows = ([float(np.float32(1.0 / t)) for t in temps], top_k, top_p, min_p)
+            temperature = temps[0]
+        elif not greedy:
+            scalars = (top_k, top_p, min_p)
+        return _Plan(prompts=prompts, limits=tuple(limits), max_tokens=int(limit), greedy=greedy,
+                     inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
+                     stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
+                     edit_rows=edit_rows, seeds=seeds, n_top=n_top)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -744,206 +715,59 @@ class Stage:
         n_commit = torch.zeros((B,), dtype=torch.int32, device=dev)
         return tokens, lps, seq_len, n_commit
 
-    def _propose(self, cfg: StageConfig, logits: torch.Tensor, inv_t: float, top_p: float, min_p: float = 0.0, r=None,
-                 top_k: Optional[int] = None, table=None):
-        """One proposal per sequence from next-token logits [B, V] under Temperature -> (TopK ->) TopP (-> MinP): (tok i32,
-        log q(tok), threshold).  r: the [B] uniforms of a seeded call; None: drawn from the stage's generator.  top_k: None =
-        cfg.top_k.  table: the rows route's packed table -- every row under its own parameters, the scalars unused."""
-        logits = logits.contiguous()
-        if r is None:
-            r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device)
-        if table is not None:
-            return self.ops.draft_sample_rows(logits, r, table)
-        top_k = cfg.top_k if top_k is None else top_k
-        if min_p > 0.0:
-            return self.ops.draft_sample_min_p(logits, r, inv_t, top_k=top_k, top_p=top_p, min_p=min_p)
-        if top_k > 0:
-            return self.ops.draft_sample_top_k(logits, r, inv_t, top_k=top_k, top_p=top_p)
-        return self.ops.draft_sample(logits, r, inv_t, top_p)
-
-    def _commit(self, end, tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap):
-        if end is None:
-            self.ops.commit_step_lp(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
-        elif isinstance(end, _FinishState):
-            self.ops.commit_step_finish(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap, end.start,
-                                        end.seq_tok, end.seq_n, end.row_first, end.row_max_len, end.finished, end.n_finished,
-                                        end.matched)
-        else:
-            self.ops.commit_step_stop(tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap, end.stop_ids,
-                                      end.finished, end.n_finished)
-
-    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, inv_t: float, top_p: float, end=None, top=None,
-                      min_p: float = 0.0, rng=None, top_k: Optional[int] = None, per_row=None, edit=None):
+    def _decode_plain(self, ids: torch.Tensor, max_tokens: int, st: _CallState):
         """Stage 0.  Without a stop set every sequence appends exactly one token per step, so all positions are known on the
-        host; with one (`end`), a sequence is fed its last committed token at seq_len - 1, which is the same for a running
-        sequence and stays put for a finished one."""
+        host and nothing is read back; with one (`st.end.stops`), a sequence is fed its last committed token at seq_len - 1,
+        which is the same for a running sequence and stays put for a finished one."""
         B, P = ids.shape
         dev = ids.device
         cap = P + max_tokens
+        end, edit, top, sampler = st.end, st.edit, st.top, st.sampler
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
         m.alloc_ragged(B, cap + 1)
-        none_accepted = torch.zeros((B,), dtype=torch.int32, device=dev)
         logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
         for step in range(max_tokens):
-            logits = logits.contiguous()
+            if sampler.dense:
+                logits = logits.contiguous()
             if edit is not None:
                 edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
-            r = None if rng is None else rng.step(step, 1, 0, False)[0][0]      # seeded: the step's one launch
-            tok, lp, thr = self._propose(self.config, logits, inv_t, top_p, min_p, r, top_k, None if per_row is None else per_row.own)
+            n_acc, tok, lp = sampler.draw(logits, step)
+            kept = sampler.kept(seq_len) if self.keep_inputs else None
             if top is not None:
                 top.score(logits)
-            self._commit(end, None, None, none_accepted, tok, lp, seq_len, tokens, lps, n_commit, cap)
+            end.commit(None, None, n_acc, tok, lp, seq_len, tokens, lps, n_commit, cap)
             if top is not None:
                 top.commit(seq_len, n_commit)
-            if self.keep_inputs:
-                self.step_inputs.append(dict(logits=logits.clone(), drawn=tok.clone(), lp_drawn=lp.clone(), thr=thr.clone()))
-                if r is not None:
-                    self.step_inputs[-1].update(r_draft=r[None].clone())
-                if top is not None:
-                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
+            if kept is not None:                                        # tests: the record, with the top-N rows behind it
+                self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
             self.last_steps = step + 1
-            if end is not None and (step + 1) % self.config.sync_every == 0 and end.all_finished():
+            if end.stops and (step + 1) % self.config.sync_every == 0 and end.done(seq_len, cap):
                 break
             if step + 1 < max_tokens:
-                if end is None:
-                    pos = torch.full((B,), P + step, dtype=torch.int64, device=dev)
-                    last = tok.to(torch.int64)[:, None]
-                else:
+                if end.stops:
                     pos = seq_len.to(torch.int64) - 1
                     last = tokens.gather(1, pos[:, None]).to(torch.int64)
+                else:
+                    pos = torch.full((B,), P + step, dtype=torch.int64, device=dev)
+                    last = tok.to(torch.int64)[:, None]
                 logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
         return tokens, lps, seq_len
 
-    def _decode_plain_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None, edit=None):
-        """Stage 0 at temperature 0: _decode_plain with one verify_greedy call (K = 0) per step in place of the draw; the logits
-        are read where the model left them."""
-        B, P = ids.shape
-        dev = ids.device
-        cap = P + max_tokens
-        tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
-        m = self.model
-        m.reset()
-        m.alloc_ragged(B, cap + 1)
-        logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
-        for step in range(max_tokens):
-            if edit is not None:
-                edit.apply(logits, seq_len)                              # in place, where the model left the logits
-            lp_t, n_acc, tok, lp, argmax, lp_argmax = self.ops.verify_greedy(logits, None, 1.0)
-            if self.keep_inputs:
-                self.step_inputs.append(dict(logits=logits.clone(), tok=None, n_acc=n_acc.clone(), argmax=argmax.clone(),
-                                             lp_argmax=lp_argmax.clone(), lp_t=lp_t.clone(), drawn=tok.clone(),
-                                             lp_drawn=lp.clone(), seq_len=seq_len.clone()))
-            if top is not None:
-                top.score(logits)
-            self._commit(end, None, None, n_acc, tok, lp, seq_len, tokens, lps, n_commit, cap)
-            if top is not None:
-                top.commit(seq_len, n_commit)
-                if self.keep_inputs:
-                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
-            self.last_steps = step + 1
-            if end is not None and (step + 1) % self.config.sync_every == 0 and end.all_finished():
-                break
-            if step + 1 < max_tokens:
-                if end is None:
-                    pos = torch.full((B,), P + step, dtype=torch.int64, device=dev)
-                    last = tok.to(torch.int64)[:, None]
-                else:
-                    pos = seq_len.to(torch.int64) - 1
-                    last = tokens.gather(1, pos[:, None]).to(torch.int64)
-                logits = m.forward_ragged(last, pos, P + step + 1)[:, -1]
-        return tokens, lps, seq_len
+    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, st: _CallState):
+        """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
 
-    def _decode_speculative_greedy(self, ids: torch.Tensor, max_tokens: int, end=None, top=None, edit=None):
-        """Stage s > 0 at temperature 0: _decode_speculative's step with the draft's arg-max as the proposal (K = 0 calls on the
-        draft logits) and ONE verify_greedy call on the target's [B, K+1, V] output as returned -- no copies of the score and
-        bonus rows, no kept draft logits, no uniforms.  A draft token is accepted iff it is the target row's arg-max, the token
-        behind the accepted prefix is the arg-max of the next row (row K: the bonus row), so the text is the target's own greedy
-        continuation.  Log-probs are the target's at temperature 1."""
+        Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
+        < L - 1 and the draft's for positions < L - 2, so the target is fed [t_{L-1}, d_0 .. d_{K-1}] at position L - 1 (row i
+        scores d_i, row K is the bonus row) and the draft first re-feeds the last two committed tokens."""
         cfg = self.config
         draft, target = self.draft.model, self.model
         B, P = ids.shape
         dev = ids.device
         Kd = cfg.draft_len
         cap = P + max_tokens
-        tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
-        for m in (draft, target):
-            m.reset()
-            m.alloc_ragged(B, cap + Kd + 2)
-        zero = torch.zeros((B,), dtype=torch.int64, device=dev)
-        target.forward_ragged(ids[:, :P - 1], zero, P)
-        if P > 2:
-            draft.forward_ragged(ids[:, :P - 2], zero, P)
-        rows = torch.arange(B, device=dev)
-        steps = 0
-        while True:
-            L = seq_len.to(torch.int64)
-            window = min(P + steps * (Kd + 1) + Kd + 1, cap + Kd + 2)
-            last2 = torch.stack([tokens[rows, L - 2], tokens[rows, L - 1]], 1).to(torch.int64)
-            dl = draft.forward_ragged(last2, L - 2, window)[:, -1]
-            toks = []
-            for k in range(Kd):
-                if edit is not None:
-                    edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
-                t = self.ops.verify_greedy(dl, None, 1.0)[2]
-                toks.append(t)
-                if k + 1 < Kd:
-                    dl = draft.forward_ragged(t.to(torch.int64)[:, None], L + k, window)[:, -1]
-            tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
-            t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
-            if edit is not None:
-                edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows
-            lp_t, n_acc, drawn, lp_drawn, argmax, lp_argmax = self.ops.verify_greedy(t_out, tok32, 1.0)
-            if self.keep_inputs:
-                self.step_inputs.append(dict(logits=t_out.clone(), tok=tok32.clone(), n_acc=n_acc.clone(), argmax=argmax.clone(),
-                                             lp_argmax=lp_argmax.clone(), lp_t=lp_t.clone(), drawn=drawn.clone(),
-                                             lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone()))
-            if top is not None:
-                top.score(t_out)
-            self._commit(end, tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
-            if top is not None:
-                top.commit(seq_len, n_commit)
-                if self.keep_inputs:
-                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
-            steps += 1
-            if steps % cfg.sync_every == 0 and (int(seq_len.min().item()) >= cap if end is None else end.all_finished()):
-                break
-            if steps > max_tokens + cfg.sync_every:
-                raise RuntimeError("stage loop did not terminate")
-        self.last_steps = steps
-        return tokens, lps, seq_len
-
-    def _verify(self, score, tok32, lp_d, u, inv_t, top_k, top_p, min_p=0.0):
-        """-> (lp_t, n_acc, t_threshold or None) against the target's Temperature -> (TopK ->) (TopP) (-> MinP) distribution."""
-        if min_p > 0.0:
-            lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_min_p(score, tok32, lp_d, u, inv_t, top_k=top_k, top_p=top_p,
-                                                                       min_p=min_p)
-            return lp_t, n_acc, t_thr
-        if top_k > 0:
-            lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_top_k(score, tok32, lp_d, u, inv_t, top_k=top_k, top_p=top_p)
-            return lp_t, n_acc, t_thr
-        if 0.0 < top_p < 1.0:
-            lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_top_p(score, tok32, lp_d, u, inv_t, top_p=top_p)
-            return lp_t, n_acc, t_thr
-        lp_t, _, n_acc, _ = self.ops.verify_accept(score, tok32, lp_d, u, inv_t)
-        return lp_t, n_acc, None
-
-    def _decode_speculative(self, ids: torch.Tensor, max_tokens: int, inv_t: float, target_top_p: float, end=None, top=None,
-                            target_min_p: float = 0.0, rng=None, target_top_k: Optional[int] = None, per_row=None, edit=None):
-        """Stage s > 0: speculative_generate_ragged's step on `ops`, with the log-probs committed beside the tokens.
-
-        Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed; the target's KV is valid for positions
-        < L - 1 and the draft's for positions < L - 2, so the target is fed [t_{L-1}, d_0 .. d_{K-1}] at position L - 1 (row i
-        scores d_i, row K is the bonus row) and the draft first re-feeds the last two committed tokens."""
-        cfg, dcfg = self.config, self.draft.config
-        draft, target = self.draft.model, self.model
-        B, P = ids.shape
-        dev = ids.device
-        Kd = cfg.draft_len
-        if target_top_k is None:
-            target_top_k = cfg.target_top_k
-        cap = P + max_tokens
+        end, edit, top, sampler = st.end, st.edit, st.top, st.sampler
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
             m.reset()
@@ -959,62 +783,31 @@ class Stage:
             window = min(P + steps * (Kd + 1) + Kd + 1, cap + Kd + 2)   # host-side bound on every position touched this step
             last2 = torch.stack([tokens[rows, L - 2], tokens[rows, L - 1]], 1).to(torch.int64)
             dl = draft.forward_ragged(last2, L - 2, window)[:, -1]
-            # seeded: ONE launch for every uniform of the step (proposal k takes rd[k], the verify u, the commit draw r)
-            rd, u, r = (None, None, None) if rng is None else rng.step(steps, Kd, Kd, True)
-            toks, lpd, dls, thrs = [], [], [], []
+            sampler.start(steps)
+            toks = []
             for k in range(Kd):
-                dl = dl.contiguous()
+                if sampler.dense:
+                    dl = dl.contiguous()
                 if edit is not None:
                     edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
-                t, lp, thr = self._propose(dcfg, dl, inv_t, dcfg.top_p, dcfg.min_p, None if rd is None else rd[k],
-                                           table=None if per_row is None else per_row.draft)
-                toks.append(t)
-                lpd.append(lp)
-                thrs.append(thr)
-                dls.append(dl)                                          # kept (edited) for the residual distribution at a rejection
+                toks.append(sampler.propose(dl, k))
                 if k + 1 < Kd:
-                    dl = draft.forward_ragged(t.to(torch.int64)[:, None], L + k, window)[:, -1]
+                    dl = draft.forward_ragged(toks[-1].to(torch.int64)[:, None], L + k, window)[:, -1]
             tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
-            lp_d = torch.stack(lpd, 1).contiguous()
-            d_thr = torch.stack(thrs, 1).contiguous()
             t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
             if edit is not None:
-                edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any copy
-            score = t_out[:, :Kd].contiguous()
-            bonus = t_out[:, Kd].contiguous()
-            if rng is None:
-                u = torch.rand((B, Kd), generator=self.gen, device=dev)
-            if per_row is not None:                         # every row against its own target distribution
-                lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_rows(score, tok32, lp_d, u, per_row.own)
-            else:
-                lp_t, n_acc, t_thr = self._verify(score, tok32, lp_d, u, inv_t, target_top_k, target_top_p, target_min_p)
-            if rng is None:
-                r = torch.rand((B,), generator=self.gen, device=dev)
-            d_rows = torch.stack(dls, 1).to(score.dtype).contiguous()
-            if per_row is not None:
-                drawn, lp_drawn = self.ops.residual_sample_lp_rows(score, d_rows, n_acc, r, bonus, per_row.own, d_threshold=d_thr,
-                                                                   t_threshold=t_thr)
-            else:
-                # (the min_p keyword only where it is on: with it off the call is the one made before)
-                mp = dict(min_p=target_min_p) if target_min_p > 0.0 else {}
-                drawn, lp_drawn = self.ops.residual_sample_lp(score, d_rows, n_acc, r, bonus, inv_t, d_threshold=d_thr,
-                                                              t_threshold=t_thr, top_k=target_top_k, top_p=target_top_p, **mp)
-            if self.keep_inputs:
-                self.step_inputs.append(dict(logits=score.clone(), bonus=bonus.clone(), tok=tok32.clone(), lp_d=lp_d.clone(),
-                                             u=u.clone(), lp_t=lp_t.clone(), n_acc=n_acc.clone(), drawn=drawn.clone(),
-                                             lp_drawn=lp_drawn.clone(), seq_len=seq_len.clone(),
-                                             t_thr=None if t_thr is None else t_thr.clone()))
-                if rd is not None:
-                    self.step_inputs[-1].update(r_draft=rd.clone(), r_commit=r.clone())
+                edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any slice
+            lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
+            kept = sampler.kept(seq_len) if self.keep_inputs else None
             if top is not None:
-                top.score(t_out)                                        # the [B, K+1, V] output as returned, not the copies
-            self._commit(end, tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+                top.score(t_out)                                        # the [B, K+1, V] output as returned, not a copy
+            end.commit(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
             if top is not None:
                 top.commit(seq_len, n_commit)
-                if self.keep_inputs:
-                    self.step_inputs[-1].update(top.record(), n_commit=n_commit.clone())
+            if kept is not None:                                        # tests: the record, with the top-N rows behind it
+                self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
             steps += 1
-            if steps % cfg.sync_every == 0 and (int(seq_len.min().item()) >= cap if end is None else end.all_finished()):
+            if steps % cfg.sync_every == 0 and end.done(seq_len, cap):
                 break
             if steps > max_tokens + cfg.sync_every:      # cannot happen: every step appends >= 1 token per unfinished row
                 raise RuntimeError("stage loop did not terminate")

@@ -3,7 +3,7 @@ ops of distributed.HipOps, the mixed parameter sets the CPU and GPU stage tests 
 tests/stage_scenario.py with each row's own temperature and thresholds.
 
 RowsOracleOps implements a *_rows op by calling the SCALAR twin op the stage loop would call for that row's values
-(Stage._propose / Stage._verify's dispatch) on the one-row slice: row b of a mixed call is the scalar call's row by
+(the dispatch of serving/stages.py's _Sampled) on the one-row slice: row b of a mixed call is the scalar call's row by
 construction, which is the semantics include/asd_hip.h states for the kernels.
 
 TEST INFRASTRUCTURE, like tests/stage_scenario.py: never importable from the package."""
@@ -118,7 +118,7 @@ class RowsOracleOps(MinPOracleOps):
         return rows.inv_t[b], k, rows.top_p[b], rows.min_p[b]
 
     def _draft_row(self, logits, r, inv_t, top_k, top_p, min_p):
-        """Stage._propose's dispatch."""
+        """_Sampled._draft_op's dispatch."""
         if min_p > 0.0:
             return self.draft_sample_min_p(logits, r, inv_t, top_k=top_k, top_p=top_p, min_p=min_p)
         if top_k > 0:
@@ -126,7 +126,7 @@ class RowsOracleOps(MinPOracleOps):
         return self.draft_sample(logits, r, inv_t, top_p)
 
     def _verify_row(self, logits, tok, lp_d, u, inv_t, top_k, top_p, min_p):
-        """Stage._verify's dispatch; the plain verify's outputs completed with thr = -inf and the leading finite run."""
+        """_Sampled._verify_op's dispatch; the plain verify's outputs completed with thr = -inf and the leading finite run."""
         if min_p > 0.0:
             return self.verify_accept_min_p(logits, tok, lp_d, u, inv_t, top_k=top_k, top_p=top_p, min_p=min_p)
         if top_k > 0:
