@@ -36,6 +36,7 @@ SOURCES = {
     "top_logprobs.hip": ["-ffp-contract=off"],    # greedy.hip's (m2, s) stream and row_logprob: slot 0 has lp_argmax's bits
     "philox.hip": [],                             # integer arithmetic and one exact conversion: no flag changes its bits
     "logit_edit.hip": [],                         # one f32 addition and one conversion per edited element: nothing to contract
+    "logit_mask.hip": [],                         # bit tests and stores of a constant: no floating-point arithmetic at all
     "lm_head_verify.hip": ["-ffp-contract=off"],  # ends in the same finish_row arithmetic as verify_accept.hip
     "decision.hip": ["-ffp-contract=off"],
     "predictor.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=11"],   # k_predictor_stop_w64x32's leading arguments

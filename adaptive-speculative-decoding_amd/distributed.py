@@ -421,6 +421,19 @@ class HipOps:
         launch, no workspace; a stage loop makes the call once per logits tensor and only when the call has an entry."""
         return self.K.logit_edit_rows(logits, edits, seq_len, start, offset)
 
+    def pack_token_masks(self, rows, V, device):
+        """One sorted tuple of allowed token ids (or None: no list) per batch row -> the device bitmasks of logit_mask_rows
+        (kernels.pack_token_masks: built with numpy on the host, uploaded once per generate call; equal lists share one mask)."""
+        return self.K.pack_token_masks(rows, V, device)
+
+    @traced("logit_mask_rows")
+    def logit_mask_rows(self, logits, masks):
+        """The dense allow-list ahead of the samplers (asd_logit_mask_rows): logits [B, V] or [B, K1, V] (any strides with a
+        unit last stride) -> the same tensor, masked: element v of every position of row b is -inf where bit v of the row's
+        mask is clear; a row without a list is not touched.  One launch, a write stream, no workspace; a stage loop makes the
+        call once per logits tensor, in front of logit_edit_rows, and only when some row of the call has a list."""
+        return self.K.logit_mask_rows(logits, masks)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

@@ -1240,3 +1240,79 @@ def logit_edit_rows(logits: torch.Tensor, edits: LogitEdits, seq_len: torch.Tens
                                     edits.n, _dev(seq_len, "seq_len", torch.int32), int(start), int(offset), _stream())
     B.check("asd_logit_edit_rows", rc)
     return logits
+
+
+# ------------------------------------------------------------------------------- token masks (allowed_token_ids)
+@dataclass
+class TokenMasks:
+    """The mask arrays of asd_logit_mask_rows on the device (pack_token_masks): bits i32 [R, W], W = (V + 31) // 32, bit
+    v & 31 of word v >> 5 set = token v is kept; mask_row i32 [B] (-1: the row has no list and is not touched), or None when
+    every row uses mask 0."""
+    bits: torch.Tensor
+    mask_row: Optional[torch.Tensor]
+    R: int                                   # distinct masks uploaded
+    B: int                                   # rows the masks were packed for
+    V: int
+
+
+def check_token_mask_rows(rows, V: int):
+    """The host side of pack_token_masks: `rows` = one sorted tuple of allowed ids, or None, per batch row -> (bits: numpy
+    uint32 [R, W], mask_row: list of B ints with -1 for None, or None when every row uses mask 0).  Equal lists share one
+    mask, so R <= B."""
+    V = int(V)
+    if V < 1:
+        raise ValueError("V must be >= 1")
+    W = (V + 31) // 32
+    index, masks, mask_row = {}, [], []
+    for r, ids in enumerate(rows):
+        if ids is None:
+            mask_row.append(-1)
+            continue
+        key = tuple(int(t) for t in ids)
+        if key not in index:
+            a = np.asarray(key, dtype=np.int64)
+            if a.size and (a.min() < 0 or a.max() >= V):
+                raise ValueError(f"the allowed token ids of row {r} must lie in [0, {V})")
+            words = np.zeros(W, dtype=np.uint32)
+            np.bitwise_or.at(words, a >> 5, np.uint32(1) << (a & 31).astype(np.uint32))
+            index[key] = len(masks)
+            masks.append(words)
+        mask_row.append(index[key])
+    bits = np.stack(masks) if masks else np.zeros((0, W), dtype=np.uint32)
+    return bits, (None if mask_row and all(m == 0 for m in mask_row) else mask_row)
+
+
+def pack_token_masks(rows, V: int, device) -> TokenMasks:
+    """The bitmasks of logit_mask_rows from host lists: `rows` holds one sorted tuple of allowed token ids per batch row, or
+    None for a row without a list.  The bits are built with numpy on the host and uploaded once; equal lists share one mask."""
+    rows = list(rows)
+    bits, mask_row = check_token_mask_rows(rows, V)
+    return TokenMasks(torch.from_numpy(bits.view(np.int32)).to(device),
+                      None if mask_row is None else torch.tensor(mask_row, dtype=torch.int32).to(device),
+                      int(bits.shape[0]), len(rows), int(V))
+
+
+def logit_mask_rows(logits: torch.Tensor, masks: TokenMasks) -> torch.Tensor:
+    """Mask `logits` in place (asd_logit_mask_rows) and return it: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  Element v of every position of row b becomes -inf where bit v of the row's mask is
+    clear; a row without a list (mask_row -1) and everything else in the allocation keep their bits."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if masks.B != Bv or masks.V != V:
+        raise ValueError(f"the masks were packed for {masks.B} rows of {masks.V} tokens; logits have {Bv} rows of {V}")
+    if tuple(masks.bits.shape) != (masks.R, (V + 31) // 32):
+        raise ValueError("mask bits must be int32 [R, (V + 31) // 32]")
+    # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
+    ld_row = view.stride(1) if K1 > 1 else V
+    ld_seq = view.stride(0) if Bv > 1 else K1 * ld_row
+    if ld_row < V or ld_seq < K1 * ld_row:
+        raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= K1 row strides")
+    rc = _lib().asd_logit_mask_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
+                                    _dev(masks.bits, "mask bits", torch.int32), masks.R,
+                                    _opt(masks.mask_row, "mask_row", torch.int32), _stream())
+    B.check("asd_logit_mask_rows", rc)
+    return logits

@@ -31,8 +31,9 @@ is handled -- and returns the results in request order.
 Logit edits (OpenAI's `logit_bias`, vLLM's `bad_words` / `min_tokens`; serving/stages.py, LOGIT EDITS): `batch_process(logit_bias=,
 banned_token_ids=, min_tokens=)` take one value for the batch -- a dict, a sequence of token ids, an int -- or one per request
 (a sequence of dicts / Nones, a sequence of id sequences, a sequence of ints), and `process_request` takes the same three for its
-one request.  A per-request value travels with the request like its `top_p`; a keyword reaches `stage.generate` only when it was
-given.  The values are checked by the stage (which knows the vocabulary); only the per-request lengths are checked here.
+one request.  `allowed_token_ids=` (vLLM's; serving/stages.py, ALLOW-LISTS) travels the same way: a sequence of ids for the
+batch, or one sequence (or None: no list) per request.  A per-request value travels with the request like its `top_p`; a keyword
+reaches `stage.generate` only when it was given.  The values are checked by the stage (which knows the vocabulary); only the per-request lengths are checked here.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -79,13 +80,13 @@ from .stages import _is_seq, check_max_tokens, check_per_prompt, check_seeds
 
 logger = logging.getLogger(__name__)
 
-_EDIT_KEYS = ("logit_bias", "banned_token_ids", "min_tokens")
+_EDIT_KEYS = ("logit_bias", "banned_token_ids", "min_tokens", "allowed_token_ids")
 
 
-def check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n: int) -> Dict[str, Any]:
-    """The three logit-edit keywords of batch_process -> {name: value} of those that were given: a `list` of n values where
-    the batch carries one per request, anything else (a dict, a tuple of ids, an int) is one value for the batch.  Only the
-    shapes are looked at here; stage.generate checks the values."""
+def check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n: int, allowed_token_ids=None) -> Dict[str, Any]:
+    """The logit-edit keywords of batch_process (the three sparse ones and the allow-list) -> {name: value} of those that were
+    given: a `list` of n values where the batch carries one per request, anything else (a dict, a tuple of ids, an int) is one
+    value for the batch.  Only the shapes are looked at here; stage.generate checks the values."""
     out: Dict[str, Any] = {}
     if logit_bias is not None:
         if _is_seq(logit_bias):
@@ -94,16 +95,18 @@ def check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n: int) -> D
             out["logit_bias"] = list(logit_bias)
         else:
             out["logit_bias"] = logit_bias
-    if banned_token_ids is not None:
-        if not _is_seq(banned_token_ids):
-            raise ValueError(f"banned_token_ids must be a sequence of token ids or one sequence per request, got {banned_token_ids!r}")
-        vals = list(banned_token_ids)
+    for name, ids in (("banned_token_ids", banned_token_ids), ("allowed_token_ids", allowed_token_ids)):
+        if ids is None:
+            continue
+        if not _is_seq(ids):
+            raise ValueError(f"{name} must be a sequence of token ids or one sequence per request, got {ids!r}")
+        vals = list(ids)
         if any(_is_seq(v) or v is None for v in vals):
             if len(vals) != n:
-                raise ValueError(f"{len(vals)} banned_token_ids lists for {n} requests")
-            out["banned_token_ids"] = vals
+                raise ValueError(f"{len(vals)} {name} lists for {n} requests")
+            out[name] = vals
         else:
-            out["banned_token_ids"] = tuple(vals)
+            out[name] = tuple(vals)
     if min_tokens is not None:
         if _is_seq(min_tokens):
             if len(min_tokens) != n:
@@ -209,7 +212,7 @@ class _Active:
     top_p: Optional[float] = None
     top_k: Optional[int] = None
     min_p: Optional[float] = None
-    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens
+    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens / allowed_token_ids
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -242,17 +245,19 @@ class AdaptiveSpeculativePipeline:
     def process_request(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
                         request_id: Optional[str] = None, seed: Optional[int] = None, top_p: Optional[float] = None,
                         top_k: Optional[int] = None, min_p: Optional[float] = None, logit_bias=None, banned_token_ids=None,
-                        min_tokens=None) -> RequestResult:
+                        min_tokens=None, allowed_token_ids=None) -> RequestResult:
         """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring).
         top_p / top_k / min_p: None = every stage's configuration, else the request's own value at every stage
         (stage.generate(top_p=, top_k=, min_p=)).  logit_bias (a dict) / banned_token_ids (token ids) / min_tokens (an int):
-        None = every stage's configuration, else handed to every stage.generate call (module docstring, Logit edits)."""
+        None = every stage's configuration, else handed to every stage.generate call (module docstring, Logit edits);
+        allowed_token_ids (token ids) likewise."""
         if seed is not None and not isinstance(seed, (int, np.integer)):
             raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
         sampling = {k: check_per_prompt(v, 1, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
-        edits = {k: v for k, v in zip(_EDIT_KEYS, (logit_bias, banned_token_ids, min_tokens)) if v is not None}
-        if _is_seq(edits.get("banned_token_ids")):
-            edits["banned_token_ids"] = tuple(edits["banned_token_ids"])         # (one value for the batch of one, never a list)
+        edits = {k: v for k, v in zip(_EDIT_KEYS, (logit_bias, banned_token_ids, min_tokens, allowed_token_ids)) if v is not None}
+        for name in ("banned_token_ids", "allowed_token_ids"):
+            if _is_seq(edits.get(name)):
+                edits[name] = tuple(edits[name])                                 # (one value for the batch of one, never a list)
         if _is_seq(edits.get("logit_bias")) or _is_seq(edits.get("min_tokens")):
             raise ValueError("process_request takes one logit_bias dict and one min_tokens int")
         return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1), sampling=sampling,
@@ -266,7 +271,7 @@ class AdaptiveSpeculativePipeline:
 
     def batch_process(self, prompts: List[str], max_tokens=512, temperature=0.7,
                       seeds=None, top_p=None, top_k=None, min_p=None, logit_bias=None, banned_token_ids=None,
-                      min_tokens=None) -> List[RequestResult]:
+                      min_tokens=None, allowed_token_ids=None) -> List[RequestResult]:
         """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
         raises ValueError); request i keeps seeds[i] through every regrouping (module docstring).  max_tokens: an int, or one
         int >= 1 per request, kept by the request in the same way.
@@ -274,14 +279,14 @@ class AdaptiveSpeculativePipeline:
         kept by the request through every regrouping and handed to stage.generate as a list only where the batch has one
         (serving/stages.py, PER-REQUEST SAMPLING).  A stage call cannot mix greedy (temperature 0) and sampled rows: a batch
         whose temperatures do is run as a greedy and a sampled sub-batch here, and the results come back in request order.
-        logit_bias, banned_token_ids, min_tokens: None (the keyword is not handed to the stages), one value for the batch, or
-        one per request, kept by the request through every regrouping (module docstring, Logit edits)."""
+        logit_bias, banned_token_ids, min_tokens, allowed_token_ids: None (the keyword is not handed to the stages), one value
+        for the batch, or one per request, kept by the request through every regrouping (module docstring, Logit edits)."""
         prompts = list(prompts)
         n = len(prompts)
         seeds = check_seeds(seeds, n)
         max_tokens = check_max_tokens(max_tokens, n)
         sampling = {k: check_per_prompt(v, n, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
-        edits = check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n)
+        edits = check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n, allowed_token_ids)
         if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
             temperature = check_per_prompt(temperature, n, "temperature")
         if isinstance(temperature, list) and any(t == 0.0 for t in temperature):

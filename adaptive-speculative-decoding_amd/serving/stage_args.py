@@ -163,6 +163,38 @@ def check_banned_token_ids(value, n: int, vocab: int) -> List[Tuple[int, ...]]:
     return _per_prompt(list(value), n, one, "banned_token_ids lists")
 
 
+def check_allowed_token_ids(value, n: int, vocab: int) -> List[Optional[Tuple[int, ...]]]:
+    """generate's `allowed_token_ids`: None, a sequence of ids for all `n` prompts, or a sequence of n such sequences / Nones
+    -> n sorted tuples of distinct ids, or None for a prompt without a list.  An EMPTY list raises: it allows nothing, and the
+    samplers forbid a row without a finite logit."""
+    def one(ids):
+        if ids is None:
+            return None
+        out = tuple(sorted({_check_token_id(t, vocab, "allowed") for t in ids}))
+        if not out:
+            raise ValueError("an allowed_token_ids list must name at least one token (None: no list)")
+        return out
+    if value is None:
+        return [None] * n
+    if not _is_seq(value):
+        raise ValueError(f"allowed_token_ids must be a sequence of token ids or one sequence per prompt, got {value!r}")
+    per_prompt = [_is_seq(v) or v is None for v in value]
+    if not any(per_prompt):                              # a flat id list: the same list for every prompt
+        return [one(value)] * n
+    if not all(per_prompt):
+        raise ValueError("allowed_token_ids mixes token ids and per-prompt lists")
+    return _per_prompt(list(value), n, one, "allowed_token_ids lists")
+
+
+def check_rows_keep_a_token(allowed: List[Optional[Tuple[int, ...]]], edit_rows: List[List[Tuple[int, float, int]]]) -> None:
+    """A row's allow-list minus every merged edit entry with until > 0 -- the permanent bans AND the min_tokens bans, during
+    whose hold-back the row would be all -inf -- must keep a token: ValueError naming the prompt otherwise."""
+    for b, (ids, entries) in enumerate(zip(allowed, edit_rows)):
+        if ids is not None and not set(ids) - {t for t, _, u in entries if u > 0}:
+            raise ValueError(f"prompt {b}: the banned token ids (min_tokens' stop ids included) leave no token of its "
+                             f"allowed_token_ids ({len(ids)})")
+
+
 def check_min_tokens(value, n: int) -> List[int]:
     """generate's `min_tokens`: an int >= 0 for all `n` prompts, or a sequence of n such ints -> n ints."""
     def one(v):

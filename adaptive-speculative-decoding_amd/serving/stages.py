@@ -132,9 +132,30 @@ dict or list, min_tokens 0, biases of 0) makes exactly the ops calls it made bef
 non-integer or out-of-vocabulary id, a bias that is no number, NaN or outside [-100, 100], a negative or non-integer
 min_tokens, a sequence of the wrong length, more than 1024 entries in one row after merging, a row whose banned ids (for ever
 or at its first token) would leave no token.  NOT BUILT: `min_tokens` > 0 on a row whose stop list holds a MULTI-token
-sequence raises ValueError (the match would have to be suppressed in the commit kernels, which stay as they are); allow-lists
-(`allowed_token_ids`: a dense mask, not a sparse edit); multi-token `bad_words`; stateful penalties (repetition, presence,
-frequency), which need per-token state on top of this operation; and serving/hierarchy.py's loop.
+sequence raises ValueError (the match would have to be suppressed in the commit kernels, which stay as they are); multi-token
+`bad_words`; stateful penalties (repetition, presence, frequency), which need per-token state on top of this operation; and
+serving/hierarchy.py's loop.  (Allow-lists are a dense mask, not a sparse edit: the next section.)
+
+ALLOW-LISTS.  `generate(allowed_token_ids=)` (or StageConfig.allowed_token_ids; None takes the configuration's value) is
+vLLM's `SamplingParams.allowed_token_ids`: a sequence of token ids for every prompt, or one sequence (or None: no list) per
+prompt.  Every logit OUTSIDE a row's list becomes -inf ahead of every sampler; the order is mask -> edit -> temperature ->
+top-k -> top-p -> min-p.  An allow-list of 4 tokens bans 152 060, 148 times what the sparse edit holds per row, so this is its
+own operation: the host builds one bitmask per DISTINCT list ([R, ceil(V / 32)] int32, bit v & 31 of word v >> 5 set = kept; the
+form grammar back ends produce), uploads it once (ops.pack_token_masks; R <= B, a row without a list gets mask_row -1 and is
+never touched), and every loop calls ops.logit_mask_rows (asd_logit_mask_rows, in place, a pure write stream) once per logits
+tensor, immediately in front of the edit's call at each of its three sites: stage 0's [B, V] logits, every proposal's draft
+logits, the target's [B, K+1, V] output before anything is sliced from or scored on it.  Draft and target receive the SAME
+mask, so -- the argument of LOGIT EDITS, word for word -- the draft -> verify -> residual chain stays lossless against the
+restricted target distribution.  The mask and the sparse edit commute (a masked element stays -inf under a bias, a ban inside
+the list is -inf either way); the order is fixed only so that the call pattern is.  Consequences: only listed tokens are
+proposed, accepted, drawn or listed; the returned log-probs and top-N tables are those of the RESTRICTED distribution; with
+`logprobs` = N and fewer than N allowed tokens the unfillable slots hold id -1 and -inf; a stop id outside a row's list can
+never end that row (the caller's choice, as in vLLM).  A call without a list (None everywhere) makes exactly the ops calls it
+made before.  ValueError before any launch: a bool, non-integer or out-of-vocabulary id, a mix of ids and lists, a sequence of
+the wrong length, an EMPTY list (it allows nothing, and the samplers forbid a row without a finite logit), and a row whose
+list minus its banned ids -- permanent bans and the stop ids under min_tokens alike -- is empty.  NOT BUILT: per-position masks
+(a grammar's mask differs at each of the K + 1 positions; the mask_row indirection leaves room), folding the mask into the
+samplers, and serving/hierarchy.py's loop.
 
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
@@ -154,8 +175,9 @@ from ..distributed import HipOps
 from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
 from .stage_args import (MAX_LOGIT_EDITS, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS, _check_logprobs, _check_min_p,  # noqa: F401
-                         _check_stop_ids, _check_stop_sequences, _is_seq, check_banned_token_ids, check_logit_bias,
-                         check_max_tokens, check_min_tokens, check_per_prompt, check_seeds, merge_logit_edits)
+                         _check_stop_ids, _check_stop_sequences, _is_seq, check_allowed_token_ids, check_banned_token_ids,
+                         check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt, check_rows_keep_a_token,
+                         check_seeds, merge_logit_edits)
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
 # reference stage label -> the Qwen2.5 shape this build runs in its place (configs/models.yaml names the tiers by size)
@@ -195,6 +217,7 @@ class StageConfig:
     logit_bias: Optional[Dict[int, float]] = None    # {token id: bias in raw logit units} (module docstring, LOGIT EDITS)
     banned_token_ids: Sequence[int] = ()     # token ids that are never proposed, accepted or drawn
     min_tokens: int = 0                      # the stop ids are banned until a row has generated this many tokens
+    allowed_token_ids: Optional[Sequence[int]] = None    # the only token ids a row may hold (module docstring, ALLOW-LISTS)
 
 
 _REASONS = {1: "stop", 2: "length"}
@@ -214,6 +237,7 @@ class _Plan(NamedTuple):
     row_seqs: List[list]                     # every row's stop list: the stop ids as length-1 sequences, the common ones, its own
     finish_route: bool                       # asd_commit_step_finish: only for what the stop-id route cannot do
     edit_rows: list                          # every row's merged (id, bias, until) entries
+    mask_rows: list                          # every row's allow-list: a sorted tuple of ids, or None
     seeds: Optional[List[int]]
     n_top: int
 
@@ -229,6 +253,19 @@ class _EditState:
     def apply(self, logits: torch.Tensor, seq_len: torch.Tensor, offset: int = 0) -> torch.Tensor:
         """logits [B, V] or [B, K+1, V], edited in place; seq_len: the step's lengths before its commit."""
         return self.ops.logit_edit_rows(logits, self.packed, seq_len, self.start, offset)
+
+
+class _MaskState:
+    """What a generate call with an allow-list keeps: the rows' bitmasks on the device (uploaded once; equal lists share one);
+    `apply` is the loops' one call per logits tensor, in front of the edit's (module docstring, ALLOW-LISTS)."""
+
+    def __init__(self, ops, rows, V: int, device):
+        self.ops = ops
+        self.packed = ops.pack_token_masks(rows, int(V), device)
+
+    def apply(self, logits: torch.Tensor) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], masked in place."""
+        return self.ops.logit_mask_rows(logits, self.packed)
 
 
 # ---------------------------------------------------------------------------------------------- how a call's rows end
@@ -508,13 +545,14 @@ class _SampledRows(_Sampled):
 
 class _CallState:
     """The device side of one generate call, built in this one place from the plan and the encoded prompts and handed to the
-    loop: how rows end (`end`), the logit edit (`edit`, None without an entry), the sampler and the top-N tables (`top`, None
-    when off).  Uploads happen here, once; a part that is off costs no launch."""
+    loop: how rows end (`end`), the allow-list (`mask`, None without a list), the logit edit (`edit`, None without an entry), the
+    sampler and the top-N tables (`top`, None when off).  Uploads happen here, once; a part that is off costs no launch."""
 
     def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor):
         (B, P), dev, ops = ids.shape, ids.device, stage.ops
         self.end = _StopSequences(ops, plan.row_seqs, plan.limits, P, dev) if plan.finish_route else \
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
+        self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
         # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
@@ -585,7 +623,7 @@ class Stage:
                  min_p=None,
                  seed=None, stop_sequences=None,
                  stop_sequences_per_prompt=None, top_k=None, logit_bias=None, banned_token_ids=None,
-                 min_tokens=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 min_tokens=None, allowed_token_ids=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -622,11 +660,17 @@ class Stage:
         whose logit becomes -inf; a ban wins over a bias) and `min_tokens` (the row's stop ids and one-token stop sequences are
         banned until it has generated that many tokens): None = the configuration's; one value for every prompt or one per
         prompt.  Draft and target logits receive the same edit, so log-probs and top-N tables are those of the edited
-        distribution and a banned token is never proposed, accepted, drawn or listed (module docstring, LOGIT EDITS)."""
+        distribution and a banned token is never proposed, accepted, drawn or listed (module docstring, LOGIT EDITS).
+        `allowed_token_ids` (vLLM's): None = StageConfig.allowed_token_ids; a sequence of ids for every prompt, or one sequence
+        (or None: no list) per prompt.  Every logit outside a row's list becomes -inf, on the draft's and the target's logits
+        alike and ahead of the edits above, so only listed tokens are proposed, accepted, drawn or listed and the log-probs are
+        those of the restricted distribution; with `logprobs` = N above the list's size the unfillable slots hold id -1 and
+        -inf.  An empty list, and a list that the bans or min_tokens' stop ids empty, raise ValueError; a stop id outside a
+        row's list can never end that row (module docstring, ALLOW-LISTS)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
-                          stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens)
+                          stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -649,7 +693,7 @@ class Stage:
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
-              stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens) -> _Plan:
+              stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -686,6 +730,8 @@ class Stage:
         edit_rows = merge_logit_edits(check_logit_bias(given(logit_bias, cfg.logit_bias), n, V),
                                       check_banned_token_ids(given(banned_token_ids, cfg.banned_token_ids), n, V),
                                       check_min_tokens(given(min_tokens, cfg.min_tokens), n), row_seqs, V)
+        mask_rows = check_allowed_token_ids(given(allowed_token_ids, cfg.allowed_token_ids), n, V)
+        check_rows_keep_a_token(mask_rows, edit_rows)
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -703,7 +749,7 @@ class Stage:
         return _Plan(prompts=prompts, limits=tuple(limits), max_tokens=int(limit), greedy=greedy,
                      inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
-                     edit_rows=edit_rows, seeds=seeds, n_top=n_top)
+                     edit_rows=edit_rows, mask_rows=mask_rows, seeds=seeds, n_top=n_top)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -722,7 +768,7 @@ class Stage:
         B, P = ids.shape
         dev = ids.device
         cap = P + max_tokens
-        end, edit, top, sampler = st.end, st.edit, st.top, st.sampler
+        end, mask, edit, top, sampler = st.end, st.mask, st.edit, st.top, st.sampler
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -731,6 +777,8 @@ class Stage:
         for step in range(max_tokens):
             if sampler.dense:
                 logits = logits.contiguous()
+            if mask is not None:
+                mask.apply(logits)                                       # the allow-list first, then the sparse edit (they commute)
             if edit is not None:
                 edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
             n_acc, tok, lp = sampler.draw(logits, step)
@@ -767,7 +815,7 @@ class Stage:
         dev = ids.device
         Kd = cfg.draft_len
         cap = P + max_tokens
-        end, edit, top, sampler = st.end, st.edit, st.top, st.sampler
+        end, mask, edit, top, sampler = st.end, st.mask, st.edit, st.top, st.sampler
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
             m.reset()
@@ -788,6 +836,8 @@ class Stage:
             for k in range(Kd):
                 if sampler.dense:
                     dl = dl.contiguous()
+                if mask is not None:
+                    mask.apply(dl)
                 if edit is not None:
                     edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
                 toks.append(sampler.propose(dl, k))
@@ -795,6 +845,8 @@ class Stage:
                     dl = draft.forward_ragged(toks[-1].to(torch.int64)[:, None], L + k, window)[:, -1]
             tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
             t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
+            if mask is not None:
+                mask.apply(t_out)                                       # the whole [B, K+1, V] output, before any slice
             if edit is not None:
                 edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any slice
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)

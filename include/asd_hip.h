@@ -508,6 +508,35 @@ int asd_logit_edit_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int6
                         const int32_t* seq_len /*[B]*/, int start, int offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Token masks: a DENSE allow-list ahead of the samplers -- vLLM's `allowed_token_ids`, and the [rows, ceil(V/32)] int32
+ * bitmask that grammar / structured-output back ends produce.  The complement of a sparse edit: an allow-list of 4 tokens
+ * bans V - 4, far beyond ASD_MAX_LOGIT_EDITS.  Like an edited row, a masked row is an ordinary input of every sampler ("no
+ * logit > -inf" must hold: a mask that keeps nothing is legal HERE and illegal THERE); applied alike to the draft's proposal
+ * rows and the target's K+1 rows, the draft -> verify -> residual chain stays lossless against the masked target distribution.
+ * logits: asd_logit_edit_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only -- edited in place.
+ * mask_bits: [R, W] uint32 on the device, W = (V + 31) / 32.  Bit (v & 31) of word (v >> 5) is SET when token v is KEPT.  Bits
+ * at v >= V of the last word are ignored, whatever they hold.
+ * Which mask: sequence b uses mask r = mask_row[b] (int32 [B] on the device); mask_row == NULL: every sequence uses mask 0.
+ * With r < 0 or r >= R the sequence's rows are not touched at all (a mixed batch; a damaged index never leaves the array).
+ * Semantics: element v < V of every position j of a masked sequence becomes -inf of the dtype (bits 0xFF80 bf16, 0xFC00 f16,
+ * -INFINITY f32, as asd_logit_edit_rows writes a ban) when its bit is clear.  EVERY OTHER element of the allocation keeps its
+ * bits: kept elements, the row padding [V, ld_row), the rows of unmasked sequences, whatever lies in front of or behind the
+ * tensor.  No logit's VALUE is needed: the launch is a write stream of 16-byte stores of -inf over the chunks whose bits are all
+ * clear, with single-element stores in front of a row's first and behind its last 16-byte boundary; a 16-byte chunk whose bits
+ * are MIXED is loaded, blended and stored back whole, its kept elements receiving the bits they had (so nothing else may write
+ * the tensor while the launch runs, as for any in-place operation); a chunk whose bits are all set is not touched.
+ * One launch, grid (B*K1) x S with S chosen by the launcher (a row is cut on mask-word boundaries; the result does not depend
+ * on S); no workspace, no atomics, nothing waits on another workgroup.
+ * Status, in this order: negative B / K1 / V / R: invalid argument; B, K1, V or R == 0: ASD_OK, nothing launched; unknown
+ * dtype, B*K1 > INT32_MAX: unsupported; NULL logits / mask_bits, ld_row < V, ld_seq < K1*ld_row: invalid argument; logits not
+ * aligned to the element size or mask_bits not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+int asd_logit_mask_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                        const uint32_t* mask_bits /*[R, (V+31)/32]*/, int R, const int32_t* mask_row /*[B], or NULL: mask 0*/,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,
  * src/training/generate_training_data.py:166-175 -- np.mean, np.std (population), np.min,
  * np.percentile(.,25) (linear interpolation), np.median, all in float64 like numpy.

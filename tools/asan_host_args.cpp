@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms and asd_logit_edit_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows and asd_logit_mask_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -267,6 +267,34 @@ int main() {
         EXPECT(EDIT(rows + 1, BF16, K1 * V, V, B, K1, V, i32, f32, i32, nullptr, 4, i32), ASD_ERR_ALIGNMENT);
         EXPECT(EDIT(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, i32, f32, i32, i32, 4, i32), ASD_ERR_ALIGNMENT);
 #undef EDIT
+    }
+
+    // ---- asd_logit_mask_rows: every rejection, and every "nothing to do", comes before the launch
+    {
+#define MASK(x_, dt_, lds_, ldr_, B_, K1_, V_, bits_, R_, row_) asd_logit_mask_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, bits_, R_, row_, nullptr)
+        const int K1 = 5;
+        const uint32_t* u32 = reinterpret_cast<const uint32_t*>(rows);
+        EXPECT(MASK(p, BF16, K1 * V, V, -1, K1, V, u32, 1, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(MASK(p, BF16, K1 * V, V, B, -1, V, u32, 1, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(MASK(p, BF16, K1 * V, V, B, K1, -1, u32, 1, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(MASK(p, BF16, K1 * V, V, B, K1, V, u32, -1, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(MASK(p, BF16, K1 * V, V, 0, K1, V, u32, -1, i32), ASD_ERR_INVALID_ARG);                 // ... before the empty batch
+        EXPECT(MASK(nullptr, 99, 0, 0, 0, K1, V, nullptr, 1, nullptr), ASD_OK);                        // B == 0
+        EXPECT(MASK(nullptr, 99, 0, 0, B, 0, V, nullptr, 1, nullptr), ASD_OK);                         // K1 == 0
+        EXPECT(MASK(nullptr, 99, 0, 0, B, K1, 0, nullptr, 1, nullptr), ASD_OK);                        // V == 0
+        EXPECT(MASK(nullptr, 99, 0, 0, B, K1, V, nullptr, 0, nullptr), ASD_OK);                        // no masks
+        EXPECT(MASK(p, 99, K1 * V, V, B, K1, V, u32, 1, i32), ASD_ERR_UNSUPPORTED);                    // dtype
+        EXPECT(MASK(p, -1, K1 * V, V, B, K1, V, u32, 1, i32), ASD_ERR_UNSUPPORTED);
+        EXPECT(MASK(p, BF16, int64_t{1} << 40, V, INT32_MAX, K1, V, u32, 1, i32), ASD_ERR_UNSUPPORTED);   // grid
+        EXPECT(MASK(nullptr, BF16, K1 * V, V, B, K1, V, u32, 1, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(MASK(p, BF16, K1 * V, V, B, K1, V, nullptr, 1, i32), ASD_ERR_INVALID_ARG);              // mask_bits
+        EXPECT(MASK(p, BF16, K1 * V, V, B, K1, V, nullptr, 1, nullptr), ASD_ERR_INVALID_ARG);          // (mask_row may be NULL, mask_bits not)
+        EXPECT(MASK(p, BF16, K1 * V, V - 1, B, K1, V, u32, 1, i32), ASD_ERR_INVALID_ARG);              // ld_row < V
+        EXPECT(MASK(p, BF16, K1 * V - 1, V, B, K1, V, u32, 1, i32), ASD_ERR_INVALID_ARG);              // ld_seq < K1 ld_row
+        EXPECT(MASK(rows + 1, BF16, K1 * V, V, B, K1, V, u32, 1, i32), ASD_ERR_ALIGNMENT);             // below the element size
+        EXPECT(MASK(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, u32, 1, nullptr), ASD_ERR_ALIGNMENT);
+        EXPECT(MASK(p, BF16, K1 * V, V, B, K1, V, reinterpret_cast<const uint32_t*>(rows + 2), 1, nullptr), ASD_ERR_ALIGNMENT);   // mask_bits
+#undef MASK
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
