@@ -456,19 +456,49 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     return out.view(*x.shape[:-1], N)
 
 
+def _commit_front(tok, n_acc, drawn, seq_len, out_tokens, n_commit, max_len, lp=None, ends=None):
+    """What the four commit_step* wrappers share: the shape checks, then the device pointers in the order of the C argument
+    lists -> (Bv, K, cap, head, tail).  `head` stands in front of B, K and the entry point's own arguments, `tail` behind them.
+    lp = (lp_tok, lp_drawn, out_lp) where the entry point commits log-probs, ends = (finished, n_finished) where it ends rows."""
+    if lp is None:
+        Bv, K = tok.shape
+    else:
+        lp_tok, lp_drawn, out_lp = lp
+        Bv = drawn.shape[0]
+        K = 0 if tok is None else tok.shape[1]
+        if tok is not None and (tok.shape[0] != Bv or lp_tok is None or lp_tok.shape != tok.shape):
+            raise ValueError("tok and lp_tok must both be [B, K]")
+    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
+        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
+    if lp is not None and (out_lp.shape != out_tokens.shape or out_lp.stride() != out_tokens.stride()):
+        raise ValueError("out_lp must have the shape and strides of out_tokens")
+    if ends is not None:
+        finished, n_finished = ends
+        if finished.shape != (Bv,):
+            raise ValueError("finished must be [B] int32")
+        if n_finished is not None and n_finished.numel() != 1:
+            raise ValueError("n_finished must hold one int32")
+    cap = out_tokens.shape[1] if max_len is None else int(max_len)
+    i32, f32 = torch.int32, torch.float32
+    if lp is None:
+        head = (_dev(tok, "tok", i32), _dev(n_acc, "n_acc", i32), _dev(drawn, "drawn", i32))
+        tail = (_dev(seq_len, "seq_len", i32), _dev(out_tokens, "out_tokens", i32))
+    else:
+        head = (_opt(tok, "tok", i32), _opt(lp_tok, "lp_tok", f32), _dev(n_acc, "n_acc", i32), _dev(drawn, "drawn", i32),
+                _dev(lp_drawn, "lp_drawn", f32))
+        tail = (_dev(seq_len, "seq_len", i32), _dev(out_tokens, "out_tokens", i32), _dev(out_lp, "out_lp", f32))
+    tail += (out_tokens.stride(0), _opt(n_commit, "n_commit", i32))
+    if ends is not None:
+        tail += (_dev(finished, "finished", i32), _opt(n_finished, "n_finished", i32))
+    return Bv, K, cap, head, tail
+
+
 def commit_step(tok: torch.Tensor, n_acc: torch.Tensor, drawn: torch.Tensor, seq_len: torch.Tensor,
                 out_tokens: torch.Tensor, n_commit: Optional[torch.Tensor] = None, max_len: Optional[int] = None) -> None:
     """N3: append every sequence's accepted prefix + drawn token to its row of `out_tokens` and advance
     `seq_len` in place (asd_commit_step).  tok [B,K] i32, n_acc / drawn / seq_len [B] i32, out_tokens [B, T] i32."""
-    Bv, K = tok.shape
-    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
-        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
-    cap = out_tokens.shape[1] if max_len is None else int(max_len)
-    rc = _lib().asd_commit_step(_dev(tok, "tok", torch.int32), _dev(n_acc, "n_acc", torch.int32),
-                                _dev(drawn, "drawn", torch.int32), Bv, K, _dev(seq_len, "seq_len", torch.int32),
-                                _dev(out_tokens, "out_tokens", torch.int32), out_tokens.stride(0),
-                                _opt(n_commit, "n_commit", torch.int32), cap, _stream())
-    B.check("asd_commit_step", rc)
+    Bv, K, cap, head, tail = _commit_front(tok, n_acc, drawn, seq_len, out_tokens, n_commit, max_len)
+    B.check("asd_commit_step", _lib().asd_commit_step(*head, Bv, K, *tail, cap, _stream()))
 
 
 def commit_step_lp(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor], n_acc: torch.Tensor, drawn: torch.Tensor,
@@ -477,21 +507,8 @@ def commit_step_lp(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor], 
     """commit_step that also appends the committed tokens' log-probs to `out_lp` (asd_commit_step_lp): lp_tok [B,K] f32 beside
     tok, lp_drawn [B] f32 beside drawn, out_lp [B, T] f32 with the row stride of out_tokens.  tok = lp_tok = None is K = 0:
     every sequence appends its drawn token (plain sampled decoding)."""
-    Bv = drawn.shape[0]
-    K = 0 if tok is None else tok.shape[1]
-    if tok is not None and (tok.shape[0] != Bv or lp_tok is None or lp_tok.shape != tok.shape):
-        raise ValueError("tok and lp_tok must both be [B, K]")
-    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
-        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
-    if out_lp.shape != out_tokens.shape or out_lp.stride() != out_tokens.stride():
-        raise ValueError("out_lp must have the shape and strides of out_tokens")
-    cap = out_tokens.shape[1] if max_len is None else int(max_len)
-    rc = _lib().asd_commit_step_lp(_opt(tok, "tok", torch.int32), _opt(lp_tok, "lp_tok", torch.float32),
-                                   _dev(n_acc, "n_acc", torch.int32), _dev(drawn, "drawn", torch.int32),
-                                   _dev(lp_drawn, "lp_drawn", torch.float32), Bv, K, _dev(seq_len, "seq_len", torch.int32),
-                                   _dev(out_tokens, "out_tokens", torch.int32), _dev(out_lp, "out_lp", torch.float32),
-                                   out_tokens.stride(0), _opt(n_commit, "n_commit", torch.int32), cap, _stream())
-    B.check("asd_commit_step_lp", rc)
+    Bv, K, cap, head, tail = _commit_front(tok, n_acc, drawn, seq_len, out_tokens, n_commit, max_len, lp=(lp_tok, lp_drawn, out_lp))
+    B.check("asd_commit_step_lp", _lib().asd_commit_step_lp(*head, Bv, K, *tail, cap, _stream()))
 
 
 def commit_step_stop(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor], n_acc: torch.Tensor, drawn: torch.Tensor,
@@ -502,30 +519,13 @@ def commit_step_stop(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tensor]
     token that is in `stop_ids` (device int32 [S], S <= 8; None: no stop set) and that token is kept.  finished [B] i32 in/out:
     0 running, 1 stopped, 2 reached max_len; a row that enters non-zero is left alone (n_commit 0).  n_finished [1] i32 in/out:
     rows that finished so far -- the one value a host loop reads."""
-    Bv = drawn.shape[0]
-    K = 0 if tok is None else tok.shape[1]
-    if tok is not None and (tok.shape[0] != Bv or lp_tok is None or lp_tok.shape != tok.shape):
-        raise ValueError("tok and lp_tok must both be [B, K]")
-    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
-        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
-    if out_lp.shape != out_tokens.shape or out_lp.stride() != out_tokens.stride():
-        raise ValueError("out_lp must have the shape and strides of out_tokens")
-    if finished.shape != (Bv,):
-        raise ValueError("finished must be [B] int32")
+    Bv, K, cap, head, tail = _commit_front(tok, n_acc, drawn, seq_len, out_tokens, n_commit, max_len, lp=(lp_tok, lp_drawn, out_lp),
+                                           ends=(finished, n_finished))
     if stop_ids is not None and stop_ids.dim() != 1:
         raise ValueError("stop_ids must be [S] int32")
-    if n_finished is not None and n_finished.numel() != 1:
-        raise ValueError("n_finished must hold one int32")
     n_stop = 0 if stop_ids is None else stop_ids.shape[0]
-    cap = out_tokens.shape[1] if max_len is None else int(max_len)
-    rc = _lib().asd_commit_step_stop(_opt(tok, "tok", torch.int32), _opt(lp_tok, "lp_tok", torch.float32),
-                                     _dev(n_acc, "n_acc", torch.int32), _dev(drawn, "drawn", torch.int32),
-                                     _dev(lp_drawn, "lp_drawn", torch.float32), Bv, K,
-                                     _opt(stop_ids, "stop_ids", torch.int32) if n_stop else None, n_stop,
-                                     _dev(seq_len, "seq_len", torch.int32), _dev(out_tokens, "out_tokens", torch.int32),
-                                     _dev(out_lp, "out_lp", torch.float32), out_tokens.stride(0),
-                                     _opt(n_commit, "n_commit", torch.int32), _dev(finished, "finished", torch.int32),
-                                     _opt(n_finished, "n_finished", torch.int32), cap, _stream())
+    rc = _lib().asd_commit_step_stop(*head, Bv, K, _opt(stop_ids, "stop_ids", torch.int32) if n_stop else None, n_stop, *tail,
+                                     cap, _stream())
     B.check("asd_commit_step_stop", rc)
 
 
@@ -567,16 +567,8 @@ def commit_step_finish(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tenso
     [n] / row_first i32 [B+1] or None (every row owns all n <= 16): the tables of pack_stop_sequences, which checks that no row
     owns more than 16 on the host lists.  row_max_len i32 [B] or None.  finished / n_finished: as commit_step_stop.  matched
     i32 [B] in/out or None: the index, within the row's list, of the sequence that ended it."""
-    Bv = drawn.shape[0]
-    K = 0 if tok is None else tok.shape[1]
-    if tok is not None and (tok.shape[0] != Bv or lp_tok is None or lp_tok.shape != tok.shape):
-        raise ValueError("tok and lp_tok must both be [B, K]")
-    if out_tokens.dim() != 2 or out_tokens.shape[0] != Bv or out_tokens.stride(1) != 1:
-        raise ValueError("out_tokens must be [B, T] int32 with contiguous rows")
-    if out_lp.shape != out_tokens.shape or out_lp.stride() != out_tokens.stride():
-        raise ValueError("out_lp must have the shape and strides of out_tokens")
-    if finished.shape != (Bv,):
-        raise ValueError("finished must be [B] int32")
+    Bv, K, cap, head, tail = _commit_front(tok, n_acc, drawn, seq_len, out_tokens, n_commit, max_len, lp=(lp_tok, lp_drawn, out_lp),
+                                           ends=(finished, n_finished))
     if (seq_tok is None) != (seq_n is None):
         raise ValueError("seq_tok and seq_n come together")
     n_seq = 0 if seq_tok is None else seq_tok.shape[0]
@@ -588,24 +580,14 @@ def commit_step_finish(tok: Optional[torch.Tensor], lp_tok: Optional[torch.Tenso
         raise ValueError(f"at most {B.MAX_STOP_SEQS} stop sequences per row")
     if row_max_len is not None and row_max_len.shape != (Bv,):
         raise ValueError("row_max_len must be [B] int32")
-    if n_finished is not None and n_finished.numel() != 1:
-        raise ValueError("n_finished must hold one int32")
     if matched is not None and matched.shape != (Bv,):
         raise ValueError("matched must be [B] int32")
     if int(start) < 0:
         raise ValueError("start must be >= 0")
-    cap = out_tokens.shape[1] if max_len is None else int(max_len)
-    rc = _lib().asd_commit_step_finish(_opt(tok, "tok", torch.int32), _opt(lp_tok, "lp_tok", torch.float32),
-                                       _dev(n_acc, "n_acc", torch.int32), _dev(drawn, "drawn", torch.int32),
-                                       _dev(lp_drawn, "lp_drawn", torch.float32), Bv, K,
-                                       _opt(seq_tok, "seq_tok", torch.int32) if n_seq else None,
+    rc = _lib().asd_commit_step_finish(*head, Bv, K, _opt(seq_tok, "seq_tok", torch.int32) if n_seq else None,
                                        _opt(seq_n, "seq_n", torch.int32) if n_seq else None, n_seq,
                                        _opt(row_first, "row_first", torch.int32), _opt(row_max_len, "row_max_len", torch.int32),
-                                       int(start), _dev(seq_len, "seq_len", torch.int32),
-                                       _dev(out_tokens, "out_tokens", torch.int32), _dev(out_lp, "out_lp", torch.float32),
-                                       out_tokens.stride(0), _opt(n_commit, "n_commit", torch.int32),
-                                       _dev(finished, "finished", torch.int32), _opt(n_finished, "n_finished", torch.int32),
-                                       _opt(matched, "matched", torch.int32), cap, _stream())
+                                       int(start), *tail, _opt(matched, "matched", torch.int32), cap, _stream())
     B.check("asd_commit_step_finish", rc)
 
 
@@ -793,6 +775,26 @@ def _rows(t: torch.Tensor, name: str) -> Tuple[int, int]:
     return t.data_ptr(), t.stride(-2)
 
 
+def _sampling_args(inv_temperature, scalars: tuple, Bv: int, V: int, dtype) -> tuple:
+    """The sampling parameters of a draw as its C entry point takes them: inv_temperature and the scalars behind it, or the
+    pointer of a SamplingRows table in their place."""
+    if isinstance(inv_temperature, SamplingRows):
+        return (inv_temperature.ptr(Bv, V, dtype),)
+    return (float(inv_temperature), *scalars)
+
+
+def _logit_strides(view: torch.Tensor, K1: int, rows: str = "K1") -> Tuple[int, int]:
+    """(ld_seq, ld_row) in elements of a [B, K1, V] logits view with unit stride along V; `rows` is how the caller's error
+    text spells K1."""
+    Bv, V = view.shape[0], view.shape[2]
+    # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
+    ld_row = view.stride(1) if K1 > 1 else V
+    ld_seq = view.stride(0) if Bv > 1 else K1 * ld_row
+    if ld_row < V or ld_seq < K1 * ld_row:
+        raise ValueError(f"logits rows overlap: the row stride must be >= V and the sequence stride >= {rows} row strides")
+    return ld_seq, ld_row
+
+
 class ResidualSampler(_StatusWorkspace):
     """asd_residual_sample with its workspace: the token each sequence commits after its accepted prefix."""
 
@@ -806,9 +808,10 @@ class ResidualSampler(_StatusWorkspace):
 
     def _sample(self, entry: str, t_logits, d_logits, n_acc, r, bonus_logits, inv_temperature, out, scalars=(), lp_out=None,
                 **thresholds):
-        """The body of __call__ / top_p / top_k / lp: `entry` is the C entry point; `scalars`, then the optional [B,K] `thresholds`
-        (in the entry point's order), are its arguments between inv_temperature and the token; `lp_out` ([B] f32) follows the
-        token where the entry point has it."""
+        """The body of __call__ / top_p / top_k / lp / lp_rows: `entry` is the C entry point; `scalars`, then the optional [B,K]
+        `thresholds` (in the entry point's order), are its arguments between inv_temperature and the token; `lp_out` ([B] f32)
+        follows the token where the entry point has it.  A SamplingRows as inv_temperature: its table pointer takes the place
+        of inv_temperature and the scalars."""
         Bv, K, V = t_logits.shape
         if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
             raise ValueError("t_logits and d_logits must have the same shape and dtype")
@@ -821,7 +824,8 @@ class ResidualSampler(_StatusWorkspace):
             if t is not None and tuple(t.shape) != (Bv, K):
                 raise ValueError(f"{name} must be [B, K]")
         rc = getattr(_lib(), entry)(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype], _dev(n_acc, "n_acc", torch.int32),
-                                    _dev(r, "r", torch.float32), Bv, K, V, float(inv_temperature), *scalars,
+                                    _dev(r, "r", torch.float32), Bv, K, V,
+                                    *_sampling_args(inv_temperature, scalars, Bv, V, t_logits.dtype),
                                     *[_opt(t, name, torch.float32) for name, t in thresholds.items()], out.data_ptr(),
                                     *(() if lp_out is None else (_dev(lp_out, "lp", torch.float32),)),
                                     self.buf.data_ptr(), self.bytes, _stream())
@@ -889,26 +893,11 @@ class ResidualSampler(_StatusWorkspace):
                 lp_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """lp_min_p(...) with every sequence's own parameters (asd_residual_sample_lp_rows): t_threshold [B,K] = the thresholds
         of verify_accept_rows; the bonus rows' are found by the sampler with the sequence's select."""
-        Bv, K, V = t_logits.shape
-        if d_logits.shape != t_logits.shape or d_logits.dtype != t_logits.dtype:
-            raise ValueError("t_logits and d_logits must have the same shape and dtype")
-        tp, ldt = _rows(t_logits, "t_logits")
-        dp, ldd = _rows(d_logits, "d_logits")
-        bp, ldb = (None, V) if bonus_logits is None else _rows(bonus_logits, "bonus_logits")
-        if out is None:
-            out = torch.empty((Bv,), dtype=torch.int32, device=t_logits.device)
         if lp_out is None:
-            lp_out = torch.empty((Bv,), dtype=torch.float32, device=t_logits.device)
-        for name, t in (("t_threshold", t_threshold), ("d_threshold", d_threshold)):
-            if t is not None and tuple(t.shape) != (Bv, K):
-                raise ValueError(f"{name} must be [B, K]")
-        rc = _lib().asd_residual_sample_lp_rows(tp, ldt, dp, ldd, bp, ldb, _DTYPE_CODE[t_logits.dtype],
-                                                _dev(n_acc, "n_acc", torch.int32), _dev(r, "r", torch.float32), Bv, K, V,
-                                                rows.ptr(Bv, V, t_logits.dtype), _opt(t_threshold, "t_threshold", torch.float32),
-                                                _opt(d_threshold, "d_threshold", torch.float32), out.data_ptr(),
-                                                _dev(lp_out, "lp", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_residual_sample_lp_rows", rc)
-        return out, lp_out
+            lp_out = torch.empty((t_logits.shape[0],), dtype=torch.float32, device=t_logits.device)
+        tok = self._sample("asd_residual_sample_lp_rows", t_logits, d_logits, n_acc, r, bonus_logits, rows, out, (), lp_out,
+                           t_threshold=t_threshold, d_threshold=d_threshold)
+        return tok, lp_out
 
 
 @dataclass
@@ -931,8 +920,8 @@ class DraftSampler(_StatusWorkspace):
         self.reset()
 
     def _draw(self, entry: str, logits, r, inv_temperature, truncation: tuple, out) -> DraftDraw:
-        """The body of __call__ / top_k: `entry` is the C entry point, `truncation` its arguments between inv_temperature and
-        the outputs."""
+        """The body of __call__ / top_k / min_p / rows: `entry` is the C entry point, `truncation` its arguments between
+        inv_temperature and the outputs.  A SamplingRows as inv_temperature: its table pointer takes the place of both."""
         if logits.dim() != 2 or logits.dtype != self.dtype or not logits.is_cuda or logits.stride(1) != 1:
             raise ValueError(f"logits must be a [B, V] {self.dtype} CUDA tensor with unit stride along V")
         Bv, V = logits.shape
@@ -944,7 +933,8 @@ class DraftSampler(_StatusWorkspace):
                             torch.empty((Bv,), dtype=torch.float32, device=dev),
                             torch.empty((Bv,), dtype=torch.float32, device=dev))
         rc = getattr(_lib(), entry)(logits.data_ptr(), logits.stride(0) if Bv > 1 else V, _DTYPE_CODE[logits.dtype],
-                                    _dev(r, "r", torch.float32), Bv, V, float(inv_temperature), *truncation,
+                                    _dev(r, "r", torch.float32), Bv, V,
+                                    *_sampling_args(inv_temperature, truncation, Bv, V, logits.dtype),
                                     _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
                                     _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
         B.check(entry, rc)
@@ -972,22 +962,7 @@ class DraftSampler(_StatusWorkspace):
     def rows(self, logits: torch.Tensor, r: torch.Tensor, rows: "SamplingRows", out: Optional[DraftDraw] = None) -> DraftDraw:
         """The proposal with every sequence's own temperature / top-k / top-p / min-p (asd_draft_sample_rows): one workgroup
         per row at every batch size, the workspace unused; sequence b returns the bits min_p(...) returns for it."""
-        if logits.dim() != 2 or logits.dtype != self.dtype or not logits.is_cuda or logits.stride(1) != 1:
-            raise ValueError(f"logits must be a [B, V] {self.dtype} CUDA tensor with unit stride along V")
-        Bv, V = logits.shape
-        if Bv > self.B or V != self.V:
-            raise ValueError(f"sampler was sized for B<={self.B}, V={self.V}")
-        dev = logits.device
-        if out is None:
-            out = DraftDraw(torch.empty((Bv,), dtype=torch.int32, device=dev),
-                            torch.empty((Bv,), dtype=torch.float32, device=dev),
-                            torch.empty((Bv,), dtype=torch.float32, device=dev))
-        rc = _lib().asd_draft_sample_rows(logits.data_ptr(), logits.stride(0) if Bv > 1 else V, _DTYPE_CODE[logits.dtype],
-                                          _dev(r, "r", torch.float32), Bv, V, rows.ptr(Bv, V, logits.dtype),
-                                          _dev(out.tok, "tok", torch.int32), _dev(out.lp, "lp", torch.float32),
-                                          _dev(out.thr, "thr", torch.float32), self.buf.data_ptr(), self.bytes, _stream())
-        B.check("asd_draft_sample_rows", rc)
-        return out
+        return self._draw("asd_draft_sample_rows", logits, r, rows, (), out)
 
 
 # ------------------------------------------------------------------------------- greedy decoding (temperature 0)
@@ -1036,11 +1011,7 @@ class GreedyVerifier:
         Bv = logits.shape[0]
         if Bv > self.B:
             raise ValueError(f"verifier was sized for B <= {self.B}")
-        # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
-        ld_row = logits.stride(1) if K > 0 else V
-        ld_seq = logits.stride(0) if Bv > 1 else (K + 1) * ld_row
-        if ld_row < V or ld_seq < (K + 1) * ld_row:
-            raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= (K + 1) row strides")
+        ld_seq, ld_row = _logit_strides(logits, K + 1, "(K + 1)")
         if K > 0:
             if tok is None or tuple(tok.shape) != (Bv, K):
                 raise ValueError("tok must be [B, K]")
@@ -1097,11 +1068,7 @@ class TopLogprobs:
         Bv = logits.shape[0]
         if Bv > self.B:
             raise ValueError(f"sized for B <= {self.B}")
-        # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
-        ld_row = logits.stride(1) if K1 > 1 else V
-        ld_seq = logits.stride(0) if Bv > 1 else K1 * ld_row
-        if ld_row < V or ld_seq < K1 * ld_row:
-            raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= K1 row strides")
+        ld_seq, ld_row = _logit_strides(logits, K1)
         if out is None:
             out = self.new_out(Bv)
         top_id, top_lp = out
@@ -1229,11 +1196,7 @@ def logit_edit_rows(logits: torch.Tensor, edits: LogitEdits, seq_len: torch.Tens
     Bv, K1, V = view.shape
     if edits.B != Bv or tuple(seq_len.shape) != (Bv,):
         raise ValueError(f"the edits were packed for {edits.B} rows and seq_len must be int32 [B]; logits have {Bv} rows")
-    # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
-    ld_row = view.stride(1) if K1 > 1 else V
-    ld_seq = view.stride(0) if Bv > 1 else K1 * ld_row
-    if ld_row < V or ld_seq < K1 * ld_row:
-        raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= K1 row strides")
+    ld_seq, ld_row = _logit_strides(view, K1)
     rc = _lib().asd_logit_edit_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
                                     _dev(edits.edit_id, "edit_id", torch.int32), _dev(edits.edit_bias, "edit_bias", torch.float32),
                                     _dev(edits.edit_until, "edit_until", torch.int32), _opt(edits.row_first, "row_first", torch.int32),
@@ -1306,11 +1269,7 @@ def logit_mask_rows(logits: torch.Tensor, masks: TokenMasks) -> torch.Tensor:
         raise ValueError(f"the masks were packed for {masks.B} rows of {masks.V} tokens; logits have {Bv} rows of {V}")
     if tuple(masks.bits.shape) != (masks.R, (V + 31) // 32):
         raise ValueError("mask bits must be int32 [R, (V + 31) // 32]")
-    # the stride of a size-1 dimension is arbitrary: give the kernel one that satisfies its checks
-    ld_row = view.stride(1) if K1 > 1 else V
-    ld_seq = view.stride(0) if Bv > 1 else K1 * ld_row
-    if ld_row < V or ld_seq < K1 * ld_row:
-        raise ValueError("logits rows overlap: the row stride must be >= V and the sequence stride >= K1 row strides")
+    ld_seq, ld_row = _logit_strides(view, K1)
     rc = _lib().asd_logit_mask_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
                                     _dev(masks.bits, "mask bits", torch.int32), masks.R,
                                     _opt(masks.mask_row, "mask_row", torch.int32), _stream())

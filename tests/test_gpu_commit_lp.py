@@ -40,6 +40,8 @@ def _inputs(B, K, seed):
             seq_len[b] = max(max_len - max(na[b] // 2, 0), 0) if na[b] else max_len    # cut inside the prefix
         elif mode == 3 and b % 8 == 3:
             seq_len[b] = max_len                       # nothing fits
+    if B >= 5:
+        seq_len[4] = max_len + 1                       # negative room (T = max_len + 2): the row is left as it is
     return tok, lp_tok, n_acc, drawn, lp_drawn, seq_len, T, max_len
 
 

@@ -67,6 +67,8 @@ def _inputs(B, K, n_stop):
             n_acc[b] = -3
         elif name == "n_acc_above_k":
             n_acc[b] = K + 5
+    if B >= 5:                                         # on top of row 4's scenario: negative room (T = max_len + 2)
+        seq_len[4], finished[4] = max_len + 1, 0
     return dict(tok=tok, lp_tok=lp_tok, n_acc=n_acc, drawn=drawn, lp_drawn=lp_drawn, seq_len=seq_len, finished=finished,
                 stops=stops, T=T, max_len=max_len)
 
@@ -104,11 +106,14 @@ def _what_happened(c, ref):
         if room == 0:
             assert fin[b] == LENGTH and nc[b] == 0
             seen.add("enters_full")
+        if room < 0:                                   # ends for its length, nothing appended, counted like any row that ends
+            assert fin[b] == LENGTH and nc[b] == 0 and ln[b] == length
+            seen.add("enters_past_max_len")
         if c["drawn"][b] == -1 and stops and not prefix_hits:
             assert fin[b] != STOP
             seen.add("drawn_minus_1")
         if rejected_hits and not prefix_hits and not drawn_hit:
-            assert fin[b] != STOP and nc[b] == min(na + 1, room)
+            assert fin[b] != STOP and nc[b] == min(na + 1, max(room, 0))
             seen.add("stop_only_rejected")
         if fin[b] == STOP:
             j = int(nc[b]) - 1
@@ -138,7 +143,7 @@ def test_every_scenario_occurs():
             for n_stop in NSTOPS:
                 c = _inputs(B, K, n_stop)
                 seen |= _what_happened(c, _reference(c))
-    assert seen >= (set(SCENARIOS) - {"plain"}) | {"stop_at_lane_63"}, sorted(set(SCENARIOS) - seen)
+    assert seen >= (set(SCENARIOS) - {"plain"}) | {"stop_at_lane_63", "enters_past_max_len"}, sorted(set(SCENARIOS) - seen)
 
 
 def _device_call(c, seq_len, out_tok, out_lp, finished, n_finished, n_commit=True):
