@@ -434,6 +434,26 @@ class HipOps:
         call once per logits tensor, in front of logit_edit_rows, and only when some row of the call has a list."""
         return self.K.logit_mask_rows(logits, masks)
 
+    def pack_penalties(self, rep, pres, freq, prompt_ids, V, device):
+        """Every row's (repetition, presence, frequency) penalty and its unpadded prompt ids -> the device state of
+        penalty_rows / penalty_commit (kernels.pack_penalties: the prompt's seen bits are built with numpy on the host and
+        uploaded once per generate call; the counts start at zero)."""
+        return self.K.pack_penalties(rep, pres, freq, prompt_ids, V, device)
+
+    @traced("penalty_rows")
+    def penalty_rows(self, logits, pen, step_tok=None, n_prev: int = 0):
+        """The stateful penalties ahead of the samplers (asd_penalty_rows): logits [B, V] or [B, K1, V] (any strides with a
+        unit last stride) -> the same tensor, penalised from the row's history: its prompt and committed tokens (the state) and
+        the step's proposals step_tok[b, :n_prev + j] at position j.  One launch, no workspace; a stage loop makes the call once
+        per logits tensor, behind logit_edit_rows, and only when some row of the call has a non-neutral penalty."""
+        return self.K.penalty_rows(logits, pen, step_tok, n_prev)
+
+    @traced("penalty_commit")
+    def penalty_commit(self, tokens, seq_len, n_commit, pen, max_len):
+        """The step's committed tokens enter the penalty state (asd_penalty_commit), behind the step's commit: a finished row
+        (n_commit 0) keeps its state, and a rejected proposal was never in it."""
+        self.K.penalty_commit(tokens, seq_len, n_commit, pen, max_len)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

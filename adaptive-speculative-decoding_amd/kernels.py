@@ -1275,3 +1275,97 @@ def logit_mask_rows(logits: torch.Tensor, masks: TokenMasks) -> torch.Tensor:
                                     _opt(masks.mask_row, "mask_row", torch.int32), _stream())
     B.check("asd_logit_mask_rows", rc)
     return logits
+
+
+# ------------------------------------------------------------------------------- stateful penalties (repetition / presence / frequency)
+@dataclass
+class Penalties:
+    """The state of asd_penalty_rows / asd_penalty_commit on the device (pack_penalties): seen i32 [B, W], W = (V + 31) // 32,
+    bit v & 31 of word v >> 5 set = token v occurs in the row's prompt or among its committed generated tokens; counts i32
+    [B, V], the occurrences among the committed generated tokens; params f32 [B, 3] = (rep, pres, freq)."""
+    seen: torch.Tensor
+    counts: torch.Tensor
+    params: torch.Tensor
+    B: int                                   # rows the state was packed for
+    V: int
+
+
+def check_penalty_rows(rep, pres, freq, prompt_ids, V: int):
+    """The host side of pack_penalties -> (seen bits: numpy uint32 [B, W] with the bits of every row's prompt ids set, params:
+    numpy float32 [B, 3]).  `prompt_ids`: one sequence of token ids in [0, V) per row -- the real prompt, without padding."""
+    V = int(V)
+    if V < 1:
+        raise ValueError("V must be >= 1")
+    rows = [np.asarray(list(r), dtype=np.int64).reshape(-1) for r in prompt_ids]
+    if not len(rep) == len(pres) == len(freq) == len(rows):
+        raise ValueError("rep, pres, freq and prompt_ids must hold one entry per row")
+    params = np.stack([np.asarray(v, dtype=np.float32).reshape(-1) for v in (rep, pres, freq)], 1) if rows else \
+        np.zeros((0, 3), dtype=np.float32)
+    if not np.isfinite(params).all() or (params[:, 0] <= 0).any():
+        raise ValueError("penalties must be finite and the repetition penalty > 0")
+    bits = np.zeros((len(rows), (V + 31) // 32), dtype=np.uint32)
+    for r, a in enumerate(rows):
+        if a.size and (a.min() < 0 or a.max() >= V):
+            raise ValueError(f"the prompt ids of row {r} must lie in [0, {V})")
+        np.bitwise_or.at(bits[r], a >> 5, np.uint32(1) << (a & 31).astype(np.uint32))
+    return bits, np.ascontiguousarray(params)
+
+
+def pack_penalties(rep, pres, freq, prompt_ids, V: int, device) -> Penalties:
+    """The state of penalty_rows / penalty_commit at the start of a generation: every row's (rep, pres, freq), the seen bits of
+    its prompt (built with numpy on the host, uploaded once) and counts of zero."""
+    bits, params = check_penalty_rows(rep, pres, freq, prompt_ids, V)
+    return Penalties(torch.from_numpy(bits.view(np.int32)).to(device), torch.zeros((bits.shape[0], int(V)), dtype=torch.int32, device=device),
+                     torch.from_numpy(params).to(device), int(bits.shape[0]), int(V))
+
+
+def penalty_rows(logits: torch.Tensor, pen: Penalties, step_tok: Optional[torch.Tensor] = None, n_prev: int = 0) -> torch.Tensor:
+    """Penalise `logits` in place (asd_penalty_rows) and return it: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  step_tok i32 [B, n_tok] (unit stride along the proposals) or None: position j of row b
+    sees step_tok[b, :n_prev + j] on top of the row's state."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if pen.B != Bv or pen.V != V:
+        raise ValueError(f"the penalties were packed for {pen.B} rows of {pen.V} tokens; logits have {Bv} rows of {V}")
+    if tuple(pen.seen.shape) != (Bv, (V + 31) // 32) or tuple(pen.counts.shape) != (Bv, V) or tuple(pen.params.shape) != (Bv, 3):
+        raise ValueError("the state must be seen i32 [B, (V + 31) // 32], counts i32 [B, V] and params f32 [B, 3]")
+    ld_tok = n_tok = 0
+    if step_tok is None:
+        if n_prev != 0:
+            raise ValueError("n_prev must be 0 without step_tok")
+    else:
+        if not step_tok.is_cuda or step_tok.dtype != torch.int32 or step_tok.dim() != 2 or step_tok.shape[0] != Bv or \
+                (step_tok.shape[1] > 1 and step_tok.stride(1) != 1):
+            raise ValueError("step_tok must be a CUDA int32 [B, n_tok] tensor with unit stride along the proposals")
+        n_tok = step_tok.shape[1]
+        ld_tok = step_tok.stride(0) if Bv > 1 else n_tok
+        if not 0 <= int(n_prev) or int(n_prev) + K1 - 1 > n_tok or ld_tok < n_tok:
+            raise ValueError(f"position {K1 - 1} would see {int(n_prev) + K1 - 1} proposals; step_tok holds {n_tok}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_penalty_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
+                                 _dev(pen.seen, "seen", torch.int32), _dev(pen.counts, "counts", torch.int32),
+                                 _dev(pen.params, "params", torch.float32), None if step_tok is None else step_tok.data_ptr(),
+                                 ld_tok, n_tok, int(n_prev), _stream())
+    B.check("asd_penalty_rows", rc)
+    return logits
+
+
+def penalty_commit(tokens: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor, pen: Penalties,
+                   max_len: Optional[int] = None) -> None:
+    """The step's committed tokens enter the state (asd_penalty_commit), behind the step's commit: for the n_commit[b] tokens
+    at tokens[b, seq_len[b] - n_commit[b] : seq_len[b]], counts grows by each token's multiplicity and its seen bit is set.
+    tokens i32 [B, >= max_len] contiguous; seq_len / n_commit i32 [B] as the commit left them."""
+    if tokens.dim() != 2:
+        raise ValueError("tokens must be int32 [B, max_len]")
+    Bv = tokens.shape[0]
+    cap = tokens.shape[1] if max_len is None else int(max_len)
+    if pen.B != Bv or tokens.shape[1] < cap or tuple(seq_len.shape) != (Bv,) or tuple(n_commit.shape) != (Bv,):
+        raise ValueError(f"the penalties were packed for {pen.B} rows; tokens must be [B, >= max_len], seq_len and n_commit [B]")
+    rc = _lib().asd_penalty_commit(_dev(tokens, "tokens", torch.int32), tokens.shape[1], _dev(seq_len, "seq_len", torch.int32),
+                                   _dev(n_commit, "n_commit", torch.int32), Bv, pen.V, cap, _dev(pen.seen, "seen", torch.int32),
+                                   _dev(pen.counts, "counts", torch.int32), _stream())
+    B.check("asd_penalty_commit", rc)

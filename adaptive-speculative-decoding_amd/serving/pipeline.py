@@ -34,6 +34,8 @@ banned_token_ids=, min_tokens=)` take one value for the batch -- a dict, a seque
 one request.  `allowed_token_ids=` (vLLM's; serving/stages.py, ALLOW-LISTS) travels the same way: a sequence of ids for the
 batch, or one sequence (or None: no list) per request.  A per-request value travels with the request like its `top_p`; a keyword
 reaches `stage.generate` only when it was given.  The values are checked by the stage (which knows the vocabulary); only the per-request lengths are checked here.
+`repetition_penalty=`, `presence_penalty=`, `frequency_penalty=` (vLLM's; serving/stages.py, PENALTIES) travel the same way: one
+number for the batch or one per request, kept by the request through every regrouping, handed on only when given.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -81,6 +83,7 @@ from .stages import _is_seq, check_max_tokens, check_per_prompt, check_seeds
 logger = logging.getLogger(__name__)
 
 _EDIT_KEYS = ("logit_bias", "banned_token_ids", "min_tokens", "allowed_token_ids")
+_PENALTY_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty")
 
 
 def check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n: int, allowed_token_ids=None) -> Dict[str, Any]:
@@ -115,6 +118,24 @@ def check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n: int, allo
         else:
             out["min_tokens"] = min_tokens
     return out
+
+
+def check_penalty_args(values: Dict[str, Any], n: int) -> Dict[str, Any]:
+    """The penalty keywords of batch_process -> {name: value} of those that were given: a `list` of n values where the batch
+    carries one per request, anything else is one value for the batch.  Only the shapes are looked at here; stage.generate checks
+    the values."""
+    out: Dict[str, Any] = {}
+    for name, v in values.items():
+        if v is None:
+            continue
+        if _is_seq(v):
+            if len(v) != n:
+                raise ValueError(f"{len(v)} {name} values for {n} requests")
+            out[name] = list(v)
+        else:
+            out[name] = v
+    return out
+
 
 DEFAULT_STAGE_NAMES = ("8b", "13b", "34b", "70b")          # pipeline.py:175
 
@@ -212,7 +233,7 @@ class _Active:
     top_p: Optional[float] = None
     top_k: Optional[int] = None
     min_p: Optional[float] = None
-    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens / allowed_token_ids
+    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens / allowed_token_ids / penalties
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -245,12 +266,14 @@ class AdaptiveSpeculativePipeline:
     def process_request(self, prompt: str, max_tokens: int = 512, temperature: float = 0.7,
                         request_id: Optional[str] = None, seed: Optional[int] = None, top_p: Optional[float] = None,
                         top_k: Optional[int] = None, min_p: Optional[float] = None, logit_bias=None, banned_token_ids=None,
-                        min_tokens=None, allowed_token_ids=None) -> RequestResult:
+                        min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
+                        frequency_penalty=None) -> RequestResult:
         """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring).
         top_p / top_k / min_p: None = every stage's configuration, else the request's own value at every stage
         (stage.generate(top_p=, top_k=, min_p=)).  logit_bias (a dict) / banned_token_ids (token ids) / min_tokens (an int):
         None = every stage's configuration, else handed to every stage.generate call (module docstring, Logit edits);
-        allowed_token_ids (token ids) likewise."""
+        allowed_token_ids (token ids) likewise; repetition_penalty / presence_penalty / frequency_penalty (one number each:
+        serving/stages.py, PENALTIES) likewise."""
         if seed is not None and not isinstance(seed, (int, np.integer)):
             raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
         sampling = {k: check_per_prompt(v, 1, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
@@ -260,6 +283,11 @@ class AdaptiveSpeculativePipeline:
                 edits[name] = tuple(edits[name])                                 # (one value for the batch of one, never a list)
         if _is_seq(edits.get("logit_bias")) or _is_seq(edits.get("min_tokens")):
             raise ValueError("process_request takes one logit_bias dict and one min_tokens int")
+        for name, v in zip(_PENALTY_KEYS, (repetition_penalty, presence_penalty, frequency_penalty)):
+            if _is_seq(v):
+                raise ValueError(f"process_request takes one {name} number")
+            if v is not None:
+                edits[name] = v
         return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1), sampling=sampling,
                                edits=edits)[0]
 
@@ -271,7 +299,8 @@ class AdaptiveSpeculativePipeline:
 
     def batch_process(self, prompts: List[str], max_tokens=512, temperature=0.7,
                       seeds=None, top_p=None, top_k=None, min_p=None, logit_bias=None, banned_token_ids=None,
-                      min_tokens=None, allowed_token_ids=None) -> List[RequestResult]:
+                      min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
+                      frequency_penalty=None) -> List[RequestResult]:
         """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
         raises ValueError); request i keeps seeds[i] through every regrouping (module docstring).  max_tokens: an int, or one
         int >= 1 per request, kept by the request in the same way.
@@ -280,13 +309,16 @@ class AdaptiveSpeculativePipeline:
         (serving/stages.py, PER-REQUEST SAMPLING).  A stage call cannot mix greedy (temperature 0) and sampled rows: a batch
         whose temperatures do is run as a greedy and a sampled sub-batch here, and the results come back in request order.
         logit_bias, banned_token_ids, min_tokens, allowed_token_ids: None (the keyword is not handed to the stages), one value
-        for the batch, or one per request, kept by the request through every regrouping (module docstring, Logit edits)."""
+        for the batch, or one per request, kept by the request through every regrouping (module docstring, Logit edits).
+        repetition_penalty, presence_penalty, frequency_penalty: None (not handed on), one number for the batch, or one per
+        request, travelling like the edits (serving/stages.py, PENALTIES)."""
         prompts = list(prompts)
         n = len(prompts)
         seeds = check_seeds(seeds, n)
         max_tokens = check_max_tokens(max_tokens, n)
         sampling = {k: check_per_prompt(v, n, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
         edits = check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n, allowed_token_ids)
+        edits.update(check_penalty_args(dict(zip(_PENALTY_KEYS, (repetition_penalty, presence_penalty, frequency_penalty))), n))
         if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
             temperature = check_per_prompt(temperature, n, "temperature")
         if isinstance(temperature, list) and any(t == 0.0 for t in temperature):

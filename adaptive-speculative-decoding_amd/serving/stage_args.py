@@ -204,6 +204,35 @@ def check_min_tokens(value, n: int) -> List[int]:
     return _per_prompt(value, n, one, "min_tokens values")
 
 
+def _check_penalty(value, n: int, name: str, lo: float, hi: float, open_lo: bool) -> List[float]:
+    """One penalty keyword of generate (PENALTIES): a number in the range for all `n` prompts, or a sequence of n such numbers
+    -> n floats.  A bool, a NaN, anything that is no number (None inside a sequence included) and a value outside the range
+    raise ValueError."""
+    def one(v):
+        ok = not isinstance(v, bool) and isinstance(v, _NUMBER) and (lo < float(v) if open_lo else lo <= float(v)) and float(v) <= hi
+        if not ok:                                        # (NaN fails both comparisons)
+            raise ValueError(f"{name} must be a number in {'(' if open_lo else '['}{lo:g}, {hi:g}], got {v!r}")
+        return float(v)
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+    return _per_prompt(value, n, one, f"{name} values")
+
+
+def check_repetition_penalty(value, n: int) -> List[float]:
+    """generate's `repetition_penalty` (vLLM's range): a number in (0, 2], or one per prompt -> n floats; 1 is neutral."""
+    return _check_penalty(value, n, "repetition_penalty", 0.0, 2.0, True)
+
+
+def check_presence_penalty(value, n: int) -> List[float]:
+    """generate's `presence_penalty` (OpenAI's / vLLM's range): a number in [-2, 2], or one per prompt -> n floats; 0 is neutral."""
+    return _check_penalty(value, n, "presence_penalty", -2.0, 2.0, False)
+
+
+def check_frequency_penalty(value, n: int) -> List[float]:
+    """generate's `frequency_penalty` (OpenAI's / vLLM's range): a number in [-2, 2], or one per prompt -> n floats; 0 is neutral."""
+    return _check_penalty(value, n, "frequency_penalty", -2.0, 2.0, False)
+
+
 def check_seeds(seed, n: int) -> Optional[List[int]]:
     """generate's `seed`: None, one int in [0, 2^64) for all `n` prompts, or a sequence of n such ints -> None or n ints."""
     def one(v):

@@ -133,8 +133,8 @@ non-integer or out-of-vocabulary id, a bias that is no number, NaN or outside [-
 min_tokens, a sequence of the wrong length, more than 1024 entries in one row after merging, a row whose banned ids (for ever
 or at its first token) would leave no token.  NOT BUILT: `min_tokens` > 0 on a row whose stop list holds a MULTI-token
 sequence raises ValueError (the match would have to be suppressed in the commit kernels, which stay as they are); multi-token
-`bad_words`; stateful penalties (repetition, presence, frequency), which need per-token state on top of this operation; and
-serving/hierarchy.py's loop.  (Allow-lists are a dense mask, not a sparse edit: the next section.)
+`bad_words`; and serving/hierarchy.py's loop.  (Allow-lists are a dense mask, not a sparse edit: the next section; the stateful
+penalties keep per-token state: PENALTIES below.)
 
 ALLOW-LISTS.  `generate(allowed_token_ids=)` (or StageConfig.allowed_token_ids; None takes the configuration's value) is
 vLLM's `SamplingParams.allowed_token_ids`: a sequence of token ids for every prompt, or one sequence (or None: no list) per
@@ -157,6 +157,37 @@ list minus its banned ids -- permanent bans and the stop ids under min_tokens al
 (a grammar's mask differs at each of the K + 1 positions; the mask_row indirection leaves room), folding the mask into the
 samplers, and serving/hierarchy.py's loop.
 
+PENALTIES.  `generate(repetition_penalty=, presence_penalty=, frequency_penalty=)` (or the StageConfig fields of those names; None
+takes the configuration's value, which defaults to 1.0 / 0.0 / 0.0) are vLLM's `apply_penalties`, each one value for the call or
+one per prompt: repetition_penalty in (0, 2], presence_penalty and frequency_penalty in [-2, 2] (vLLM's and OpenAI's ranges).  They
+run behind the allow-list and the sparse edit and ahead of the temperature -- mask -> edit -> penalties -> temperature -> top-k
+-> top-p -> min-p, vLLM V1's order (`logit_bias` first, penalties second).  For row b at a position whose history is H -- the
+row's real prompt tokens (the left-padding is not history), its committed generated tokens, and the step's proposals in front of
+that position -- token v is SEEN when it occurs anywhere in H and c is the number of its occurrences among the generated tokens
+and proposals in H (the prompt is not counted).  In f32, in this order, with one rounding to the logits' dtype at the end:
+y = x; if seen and rep != 1: y = x / rep where x > 0, else x * rep; if c > 0: y = y - freq * c, then y = y - pres.  -inf stays
+-inf (a masked or banned token stays so); a result that would round to +inf (f16 with rep < 1) is stored as the dtype's largest
+finite value; an element the penalties do not change is not stored at all.  STATE, allocated once per call and only when some
+row has a non-neutral value: `seen`, one bit per (row, token) in the allow-list's bit layout, whose prompt bits are built on the
+host from the unpadded prompt ids and uploaded once (ops.pack_penalties); `counts`, int32 [B, V]; the rows' three values; and at
+a verifying stage a [B, draft_len] buffer of the step's proposals, whose column k the loop fills after proposal k.  Every loop
+calls ops.penalty_rows (asd_penalty_rows, in place) once per logits tensor, immediately behind the edit's call at each of its
+three sites: stage 0's [B, V] logits (no proposals); every proposal's draft logits (proposal k sees the proposals 0 .. k - 1 of
+the step, which are not committed yet); the target's [B, K+1, V] output before anything is sliced from or scored on it (row j
+sees the proposals 0 .. j - 1 -- the history the draft's row j had).  Draft and target so receive the SAME penalty from the
+SAME history at every position, and -- the argument of LOGIT EDITS, word for word -- the draft -> verify -> residual chain
+stays lossless against the penalised target distribution.  ops.penalty_commit (asd_penalty_commit) follows the step's commit
+(and the top-N commit): the step's committed tokens enter `seen` and `counts` on the device.  Rejected proposals were never
+written there, so nothing is rolled back; the commit kernels leave n_commit = 0 for a finished row, so its state is frozen.
+Consequences: the returned log-probs and top-N tables are those of the PENALISED distribution; greedy decoding takes the
+arg-max of the penalised row; the rows route, seeds, the stop and finish routes, edits, masks and `logprobs = N` are untouched
+and compose with it.  A call whose rows are all neutral (no keyword, 1.0 / 0.0 / 0.0, sequences of them) makes exactly the ops
+calls it made before.  ValueError before any launch and before the prompts are encoded: a bool, a NaN, a value that is no
+number or lies outside its range, a sequence of the wrong length or one that holds None.  COST: the kernel scans a row's seen
+bits (19 KB at V = 152064) and works per distinct seen token, not per vocabulary entry (profiles/penalties_step.json).  NOT
+BUILT: vLLM's `repetition_penalty` over the OUTPUT only (here, as in vLLM, the prompt counts as seen), removing finished rows
+from the state, and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -176,8 +207,8 @@ from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
 from .stage_args import (MAX_LOGIT_EDITS, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS, _check_logprobs, _check_min_p,  # noqa: F401
                          _check_stop_ids, _check_stop_sequences, _is_seq, check_allowed_token_ids, check_banned_token_ids,
-                         check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt, check_rows_keep_a_token,
-                         check_seeds, merge_logit_edits)
+                         check_frequency_penalty, check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt,
+                         check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
 # reference stage label -> the Qwen2.5 shape this build runs in its place (configs/models.yaml names the tiers by size)
@@ -218,6 +249,9 @@ class StageConfig:
     banned_token_ids: Sequence[int] = ()     # token ids that are never proposed, accepted or drawn
     min_tokens: int = 0                      # the stop ids are banned until a row has generated this many tokens
     allowed_token_ids: Optional[Sequence[int]] = None    # the only token ids a row may hold (module docstring, ALLOW-LISTS)
+    repetition_penalty: float = 1.0          # in (0, 2]; 1: off (module docstring, PENALTIES)
+    presence_penalty: float = 0.0            # in [-2, 2]; 0: off
+    frequency_penalty: float = 0.0           # in [-2, 2]; 0: off
 
 
 _REASONS = {1: "stop", 2: "length"}
@@ -238,6 +272,7 @@ class _Plan(NamedTuple):
     finish_route: bool                       # asd_commit_step_finish: only for what the stop-id route cannot do
     edit_rows: list                          # every row's merged (id, bias, until) entries
     mask_rows: list                          # every row's allow-list: a sorted tuple of ids, or None
+    penalties: Optional[Tuple[list, list, list]]    # every row's repetition, presence and frequency penalty; None: all neutral
     seeds: Optional[List[int]]
     n_top: int
 
@@ -266,6 +301,31 @@ class _MaskState:
     def apply(self, logits: torch.Tensor) -> torch.Tensor:
         """logits [B, V] or [B, K+1, V], masked in place."""
         return self.ops.logit_mask_rows(logits, self.packed)
+
+
+class _PenaltyState:
+    """What a generate call with a non-neutral penalty keeps: the rows' seen bits, counts and parameters on the device (the
+    prompt's bits uploaded once) and, at a verifying stage, the [B, draft_len] buffer of the step's proposals.  `apply` is the
+    loops' one call per logits tensor, behind the edit's; `propose` notes proposal k; `commit` follows the step's commit
+    (module docstring, PENALTIES)."""
+
+    def __init__(self, ops, penalties, prompt_ids, V: int, draft_len: int, device):
+        self.ops = ops
+        self.packed = ops.pack_penalties(*penalties, prompt_ids, int(V), device)
+        self.step_tok = torch.zeros((len(prompt_ids), draft_len), dtype=torch.int32, device=device) if draft_len else None
+
+    def apply(self, logits: torch.Tensor, n_prev: int = 0) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], penalised in place; position j sees the step's first n_prev + j proposals."""
+        if self.step_tok is None:
+            return self.ops.penalty_rows(logits, self.packed)
+        return self.ops.penalty_rows(logits, self.packed, self.step_tok, n_prev)
+
+    def propose(self, k: int, tok: torch.Tensor) -> None:
+        self.step_tok[:, k] = tok
+
+    def commit(self, tokens: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor, cap: int) -> None:
+        """Behind the step's commit, which left seq_len and n_commit (0 for a finished row: its state stays)."""
+        self.ops.penalty_commit(tokens, seq_len, n_commit, self.packed, cap)
 
 
 # ---------------------------------------------------------------------------------------------- how a call's rows end
@@ -546,14 +606,17 @@ class _SampledRows(_Sampled):
 class _CallState:
     """The device side of one generate call, built in this one place from the plan and the encoded prompts and handed to the
     loop: how rows end (`end`), the allow-list (`mask`, None without a list), the logit edit (`edit`, None without an entry), the
-    sampler and the top-N tables (`top`, None when off).  Uploads happen here, once; a part that is off costs no launch."""
+    penalties (`pen`, None when every row is neutral), the sampler and the top-N tables (`top`, None when off).  Uploads happen
+    here, once; a part that is off costs no launch.  `prompt_ids`: every row's prompt ids without the padding."""
 
-    def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor):
+    def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor, prompt_ids: List[List[int]]):
         (B, P), dev, ops = ids.shape, ids.device, stage.ops
         self.end = _StopSequences(ops, plan.row_seqs, plan.limits, P, dev) if plan.finish_route else \
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
         self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
+        self.pen = _PenaltyState(ops, plan.penalties, prompt_ids, stage.shape.vocab,
+                                 0 if stage.draft is None else stage.config.draft_len, dev) if plan.penalties else None
         # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
         self.top = _TopState(ops, plan.n_top, plan.inv_t, B, P + plan.max_tokens, dev,
@@ -605,11 +668,16 @@ class Stage:
     # ------------------------------------------------------------------------------------------ prompts / text
     def encode_prompts(self, prompts: Sequence[str]) -> torch.Tensor:
         """[B, P] int64 on the stage's device: the last P ids of every prompt, left-padded with id 0 (module docstring)."""
+        return self._encode(prompts)[0]
+
+    def _encode(self, prompts: Sequence[str]) -> Tuple[torch.Tensor, List[List[int]]]:
+        """-> (encode_prompts' tensor, every row's kept ids WITHOUT the padding: the lists the tensor was padded from)."""
         V = self.shape.vocab
         rows = [[i % V for i in self.tokenizer.encode(p, return_tensors=None)] for p in prompts]
         P = max(2, min(max((len(r) for r in rows), default=0), int(self.config.max_prompt_tokens)))
-        rows = [[0] * (P - len(r)) + r[-P:] for r in rows]
-        return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), P).to(self.device)
+        real = [r[-P:] for r in rows]
+        rows = [[0] * (P - len(r)) + r for r in real]
+        return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), P).to(self.device), real
 
     @staticmethod
     def decode_tokens(ids: Sequence[int]) -> str:
@@ -623,7 +691,8 @@ class Stage:
                  min_p=None,
                  seed=None, stop_sequences=None,
                  stop_sequences_per_prompt=None, top_k=None, logit_bias=None, banned_token_ids=None,
-                 min_tokens=None, allowed_token_ids=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
+                 frequency_penalty=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -666,17 +735,25 @@ class Stage:
         alike and ahead of the edits above, so only listed tokens are proposed, accepted, drawn or listed and the log-probs are
         those of the restricted distribution; with `logprobs` = N above the list's size the unfillable slots hold id -1 and
         -inf.  An empty list, and a list that the bans or min_tokens' stop ids empty, raise ValueError; a stop id outside a
-        row's list can never end that row (module docstring, ALLOW-LISTS)."""
+        row's list can never end that row (module docstring, ALLOW-LISTS).
+        `repetition_penalty` (in (0, 2]; 1 = off), `presence_penalty` and `frequency_penalty` (in [-2, 2]; 0 = off) are vLLM's:
+        None = the StageConfig field of that name; one value for every prompt or one per prompt.  A token that occurs in the
+        row's prompt or among its generated tokens has its logit divided (when positive) or multiplied (otherwise) by the
+        repetition penalty; a token that occurs c > 0 times among the generated tokens loses frequency_penalty * c +
+        presence_penalty.  The history at a position includes the step's own proposals in front of it, draft and target logits
+        receive the same penalty, and log-probs and top-N tables are those of the penalised distribution, behind the mask and
+        the edits above and ahead of the temperature (module docstring, PENALTIES)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
-                          stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids)
+                          stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
+                          repetition_penalty, presence_penalty, frequency_penalty)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
-        ids = self.encode_prompts(plan.prompts)
+        ids, prompt_ids = self._encode(plan.prompts)
         P = ids.shape[1]
-        state = _CallState(self, plan, ids)
+        state = _CallState(self, plan, ids, prompt_ids)
         decode = self._decode_plain if self.draft is None else self._decode_speculative
         tokens, lps, seq_len = decode(ids, plan.max_tokens, state)
         self.ops.check_status()
@@ -693,7 +770,8 @@ class Stage:
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
-              stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids) -> _Plan:
+              stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
+              repetition_penalty, presence_penalty, frequency_penalty) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -732,6 +810,11 @@ class Stage:
                                       check_min_tokens(given(min_tokens, cfg.min_tokens), n), row_seqs, V)
         mask_rows = check_allowed_token_ids(given(allowed_token_ids, cfg.allowed_token_ids), n, V)
         check_rows_keep_a_token(mask_rows, edit_rows)
+        penalties = (check_repetition_penalty(given(repetition_penalty, cfg.repetition_penalty), n),
+                     check_presence_penalty(given(presence_penalty, cfg.presence_penalty), n),
+                     check_frequency_penalty(given(frequency_penalty, cfg.frequency_penalty), n))
+        if all(r == 1.0 and p == 0.0 and f == 0.0 for r, p, f in zip(*penalties)):
+            penalties = None                             # every row neutral: no state, no call
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -749,7 +832,7 @@ class Stage:
         return _Plan(prompts=prompts, limits=tuple(limits), max_tokens=int(limit), greedy=greedy,
                      inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
-                     edit_rows=edit_rows, mask_rows=mask_rows, seeds=seeds, n_top=n_top)
+                     edit_rows=edit_rows, mask_rows=mask_rows, penalties=penalties, seeds=seeds, n_top=n_top)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -768,7 +851,7 @@ class Stage:
         B, P = ids.shape
         dev = ids.device
         cap = P + max_tokens
-        end, mask, edit, top, sampler = st.end, st.mask, st.edit, st.top, st.sampler
+        end, mask, edit, pen, top, sampler = st.end, st.mask, st.edit, st.pen, st.top, st.sampler
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -781,6 +864,8 @@ class Stage:
                 mask.apply(logits)                                       # the allow-list first, then the sparse edit (they commute)
             if edit is not None:
                 edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
+            if pen is not None:
+                pen.apply(logits)                                        # the penalties last: mask -> edit -> penalties
             n_acc, tok, lp = sampler.draw(logits, step)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
             if top is not None:
@@ -788,6 +873,8 @@ class Stage:
             end.commit(None, None, n_acc, tok, lp, seq_len, tokens, lps, n_commit, cap)
             if top is not None:
                 top.commit(seq_len, n_commit)
+            if pen is not None:
+                pen.commit(tokens, seq_len, n_commit, cap)               # the committed tokens enter the history
             if kept is not None:                                        # tests: the record, with the top-N rows behind it
                 self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
             self.last_steps = step + 1
@@ -815,7 +902,7 @@ class Stage:
         dev = ids.device
         Kd = cfg.draft_len
         cap = P + max_tokens
-        end, mask, edit, top, sampler = st.end, st.mask, st.edit, st.top, st.sampler
+        end, mask, edit, pen, top, sampler = st.end, st.mask, st.edit, st.pen, st.top, st.sampler
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
             m.reset()
@@ -840,7 +927,11 @@ class Stage:
                     mask.apply(dl)
                 if edit is not None:
                     edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
+                if pen is not None:
+                    pen.apply(dl, k)                                    # ... and sees the proposals 0 .. k - 1 of this step
                 toks.append(sampler.propose(dl, k))
+                if pen is not None:
+                    pen.propose(k, toks[-1])
                 if k + 1 < Kd:
                     dl = draft.forward_ragged(toks[-1].to(torch.int64)[:, None], L + k, window)[:, -1]
             tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
@@ -849,6 +940,8 @@ class Stage:
                 mask.apply(t_out)                                       # the whole [B, K+1, V] output, before any slice
             if edit is not None:
                 edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any slice
+            if pen is not None:
+                pen.apply(t_out)                                        # row j sees the proposals 0 .. j - 1, as the draft's did
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
             if top is not None:
@@ -856,6 +949,8 @@ class Stage:
             end.commit(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
             if top is not None:
                 top.commit(seq_len, n_commit)
+            if pen is not None:
+                pen.commit(tokens, seq_len, n_commit, cap)               # the committed tokens enter the history
             if kept is not None:                                        # tests: the record, with the top-N rows behind it
                 self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
             steps += 1

@@ -537,6 +537,58 @@ int asd_logit_mask_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int6
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Stateful penalties AHEAD of the samplers and behind the mask and the edit -- vLLM's `apply_penalties`: repetition_penalty,
+ * presence_penalty, frequency_penalty.  A penalised row is an ordinary input of every sampler; applied alike, from the same
+ * history, to the draft's proposal rows and the target's K+1 rows, the draft -> verify -> residual chain stays lossless against
+ * the PENALISED target distribution.
+ * State, DEVICE arrays kept by the caller for one generation: seen uint32 [B, W], W = (V + 31) / 32, in asd_logit_mask_rows'
+ * bit layout -- bit (v & 31) of word (v >> 5) of row b SET when token v occurs in sequence b's prompt or among its committed
+ * generated tokens (bits at v >= V are ignored) -- and counts int32 [B, V], the occurrences of v among sequence b's committed
+ * generated tokens (the prompt is not counted).  THE STATE CONTRACT: counts[b][v] > 0 only where the bit is set;
+ * asd_penalty_commit keeps it.  counts is read only where the bit is set or the token is one of the step's proposals.
+ * params float [B, 3]: (rep, pres, freq) of sequence b.  rep <= 0 or NaN reads as 1.  A sequence with (1, 0, 0) is not touched.
+ *
+ * asd_penalty_rows: logits in asd_logit_edit_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32,
+ * K1 == 1 is a [B, V] matrix -- edited in place.  step_tok: int32 [B] rows of n_tok proposals, ld_tok >= n_tok elements apart:
+ * the tokens the step has proposed and NOT committed.  Position j of sequence b sees step_tok[b][0 .. n_prev + j): a proposal
+ * row of draft slot k is K1 = 1 with n_prev = k, the target's K+1 rows are n_prev = 0.  step_tok == NULL: no position sees a
+ * proposal, and n_prev must be 0.  A proposal outside [0, V) is skipped.  n_tok <= ASD_MAX_DRAFT_LEN.
+ * At (b, j), token v is SEEN when its bit is set or it is among the proposals the position sees, and c is counts[b][v] plus
+ * its occurrences among them.  In f32, in exactly this order, without fused multiply-add, the division correctly rounded:
+ *     y = x
+ *     if seen and rep != 1:   y = (x > 0) ? x / rep : x * rep
+ *     if c > 0:               y = y - freq * (float)c;   y = y - pres
+ * and the element becomes round_to_dtype(y), one rounding to nearest even -- except that nothing is stored where y == x (an
+ * element that is neither seen nor counted, a -inf, a zero keep their bits), and that a result which rounds to +inf (f16 with
+ * rep < 1; an f32 overflow) is stored as the dtype's largest finite value: the samplers forbid +inf.  Nothing but such
+ * elements is written: the row padding, neutral sequences and everything around the tensor keep their bits.
+ * One launch, grid B x S with S chosen by the launcher (a row's mask words are cut into slices of whole words; the result does
+ * not depend on S); the cost follows the number of distinct seen tokens, not V.  Every element is written by at most one lane
+ * of one workgroup: no atomics, no workspace, nothing waits on another workgroup.
+ * Status, in this order: negative B / K1 / V / n_tok / n_prev: invalid argument; B, K1 or V == 0: ASD_OK, nothing launched;
+ * unknown dtype, n_tok > ASD_MAX_DRAFT_LEN: unsupported; NULL logits / seen / counts / params, ld_row < V,
+ * ld_seq < K1*ld_row, step_tok == NULL with n_prev != 0, step_tok != NULL with n_prev + K1 - 1 > n_tok or ld_tok < n_tok:
+ * invalid argument; logits not aligned to the element size, or seen / counts / params / step_tok not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+int asd_penalty_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                     const uint32_t* seen /*[B, (V+31)/32]*/, const int32_t* counts /*[B, V]*/, const float* params /*[B, 3]*/,
+                     const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
+
+/* asd_penalty_commit: behind the step's commit kernel (asd_commit_step_lp / _stop / _finish, which left seq_len and n_commit),
+ * the n_commit[b] tokens at tokens[b][seq_len[b] - n_commit[b] .. seq_len[b]) enter sequence b's state: counts[b][v] grows by
+ * the multiplicity of v among them and the bit of v is set.  tokens: int32 rows ld_tokens >= max_len elements apart.
+ * n_commit[b] is clamped into [0, ASD_MAX_DRAFT_LEN + 1], a position into [0, max_len), and a token outside [0, V) is skipped,
+ * so damaged inputs never leave the arrays.  The commit kernels leave n_commit == 0 for a finished sequence: its state is
+ * frozen.  Rejected proposals were never written to `tokens`: there is nothing to roll back.
+ * One launch, one workgroup per sequence; a token committed twice in one step is counted by ONE lane (its first occurrence),
+ * the bit is set with a vector atomic OR (two tokens may share a word).
+ * Status, in this order: negative B / V / max_len: invalid argument; B, V or max_len == 0: ASD_OK, nothing launched; NULL
+ * tokens / seq_len / n_commit / seen / counts, ld_tokens < max_len: invalid argument; a pointer not aligned to 4: alignment. */
+int asd_penalty_commit(const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens, const int32_t* seq_len /*[B]*/,
+                       const int32_t* n_commit /*[B]*/, int B, int V, int max_len, uint32_t* seen /*in/out [B, (V+31)/32]*/,
+                       int32_t* counts /*in/out [B, V]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A7  log-prob statistics: features [5..9] of extract_features,
  * src/training/generate_training_data.py:166-175 -- np.mean, np.std (population), np.min,
  * np.percentile(.,25) (linear interpolation), np.median, all in float64 like numpy.

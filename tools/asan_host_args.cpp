@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows and asd_logit_mask_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows and asd_penalty_commit in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -295,6 +295,61 @@ int main() {
         EXPECT(MASK(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, u32, 1, nullptr), ASD_ERR_ALIGNMENT);
         EXPECT(MASK(p, BF16, K1 * V, V, B, K1, V, reinterpret_cast<const uint32_t*>(rows + 2), 1, nullptr), ASD_ERR_ALIGNMENT);   // mask_bits
 #undef MASK
+    }
+
+    // ---- asd_penalty_rows / asd_penalty_commit: every rejection, and every "nothing to do", comes before the launch
+    {
+#define PEN(x_, dt_, lds_, ldr_, B_, K1_, V_, seen_, cnt_, par_, tok_, ldt_, nt_, np_) \
+    asd_penalty_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, seen_, cnt_, par_, tok_, ldt_, nt_, np_, nullptr)
+        const int K1 = 5;
+        const uint32_t* u32 = reinterpret_cast<const uint32_t*>(rows);
+        const uint32_t* u32_off = reinterpret_cast<const uint32_t*>(rows + 2);
+        EXPECT(PEN(p, BF16, K1 * V, V, -1, K1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, -1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, -1, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, f32, i32, 4, -1, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, f32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);
+        EXPECT(PEN(p, BF16, K1 * V, V, 0, K1, V, u32, i32, f32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);      // ... before the empty batch
+        EXPECT(PEN(nullptr, 99, 0, 0, 0, K1, V, nullptr, nullptr, nullptr, nullptr, 0, 0, 0), ASD_OK);       // B == 0
+        EXPECT(PEN(nullptr, 99, 0, 0, B, 0, V, nullptr, nullptr, nullptr, nullptr, 0, 0, 0), ASD_OK);        // K1 == 0
+        EXPECT(PEN(nullptr, 99, 0, 0, B, K1, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0), ASD_OK);       // V == 0
+        EXPECT(PEN(p, 99, K1 * V, V, B, K1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);          // dtype
+        EXPECT(PEN(p, -1, K1 * V, V, B, K1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, f32, i32, 65, ASD_MAX_DRAFT_LEN + 1, 0), ASD_ERR_UNSUPPORTED);   // n_tok
+        EXPECT(PEN(nullptr, BF16, K1 * V, V, B, K1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, nullptr, i32, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // seen
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, nullptr, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // counts
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, nullptr, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // params
+        EXPECT(PEN(p, BF16, K1 * V, V - 1, B, K1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // ld_row < V
+        EXPECT(PEN(p, BF16, K1 * V - 1, V, B, K1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // ld_seq < K1 ld_row
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, f32, nullptr, 0, 0, 1), ASD_ERR_INVALID_ARG);    // n_prev without step_tok
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, f32, i32, 4, 4, 1), ASD_ERR_INVALID_ARG);        // position 4 would see 5 of 4
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, f32, i32, 3, 4, 0), ASD_ERR_INVALID_ARG);        // ld_tok < n_tok
+        EXPECT(PEN(rows + 1, BF16, K1 * V, V, B, K1, V, u32, i32, f32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);   // below the element size
+        EXPECT(PEN(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, u32, i32, f32, nullptr, 0, 0, 0), ASD_ERR_ALIGNMENT);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32_off, i32, f32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);      // seen
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, reinterpret_cast<int32_t*>(rows + 2), f32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, reinterpret_cast<float*>(rows + 2), i32, 4, 4, 0), ASD_ERR_ALIGNMENT);
+        EXPECT(PEN(p, BF16, K1 * V, V, B, K1, V, u32, i32, f32, reinterpret_cast<int32_t*>(rows + 2), 4, 4, 0), ASD_ERR_ALIGNMENT);
+#undef PEN
+#define PCOMMIT(tok_, ld_, seq_, n_, B_, V_, cap_, seen_, cnt_) asd_penalty_commit(tok_, ld_, seq_, n_, B_, V_, cap_, seen_, cnt_, nullptr)
+        uint32_t* seen = reinterpret_cast<uint32_t*>(rows);
+        EXPECT(PCOMMIT(i32, 32, i32, i32, -1, V, 32, seen, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(i32, 32, i32, i32, B, -1, 32, seen, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(i32, 32, i32, i32, B, V, -1, seen, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(nullptr, 0, nullptr, nullptr, 0, V, 32, nullptr, nullptr), ASD_OK);                  // B == 0
+        EXPECT(PCOMMIT(nullptr, 0, nullptr, nullptr, B, 0, 32, nullptr, nullptr), ASD_OK);                  // V == 0
+        EXPECT(PCOMMIT(nullptr, 0, nullptr, nullptr, B, V, 0, nullptr, nullptr), ASD_OK);                   // max_len == 0
+        EXPECT(PCOMMIT(nullptr, 32, i32, i32, B, V, 32, seen, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(i32, 32, nullptr, i32, B, V, 32, seen, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(i32, 32, i32, nullptr, B, V, 32, seen, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(i32, 32, i32, i32, B, V, 32, nullptr, i32), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(i32, 32, i32, i32, B, V, 32, seen, nullptr), ASD_ERR_INVALID_ARG);
+        EXPECT(PCOMMIT(i32, 31, i32, i32, B, V, 32, seen, i32), ASD_ERR_INVALID_ARG);                       // ld_tokens < max_len
+        EXPECT(PCOMMIT(reinterpret_cast<int32_t*>(rows + 2), 32, i32, i32, B, V, 32, seen, i32), ASD_ERR_ALIGNMENT);
+        EXPECT(PCOMMIT(i32, 32, i32, i32, B, V, 32, reinterpret_cast<uint32_t*>(rows + 2), i32), ASD_ERR_ALIGNMENT);
+        EXPECT(PCOMMIT(i32, 32, i32, i32, B, V, 32, seen, reinterpret_cast<int32_t*>(rows + 2)), ASD_ERR_ALIGNMENT);
+#undef PCOMMIT
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);

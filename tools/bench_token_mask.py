@@ -103,9 +103,10 @@ def _column(fields, *names):
     raise KeyError(f"none of {names} among the trace's columns {fields}")
 
 
-def parse_trace(directory, names, calls):
+def parse_trace(directory, names, calls, separator=SEPARATOR, trailing=0):
     """The kernel-trace CSV(s) under `directory` -> {variant: [per-call kernel time in us]}: dispatches in start order, cut at
-    the separator kernel; the last len(names) + 1 separators delimit the variants in order (the warm-up has none)."""
+    the separator kernel; the last len(names) + 1 separators delimit the variants in order (the warm-up has none).  `trailing`:
+    dispatches at the end of every segment that prepare the NEXT variant and are left out."""
     rows = []
     for path in glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True):
         with open(path, newline="") as f:
@@ -116,13 +117,13 @@ def parse_trace(directory, names, calls):
     if not rows:
         raise RuntimeError(f"no kernel trace under {directory}")
     rows.sort()
-    cuts = [i for i, r in enumerate(rows) if any(s in r[2] for s in SEPARATOR)]
+    cuts = [i for i, r in enumerate(rows) if any(s in r[2] for s in separator)]
     if len(cuts) < len(names) + 1:
         raise RuntimeError(f"{len(cuts)} separator launches in the trace, expected {len(names) + 1}")
     cuts = cuts[-(len(names) + 1):]
     out = {}
     for name, lo, hi in zip(names, cuts, cuts[1:]):
-        seg = rows[lo + 1:hi]
+        seg = rows[lo + 1:hi - trailing]
         if not seg or len(seg) % calls:
             raise RuntimeError(f"{name}: {len(seg)} dispatches for {calls} calls")
         m = len(seg) // calls                               # kernels per call (1 for every variant here, but counted, not assumed)
