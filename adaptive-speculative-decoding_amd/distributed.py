@@ -454,6 +454,20 @@ class HipOps:
         (n_commit 0) keeps its state, and a rejected proposal was never in it."""
         self.K.penalty_commit(tokens, seq_len, n_commit, pen, max_len)
 
+    def pack_bad_words(self, rows, device):
+        """Every row's bad words (1..8 token ids each, at most 256 per row) -> the device tables of bad_words_rows
+        (kernels.pack_bad_words: one upload per generate call; equal rows share one list)."""
+        return self.K.pack_bad_words(rows, device)
+
+    @traced("bad_words_rows")
+    def bad_words_rows(self, logits, words, tokens, seq_len, start, max_len, step_tok=None, n_prev: int = 0):
+        """Multi-token bans ahead of the samplers (asd_bad_words_rows): logits [B, V] or [B, K1, V] (any strides with a unit
+        last stride) -> the same tensor, with the last id of every word of row b at -inf where the word's other ids end the
+        row's history: its committed generated tokens tokens[b, start:seq_len[b]] and the step's proposals
+        step_tok[b, :n_prev + j] at position j.  One launch, no workspace, no state; a stage loop makes the call once per logits
+        tensor, behind logit_mask_rows and in front of logit_edit_rows, and only when some row of the call has a word."""
+        return self.K.bad_words_rows(logits, words, tokens, seq_len, start, max_len, step_tok, n_prev)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

@@ -1369,3 +1369,88 @@ def penalty_commit(tokens: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.
                                    _dev(n_commit, "n_commit", torch.int32), Bv, pen.V, cap, _dev(pen.seen, "seen", torch.int32),
                                    _dev(pen.counts, "counts", torch.int32), _stream())
     B.check("asd_penalty_commit", rc)
+
+
+# ------------------------------------------------------------------------------- bad words (multi-token bans)
+@dataclass
+class BadWords:
+    """The word tables of asd_bad_words_rows on the device (pack_bad_words): word_tok i32 [n, MAX_BAD_WORD_LEN], word_n i32 [n];
+    row_first i32 [B+1], or None when every row owns the words [0, n) (n_shared = n)."""
+    word_tok: torch.Tensor
+    word_n: torch.Tensor
+    row_first: Optional[torch.Tensor]
+    n: int                                   # words uploaded
+    B: int                                   # rows the lists were packed for
+
+
+def check_bad_word_rows(rows):
+    """The host side of pack_bad_words: `rows` = one list of words per batch row, a word 1..MAX_BAD_WORD_LEN token ids, at most
+    MAX_BAD_WORDS per row -> (flat words, row_first list or None when all rows hold equal lists)."""
+    lists = [[tuple(int(t) for t in w) for w in r] for r in rows]
+    for r, words in enumerate(lists):
+        if len(words) > B.MAX_BAD_WORDS:
+            raise ValueError(f"row {r} owns {len(words)} bad words, at most {B.MAX_BAD_WORDS}")
+        for w in words:
+            if not 1 <= len(w) <= B.MAX_BAD_WORD_LEN:
+                raise ValueError(f"a bad word holds 1..{B.MAX_BAD_WORD_LEN} token ids, got {len(w)}")
+            if any(not -2 ** 31 <= t < 2 ** 31 for t in w):
+                raise ValueError("bad word token ids must fit int32")
+    if lists and all(r == lists[0] for r in lists):
+        return lists[0], None
+    first = [0]
+    for words in lists:
+        first.append(first[-1] + len(words))
+    return [w for words in lists for w in words], first
+
+
+def pack_bad_words(rows, device) -> BadWords:
+    """The word tables of bad_words_rows from host lists, checked BEFORE anything is uploaded: `rows` holds one list of words per
+    batch row (a row's list may be empty).  When all rows hold equal lists one copy is uploaded and row_first is None (the
+    way pack_logit_edits treats a shared list)."""
+    rows = list(rows)
+    flat, first = check_bad_word_rows(rows)
+    tok = np.zeros((len(flat), B.MAX_BAD_WORD_LEN), dtype=np.int32)
+    for i, w in enumerate(flat):
+        tok[i, :len(w)] = w
+    return BadWords(torch.from_numpy(tok).to(device), torch.tensor([len(w) for w in flat], dtype=torch.int32).to(device),
+                    None if first is None else torch.tensor(first, dtype=torch.int32).to(device), len(flat), len(rows))
+
+
+def bad_words_rows(logits: torch.Tensor, words: BadWords, tokens: torch.Tensor, seq_len: torch.Tensor, start: int, max_len: int,
+                   step_tok: Optional[torch.Tensor] = None, n_prev: int = 0) -> torch.Tensor:
+    """Ban in place (asd_bad_words_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row stride
+    with unit stride along V.  The last id of a word of row b becomes -inf at position j when the word's other ids are the end
+    of the row's history tokens[b, start:seq_len[b]] ++ step_tok[b, :n_prev + j].  tokens i32 [B, >= max_len] contiguous;
+    seq_len i32 [B]: the step's lengths BEFORE its commit; start: the prompt length; step_tok i32 [B, n_tok] (unit stride along
+    the proposals) or None."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if words.B != Bv or tuple(seq_len.shape) != (Bv,):
+        raise ValueError(f"the bad words were packed for {words.B} rows and seq_len must be int32 [B]; logits have {Bv} rows")
+    if tokens.dim() != 2 or tokens.shape[0] != Bv or not 0 <= int(start) <= int(max_len) <= tokens.shape[1]:
+        raise ValueError(f"tokens must be int32 [B, >= max_len] and 0 <= start <= max_len, got {tuple(tokens.shape)}, {start}, {max_len}")
+    ld_tok = n_tok = 0
+    if step_tok is None:
+        if n_prev != 0:
+            raise ValueError("n_prev must be 0 without step_tok")
+    else:
+        if not step_tok.is_cuda or step_tok.dtype != torch.int32 or step_tok.dim() != 2 or step_tok.shape[0] != Bv or \
+                (step_tok.shape[1] > 1 and step_tok.stride(1) != 1):
+            raise ValueError("step_tok must be a CUDA int32 [B, n_tok] tensor with unit stride along the proposals")
+        n_tok = step_tok.shape[1]
+        ld_tok = step_tok.stride(0) if Bv > 1 else n_tok
+        if not 0 <= int(n_prev) or int(n_prev) + K1 - 1 > n_tok or ld_tok < n_tok:
+            raise ValueError(f"position {K1 - 1} would see {int(n_prev) + K1 - 1} proposals; step_tok holds {n_tok}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_bad_words_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
+                                   _dev(words.word_tok, "word_tok", torch.int32), _dev(words.word_n, "word_n", torch.int32),
+                                   _opt(words.row_first, "row_first", torch.int32), words.n,
+                                   _dev(tokens, "tokens", torch.int32), tokens.shape[1], _dev(seq_len, "seq_len", torch.int32),
+                                   int(start), int(max_len), None if step_tok is None else step_tok.data_ptr(), ld_tok, n_tok,
+                                   int(n_prev), _stream())
+    B.check("asd_bad_words_rows", rc)
+    return logits

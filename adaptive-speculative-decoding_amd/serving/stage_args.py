@@ -12,7 +12,9 @@ MAX_STOP_SEQS = 16                           # ASD_MAX_STOP_SEQS: entries of one
 MAX_STOP_SEQ_LEN = 8                         # ASD_MAX_STOP_SEQ_LEN
 MAX_TOP_LOGPROBS = 8                         # ASD_MAX_TOP_LOGPROBS
 MAX_LOGIT_EDITS = 1024                       # ASD_MAX_LOGIT_EDITS: (id, bias, until) entries of one row after merging
-MAX_LOGIT_BIAS = 100.0                       # |bias| <= 100, the range OpenAI documents
+MAX_BAD_WORDS = 256                          # ASD_MAX_BAD_WORDS: distinct words of one row (BAD WORDS)
+MAX_BAD_WORD_LEN = 8                         # ASD_MAX_BAD_WORD_LEN
+MAX_LOGIT_BIAS = 100.0                      # |bias| <= 100, the range OpenAI documents
 _EDIT_FOREVER = 2 ** 31 - 1                  # `until` of a permanent ban
 _NUMBER = (int, float, np.integer, np.floating)
 
@@ -186,13 +188,61 @@ def check_allowed_token_ids(value, n: int, vocab: int) -> List[Optional[Tuple[in
     return _per_prompt(list(value), n, one, "allowed_token_ids lists")
 
 
-def check_rows_keep_a_token(allowed: List[Optional[Tuple[int, ...]]], edit_rows: List[List[Tuple[int, float, int]]]) -> None:
+def check_rows_keep_a_token(allowed: List[Optional[Tuple[int, ...]]], edit_rows: List[List[Tuple[int, float, int]]],
+                            bad_rows: Optional[List[List[Tuple[int, ...]]]] = None, vocab: Optional[int] = None) -> None:
     """A row's allow-list minus every merged edit entry with until > 0 -- the permanent bans AND the min_tokens bans, during
-    whose hold-back the row would be all -inf -- must keep a token: ValueError naming the prompt otherwise."""
-    for b, (ids, entries) in enumerate(zip(allowed, edit_rows)):
-        if ids is not None and not set(ids) - {t for t, _, u in entries if u > 0}:
-            raise ValueError(f"prompt {b}: the banned token ids (min_tokens' stop ids included) leave no token of its "
-                             f"allowed_token_ids ({len(ids)})")
+    whose hold-back the row would be all -inf -- must keep a token: ValueError naming the prompt otherwise.  With `bad_rows`
+    (every row's bad words; BAD WORDS) the rule is conservative, because which word matches is decided on the device: the LAST id
+    of every word of the row counts as banned, and a row without an allow-list must keep a token of the `vocab` ids."""
+    bad_rows = [[] for _ in allowed] if bad_rows is None else bad_rows
+    for b, (ids, entries, words) in enumerate(zip(allowed, edit_rows, bad_rows)):
+        gone = {t for t, _, u in entries if u > 0} | {w[-1] for w in words}
+        if ids is not None and not set(ids) - gone:
+            raise ValueError(f"prompt {b}: the banned token ids (min_tokens' stop ids and the last ids of its bad_words "
+                             f"included) leave no token of its allowed_token_ids ({len(ids)})")
+        if ids is None and words and len(gone) >= vocab:
+            raise ValueError(f"prompt {b}: the banned token ids and the last ids of its bad_words leave no token of the "
+                             f"vocabulary ({vocab})")
+
+
+def _check_bad_word_list(entries, vocab: int, tokenizer, what: str) -> List[Tuple[int, ...]]:
+    """One list of bad words: each entry a str (encoded by the stage's tokenizer, ids folded into the vocabulary exactly as
+    _check_stop_sequences folds a stop string) or a sequence of integer ids in [0, vocab); every entry must come to 1..8 ids."""
+    if entries is None:
+        return []
+    if not _is_seq(entries):
+        raise ValueError(f"{what} must be a list of strings or token-id sequences, got {entries!r}")
+    out = []
+    for e in entries:
+        if isinstance(e, str):
+            ids = [int(i) % vocab for i in tokenizer.encode(e, return_tensors=None)]
+        elif not _is_seq(e):
+            raise ValueError(f"an entry of {what} is a string or a sequence of token ids, got {e!r}")
+        else:
+            ids = [_check_token_id(t, vocab, "bad_words") for t in e]
+        if not 1 <= len(ids) <= MAX_BAD_WORD_LEN:
+            raise ValueError(f"an entry of {what} must come to 1..{MAX_BAD_WORD_LEN} token ids, {e!r} gives {len(ids)}")
+        out.append(tuple(ids))
+    return out
+
+
+def check_bad_words(common, per_prompt, n: int, vocab: int, tokenizer) -> List[List[Tuple[int, ...]]]:
+    """generate's `bad_words` (one list for every prompt, or None) and `bad_words_per_prompt` (n lists, or None) -> every row's
+    words as tuples of ids: the common list followed by the row's own, duplicates dropped (the first occurrence stays), at
+    most MAX_BAD_WORDS afterwards."""
+    shared = _check_bad_word_list(common, vocab, tokenizer, "bad_words")
+    own = [[] for _ in range(n)]
+    if per_prompt is not None:
+        if not _is_seq(per_prompt) or len(per_prompt) != n:
+            raise ValueError(f"bad_words_per_prompt must hold one list per prompt ({n})")
+        own = [_check_bad_word_list(e, vocab, tokenizer, "bad_words_per_prompt") for e in per_prompt]
+    rows = []
+    for b, o in enumerate(own):
+        row = list(dict.fromkeys(shared + o))
+        if len(row) > MAX_BAD_WORDS:
+            raise ValueError(f"prompt {b}: {len(row)} distinct bad_words, at most {MAX_BAD_WORDS}")
+        rows.append(row)
+    return rows
 
 
 def check_min_tokens(value, n: int) -> List[int]:

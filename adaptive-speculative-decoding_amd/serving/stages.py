@@ -132,9 +132,9 @@ dict or list, min_tokens 0, biases of 0) makes exactly the ops calls it made bef
 non-integer or out-of-vocabulary id, a bias that is no number, NaN or outside [-100, 100], a negative or non-integer
 min_tokens, a sequence of the wrong length, more than 1024 entries in one row after merging, a row whose banned ids (for ever
 or at its first token) would leave no token.  NOT BUILT: `min_tokens` > 0 on a row whose stop list holds a MULTI-token
-sequence raises ValueError (the match would have to be suppressed in the commit kernels, which stay as they are); multi-token
-`bad_words`; and serving/hierarchy.py's loop.  (Allow-lists are a dense mask, not a sparse edit: the next section; the stateful
-penalties keep per-token state: PENALTIES below.)
+sequence raises ValueError (the match would have to be suppressed in the commit kernels, which stay as they are); and
+serving/hierarchy.py's loop.  (Allow-lists are a dense mask, not a sparse edit: the next section; the stateful penalties keep
+per-token state: PENALTIES below; multi-token `bad_words` depend on the row's history: BAD WORDS below.)
 
 ALLOW-LISTS.  `generate(allowed_token_ids=)` (or StageConfig.allowed_token_ids; None takes the configuration's value) is
 vLLM's `SamplingParams.allowed_token_ids`: a sequence of token ids for every prompt, or one sequence (or None: no list) per
@@ -188,6 +188,39 @@ bits (19 KB at V = 152064) and works per distinct seen token, not per vocabulary
 BUILT: vLLM's `repetition_penalty` over the OUTPUT only (here, as in vLLM, the prompt counts as seen), removing finished rows
 from the state, and serving/hierarchy.py's loop.
 
+BAD WORDS.  `generate(bad_words=, bad_words_per_prompt=)` is vLLM's `SamplingParams.bad_words`, on token ids.  `bad_words` (or
+StageConfig.bad_words; None takes the configuration's value) is one list for every prompt, `bad_words_per_prompt` holds
+len(prompts) lists; an entry is a str -- encoded by the stage's tokenizer and folded into the vocabulary exactly as a stop
+string is -- or a sequence of 1..8 integer ids in [0, V).  A row's list is the common list followed by its own, duplicates
+dropped (not refused), at most MAX_BAD_WORDS = 256 words afterwards.  `banned_token_ids` is the one-token case, fixed for the
+whole call; for a word w_0 .. w_{m-1} WHICH logit is banned depends on what the row has just produced.  Take a logits position
+of row b whose history is H: the row's committed GENERATED tokens, tokens[b][P : seq_len[b]] with seq_len as it stands before
+the step's commit, and behind them the step's proposals that the position sees.  The prompt and the left-padding are not history
+(vLLM also matches over the output only).  Element w_{m-1} becomes -inf when len(H) >= m - 1 and the last m - 1 tokens of H
+equal w_0 .. w_{m-2}; a word of one token always bans its token; nothing else is written.  So no row's generated tokens hold
+one of its words as a contiguous run.  The words are uploaded once per call (ops.pack_bad_words: two tables in the layout of the
+stop sequences; equal rows share one list) and every loop calls ops.bad_words_rows (asd_bad_words_rows, in place) once per
+logits tensor at the three sites of the edit: stage 0's [B, V] logits (no proposals); every proposal's draft logits (proposal k
+sees the proposals 0 .. k - 1 of the step: K1 = 1, n_prev = k); the target's [B, K+1, V] output before anything is sliced from
+or scored on it (n_prev = 0, row j sees the proposals 0 .. j - 1 -- the history the draft's row j had).  The [B, draft_len]
+buffer of the step's proposals is ONE buffer of the call, which the penalties read too when both are on.  The order is mask ->
+bad words -> edit -> penalties -> temperature, vLLM V1's; the four operations commute on a -inf (a banned element stays -inf
+under a bias and under a penalty), and the order is fixed only so that the call pattern is.  Draft and target receive the SAME
+ban from the SAME history at every position, so -- the argument of LOGIT EDITS and PENALTIES, word for word -- the draft ->
+verify -> residual chain stays lossless against the target distribution with the bad words removed.  A rejected proposal never
+reaches `tokens`: nothing is rolled back, and the operation keeps no state -- nothing follows the commit.  Consequences: the
+returned log-probs and top-N tables are those of the distribution with the banned tokens removed; greedy decoding takes the
+arg-max of what is left; the rows route, seeds, the stop and finish routes, `logprobs = N`, edits, masks and penalties are
+untouched and compose with it.  A call whose lists are all empty makes exactly the ops calls it made before.  THE ROW KEEPS A
+TOKEN, conservatively, because the match is decided on the device: a row's allow-list minus its banned ids (permanent bans and
+the stop ids under min_tokens) minus the LAST ids of all its words must be non-empty; without an allow-list the union of those
+ids must be smaller than V.  ValueError before any launch and before the prompts are encoded: a bool, float or out-of-vocabulary
+id, an empty word, a word of more than 8 ids, more than 256 distinct words in a row, the wrong number of per-prompt lists, a
+str where a list is wanted, a row that would keep no token.  COST: one workgroup per logits row, one lane per word, at most
+seven history loads and one store per lane (profiles/bad_words_step.json).  NOT BUILT: `no_repeat_ngram_size` (its bans can
+empty a row dynamically, which the samplers forbid and no host check can exclude); vLLM's second variant of every word with a
+leading space (SimpleTokenizer has no such variant); and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -205,9 +238,9 @@ import torch
 from ..distributed import HipOps
 from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
-from .stage_args import (MAX_LOGIT_EDITS, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS, _check_logprobs, _check_min_p,  # noqa: F401
-                         _check_stop_ids, _check_stop_sequences, _is_seq, check_allowed_token_ids, check_banned_token_ids,
-                         check_frequency_penalty, check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt,
+from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS,  # noqa: F401
+                         _check_logprobs, _check_min_p, _check_stop_ids, _check_stop_sequences, _is_seq,
+                         check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt,
                          check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -252,6 +285,7 @@ class StageConfig:
     repetition_penalty: float = 1.0          # in (0, 2]; 1: off (module docstring, PENALTIES)
     presence_penalty: float = 0.0            # in [-2, 2]; 0: off
     frequency_penalty: float = 0.0           # in [-2, 2]; 0: off
+    bad_words: Sequence = ()                 # words (strings / sequences of 1..8 token ids) no row may produce (module docstring, BAD WORDS)
 
 
 _REASONS = {1: "stop", 2: "length"}
@@ -272,6 +306,7 @@ class _Plan(NamedTuple):
     finish_route: bool                       # asd_commit_step_finish: only for what the stop-id route cannot do
     edit_rows: list                          # every row's merged (id, bias, until) entries
     mask_rows: list                          # every row's allow-list: a sorted tuple of ids, or None
+    bad_rows: list                           # every row's bad words: distinct tuples of 1..8 ids
     penalties: Optional[Tuple[list, list, list]]    # every row's repetition, presence and frequency penalty; None: all neutral
     seeds: Optional[List[int]]
     n_top: int
@@ -303,25 +338,39 @@ class _MaskState:
         return self.ops.logit_mask_rows(logits, self.packed)
 
 
+class _BadWordState:
+    """What a generate call with bad words keeps: the rows' word tables on the device (uploaded once; equal lists share one),
+    the prompt length, the size of the token buffer and, at a verifying stage, the call's [B, draft_len] buffer of the step's
+    proposals.  `apply` is the loops' one call per logits tensor, behind the mask's and in front of the edit's; nothing follows
+    the commit: the operation reads `tokens` and keeps no state (module docstring, BAD WORDS)."""
+
+    def __init__(self, ops, rows, P: int, cap: int, step_tok: Optional[torch.Tensor], device):
+        self.ops, self.start, self.cap, self.step_tok = ops, int(P), int(cap), step_tok
+        self.packed = ops.pack_bad_words(rows, device)
+
+    def apply(self, logits: torch.Tensor, tokens: torch.Tensor, seq_len: torch.Tensor, n_prev: int = 0) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], banned in place; seq_len: the step's lengths before its commit; position j sees the
+        step's first n_prev + j proposals behind the row's committed tokens."""
+        if self.step_tok is None:
+            return self.ops.bad_words_rows(logits, self.packed, tokens, seq_len, self.start, self.cap)
+        return self.ops.bad_words_rows(logits, self.packed, tokens, seq_len, self.start, self.cap, self.step_tok, n_prev)
+
+
 class _PenaltyState:
     """What a generate call with a non-neutral penalty keeps: the rows' seen bits, counts and parameters on the device (the
-    prompt's bits uploaded once) and, at a verifying stage, the [B, draft_len] buffer of the step's proposals.  `apply` is the
-    loops' one call per logits tensor, behind the edit's; `propose` notes proposal k; `commit` follows the step's commit
-    (module docstring, PENALTIES)."""
+    prompt's bits uploaded once) and, at a verifying stage, the call's [B, draft_len] buffer of the step's proposals (shared
+    with _BadWordState; the loop fills column k after proposal k).  `apply` is the loops' one call per logits tensor, behind
+    the edit's; `commit` follows the step's commit (module docstring, PENALTIES)."""
 
-    def __init__(self, ops, penalties, prompt_ids, V: int, draft_len: int, device):
-        self.ops = ops
+    def __init__(self, ops, penalties, prompt_ids, V: int, step_tok: Optional[torch.Tensor], device):
+        self.ops, self.step_tok = ops, step_tok
         self.packed = ops.pack_penalties(*penalties, prompt_ids, int(V), device)
-        self.step_tok = torch.zeros((len(prompt_ids), draft_len), dtype=torch.int32, device=device) if draft_len else None
 
     def apply(self, logits: torch.Tensor, n_prev: int = 0) -> torch.Tensor:
         """logits [B, V] or [B, K+1, V], penalised in place; position j sees the step's first n_prev + j proposals."""
         if self.step_tok is None:
             return self.ops.penalty_rows(logits, self.packed)
         return self.ops.penalty_rows(logits, self.packed, self.step_tok, n_prev)
-
-    def propose(self, k: int, tok: torch.Tensor) -> None:
-        self.step_tok[:, k] = tok
 
     def commit(self, tokens: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor, cap: int) -> None:
         """Behind the step's commit, which left seq_len and n_commit (0 for a finished row: its state stays)."""
@@ -606,8 +655,10 @@ class _SampledRows(_Sampled):
 class _CallState:
     """The device side of one generate call, built in this one place from the plan and the encoded prompts and handed to the
     loop: how rows end (`end`), the allow-list (`mask`, None without a list), the logit edit (`edit`, None without an entry), the
-    penalties (`pen`, None when every row is neutral), the sampler and the top-N tables (`top`, None when off).  Uploads happen
-    here, once; a part that is off costs no launch.  `prompt_ids`: every row's prompt ids without the padding."""
+    bad words (`bad`, None when no row has one), the penalties (`pen`, None when every row is neutral), the sampler and the
+    top-N tables (`top`, None when off).  `step_tok`: the [B, draft_len] buffer of the step's proposals, ONE per call, which
+    `bad` and `pen` both read at a verifying stage (None at stage 0, and when both are off).  Uploads happen here, once; a part
+    that is off costs no launch.  `prompt_ids`: every row's prompt ids without the padding."""
 
     def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor, prompt_ids: List[List[int]]):
         (B, P), dev, ops = ids.shape, ids.device, stage.ops
@@ -615,8 +666,11 @@ class _CallState:
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
         self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
-        self.pen = _PenaltyState(ops, plan.penalties, prompt_ids, stage.shape.vocab,
-                                 0 if stage.draft is None else stage.config.draft_len, dev) if plan.penalties else None
+        history = any(plan.bad_rows) or bool(plan.penalties)
+        self.step_tok = torch.zeros((B, stage.config.draft_len), dtype=torch.int32, device=dev) \
+            if history and stage.draft is not None else None
+        self.bad = _BadWordState(ops, plan.bad_rows, P, P + plan.max_tokens, self.step_tok, dev) if any(plan.bad_rows) else None
+        self.pen = _PenaltyState(ops, plan.penalties, prompt_ids, stage.shape.vocab, self.step_tok, dev) if plan.penalties else None
         # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
         self.top = _TopState(ops, plan.n_top, plan.inv_t, B, P + plan.max_tokens, dev,
@@ -692,7 +746,8 @@ class Stage:
                  seed=None, stop_sequences=None,
                  stop_sequences_per_prompt=None, top_k=None, logit_bias=None, banned_token_ids=None,
                  min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
-                 frequency_penalty=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 frequency_penalty=None, bad_words=None,
+                 bad_words_per_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -742,12 +797,21 @@ class Stage:
         repetition penalty; a token that occurs c > 0 times among the generated tokens loses frequency_penalty * c +
         presence_penalty.  The history at a position includes the step's own proposals in front of it, draft and target logits
         receive the same penalty, and log-probs and top-N tables are those of the penalised distribution, behind the mask and
-        the edits above and ahead of the temperature (module docstring, PENALTIES)."""
+        the edits above and ahead of the temperature (module docstring, PENALTIES).
+        `bad_words` (vLLM's, on token ids): None = StageConfig.bad_words; strings (encoded like a stop string) or sequences of
+        1..8 token ids that NO prompt's row may produce; `bad_words_per_prompt`: len(prompts) such lists (possibly empty), each
+        for its own row, behind the common list.  A word of one token is banned for ever; the last token of a longer word is
+        banned at every position whose history -- the row's generated tokens, the prompt excluded, and the step's own proposals
+        in front of the position -- ends in the word's other tokens, so no row's generated tokens hold a word as a contiguous
+        run.  Draft and target logits receive the same ban, behind the mask and ahead of the edits and the penalties, and
+        log-probs and top-N tables are those of the distribution with the banned tokens removed.  Duplicates are dropped; a
+        row keeps at most 256 words; a row whose allow-list (or vocabulary) the bans and the words' last ids would empty
+        raises ValueError (module docstring, BAD WORDS)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
                           stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
-                          repetition_penalty, presence_penalty, frequency_penalty)
+                          repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -771,7 +835,7 @@ class Stage:
 
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
-              repetition_penalty, presence_penalty, frequency_penalty) -> _Plan:
+              repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -809,7 +873,8 @@ class Stage:
                                       check_banned_token_ids(given(banned_token_ids, cfg.banned_token_ids), n, V),
                                       check_min_tokens(given(min_tokens, cfg.min_tokens), n), row_seqs, V)
         mask_rows = check_allowed_token_ids(given(allowed_token_ids, cfg.allowed_token_ids), n, V)
-        check_rows_keep_a_token(mask_rows, edit_rows)
+        bad_rows = check_bad_words(given(bad_words, cfg.bad_words), bad_words_per_prompt, n, V, self.tokenizer)
+        check_rows_keep_a_token(mask_rows, edit_rows, bad_rows, V)
         penalties = (check_repetition_penalty(given(repetition_penalty, cfg.repetition_penalty), n),
                      check_presence_penalty(given(presence_penalty, cfg.presence_penalty), n),
                      check_frequency_penalty(given(frequency_penalty, cfg.frequency_penalty), n))
@@ -832,7 +897,7 @@ class Stage:
         return _Plan(prompts=prompts, limits=tuple(limits), max_tokens=int(limit), greedy=greedy,
                      inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
-                     edit_rows=edit_rows, mask_rows=mask_rows, penalties=penalties, seeds=seeds, n_top=n_top)
+                     edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, penalties=penalties, seeds=seeds, n_top=n_top)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -851,7 +916,7 @@ class Stage:
         B, P = ids.shape
         dev = ids.device
         cap = P + max_tokens
-        end, mask, edit, pen, top, sampler = st.end, st.mask, st.edit, st.pen, st.top, st.sampler
+        end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -862,6 +927,8 @@ class Stage:
                 logits = logits.contiguous()
             if mask is not None:
                 mask.apply(logits)                                       # the allow-list first, then the sparse edit (they commute)
+            if bad is not None:
+                bad.apply(logits, tokens, seq_len)                       # mask -> bad words -> edit -> penalties
             if edit is not None:
                 edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
             if pen is not None:
@@ -902,7 +969,8 @@ class Stage:
         dev = ids.device
         Kd = cfg.draft_len
         cap = P + max_tokens
-        end, mask, edit, pen, top, sampler = st.end, st.mask, st.edit, st.pen, st.top, st.sampler
+        end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
+        step_tok = st.step_tok                                          # the step's proposals, for `bad` and `pen`; None: both off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
             m.reset()
@@ -925,19 +993,23 @@ class Stage:
                     dl = dl.contiguous()
                 if mask is not None:
                     mask.apply(dl)
+                if bad is not None:
+                    bad.apply(dl, tokens, seq_len, k)                   # the history: the committed tokens, then proposals 0 .. k - 1
                 if edit is not None:
                     edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
                 if pen is not None:
                     pen.apply(dl, k)                                    # ... and sees the proposals 0 .. k - 1 of this step
                 toks.append(sampler.propose(dl, k))
-                if pen is not None:
-                    pen.propose(k, toks[-1])
+                if step_tok is not None:
+                    step_tok[:, k] = toks[-1]
                 if k + 1 < Kd:
                     dl = draft.forward_ragged(toks[-1].to(torch.int64)[:, None], L + k, window)[:, -1]
             tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
             t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
             if mask is not None:
                 mask.apply(t_out)                                       # the whole [B, K+1, V] output, before any slice
+            if bad is not None:
+                bad.apply(t_out, tokens, seq_len)                       # row j sees the proposals 0 .. j - 1, as the draft's did
             if edit is not None:
                 edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any slice
             if pen is not None:

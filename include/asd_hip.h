@@ -52,6 +52,8 @@ typedef enum asd_dtype {
 #define ASD_MAX_STOP_SEQ_LEN 8 /* tokens per stop sequence of asd_commit_step_finish */
 #define ASD_MAX_TOP_LOGPROBS 8 /* N of asd_top_logprobs: the most likely tokens listed per row */
 #define ASD_MAX_LOGIT_EDITS 1024 /* entries one row may own in asd_logit_edit_rows */
+#define ASD_MAX_BAD_WORDS 256  /* words one row may own in asd_bad_words_rows */
+#define ASD_MAX_BAD_WORD_LEN 8 /* tokens per word of asd_bad_words_rows */
 #define ASD_MAX_STAGES 16      /* L: tiers in the DP rule */
 #define ASD_MAX_SPLITS 64      /* vocab splits per row inside one launch */
 #define ASD_MAX_MLP_DIM 1024   /* predictor input / hidden width */
@@ -535,6 +537,57 @@ int asd_logit_edit_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int6
 int asd_logit_mask_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
                         const uint32_t* mask_bits /*[R, (V+31)/32]*/, int R, const int32_t* mask_row /*[B], or NULL: mask 0*/,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Bad words: MULTI-token bans ahead of the samplers -- vLLM's `bad_words`, on token ids.  asd_logit_edit_rows bans a token for
+ * a whole call; here WHICH logit is banned depends on what the row has just produced, and inside a speculative step on the
+ * step's own uncommitted proposals.  A row with banned elements is an ordinary input of every sampler ("no logit > -inf" must
+ * hold); applied alike, from the same history, to the draft's proposal rows and the target's K+1 rows, the draft -> verify ->
+ * residual chain stays lossless against the target distribution with the bad words removed.
+ * logits: asd_logit_edit_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only; K1 == 1 is a [B, V] matrix -- edited in
+ * place.
+ * Words: two DEVICE tables in asd_commit_step_finish's layout: word_tok int32 [n, ASD_MAX_BAD_WORD_LEN], word w's ids
+ * w_0 .. w_{m-1} at word_tok[w][0 .. m) with m = word_n[w] in 1..ASD_MAX_BAD_WORD_LEN (the padding behind them is never
+ * looked at).  row_first != NULL: int32 [B+1], sequence b owns the words [row_first[b], row_first[b+1]) and n_shared is n, the
+ * number of words in the tables (indices are clamped into [0, n_shared], so a damaged row_first never leaves them).
+ * row_first == NULL: every sequence owns the words [0, n_shared).  At most ASD_MAX_BAD_WORDS words of a sequence are honoured.
+ * History: position j of sequence b has
+ *     H = tokens[b][start .. seq_len[b])  ++  step_tok[b][0 .. n_prev + j)
+ * tokens: int32 rows ld_tokens >= max_len elements apart; seq_len[b], as it stands BEFORE the step's commit, is clamped into
+ * [start, max_len].  The prompt and its padding in front of `start` are NOT history (vLLM matches over the output only).
+ * step_tok: int32 [B] rows of n_tok proposals, ld_tok >= n_tok elements apart: the tokens the step has proposed and not
+ * committed (asd_penalty_rows' argument): a proposal row of draft slot k is K1 = 1 with n_prev = k, the target's K+1 rows are
+ * n_prev = 0, and row j of them sees the proposals 0 .. j-1.  step_tok == NULL: no position sees a proposal, and n_prev must be
+ * 0.  n_tok <= ASD_MAX_DRAFT_LEN.
+ * Semantics: element w_{m-1} of position (b, j) becomes -inf of the dtype (bits 0xFF80 bf16, 0xFC00 f16, -INFINITY f32, the
+ * ones asd_logit_edit_rows and asd_logit_mask_rows write) when BOTH
+ *     len(H) >= m - 1
+ *     the last m - 1 tokens of H equal w_0 .. w_{m-2}
+ * hold; a word with m == 1 always bans its token.  Nothing else is written: a matched element that is already -inf may be
+ * stored again, every other bit of the allocation stays as it was.  A rejected proposal never reaches `tokens`: nothing is
+ * rolled back, and the operation keeps no state.
+ * THE DATA CONTRACT: the launcher cannot check device data, so the kernel does: a word with word_n outside
+ * 1..ASD_MAX_BAD_WORD_LEN, or with a last id outside [0, V), is skipped, never written; prefix ids, committed tokens and
+ * proposals are compared as plain integers and index nothing.  Two words of one sequence MAY end in the same id (and the host
+ * need not remove that): both lanes then store the same -inf bits to one element with ordinary per-lane vector-memory stores,
+ * which gives the same result in either order -- no atomics.
+ * One launch, one workgroup of ASD_MAX_BAD_WORDS threads per (b, j), lane t handling word t of the sequence: at most
+ * ASD_MAX_BAD_WORD_LEN - 1 independent history loads and one store per lane.  No loop over the vocabulary, no LDS, no
+ * workspace, nothing waits on another workgroup.
+ * Status, in this order: negative B / K1 / V / n_shared / n_tok / n_prev / start / max_len: invalid argument; B, K1, V or
+ * n_shared == 0: ASD_OK, nothing launched; unknown dtype, row_first == NULL with n_shared > ASD_MAX_BAD_WORDS,
+ * n_tok > ASD_MAX_DRAFT_LEN, B*K1 > INT32_MAX: unsupported; NULL logits / word_tok / word_n / tokens / seq_len, ld_row < V,
+ * ld_seq < K1*ld_row, ld_tokens < max_len, start > max_len, step_tok == NULL with n_prev != 0, step_tok != NULL with
+ * n_prev + K1 - 1 > n_tok or ld_tok < n_tok: invalid argument; logits not aligned to the element size, or word_tok / word_n /
+ * row_first / tokens / seq_len / step_tok not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+int asd_bad_words_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                       const int32_t* word_tok /*[n, ASD_MAX_BAD_WORD_LEN]*/, const int32_t* word_n /*[n]*/,
+                       const int32_t* row_first /*[B+1], or NULL: words [0, n_shared) for every row*/, int n_shared,
+                       const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens, const int32_t* seq_len /*[B]*/,
+                       int start, int max_len,
+                       const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stateful penalties AHEAD of the samplers and behind the mask and the edit -- vLLM's `apply_penalties`: repetition_penalty,

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows and asd_penalty_commit in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit and asd_bad_words_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -350,6 +350,54 @@ int main() {
         EXPECT(PCOMMIT(i32, 32, i32, i32, B, V, 32, reinterpret_cast<uint32_t*>(rows + 2), i32), ASD_ERR_ALIGNMENT);
         EXPECT(PCOMMIT(i32, 32, i32, i32, B, V, 32, seen, reinterpret_cast<int32_t*>(rows + 2)), ASD_ERR_ALIGNMENT);
 #undef PCOMMIT
+    }
+
+    // ---- asd_bad_words_rows: every rejection, and every "nothing to do", comes before the launch
+    {
+#define BADW(x_, dt_, lds_, ldr_, B_, K1_, V_, wt_, wn_, rf_, n_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_) \
+    asd_bad_words_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, wt_, wn_, rf_, n_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_, nullptr)
+        const int K1 = 5;
+        int32_t* off = reinterpret_cast<int32_t*>(rows + 2);
+        EXPECT(BADW(p, BF16, K1 * V, V, -1, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, -1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, -1, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, -1, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, -1, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // start
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, -1, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // max_len
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, -1, 0), ASD_ERR_INVALID_ARG);   // n_tok
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);   // n_prev
+        EXPECT(BADW(p, BF16, K1 * V, V, 0, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);   // ... before the empty batch
+        EXPECT(BADW(nullptr, 99, 0, 0, 0, K1, V, nullptr, nullptr, nullptr, 8, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // B == 0
+        EXPECT(BADW(nullptr, 99, 0, 0, B, 0, V, nullptr, nullptr, nullptr, 8, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);    // K1 == 0
+        EXPECT(BADW(nullptr, 99, 0, 0, B, K1, 0, nullptr, nullptr, nullptr, 8, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // V == 0
+        EXPECT(BADW(nullptr, 99, 0, 0, B, K1, V, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // no word
+        EXPECT(BADW(p, 99, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);     // dtype
+        EXPECT(BADW(p, -1, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, nullptr, ASD_MAX_BAD_WORDS + 1, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 65, ASD_MAX_DRAFT_LEN + 1, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(BADW(nullptr, 99, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);  // ... before the NULL checks
+        EXPECT(BADW(nullptr, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, nullptr, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // word_tok
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, nullptr, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // word_n
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, nullptr, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // tokens
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, nullptr, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // seq_len
+        EXPECT(BADW(p, BF16, K1 * V, V - 1, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // ld_row < V
+        EXPECT(BADW(p, BF16, K1 * V - 1, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // ld_seq < K1 ld_row
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 31, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);      // ld_tokens < max_len
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 33, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);     // start > max_len
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, nullptr, 0, 0, 1), ASD_ERR_INVALID_ARG);  // n_prev without step_tok
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 1), ASD_ERR_INVALID_ARG);      // position 4 would see 5 of 4
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 3, 4, 0), ASD_ERR_INVALID_ARG);      // ld_tok < n_tok
+        EXPECT(BADW(rows + 1, BF16, K1 * V, V - 1, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // ... before alignment
+        EXPECT(BADW(rows + 1, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);   // below the element size
+        EXPECT(BADW(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, nullptr, 0, 0, 0), ASD_ERR_ALIGNMENT);
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, off, i32, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // word_tok
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, off, i32, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // word_n
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, off, 8, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // row_first
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, off, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // tokens
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, off, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // seq_len
+        EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, off, 4, 4, 0), ASD_ERR_ALIGNMENT);        // step_tok
+#undef BADW
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
