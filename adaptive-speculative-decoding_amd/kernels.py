@@ -770,7 +770,9 @@ def _rows(t: torch.Tensor, name: str) -> Tuple[int, int]:
     """(data_ptr, row stride in elements) of a [rows, V] or [B, K, V] logits tensor with unit stride in V."""
     if not t.is_cuda or t.dtype not in _DTYPE_CODE or t.stride(-1) != 1:
         raise ValueError(f"{name} must be a CUDA f32/bf16/f16 tensor with unit stride along the vocabulary")
-    if t.dim() == 3 and t.stride(0) != t.shape[1] * t.stride(1):
+    # (one sequence: its stride is never used, and torch leaves a size-1 dimension's stride as it was -- a slice [:, :K] of a
+    # [1, K + 1, V] tensor is already "contiguous" and keeps stride(0) = (K + 1) V)
+    if t.dim() == 3 and t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1):
         raise ValueError(f"{name}: rows must be evenly spaced over (b, k)")
     return t.data_ptr(), t.stride(-2)
 

@@ -159,3 +159,32 @@ def test_lp_is_required():
     rc = lib.asd_residual_sample_lp(t.data_ptr(), 1024, t.data_ptr(), 1024, None, 1024, 1, z.data_ptr(), z.data_ptr(), 2, 2, 1024,
                                     1.0, 0, 1.0, None, None, z.data_ptr(), None, ws.data_ptr(), ws.numel(), None)
     assert rc == -1
+
+
+def test_one_sequence_sliced_from_a_longer_output():
+    """B = 1, as a verifying stage hands it over: score = t_out[:, :K].contiguous() of a [1, K + 1, V] output is the view itself
+    (torch ignores the stride of a size-1 dimension), so stride(0) is (K + 1) V, not K V.  The launcher never uses that stride;
+    it once refused such a tensor.  Same token and log-prob bits as the compact copy; two unevenly spaced sequences still raise."""
+    import torch
+    from asd_amd import kernels as Kn
+    K, V = 4, 1024
+    g = torch.Generator(device="cuda").manual_seed(3)
+    out = torch.randn((1, K + 1, V), generator=g, device="cuda") * 3
+    score, bonus = out[:, :K].contiguous(), out[:, K].contiguous()
+    assert score.stride(0) == (K + 1) * V
+    compact = torch.empty((1, K, V), device="cuda").copy_(score)
+    d = compact + torch.randn((1, K, V), generator=g, device="cuda")
+    samp = Kn.ResidualSampler(1, V, score.dtype)
+    r = torch.full((1,), 0.37, device="cuda")
+    for n in (0, 2, K):
+        na = torch.full((1,), n, dtype=torch.int32, device="cuda")
+        tok_a, lp_a = (x.clone() for x in samp.lp(score, d, na, r, bonus, INV_T))
+        tok_b, lp_b = samp.lp(compact, d, na, r, bonus, INV_T)
+        assert int(tok_a) == int(tok_b) >= 0 and lp_a.cpu().numpy().tobytes() == lp_b.cpu().numpy().tobytes()
+        ref = ref_logprob((compact[0, n] if n < K else bonus[0]).cpu().numpy(), int(tok_a), INV_T)
+        assert abs(float(lp_a) - ref) <= LP_ATOL
+    two = torch.randn((2, K + 1, V), generator=g, device="cuda")
+    with pytest.raises(ValueError, match="evenly spaced"):
+        Kn.ResidualSampler(2, V, two.dtype).lp(two[:, :K], two[:, :K], torch.zeros(2, dtype=torch.int32, device="cuda"),
+                                               torch.zeros(2, device="cuda"), None, INV_T)
+    assert samp.status() == 0
