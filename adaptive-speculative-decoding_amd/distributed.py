@@ -454,6 +454,31 @@ class HipOps:
         (n_commit 0) keeps its state, and a rejected proposal was never in it."""
         self.K.penalty_commit(tokens, seq_len, n_commit, pen, max_len)
 
+    def pack_fsm(self, fsm, ld_state: int, device):
+        """The compiled automata of one generate call (serving/guided.py::compile_rows) -> the device tables and state columns
+        of fsm_mask_rows / fsm_advance / fsm_commit (kernels.pack_fsm: state_bits is built on the host from the CSR tables; one
+        upload per generate call).  ld_state: draft_len + 1 at a verifying stage, 1 at stage 0."""
+        return self.K.pack_fsm(fsm, ld_state, device)
+
+    @traced("fsm_mask_rows")
+    def fsm_mask_rows(self, logits, fsm, first: int = 0):
+        """The automaton's mask ahead of the samplers (asd_fsm_mask_rows): logits [B, V] or [B, K1, V] (any strides with a unit
+        last stride) -> the same tensor, position j of row b at -inf outside what state pos_state[b, first + j] allows.  The
+        write stream of logit_mask_rows with a mask index per (row, position); a stage loop makes the call once per logits
+        tensor, directly behind logit_mask_rows, and only when some row of the call is guided."""
+        return self.K.fsm_mask_rows(logits, fsm, first)
+
+    @traced("fsm_advance")
+    def fsm_advance(self, fsm, step_tok, k: int):
+        """Behind proposal k of a step (asd_fsm_advance): pos_state[b, k + 1] = delta(pos_state[b, k], step_tok[b, k])."""
+        self.K.fsm_advance(fsm, step_tok, k)
+
+    @traced("fsm_commit")
+    def fsm_commit(self, fsm, tokens, seq_len, n_commit, max_len):
+        """Behind the step's commit (asd_fsm_commit): the state behind the committed tokens moves to column 0; a finished row
+        (n_commit 0) keeps its state."""
+        self.K.fsm_commit(fsm, tokens, seq_len, n_commit, max_len)
+
     def pack_bad_words(self, rows, device):
         """Every row's bad words (1..8 token ids each, at most 256 per row) -> the device tables of bad_words_rows
         (kernels.pack_bad_words: one upload per generate call; equal rows share one list)."""

@@ -1456,3 +1456,134 @@ def bad_words_rows(logits: torch.Tensor, words: BadWords, tokens: torch.Tensor, 
                                    int(n_prev), _stream())
     B.check("asd_bad_words_rows", rc)
     return logits
+
+
+# ------------------------------------------------------------------------------- guided decoding (token automata)
+@dataclass
+class TokenFsm:
+    """The tables of asd_fsm_mask_rows / asd_fsm_advance / asd_fsm_commit on the device (pack_fsm): state_first i32 [S + 1],
+    edge_tok / edge_next i32 [max(E, 1)], state_other i32 [S], state_bits i32 [S, W] with W = (V + 31) // 32 (the allow-list's
+    bit layout), and the state columns pos_state i32 [B, ld_state]: column 0 the state behind a row's committed tokens (-1:
+    the row has no automaton), column i the state behind the proposals 0 .. i - 1 of the running step."""
+    state_first: torch.Tensor
+    edge_tok: torch.Tensor
+    edge_next: torch.Tensor
+    state_other: torch.Tensor
+    state_bits: torch.Tensor
+    pos_state: torch.Tensor
+    S: int
+    E: int
+    B: int                                   # rows the state was packed for
+    V: int
+    ld_state: int
+
+
+def check_fsm_tables(state_first, edge_tok, edge_next, state_other, starts, V: int):
+    """The host side of pack_fsm: the CSR tables as include/asd_hip.h states them, checked, -> (the four tables as int32
+    arrays, state_bits: numpy uint32 [S, W] built FROM them -- bit v set = token v has a transition that is not -1 -- and the
+    rows' start states)."""
+    V = int(V)
+    if V < 1:
+        raise ValueError("V must be >= 1")
+    first, tok, nxt, other = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (state_first, edge_tok, edge_next, state_other))
+    S, E = other.size, tok.size
+    if first.size != S + 1 or nxt.size != E or (S and (first[0] != 0 or first[-1] != E)) or (np.diff(first) < 0).any():
+        raise ValueError("state_first must be S + 1 ascending CSR offsets from 0 to E, edge_tok and edge_next [E], state_other [S]")
+    if E and (tok.min() < 0 or tok.max() >= V):
+        raise ValueError(f"edge token ids must lie in [0, {V})")
+    if (E and (nxt.min() < -1 or nxt.max() >= S)) or (S and (other.min() < -1 or other.max() >= S)):
+        raise ValueError("next states must lie in [-1, S)")
+    starts = [int(s) for s in starts]
+    if any(not -1 <= s < S for s in starts):
+        raise ValueError("a row's start state must lie in [0, S), or be -1 for a row without an automaton")
+    W = (V + 31) // 32
+    bits = np.zeros((S, W), dtype=np.uint32)
+    keep = np.zeros(W * 32, dtype=bool)                      # one state's allowed set, padded to whole words (the padding stays clear)
+    for s in range(S):
+        ids, to = tok[first[s]:first[s + 1]], nxt[first[s]:first[s + 1]]
+        if ids.size > 1 and (np.diff(ids) <= 0).any():
+            raise ValueError(f"the edge token ids of state {s} must be ascending and distinct")
+        keep[:V] = other[s] >= 0
+        keep[ids] = to >= 0
+        bits[s] = np.packbits(keep, bitorder="little").view("<u4")       # bit v & 31 of word v >> 5: one vectorised step
+    return first, tok, nxt, other, bits, starts
+
+
+def pack_fsm(fsm, ld_state: int, device) -> TokenFsm:
+    """The device side of one call's automata: `fsm` carries state_first / edge_tok / edge_next / state_other (numpy), the rows'
+    `starts` and `V` (serving/guided.py::compile_rows).  state_bits is built here from the other tables; everything is uploaded
+    once, and pos_state [B, ld_state] starts with every column at the row's start state (-1 for a row without an automaton)."""
+    first, tok, nxt, other, bits, starts = check_fsm_tables(fsm.state_first, fsm.edge_tok, fsm.edge_next, fsm.state_other, fsm.starts, fsm.V)
+    ld_state = int(ld_state)
+    if ld_state < 1:
+        raise ValueError("ld_state must be >= 1")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)             # noqa: E731
+    pad = lambda a: a if a.size else np.zeros(1, np.int32)                          # noqa: E731  (E == 0: never read)
+    pos = np.repeat(np.asarray(starts, dtype=np.int32).reshape(-1, 1), ld_state, axis=1)
+    return TokenFsm(up(first), up(pad(tok)), up(pad(nxt)), up(other), up(bits.view(np.int32)), up(pos), int(other.size), int(tok.size),
+                    len(starts), int(fsm.V), ld_state)
+
+
+def _fsm_tables(f: TokenFsm):
+    return (_dev(f.state_first, "state_first", torch.int32), _dev(f.edge_tok, "edge_tok", torch.int32),
+            _dev(f.edge_next, "edge_next", torch.int32), _dev(f.state_other, "state_other", torch.int32), f.S, f.E, f.V)
+
+
+def _fsm_state(f: TokenFsm) -> int:
+    if tuple(f.pos_state.shape) != (f.B, f.ld_state) or not f.pos_state.is_contiguous():
+        raise ValueError("pos_state must be a contiguous int32 [B, ld_state] tensor")
+    return _dev(f.pos_state, "pos_state", torch.int32)
+
+
+def fsm_mask_rows(logits: torch.Tensor, fsm: TokenFsm, first: int = 0) -> torch.Tensor:
+    """Mask `logits` in place (asd_fsm_mask_rows) and return it: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  Position j of row b is masked with the bits of state pos_state[b, first + j]; a row
+    without an automaton (-1) and everything else in the allocation keep their bits."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if fsm.B != Bv or fsm.V != V:
+        raise ValueError(f"the automata were packed for {fsm.B} rows of {fsm.V} tokens; logits have {Bv} rows of {V}")
+    if tuple(fsm.state_bits.shape) != (fsm.S, (V + 31) // 32):
+        raise ValueError("state_bits must be int32 [S, (V + 31) // 32]")
+    if not 0 <= int(first) or int(first) + K1 > fsm.ld_state:
+        raise ValueError(f"positions {int(first)} .. {int(first) + K1 - 1} need that many state columns; pos_state holds {fsm.ld_state}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_fsm_mask_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
+                                  _dev(fsm.state_bits, "state_bits", torch.int32), fsm.S, _fsm_state(fsm), fsm.ld_state, int(first),
+                                  _stream())
+    B.check("asd_fsm_mask_rows", rc)
+    return logits
+
+
+def fsm_advance(fsm: TokenFsm, step_tok: torch.Tensor, k: int) -> None:
+    """pos_state[b, k + 1] = delta(pos_state[b, k], step_tok[b, k]) (asd_fsm_advance): behind proposal k of a step.  step_tok
+    i32 [B, n_tok] with unit stride along the proposals."""
+    if not step_tok.is_cuda or step_tok.dtype != torch.int32 or step_tok.dim() != 2 or step_tok.shape[0] != fsm.B or \
+            (step_tok.shape[1] > 1 and step_tok.stride(1) != 1):
+        raise ValueError("step_tok must be a CUDA int32 [B, n_tok] tensor with unit stride along the proposals")
+    n_tok = step_tok.shape[1]
+    ld_tok = step_tok.stride(0) if fsm.B > 1 else n_tok
+    if not 0 <= int(k) < n_tok or int(k) + 1 >= fsm.ld_state or ld_tok < n_tok:
+        raise ValueError(f"proposal {int(k)} needs step_tok column {int(k)} of {n_tok} and state column {int(k) + 1} of {fsm.ld_state}")
+    rc = _lib().asd_fsm_advance(*_fsm_tables(fsm), _fsm_state(fsm), fsm.ld_state, fsm.B, int(k), step_tok.data_ptr(), ld_tok, n_tok,
+                                _stream())
+    B.check("asd_fsm_advance", rc)
+
+
+def fsm_commit(fsm: TokenFsm, tokens: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor, max_len: Optional[int] = None) -> None:
+    """Behind the step's commit (asd_fsm_commit): for a row with c = n_commit[b] > 0, pos_state[b, 0] =
+    delta(pos_state[b, c - 1], tokens[b, seq_len[b] - 1]); a finished row (c == 0) keeps its state.  tokens i32 [B, >= max_len]
+    contiguous; seq_len / n_commit i32 [B] as the commit left them."""
+    if tokens.dim() != 2:
+        raise ValueError("tokens must be int32 [B, max_len]")
+    cap = tokens.shape[1] if max_len is None else int(max_len)
+    if fsm.B != tokens.shape[0] or not 1 <= cap <= tokens.shape[1] or tuple(seq_len.shape) != (fsm.B,) or tuple(n_commit.shape) != (fsm.B,):
+        raise ValueError(f"the automata were packed for {fsm.B} rows; tokens must be [B, >= max_len >= 1], seq_len and n_commit [B]")
+    rc = _lib().asd_fsm_commit(*_fsm_tables(fsm), _fsm_state(fsm), fsm.ld_state, fsm.B, _dev(tokens, "tokens", torch.int32),
+                               tokens.shape[1], _dev(seq_len, "seq_len", torch.int32), _dev(n_commit, "n_commit", torch.int32), cap,
+                               _stream())
+    B.check("asd_fsm_commit", rc)

@@ -38,6 +38,9 @@ reaches `stage.generate` only when it was given.  The values are checked by the 
 number for the batch or one per request, kept by the request through every regrouping, handed on only when given.
 `bad_words=` (vLLM's; serving/stages.py, BAD WORDS) likewise: one list of words for the batch, which reaches the stages as
 `bad_words`, or one list (or None) per request, which a request keeps and the stages receive as `bad_words_per_prompt`.
+`guided_choice=` (serving/stages.py, GUIDED DECODING) likewise: one list of choices for the batch, which reaches the stages as
+`guided_choice`, or one list (or None: the request is free) per request, which a request keeps and the stages receive as
+`guided_choice_per_prompt`.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -159,6 +162,27 @@ def check_bad_words_arg(bad_words, n: int) -> Dict[str, Any]:
     return {"bad_words": [[] if v is None else list(v) for v in vals]}
 
 
+def check_guided_choice_arg(guided_choice, n: int) -> Dict[str, Any]:
+    """The `guided_choice` keyword of batch_process -> {} when it was not given, else {"guided_choice": value}: a `list` of n
+    entries where the batch carries one list per request (an entry that is None, empty or itself holds choices), else a tuple of
+    choices, the batch's one list.  A choice is a str or a sequence of token ids.  Only the shapes are looked at here;
+    stage.generate checks the values."""
+    if guided_choice is None:
+        return {}
+    if not _is_seq(guided_choice):
+        raise ValueError(f"guided_choice must be a list of choices or one list per request, got {guided_choice!r}")
+    vals = list(guided_choice)
+    per_request = [v is None or (_is_seq(v) and (len(v) == 0 or any(isinstance(x, str) or _is_seq(x) for x in v))) for v in vals]
+    if not any(per_request):
+        return {"guided_choice": tuple(vals)}
+    if not all(per_request):
+        raise ValueError("guided_choice mixes choices and per-request lists")
+    if len(vals) != n:
+        raise ValueError(f"{len(vals)} guided_choice lists for {n} requests")
+    return {"guided_choice": [None if v is None else list(v) for v in vals]}
+
+
+_PER_PROMPT_KEYWORD = {"bad_words": "bad_words_per_prompt", "guided_choice": "guided_choice_per_prompt"}
 DEFAULT_STAGE_NAMES = ("8b", "13b", "34b", "70b")          # pipeline.py:175
 
 
@@ -255,7 +279,7 @@ class _Active:
     top_p: Optional[float] = None
     top_k: Optional[int] = None
     min_p: Optional[float] = None
-    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens / allowed_token_ids / penalties / bad_words
+    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens / allowed_token_ids / penalties / bad_words / guided_choice
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -289,14 +313,15 @@ class AdaptiveSpeculativePipeline:
                         request_id: Optional[str] = None, seed: Optional[int] = None, top_p: Optional[float] = None,
                         top_k: Optional[int] = None, min_p: Optional[float] = None, logit_bias=None, banned_token_ids=None,
                         min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
-                        frequency_penalty=None, bad_words=None) -> RequestResult:
+                        frequency_penalty=None, bad_words=None, guided_choice=None) -> RequestResult:
         """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring).
         top_p / top_k / min_p: None = every stage's configuration, else the request's own value at every stage
         (stage.generate(top_p=, top_k=, min_p=)).  logit_bias (a dict) / banned_token_ids (token ids) / min_tokens (an int):
         None = every stage's configuration, else handed to every stage.generate call (module docstring, Logit edits);
         allowed_token_ids (token ids) likewise; repetition_penalty / presence_penalty / frequency_penalty (one number each:
         serving/stages.py, PENALTIES) likewise; bad_words (one list of words, a word a str or a sequence of token ids:
-        serving/stages.py, BAD WORDS) likewise."""
+        serving/stages.py, BAD WORDS) likewise; guided_choice (one list of choices, a choice a str or a sequence of token ids:
+        serving/stages.py, GUIDED DECODING) likewise."""
         if seed is not None and not isinstance(seed, (int, np.integer)):
             raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
         sampling = {k: check_per_prompt(v, 1, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
@@ -315,6 +340,10 @@ class AdaptiveSpeculativePipeline:
         if isinstance(words.get("bad_words"), list):
             raise ValueError("process_request takes one bad_words list of words")
         edits.update(words)
+        choices = check_guided_choice_arg(guided_choice, 1)
+        if isinstance(choices.get("guided_choice"), list):
+            raise ValueError("process_request takes one guided_choice list of choices")
+        edits.update(choices)
         return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1), sampling=sampling,
                                edits=edits)[0]
 
@@ -327,7 +356,7 @@ class AdaptiveSpeculativePipeline:
     def batch_process(self, prompts: List[str], max_tokens=512, temperature=0.7,
                       seeds=None, top_p=None, top_k=None, min_p=None, logit_bias=None, banned_token_ids=None,
                       min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
-                      frequency_penalty=None, bad_words=None) -> List[RequestResult]:
+                      frequency_penalty=None, bad_words=None, guided_choice=None) -> List[RequestResult]:
         """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
         raises ValueError); request i keeps seeds[i] through every regrouping (module docstring).  max_tokens: an int, or one
         int >= 1 per request, kept by the request in the same way.
@@ -340,7 +369,10 @@ class AdaptiveSpeculativePipeline:
         repetition_penalty, presence_penalty, frequency_penalty: None (not handed on), one number for the batch, or one per
         request, travelling like the edits (serving/stages.py, PENALTIES).
         bad_words: None (not handed on), one list of words for the batch (stage.generate(bad_words=)), or one list (or None:
-        no word) per request, kept by the request and handed on as bad_words_per_prompt (serving/stages.py, BAD WORDS)."""
+        no word) per request, kept by the request and handed on as bad_words_per_prompt (serving/stages.py, BAD WORDS).
+        guided_choice: None (not handed on), one list of choices for the batch (stage.generate(guided_choice=)), or one list (or
+        None: the request is free) per request, kept by the request and handed on as guided_choice_per_prompt (serving/stages.py,
+        GUIDED DECODING)."""
         prompts = list(prompts)
         n = len(prompts)
         seeds = check_seeds(seeds, n)
@@ -349,6 +381,7 @@ class AdaptiveSpeculativePipeline:
         edits = check_logit_edit_args(logit_bias, banned_token_ids, min_tokens, n, allowed_token_ids)
         edits.update(check_penalty_args(dict(zip(_PENALTY_KEYS, (repetition_penalty, presence_penalty, frequency_penalty))), n))
         edits.update(check_bad_words_arg(bad_words, n))
+        edits.update(check_guided_choice_arg(guided_choice, n))
         if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
             temperature = check_per_prompt(temperature, n, "temperature")
         if isinstance(temperature, list) and any(t == 0.0 for t in temperature):
@@ -548,8 +581,9 @@ class AdaptiveSpeculativePipeline:
                     if getattr(todo[0], name) is not None:
                         stop_kw[name] = [getattr(r, name) for r in todo]
                 for name in todo[0].edits:                              # (a batch carries a per-request edit for all requests or none)
-                    # (per-request bad words have a keyword of their own at the stage: `bad_words` is its common list)
-                    stop_kw["bad_words_per_prompt" if name == "bad_words" else name] = [r.edits[name] for r in todo]
+                    # (per-request bad words and choices have keywords of their own at the stage: `bad_words` is its common list,
+                    # `guided_choice` the one list of every row)
+                    stop_kw[_PER_PROMPT_KEYWORD.get(name, name)] = [r.edits[name] for r in todo]
                 temp = [r.temperature for r in todo] if isinstance(temperature, list) else temperature
                 texts, logprobs, stage_stats = stage.generate(prompts=[r.current_prompt for r in todo],
                                                               max_tokens=limit, temperature=temp,

@@ -7,6 +7,8 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from .guided import TokenFSM
+
 MAX_STOP_IDS = 8                             # ASD_MAX_STOP_IDS of include/asd_hip.h
 MAX_STOP_SEQS = 16                           # ASD_MAX_STOP_SEQS: entries of one row's list (stop ids included)
 MAX_STOP_SEQ_LEN = 8                         # ASD_MAX_STOP_SEQ_LEN
@@ -243,6 +245,41 @@ def check_bad_words(common, per_prompt, n: int, vocab: int, tokenizer) -> List[L
             raise ValueError(f"prompt {b}: {len(row)} distinct bad_words, at most {MAX_BAD_WORDS}")
         rows.append(row)
     return rows
+
+
+def check_guided(guided_fsm, guided_choice, guided_choice_per_prompt, n: int, vocab: int, tokenizer) -> List[Optional[TokenFSM]]:
+    """generate's `guided_fsm` (one TokenFSM for every prompt, or n entries, each a TokenFSM or None), `guided_choice` (one
+    list of choices for every prompt) and `guided_choice_per_prompt` (n lists; None or an empty list: the row is unguided)
+    -> every row's automaton, checked against the vocabulary, or None.  A row with both an automaton and choices raises."""
+    rows: List[Optional[TokenFSM]] = [None] * n
+    if guided_fsm is not None:
+        if isinstance(guided_fsm, TokenFSM):
+            rows = [guided_fsm.check_vocab(vocab)] * n
+        elif not _is_seq(guided_fsm) or len(guided_fsm) != n or any(f is not None and not isinstance(f, TokenFSM) for f in guided_fsm):
+            raise ValueError(f"guided_fsm must be a TokenFSM or one TokenFSM (or None) per prompt ({n}), got {guided_fsm!r}")
+        else:
+            rows = [None if f is None else f.check_vocab(vocab) for f in guided_fsm]
+
+    def choices(value, what):
+        if not _is_seq(value):
+            raise ValueError(f"{what} must be a list of strings or token-id sequences, got {value!r}")
+        return TokenFSM.from_choices(value, tokenizer, vocab)
+    own: List[Optional[TokenFSM]] = [None] * n
+    if guided_choice is not None:
+        own = [choices(guided_choice, "guided_choice")] * n
+    if guided_choice_per_prompt is not None:
+        if not _is_seq(guided_choice_per_prompt) or len(guided_choice_per_prompt) != n:
+            raise ValueError(f"guided_choice_per_prompt must hold one list per prompt ({n})")
+        for b, e in enumerate(guided_choice_per_prompt):
+            if e is None or (_is_seq(e) and len(e) == 0):
+                continue
+            if own[b] is not None:
+                raise ValueError(f"prompt {b}: guided_choice and guided_choice_per_prompt both name choices")
+            own[b] = choices(e, "an entry of guided_choice_per_prompt")
+    for b, (f, c) in enumerate(zip(rows, own)):
+        if f is not None and c is not None:
+            raise ValueError(f"prompt {b}: a row takes a guided_fsm or guided choices, not both")
+    return [f if f is not None else c for f, c in zip(rows, own)]
 
 
 def check_min_tokens(value, n: int) -> List[int]:

@@ -134,7 +134,7 @@ min_tokens, a sequence of the wrong length, more than 1024 entries in one row af
 or at its first token) would leave no token.  NOT BUILT: `min_tokens` > 0 on a row whose stop list holds a MULTI-token
 sequence raises ValueError (the match would have to be suppressed in the commit kernels, which stay as they are); and
 serving/hierarchy.py's loop.  (Allow-lists are a dense mask, not a sparse edit: the next section; the stateful penalties keep
-per-token state: PENALTIES below; multi-token `bad_words` depend on the row's history: BAD WORDS below.)
+per-token state: PENALTIES below; multi-token `bad_words` depend on the row's history: BAD WORDS below; automata: GUIDED DECODING.)
 
 ALLOW-LISTS.  `generate(allowed_token_ids=)` (or StageConfig.allowed_token_ids; None takes the configuration's value) is
 vLLM's `SamplingParams.allowed_token_ids`: a sequence of token ids for every prompt, or one sequence (or None: no list) per
@@ -153,9 +153,9 @@ proposed, accepted, drawn or listed; the returned log-probs and top-N tables are
 never end that row (the caller's choice, as in vLLM).  A call without a list (None everywhere) makes exactly the ops calls it
 made before.  ValueError before any launch: a bool, non-integer or out-of-vocabulary id, a mix of ids and lists, a sequence of
 the wrong length, an EMPTY list (it allows nothing, and the samplers forbid a row without a finite logit), and a row whose
-list minus its banned ids -- permanent bans and the stop ids under min_tokens alike -- is empty.  NOT BUILT: per-position masks
-(a grammar's mask differs at each of the K + 1 positions; the mask_row indirection leaves room), folding the mask into the
-samplers, and serving/hierarchy.py's loop.
+list minus its banned ids -- permanent bans and the stop ids under min_tokens alike -- is empty.  NOT BUILT: folding the mask into
+the samplers, and serving/hierarchy.py's loop.  (Per-position masks -- a grammar's mask differs at each of the K + 1 positions --
+are GUIDED DECODING below.)
 
 PENALTIES.  `generate(repetition_penalty=, presence_penalty=, frequency_penalty=)` (or the StageConfig fields of those names; None
 takes the configuration's value, which defaults to 1.0 / 0.0 / 0.0) are vLLM's `apply_penalties`, each one value for the call or
@@ -221,6 +221,61 @@ seven history loads and one store per lane (profiles/bad_words_step.json).  NOT 
 empty a row dynamically, which the samplers forbid and no host check can exclude); vLLM's second variant of every word with a
 leading space (SimpleTokenizer has no such variant); and serving/hierarchy.py's loop.
 
+GUIDED DECODING.  `generate(guided_fsm=, guided_choice=, guided_choice_per_prompt=)` (or StageConfig.guided_fsm / guided_choice; a
+keyword of None takes the configuration's value) is structured output: a row that must follow a grammar, or be one of a set of
+answers (vLLM's `guided_choice`).  The unit is serving/guided.py's `TokenFSM(n_states, start, edges, other=None, accepting=())`, a
+deterministic automaton over token ids: edges[s] = {token id: next state} (a next state of -1: the token is forbidden in s),
+other[s] = the next state of every token without an edge in s (-1, the default: forbidden), `accepting` = the states in which the
+row may end.  `TokenFSM.from_choices(choices)` is the trie of up to 256 choices, each a str (encoded by the stage's tokenizer and
+folded into the vocabulary exactly as a stop string is) or a sequence of 1..64 ids, duplicates dropped, a choice's end node
+accepting -- an inner node too when one choice is a prefix of another.  `guided_fsm` is one TokenFSM for every prompt or one (or
+None) per prompt, `guided_choice` one list of choices for every prompt, `guided_choice_per_prompt` len(prompts) lists (None or
+empty: the row is free).  In a speculative step the mask of position j depends on the proposals 0 .. j - 1, which exist only on
+the device, so a host-side grammar back end could drive this loop only with a read-back per proposal: the automaton LIVES ON THE
+DEVICE.  COMPILATION, per (automaton, row stop set): Z is the row's length-1 stop-list entries -- its stop ids and one-token stop
+sequences, which is what grammar back ends do with EOS.  One state END is appended, which allows exactly Z and loops; in an
+accepting state every z of Z without an explicit edge leads to END; in a non-accepting state every such z is forbidden, even
+under `other`.  Rows with the same automaton and the same Z share one compiled automaton; all of a call's are laid into one
+state space (at most MAX_FSM_STATES = 1024 states and 2^20 edges per call) and uploaded once (ops.pack_fsm): CSR edge tables
+(state_first, edge_tok ascending, edge_next), state_other, state_bits [S, ceil(V / 32)] in the allow-list's bit layout -- built by
+the host from the other tables -- and pos_state [B, ld_state], ld_state = draft_len + 1 at a verifying stage and 1 at stage 0:
+column 0 is the state behind the row's committed tokens (the start state at first; -1, never touched, for a free row), column i
+the state behind the proposals 0 .. i - 1 of the running step.  THREE OPS.  ops.fsm_mask_rows (asd_fsm_mask_rows, in place, the
+allow-list's write stream with a mask index per (row, position) -- one shared kernel body) directly behind the allow-list's call at
+each of its three sites: stage 0's [B, V] logits (first = 0); every proposal's draft logits (first = k); the target's [B, K+1, V]
+output before anything is sliced from or scored on it (first = 0: row j under column j).  ops.fsm_advance (asd_fsm_advance)
+behind every proposal k, once it is drawn and written to the call's proposal buffer -- the ONE [B, draft_len] buffer the bad
+words and the penalties read too, allocated when any of the three is on: column k + 1 = delta(column k, proposal k), for every k
+including the last, so that column K exists for the bonus row.  ops.fsm_commit (asd_fsm_commit) behind the step's commit, the
+top-N commit and penalty_commit: for a row that committed c > 0 tokens, column 0 = delta(column c - 1, the last committed token)
+-- ONE transition, because the first c - 1 committed tokens of a step are always its accepted proposals 0 .. c - 2 (stops and
+limits cut from the end), so column c - 1 already is the state behind them; a finished row (c = 0) keeps its state.  delta(s, t)
+is the edge's next state, else other[s]; where that is -1, or t lies outside the vocabulary -- which cannot happen, every
+proposal having been drawn from masked logits -- the state STAYS, so a row never loses its non-empty mask.  The order is mask ->
+fsm -> bad words -> edit -> penalties -> temperature; all five commute on a -inf.  Nothing is read back inside a step.  Draft and
+target receive the SAME mask from the SAME history at every position, so -- the argument of LOGIT EDITS, word for word -- the
+draft -> verify -> residual chain stays lossless against the grammar-restricted target distribution.  Consequences: the returned
+log-probs and top-N tables are those of the RESTRICTED distribution, unfillable top-N slots holding -1 / -inf as with allow-lists;
+a guided-choice row ends by "stop" and its generated tokens are exactly one choice followed by one stop id; a row cut by
+`max_tokens` ends by "length" holding a prefix of some choice; greedy decoding takes the arg-max of what the state allows; the
+rows route, seeds, the stop and finish routes, `logprobs = N`, edits, masks, penalties and bad words are untouched and compose
+with it.  A call without a guided row makes exactly the ops calls it made before.  THE ROW KEEPS A TOKEN, conservatively, because
+the state lives on the device: for every state reachable from the row's start, the state's allowed set, intersected with the
+row's allow-list, minus its permanent bans, minus the last ids of all its bad words, must be non-empty -- which refuses a
+non-accepting dead end, and an accepting leaf on a row without a stop id: `guided_choice` needs a stop id on the row.  ValueError
+before any launch and before the prompts are encoded: a bool or non-integer id, an id outside the vocabulary, a state out of
+range, a str where a list is wanted, an empty choice or one of more than 64 ids, more than 256 choices, the wrong number of
+per-prompt entries, a row with both an automaton and choices, more than 1024 states or 2^20 edges in the call, a row that would
+not keep a token, and `min_tokens` > 0 on a guided row (below).  COST: 2 * draft_len + 2 extra launches per speculative step
+(draft_len + 1 masks, draft_len advances, one commit; 2 per plain step).  Measured at B = 32, K = 8, V = 152064, bf16
+(profiles/fsm_step.json), kernel time: the mask 15.7 us on the target's [32, 9, V] output and 4.7 us on one proposal's row, against
+16.0 and 4.7 us for asd_logit_mask_rows with an allow-list of the same size in the same run (ratios 0.98 and 1.00, inside the
+run-to-run spread: it is the same stream); an advance 2.7 us at a state of 1 edge and 2.9 us at a state of V edges (three search
+rounds), a commit 3.1 and 3.4 us; from Python every one of these calls costs the launch cadence, 10 - 11 us.
+NOT BUILT: regex- or JSON-schema-to-automaton compilers (a caller hands over the automaton); byte-level grammars; `min_tokens` > 0
+on a guided row raises ValueError (its temporary ban of the stop ids can empty an accepting leaf); fusing the advance into the
+mask launch; and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -240,8 +295,9 @@ from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
 from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS,  # noqa: F401
                          _check_logprobs, _check_min_p, _check_stop_ids, _check_stop_sequences, _is_seq,
-                         check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt,
+                         check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt,
                          check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
 # reference stage label -> the Qwen2.5 shape this build runs in its place (configs/models.yaml names the tiers by size)
@@ -286,6 +342,8 @@ class StageConfig:
     presence_penalty: float = 0.0            # in [-2, 2]; 0: off
     frequency_penalty: float = 0.0           # in [-2, 2]; 0: off
     bad_words: Sequence = ()                 # words (strings / sequences of 1..8 token ids) no row may produce (module docstring, BAD WORDS)
+    guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
+    guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
 
 
 _REASONS = {1: "stop", 2: "length"}
@@ -308,6 +366,7 @@ class _Plan(NamedTuple):
     mask_rows: list                          # every row's allow-list: a sorted tuple of ids, or None
     bad_rows: list                           # every row's bad words: distinct tuples of 1..8 ids
     penalties: Optional[Tuple[list, list, list]]    # every row's repetition, presence and frequency penalty; None: all neutral
+    fsm: Optional[CompiledFsm]               # the rows' guided automata in one state space (host arrays); None: no row is guided
     seeds: Optional[List[int]]
     n_top: int
 
@@ -354,6 +413,30 @@ class _BadWordState:
         if self.step_tok is None:
             return self.ops.bad_words_rows(logits, self.packed, tokens, seq_len, self.start, self.cap)
         return self.ops.bad_words_rows(logits, self.packed, tokens, seq_len, self.start, self.cap, self.step_tok, n_prev)
+
+
+class _FsmState:
+    """What a generate call with a guided row keeps: the call's automata and the rows' state columns on the device (uploaded
+    once; rows with the same automaton and stop ids share one), and at a verifying stage the call's [B, draft_len] buffer of the
+    step's proposals (shared with _BadWordState and _PenaltyState).  `apply` is the loops' one call per logits tensor, directly
+    behind the allow-list's; `advance` follows proposal k; `commit` follows the step's commit (module docstring, GUIDED
+    DECODING)."""
+
+    def __init__(self, ops, fsm: CompiledFsm, ld_state: int, step_tok: Optional[torch.Tensor], device):
+        self.ops, self.step_tok = ops, step_tok
+        self.packed = ops.pack_fsm(fsm, int(ld_state), device)
+
+    def apply(self, logits: torch.Tensor, first: int = 0) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], masked in place: position j by the state behind the step's first `first` + j proposals."""
+        return self.ops.fsm_mask_rows(logits, self.packed, first)
+
+    def advance(self, k: int) -> None:
+        """Behind proposal k, which the loop has written to column k of the proposal buffer."""
+        self.ops.fsm_advance(self.packed, self.step_tok, k)
+
+    def commit(self, tokens: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor, cap: int) -> None:
+        """Behind the step's commit, which left seq_len and n_commit (0 for a finished row: its state stays)."""
+        self.ops.fsm_commit(self.packed, tokens, seq_len, n_commit, cap)
 
 
 class _PenaltyState:
@@ -655,9 +738,10 @@ class _SampledRows(_Sampled):
 class _CallState:
     """The device side of one generate call, built in this one place from the plan and the encoded prompts and handed to the
     loop: how rows end (`end`), the allow-list (`mask`, None without a list), the logit edit (`edit`, None without an entry), the
-    bad words (`bad`, None when no row has one), the penalties (`pen`, None when every row is neutral), the sampler and the
-    top-N tables (`top`, None when off).  `step_tok`: the [B, draft_len] buffer of the step's proposals, ONE per call, which
-    `bad` and `pen` both read at a verifying stage (None at stage 0, and when both are off).  Uploads happen here, once; a part
+    guided automata (`fsm`, None when no row is guided), the bad words (`bad`, None when no row has one), the penalties (`pen`,
+    None when every row is neutral), the sampler and the top-N tables (`top`, None when off).  `step_tok`: the [B, draft_len]
+    buffer of the step's proposals, ONE per call, which `fsm`, `bad` and `pen` all read at a verifying stage (None at stage 0,
+    and when all three are off).  Uploads happen here, once; a part
     that is off costs no launch.  `prompt_ids`: every row's prompt ids without the padding."""
 
     def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor, prompt_ids: List[List[int]]):
@@ -666,9 +750,11 @@ class _CallState:
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
         self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
-        history = any(plan.bad_rows) or bool(plan.penalties)
+        history = any(plan.bad_rows) or bool(plan.penalties) or plan.fsm is not None
         self.step_tok = torch.zeros((B, stage.config.draft_len), dtype=torch.int32, device=dev) \
             if history and stage.draft is not None else None
+        self.fsm = _FsmState(ops, plan.fsm, 1 if stage.draft is None else stage.config.draft_len + 1, self.step_tok, dev) \
+            if plan.fsm is not None else None
         self.bad = _BadWordState(ops, plan.bad_rows, P, P + plan.max_tokens, self.step_tok, dev) if any(plan.bad_rows) else None
         self.pen = _PenaltyState(ops, plan.penalties, prompt_ids, stage.shape.vocab, self.step_tok, dev) if plan.penalties else None
         # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
@@ -747,7 +833,8 @@ class Stage:
                  stop_sequences_per_prompt=None, top_k=None, logit_bias=None, banned_token_ids=None,
                  min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
                  frequency_penalty=None, bad_words=None,
-                 bad_words_per_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 bad_words_per_prompt=None, guided_fsm=None, guided_choice=None,
+                 guided_choice_per_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -806,12 +893,24 @@ class Stage:
         run.  Draft and target logits receive the same ban, behind the mask and ahead of the edits and the penalties, and
         log-probs and top-N tables are those of the distribution with the banned tokens removed.  Duplicates are dropped; a
         row keeps at most 256 words; a row whose allow-list (or vocabulary) the bans and the words' last ids would empty
-        raises ValueError (module docstring, BAD WORDS)."""
+        raises ValueError (module docstring, BAD WORDS).
+        `guided_fsm` (None = StageConfig.guided_fsm): one serving.guided.TokenFSM for every prompt, or one TokenFSM (or None:
+        the row is free) per prompt; `guided_choice` (None = StageConfig.guided_choice): one list of choices -- strings, encoded
+        like a stop string, or sequences of 1..64 token ids, at most 256 -- for every prompt; `guided_choice_per_prompt`:
+        len(prompts) such lists, None or an empty list leaving the row free.  A guided row produces only tokens its automaton
+        allows in the state its generated tokens have led to; in an accepting state it may produce one of its stop ids (which
+        ends it), elsewhere its stop ids are forbidden.  A guided-choice row therefore returns exactly one choice followed by
+        one stop id with reason "stop", or a prefix of a choice with reason "length"; it needs a stop id.  Draft and target
+        logits receive the same mask at every position, directly behind the allow-list's, and log-probs and top-N tables are
+        those of the restricted distribution.  A row with both an automaton and choices, `min_tokens` > 0 on a guided row,
+        more than 1024 states in a call, and a reachable state that the row's other restrictions leave without a token raise
+        ValueError (module docstring, GUIDED DECODING)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
                           stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
-                          repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt)
+                          repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
+                          guided_choice, guided_choice_per_prompt)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -835,7 +934,8 @@ class Stage:
 
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
-              repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt) -> _Plan:
+              repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm=None,
+              guided_choice=None, guided_choice_per_prompt=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -871,10 +971,20 @@ class Stage:
                 raise ValueError("the stop sequences of a prompt must be distinct")
         edit_rows = merge_logit_edits(check_logit_bias(given(logit_bias, cfg.logit_bias), n, V),
                                       check_banned_token_ids(given(banned_token_ids, cfg.banned_token_ids), n, V),
-                                      check_min_tokens(given(min_tokens, cfg.min_tokens), n), row_seqs, V)
+                                      min_tokens := check_min_tokens(given(min_tokens, cfg.min_tokens), n), row_seqs, V)
         mask_rows = check_allowed_token_ids(given(allowed_token_ids, cfg.allowed_token_ids), n, V)
         bad_rows = check_bad_words(given(bad_words, cfg.bad_words), bad_words_per_prompt, n, V, self.tokenizer)
         check_rows_keep_a_token(mask_rows, edit_rows, bad_rows, V)
+        fsm_rows = check_guided(given(guided_fsm, cfg.guided_fsm), given(guided_choice, cfg.guided_choice), guided_choice_per_prompt,
+                                n, V, self.tokenizer)
+        fsm = None
+        if any(f is not None for f in fsm_rows):
+            for b, (f, m) in enumerate(zip(fsm_rows, min_tokens)):
+                if f is not None and m > 0:      # (its temporary ban of the stop ids can empty an accepting leaf)
+                    raise ValueError(f"prompt {b}: min_tokens > 0 is not built for a guided row")
+            # Z: the row's length-1 stop-list entries -- its stop ids and one-token stop sequences (what grammar back ends do with EOS)
+            fsm = compile_rows(fsm_rows, [[s[0] for s in r if len(s) == 1] for r in row_seqs], V)
+            check_guided_rows_keep_a_token(fsm, fsm_rows, mask_rows, edit_rows, bad_rows)
         penalties = (check_repetition_penalty(given(repetition_penalty, cfg.repetition_penalty), n),
                      check_presence_penalty(given(presence_penalty, cfg.presence_penalty), n),
                      check_frequency_penalty(given(frequency_penalty, cfg.frequency_penalty), n))
@@ -897,7 +1007,8 @@ class Stage:
         return _Plan(prompts=prompts, limits=tuple(limits), max_tokens=int(limit), greedy=greedy,
                      inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
-                     edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, penalties=penalties, seeds=seeds, n_top=n_top)
+                     edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, penalties=penalties, fsm=fsm, seeds=seeds,
+                     n_top=n_top)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -917,6 +1028,7 @@ class Stage:
         dev = ids.device
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
+        fsm = st.fsm
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -927,6 +1039,8 @@ class Stage:
                 logits = logits.contiguous()
             if mask is not None:
                 mask.apply(logits)                                       # the allow-list first, then the sparse edit (they commute)
+            if fsm is not None:
+                fsm.apply(logits)                                        # mask -> fsm: the state behind the committed tokens
             if bad is not None:
                 bad.apply(logits, tokens, seq_len)                       # mask -> bad words -> edit -> penalties
             if edit is not None:
@@ -942,6 +1056,8 @@ class Stage:
                 top.commit(seq_len, n_commit)
             if pen is not None:
                 pen.commit(tokens, seq_len, n_commit, cap)               # the committed tokens enter the history
+            if fsm is not None:
+                fsm.commit(tokens, seq_len, n_commit, cap)               # ... and move the automaton
             if kept is not None:                                        # tests: the record, with the top-N rows behind it
                 self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
             self.last_steps = step + 1
@@ -970,7 +1086,8 @@ class Stage:
         Kd = cfg.draft_len
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        step_tok = st.step_tok                                          # the step's proposals, for `bad` and `pen`; None: both off
+        fsm = st.fsm
+        step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
             m.reset()
@@ -993,6 +1110,8 @@ class Stage:
                     dl = dl.contiguous()
                 if mask is not None:
                     mask.apply(dl)
+                if fsm is not None:
+                    fsm.apply(dl, k)                                    # the state behind the proposals 0 .. k - 1
                 if bad is not None:
                     bad.apply(dl, tokens, seq_len, k)                   # the history: the committed tokens, then proposals 0 .. k - 1
                 if edit is not None:
@@ -1002,12 +1121,16 @@ class Stage:
                 toks.append(sampler.propose(dl, k))
                 if step_tok is not None:
                     step_tok[:, k] = toks[-1]
+                if fsm is not None:
+                    fsm.advance(k)                                      # column k + 1; the last one is the bonus row's
                 if k + 1 < Kd:
                     dl = draft.forward_ragged(toks[-1].to(torch.int64)[:, None], L + k, window)[:, -1]
             tok32 = torch.stack(toks, 1).to(torch.int32).contiguous()
             t_out = target.forward_ragged(torch.cat([last2[:, 1:], tok32.to(torch.int64)], 1), L - 1, window)   # [B, K+1, V]
             if mask is not None:
                 mask.apply(t_out)                                       # the whole [B, K+1, V] output, before any slice
+            if fsm is not None:
+                fsm.apply(t_out)                                        # row j under the state the draft's proposal j had
             if bad is not None:
                 bad.apply(t_out, tokens, seq_len)                       # row j sees the proposals 0 .. j - 1, as the draft's did
             if edit is not None:
@@ -1023,6 +1146,8 @@ class Stage:
                 top.commit(seq_len, n_commit)
             if pen is not None:
                 pen.commit(tokens, seq_len, n_commit, cap)               # the committed tokens enter the history
+            if fsm is not None:
+                fsm.commit(tokens, seq_len, n_commit, cap)               # ... and move the automaton
             if kept is not None:                                        # tests: the record, with the top-N rows behind it
                 self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
             steps += 1

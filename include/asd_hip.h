@@ -590,6 +590,77 @@ int asd_bad_words_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64
                        const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /
+ * structured-output back ends compile a set of answers, a regex or a schema to.  Inside a speculative step the mask of
+ * position j depends on the proposals 0 .. j-1, which exist only on the device: so the state lives there, small kernels
+ * advance it, and the mask is chosen per (sequence, position).  Applied alike, from the same history, to the draft's proposal
+ * rows and the target's K+1 rows, the draft -> verify -> residual chain stays lossless against the grammar-restricted target
+ * distribution.
+ * TABLES (device, int32 unless stated; one state space of S states and E edges for the whole call):
+ *   state_first [S+1]  CSR offsets: state s owns the edges [state_first[s], state_first[s+1])
+ *   edge_tok    [E]    the edges' token ids, ASCENDING and DISTINCT within a state
+ *   edge_next   [E]    the edges' next states; -1: the token is forbidden in that state
+ *   state_other [S]    the next state of every token WITHOUT an edge in s; -1: such tokens are forbidden
+ *   state_bits  uint32 [S, W], W = (V+31)/32, asd_logit_mask_rows' bit layout: bit v & 31 of word v >> 5 of row s SET = token v
+ *               has a transition in s that is not -1.  Built by the host from the other four; bits at v >= V are never looked at.
+ *   pos_state   [B] rows of ld_state columns: column 0 is the state behind the sequence's committed tokens, column i the
+ *               state behind the proposals 0 .. i-1 of the running step.  A sequence without an automaton holds -1.
+ * THE TRANSITION delta(s, t):
+ *     s outside [0, S)                                   -> s (no automaton, or damaged data)
+ *     t has an edge in s                                 -> that edge's next state
+ *     t has no edge in s                                 -> state_other[s]
+ *     that result outside [0, S) (-1: forbidden), or t outside [0, V)   -> s
+ * The last line cannot occur in correct operation -- every proposal was drawn from masked logits -- and mapping it to "s
+ * unchanged" means a sequence never loses its non-empty mask.
+ *
+ * asd_fsm_mask_rows: logits in asd_logit_edit_rows' addressing (element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32,
+ * unit last stride, any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only), masked in place:
+ * position j of sequence b with row s = pos_state[b][first + j] of state_bits -- element v becomes -inf of the dtype (the bits
+ * asd_logit_mask_rows writes) where bit v of row s is clear; s outside [0, S) leaves the position alone.  Nothing else in the
+ * allocation is written.  This is asd_logit_mask_rows with a mask index per (b, j) instead of per b, and the same write stream
+ * (one shared kernel body): 16-byte all-clear stores, mixed chunks loaded, blended and stored whole, single elements in front
+ * of the first and behind the last 16-byte boundary, grid (B*K1) x slices of whole mask words.
+ * Status, in this order: negative B / K1 / V / S / first / ld_state: invalid argument; B, K1, V or S == 0: ASD_OK, nothing
+ * launched; unknown dtype, B*K1 > INT32_MAX: unsupported; NULL logits / state_bits / pos_state, ld_row < V, ld_seq < K1*ld_row,
+ * first + K1 > ld_state: invalid argument; logits not aligned to the element size, state_bits / pos_state not to 4: alignment.
+ *
+ * asd_fsm_advance: pos_state[b][k+1] = delta(pos_state[b][k], step_tok[b][k]) for every sequence -- behind proposal k of a
+ * step, for every k including the last, so that column K exists for the target's bonus row.  step_tok: int32 [B] rows of n_tok
+ * proposals, ld_tok >= n_tok apart (asd_bad_words_rows' argument).
+ * Status, in this order: negative B / S / E / V / k / n_tok / ld_state: invalid argument; B == 0: ASD_OK; n_tok >
+ * ASD_MAX_DRAFT_LEN: unsupported; NULL state_first / state_other / pos_state / step_tok, NULL edge_tok / edge_next with E > 0,
+ * k + 1 >= ld_state, k >= n_tok, ld_tok < n_tok: invalid argument; a pointer not aligned to 4: alignment.
+ *
+ * asd_fsm_commit: behind the step's commit, which left seq_len and n_commit.  For a sequence with c = n_commit[b] > 0, c
+ * clamped to ld_state and L = seq_len[b] clamped into [1, max_len]:
+ *     pos_state[b][0] = delta(pos_state[b][c-1], tokens[b][L-1])
+ * One transition is enough: the first c-1 committed tokens of a step are always its accepted proposals 0 .. c-2 (stop rules
+ * and length limits cut from the END), so column c-1 already is the state behind them.  c <= 0 (a finished sequence) leaves
+ * the state as it is.  tokens: int32 rows ld_tokens >= max_len apart.
+ * Status, in this order: negative B / S / E / V / max_len / ld_state: invalid argument; B == 0: ASD_OK; NULL state_first /
+ * state_other / pos_state / tokens / seq_len / n_commit, NULL edge_tok / edge_next with E > 0, ld_state < 1, max_len < 1,
+ * ld_tokens < max_len: invalid argument; a pointer not aligned to 4: alignment.
+ *
+ * Both small kernels: one launch, ONE WAVE per sequence, on the serial draft path where latency counts, not bytes.  The wave
+ * searches the state's sorted edge range cooperatively -- one probe per lane per round, a wave ballot picks the bracket -- in at
+ * most ceil(log64(n_edges)) dependent rounds (3 at a vocabulary-sized state, against 18 for a per-lane binary search).  No LDS,
+ * no atomics, no workspace; the result is one ordinary per-lane vector-memory store.  THE DATA CONTRACT: the launchers cannot
+ * check device data, so the kernels do: the edge range of a state is clamped into [0, E], tokens and states are compared as
+ * plain integers, and a state indexes the tables only inside [0, S).
+ * ---------------------------------------------------------------------------------------- */
+int asd_fsm_mask_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                      const uint32_t* state_bits /*[S, (V+31)/32]*/, int S, const int32_t* pos_state /*[B, ld_state]*/,
+                      int64_t ld_state, int first, void* stream);
+int asd_fsm_advance(const int32_t* state_first /*[S+1]*/, const int32_t* edge_tok /*[E]*/, const int32_t* edge_next /*[E]*/,
+                    const int32_t* state_other /*[S]*/, int S, int E, int V, int32_t* pos_state /*[B, ld_state] in/out*/,
+                    int64_t ld_state, int B, int k, const int32_t* step_tok /*[B, ld_tok]*/, int64_t ld_tok, int n_tok,
+                    void* stream);
+int asd_fsm_commit(const int32_t* state_first /*[S+1]*/, const int32_t* edge_tok /*[E]*/, const int32_t* edge_next /*[E]*/,
+                   const int32_t* state_other /*[S]*/, int S, int E, int V, int32_t* pos_state /*[B, ld_state] in/out*/,
+                   int64_t ld_state, int B, const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens,
+                   const int32_t* seq_len /*[B]*/, const int32_t* n_commit /*[B]*/, int max_len, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stateful penalties AHEAD of the samplers and behind the mask and the edit -- vLLM's `apply_penalties`: repetition_penalty,
  * presence_penalty, frequency_penalty.  A penalised row is an ordinary input of every sampler; applied alike, from the same
  * history, to the draft's proposal rows and the target's K+1 rows, the draft -> verify -> residual chain stays lossless against

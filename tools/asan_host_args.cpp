@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit and asd_bad_words_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance and asd_fsm_commit in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -398,6 +398,104 @@ int main() {
         EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, off, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // seq_len
         EXPECT(BADW(p, BF16, K1 * V, V, B, K1, V, i32, i32, i32, 8, i32, 32, i32, 4, 32, off, 4, 4, 0), ASD_ERR_ALIGNMENT);        // step_tok
 #undef BADW
+    }
+
+    // ---- asd_fsm_mask_rows / asd_fsm_advance / asd_fsm_commit: every rejection, and every "nothing to do", comes before the launch
+    {
+#define FMASK(x_, dt_, lds_, ldr_, B_, K1_, V_, bits_, S_, pos_, ldst_, first_) \
+    asd_fsm_mask_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, bits_, S_, pos_, ldst_, first_, nullptr)
+#define FADV(sf_, et_, en_, so_, S_, E_, V_, pos_, ldst_, B_, k_, tok_, ldt_, nt_) \
+    asd_fsm_advance(sf_, et_, en_, so_, S_, E_, V_, pos_, ldst_, B_, k_, tok_, ldt_, nt_, nullptr)
+#define FCOM(sf_, et_, en_, so_, S_, E_, V_, pos_, ldst_, B_, tk_, ldk_, sl_, nc_, ml_) \
+    asd_fsm_commit(sf_, et_, en_, so_, S_, E_, V_, pos_, ldst_, B_, tk_, ldk_, sl_, nc_, ml_, nullptr)
+        const int K1 = 5, S = 7, E = 9;
+        const uint32_t* bits = reinterpret_cast<const uint32_t*>(rows);
+        int32_t* off = reinterpret_cast<int32_t*>(rows + 2);
+        EXPECT(FMASK(p, BF16, K1 * V, V, -1, K1, V, bits, S, i32, 5, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, -1, V, bits, S, i32, 5, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, -1, bits, S, i32, 5, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, bits, -1, i32, 5, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, bits, S, i32, 5, -1), ASD_ERR_INVALID_ARG);      // first
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, bits, S, i32, -1, 0), ASD_ERR_INVALID_ARG);      // ld_state
+        EXPECT(FMASK(p, BF16, K1 * V, V, 0, K1, V, bits, S, i32, 5, -1), ASD_ERR_INVALID_ARG);      // ... before the empty batch
+        EXPECT(FMASK(nullptr, 99, 0, 0, 0, K1, V, nullptr, S, nullptr, 0, 0), ASD_OK);              // B == 0
+        EXPECT(FMASK(nullptr, 99, 0, 0, B, 0, V, nullptr, S, nullptr, 0, 0), ASD_OK);               // K1 == 0
+        EXPECT(FMASK(nullptr, 99, 0, 0, B, K1, 0, nullptr, S, nullptr, 0, 0), ASD_OK);              // V == 0
+        EXPECT(FMASK(nullptr, 99, 0, 0, B, K1, V, nullptr, 0, nullptr, 0, 0), ASD_OK);              // no state
+        EXPECT(FMASK(p, 99, K1 * V, V, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_UNSUPPORTED);         // dtype
+        EXPECT(FMASK(nullptr, 99, K1 * V, V, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_UNSUPPORTED);   // ... before the NULL checks
+        EXPECT(FMASK(nullptr, BF16, K1 * V, V, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, nullptr, S, i32, 5, 0), ASD_ERR_INVALID_ARG);    // state_bits
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, bits, S, nullptr, 5, 0), ASD_ERR_INVALID_ARG);   // pos_state
+        EXPECT(FMASK(p, BF16, K1 * V, V - 1, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_INVALID_ARG);   // ld_row < V
+        EXPECT(FMASK(p, BF16, K1 * V - 1, V, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_INVALID_ARG);   // ld_seq < K1 ld_row
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, bits, S, i32, 5, 1), ASD_ERR_INVALID_ARG);       // positions 1 .. 5 of 5 columns
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, bits, S, i32, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(FMASK(rows + 1, BF16, K1 * V, V - 1, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_INVALID_ARG);   // ... before alignment
+        EXPECT(FMASK(rows + 1, BF16, K1 * V, V, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_ALIGNMENT);  // below the element size
+        EXPECT(FMASK(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, bits, S, i32, 5, 0), ASD_ERR_ALIGNMENT);
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, reinterpret_cast<const uint32_t*>(rows + 2), S, i32, 5, 0), ASD_ERR_ALIGNMENT);
+        EXPECT(FMASK(p, BF16, K1 * V, V, B, K1, V, bits, S, off, 5, 0), ASD_ERR_ALIGNMENT);
+
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, -1, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);
+        EXPECT(FADV(i32, i32, i32, i32, -1, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);
+        EXPECT(FADV(i32, i32, i32, i32, S, -1, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);
+        EXPECT(FADV(i32, i32, i32, i32, S, E, -1, i32, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, B, -1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // k
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, B, 1, i32, 4, -1), ASD_ERR_INVALID_ARG);   // n_tok
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, -1, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // ld_state
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, 0, -1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // ... before the empty batch
+        EXPECT(FADV(nullptr, nullptr, nullptr, nullptr, S, E, V, nullptr, 0, 0, 0, nullptr, 0, 0), ASD_OK);   // B == 0
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, B, 1, i32, 65, ASD_MAX_DRAFT_LEN + 1), ASD_ERR_UNSUPPORTED);
+        EXPECT(FADV(nullptr, i32, i32, i32, S, E, V, i32, 5, B, 1, i32, 65, ASD_MAX_DRAFT_LEN + 1), ASD_ERR_UNSUPPORTED);   // ... before the NULL checks
+        EXPECT(FADV(nullptr, i32, i32, i32, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // state_first
+        EXPECT(FADV(i32, nullptr, i32, i32, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // edge_tok with E > 0
+        EXPECT(FADV(i32, i32, nullptr, i32, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // edge_next with E > 0
+        EXPECT(FADV(i32, i32, i32, nullptr, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // state_other
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, nullptr, 5, B, 1, i32, 4, 4), ASD_ERR_INVALID_ARG);   // pos_state
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, B, 1, nullptr, 4, 4), ASD_ERR_INVALID_ARG);   // step_tok
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, B, 4, i32, 8, 8), ASD_ERR_INVALID_ARG);       // k + 1 == ld_state
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 9, B, 4, i32, 4, 4), ASD_ERR_INVALID_ARG);       // k == n_tok
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, B, 1, i32, 3, 4), ASD_ERR_INVALID_ARG);       // ld_tok < n_tok
+        EXPECT(FADV(off, i32, i32, i32, S, E, V, i32, 5, B, 4, i32, 8, 8), ASD_ERR_INVALID_ARG);       // ... before alignment
+        EXPECT(FADV(off, i32, i32, i32, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_ALIGNMENT);
+        EXPECT(FADV(i32, off, i32, i32, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_ALIGNMENT);
+        EXPECT(FADV(i32, i32, off, i32, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_ALIGNMENT);
+        EXPECT(FADV(i32, i32, i32, off, S, E, V, i32, 5, B, 1, i32, 4, 4), ASD_ERR_ALIGNMENT);
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, off, 5, B, 1, i32, 4, 4), ASD_ERR_ALIGNMENT);
+        EXPECT(FADV(i32, i32, i32, i32, S, E, V, i32, 5, B, 1, off, 4, 4), ASD_ERR_ALIGNMENT);
+
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, -1, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(FCOM(i32, i32, i32, i32, -1, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(FCOM(i32, i32, i32, i32, S, -1, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, -1, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, -1), ASD_ERR_INVALID_ARG);   // max_len
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, -1, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);  // ld_state
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, 0, i32, 32, i32, i32, -1), ASD_ERR_INVALID_ARG);   // ... before the empty batch
+        EXPECT(FCOM(nullptr, nullptr, nullptr, nullptr, S, E, V, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0), ASD_OK);   // B == 0
+        EXPECT(FCOM(nullptr, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);   // state_first
+        EXPECT(FCOM(i32, nullptr, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);   // edge_tok with E > 0
+        EXPECT(FCOM(i32, i32, nullptr, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);   // edge_next with E > 0
+        EXPECT(FCOM(i32, i32, i32, nullptr, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);   // state_other
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, nullptr, 5, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);   // pos_state
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, nullptr, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);   // tokens
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, nullptr, i32, 32), ASD_ERR_INVALID_ARG);   // seq_len
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, nullptr, 32), ASD_ERR_INVALID_ARG);   // n_commit
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 0, B, i32, 32, i32, i32, 32), ASD_ERR_INVALID_ARG);       // ld_state < 1
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, 0), ASD_ERR_INVALID_ARG);        // max_len < 1
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, i32, 31, i32, i32, 32), ASD_ERR_INVALID_ARG);       // ld_tokens < max_len
+        EXPECT(FCOM(off, i32, i32, i32, S, E, V, i32, 5, B, i32, 31, i32, i32, 32), ASD_ERR_INVALID_ARG);       // ... before alignment
+        EXPECT(FCOM(off, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_ALIGNMENT);
+        EXPECT(FCOM(i32, off, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_ALIGNMENT);
+        EXPECT(FCOM(i32, i32, off, i32, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_ALIGNMENT);
+        EXPECT(FCOM(i32, i32, i32, off, S, E, V, i32, 5, B, i32, 32, i32, i32, 32), ASD_ERR_ALIGNMENT);
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, off, 5, B, i32, 32, i32, i32, 32), ASD_ERR_ALIGNMENT);
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, off, 32, i32, i32, 32), ASD_ERR_ALIGNMENT);
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, off, i32, 32), ASD_ERR_ALIGNMENT);
+        EXPECT(FCOM(i32, i32, i32, i32, S, E, V, i32, 5, B, i32, 32, i32, off, 32), ASD_ERR_ALIGNMENT);
+#undef FMASK
+#undef FADV
+#undef FCOM
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
