@@ -24,6 +24,7 @@ MAX_TOP_LOGPROBS = 8
 MAX_LOGIT_EDITS = 1024
 MAX_STOP_SEQS, MAX_STOP_SEQ_LEN = 16, 8
 MAX_BAD_WORDS, MAX_BAD_WORD_LEN = 256, 8
+MAX_NGRAM, NGRAM_SLICE = 8, 2048
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
@@ -112,6 +113,7 @@ SIGNATURES = {
     "asd_logit_edit_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "asd_logit_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _vp]),
     "asd_bad_words_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
+    "asd_no_repeat_ngram_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
     "asd_fsm_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_advance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_commit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _vp, _i64, _vp, _vp, _i, _vp]),

@@ -38,6 +38,7 @@ SOURCES = {
     "logit_edit.hip": [],                         # one f32 addition and one conversion per edited element: nothing to contract
     "logit_mask.hip": [],                         # bit tests and stores of a constant: no floating-point arithmetic at all
     "bad_words.hip": [],                          # integer compares and stores of a constant: no floating-point arithmetic at all
+    "no_repeat_ngram.hip": [],                    # integer compares and stores of a constant: no floating-point arithmetic at all
     "fsm.hip": [],                                # logit_mask.hip's write stream and integer searches: no floating-point arithmetic
     "penalty.hip": ["-ffp-contract=off"],         # y - freq * c must round twice, as the header and the numpy reference state it
     "lm_head_verify.hip": ["-ffp-contract=off"],  # ends in the same finish_row arithmetic as verify_accept.hip

@@ -493,6 +493,21 @@ class HipOps:
         tensor, behind logit_mask_rows and in front of logit_edit_rows, and only when some row of the call has a word."""
         return self.K.bad_words_rows(logits, words, tokens, seq_len, start, max_len, step_tok, n_prev)
 
+    @traced("pack_no_repeat_ngram")
+    def pack_no_repeat_ngram(self, ns, prompt_lens, P: int, device):
+        """Every row's no_repeat_ngram_size (0: off) and its number of real prompt ids, which end at index P of the token
+        buffer -> the device arguments of no_repeat_ngram_rows (kernels.pack_no_repeat_ngram: one upload per generate call)."""
+        return self.K.pack_no_repeat_ngram(ns, prompt_lens, P, device)
+
+    @traced("no_repeat_ngram_rows")
+    def no_repeat_ngram_rows(self, logits, ngram, tokens, seq_len, max_len, step_tok=None, n_prev: int = 0):
+        """HF generate's no_repeat_ngram_size ahead of the samplers (asd_no_repeat_ngram_rows): logits [B, V] or [B, K1, V] (any
+        strides with a unit last stride) -> the same tensor, with every token at -inf that would repeat an n-gram of the row's
+        history: its real prompt ids and committed tokens tokens[b, row_start[b]:seq_len[b]] and the step's proposals
+        step_tok[b, :n_prev + j] at position j.  One launch, no workspace, no state; a stage loop makes the call once per logits
+        tensor, behind bad_words_rows and in front of logit_edit_rows, and only when some row of the call has n > 0."""
+        return self.K.no_repeat_ngram_rows(logits, ngram, tokens, seq_len, max_len, step_tok, n_prev)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

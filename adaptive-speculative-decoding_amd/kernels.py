@@ -1587,3 +1587,83 @@ def fsm_commit(fsm: TokenFsm, tokens: torch.Tensor, seq_len: torch.Tensor, n_com
                                tokens.shape[1], _dev(seq_len, "seq_len", torch.int32), _dev(n_commit, "n_commit", torch.int32), cap,
                                _stream())
     B.check("asd_fsm_commit", rc)
+
+
+# ------------------------------------------------------------------------------- no repeated n-gram (no_repeat_ngram_size)
+@dataclass
+class NoRepeatNgram:
+    """The per-row arguments of asd_no_repeat_ngram_rows on the device (pack_no_repeat_ngram): ngram_n i32 [B] (0: the row is
+    off), or None when every row has n_shared; row_start i32 [B], the index of every row's first real prompt id behind the
+    left-padding, or None when no row has a prompt id (row_start = P everywhere)."""
+    ngram_n: Optional[torch.Tensor]
+    row_start: Optional[torch.Tensor]
+    n_shared: int                            # every row's n when ngram_n is None
+    P: int                                   # the padded prompt length the rows were packed for (`start` of the calls)
+    B: int                                   # rows the arguments were packed for
+
+
+def check_no_repeat_ngram_rows(ns, prompt_lens, P: int):
+    """The host side of pack_no_repeat_ngram: every row's n in [0, MAX_NGRAM] and its count of real prompt ids in [0, P] ->
+    (ngram_n list, row_start list) with row_start[b] = P - prompt_lens[b]."""
+    ns, lens = list(ns), list(prompt_lens)
+    if len(ns) != len(lens):
+        raise ValueError(f"{len(ns)} n-gram sizes for {len(lens)} prompt lengths")
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or not 0 <= int(P) < 2 ** 31:
+        raise ValueError(f"P must be an integer in [0, 2^31), got {P!r}")
+    for b, (n, m) in enumerate(zip(ns, lens)):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= B.MAX_NGRAM:
+            raise ValueError(f"row {b}: the n-gram size must be an integer in [0, {B.MAX_NGRAM}], got {n!r}")
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= int(m) <= int(P):
+            raise ValueError(f"row {b}: the prompt length must be an integer in [0, {int(P)}], got {m!r}")
+    return [int(n) for n in ns], [int(P) - int(m) for m in lens]
+
+
+def pack_no_repeat_ngram(ns, prompt_lens, P: int, device) -> NoRepeatNgram:
+    """The per-row arguments of no_repeat_ngram_rows from host lists, checked BEFORE anything is uploaded: `ns` holds every
+    row's n (0: off), `prompt_lens` its number of real prompt ids, which end at index P of the row's token buffer."""
+    n_list, first = check_no_repeat_ngram_rows(ns, prompt_lens, P)
+    shared = bool(n_list) and all(n == n_list[0] for n in n_list)          # one n for every row: no table (a shared list's way)
+    return NoRepeatNgram(None if shared else torch.tensor(n_list, dtype=torch.int32).to(device),
+                         None if all(f == int(P) for f in first) else torch.tensor(first, dtype=torch.int32).to(device),
+                         n_list[0] if shared else 0, int(P), len(n_list))
+
+
+def no_repeat_ngram_rows(logits: torch.Tensor, ngram: NoRepeatNgram, tokens: torch.Tensor, seq_len: torch.Tensor, max_len: int,
+                         step_tok: Optional[torch.Tensor] = None, n_prev: int = 0) -> torch.Tensor:
+    """Ban in place (asd_no_repeat_ngram_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  With n = ngram.ngram_n[b] (or ngram.n_shared) and H = tokens[b, row_start[b]:seq_len[b]] ++
+    step_tok[b, :n_prev + j], every token that followed an earlier occurrence of H's last n - 1 tokens becomes -inf at
+    position j.  tokens i32 [B, >= max_len] contiguous; seq_len i32 [B]: the step's lengths BEFORE its commit; step_tok
+    i32 [B, n_tok] (unit stride along the proposals) or None."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    start = ngram.P
+    if ngram.B != Bv or tuple(seq_len.shape) != (Bv,):
+        raise ValueError(f"the n-gram sizes were packed for {ngram.B} rows and seq_len must be int32 [B]; logits have {Bv} rows")
+    if tokens.dim() != 2 or tokens.shape[0] != Bv or not 0 <= start <= int(max_len) <= tokens.shape[1]:
+        raise ValueError(f"tokens must be int32 [B, >= max_len] and 0 <= start <= max_len, got {tuple(tokens.shape)}, {start}, {max_len}")
+    ld_tok = n_tok = 0
+    if step_tok is None:
+        if n_prev != 0:
+            raise ValueError("n_prev must be 0 without step_tok")
+    else:
+        if not step_tok.is_cuda or step_tok.dtype != torch.int32 or step_tok.dim() != 2 or step_tok.shape[0] != Bv or \
+                (step_tok.shape[1] > 1 and step_tok.stride(1) != 1):
+            raise ValueError("step_tok must be a CUDA int32 [B, n_tok] tensor with unit stride along the proposals")
+        n_tok = step_tok.shape[1]
+        ld_tok = step_tok.stride(0) if Bv > 1 else n_tok
+        if not 0 <= int(n_prev) or int(n_prev) + K1 - 1 > n_tok or ld_tok < n_tok:
+            raise ValueError(f"position {K1 - 1} would see {int(n_prev) + K1 - 1} proposals; step_tok holds {n_tok}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_no_repeat_ngram_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V,
+                                         _opt(ngram.ngram_n, "ngram_n", torch.int32), int(ngram.n_shared),
+                                         _opt(ngram.row_start, "row_start", torch.int32),
+                                         _dev(tokens, "tokens", torch.int32), tokens.shape[1], _dev(seq_len, "seq_len", torch.int32),
+                                         start, int(max_len), None if step_tok is None else step_tok.data_ptr(), ld_tok, n_tok,
+                                         int(n_prev), _stream())
+    B.check("asd_no_repeat_ngram_rows", rc)
+    return logits

@@ -41,6 +41,9 @@ number for the batch or one per request, kept by the request through every regro
 `guided_choice=` (serving/stages.py, GUIDED DECODING) likewise: one list of choices for the batch, which reaches the stages as
 `guided_choice`, or one list (or None: the request is free) per request, which a request keeps and the stages receive as
 `guided_choice_per_prompt`.
+`no_repeat_ngram_size=` (HF generate's; serving/stages.py, NO REPEAT N-GRAM) travels like a penalty: one int in [0, 8] for the
+batch or one per request, kept by the request through every regrouping, handed on only when it is set (here or as
+`PipelineConfig.no_repeat_ngram_size`).
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -207,6 +210,9 @@ class PipelineConfig:
     logprobs: Optional[int] = None
     # stop strings / token-id sequences handed to stage.generate(stop_sequences=); None: the keyword is not passed
     stop_sequences: Optional[Sequence] = None
+    # HF generate's no_repeat_ngram_size, handed to stage.generate(no_repeat_ngram_size=) unless the call names its own; None:
+    # the keyword is not passed
+    no_repeat_ngram_size: Optional[int] = None
 
     @classmethod
     def from_yaml(cls, path: str) -> "PipelineConfig":
@@ -238,6 +244,8 @@ class PipelineConfig:
             kw["logprobs"] = int(sec["logprobs"])
         if sec.get("stop_sequences") is not None:
             kw["stop_sequences"] = tuple(e if isinstance(e, str) else tuple(int(t) for t in e) for e in sec["stop_sequences"])
+        if sec.get("no_repeat_ngram_size") is not None:
+            kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
         return cls(**kw)
 
 
@@ -279,7 +287,7 @@ class _Active:
     top_p: Optional[float] = None
     top_k: Optional[int] = None
     min_p: Optional[float] = None
-    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens / allowed_token_ids / penalties / bad_words / guided_choice
+    edits: Dict[str, Any] = field(default_factory=dict)     # the request's own logit_bias / banned_token_ids / min_tokens / allowed_token_ids / penalties / bad_words / guided_choice / no_repeat_ngram_size
 
 
 def _fresh_stats(n_stages: int) -> Dict[str, Any]:
@@ -313,7 +321,8 @@ class AdaptiveSpeculativePipeline:
                         request_id: Optional[str] = None, seed: Optional[int] = None, top_p: Optional[float] = None,
                         top_k: Optional[int] = None, min_p: Optional[float] = None, logit_bias=None, banned_token_ids=None,
                         min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
-                        frequency_penalty=None, bad_words=None, guided_choice=None) -> RequestResult:
+                        frequency_penalty=None, bad_words=None, guided_choice=None,
+                        no_repeat_ngram_size=None) -> RequestResult:
         """seed: None, or an int in [0, 2^64): the request's sampling seed at every stage (module docstring).
         top_p / top_k / min_p: None = every stage's configuration, else the request's own value at every stage
         (stage.generate(top_p=, top_k=, min_p=)).  logit_bias (a dict) / banned_token_ids (token ids) / min_tokens (an int):
@@ -321,7 +330,8 @@ class AdaptiveSpeculativePipeline:
         allowed_token_ids (token ids) likewise; repetition_penalty / presence_penalty / frequency_penalty (one number each:
         serving/stages.py, PENALTIES) likewise; bad_words (one list of words, a word a str or a sequence of token ids:
         serving/stages.py, BAD WORDS) likewise; guided_choice (one list of choices, a choice a str or a sequence of token ids:
-        serving/stages.py, GUIDED DECODING) likewise."""
+        serving/stages.py, GUIDED DECODING) likewise; no_repeat_ngram_size (one int in [0, 8]: serving/stages.py, NO REPEAT
+        N-GRAM) likewise."""
         if seed is not None and not isinstance(seed, (int, np.integer)):
             raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
         sampling = {k: check_per_prompt(v, 1, k) for k, v in (("top_p", top_p), ("top_k", top_k), ("min_p", min_p))}
@@ -344,6 +354,10 @@ class AdaptiveSpeculativePipeline:
         if isinstance(choices.get("guided_choice"), list):
             raise ValueError("process_request takes one guided_choice list of choices")
         edits.update(choices)
+        if _is_seq(no_repeat_ngram_size):
+            raise ValueError("process_request takes one no_repeat_ngram_size integer")
+        if no_repeat_ngram_size is not None:
+            edits["no_repeat_ngram_size"] = no_repeat_ngram_size
         return self._run_batch([prompt], max_tokens, temperature, [request_id], seeds=check_seeds(seed, 1), sampling=sampling,
                                edits=edits)[0]
 
@@ -356,7 +370,8 @@ class AdaptiveSpeculativePipeline:
     def batch_process(self, prompts: List[str], max_tokens=512, temperature=0.7,
                       seeds=None, top_p=None, top_k=None, min_p=None, logit_bias=None, banned_token_ids=None,
                       min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
-                      frequency_penalty=None, bad_words=None, guided_choice=None) -> List[RequestResult]:
+                      frequency_penalty=None, bad_words=None, guided_choice=None,
+                      no_repeat_ngram_size=None) -> List[RequestResult]:
         """seeds: None, one int in [0, 2^64) for every request, or one per request (all or none: a sequence that holds None
         raises ValueError); request i keeps seeds[i] through every regrouping (module docstring).  max_tokens: an int, or one
         int >= 1 per request, kept by the request in the same way.
@@ -372,7 +387,9 @@ class AdaptiveSpeculativePipeline:
         no word) per request, kept by the request and handed on as bad_words_per_prompt (serving/stages.py, BAD WORDS).
         guided_choice: None (not handed on), one list of choices for the batch (stage.generate(guided_choice=)), or one list (or
         None: the request is free) per request, kept by the request and handed on as guided_choice_per_prompt (serving/stages.py,
-        GUIDED DECODING)."""
+        GUIDED DECODING).
+        no_repeat_ngram_size: None (not handed on, unless the configuration sets one), one int in [0, 8] for the batch, or one
+        per request, travelling like a penalty (serving/stages.py, NO REPEAT N-GRAM)."""
         prompts = list(prompts)
         n = len(prompts)
         seeds = check_seeds(seeds, n)
@@ -382,6 +399,7 @@ class AdaptiveSpeculativePipeline:
         edits.update(check_penalty_args(dict(zip(_PENALTY_KEYS, (repetition_penalty, presence_penalty, frequency_penalty))), n))
         edits.update(check_bad_words_arg(bad_words, n))
         edits.update(check_guided_choice_arg(guided_choice, n))
+        edits.update(check_penalty_args({"no_repeat_ngram_size": no_repeat_ngram_size}, n))
         if isinstance(temperature, (Sequence, np.ndarray)) and not isinstance(temperature, (str, bytes)):
             temperature = check_per_prompt(temperature, n, "temperature")
         if isinstance(temperature, list) and any(t == 0.0 for t in temperature):
@@ -573,6 +591,8 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["seed"] = [r.seed for r in todo]
                 if cfg.stop_sequences is not None:
                     stop_kw["stop_sequences"] = list(cfg.stop_sequences)
+                if cfg.no_repeat_ngram_size is not None:                # (the call's own value, shared or per request, replaces it below)
+                    stop_kw["no_repeat_ngram_size"] = int(cfg.no_repeat_ngram_size)
                 # (limits likewise: one per request of the batch, or the batch's one int)
                 limit = [r.max_tokens for r in todo] if isinstance(max_tokens, list) else max_tokens
                 # (sampling parameters likewise: a list only where the batch carries one, so other calls are unchanged)

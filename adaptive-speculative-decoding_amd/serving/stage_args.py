@@ -16,6 +16,7 @@ MAX_TOP_LOGPROBS = 8                         # ASD_MAX_TOP_LOGPROBS
 MAX_LOGIT_EDITS = 1024                       # ASD_MAX_LOGIT_EDITS: (id, bias, until) entries of one row after merging
 MAX_BAD_WORDS = 256                          # ASD_MAX_BAD_WORDS: distinct words of one row (BAD WORDS)
 MAX_BAD_WORD_LEN = 8                         # ASD_MAX_BAD_WORD_LEN
+MAX_NGRAM = 8                                # ASD_MAX_NGRAM: the largest no_repeat_ngram_size (NO REPEAT N-GRAM)
 MAX_LOGIT_BIAS = 100.0                      # |bias| <= 100, the range OpenAI documents
 _EDIT_FOREVER = 2 ** 31 - 1                  # `until` of a permanent ban
 _NUMBER = (int, float, np.integer, np.floating)
@@ -205,6 +206,44 @@ def check_rows_keep_a_token(allowed: List[Optional[Tuple[int, ...]]], edit_rows:
         if ids is None and words and len(gone) >= vocab:
             raise ValueError(f"prompt {b}: the banned token ids and the last ids of its bad_words leave no token of the "
                              f"vocabulary ({vocab})")
+
+
+def check_no_repeat_ngram_size(value, n: int) -> List[int]:
+    """generate's `no_repeat_ngram_size` (HF generate's): an int in [0, MAX_NGRAM] for all `n` prompts (0: off), or a sequence
+    of n such ints -> n ints.  A bool, a float, None inside a sequence, the wrong length and a value outside the range raise
+    ValueError."""
+    def one(v):
+        if not _is_int(v) or not 0 <= int(v) <= MAX_NGRAM:
+            raise ValueError(f"no_repeat_ngram_size must be an integer in [0, {MAX_NGRAM}], got {v!r}")
+        return int(v)
+    if isinstance(value, (str, bytes)):
+        raise ValueError(f"no_repeat_ngram_size must be an integer or one integer per prompt, got {value!r}")
+    return _per_prompt(value, n, one, "no_repeat_ngram_size values")
+
+
+def check_ngram_rows_keep_a_token(ngram_rows: List[int], prompt_lens: List[int], limits, draft_len: int,
+                                  allowed: List[Optional[Tuple[int, ...]]], edit_rows: List[List[Tuple[int, float, int]]],
+                                  bad_rows: List[List[Tuple[int, ...]]], vocab: int) -> None:
+    """THE ROW KEEPS A TOKEN under no_repeat_ngram_size (NO REPEAT N-GRAM).  A position bans at most one token per n-gram that
+    starts in its history, so at most len(H) of them, and no position of row b sees a history longer than
+        bound_b = prompt_lens[b] + limits[b] + draft_len
+    (its real prompt ids, its max_tokens, one step's proposals).  With gone_b the set check_rows_keep_a_token counts -- the
+    permanent bans, the stop ids under min_tokens, the last ids of the row's bad words -- a row with n > 0 and without an
+    allow-list needs |gone_b| + bound_b < vocab, one with an allow-list |allowed_b - gone_b| > bound_b: ValueError naming the
+    prompt otherwise.  Rows with n == 0 are not looked at."""
+    for b, n in enumerate(ngram_rows):
+        if n <= 0:
+            continue
+        bound = int(prompt_lens[b]) + int(limits[b]) + int(draft_len)
+        gone = {t for t, _, u in edit_rows[b] if u > 0} | {w[-1] for w in bad_rows[b]}
+        if allowed[b] is None and len(gone) + bound >= vocab:
+            raise ValueError(f"prompt {b}: no_repeat_ngram_size can ban up to {bound} tokens (prompt {int(prompt_lens[b])} + "
+                             f"max_tokens {int(limits[b])} + draft_len {int(draft_len)}), which with its {len(gone)} banned ids "
+                             f"may leave no token of the vocabulary ({vocab})")
+        if allowed[b] is not None and len(set(allowed[b]) - gone) <= bound:
+            raise ValueError(f"prompt {b}: no_repeat_ngram_size can ban up to {bound} tokens (prompt {int(prompt_lens[b])} + "
+                             f"max_tokens {int(limits[b])} + draft_len {int(draft_len)}), which may leave no token of its "
+                             f"allowed_token_ids ({len(set(allowed[b]) - gone)} after its bans)")
 
 
 def _check_bad_word_list(entries, vocab: int, tokenizer, what: str) -> List[Tuple[int, ...]]:

@@ -217,9 +217,42 @@ the stop ids under min_tokens) minus the LAST ids of all its words must be non-e
 ids must be smaller than V.  ValueError before any launch and before the prompts are encoded: a bool, float or out-of-vocabulary
 id, an empty word, a word of more than 8 ids, more than 256 distinct words in a row, the wrong number of per-prompt lists, a
 str where a list is wanted, a row that would keep no token.  COST: one workgroup per logits row, one lane per word, at most
-seven history loads and one store per lane (profiles/bad_words_step.json).  NOT BUILT: `no_repeat_ngram_size` (its bans can
-empty a row dynamically, which the samplers forbid and no host check can exclude); vLLM's second variant of every word with a
-leading space (SimpleTokenizer has no such variant); and serving/hierarchy.py's loop.
+seven history loads and one store per lane (profiles/bad_words_step.json).  NOT BUILT: vLLM's second variant of every word
+with a leading space (SimpleTokenizer has no such variant); and serving/hierarchy.py's loop.  (`no_repeat_ngram_size`, whose
+"words" are the n-grams of the row's own history, is the next section: its bans are dynamic, but a position bans at most one
+token per n-gram of its history, which the host bounds before the call.)
+
+NO REPEAT N-GRAM.  `generate(no_repeat_ngram_size=)` (or StageConfig.no_repeat_ngram_size; None takes the configuration's value)
+is HF generate's `no_repeat_ngram_size` (transformers' NoRepeatNGramLogitsProcessor): an int n in [0, MAX_NGRAM = 8] for every
+prompt, or one per prompt; 0 is off.  It is the usual cure for greedy or low-temperature decoding that runs into loops.  A
+logits position of row b has the history H = tokens[b][row_start[b] : L] ++ the step's proposals the position sees, with L =
+seq_len[b] as it stands before the step's commit: the row's REAL prompt ids (the `real` lists of _encode, so row_start[b] =
+P - len(real[b]); the prompt counts as history, as in HF for decoder-only models, the left-padding in front of it does not),
+its committed generated tokens, and behind them the step's uncommitted proposals, exactly as for bad words.  For every i in
+[0, len(H) - n] with H[i : i+n-1] == H[len(H)-n+1 :] element H[i+n-1] becomes -inf; nothing else is written.  With n = 1 the
+compared run is empty and every token of H is banned; with len(H) < n nothing is.  So no n-gram that ends in a row's generated
+tokens equals an earlier n-gram of its prompt plus generated tokens.  This is the operation ops.bad_words_rows cannot express:
+the "words" are not given by the caller, they are every n-gram of the row's own history, so the kernel scans the history
+(asd_no_repeat_ngram_rows: a workgroup per logits row and per slice of 2048 n-gram starts, the last suffix token compared
+first).  The rows' n and row_start are uploaded once per call (ops.pack_no_repeat_ngram) and every loop calls
+ops.no_repeat_ngram_rows (in place) once per logits tensor at the three sites of bad.apply: stage 0's [B, V] logits (no
+proposals); every proposal's draft logits (K1 = 1, n_prev = k); the target's [B, K+1, V] output before anything is sliced from
+or scored on it (n_prev = 0).  The proposal buffer is the call's ONE [B, draft_len] buffer, now also allocated when only this
+feature is on.  The order is mask -> fsm -> bad words -> n-gram -> edit -> penalties -> temperature; all of them commute on a
+-inf, and the place is fixed only so that the call pattern is.  Draft and target receive the SAME ban from the SAME history at
+every position, so -- the argument of LOGIT EDITS, word for word -- the draft -> verify -> residual chain stays lossless against
+the target distribution with the repeating tokens removed.  The operation keeps no state: a rejected proposal never reaches
+`tokens`, nothing follows the commit, nothing is rolled back.  Consequences: the returned log-probs and top-N tables are those of
+the restricted distribution; greedy decoding takes the arg-max of what is left; a stop id can be banned like any other token (HF
+does the same); everything else is untouched and composes with it.  A call whose every n is 0 makes exactly the ops calls it
+made before.  THE ROW KEEPS A TOKEN: the bans are dynamic, but a position bans at most one token per n-gram that starts in its
+history, so at most len(H), and no position of row b sees a history longer than bound_b = len(real[b]) + max_tokens_b +
+draft_len (0 at stage 0).  With gone_b the set of BAD WORDS' rule (permanent bans, the stop ids under min_tokens, the last ids
+of the row's bad words): a row without an allow-list needs |gone_b| + bound_b < V, a row with one |allowed_b - gone_b| >
+bound_b.  ValueError before any launch, naming the prompt: a bool, a float, None inside a sequence, the wrong length, a value
+outside [0, 8], a row that fails the rule above (raised once the prompts are encoded: the one check that needs their
+lengths), and a guided row with n > 0.  COST: profiles/no_repeat_ngram_step.json.  NOT BUILT: n > 0 on a guided row (a state's
+allowed set can be one token, which the rule may ban); HF's encoder-decoder variant; and serving/hierarchy.py's loop.
 
 GUIDED DECODING.  `generate(guided_fsm=, guided_choice=, guided_choice_per_prompt=)` (or StageConfig.guided_fsm / guided_choice; a
 keyword of None takes the configuration's value) is structured output: a row that must follow a grammar, or be one of a set of
@@ -252,7 +285,7 @@ top-N commit and penalty_commit: for a row that committed c > 0 tokens, column 0
 limits cut from the end), so column c - 1 already is the state behind them; a finished row (c = 0) keeps its state.  delta(s, t)
 is the edge's next state, else other[s]; where that is -1, or t lies outside the vocabulary -- which cannot happen, every
 proposal having been drawn from masked logits -- the state STAYS, so a row never loses its non-empty mask.  The order is mask ->
-fsm -> bad words -> edit -> penalties -> temperature; all five commute on a -inf.  Nothing is read back inside a step.  Draft and
+fsm -> bad words -> n-gram -> edit -> penalties -> temperature; all of them commute on a -inf.  Nothing is read back inside a step.  Draft and
 target receive the SAME mask from the SAME history at every position, so -- the argument of LOGIT EDITS, word for word -- the
 draft -> verify -> residual chain stays lossless against the grammar-restricted target distribution.  Consequences: the returned
 log-probs and top-N tables are those of the RESTRICTED distribution, unfillable top-N slots holding -1 / -inf as with allow-lists;
@@ -293,9 +326,9 @@ import torch
 from ..distributed import HipOps
 from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
-from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS,  # noqa: F401
+from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_NGRAM, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS,  # noqa: F401
                          _check_logprobs, _check_min_p, _check_stop_ids, _check_stop_sequences, _is_seq,
-                         check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_per_prompt,
+                         check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
                          check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
@@ -342,6 +375,7 @@ class StageConfig:
     presence_penalty: float = 0.0            # in [-2, 2]; 0: off
     frequency_penalty: float = 0.0           # in [-2, 2]; 0: off
     bad_words: Sequence = ()                 # words (strings / sequences of 1..8 token ids) no row may produce (module docstring, BAD WORDS)
+    no_repeat_ngram_size: int = 0            # in [0, 8]; 0: off (module docstring, NO REPEAT N-GRAM)
     guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
     guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
 
@@ -365,6 +399,7 @@ class _Plan(NamedTuple):
     edit_rows: list                          # every row's merged (id, bias, until) entries
     mask_rows: list                          # every row's allow-list: a sorted tuple of ids, or None
     bad_rows: list                           # every row's bad words: distinct tuples of 1..8 ids
+    ngram_rows: list                         # every row's no_repeat_ngram_size in [0, 8]; 0: off
     penalties: Optional[Tuple[list, list, list]]    # every row's repetition, presence and frequency penalty; None: all neutral
     fsm: Optional[CompiledFsm]               # the rows' guided automata in one state space (host arrays); None: no row is guided
     seeds: Optional[List[int]]
@@ -415,10 +450,28 @@ class _BadWordState:
         return self.ops.bad_words_rows(logits, self.packed, tokens, seq_len, self.start, self.cap, self.step_tok, n_prev)
 
 
+class _NgramState:
+    """What a generate call with a no_repeat_ngram_size keeps: the rows' n and the index of their first real prompt id on the
+    device (uploaded once), the size of the token buffer and, at a verifying stage, the call's [B, draft_len] buffer of the
+    step's proposals.  `apply` is the loops' one call per logits tensor, behind the bad words' and in front of the edit's;
+    nothing follows the commit: the operation reads `tokens` and keeps no state (module docstring, NO REPEAT N-GRAM)."""
+
+    def __init__(self, ops, ns, prompt_ids, P: int, cap: int, step_tok: Optional[torch.Tensor], device):
+        self.ops, self.cap, self.step_tok = ops, int(cap), step_tok
+        self.packed = ops.pack_no_repeat_ngram(ns, [len(r) for r in prompt_ids], int(P), device)
+
+    def apply(self, logits: torch.Tensor, tokens: torch.Tensor, seq_len: torch.Tensor, n_prev: int = 0) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], banned in place; seq_len: the step's lengths before its commit; position j sees the
+        step's first n_prev + j proposals behind the row's prompt and committed tokens."""
+        if self.step_tok is None:
+            return self.ops.no_repeat_ngram_rows(logits, self.packed, tokens, seq_len, self.cap)
+        return self.ops.no_repeat_ngram_rows(logits, self.packed, tokens, seq_len, self.cap, self.step_tok, n_prev)
+
+
 class _FsmState:
     """What a generate call with a guided row keeps: the call's automata and the rows' state columns on the device (uploaded
     once; rows with the same automaton and stop ids share one), and at a verifying stage the call's [B, draft_len] buffer of the
-    step's proposals (shared with _BadWordState and _PenaltyState).  `apply` is the loops' one call per logits tensor, directly
+    step's proposals (shared with _BadWordState, _NgramState and _PenaltyState).  `apply` is the loops' one call per logits tensor, directly
     behind the allow-list's; `advance` follows proposal k; `commit` follows the step's commit (module docstring, GUIDED
     DECODING)."""
 
@@ -738,10 +791,10 @@ class _SampledRows(_Sampled):
 class _CallState:
     """The device side of one generate call, built in this one place from the plan and the encoded prompts and handed to the
     loop: how rows end (`end`), the allow-list (`mask`, None without a list), the logit edit (`edit`, None without an entry), the
-    guided automata (`fsm`, None when no row is guided), the bad words (`bad`, None when no row has one), the penalties (`pen`,
-    None when every row is neutral), the sampler and the top-N tables (`top`, None when off).  `step_tok`: the [B, draft_len]
-    buffer of the step's proposals, ONE per call, which `fsm`, `bad` and `pen` all read at a verifying stage (None at stage 0,
-    and when all three are off).  Uploads happen here, once; a part
+    guided automata (`fsm`, None when no row is guided), the bad words (`bad`, None when no row has one), the n-gram rule
+    (`ngram`, None when every row's n is 0), the penalties (`pen`, None when every row is neutral), the sampler and the top-N
+    tables (`top`, None when off).  `step_tok`: the [B, draft_len] buffer of the step's proposals, ONE per call, which `fsm`,
+    `bad`, `ngram` and `pen` all read at a verifying stage (None at stage 0, and when all four are off).  Uploads happen here, once; a part
     that is off costs no launch.  `prompt_ids`: every row's prompt ids without the padding."""
 
     def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor, prompt_ids: List[List[int]]):
@@ -750,12 +803,14 @@ class _CallState:
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
         self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
-        history = any(plan.bad_rows) or bool(plan.penalties) or plan.fsm is not None
+        history = any(plan.bad_rows) or any(plan.ngram_rows) or bool(plan.penalties) or plan.fsm is not None
         self.step_tok = torch.zeros((B, stage.config.draft_len), dtype=torch.int32, device=dev) \
             if history and stage.draft is not None else None
         self.fsm = _FsmState(ops, plan.fsm, 1 if stage.draft is None else stage.config.draft_len + 1, self.step_tok, dev) \
             if plan.fsm is not None else None
         self.bad = _BadWordState(ops, plan.bad_rows, P, P + plan.max_tokens, self.step_tok, dev) if any(plan.bad_rows) else None
+        self.ngram = _NgramState(ops, plan.ngram_rows, prompt_ids, P, P + plan.max_tokens, self.step_tok, dev) \
+            if any(plan.ngram_rows) else None
         self.pen = _PenaltyState(ops, plan.penalties, prompt_ids, stage.shape.vocab, self.step_tok, dev) if plan.penalties else None
         # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
@@ -834,7 +889,8 @@ class Stage:
                  min_tokens=None, allowed_token_ids=None, repetition_penalty=None, presence_penalty=None,
                  frequency_penalty=None, bad_words=None,
                  bad_words_per_prompt=None, guided_fsm=None, guided_choice=None,
-                 guided_choice_per_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 guided_choice_per_prompt=None,
+                 no_repeat_ngram_size=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -904,18 +960,31 @@ class Stage:
         logits receive the same mask at every position, directly behind the allow-list's, and log-probs and top-N tables are
         those of the restricted distribution.  A row with both an automaton and choices, `min_tokens` > 0 on a guided row,
         more than 1024 states in a call, and a reachable state that the row's other restrictions leave without a token raise
-        ValueError (module docstring, GUIDED DECODING)."""
+        ValueError (module docstring, GUIDED DECODING).
+        `no_repeat_ngram_size` (HF generate's): None = StageConfig.no_repeat_ngram_size; an int in [0, 8] for every prompt or
+        one per prompt, 0: off.  With n > 0 no n-gram that ends in a row's generated tokens equals an earlier n-gram of its
+        prompt (the real ids, not the padding) plus generated tokens: at every position the tokens that followed an earlier
+        occurrence of the last n - 1 tokens of the history -- prompt, generated tokens, and the step's own proposals in front
+        of the position -- are banned; n = 1 bans every token of the history.  Draft and target logits receive the same ban,
+        behind the bad words and ahead of the edits and the penalties, and log-probs and top-N tables are those of the
+        distribution with the repeating tokens removed.  A row whose vocabulary (or allow-list) its bans and prompt length +
+        max_tokens + draft_len repeats could empty, and a guided row with n > 0, raise ValueError (module docstring, NO REPEAT
+        N-GRAM)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
                           stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
                           repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
-                          guided_choice, guided_choice_per_prompt)
+                          guided_choice, guided_choice_per_prompt, no_repeat_ngram_size)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
         ids, prompt_ids = self._encode(plan.prompts)
         P = ids.shape[1]
+        if any(plan.ngram_rows):                 # (the one check that needs the prompts' lengths: host lists, nothing launched yet)
+            check_ngram_rows_keep_a_token(plan.ngram_rows, [len(r) for r in prompt_ids], plan.limits,
+                                          0 if self.draft is None else self.config.draft_len, plan.mask_rows, plan.edit_rows,
+                                          plan.bad_rows, self.shape.vocab)
         state = _CallState(self, plan, ids, prompt_ids)
         decode = self._decode_plain if self.draft is None else self._decode_speculative
         tokens, lps, seq_len = decode(ids, plan.max_tokens, state)
@@ -935,7 +1004,7 @@ class Stage:
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
               repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm=None,
-              guided_choice=None, guided_choice_per_prompt=None) -> _Plan:
+              guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -977,6 +1046,10 @@ class Stage:
         check_rows_keep_a_token(mask_rows, edit_rows, bad_rows, V)
         fsm_rows = check_guided(given(guided_fsm, cfg.guided_fsm), given(guided_choice, cfg.guided_choice), guided_choice_per_prompt,
                                 n, V, self.tokenizer)
+        ngram_rows = check_no_repeat_ngram_size(given(no_repeat_ngram_size, cfg.no_repeat_ngram_size), n)
+        for b, (f, g) in enumerate(zip(fsm_rows, ngram_rows)):
+            if f is not None and g > 0:          # (a state's allowed set can be one token, which the n-gram rule may ban)
+                raise ValueError(f"prompt {b}: no_repeat_ngram_size > 0 is not built for a guided row")
         fsm = None
         if any(f is not None for f in fsm_rows):
             for b, (f, m) in enumerate(zip(fsm_rows, min_tokens)):
@@ -1007,8 +1080,8 @@ class Stage:
         return _Plan(prompts=prompts, limits=tuple(limits), max_tokens=int(limit), greedy=greedy,
                      inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
-                     edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, penalties=penalties, fsm=fsm, seeds=seeds,
-                     n_top=n_top)
+                     edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, ngram_rows=ngram_rows,
+                     penalties=penalties, fsm=fsm, seeds=seeds, n_top=n_top)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -1028,7 +1101,7 @@ class Stage:
         dev = ids.device
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm = st.fsm
+        fsm, ngram = st.fsm, st.ngram
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1042,7 +1115,9 @@ class Stage:
             if fsm is not None:
                 fsm.apply(logits)                                        # mask -> fsm: the state behind the committed tokens
             if bad is not None:
-                bad.apply(logits, tokens, seq_len)                       # mask -> bad words -> edit -> penalties
+                bad.apply(logits, tokens, seq_len)                       # mask -> bad words -> n-gram -> edit -> penalties
+            if ngram is not None:
+                ngram.apply(logits, tokens, seq_len)                     # the history: the prompt's real ids and the committed tokens
             if edit is not None:
                 edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
             if pen is not None:
@@ -1086,8 +1161,8 @@ class Stage:
         Kd = cfg.draft_len
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm = st.fsm
-        step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad` and `pen`; None: all off
+        fsm, ngram = st.fsm, st.ngram
+        step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
             m.reset()
@@ -1114,6 +1189,8 @@ class Stage:
                     fsm.apply(dl, k)                                    # the state behind the proposals 0 .. k - 1
                 if bad is not None:
                     bad.apply(dl, tokens, seq_len, k)                   # the history: the committed tokens, then proposals 0 .. k - 1
+                if ngram is not None:
+                    ngram.apply(dl, tokens, seq_len, k)                 # ... with the prompt's real ids in front
                 if edit is not None:
                     edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
                 if pen is not None:
@@ -1133,6 +1210,8 @@ class Stage:
                 fsm.apply(t_out)                                        # row j under the state the draft's proposal j had
             if bad is not None:
                 bad.apply(t_out, tokens, seq_len)                       # row j sees the proposals 0 .. j - 1, as the draft's did
+            if ngram is not None:
+                ngram.apply(t_out, tokens, seq_len)                     # the same history per row as the draft's proposal j had
             if edit is not None:
                 edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any slice
             if pen is not None:

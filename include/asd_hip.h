@@ -54,6 +54,10 @@ typedef enum asd_dtype {
 #define ASD_MAX_LOGIT_EDITS 1024 /* entries one row may own in asd_logit_edit_rows */
 #define ASD_MAX_BAD_WORDS 256  /* words one row may own in asd_bad_words_rows */
 #define ASD_MAX_BAD_WORD_LEN 8 /* tokens per word of asd_bad_words_rows */
+#define ASD_MAX_NGRAM 8        /* largest n of asd_no_repeat_ngram_rows */
+#ifndef ASD_NGRAM_SLICE        /* (tools/bench_no_repeat_ngram.py builds the kernel once more with one slice for any history) */
+#define ASD_NGRAM_SLICE 2048   /* n-gram starts one workgroup of asd_no_repeat_ngram_rows scans */
+#endif
 #define ASD_MAX_STAGES 16      /* L: tiers in the DP rule */
 #define ASD_MAX_SPLITS 64      /* vocab splits per row inside one launch */
 #define ASD_MAX_MLP_DIM 1024   /* predictor input / hidden width */
@@ -588,6 +592,55 @@ int asd_bad_words_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64
                        const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens, const int32_t* seq_len /*[B]*/,
                        int start, int max_len,
                        const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * No repeated n-gram AHEAD of the samplers -- HF generate's `no_repeat_ngram_size` (NoRepeatNGramLogitsProcessor).  The
+ * "words" of asd_bad_words_rows are given by the caller; here they are every n-gram of the row's own history, so the kernel
+ * scans the history instead of a table.  A row with banned elements is an ordinary input of every sampler ("no logit > -inf"
+ * must hold: a position bans at most len(H) - n + 1 tokens, which the host can bound before the call); applied alike, from the
+ * same history, to the draft's proposal rows and the target's K+1 rows, the draft -> verify -> residual chain stays lossless
+ * against the target distribution with the repeating tokens removed.
+ * logits: asd_bad_words_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only; K1 == 1 is a [B, V] matrix -- edited in
+ * place.
+ * n: ngram_n != NULL: int32 [B], sequence b has n = ngram_n[b]; 0 switches the row off, a value outside
+ * 1..ASD_MAX_NGRAM skips the row.  ngram_n == NULL: every sequence has n = n_shared, in 0..ASD_MAX_NGRAM.
+ * History: position j of sequence b has
+ *     H = tokens[b][row_start[b] .. L)  ++  step_tok[b][0 .. n_prev + j),      L = clamp(seq_len[b], start, max_len)
+ * tokens: int32 rows ld_tokens >= max_len elements apart, only read; seq_len[b] is the length as it stands BEFORE the step's
+ * commit.  `start` is the (padded) prompt length; row_start != NULL: int32 [B], the index of the row's first REAL prompt id,
+ * clamped into [0, start]: the prompt counts as history (as in HF for decoder-only models), the left-padding in front of it
+ * does not.  row_start == NULL: `start` for every row (no prompt in the history).  step_tok, ld_tok, n_tok, n_prev: as in
+ * asd_bad_words_rows -- a proposal row of draft slot k is K1 = 1 with n_prev = k, the target's K+1 rows are n_prev = 0, and
+ * row j of them sees the proposals 0 .. j-1; step_tok == NULL: no position sees a proposal, and n_prev must be 0.
+ * Semantics: for every i in [0, len(H) - n] with
+ *     H[i .. i+n-1) == H[len(H)-n+1 .. len(H))          (n - 1 tokens on either side)
+ * element H[i+n-1] of position (b, j) becomes -inf of the dtype (bits 0xFF80 bf16, 0xFC00 f16, -INFINITY f32, the ones
+ * asd_logit_edit_rows, asd_logit_mask_rows and asd_bad_words_rows write).  With n == 1 the compared run is empty: every token
+ * of H is banned.  With len(H) < n nothing is banned.  Nothing else is written: a matched element that is already -inf may be
+ * stored again, every other bit of the allocation stays as it was.  A rejected proposal never reaches `tokens`: nothing is
+ * rolled back, and the operation keeps no state.
+ * THE DATA CONTRACT: the launcher cannot check device data, so the kernel does: seq_len[b] is clamped into [start, max_len],
+ * row_start[b] into [0, start], a row with ngram_n[b] outside 1..ASD_MAX_NGRAM is skipped, and a history token outside [0, V)
+ * is compared as a plain integer but never used as a store index.
+ * One launch: a workgroup of 256 threads per (b, j) and per slice of ASD_NGRAM_SLICE n-gram starts (the number of slices
+ * follows max_len + n_tok, so a long context is not walked by one workgroup); each lane compares the LAST suffix token first
+ * and stores with ordinary per-lane vector-memory stores; several lanes and slices may store the same bits to one element, in
+ * either order the same result.  No atomics, no loop over the vocabulary, no LDS, no workspace, nothing waits on another
+ * workgroup.
+ * Status, in this order: negative B / K1 / V / n_shared / n_tok / n_prev / start / max_len: invalid argument; B, K1 or V == 0,
+ * or ngram_n == NULL with n_shared == 0: ASD_OK, nothing launched; unknown dtype, ngram_n == NULL with
+ * n_shared > ASD_MAX_NGRAM, n_tok > ASD_MAX_DRAFT_LEN, B*K1 > INT32_MAX, max_len + n_tok > INT32_MAX - 256: unsupported; NULL
+ * logits / tokens / seq_len, ld_row < V, ld_seq < K1*ld_row, ld_tokens < max_len, start > max_len, step_tok == NULL with
+ * n_prev != 0, step_tok != NULL with n_prev + K1 - 1 > n_tok or ld_tok < n_tok: invalid argument; logits not aligned to the
+ * element size, or ngram_n / row_start / tokens / seq_len / step_tok not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+int asd_no_repeat_ngram_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                             const int32_t* ngram_n /*[B], or NULL: n_shared for every row*/, int n_shared,
+                             const int32_t* row_start /*[B], or NULL: start for every row*/,
+                             const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens, const int32_t* seq_len /*[B]*/,
+                             int start, int max_len,
+                             const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance and asd_fsm_commit in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit and asd_no_repeat_ngram_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -496,6 +496,52 @@ int main() {
 #undef FMASK
 #undef FADV
 #undef FCOM
+    }
+
+    // ---- asd_no_repeat_ngram_rows: every rejection, and every "nothing to do", comes before the launch
+    {
+#define NGRAM(x_, dt_, lds_, ldr_, B_, K1_, V_, nn_, n_, rs_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_) \
+    asd_no_repeat_ngram_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, nn_, n_, rs_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_, nullptr)
+        const int K1 = 5;
+        int32_t* off = reinterpret_cast<int32_t*>(rows + 2);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, -1, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, -1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, -1, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, -1, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // n_shared
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, -1, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // start
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, -1, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // max_len
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, -1, 0), ASD_ERR_INVALID_ARG);   // n_tok
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);   // n_prev
+        EXPECT(NGRAM(p, BF16, K1 * V, V, 0, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);   // ... before the empty batch
+        EXPECT(NGRAM(nullptr, 99, 0, 0, 0, K1, V, nullptr, 3, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // B == 0
+        EXPECT(NGRAM(nullptr, 99, 0, 0, B, 0, V, nullptr, 3, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);    // K1 == 0
+        EXPECT(NGRAM(nullptr, 99, 0, 0, B, K1, 0, nullptr, 3, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // V == 0
+        EXPECT(NGRAM(nullptr, 99, 0, 0, B, K1, V, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // every row off
+        EXPECT(NGRAM(p, 99, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);     // dtype
+        EXPECT(NGRAM(p, -1, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, nullptr, ASD_MAX_NGRAM + 1, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 65, ASD_MAX_DRAFT_LEN + 1, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, INT64_C(1) << 31, i32, 4, INT32_MAX - 200, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);   // the scan counts in int32
+        EXPECT(NGRAM(nullptr, 99, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);  // ... before the NULL checks
+        EXPECT(NGRAM(nullptr, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, nullptr, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // tokens
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, nullptr, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // seq_len
+        EXPECT(NGRAM(p, BF16, K1 * V, V - 1, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // ld_row < V
+        EXPECT(NGRAM(p, BF16, K1 * V - 1, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);  // ld_seq < K1 ld_row
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 31, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);      // ld_tokens < max_len
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 33, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);     // start > max_len
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, nullptr, 0, 0, 1), ASD_ERR_INVALID_ARG);  // n_prev without step_tok
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 1), ASD_ERR_INVALID_ARG);      // position 4 would see 5 of 4
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 3, 4, 0), ASD_ERR_INVALID_ARG);      // ld_tok < n_tok
+        EXPECT(NGRAM(rows + 1, BF16, K1 * V, V - 1, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // ... before alignment
+        EXPECT(NGRAM(rows + 1, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);   // below the element size
+        EXPECT(NGRAM(rows + 2, 0 /*f32*/, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, nullptr, 0, 0, 0), ASD_ERR_ALIGNMENT);
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, off, 0, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // ngram_n
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, off, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // row_start
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, off, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // tokens
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, off, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // seq_len
+        EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, off, 4, 4, 0), ASD_ERR_ALIGNMENT);        // step_tok
+#undef NGRAM
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
