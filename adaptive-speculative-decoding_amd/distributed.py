@@ -381,6 +381,19 @@ class HipOps:
             t = self._ws[key] = self.K.TopLogprobs(Bv, K1, V, logits.dtype, int(n), logits.device)
         return t(logits, inv_temperature, splits)
 
+    @traced("prompt_logprobs")
+    def prompt_logprobs(self, logits, target, first, n, inv_temperature: float = 1.0, splits: int = 0):
+        """The log-prob and the rank of target[b, t] in every row of [B,T,V] logits and, with n >= 1, the rows' top-n tables
+        (asd_prompt_logprobs) -> (lp f32 [B,T], rank i32 [B,T], top_id i32 [B,T,n] | None, top_lp f32 [B,T,n] | None).  logits
+        and target may be strided views, nothing is copied; rows with t < first[b] are skipped.  One workspace per shape and
+        calling thread, like `top_logprobs`."""
+        Bv, T, V = logits.shape
+        key = ("prompt_logprobs", Bv, T, V, int(n), int(splits), str(logits.dtype), str(logits.device))
+        t = self._ws.get(key)
+        if t is None:
+            t = self._ws[key] = self.K.PromptLogprobs(Bv, T, V, logits.dtype, int(n), int(splits), logits.device)
+        return t(logits, target, first, inv_temperature)
+
     @traced("commit_top_logprobs")
     def commit_top_logprobs(self, top_id, top_lp, seq_len, n_commit, out_id, out_lp, max_len):
         """The step's top-N rows follow its commit (asd_commit_top_logprobs); runs behind commit_step_lp / commit_step_stop and

@@ -1089,6 +1089,67 @@ class TopLogprobs:
         return out
 
 
+class PromptLogprobs:
+    """asd_prompt_logprobs with its workspace: per row of [B, T, V] logits the log-prob and the rank of the token `target[b, t]`
+    and, with n >= 1, the row's top-n table (asd_top_logprobs' bits).  `logits` and `target` are read in place: strided views
+    with unit last stride, nothing is copied.  Rows with t < first[b] are skipped (lp 0, rank 0, ids -1, table -inf).  The
+    workspace is sized for the split count the launch uses at (B, T, V, dtype, splits), not for ASD_MAX_SPLITS."""
+
+    def __init__(self, B_: int, T: int, V: int, dtype: torch.dtype = torch.bfloat16, n: int = 0, splits: int = 0,
+                 device: Optional[torch.device] = None):
+        if isinstance(n, bool) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"n must be in [0, {MAX_TOP_LOGPROBS}]")
+        if dtype not in _DTYPE_CODE:
+            raise ValueError(f"unsupported logits dtype {dtype}")
+        self.B, self.T, self.V, self.dtype, self.n, self.splits = B_, T, V, dtype, int(n), int(splits)
+        self.device = device or torch.device("cuda")
+        with torch.cuda.device(self.device):       # splits == 0: the heuristic counts the CUs of the device that launches
+            self.bytes = int(_lib().asd_prompt_logprobs_workspace_bytes(B_, T, V, _DTYPE_CODE[dtype], self.splits))
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+
+    def __call__(self, logits: torch.Tensor, target: torch.Tensor, first: Optional[torch.Tensor] = None,
+                 inv_temperature: float = 1.0):
+        """-> (lp f32 [B,T], rank i32 [B,T], top_id i32 [B,T,n] | None, top_lp f32 [B,T,n] | None), fresh tensors."""
+        T, V, n = self.T, self.V, self.n
+        if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != self.dtype:
+            raise ValueError(f"logits must be a {self.dtype} CUDA (HIP) tensor; this package has no CPU path")
+        if logits.dim() != 3 or logits.shape[1] != T or logits.shape[2] != V or logits.stride(2) != 1:
+            raise ValueError(f"logits must be [B, {T}, {V}] with unit stride along V")
+        Bv = logits.shape[0]
+        if Bv != self.B:                           # the heuristic's split count, and with it the workspace, depends on B
+            raise ValueError(f"sized for B == {self.B}")
+        if not isinstance(target, torch.Tensor) or not target.is_cuda or target.dtype != torch.int32:
+            raise ValueError("target must be an int32 CUDA (HIP) tensor")
+        if tuple(target.shape) != (Bv, T) or (T > 1 and target.stride(1) != 1):
+            raise ValueError(f"target must be [B, {T}] with unit stride along T")
+        ld_target = target.stride(0) if Bv > 1 else T
+        if ld_target < T:
+            raise ValueError("target rows overlap: the row stride must be >= T")
+        if first is not None and tuple(first.shape) != (Bv,):
+            raise ValueError("first must be int32 [B]")
+        ld_seq, ld_row = _logit_strides(logits, T, rows="T")
+        lp = torch.empty((Bv, T), dtype=torch.float32, device=self.device)
+        rank = torch.empty((Bv, T), dtype=torch.int32, device=self.device)
+        top_id = torch.empty((Bv, T, n), dtype=torch.int32, device=self.device) if n else None
+        top_lp = torch.empty((Bv, T, n), dtype=torch.float32, device=self.device) if n else None
+        rc = _lib().asd_prompt_logprobs(logits.data_ptr(), _DTYPE_CODE[logits.dtype], ld_seq, ld_row, Bv, T, V,
+                                        target.data_ptr(), ld_target, _opt(first, "first", torch.int32), float(inv_temperature),
+                                        n, self.splits, lp.data_ptr(), rank.data_ptr(),
+                                        None if top_id is None else top_id.data_ptr(),
+                                        None if top_lp is None else top_lp.data_ptr(), self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_prompt_logprobs", rc)
+        return lp, rank, top_id, top_lp
+
+
+def prompt_logprobs(logits: torch.Tensor, target: torch.Tensor, first: Optional[torch.Tensor], n: int,
+                    inv_temperature: float = 1.0, splits: int = 0):
+    """One asd_prompt_logprobs call with a workspace of its own -> (lp, rank, top_id | None, top_lp | None); see PromptLogprobs."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise ValueError("logits must be a [B, T, V] tensor")
+    Bv, T, V = logits.shape
+    return PromptLogprobs(Bv, T, V, logits.dtype, n, splits, logits.device)(logits, target, first, inv_temperature)
+
+
 def commit_top_logprobs(top_id: torch.Tensor, top_lp: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor,
                         out_id: torch.Tensor, out_lp: torch.Tensor, max_len: Optional[int] = None) -> None:
     """The top-N rows of a step follow its commit (asd_commit_top_logprobs): out[b, seq_len[b] - n_commit[b] + j] = top[b, j]

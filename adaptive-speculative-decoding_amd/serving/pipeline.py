@@ -213,6 +213,9 @@ class PipelineConfig:
     # HF generate's no_repeat_ngram_size, handed to stage.generate(no_repeat_ngram_size=) unless the call names its own; None:
     # the keyword is not passed
     no_repeat_ngram_size: Optional[int] = None
+    # vLLM's prompt_logprobs (serving/stages.py, PROMPT LOG-PROBS), handed to every stage.generate(prompt_logprobs=): each
+    # stage's entry then carries "prompt_logprobs" and "prompt_ranks"; not fed to the predictor.  None: the keyword is not passed
+    prompt_logprobs: Optional[int] = None
 
     @classmethod
     def from_yaml(cls, path: str) -> "PipelineConfig":
@@ -246,6 +249,8 @@ class PipelineConfig:
             kw["stop_sequences"] = tuple(e if isinstance(e, str) else tuple(int(t) for t in e) for e in sec["stop_sequences"])
         if sec.get("no_repeat_ngram_size") is not None:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
+        if sec.get("prompt_logprobs") is not None:
+            kw["prompt_logprobs"] = int(sec["prompt_logprobs"])
         return cls(**kw)
 
 
@@ -593,6 +598,8 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["stop_sequences"] = list(cfg.stop_sequences)
                 if cfg.no_repeat_ngram_size is not None:                # (the call's own value, shared or per request, replaces it below)
                     stop_kw["no_repeat_ngram_size"] = int(cfg.no_repeat_ngram_size)
+                if cfg.prompt_logprobs is not None:
+                    stop_kw["prompt_logprobs"] = cfg.prompt_logprobs
                 # (limits likewise: one per request of the batch, or the batch's one int)
                 limit = [r.max_tokens for r in todo] if isinstance(max_tokens, list) else max_tokens
                 # (sampling parameters likewise: a list only where the batch carries one, so other calls are unchanged)
@@ -614,6 +621,9 @@ class AdaptiveSpeculativePipeline:
                     entry = {"output": texts[j], "logprobs": lp}
                     if tables is not None:                              # the [n_j, N] table takes the vector's place at the predictor
                         entry["top_logprobs"] = lp = tables[j]
+                    if cfg.prompt_logprobs is not None and "prompt_logprobs" in (stage_stats or {}):
+                        entry["prompt_logprobs"] = stage_stats["prompt_logprobs"][j]       # (kept with the entry, not predicted on)
+                        entry["prompt_ranks"] = stage_stats["prompt_ranks"][j]
                     gen_out[r.request_id] = (texts[j], lp)
                     if self.cache_manager:
                         self.cache_manager.allocate(r.request_id, i, entry)

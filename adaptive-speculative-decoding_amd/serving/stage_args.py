@@ -94,6 +94,15 @@ def _check_logprobs(n) -> int:
     return int(n)
 
 
+def _check_prompt_logprobs(n) -> Optional[int]:
+    """None: off.  An int in [0, MAX_TOP_LOGPROBS]: on (0: the tokens' own log-prob and rank, no table)."""
+    if n is None:
+        return None
+    if not _is_int(n) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"prompt_logprobs must be None or an integer in [0, {MAX_TOP_LOGPROBS}], got {n!r}")
+    return int(n)
+
+
 def _check_min_p(v, name: str = "min_p") -> float:
     if isinstance(v, bool) or not isinstance(v, _NUMBER) or not 0.0 <= float(v) <= 1.0:
         raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")           # (NaN included)

@@ -309,6 +309,31 @@ NOT BUILT: regex- or JSON-schema-to-automaton compilers (a caller hands over the
 on a guided row raises ValueError (its temporary ban of the stop ids can empty an accepting leaf); fusing the advance into the
 mask launch; and serving/hierarchy.py's loop.
 
+PROMPT LOG-PROBS.  `generate(prompt_logprobs=N)` (or StageConfig.prompt_logprobs; None takes the configuration's value, and None
+there is OFF) is vLLM's `SamplingParams(prompt_logprobs=N)`, OpenAI's `echo` + `logprobs`: the stage's model is scored on the
+given text -- the perplexity of a prompt, the log-likelihood of a fixed continuation, "how surprised is this stage by the
+request".  N is an int in [0, 8]; 0 is ON and returns the tokens' own log-prob and rank without a table (vLLM's meaning, and the
+reason "off" is None and not 0); a bool, a float, a sequence or a value outside the range raises ValueError before the prompts
+are encoded.  Both loops run the prefill through forward_ragged, which returns logits for every prompt position; they used to be
+dropped.  With the feature on a loop makes ONE ops.prompt_logprobs call (asd_prompt_logprobs: one streaming pass that keeps the
+row's log-sum-exp, gathers the logit of the NEXT prompt token, counts the logits that stand ahead of it and, with N >= 1, keeps
+asd_top_logprobs' table) directly behind the prefill pass that produced the logits and before the first decode pass (with
+graphs enabled the model's output is a buffer that the next replay overwrites): stage 0 on rows [:, :P-1] of its [B, P, V]
+result, a verifying stage on the target's whole [B, P-1, V] result, both read where they lie; `target` is the view ids32[:, 1:]
+and first[b] = P - (row b's real prompt tokens), so the rows of the left-padding are skipped and cost no pass.  The draft
+model's prefill is not scored.  WHAT IS SCORED: the RAW model distribution at temperature 1, ahead of the mask, the automata,
+the bad words, the n-gram rule, the edits and the penalties -- vLLM scores prompts on unprocessed logits too, and those
+operations describe generated text.  The left-padding is attended (PROMPTS, below), so a short prompt's numbers are conditioned
+on the padding in front of it; the longest prompt of a call has none.  Nothing is read back before the loop ends, the generator
+is not consumed, and the texts, log-probs and tables of the generated tokens keep their bits; with the feature off a call makes
+exactly the ops calls it made before.  RESULTS, with m_i = (row i's real prompt tokens) - 1 and entry j belonging to real prompt
+token j + 1 (the first real token has no log-prob, as in vLLM): stats["prompt_token_ids"][i] (int32 [m_i + 1], all real ids),
+stats["prompt_logprobs"][i] (float32 [m_i]), stats["prompt_ranks"][i] (int32 [m_i]; 1 = the most likely token, ties by lowest
+id: the table's order, so rank <= N means the token stands in slot rank - 1 with the same bits) and, with N >= 1,
+stats["prompt_top_token_ids"][i] (int32 [m_i, N]) / stats["prompt_top_logprobs"][i] (float32 [m_i, N]).  Off: none of the keys.
+COST: profiles/prompt_logprobs.json.  NOT BUILT: the [B, P, V] prefill logits are materialised as before -- chunking the prefill
+over positions is not part of this; the rank of GENERATED tokens; one N per request; and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -327,7 +352,7 @@ from ..distributed import HipOps
 from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
 from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_NGRAM, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS,  # noqa: F401
-                         _check_logprobs, _check_min_p, _check_stop_ids, _check_stop_sequences, _is_seq,
+                         _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
                          check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
@@ -378,6 +403,7 @@ class StageConfig:
     no_repeat_ngram_size: int = 0            # in [0, 8]; 0: off (module docstring, NO REPEAT N-GRAM)
     guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
     guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
+    prompt_logprobs: Optional[int] = None    # None: off; 0..8: the prompt tokens' log-probs and ranks, and a top-N table (PROMPT LOG-PROBS)
 
 
 _REASONS = {1: "stop", 2: "length"}
@@ -404,6 +430,7 @@ class _Plan(NamedTuple):
     fsm: Optional[CompiledFsm]               # the rows' guided automata in one state space (host arrays); None: no row is guided
     seeds: Optional[List[int]]
     n_top: int
+    n_prompt: Optional[int] = None           # prompt_logprobs: None off, else the table's N in [0, 8]
 
 
 class _EditState:
@@ -615,6 +642,40 @@ class _TopState:
         return dict(top_id=self.step[0].clone(), top_lp=self.step[1].clone())
 
 
+class _PromptState:
+    """What a generate call with prompt_logprobs = n keeps (module docstring, PROMPT LOG-PROBS): the scored tokens -- the view
+    ids32[:, 1:], row t scores prompt position t + 1 -- and every row's first scored position on the device, uploaded once.
+    `score` is the loops' ONE call, directly behind the prefill pass whose logits it reads; `stats` reads back after the loop."""
+
+    def __init__(self, ops, n: int, ids: torch.Tensor, prompt_ids: List[List[int]]):
+        P = ids.shape[1]
+        self.ops, self.n, self.P = ops, int(n), P
+        self.real = prompt_ids
+        self.target = ids.to(torch.int32)[:, 1:]
+        self.first = torch.tensor([P - len(r) for r in prompt_ids], dtype=torch.int32).to(ids.device)
+        self.out = None
+
+    def score(self, logits: torch.Tensor, keep: bool = False) -> Optional[dict]:
+        """logits: the prefill's rows 0 .. P - 2, [B, P - 1, V], read where they lie (a view; possibly a buffer that the next
+        pass overwrites, so this runs before it).  keep: the tests' record."""
+        self.out = self.ops.prompt_logprobs(logits, self.target, self.first, self.n)
+        return dict(logits=logits.clone(), target=self.target.clone(), first=self.first.clone()) if keep else None
+
+    def stats(self) -> dict:
+        """Entry j of row i belongs to its real prompt token j + 1; the first real token has no log-prob."""
+        lp, rank, top_id, top_lp = (None if t is None else t.cpu().numpy() for t in self.out)
+        m = [max(len(r) - 1, 0) for r in self.real]
+        tail = lambda a, i: np.ascontiguousarray(a[i, self.P - 1 - m[i]:])             # noqa: E731
+        rows = range(len(m))
+        out = {"prompt_token_ids": [np.asarray(r, dtype=np.int32) for r in self.real],
+               "prompt_logprobs": [tail(lp, i).astype(np.float32, copy=False) for i in rows],
+               "prompt_ranks": [tail(rank, i).astype(np.int32, copy=False) for i in rows]}
+        if self.n:
+            out["prompt_top_token_ids"] = [tail(top_id, i) for i in rows]
+            out["prompt_top_logprobs"] = [tail(top_lp, i) for i in rows]
+        return out
+
+
 # ---------------------------------------------------------------------------------------------- what a step draws with
 # What differs between greedy and sampled decoding, behind one interface; the loops hold everything else.
 #   draw(logits, step)   stage 0's step -> (n_acc, tok, lp) for the commit
@@ -793,7 +854,7 @@ class _CallState:
     loop: how rows end (`end`), the allow-list (`mask`, None without a list), the logit edit (`edit`, None without an entry), the
     guided automata (`fsm`, None when no row is guided), the bad words (`bad`, None when no row has one), the n-gram rule
     (`ngram`, None when every row's n is 0), the penalties (`pen`, None when every row is neutral), the sampler and the top-N
-    tables (`top`, None when off).  `step_tok`: the [B, draft_len] buffer of the step's proposals, ONE per call, which `fsm`,
+    tables (`top`, None when off) and the prompt's scores (`prompt`, None when off).  `step_tok`: the [B, draft_len] buffer of the step's proposals, ONE per call, which `fsm`,
     `bad`, `ngram` and `pen` all read at a verifying stage (None at stage 0, and when all four are off).  Uploads happen here, once; a part
     that is off costs no launch.  `prompt_ids`: every row's prompt ids without the padding."""
 
@@ -816,6 +877,7 @@ class _CallState:
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
         self.top = _TopState(ops, plan.n_top, plan.inv_t, B, P + plan.max_tokens, dev,
                              self.sampler.table if plan.rows else None) if plan.n_top else None
+        self.prompt = _PromptState(ops, plan.n_prompt, ids, prompt_ids) if plan.n_prompt is not None else None
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -851,6 +913,7 @@ class Stage:
         self.gen = torch.Generator(device=self.device).manual_seed(int(config.seed))
         self.keep_inputs = False                         # tests: keep every step's inputs and draws in `step_inputs`
         self.step_inputs: List[dict] = []
+        self.prompt_inputs: Optional[dict] = None        # tests: the prefill logits, targets and first rows a call scored
         self.last_steps = 0
 
     def get_model_info(self) -> Dict[str, object]:
@@ -890,7 +953,8 @@ class Stage:
                  frequency_penalty=None, bad_words=None,
                  bad_words_per_prompt=None, guided_fsm=None, guided_choice=None,
                  guided_choice_per_prompt=None,
-                 no_repeat_ngram_size=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 no_repeat_ngram_size=None,
+                 prompt_logprobs: Optional[int] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -969,13 +1033,23 @@ class Stage:
         behind the bad words and ahead of the edits and the penalties, and log-probs and top-N tables are those of the
         distribution with the repeating tokens removed.  A row whose vocabulary (or allow-list) its bans and prompt length +
         max_tokens + draft_len repeats could empty, and a guided row with n > 0, raise ValueError (module docstring, NO REPEAT
-        N-GRAM)."""
+        N-GRAM).
+        `prompt_logprobs` (vLLM's; OpenAI's echo + logprobs): None = StageConfig.prompt_logprobs, and None there is off; an int
+        N in [0, 8] scores the prompt under THIS stage's model, raw and at temperature 1.  With m_i = (row i's real prompt
+        tokens) - 1, entry j belongs to real prompt token j + 1 (the first has no log-prob): stats["prompt_token_ids"][i] (int32
+        [m_i + 1], all real ids), stats["prompt_logprobs"][i] (float32 [m_i]: log p(token | the tokens before it)),
+        stats["prompt_ranks"][i] (int32 [m_i]: 1 = the most likely token; ties by lowest id) and, with N >= 1,
+        stats["prompt_top_token_ids"][i] (int32 [m_i, N]) / stats["prompt_top_logprobs"][i] (float32 [m_i, N]), most likely
+        first.  N = 0 is ON and returns no table.  Off: none of the keys.  The generated tokens, their log-probs and tables
+        keep their bits; a bool, a float, a sequence or a value outside [0, 8] raises ValueError (module docstring, PROMPT
+        LOG-PROBS)."""
         t0 = time.perf_counter()
         self.step_inputs = []
+        self.prompt_inputs = None
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
                           stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
                           repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
-                          guided_choice, guided_choice_per_prompt, no_repeat_ngram_size)
+                          guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -999,12 +1073,14 @@ class Stage:
             id_h, tlp_h = state.top.ids[:, P:].cpu().numpy(), state.top.lps[:, P:].cpu().numpy()
             stats["top_token_ids"] = [np.ascontiguousarray(r[:n]) for r, n in zip(id_h, n_tok)]
             stats["top_logprobs"] = [np.ascontiguousarray(r[:n]) for r, n in zip(tlp_h, n_tok)]
+        if state.prompt is not None:
+            stats.update(state.prompt.stats())
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
               repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm=None,
-              guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None) -> _Plan:
+              guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1013,6 +1089,7 @@ class Stage:
         given = lambda v, default: default if v is None else v                       # noqa: E731
         stop = _check_stop_ids(given(stop_token_ids, cfg.stop_token_ids), V)
         n_top = _check_logprobs(given(logprobs, cfg.logprobs))
+        n_prompt = _check_prompt_logprobs(given(prompt_logprobs, cfg.prompt_logprobs))
         own_top_k, own_top_p, own_min_p = (cfg.top_k, cfg.top_p, cfg.min_p) if self.draft is None else \
             (cfg.target_top_k, cfg.target_top_p, cfg.target_min_p)
         min_p = check_per_prompt(given(min_p, own_min_p), n, "min_p")
@@ -1081,7 +1158,7 @@ class Stage:
                      inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
                      edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, ngram_rows=ngram_rows,
-                     penalties=penalties, fsm=fsm, seeds=seeds, n_top=n_top)
+                     penalties=penalties, fsm=fsm, seeds=seeds, n_top=n_top, n_prompt=n_prompt)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -1106,7 +1183,10 @@ class Stage:
         m = self.model
         m.reset()
         m.alloc_ragged(B, cap + 1)
-        logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)[:, -1]
+        logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)
+        if st.prompt is not None:                # rows 0 .. P - 2 score prompt tokens 1 .. P - 1: raw, ahead of every edit below
+            self.prompt_inputs = st.prompt.score(logits[:, :P - 1], self.keep_inputs)
+        logits = logits[:, -1]
         for step in range(max_tokens):
             if sampler.dense:
                 logits = logits.contiguous()
@@ -1168,7 +1248,10 @@ class Stage:
             m.reset()
             m.alloc_ragged(B, cap + Kd + 2)
         zero = torch.zeros((B,), dtype=torch.int64, device=dev)
-        target.forward_ragged(ids[:, :P - 1], zero, P)                  # prefill: everything but the last prompt token
+        prefill = target.forward_ragged(ids[:, :P - 1], zero, P)        # prefill: everything but the last prompt token
+        if st.prompt is not None:                # the target's [B, P - 1, V] rows, before the next pass; the draft's are not scored
+            self.prompt_inputs = st.prompt.score(prefill, self.keep_inputs)
+        del prefill
         if P > 2:
             draft.forward_ragged(ids[:, :P - 2], zero, P)
         rows = torch.arange(B, device=dev)

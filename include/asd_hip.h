@@ -443,6 +443,43 @@ int asd_top_logprobs_rows(const void* logits, int dtype, int64_t ld_seq, int64_t
                           const float* inv_temperature /*[B], device*/, int N, int splits,
                           int32_t* top_id /*[B,K1,N] out*/, float* top_lp /*[B,K1,N] out*/,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Prompt log-probs (SamplingParams(prompt_logprobs=N); OpenAI's echo + logprobs): per row of [B, T, V] logits the log-prob and
+ * the rank of ONE GIVEN token, and optionally the row's top-N table, in asd_top_logprobs' one streaming pass.
+ * logits: element (b, t, v) at b*ld_seq + t*ld_row + v (asd_top_logprobs' addressing), read in place, never written; any
+ * T >= 1 (no ASD_MAX_DRAFT_LEN limit; B*T*splits <= INT32_MAX).  target[b*ld_target + t] is the token row (b, t) scores.
+ * first: DEVICE array [B], or NULL for 0 everywhere.  Row (b, t) is SCORED when t >= first[b]; with x the stored row and
+ * g = target[b, t]:
+ *   lp[b,t]   = x[g]*inv_temperature - lse(x*inv_temperature): the operations of a table slot, so where the table lists g the
+ *               bits are equal.
+ *   rank[b,t] = 1 + #{v : x[v] > x[g], or x[v] == x[g] and v < g} over the stored values -- the table's total order (value
+ *               descending, then id ascending); exact, the same in every launch geometry.  A NaN element is never counted; a
+ *               -inf element takes part like any other value.  For x[g] > -inf: rank <= N  <=>  top_id[b,t,rank-1] == g, and
+ *               top_lp[b,t,rank-1] has lp's bits (the table itself never lists a -inf logit).
+ *   top_id / top_lp [b,t,:N]: what asd_top_logprobs writes for the row at the same inv_temperature, N and split count, bit
+ *               for bit.  N == 0: no table is kept or written; top_id / top_lp may be NULL.
+ *   g outside [0, V) is never dereferenced: lp = NaN, rank = 0, the table is written all the same.  A NaN x[g]: lp = NaN,
+ *   rank = 0.
+ * A SKIPPED row (t < first[b]: left-padding) costs no pass over its logits: lp = 0, rank = 0, ids -1, table log-probs -inf.
+ * splits: workgroups per row in [1, ASD_MAX_SPLITS], 0 = heuristic (asd_verify_greedy's).  The workspace is sized for the split
+ * count the launch USES (with splits == 0 the heuristic's choice on the current device; a host without a device counts 256
+ * CUs): asd_prompt_logprobs_workspace_bytes takes the same five values; whole rows (one slice) need 256 bytes.  Tickets are
+ * zeroed by the launcher ahead of every launch, as in asd_top_logprobs.
+ * Status, in this order: NULL lp / rank (NULL top_id / top_lp with N > 0), inv_temperature not > 0, negative sizes: invalid
+ * argument; B == 0 or T == 0: ASD_OK, nothing launched; V == 0: invalid argument; unknown dtype: unsupported;
+ * N > ASD_MAX_TOP_LOGPROBS, splits outside [0, ASD_MAX_SPLITS]: unsupported; NULL logits / target / workspace, ld_row < V,
+ * ld_seq < T*ld_row, ld_target < T: invalid argument; a row of 2 GiB or more: unsupported; logits not aligned to the element
+ * size: alignment; workspace misaligned (256): workspace; B*T*splits > INT32_MAX: unsupported; workspace too small: workspace.
+ * ---------------------------------------------------------------------------------------- */
+size_t asd_prompt_logprobs_workspace_bytes(int B, int T, int V, int dtype, int splits);   /* a multiple of 256; 256 for empty or invalid sizes */
+int asd_prompt_logprobs(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int T, int V,
+                        const int32_t* target /*[B, ld_target]: target[b*ld_target + t] is the token row (b, t) scores*/,
+                        int64_t ld_target, const int32_t* first /*[B], or NULL: 0 for every sequence*/,
+                        float inv_temperature, int N /*0..ASD_MAX_TOP_LOGPROBS*/, int splits /*0 = heuristic*/,
+                        float* lp /*[B,T]*/, int32_t* rank /*[B,T]*/,
+                        int32_t* top_id /*[B,T,N]; may be NULL when N == 0*/, float* top_lp /*likewise*/,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* The table of a step follows the step's commit (RESEARCH_PROTOCOL.md:272-277: one [N] row per GENERATED token).  Runs behind
  * asd_commit_step_lp / asd_commit_step_stop of the same step and reads their outputs: seq_len[b] AFTER the commit and
  * n_commit[b].  For j < min(n_commit[b], K1):  out[b, seq_len[b] - n_commit[b] + j, :] = top[b, j, :]  (ids and log-probs;

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit and asd_no_repeat_ngram_rows in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows and asd_prompt_logprobs in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -542,6 +542,59 @@ int main() {
         EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, off, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // seq_len
         EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, off, 4, 4, 0), ASD_ERR_ALIGNMENT);        // step_tok
 #undef NGRAM
+    }
+
+    // ---- asd_prompt_logprobs: the header's order (NULL outputs and the temperature, sizes, the empty batch, dtype, N / splits,
+    // pointers and strides, a 2 GiB row, alignment, the workspace) and the size query, which is sized for the splits in use
+    {
+        const int T = 70, VP = 1000, NP = 5;
+        const int64_t ldr = VP, lds = static_cast<int64_t>(T) * VP, ldt = T;
+        const size_t ws64 = asd_prompt_logprobs_workspace_bytes(B, T, VP, BF16, ASD_MAX_SPLITS);
+        const size_t ws2 = asd_prompt_logprobs_workspace_bytes(B, T, VP, BF16, 2);
+        if (ws64 % 256 != 0 || ws2 % 256 != 0 || ws2 >= ws64 || asd_prompt_logprobs_workspace_bytes(B, T, VP, BF16, 1) != 256 ||
+            asd_prompt_logprobs_workspace_bytes(0, T, VP, BF16, 0) != 256 || asd_prompt_logprobs_workspace_bytes(B, T, VP, 99, 0) != 256 ||
+            asd_prompt_logprobs_workspace_bytes(32, 2047, 152064, BF16, 0) >= (size_t{1} << 20)) {
+            std::printf("FAIL prompt_logprobs workspace sizes %zu %zu\n", ws2, ws64);
+            ++failures;
+        }
+#define PROMPT(x_, dt_, lds_, ldr_, B_, T_, V_, tg_, ldt_, first_, inv_t_, N_, splits_, lp_, rank_, id_, tlp_, ws_, wsb_) \
+    asd_prompt_logprobs(x_, dt_, lds_, ldr_, B_, T_, V_, tg_, ldt_, first_, inv_t_, N_, splits_, lp_, rank_, id_, tlp_, ws_, wsb_, nullptr)
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, nullptr, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);     // lp
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, nullptr, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);     // rank
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, nullptr, f32, p, ws64), ASD_ERR_INVALID_ARG);     // top_id with N > 0
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, nullptr, p, ws64), ASD_ERR_INVALID_ARG);     // top_lp with N > 0
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, 0, 2, f32, i32, nullptr, nullptr, p, 0), ASD_ERR_WORKSPACE);       // N == 0 needs no table
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 0.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);         // temperature
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, NAN, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(PROMPT(p, BF16, lds, ldr, -1, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);        // negative sizes
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, -1, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, -1, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, -1, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(PROMPT(nullptr, 99, 0, 0, 0, T, VP, nullptr, 0, nullptr, 1.0f, 99, 99, nullptr, nullptr, nullptr, nullptr, nullptr, 0), ASD_OK);   // B == 0: nothing launched
+        EXPECT(PROMPT(p, BF16, 0, ldr, B, 0, VP, i32, 0, i32, 1.0f, NP, 0, nullptr, nullptr, nullptr, nullptr, p, 0), ASD_OK);             // T == 0 likewise
+        EXPECT(PROMPT(p, BF16, 0, 0, B, T, 0, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);              // V == 0
+        EXPECT(PROMPT(p, 99, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);           // dtype
+        EXPECT(PROMPT(p, 99, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, ASD_MAX_TOP_LOGPROBS + 1, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, ASD_MAX_TOP_LOGPROBS + 1, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // N
+        EXPECT(PROMPT(p, BF16, lds, ldr - 1, B, T, VP, i32, ldt, i32, 1.0f, ASD_MAX_TOP_LOGPROBS + 1, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // ... before the strides
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, -1, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);        // splits
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, ASD_MAX_SPLITS + 1, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);
+        EXPECT(PROMPT(nullptr, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // logits
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, nullptr, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);     // target
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, nullptr, ws64), ASD_ERR_INVALID_ARG);   // workspace
+        EXPECT(PROMPT(p, BF16, lds, ldr - 1, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);     // ld_row < V
+        EXPECT(PROMPT(p, BF16, lds - 1, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);     // ld_seq < T ld_row
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt - 1, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);     // ld_target < T
+        EXPECT(PROMPT(rows + 1, BF16, lds, ldr, B, T, VP, i32, ldt - 1, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // ... before alignment
+        EXPECT(PROMPT(rows + 1, BF16, static_cast<int64_t>(T) << 30, int64_t{1} << 30, B, T, 1 << 30, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // a 2 GiB row, before alignment
+        EXPECT(PROMPT(rows + 1, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_ALIGNMENT);    // below the element size
+        EXPECT(PROMPT(rows + 2, 0 /*f32*/, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, p, ws64), ASD_ERR_ALIGNMENT);
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 0, f32, i32, i32, f32, rows + 16, ws64), ASD_ERR_WORKSPACE);   // misaligned workspace
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, ASD_MAX_SPLITS, f32, i32, i32, f32, p, ws64 - 1), ASD_ERR_WORKSPACE);   // too small
+        EXPECT(PROMPT(p, BF16, lds, ldr, B, T, VP, i32, ldt, i32, 1.0f, NP, 2, f32, i32, i32, f32, p, ws2 - 1), ASD_ERR_WORKSPACE);
+        EXPECT(PROMPT(rows + 2, BF16, lds, ldr, B, T, VP, i32, ldt, nullptr, 1.0f, NP, 1, f32, i32, i32, f32, p, 255), ASD_ERR_WORKSPACE); // (an element-aligned base and a NULL `first` are valid)
+        EXPECT(PROMPT(p, BF16, int64_t{VP} << 10, ldr, 1 << 20, 1 << 10, VP, i32, 1 << 10, i32, 1.0f, NP, 4, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // B*T*splits > INT32_MAX
+#undef PROMPT
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
