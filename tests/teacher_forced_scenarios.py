@@ -3,7 +3,8 @@ generate call below is checked by tests/teacher_forced_ref.py::check from what i
 ones of tests/stage_scenario.py (vocabulary 1000, 5 prompts, 12 tokens, draft_len 4).  "13b" shares its draft's weights and
 verifies untruncated what the draft proposed under top_p = 0.9: its steps accept 0 .. 4 proposals, so partial acceptances, whole
 blocks and bonus rows all occur there.  "34b" and its draft are unrelated random models: its steps accept next to nothing, which
-is the path on which every token is a residual draw and every proposal's KV entry is overwritten.
+is the path on which every token is a residual draw and every proposal's KV entry is overwritten.  The scenarios behind
+everything() add guided rows, no_repeat_ngram_size (on the same stages at vocabulary 64, where bans are live) and prompt_logprobs.
 
 TEST INFRASTRUCTURE: never importable from the package."""
 from tests.logit_edit_ref import SEEDS
@@ -89,6 +90,168 @@ def everything(stage, lp_bar, prompts=PROMPTS, max_tokens=MAX_TOKENS, **extra):
     assert recurring(gens) and all(ban not in g for g in gens)
     assert all((i < 0) == (j >= 4) for row in out[2]["top_token_ids"][3] for j, i in enumerate(row))   # the 4-token list: slot 4 unfillable
     return rep
+
+
+# ------------------------------------------------------------------------------------------ guided rows, n-gram bans, prompt log-probs
+STOP = 2
+A, B_TOK, C = 40, 41, 43
+CHOICES = [(5, 17, 300), (5, 17), (5, 900, 31, 32)]                              # (5, 17): an inner accepting node
+OTHER_CHOICES = [(640, 3), (11,), (640, 4, 4, 4)]
+GUIDED_HOW = ("defaults", "all", "mixed", "sync1", "sync4", "greedy")
+
+
+def guided_cases(names):
+    """(stage, how) of the guided scenario: "all" is TARGET truncation, so it runs on the verifying stages."""
+    return [(name, how) for name in names for how in GUIDED_HOW if how != "all" or name != names[0]]
+
+
+def _fsms():
+    """-> (A, a free token that is not B_TOK, a second free token, C, then only the stop id: `other` states and a forbidden edge;
+    a chain of 13 free tokens, B_TOK forbidden in each, whose only accepting state lies behind them: 12 tokens cut it)."""
+    from asd_amd.serving.guided import TokenFSM
+    free = TokenFSM(5, 0, [{A: 1}, {B_TOK: -1}, {}, {C: 4}, {}], [-1, 2, 3, -1, -1], accepting=[4])
+    long = TokenFSM(14, 0, [{B_TOK: -1}] * 13 + [{}], list(range(1, 14)) + [-1], accepting=[13])
+    return free, long
+
+
+def cycle3(V):
+    """A three-state TokenFSM over the whole vocabulary: the token at generated position i is congruent to i mod 3.  Every state
+    allows another third of the ids, so a state that is one transition off forbids the token the row should produce; every
+    state is accepting, so a stop id may end the row anywhere."""
+    from asd_amd.serving.guided import TokenFSM
+    return TokenFSM(3, 0, [{t: (s + 1) % 3 for t in range(s, V, 3)} for s in range(3)], accepting=[0, 1, 2])
+
+
+def guided(stage, lp_bar, how):
+    """Seeded, logprobs = 5 (a choice row allows one or two tokens: unfillable slots), a different kind of row per prompt:
+    choices one of which is a prefix of another; a free row; a general TokenFSM; a second choice list; a TokenFSM that
+    max_tokens cuts ("length").  `how`: the stage's defaults (stage 0's top_p = 0.9); "all": the stage's own top-k, top-p and
+    min-p together; the rows route MIXED; sync_every 1 and 4; greedy."""
+    free, long = _fsms()
+    kw = dict(KW, seed=SEEDS, logprobs=5, stop_token_ids=[STOP], guided_fsm=[None, None, free, None, long],
+              guided_choice_per_prompt=[CHOICES, None, None, OTHER_CHOICES, None])
+    kw.update(TARGET_TRUNCATION["all"] if how == "all" else MIXED if how == "mixed" else dict(temperature=0.0) if how == "greedy" else {})
+    if how == "greedy":
+        del kw["seed"]
+    old = stage.config.sync_every
+    stage.config.sync_every = {"sync1": 1, "sync4": 4}.get(how, old)
+    try:
+        (texts, _, st), rep = run_checked(stage, lp_bar, label(stage, "guided " + how), **kw)
+    finally:
+        stage.config.sync_every = old
+    gens = [text_ids(t) for t in texts]
+    assert st["finish_reasons"][0] == st["finish_reasons"][2] == st["finish_reasons"][3] == "stop", st["finish_reasons"]
+    assert st["finish_reasons"][4] == "length" and len(gens[4]) == MAX_TOKENS and B_TOK not in gens[4]
+    assert (gens[2][0], gens[2][3:]) == (A, [C, STOP]) and gens[2][1] != B_TOK
+    assert all(i < 0 for row in st["top_token_ids"][0] for i in row[2:])         # a choice row: at most two tokens are allowed
+    return rep
+
+
+NGRAM_VOCAB = 64                                 # a manager at this vocabulary, as the feature's own stage tests: bans are live
+NGRAM_ROWS = [2, 0, 3, 1, 8]
+NGRAM_RECUR = 7
+NGRAM_LIMITS = [MAX_TOKENS, MAX_TOKENS, 32, MAX_TOKENS, MAX_TOKENS]              # the n = 3 row: up to ngram_ref.NG_MAX_TOKENS
+
+
+def ngram(stage, lp_bar, greedy):
+    """One n per prompt and a bias that makes a token recur, on a stage of vocabulary 64.  Liveness comes from the f64 reference
+    alone (teacher_forced_ref: positions whose ban removes more mass than the bound): at least 3 on the n = 1 row and on the
+    n = 2 row; -> the figures, whose n = 3 row the caller sums over the scenario."""
+    assert stage.shape.vocab == NGRAM_VOCAB
+    kw = dict(prompts=PROMPTS, max_tokens=NGRAM_LIMITS, no_repeat_ngram_size=NGRAM_ROWS, logit_bias={NGRAM_RECUR: 4.0},
+              **(dict(temperature=0.0) if greedy else dict(temperature=TEMPERATURE, seed=SEEDS)))
+    _, rep = run_checked(stage, lp_bar, label(stage, "n-gram greedy" if greedy else "n-gram"), **kw)
+    live = rep["ngram_live"]
+    assert live[3] >= 3 and live[0] >= 3 and live[1] == 0, live
+    return rep
+
+
+def everything_now(stage, lp_bar, prompts=PROMPTS, max_tokens=MAX_TOKENS, **extra):
+    """everything()'s call with the three later features: row 0 follows a TokenFSM (cycle3; it has no min_tokens and
+    no n), rows 1, 2 and 4 have n = 2, 3 and 1 (row 3's four-token list is smaller than any n-gram bound), and
+    prompt_logprobs = 5.  Log-probs, generated tables, ends, prompt log-probs, ranks and prompt tables are checked."""
+    n, V = len(prompts), stage.shape.vocab
+    short = [RECUR, 5, 6, 7]
+    allowed = [None if b == 1 else short if b == 3 else sorted(set(range(b % 2, V, 2)) | {RECUR}) for b in range(n)]
+    kw = dict(prompts=prompts, max_tokens=max_tokens, temperature=TEMPERATURE, seed=SEEDS[:n], logprobs=5,
+              allowed_token_ids=allowed, logit_bias=RECUR_BIAS, **{k: v[:n] for k, v in PENALTIES.items()},
+              guided_fsm=[cycle3(V), None, None, None, None][:n], no_repeat_ngram_size=[0, 2, 3, 0, 1][:n],
+              prompt_logprobs=5, **extra)
+    (texts, _, _), _ = run_checked(stage, lp_bar, label(stage, "everything now: free run"), **kw)
+    free = [text_ids(t) for t in texts]
+    words = [[] if b == 3 else [(g[-1],), tuple(g[0:2]), tuple(g[2:5])] for b, g in enumerate(free)]
+    outside = [t for g in free for t in g if t != RECUR and t not in short]
+    # (the stop id is no last id of a bad word of the guided row: the state behind it would keep no token, which generate refuses)
+    stop = next(t for t in outside[3:] if t not in {w[-1] for w in words[0]})
+    ban = next(t for t in outside[4:] if t != stop)
+    out, rep = run_checked(stage, lp_bar, label(stage, "everything now"), **kw, bad_words_per_prompt=words, stop_token_ids=[stop],
+                           banned_token_ids=[ban], min_tokens=[0, 3, 5, 1, 2][:n])
+    gens = [text_ids(t) for t in out[0]]
+    assert recurring(gens) and all(ban not in g for g in gens)
+    assert all((i < 0) == (j >= 4) for row in out[2]["top_token_ids"][3] for j, i in enumerate(row))   # the 4-token list: slot 4 unfillable
+    body = gens[0][:-1] if out[2]["finish_reasons"][0] == "stop" else gens[0]   # (every state is accepting: the stop id ends it anywhere)
+    assert all(t % 3 == i % 3 for i, t in enumerate(body))                       # the automaton
+    return rep
+
+
+PROMPT_HOW = ((0, "sampled"), (3, "sampled"), (8, "sampled"), (3, "greedy"), (3, "processors"))
+
+
+def prompt(stage, lp_bar, n, how, **extra):
+    """prompt_logprobs = n on PROMPTS (rows with m = 0 and m = 1): sampled and seeded, greedy, and with processors on -- the
+    prompt's numbers are the raw model's regardless."""
+    kw = dict(KW, prompt_logprobs=n, **extra)
+    if how == "greedy":
+        kw["temperature"] = 0.0
+    else:
+        kw["seed"] = SEEDS
+    if how == "processors":
+        V = stage.shape.vocab
+        kw.update(allowed_token_ids=[t for t in range(V) if t % 4 != 1], logit_bias=RECUR_BIAS, no_repeat_ngram_size=2, **PENALTIES)
+    (_, _, st), rep = run_checked(stage, lp_bar, label(stage, f"prompt_logprobs {n} {how}"), **kw)
+    m = [len(v) for v in st["prompt_logprobs"]]
+    assert 0 in m and 1 in m and max(m) > 2 and rep["prompt_entries"] == sum(m), m
+    return rep
+
+
+def edge_now(make_manager, lp_bar, which):
+    """The edges of the loop, crossed with a guided row, n-gram rows and prompt_logprobs = 2.  With one row the guided call and
+    the n-gram call are two."""
+    margs, gargs = EDGES[which]
+    sm = make_manager(**margs)
+    reps = []
+    for name in sm.names:
+        stage = sm.get_stage(name)
+        kw = {**KW, "seed": SEEDS, "logit_bias": RECUR_BIAS, "stop_token_ids": [STOP], "prompt_logprobs": 2, **gargs}
+        B = len(kw["prompts"])
+        calls = [dict(guided_fsm=[cycle3(stage.shape.vocab), None, None, None, None][:B], no_repeat_ngram_size=[0, 1, 0, 2, 3][:B])]
+        if B == 1:
+            calls.append(dict(no_repeat_ngram_size=[1]))
+        for more in calls:
+            (_, _, st), rep = run_checked(stage, lp_bar, label(stage, which + " now"), **kw, **more)
+            reps.append(rep)
+            kept = [[i % stage.shape.vocab for i in stage.tokenizer.encode(p, return_tensors=None)] for p in kw["prompts"]]
+            if which == "max_prompt_tokens_3":                                   # the prompt's kept ids are its last 3
+                kept = [r[-3:] for r in kept]
+                assert any(len(r) == 3 for r in kept)
+            assert [v.tolist() for v in st["prompt_token_ids"]] == kept
+    return sm, reps
+
+
+def back_to_back_now(stage, lp_bar):
+    """One manager: everything_now -> a plain seeded call -> guided.  The plain call holds no prompt key (the check asserts it),
+    and a state or a ban left over would move its log-probs off the plain reference."""
+    everything_now(stage, lp_bar)
+    (_, _, st), _ = run_checked(stage, lp_bar, label(stage, "a plain call behind everything now"), **dict(KW, prompts=PROMPTS[:3], seed=SEEDS[:3]))
+    assert not [k for k in st if k.startswith("prompt_") or k.startswith("top_")], sorted(st)
+    guided(stage, lp_bar, "defaults")
+
+
+def bf16_now(stage, lp_bar):
+    """The default (bfloat16) stages under everything_now and prompt and the same formulas: coarse, as bf16() says; stage 0 at
+    top_p = 1 for the reason given there."""
+    extra = dict(top_p=1.0) if stage.draft is None else {}
+    return everything_now(stage, lp_bar, **extra), prompt(stage, lp_bar, 3, "sampled", **extra)
 
 
 def greedy(stage, lp_bar):
