@@ -29,7 +29,7 @@ asan-host:        ## host side of the launchers under AddressSanitizer + UBSan (
 	ASAN_OPTIONS=detect_leaks=0:detect_odr_violation=0:verify_asan_link_order=0:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(PY) -m pytest tests/test_abi.py -q -p no:cacheprovider
 
-asan-host-args:   ## stand-alone program (its own main, no Python): the argument checks of asd_residual_sample_lp / asd_commit_step_lp / asd_commit_step_stop / asd_commit_step_finish / asd_verify_greedy / asd_top_logprobs / asd_commit_top_logprobs / asd_step_uniforms / asd_logit_edit_rows / asd_logit_mask_rows / asd_penalty_rows / asd_penalty_commit / asd_bad_words_rows / asd_fsm_mask_rows / asd_fsm_advance / asd_fsm_commit / asd_no_repeat_ngram_rows / asd_prompt_logprobs under ASan + UBSan
+asan-host-args:   ## stand-alone program (its own main, no Python): the argument checks of asd_residual_sample_lp / asd_commit_step_lp / asd_commit_step_stop / asd_commit_step_finish / asd_verify_greedy / asd_top_logprobs / asd_commit_top_logprobs / asd_step_uniforms / asd_logit_edit_rows / asd_logit_mask_rows / asd_penalty_rows / asd_penalty_commit / asd_bad_words_rows / asd_fsm_mask_rows / asd_fsm_advance / asd_fsm_commit / asd_no_repeat_ngram_rows / asd_prompt_logprobs / asd_token_stats under ASan + UBSan
 	$(PY) adaptive-speculative-decoding_amd/build.py --asan
 	/opt/rocm/lib/llvm/bin/clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude tools/asan_host_args.cpp \
 	  -Ladaptive-speculative-decoding_amd/lib -lasd_hip_asan -L/opt/rocm/lib -lamdhip64 \

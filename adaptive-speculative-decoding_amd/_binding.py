@@ -107,6 +107,8 @@ SIGNATURES = {
     "asd_top_logprobs": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "asd_prompt_logprobs_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "asd_prompt_logprobs": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "asd_token_stats_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "asd_token_stats": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "asd_top_logprobs_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "asd_commit_step_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i,
                                     _vp]),

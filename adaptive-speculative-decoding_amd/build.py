@@ -35,7 +35,8 @@ SOURCES = {
     "greedy.hip": ["-ffp-contract=off"],          # lp_argmax / lp_target end in finish_row's arithmetic, as verify_accept.hip's do
     "top_logprobs.hip": ["-ffp-contract=off"],    # greedy.hip's (m2, s) stream and row_logprob: slot 0 has lp_argmax's bits
     "prompt_logprobs.hip": ["-ffp-contract=off"], # top_logprobs.hip's pass (top_logprobs_device.hpp) and its flags: the same bits
-    "philox.hip": [],                             # integer arithmetic and one exact conversion: no flag changes its bits
+    "token_stats.hip": ["-ffp-contract=off"],     # the same pass again (mode kStats): slot 0 and the table keep top_logprobs.hip's bits
+    "philox.hip": [],                            # integer arithmetic and one exact conversion: no flag changes its bits
     "logit_edit.hip": [],                         # one f32 addition and one conversion per edited element: nothing to contract
     "logit_mask.hip": [],                         # bit tests and stores of a constant: no floating-point arithmetic at all
     "bad_words.hip": [],                          # integer compares and stores of a constant: no floating-point arithmetic at all

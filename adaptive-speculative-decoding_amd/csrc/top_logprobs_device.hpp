@@ -1,6 +1,7 @@
-// top_logprobs_device.hpp -- the device parts of the row-streaming top-N pass, shared by top_logprobs.hip (the table alone) and
-// prompt_logprobs.hip (the table, plus the log-prob and the rank of one given token per row): the per-lane list, wave_bound,
-// wave_top, the merges, the ticket hand-off and the workspace layout.  top_logprobs.hip's header describes them.  One row body,
+// top_logprobs_device.hpp -- the device parts of the row-streaming top-N pass, shared by top_logprobs.hip (the table alone),
+// prompt_logprobs.hip (the table, plus the log-prob and the rank of one given token per row) and token_stats.hip (the table, the
+// rank of the step's committed token and the row's entropy): the per-lane list, wave_bound, wave_top, the merges, the ticket
+// hand-off and the workspace layout.  top_logprobs.hip's header describes them.  One row body,
 // top_logprobs_row<DT, kRows, kMode>; what a mode adds stands under `if constexpr`, so kTopOnly is the pass as it was.
 #pragma once
 
@@ -31,14 +32,18 @@ struct __attribute__((aligned(16))) SlicePartial {
     float m2, s;
     float v[kTop];
     int i[kTop];
-    int count;                // kScore*: the slice's share of the target's rank; 0 otherwise
-    int pad;
+    int count;                // kScore* / kStats: the slice's share of the target's rank; 0 otherwise
+    int pad;                  // kStats: the bits of the slice's entropy sum u (below); 0 otherwise
 };
 static_assert(sizeof(SlicePartial) == 80, "SlicePartial");
 
 // what the row body does beside the lse: the table alone (asd_top_logprobs), the table and one scored token per row, or the
 // scored token alone (asd_prompt_logprobs with N >= 1 / N == 0: no list is kept)
-constexpr int kTopOnly = 0, kScoreTop = 1, kScoreOnly = 2;
+// kStats / kStatsOnly (asd_token_stats with N >= 1 / N == 0): the rank of the row's committed token and the third running sum of
+// the entropy, beside the table / beside the arg-max alone (slot 0 of a list of one: the same element, so the same bits)
+constexpr int kTopOnly = 0, kScoreTop = 1, kScoreOnly = 2, kStats = 3, kStatsOnly = 4;
+constexpr bool keeps_list(int mode) { return mode == kTopOnly || mode == kScoreTop || mode == kStats; }
+constexpr bool keeps_stats(int mode) { return mode == kStats || mode == kStatsOnly; }
 
 struct TopParams {
     const void* logits;
@@ -58,6 +63,15 @@ struct PromptParams : TopParams {
     const int32_t* first;     // [B] or nullptr
     float* lp;
     int32_t* rank;
+};
+// asd_token_stats: row j of sequence b is live while j <= a = clamp(n_acc[b], 0, K1 - 1) and scores tok[b, j] (j < a) or drawn[b]
+struct StatsParams : TopParams {
+    const int32_t* tok;       // [B, K1 - 1] or nullptr (K1 == 1)
+    int64_t ld_tok;
+    const int32_t* n_acc;     // [B]
+    const int32_t* drawn;     // [B]
+    int32_t* stat_id;         // [B, K1, 2]: rank, arg-max id
+    float* stat_val;          // [B, K1, 2]: entropy (nats), log-prob of the arg-max
 };
 
 // the scored token of a row: its id and its stored value (both uniform: scalar registers), and the count of the elements that
@@ -166,14 +180,74 @@ __device__ __forceinline__ void wave_top(Top& t, Top& out) {
     }
 }
 
+// ---- kStats: the entropy's running sum.  Beside (m2, s) a partial carries u = sum_v e_v (x_v c2 - m2) with e_v = 2^(x_v c2 - m2),
+// the terms of s weighted by their own exponents, so that H = -sum p ln p = ln2 (log2 s - u / s) at any m2.  The weights are
+// differences from the running maximum (<= 0, and small where the mass is), which keeps the sum well conditioned when biases of
+// +-100 have moved the logits; moving a partial from m2 to M >= m2 is u' = 2^(m2 - M) (u + (m2 - M) s).  An element without
+// mass (e == 0: a -inf logit, or one that underflows) adds nothing: 0 * -inf never reaches the sum.  A NaN element makes s and
+// u NaN.  The neutral partial is (kSentinel, 0, 0): kSentinel is finite, so (m2 - M) * 0 is 0.
+__device__ __forceinline__ float rebase_u(float u, float s, float m2, float M, float scale) { return scale * fmaf(m2 - M, s, u); }
+__device__ __forceinline__ void ms_merge_u(float& m2, float& s, float& u, float m2b, float sb, float ub) {
+    const float M = fmaxf(m2, m2b);
+    const float ea = fast_exp2(m2 - M);
+    const float eb = fast_exp2(m2b - M);
+    u = rebase_u(u, s, m2, M, ea) + rebase_u(ub, sb, m2b, M, eb);
+    s = fmaf(s, ea, sb * eb);                      // (ms_merge's operations: the pair keeps its bits)
+    m2 = M;
+}
+// wave_merge with the third sum: the same DPP order for u as for s
+__device__ __forceinline__ void wave_merge_u(float& m2, float& s, float& u) {
+    const float M = wave_max(m2);
+    const float f = fast_exp2(m2 - M);
+    u = wave_sum(rebase_u(u, s, m2, M, f));
+    s = wave_sum(s * f);
+    m2 = M;
+}
+// H in nats of a finished row: NaN when s == 0 (no finite logit) or when a NaN went in
+__device__ __forceinline__ float row_entropy_u(float s, float u) {
+    return static_cast<float>(kLn2d * (log2_split(s) - static_cast<double>(u) / static_cast<double>(s)));
+}
+
+// kStatsOnly: the lane's best element in slot 0.  A lane meets its ids in ascending order, so `>` keeps the lowest id of a tie;
+// NaN and -inf never compare greater than the empty slot's -inf and are never taken, as in the list.
+__device__ __forceinline__ void best_take(Top& t, float x, int id) {
+    const bool up = x > t.v[0];
+    t.v[0] = up ? x : t.v[0];
+    t.i[0] = up ? id : t.i[0];
+}
+// the lanes' slot 0 -> the wave's, uniform in every lane: wave_top's first round; the other slots of `out` are empty
+__device__ __forceinline__ void wave_best(const Top& t, Top& out) {
+    top_clear(out);
+    const float wv = wave_max(t.v[0]);
+    out.v[0] = wv;
+    out.i[0] = wave_min_i32(t.v[0] == wv ? t.i[0] : kNoIndex);
+}
+template <int kMode>
+__device__ __forceinline__ void wave_reduce_top(Top& t, Top& out) {
+    if constexpr (keeps_list(kMode)) wave_top(t, out);
+    else if constexpr (kMode == kStatsOnly) wave_best(t, out);
+    else top_clear(out);
+}
+
 // one element (the scalar head and tail of a row)
 template <int kMode>
-__device__ __forceinline__ void accum_one(float x, int id, float c2, float& m2, float& s, Top& t, Score& sc) {
-    if constexpr (kMode != kScoreOnly) {
+__device__ __forceinline__ void accum_one(float x, int id, float c2, float& m2, float& s, float& u, Top& t, Score& sc) {
+    if constexpr (keeps_list(kMode)) {
         if (x > t.v[kTop - 1]) top_insert(t, x, id);
     }
+    if constexpr (kMode == kStatsOnly) best_take(t, x, id);
     if constexpr (kMode != kTopOnly) sc.n += (x > sc.xg || (x == sc.xg && id < sc.g)) ? 1 : 0;
-    accum_scalar(x, c2, m2, s);
+    if constexpr (keeps_stats(kMode)) {               // accum_scalar's operations on (m2, s), and the weighted term
+        const float M = max2(m2, x * c2);
+        const float scale = fast_exp2(m2 - M);
+        const float d = fmaf(x, c2, -M);
+        const float e = fast_exp2(d);
+        u = fmaf(e, e > 0.0f ? d : 0.0f, rebase_u(u, s, m2, M, scale));
+        s = fmaf(s, scale, e);
+        m2 = M;
+    } else {
+        accum_scalar(x, c2, m2, s);
+    }
 }
 
 // one 16-byte vector whose first element has vocabulary id `id0`: greedy.hip's accum_arg with the list in place of the arg-max
@@ -184,8 +258,8 @@ __device__ __forceinline__ void accum_one(float x, int id, float c2, float& m2, 
 // `>`: one v_cmp into a scalar register pair per element, whose set bits the scalar unit counts and adds (s_bcnt1, s_add) -- no
 // per-lane add, no VCC round trip.  The one wave-batch of the row that holds the token takes the order element by element.
 template <int N, int kMode>
-__device__ __forceinline__ void accum_top(const float (&x)[N], int id0, float c2, float& m2, float& s, Top& t, float bound,
-                                          Score& sc, bool live) {
+__device__ __forceinline__ void accum_top(const float (&x)[N], int id0, float c2, float& m2, float& s, float& u, Top& t,
+                                          float bound, Score& sc, bool live) {
     if constexpr (kMode != kTopOnly) {
         const float xg = live ? sc.xg : __int_as_float(0x7fc00000);                // a dead lane counts nothing
         const int lo = __builtin_amdgcn_readfirstlane(id0);
@@ -207,18 +281,35 @@ __device__ __forceinline__ void accum_top(const float (&x)[N], int id0, float c2
     float vmax;
     if constexpr (N == 8) vmax = fmaxf(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])), fmaxf(fmaxf(x[4], x[5]), fmaxf(x[6], x[7])));
     else vmax = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
-    if constexpr (kMode != kScoreOnly) {
+    if constexpr (keeps_list(kMode)) {
         if (vmax > t.v[kTop - 1] && vmax >= bound) {
 #pragma unroll
             for (int i = 0; i < N; ++i)
                 if (x[i] > t.v[kTop - 1] && x[i] >= bound) top_insert(t, x[i], id0 + i);
         }
     }
+    if constexpr (kMode == kStatsOnly) {
+        if (vmax > t.v[0]) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) best_take(t, x[i], id0 + i);
+        }
+    }
     const float M = fmaxf(m2, vmax * c2);
     const float scale = fast_exp2(m2 - M);
     float e[N];
+    if constexpr (keeps_stats(kMode)) {
+        float w = 0.0f;
 #pragma unroll
-    for (int i = 0; i < N; ++i) e[i] = fast_exp2(fmaf(x[i], c2, -M));
+        for (int i = 0; i < N; ++i) {
+            const float d = fmaf(x[i], c2, -M);
+            e[i] = fast_exp2(d);
+            w = fmaf(e[i], e[i] > 0.0f ? d : 0.0f, w);
+        }
+        u = rebase_u(u, s, m2, M, scale) + w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) e[i] = fast_exp2(fmaf(x[i], c2, -M));
+    }
     float sum;
     if constexpr (N == 8) sum = ((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7]));
     else sum = (e[0] + e[1]) + (e[2] + e[3]);
@@ -227,8 +318,8 @@ __device__ __forceinline__ void accum_top(const float (&x)[N], int id0, float c2
 }
 
 template <int DT, int kMode>
-__device__ __forceinline__ void accum_vec(const u32x4& v, int id0, float c2, float& m2, float& s, Top& t, float bound, Score& sc,
-                                          bool live) {
+__device__ __forceinline__ void accum_vec(const u32x4& v, int id0, float c2, float& m2, float& s, float& u, Top& t, float bound,
+                                          Score& sc, bool live) {
     if constexpr (DT == ASD_DTYPE_BF16) {
         float x[8];
 #pragma unroll
@@ -236,7 +327,7 @@ __device__ __forceinline__ void accum_vec(const u32x4& v, int id0, float c2, flo
             x[2 * i] = __uint_as_float(v[i] << 16);
             x[2 * i + 1] = __uint_as_float(v[i] & 0xFFFF0000u);
         }
-        accum_top<8, kMode>(x, id0, c2, m2, s, t, bound, sc, live);
+        accum_top<8, kMode>(x, id0, c2, m2, s, u, t, bound, sc, live);
     } else if constexpr (DT == ASD_DTYPE_F16) {
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
         float x[8];
@@ -247,12 +338,12 @@ __device__ __forceinline__ void accum_vec(const u32x4& v, int id0, float c2, flo
             x[2 * i] = static_cast<float>(h[0]);
             x[2 * i + 1] = static_cast<float>(h[1]);
         }
-        accum_top<8, kMode>(x, id0, c2, m2, s, t, bound, sc, live);
+        accum_top<8, kMode>(x, id0, c2, m2, s, u, t, bound, sc, live);
     } else {
         float x[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) x[i] = __uint_as_float(v[i]);
-        accum_top<4, kMode>(x, id0, c2, m2, s, t, bound, sc, live);
+        accum_top<4, kMode>(x, id0, c2, m2, s, u, t, bound, sc, live);
     }
 }
 
@@ -269,8 +360,18 @@ __device__ __forceinline__ void merge_in_lane_order(float m2, float s, int n, fl
         ms_merge(rm2, rs, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m2), l)),
                  __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l)));
 }
+__device__ __forceinline__ void merge_in_lane_order_u(float m2, float s, float u, int n, float& rm2, float& rs, float& ru) {
+    rm2 = kSentinel;
+    rs = 0.0f;
+    ru = 0.0f;
+    for (int l = 0; l < n; ++l)
+        ms_merge_u(rm2, rs, ru, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m2), l)),
+                   __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l)),
+                   __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), l)));
+}
 
-// The body of one workgroup: slice blockIdx.y of row blockIdx.x.  P is TopParams (kTopOnly) or PromptParams.
+// The body of one workgroup: slice blockIdx.y of row blockIdx.x.  P is TopParams (kTopOnly), PromptParams (kScore*) or
+// StatsParams (kStats).
 // kRows (asd_top_logprobs_rows): the scale of sequence b is formed from inv_t[b] by log2_scale's own f64 product
 template <int DT, bool kRows, int kMode, class P>
 __device__ __forceinline__ void top_logprobs_row(const P& p) {
@@ -278,6 +379,7 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
     __shared__ float meet_v[kWaves][kTop];
     __shared__ int meet_i[kWaves][kTop];
     __shared__ float meet_ms[kWaves][2];
+    __shared__ float meet_u[kWaves];               // (kStats)
     __shared__ int meet_count[kWaves];
     __shared__ int meet_last;
 
@@ -298,7 +400,31 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
     const char* rowp = static_cast<const char*>(p.logits) + (static_cast<int64_t>(b) * p.ld_seq + static_cast<int64_t>(k) * p.ld_row) * E::kBytes;
     Score sc{0, 0.0f, 0, 0};
     bool scored = false;                           // g is inside [0, V) and x[g] is no NaN: the row has a log-prob and a rank
-    if constexpr (kMode != kTopOnly) {
+    if constexpr (keeps_stats(kMode)) {
+        int a = p.n_acc[b];
+        a = a < 0 ? 0 : (a > K1 - 1 ? K1 - 1 : a);
+        if (k > a) {                                      // a row that is never committed (workgroup-uniform): neutral outputs, no pass
+            if (split == 0) {
+                if (tid == 0) {
+                    p.stat_id[2 * static_cast<int64_t>(row)] = 0;
+                    p.stat_id[2 * static_cast<int64_t>(row) + 1] = -1;
+                    p.stat_val[2 * static_cast<int64_t>(row)] = 0.0f;
+                    p.stat_val[2 * static_cast<int64_t>(row) + 1] = 0.0f;
+                }
+                if (tid < p.N) {
+                    const int64_t at = static_cast<int64_t>(row) * p.N + tid;
+                    p.top_id[at] = -1;
+                    p.top_lp[at] = -INFINITY;
+                }
+            }
+            return;
+        }
+        sc.g = __builtin_amdgcn_readfirstlane(k < a ? p.tok[static_cast<int64_t>(b) * p.ld_tok + k] : p.drawn[b]);
+        const bool inside = static_cast<uint32_t>(sc.g) < static_cast<uint32_t>(p.V);     // an id outside is never dereferenced
+        sc.xg = __int_as_float(__builtin_amdgcn_readfirstlane(
+            __float_as_int(inside ? E::scalar(rowp, sc.g) : __int_as_float(0x7fc00000))));
+        scored = sc.xg == sc.xg;
+    } else if constexpr (kMode != kTopOnly) {
         if (p.first != nullptr && k < p.first[b]) {       // a skipped row (workgroup-uniform): neutral outputs, no pass
             if (split == 0) {
                 if (tid == 0) { p.lp[row] = 0.0f; p.rank[row] = 0; }
@@ -325,10 +451,10 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
     const int v0 = static_cast<int>(static_cast<uint64_t>(nvec) * static_cast<uint32_t>(split) / static_cast<uint32_t>(S));
     const int v1 = static_cast<int>(static_cast<uint64_t>(nvec) * static_cast<uint32_t>(split + 1) / static_cast<uint32_t>(S));
 
-    float m2 = kSentinel, s = 0.0f;
+    float m2 = kSentinel, s = 0.0f, u = 0.0f;      // (u: kStats)
     Top t;
     top_clear(t);
-    if (wave == 0 && split == 0 && lane < head) accum_one<kMode>(E::scalar(rowp, lane), lane, c2, m2, s, t, sc);
+    if (wave == 0 && split == 0 && lane < head) accum_one<kMode>(E::scalar(rowp, lane), lane, c2, m2, s, u, t, sc);
 
     // ---- the stream: greedy.hip's (16-byte buffer loads through a descriptor that ends with the slice; the next batch is issued
     // before the current one is consumed); the wave's bound is refreshed behind every batch
@@ -350,25 +476,25 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
             const uint32_t off = base + lane_off + static_cast<uint32_t>(j) * (kThreads * 16u);
             const int id0 = id_first + static_cast<int>(off >> 4) * E::kPerVec;
             if constexpr (kMode == kTopOnly) {
-                if (off < end) accum_vec<DT, kMode>(cur[j], id0, c2, m2, s, t, bound, sc, true);
+                if (off < end) accum_vec<DT, kMode>(cur[j], id0, c2, m2, s, u, t, bound, sc, true);
             } else {
-                accum_vec<DT, kMode>(cur[j], id0, c2, m2, s, t, bound, sc, off < end);     // (the count is taken by the whole wave)
+                accum_vec<DT, kMode>(cur[j], id0, c2, m2, s, u, t, bound, sc, off < end);     // (the count is taken by the whole wave)
             }
         }
-        if constexpr (kMode != kScoreOnly) bound = wave_bound(t.v[0]);
+        if constexpr (keeps_list(kMode)) bound = wave_bound(t.v[0]);
 #pragma unroll
         for (int j = 0; j < kUnroll; ++j) cur[j] = nxt[j];
     }
     if (wave == 0 && split == S - 1 && lane < tail) {
         const int id = head + nvec * E::kPerVec + lane;
-        accum_one<kMode>(E::scalar(rowp, id), id, c2, m2, s, t, sc);
+        accum_one<kMode>(E::scalar(rowp, id), id, c2, m2, s, u, t, sc);
     }
 
     // ---- lanes -> wave, waves -> workgroup (lane w of wave 0 takes wave w's list and pair out of LDS)
     Top w;
-    if constexpr (kMode != kScoreOnly) wave_top(t, w);
-    else top_clear(w);
-    wave_merge(m2, s);
+    wave_reduce_top<kMode>(t, w);
+    if constexpr (keeps_stats(kMode)) wave_merge_u(m2, s, u);
+    else wave_merge(m2, s);
     int count = 0;                                 // kScore*: uniform in wave 0 from here on
     if constexpr (kMode != kTopOnly) count = wave_sum_i32(sc.n) + sc.w;
     if (lane == 0) {
@@ -377,21 +503,24 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
         meet_ms[wave][0] = m2;
         meet_ms[wave][1] = s;
         if constexpr (kMode != kTopOnly) meet_count[wave] = count;
+        if constexpr (keeps_stats(kMode)) meet_u[wave] = u;
     }
     __syncthreads();
-    float rm2 = kSentinel, rs = 0.0f;
+    float rm2 = kSentinel, rs = 0.0f, ru = 0.0f;
     if (wave == 0) {
         if constexpr (kMode != kTopOnly) count = wave_sum_i32(lane < kWaves ? meet_count[lane] : 0);
         top_clear(t);
-        m2 = kSentinel; s = 0.0f;
+        m2 = kSentinel; s = 0.0f; u = 0.0f;
         if (lane < kWaves) {
 #pragma unroll
             for (int j = 0; j < kTop; ++j) { t.v[j] = meet_v[lane][j]; t.i[j] = meet_i[lane][j]; }
             m2 = meet_ms[lane][0];
             s = meet_ms[lane][1];
+            if constexpr (keeps_stats(kMode)) u = meet_u[lane];
         }
-        if constexpr (kMode != kScoreOnly) wave_top(t, w);
-        merge_in_lane_order(m2, s, kWaves, rm2, rs);
+        if constexpr (kMode != kScoreOnly) wave_reduce_top<kMode>(t, w);
+        if constexpr (keeps_stats(kMode)) merge_in_lane_order_u(m2, s, u, kWaves, rm2, rs, ru);
+        else merge_in_lane_order(m2, s, kWaves, rm2, rs);
     }
 
     if (S > 1) {
@@ -403,6 +532,7 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
 #pragma unroll
             for (int j = 0; j < kTop; ++j) { q.v[j] = w.v[j]; q.i[j] = w.i[j]; }
             q.count = count; q.pad = 0;
+            if constexpr (keeps_stats(kMode)) q.pad = __float_as_int(ru);
             mine[split] = q;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -422,7 +552,7 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
         __syncthreads();
         if (meet_last == 0 || wave != 0) return;
         top_clear(t);
-        m2 = kSentinel; s = 0.0f;
+        m2 = kSentinel; s = 0.0f; u = 0.0f;
         if (lane < S) {                            // lane <-> slice: S <= 64
             const SlicePartial* const q = mine + lane;
 #pragma unroll
@@ -430,11 +560,13 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
             m2 = q->m2;
             s = q->s;
             if constexpr (kMode != kTopOnly) count = q->count;
+            if constexpr (keeps_stats(kMode)) u = __int_as_float(q->pad);
         } else {
             count = 0;
         }
-        if constexpr (kMode != kScoreOnly) wave_top(t, w);
-        merge_in_lane_order(m2, s, S, rm2, rs);    // slice order, not arrival order
+        if constexpr (kMode != kScoreOnly) wave_reduce_top<kMode>(t, w);
+        if constexpr (keeps_stats(kMode)) merge_in_lane_order_u(m2, s, u, S, rm2, rs, ru);
+        else merge_in_lane_order(m2, s, S, rm2, rs);    // slice order, not arrival order
         if constexpr (kMode != kTopOnly) count = wave_sum_i32(count);
     } else if (wave != 0) {
         return;
@@ -455,7 +587,16 @@ __device__ __forceinline__ void top_logprobs_row(const P& p) {
         p.top_id[at] = filled ? mi : -1;
         p.top_lp[at] = filled ? row_logprob(mv, c2, l2) : -INFINITY;
     }
-    if constexpr (kMode != kTopOnly) {
+    if constexpr (keeps_stats(kMode)) {
+        if (lane == 0) {                           // slot 0 again (the table may have N == 0), the rank and the entropy
+            const double l2 = static_cast<double>(rm2) + log2_split(rs);
+            const bool filled = mi != kNoIndex;
+            p.stat_id[2 * static_cast<int64_t>(row)] = scored ? 1 + count : 0;
+            p.stat_id[2 * static_cast<int64_t>(row) + 1] = filled ? mi : -1;
+            p.stat_val[2 * static_cast<int64_t>(row)] = row_entropy_u(rs, ru);
+            p.stat_val[2 * static_cast<int64_t>(row) + 1] = filled ? row_logprob(mv, c2, l2) : -INFINITY;
+        }
+    } else if constexpr (kMode != kTopOnly) {
         if (lane == 0) {                           // a slot's own operations on x[g]: the bits of a slot that holds g
             const double l2 = static_cast<double>(rm2) + log2_split(rs);
             p.lp[row] = scored ? row_logprob(sc.xg, c2, l2) : __int_as_float(0x7fc00000);

@@ -394,6 +394,22 @@ class HipOps:
             t = self._ws[key] = self.K.PromptLogprobs(Bv, T, V, logits.dtype, int(n), int(splits), logits.device)
         return t(logits, target, first, inv_temperature)
 
+    @traced("token_stats")
+    def token_stats(self, logits, tok, n_acc, drawn, n: int = 0, inv_temperature: float = 1.0, rows=None, splits: int = 0):
+        """Per row of a step's [B,K1,V] (or [B,V]) logits that may be committed -- row j of sequence b while j <= n_acc[b], scoring
+        tok[b, j] below n_acc[b] and drawn[b] at it -- the rank of that token, the arg-max and its log-prob, the entropy and,
+        with n >= 1, the row's top-n table, in one streaming pass (asd_token_stats) -> (stat_id i32 [B,K1,2] (rank, arg-max id),
+        stat_val f32 [B,K1,2] (entropy in nats, max log-prob), top_id i32 [B,K1,n] | None, top_lp f32 [B,K1,n] | None).  rows:
+        the pack_sampling_rows handle, whose per-sequence temperatures then hold (as in top_logprobs_rows).  logits and tok may
+        be strided views, nothing is copied.  One workspace per shape and calling thread, like `prompt_logprobs`."""
+        K1 = 1 if logits.dim() == 2 else logits.shape[1]
+        Bv, V = logits.shape[0], logits.shape[-1]
+        key = ("token_stats", Bv, K1, V, int(n), int(splits), str(logits.dtype), str(logits.device))
+        t = self._ws.get(key)
+        if t is None:
+            t = self._ws[key] = self.K.TokenStats(Bv, K1, V, logits.dtype, int(n), int(splits), logits.device)
+        return t(logits, tok, n_acc, drawn, inv_temperature if rows is None else rows.inv_t)
+
     @traced("commit_top_logprobs")
     def commit_top_logprobs(self, top_id, top_lp, seq_len, n_commit, out_id, out_lp, max_len):
         """The step's top-N rows follow its commit (asd_commit_top_logprobs); runs behind commit_step_lp / commit_step_stop and

@@ -1150,6 +1150,85 @@ def prompt_logprobs(logits: torch.Tensor, target: torch.Tensor, first: Optional[
     return PromptLogprobs(Bv, T, V, logits.dtype, n, splits, logits.device)(logits, target, first, inv_temperature)
 
 
+class TokenStats:
+    """asd_token_stats with its workspace: per row of a step's [B, K1, V] logits that may be committed, the rank of the committed
+    token, the arg-max and its log-prob, the entropy and, with n >= 1, the row's top-n table (asd_top_logprobs' bits), in one
+    streaming pass.  Row j of sequence b is live while j <= a = clamp(n_acc[b], 0, K1 - 1) and scores tok[b, j] (j < a) or
+    drawn[b] (j == a); later rows are not streamed and hold the neutral outputs (rank 0, id -1, 0.0, 0.0, table (-1, -inf)).
+    `logits` and `tok` are read in place: strided views with unit last stride, nothing is copied; K1 = 1 also takes [B, V] and
+    tok = None.  The workspace is sized for the split count the launch uses at (B, K1, V, dtype, splits)."""
+
+    def __init__(self, B_: int, K1: int, V: int, dtype: torch.dtype = torch.bfloat16, n: int = 0, splits: int = 0,
+                 device: Optional[torch.device] = None):
+        if isinstance(n, bool) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"n must be in [0, {MAX_TOP_LOGPROBS}]")
+        if dtype not in _DTYPE_CODE:
+            raise ValueError(f"unsupported logits dtype {dtype}")
+        self.B, self.K1, self.V, self.dtype, self.n, self.splits = B_, K1, V, dtype, int(n), int(splits)
+        self.device = device or torch.device("cuda")
+        with torch.cuda.device(self.device):       # splits == 0: the heuristic counts the CUs of the device that launches
+            self.bytes = int(_lib().asd_token_stats_workspace_bytes(B_, K1, V, _DTYPE_CODE[dtype], self.splits))
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+
+    def __call__(self, logits: torch.Tensor, tok: Optional[torch.Tensor], n_acc: torch.Tensor, drawn: torch.Tensor,
+                 inv_temperature=1.0):
+        """inv_temperature: a number, or a float32 [B] device tensor with one value per sequence.
+        -> (stat_id i32 [B,K1,2] (rank, arg-max id), stat_val f32 [B,K1,2] (entropy, max log-prob), top_id i32 [B,K1,n] | None,
+        top_lp f32 [B,K1,n] | None), fresh tensors."""
+        K1, V, n = self.K1, self.V, self.n
+        if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != self.dtype:
+            raise ValueError(f"logits must be a {self.dtype} CUDA (HIP) tensor; this package has no CPU path")
+        if logits.dim() == 2 and K1 == 1:
+            logits = logits[:, None]
+        if logits.dim() != 3 or logits.shape[1] != K1 or logits.shape[2] != V or logits.stride(2) != 1:
+            raise ValueError(f"logits must be [B, {K1}, {V}]" + (f" or [B, {V}]" if K1 == 1 else "") + " with unit stride along V")
+        Bv = logits.shape[0]
+        if Bv != self.B:                           # the heuristic's split count, and with it the workspace, depends on B
+            raise ValueError(f"sized for B == {self.B}")
+        ld_seq, ld_row = _logit_strides(logits, K1)
+        tok_p, ld_tok = None, 0
+        if K1 > 1:
+            if not isinstance(tok, torch.Tensor) or not tok.is_cuda or tok.dtype != torch.int32:
+                raise ValueError("tok must be an int32 CUDA (HIP) tensor")
+            if tuple(tok.shape) != (Bv, K1 - 1) or (K1 > 2 and tok.stride(1) != 1):
+                raise ValueError(f"tok must be [B, {K1 - 1}] with unit stride along its rows")
+            ld_tok = tok.stride(0) if Bv > 1 else K1 - 1
+            if ld_tok < K1 - 1:
+                raise ValueError("tok rows overlap: the row stride must be >= K1 - 1")
+            tok_p = tok.data_ptr()
+        elif tok is not None:
+            raise ValueError("tok must be None when K1 == 1")
+        if tuple(n_acc.shape) != (Bv,) or tuple(drawn.shape) != (Bv,):
+            raise ValueError("n_acc and drawn must be int32 [B]")
+        if isinstance(inv_temperature, torch.Tensor):
+            if tuple(inv_temperature.shape) != (Bv,):
+                raise ValueError("a per-sequence inv_temperature must be float32 [B]")
+            scalar, rows = 1.0, _dev(inv_temperature, "inv_temperature", torch.float32)
+        else:
+            scalar, rows = float(inv_temperature), None
+        stat_id = torch.empty((Bv, K1, 2), dtype=torch.int32, device=self.device)
+        stat_val = torch.empty((Bv, K1, 2), dtype=torch.float32, device=self.device)
+        top_id = torch.empty((Bv, K1, n), dtype=torch.int32, device=self.device) if n else None
+        top_lp = torch.empty((Bv, K1, n), dtype=torch.float32, device=self.device) if n else None
+        rc = _lib().asd_token_stats(logits.data_ptr(), _DTYPE_CODE[logits.dtype], ld_seq, ld_row, Bv, K1, V, tok_p, ld_tok,
+                                    _dev(n_acc, "n_acc", torch.int32), _dev(drawn, "drawn", torch.int32), scalar, rows,
+                                    n, self.splits, stat_id.data_ptr(), stat_val.data_ptr(),
+                                    None if top_id is None else top_id.data_ptr(),
+                                    None if top_lp is None else top_lp.data_ptr(), self.buf.data_ptr(), self.bytes, _stream())
+        B.check("asd_token_stats", rc)
+        return stat_id, stat_val, top_id, top_lp
+
+
+def token_stats(logits: torch.Tensor, tok: Optional[torch.Tensor], n_acc: torch.Tensor, drawn: torch.Tensor, n: int = 0,
+                inv_temperature=1.0, splits: int = 0):
+    """One asd_token_stats call with a workspace of its own -> (stat_id, stat_val, top_id | None, top_lp | None); see TokenStats."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() not in (2, 3):
+        raise ValueError("logits must be a [B, K1, V] (or [B, V]) tensor")
+    Bv, V = logits.shape[0], logits.shape[-1]
+    K1 = logits.shape[1] if logits.dim() == 3 else 1
+    return TokenStats(Bv, K1, V, logits.dtype, n, splits, logits.device)(logits, tok, n_acc, drawn, inv_temperature)
+
+
 def commit_top_logprobs(top_id: torch.Tensor, top_lp: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor,
                         out_id: torch.Tensor, out_lp: torch.Tensor, max_len: Optional[int] = None) -> None:
     """The top-N rows of a step follow its commit (asd_commit_top_logprobs): out[b, seq_len[b] - n_commit[b] + j] = top[b, j]

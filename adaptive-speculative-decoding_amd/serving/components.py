@@ -94,6 +94,12 @@ class QualityPredictor(nn.Module):
         x = np.stack([fx.extract(p, o, lp, s) for p, o, lp, s in zip(prompts, draft_outputs, draft_logprobs, stage_ids)])
         return get_backend().mlp_predict(x.astype(np.float32), *self._weights())
 
+    def predict_features(self, features) -> np.ndarray:
+        """[n, feature_dim] feature rows (FeatureExtractor.extract_device's, as Stage.generate(token_stats=True) returns them)
+        -> n probabilities, through one asd_mlp_predict launch."""
+        x = np.ascontiguousarray(np.asarray(features, dtype=np.float32).reshape(-1, self.feature_dim))
+        return np.asarray(get_backend().mlp_predict(x, *self._weights())).reshape(-1)
+
     def predict(self, prompt: str, draft_output: str, draft_logprobs, stage_id: int,
                 feature_extractor: Optional[FeatureExtractor] = None) -> float:
         return float(self.predict_batch([prompt], [draft_output], [draft_logprobs], [stage_id], feature_extractor)[0])

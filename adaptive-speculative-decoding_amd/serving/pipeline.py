@@ -216,6 +216,10 @@ class PipelineConfig:
     # vLLM's prompt_logprobs (serving/stages.py, PROMPT LOG-PROBS), handed to every stage.generate(prompt_logprobs=): each
     # stage's entry then carries "prompt_logprobs" and "prompt_ranks"; not fed to the predictor.  None: the keyword is not passed
     prompt_logprobs: Optional[int] = None
+    # the per-token statistics (serving/stages.py, TOKEN STATS), handed to every stage.generate(token_stats=): each stage's
+    # entry then carries "token_entropy", "token_max_logprobs", "token_ranks" and "features" (the row of the stage's
+    # predictor_features), and a predictor with predict_features is fed that row.  None: the keyword is not passed
+    token_stats: Optional[bool] = None
 
     @classmethod
     def from_yaml(cls, path: str) -> "PipelineConfig":
@@ -251,6 +255,8 @@ class PipelineConfig:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
         if sec.get("prompt_logprobs") is not None:
             kw["prompt_logprobs"] = int(sec["prompt_logprobs"])
+        if sec.get("token_stats") is not None:
+            kw["token_stats"] = bool(sec["token_stats"])
         return cls(**kw)
 
 
@@ -562,7 +568,9 @@ class AdaptiveSpeculativePipeline:
                 if self.cache_manager:
                     self.cache_manager.cleanup_request(r.request_id)
 
-    def _predict(self, r: _Active, stage_idx: int, output: str, logprobs) -> float:
+    def _predict(self, r: _Active, stage_idx: int, output: str, logprobs, features=None) -> float:
+        if features is not None and hasattr(self.predictor, "predict_features"):       # the stage's own feature row (TOKEN STATS)
+            return float(self.predictor.predict_features(np.asarray(features, dtype=np.float32)[None, :])[0])
         return float(self.predictor.predict(prompt=r.current_prompt, draft_output=output, draft_logprobs=logprobs,
                                             stage_id=stage_idx, feature_extractor=self.feature_extractor))
 
@@ -588,6 +596,7 @@ class AdaptiveSpeculativePipeline:
                 else:
                     todo.append(r)
             gen_out: Dict[str, Any] = {}
+            feat_out: Dict[str, Any] = {}                               # token_stats: every generated request's feature row
             if todo:
                 stop_kw = {} if cfg.stop_token_ids is None else {"stop_token_ids": tuple(cfg.stop_token_ids)}
                 if cfg.logprobs is not None:
@@ -600,6 +609,8 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["no_repeat_ngram_size"] = int(cfg.no_repeat_ngram_size)
                 if cfg.prompt_logprobs is not None:
                     stop_kw["prompt_logprobs"] = cfg.prompt_logprobs
+                if cfg.token_stats is not None:
+                    stop_kw["token_stats"] = cfg.token_stats
                 # (limits likewise: one per request of the batch, or the batch's one int)
                 limit = [r.max_tokens for r in todo] if isinstance(max_tokens, list) else max_tokens
                 # (sampling parameters likewise: a list only where the batch carries one, so other calls are unchanged)
@@ -624,6 +635,10 @@ class AdaptiveSpeculativePipeline:
                     if cfg.prompt_logprobs is not None and "prompt_logprobs" in (stage_stats or {}):
                         entry["prompt_logprobs"] = stage_stats["prompt_logprobs"][j]       # (kept with the entry, not predicted on)
                         entry["prompt_ranks"] = stage_stats["prompt_ranks"][j]
+                    if cfg.token_stats is not None and "predictor_features" in (stage_stats or {}):
+                        for key in ("token_entropy", "token_max_logprobs", "token_ranks"):
+                            entry[key] = stage_stats[key][j]
+                        entry["features"] = feat_out[r.request_id] = stage_stats["predictor_features"][j]
                     gen_out[r.request_id] = (texts[j], lp)
                     if self.cache_manager:
                         self.cache_manager.allocate(r.request_id, i, entry)
@@ -637,7 +652,7 @@ class AdaptiveSpeculativePipeline:
                 r.costs.append(float(stage.cost_per_token))
                 r.total_tokens += len(text.split())
                 if not last_stage:
-                    probs[j] = self._predict(r, i, text, lp if len(lp) else None)
+                    probs[j] = self._predict(r, i, text, lp if len(lp) else None, feat_out.get(r.request_id))
             # ... then ONE Bayes launch and ONE DP launch for the whole batch
             if not last_stage and cfg.risk_adjustment:
                 with self._stats_lock:

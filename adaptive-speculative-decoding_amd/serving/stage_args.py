@@ -103,6 +103,14 @@ def _check_prompt_logprobs(n) -> Optional[int]:
     return int(n)
 
 
+def _check_token_stats(v) -> Optional[bool]:
+    """None stays None (the caller's default then holds); a bool is returned as given; anything else -- an int, a string, a
+    sequence -- raises."""
+    if v is None or isinstance(v, bool):
+        return v
+    raise ValueError(f"token_stats must be None or a bool, got {v!r}")
+
+
 def _check_min_p(v, name: str = "min_p") -> float:
     if isinstance(v, bool) or not isinstance(v, _NUMBER) or not 0.0 <= float(v) <= 1.0:
         raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")           # (NaN included)

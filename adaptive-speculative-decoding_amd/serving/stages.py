@@ -332,7 +332,33 @@ stats["prompt_logprobs"][i] (float32 [m_i]), stats["prompt_ranks"][i] (int32 [m_
 id: the table's order, so rank <= N means the token stands in slot rank - 1 with the same bits) and, with N >= 1,
 stats["prompt_top_token_ids"][i] (int32 [m_i, N]) / stats["prompt_top_logprobs"][i] (float32 [m_i, N]).  Off: none of the keys.
 COST: profiles/prompt_logprobs.json.  NOT BUILT: the [B, P, V] prefill logits are materialised as before -- chunking the prefill
-over positions is not part of this; the rank of GENERATED tokens; one N per request; and serving/hierarchy.py's loop.
+over positions is not part of this; one N per request; and serving/hierarchy.py's loop.
+
+TOKEN STATS.  `generate(token_stats=True)` (or StageConfig.token_stats; None takes the configuration's value; anything but None
+or a bool raises ValueError before the prompts are encoded) returns, per COMMITTED token, the uncertainty figures the quality
+predictor is specified on (RESEARCH_PROTOCOL.md:366-409: the entropy of the last 32 tokens' distributions and the mean of the
+per-token maximum log-prob) and vLLM's rank of a sampled token.  A step makes ONE ops.token_stats call (asd_token_stats: the
+top-N pass with the committed token's rank counted beside it and a third running sum for the entropy) where the table's call
+stands -- behind sampler.draw / sampler.settle, on the tensor the table reads: stage 0's processed [B, V] logits with n_acc = 0
+and the drawn token, a verifying stage's processed [B, K+1, V] output as returned with the step's proposals, n_acc and drawn
+token -- and one more ops.commit_top_logprobs (N = 2: the pair per row) behind the step's commit, which moves row j to the
+step's j-th committed token.  Rows behind n_acc are never committed and are not streamed.  With `logprobs` = N on, that one
+call returns the table too (in place of ops.top_logprobs / top_logprobs_rows: the rows are not read again) and the table's
+commit is unchanged.  WHAT IS DESCRIBED: the distribution the top-N table describes -- processed (mask -> automaton -> bad
+words -> n-gram -> edits -> penalties), temperature-scaled (the call's temperature; 1 when greedy; the row's own on the rows
+route) and UNTRUNCATED by top-k / top-p / min-p.  So `token_argmax_ids` / `token_max_logprobs` are table slot 0 with its bits,
+rank <= N means the token stands in table slot rank - 1, greedy rows have rank 1, and a sampled token's rank can exceed 1.
+Nothing is read back inside a step, the generator is not consumed, and tokens, log-probs and tables keep their bits; with the
+feature off a call makes exactly the ops calls it made before.  RESULTS, ragged like logprobs[i]: stats["token_entropy"][i]
+(float32 [n_i], nats), stats["token_max_logprobs"][i] (float32 [n_i]), stats["token_argmax_ids"][i] (int32 [n_i]),
+stats["token_ranks"][i] (int32 [n_i]) and stats["predictor_features"] (float32 [B, 256]): FeatureExtractor.extract_device on the
+[B, cap, 2] device buffer's max log-probs and entropies behind the prompt with n_valid = seq_len - P, the prompt's word count and
+the row's token count, formed before anything is read back.  A finished row's entries stay as committed.  Off: none of the keys.
+COST (profiles/token_stats.json: B = 32, K1 = 9, V = 152064, bf16, kernel time): every row live, with the table (N = 5) 76.4 us
+against 76.6 us for asd_top_logprobs alone (ratio 1.00: the statistics ride on the table's pass) and without it (N = 0) 77.6 us
+against 67.3 us for asd_prompt_logprobs at N = 0 (ratio 1.15, more than that pass's run-to-run spread of 0.13); with n_acc
+uniform in 0..K 52.9 / 45.1 us; plus one commit launch per step.  NOT BUILT: serving/hierarchy.py's loop; statistics of the
+draft model's rows.
 
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
@@ -352,7 +378,8 @@ from ..distributed import HipOps
 from ..kernels import pack_stop_sequences
 from ..minimal_adaptive_decoder import SimpleTokenizer
 from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_NGRAM, MAX_STOP_SEQ_LEN, MAX_STOP_SEQS,  # noqa: F401
-                         _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _is_seq,
+                         _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
+                         _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
                          check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
@@ -404,6 +431,7 @@ class StageConfig:
     guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
     guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
     prompt_logprobs: Optional[int] = None    # None: off; 0..8: the prompt tokens' log-probs and ranks, and a top-N table (PROMPT LOG-PROBS)
+    token_stats: bool = False                # per committed token: entropy, max log-prob, arg-max and rank; the predictor's features (TOKEN STATS)
 
 
 _REASONS = {1: "stop", 2: "length"}
@@ -431,6 +459,7 @@ class _Plan(NamedTuple):
     seeds: Optional[List[int]]
     n_top: int
     n_prompt: Optional[int] = None           # prompt_logprobs: None off, else the table's N in [0, 8]
+    token_stats: bool = False                # the per-token statistics and the predictor's feature batch (TOKEN STATS)
 
 
 class _EditState:
@@ -640,6 +669,50 @@ class _TopState:
 
     def record(self) -> dict:
         return dict(top_id=self.step[0].clone(), top_lp=self.step[1].clone())
+
+
+class _StatsState:
+    """What a generate call with token_stats on keeps beside the token buffer (module docstring, TOKEN STATS): [B, cap, 2] buffers
+    -- int32 (rank, arg-max id), filled with (0, -1), and float32 (entropy, max log-prob), filled with NaN -- that the commit
+    fills like the top-N tables, and the step's two calls.  With a table on (`top`), the step's ONE ops.token_stats call
+    returns the table too and hands it to `top`, whose commit then moves it: the rows are not read a second time."""
+
+    def __init__(self, ops, top: Optional[_TopState], inv_t: float, B: int, cap: int, device, rows=None):
+        self.ops, self.top, self.inv_t, self.cap, self.rows = ops, top, inv_t, cap, rows
+        self.ids = torch.zeros((B, cap, 2), dtype=torch.int32, device=device)
+        self.ids[:, :, 1] = -1
+        self.vals = torch.full((B, cap, 2), float("nan"), dtype=torch.float32, device=device)
+        self.step = self.given = None
+
+    def score(self, logits: torch.Tensor, tok32, n_acc: torch.Tensor, drawn: torch.Tensor) -> None:
+        """logits: the rows the step commits from, [B, V] (tok32 None) or [B, K+1, V], read where they are; n_acc / drawn: what
+        the step's draw or verification left, which the commit reads too."""
+        out = self.ops.token_stats(logits, tok32, n_acc, drawn, n=0 if self.top is None else self.top.n,
+                                   inv_temperature=self.inv_t, rows=self.rows)
+        self.step, self.given = out[:2], (n_acc, drawn)
+        if self.top is not None:
+            self.top.step = out[2:]
+
+    def commit(self, seq_len: torch.Tensor, n_commit: torch.Tensor) -> None:
+        """Behind the step's commit: row j goes to the step's j-th committed token (N = 2: the pair per row)."""
+        self.ops.commit_top_logprobs(self.step[0], self.step[1], seq_len, n_commit, self.ids, self.vals, self.cap)
+
+    def record(self) -> dict:
+        return dict(stat_id=self.step[0].clone(), stat_val=self.step[1].clone(), n_acc=self.given[0].clone(),
+                    drawn=self.given[1].clone())
+
+    def features(self, P: int, seq_len: torch.Tensor, prompts: Sequence[str], stage_id: int) -> torch.Tensor:
+        """The predictor's [B, 256] batch (FeatureExtractor.extract_device) from the committed figures, on the device."""
+        from .components import FeatureExtractor
+        n_valid = seq_len.to(torch.int64) - P
+        return FeatureExtractor.extract_device(self.vals[:, P:, 1], self.vals[:, P:, 0], [len(p.split()) for p in prompts],
+                                               n_valid.to(torch.float64), stage_id, n_valid=n_valid)
+
+    def stats(self, P: int, n_tok, features: torch.Tensor) -> dict:
+        ids, vals = self.ids[:, P:].cpu().numpy(), self.vals[:, P:].cpu().numpy()
+        cut = lambda a, k: [np.ascontiguousarray(r[:n, k]) for r, n in zip(a, n_tok)]        # noqa: E731
+        return {"token_entropy": cut(vals, 0), "token_max_logprobs": cut(vals, 1), "token_argmax_ids": cut(ids, 1),
+                "token_ranks": cut(ids, 0), "predictor_features": features.cpu().numpy()}
 
 
 class _PromptState:
@@ -854,7 +927,7 @@ class _CallState:
     loop: how rows end (`end`), the allow-list (`mask`, None without a list), the logit edit (`edit`, None without an entry), the
     guided automata (`fsm`, None when no row is guided), the bad words (`bad`, None when no row has one), the n-gram rule
     (`ngram`, None when every row's n is 0), the penalties (`pen`, None when every row is neutral), the sampler and the top-N
-    tables (`top`, None when off) and the prompt's scores (`prompt`, None when off).  `step_tok`: the [B, draft_len] buffer of the step's proposals, ONE per call, which `fsm`,
+    tables (`top`, None when off), the per-token statistics (`stats`, None when off) and the prompt's scores (`prompt`, None when off).  `step_tok`: the [B, draft_len] buffer of the step's proposals, ONE per call, which `fsm`,
     `bad`, `ngram` and `pen` all read at a verifying stage (None at stage 0, and when all four are off).  Uploads happen here, once; a part
     that is off costs no launch.  `prompt_ids`: every row's prompt ids without the padding."""
 
@@ -877,6 +950,8 @@ class _CallState:
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
         self.top = _TopState(ops, plan.n_top, plan.inv_t, B, P + plan.max_tokens, dev,
                              self.sampler.table if plan.rows else None) if plan.n_top else None
+        self.stats = _StatsState(ops, self.top, plan.inv_t, B, P + plan.max_tokens, dev,
+                                 self.sampler.table if plan.rows else None) if plan.token_stats else None
         self.prompt = _PromptState(ops, plan.n_prompt, ids, prompt_ids) if plan.n_prompt is not None else None
 
 
@@ -954,7 +1029,8 @@ class Stage:
                  bad_words_per_prompt=None, guided_fsm=None, guided_choice=None,
                  guided_choice_per_prompt=None,
                  no_repeat_ngram_size=None,
-                 prompt_logprobs: Optional[int] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 prompt_logprobs: Optional[int] = None,
+                 token_stats: Optional[bool] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1042,14 +1118,23 @@ class Stage:
         stats["prompt_top_token_ids"][i] (int32 [m_i, N]) / stats["prompt_top_logprobs"][i] (float32 [m_i, N]), most likely
         first.  N = 0 is ON and returns no table.  Off: none of the keys.  The generated tokens, their log-probs and tables
         keep their bits; a bool, a float, a sequence or a value outside [0, 8] raises ValueError (module docstring, PROMPT
-        LOG-PROBS)."""
+        LOG-PROBS).
+        `token_stats`: None = StageConfig.token_stats; True adds, ragged like logprobs[i], stats["token_entropy"][i] (float32
+        [n_i]: the entropy in nats of the distribution committed token j came from), stats["token_max_logprobs"][i] (float32
+        [n_i]) and stats["token_argmax_ids"][i] (int32 [n_i]): that distribution's most likely token and its log-prob -- the
+        top-N table's slot 0 --, stats["token_ranks"][i] (int32 [n_i]: the committed token's rank there, 1 = the most likely,
+        ties by lowest id; rank <= N means the token stands in table slot rank - 1; greedy rows have rank 1) and
+        stats["predictor_features"] (float32 [B, 256]: FeatureExtractor.extract_device on the two float arrays, formed on the
+        device).  The distribution is the one the top-N table describes: processed, temperature-scaled, UNTRUNCATED.  Off: none
+        of the five keys and no extra call.  Tokens, log-probs and tables keep their bits; anything but None or a bool raises
+        ValueError (module docstring, TOKEN STATS)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
                           stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
                           repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
-                          guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs)
+                          guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1063,6 +1148,7 @@ class Stage:
         decode = self._decode_plain if self.draft is None else self._decode_speculative
         tokens, lps, seq_len = decode(ids, plan.max_tokens, state)
         self.ops.check_status()
+        feats = None if state.stats is None else state.stats.features(P, seq_len, plan.prompts, self.index)   # before any read-back
         tok_h = tokens[:, P:].cpu().numpy()
         lp_h = lps[:, P:].cpu().numpy().astype(np.float32, copy=False)
         n_tok, reasons, matches = state.end.outcome(seq_len, tok_h, P, plan.limits)
@@ -1073,6 +1159,8 @@ class Stage:
             id_h, tlp_h = state.top.ids[:, P:].cpu().numpy(), state.top.lps[:, P:].cpu().numpy()
             stats["top_token_ids"] = [np.ascontiguousarray(r[:n]) for r, n in zip(id_h, n_tok)]
             stats["top_logprobs"] = [np.ascontiguousarray(r[:n]) for r, n in zip(tlp_h, n_tok)]
+        if state.stats is not None:
+            stats.update(state.stats.stats(P, n_tok, feats))
         if state.prompt is not None:
             stats.update(state.prompt.stats())
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
@@ -1080,7 +1168,8 @@ class Stage:
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
               repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm=None,
-              guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None) -> _Plan:
+              guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None,
+              token_stats=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1090,6 +1179,7 @@ class Stage:
         stop = _check_stop_ids(given(stop_token_ids, cfg.stop_token_ids), V)
         n_top = _check_logprobs(given(logprobs, cfg.logprobs))
         n_prompt = _check_prompt_logprobs(given(prompt_logprobs, cfg.prompt_logprobs))
+        token_stats = bool(given(_check_token_stats(token_stats), _check_token_stats(cfg.token_stats)))
         own_top_k, own_top_p, own_min_p = (cfg.top_k, cfg.top_p, cfg.min_p) if self.draft is None else \
             (cfg.target_top_k, cfg.target_top_p, cfg.target_min_p)
         min_p = check_per_prompt(given(min_p, own_min_p), n, "min_p")
@@ -1158,7 +1248,8 @@ class Stage:
                      inv_t=1.0 if greedy else float(np.float32(1.0 / temperature)), scalars=scalars, rows=rows,
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
                      edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, ngram_rows=ngram_rows,
-                     penalties=penalties, fsm=fsm, seeds=seeds, n_top=n_top, n_prompt=n_prompt)
+                     penalties=penalties, fsm=fsm, seeds=seeds, n_top=n_top, n_prompt=n_prompt,
+                     token_stats=token_stats)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -1178,7 +1269,7 @@ class Stage:
         dev = ids.device
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram = st.fsm, st.ngram
+        fsm, ngram, stat = st.fsm, st.ngram, st.stats
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1204,17 +1295,23 @@ class Stage:
                 pen.apply(logits)                                        # the penalties last: mask -> edit -> penalties
             n_acc, tok, lp = sampler.draw(logits, step)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
-            if top is not None:
+            if stat is not None:
+                stat.score(logits, None, n_acc, tok)                     # one pass: the statistics, and the table when it is on
+            elif top is not None:
                 top.score(logits)
             end.commit(None, None, n_acc, tok, lp, seq_len, tokens, lps, n_commit, cap)
             if top is not None:
                 top.commit(seq_len, n_commit)
+            if stat is not None:
+                stat.commit(seq_len, n_commit)
             if pen is not None:
                 pen.commit(tokens, seq_len, n_commit, cap)               # the committed tokens enter the history
             if fsm is not None:
                 fsm.commit(tokens, seq_len, n_commit, cap)               # ... and move the automaton
             if kept is not None:                                        # tests: the record, with the top-N rows behind it
-                self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
+                if top is not None:
+                    kept = dict(kept, **top.record(), n_commit=n_commit.clone())
+                self.step_inputs.append(kept if stat is None else dict(kept, **stat.record(), n_commit=n_commit.clone()))
             self.last_steps = step + 1
             if end.stops and (step + 1) % self.config.sync_every == 0 and end.done(seq_len, cap):
                 break
@@ -1241,7 +1338,7 @@ class Stage:
         Kd = cfg.draft_len
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram = st.fsm, st.ngram
+        fsm, ngram, stat = st.fsm, st.ngram, st.stats
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -1301,17 +1398,23 @@ class Stage:
                 pen.apply(t_out)                                        # row j sees the proposals 0 .. j - 1, as the draft's did
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
-            if top is not None:
+            if stat is not None:
+                stat.score(t_out, tok32, n_acc, drawn)                  # one pass: the statistics, and the table when it is on
+            elif top is not None:
                 top.score(t_out)                                        # the [B, K+1, V] output as returned, not a copy
             end.commit(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
             if top is not None:
                 top.commit(seq_len, n_commit)
+            if stat is not None:
+                stat.commit(seq_len, n_commit)
             if pen is not None:
                 pen.commit(tokens, seq_len, n_commit, cap)               # the committed tokens enter the history
             if fsm is not None:
                 fsm.commit(tokens, seq_len, n_commit, cap)               # ... and move the automaton
             if kept is not None:                                        # tests: the record, with the top-N rows behind it
-                self.step_inputs.append(kept if top is None else dict(kept, **top.record(), n_commit=n_commit.clone()))
+                if top is not None:
+                    kept = dict(kept, **top.record(), n_commit=n_commit.clone())
+                self.step_inputs.append(kept if stat is None else dict(kept, **stat.record(), n_commit=n_commit.clone()))
             steps += 1
             if steps % cfg.sync_every == 0 and end.done(seq_len, cap):
                 break

@@ -479,6 +479,44 @@ int asd_prompt_logprobs(const void* logits, int dtype, int64_t ld_seq, int64_t l
                         float* lp /*[B,T]*/, int32_t* rank /*[B,T]*/,
                         int32_t* top_id /*[B,T,N]; may be NULL when N == 0*/, float* top_lp /*likewise*/,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Token statistics: per row of a step's [B, K1, V] logits that may be COMMITTED, the rank of the committed token, the arg-max
+ * and its log-prob, the entropy of the row's softmax and optionally the row's top-N table, in asd_top_logprobs' one streaming
+ * pass.  All figures are of the UNTRUNCATED softmax of x * inv_temperature over the whole vocabulary.
+ * logits: asd_top_logprobs' addressing, read in place, never written; 1 <= K1 <= ASD_MAX_DRAFT_LEN + 1.
+ * With a = clamp(n_acc[b], 0, K1 - 1): rows j <= a are LIVE; live row j scores g = tok[b*ld_tok + j] for j < a and
+ * g = drawn[b] for j == a (what the step's commit may commit; K1 == 1, n_acc == 0 is a stage without a draft: tok may be
+ * NULL).  Rows j > a are never committed: no pass is made over them and their outputs are NEUTRAL: rank 0, arg-max id -1,
+ * entropy 0.0, max log-prob 0.0, table slots (-1, -inf).
+ * Per live row (b, j), x the stored row:
+ *   stat_id[b,j,0]  = rank of g: 1 + #{v : x[v] > x[g], or x[v] == x[g] and v < g} (asd_prompt_logprobs' definition and count:
+ *                     exact, the same in every launch geometry); 0 when g is outside [0, V) (never dereferenced) or x[g] is NaN.
+ *   stat_id[b,j,1], stat_val[b,j,1] = the arg-max id (ties: the lowest id) and its log-prob: the bits of asd_top_logprobs'
+ *                     slot 0 at the same inv_temperature and split count; a row without a finite logit: (-1, -inf).
+ *   stat_val[b,j,0] = the entropy H = -sum_v p_v ln p_v in nats.  A -inf element carries no mass; s == 0 (no finite logit) or
+ *                     any NaN element: NaN.  Its partial sums are merged in the fixed lane / wave / slice order of the lse's.
+ *   top_id / top_lp [b,j,:N]: what asd_top_logprobs writes for the row at the same inv_temperature, N and split count, bit
+ *                     for bit.  N == 0: no table is written; top_id / top_lp may be NULL.
+ * inv_t_rows: DEVICE array [B] of per-sequence 1 / T as in asd_top_logprobs_rows (a sequence returns the bits the scalar call
+ * returns for it), or NULL: the scalar inv_temperature holds.  With inv_t_rows the scalar is ignored.
+ * stat_id / stat_val are [B, K1, 2], so asd_commit_top_logprobs with N = 2 moves row j to the step's j-th committed token.
+ * splits and the workspace: asd_prompt_logprobs' (sized for the split count the launch USES; whole rows need 256 bytes).
+ * Status, in this order: NULL stat_id / stat_val (NULL top_id / top_lp with N > 0), inv_temperature not > 0 (without
+ * inv_t_rows), negative sizes: invalid argument; B == 0 or K1 == 0: ASD_OK, nothing launched; V == 0: invalid argument;
+ * unknown dtype: unsupported; N > ASD_MAX_TOP_LOGPROBS, splits outside [0, ASD_MAX_SPLITS], K1 > ASD_MAX_DRAFT_LEN + 1:
+ * unsupported; NULL logits / n_acc / drawn / workspace, NULL tok with K1 > 1, ld_row < V, ld_seq < K1*ld_row,
+ * ld_tok < K1 - 1 (K1 > 1): invalid argument; a row of 2 GiB or more: unsupported; logits not aligned to the element size:
+ * alignment; workspace misaligned (256): workspace; B*K1*splits > INT32_MAX: unsupported; workspace too small: workspace.
+ * ---------------------------------------------------------------------------------------- */
+size_t asd_token_stats_workspace_bytes(int B, int K1, int V, int dtype, int splits);   /* a multiple of 256; 256 for empty or invalid sizes */
+int asd_token_stats(const void* logits, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                    const int32_t* tok /*[B, ld_tok]; NULL iff K1 == 1*/, int64_t ld_tok,
+                    const int32_t* n_acc /*[B]*/, const int32_t* drawn /*[B]*/,
+                    float inv_temperature, const float* inv_t_rows /*[B] device, or NULL*/,
+                    int N /*0..ASD_MAX_TOP_LOGPROBS*/, int splits /*0 = heuristic*/,
+                    int32_t* stat_id /*[B,K1,2]: rank, arg-max id*/, float* stat_val /*[B,K1,2]: entropy, max log-prob*/,
+                    int32_t* top_id /*[B,K1,N]; may be NULL when N == 0*/, float* top_lp /*likewise*/,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* The table of a step follows the step's commit (RESEARCH_PROTOCOL.md:272-277: one [N] row per GENERATED token).  Runs behind
  * asd_commit_step_lp / asd_commit_step_stop of the same step and reads their outputs: seq_len[b] AFTER the commit and

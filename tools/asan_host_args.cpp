@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows and asd_prompt_logprobs in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -595,6 +595,63 @@ int main() {
         EXPECT(PROMPT(rows + 2, BF16, lds, ldr, B, T, VP, i32, ldt, nullptr, 1.0f, NP, 1, f32, i32, i32, f32, p, 255), ASD_ERR_WORKSPACE); // (an element-aligned base and a NULL `first` are valid)
         EXPECT(PROMPT(p, BF16, int64_t{VP} << 10, ldr, 1 << 20, 1 << 10, VP, i32, 1 << 10, i32, 1.0f, NP, 4, f32, i32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // B*T*splits > INT32_MAX
 #undef PROMPT
+    }
+
+    // ---- asd_token_stats: asd_prompt_logprobs' order with its own checks (NULL tok with K1 > 1, ld_tok, n_acc / drawn, the draft
+    // length's bound on K1, inv_t_rows in place of the scalar) and the size query: asd_prompt_logprobs' byte counts
+    {
+        const int K1 = 9, VS = 1000, NS = 5;
+        const int64_t ldr = VS, lds = static_cast<int64_t>(K1) * VS, ldk = K1 - 1;
+        const size_t ws64 = asd_token_stats_workspace_bytes(B, K1, VS, BF16, ASD_MAX_SPLITS);
+        const size_t ws2 = asd_token_stats_workspace_bytes(B, K1, VS, BF16, 2);
+        if (ws64 % 256 != 0 || ws2 % 256 != 0 || ws2 >= ws64 || asd_token_stats_workspace_bytes(B, K1, VS, BF16, 1) != 256 ||
+            asd_token_stats_workspace_bytes(0, K1, VS, BF16, 0) != 256 || asd_token_stats_workspace_bytes(B, K1, VS, 99, 0) != 256 ||
+            ws64 != asd_prompt_logprobs_workspace_bytes(B, K1, VS, BF16, ASD_MAX_SPLITS) ||
+            ws2 != asd_prompt_logprobs_workspace_bytes(B, K1, VS, BF16, 2)) {
+            std::printf("FAIL token_stats workspace sizes %zu %zu\n", ws2, ws64);
+            ++failures;
+        }
+#define STATS(x_, dt_, lds_, ldr_, B_, K1_, V_, tok_, ldk_, acc_, drawn_, inv_t_, rows_, N_, splits_, sid_, sval_, id_, tlp_, ws_, wsb_) \
+    asd_token_stats(x_, dt_, lds_, ldr_, B_, K1_, V_, tok_, ldk_, acc_, drawn_, inv_t_, rows_, N_, splits_, sid_, sval_, id_, tlp_, ws_, wsb_, nullptr)
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, nullptr, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // stat_id
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, nullptr, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // stat_val
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, nullptr, f32, p, ws64), ASD_ERR_INVALID_ARG);   // top_id with N > 0
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, nullptr, p, ws64), ASD_ERR_INVALID_ARG);   // top_lp with N > 0
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, 0, 2, i32, f32, nullptr, nullptr, p, 0), ASD_ERR_WORKSPACE);     // N == 0 needs no table
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 0.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);       // temperature
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, NAN, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, NAN, f32, NS, 2, i32, f32, i32, f32, p, 0), ASD_ERR_WORKSPACE);                 // ... which inv_t_rows replaces
+        EXPECT(STATS(p, BF16, lds, ldr, -1, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);      // negative sizes
+        EXPECT(STATS(p, BF16, lds, ldr, B, -1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, -1, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, -1, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);
+        EXPECT(STATS(nullptr, 99, 0, 0, 0, K1, VS, nullptr, 0, nullptr, nullptr, 1.0f, nullptr, 99, 99, nullptr, nullptr, nullptr, nullptr, nullptr, 0), ASD_OK);   // B == 0: nothing launched
+        EXPECT(STATS(p, BF16, 0, ldr, B, 0, VS, nullptr, 0, i32, i32, 1.0f, nullptr, NS, 0, nullptr, nullptr, nullptr, nullptr, p, 0), ASD_OK);        // K1 == 0 likewise
+        EXPECT(STATS(p, BF16, 0, 0, B, K1, 0, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);            // V == 0
+        EXPECT(STATS(p, 99, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);         // dtype
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, ASD_MAX_TOP_LOGPROBS + 1, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // N
+        EXPECT(STATS(p, BF16, lds, ldr - 1, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, ASD_MAX_TOP_LOGPROBS + 1, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // ... before the strides
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, -1, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);      // splits
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, ASD_MAX_SPLITS + 1, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);
+        EXPECT(STATS(p, BF16, static_cast<int64_t>(ASD_MAX_DRAFT_LEN + 2) * VS, ldr, B, ASD_MAX_DRAFT_LEN + 2, VS, i32, ASD_MAX_DRAFT_LEN + 1, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // K1 above the draft length's bound
+        EXPECT(STATS(nullptr, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG); // logits
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, nullptr, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // tok with K1 > 1
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, nullptr, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // n_acc
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, nullptr, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // drawn
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, nullptr, ws64), ASD_ERR_INVALID_ARG); // workspace
+        EXPECT(STATS(p, BF16, lds, ldr - 1, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // ld_row < V
+        EXPECT(STATS(p, BF16, lds - 1, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // ld_seq < K1 ld_row
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk - 1, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // ld_tok < K1 - 1
+        EXPECT(STATS(rows + 1, BF16, lds, ldr, B, K1, VS, i32, ldk - 1, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_INVALID_ARG);   // ... before alignment
+        EXPECT(STATS(rows + 1, BF16, static_cast<int64_t>(K1) << 30, int64_t{1} << 30, B, K1, 1 << 30, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // a 2 GiB row, before alignment
+        EXPECT(STATS(rows + 1, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_ALIGNMENT);  // below the element size
+        EXPECT(STATS(rows + 2, 0 /*f32*/, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, p, ws64), ASD_ERR_ALIGNMENT);
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 0, i32, f32, i32, f32, rows + 16, ws64), ASD_ERR_WORKSPACE); // misaligned workspace
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, ASD_MAX_SPLITS, i32, f32, i32, f32, p, ws64 - 1), ASD_ERR_WORKSPACE);   // too small
+        EXPECT(STATS(p, BF16, lds, ldr, B, K1, VS, i32, ldk, i32, i32, 1.0f, nullptr, NS, 2, i32, f32, i32, f32, p, ws2 - 1), ASD_ERR_WORKSPACE);
+        EXPECT(STATS(rows + 2, BF16, VS, ldr, B, 1, VS, nullptr, 0, i32, i32, 1.0f, nullptr, NS, 1, i32, f32, i32, f32, p, 255), ASD_ERR_WORKSPACE);   // (K1 == 1: a NULL tok and any ld_tok are valid)
+        EXPECT(STATS(p, BF16, static_cast<int64_t>(ASD_MAX_DRAFT_LEN + 1) * VS, ldr, 1 << 20, ASD_MAX_DRAFT_LEN + 1, VS, i32, ASD_MAX_DRAFT_LEN, i32, i32, 1.0f, nullptr, NS, ASD_MAX_SPLITS, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // B*K1*splits > INT32_MAX
+#undef STATS
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
