@@ -25,6 +25,7 @@ MAX_LOGIT_EDITS = 1024
 MAX_STOP_SEQS, MAX_STOP_SEQ_LEN = 16, 8
 MAX_BAD_WORDS, MAX_BAD_WORD_LEN = 256, 8
 MAX_NGRAM, NGRAM_SLICE = 8, 2048
+ENTROPY_CUT_REC_BYTES = 12            # ASD_ENTROPY_CUT_REC_BYTES: one {inv_t f32, mode i32, value f32} record of asd_entropy_cut_rows
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
@@ -118,6 +119,7 @@ SIGNATURES = {
     "asd_logit_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _vp]),
     "asd_bad_words_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
     "asd_no_repeat_ngram_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
+    "asd_entropy_cut_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp]),
     "asd_fsm_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_advance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_commit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _vp, _i64, _vp, _vp, _i, _vp]),

@@ -41,6 +41,7 @@ SOURCES = {
     "logit_mask.hip": [],                         # bit tests and stores of a constant: no floating-point arithmetic at all
     "bad_words.hip": [],                          # integer compares and stores of a constant: no floating-point arithmetic at all
     "no_repeat_ngram.hip": [],                    # integer compares and stores of a constant: no floating-point arithmetic at all
+    "entropy_cut.hip": ["-ffp-contract=off"],     # token_stats.hip's (m2, s, u) recurrences, and keys a reference must be able to restate
     "fsm.hip": [],                                # logit_mask.hip's write stream and integer searches: no floating-point arithmetic
     "penalty.hip": ["-ffp-contract=off"],         # y - freq * c must round twice, as the header and the numpy reference state it
     "lm_head_verify.hip": ["-ffp-contract=off"],  # ends in the same finish_row arithmetic as verify_accept.hip

@@ -537,6 +537,20 @@ class HipOps:
         tensor, behind bad_words_rows and in front of logit_edit_rows, and only when some row of the call has n > 0."""
         return self.K.no_repeat_ngram_rows(logits, ngram, tokens, seq_len, max_len, step_tok, n_prev)
 
+    @traced("pack_entropy_cut")
+    def pack_entropy_cut(self, inv_t, modes, values, device):
+        """Every row's 1 / temperature, mode (0 off, 1 typical_p, 2 epsilon_cutoff, 3 eta_cutoff) and value -> the device table
+        of entropy_cut_rows (kernels.pack_entropy_cut: one upload per generate call and side)."""
+        return self.K.pack_entropy_cut(inv_t, modes, values, device)
+
+    @traced("entropy_cut_rows")
+    def entropy_cut_rows(self, logits, cut):
+        """HF's typical_p / epsilon_cutoff / eta_cutoff ahead of the samplers (asd_entropy_cut_rows): logits [B, V] or
+        [B, K1, V] (any strides with a unit last stride) -> the same tensor, with every token at -inf that the row's cut removes
+        from softmax(x / T) of the row as it stands.  One launch, no workspace, no state; a stage loop makes the call once per
+        logits tensor, behind penalty_rows and directly ahead of the draw, and only when some row of the call has a cut."""
+        return self.K.entropy_cut_rows(logits, cut)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

@@ -1807,3 +1807,64 @@ def no_repeat_ngram_rows(logits: torch.Tensor, ngram: NoRepeatNgram, tokens: tor
                                          int(n_prev), _stream())
     B.check("asd_no_repeat_ngram_rows", rc)
     return logits
+
+
+# ------------------------------------------------------------------------------- entropy cuts (typical_p / epsilon_cutoff / eta_cutoff)
+CUT_OFF, CUT_TYPICAL, CUT_EPSILON, CUT_ETA = 0, 1, 2, 3
+_CUT_REC = np.dtype([("inv_t", np.float32), ("mode", np.int32), ("value", np.float32)])
+
+
+@dataclass
+class EntropyCut:
+    """The table of asd_entropy_cut_rows on the device (pack_entropy_cut): B records {inv_t f32, mode i32, value f32} of 12
+    bytes, as a uint8 [B, 12] tensor; `modes`: the host's copy of the rows' modes."""
+    table: torch.Tensor
+    modes: Tuple[int, ...]
+    B: int
+
+
+def check_entropy_cut_rows(inv_t, modes, values) -> np.ndarray:
+    """The host side of pack_entropy_cut: every row's 1 / temperature (a positive finite number), mode (0 off, 1 typical,
+    2 epsilon, 3 eta) and value (inside (0, 1) where the row is on) -> the records, a numpy structured array."""
+    inv_t, modes, values = list(inv_t), list(modes), list(values)
+    if not len(inv_t) == len(modes) == len(values):
+        raise ValueError(f"{len(inv_t)} temperatures, {len(modes)} modes and {len(values)} values must describe the same rows")
+    rec = np.zeros(len(modes), dtype=_CUT_REC)
+    for b, (t, m, v) in enumerate(zip(inv_t, modes, values)):
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (CUT_OFF, CUT_TYPICAL, CUT_EPSILON, CUT_ETA):
+            raise ValueError(f"row {b}: the mode must be 0 (off), 1 (typical), 2 (epsilon) or 3 (eta), got {m!r}")
+        t32 = np.float32(t)
+        if isinstance(t, bool) or not (t32 > 0.0 and t32 < np.float32(3.0e38)):
+            raise ValueError(f"row {b}: 1 / temperature must be a positive finite number, got {t!r}")
+        v32 = np.float32(v)
+        if int(m) != CUT_OFF and (isinstance(v, bool) or not 0.0 < float(v32) < 1.0):
+            raise ValueError(f"row {b}: the value of a row that is on must lie inside (0, 1), got {v!r}")
+        rec[b] = (t32, int(m), v32 if int(m) != CUT_OFF else np.float32(0.0))
+    return rec
+
+
+def pack_entropy_cut(inv_t, modes, values, device) -> EntropyCut:
+    """The table of entropy_cut_rows from host lists, checked BEFORE anything is uploaded."""
+    rec = check_entropy_cut_rows(inv_t, modes, values)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _CUT_REC.itemsize).copy()).to(device)
+    return EntropyCut(table, tuple(int(m) for m in rec["mode"]), len(rec))
+
+
+def entropy_cut_rows(logits: torch.Tensor, cut: EntropyCut) -> torch.Tensor:
+    """Cut in place (asd_entropy_cut_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  Row (b, j) under record b: with p = softmax(x * inv_t) and its entropy H, typical-p keeps
+    the smallest set of tokens closest to H in -ln p whose mass reaches the value (ties kept), epsilon cuts p < value, eta cuts
+    p < min(value, sqrt(value) exp(-H)); both keep every token that ties the maximum.  A cut token becomes -inf."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if cut.B != Bv:
+        raise ValueError(f"the cuts were packed for {cut.B} rows; logits have {Bv}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_entropy_cut_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], Bv, K1, V, ld_seq, ld_row,
+                                     _dev(cut.table, "table", torch.uint8), _stream())
+    B.check("asd_entropy_cut_rows", rc)
+    return logits

@@ -44,6 +44,8 @@ number for the batch or one per request, kept by the request through every regro
 `no_repeat_ngram_size=` (HF generate's; serving/stages.py, NO REPEAT N-GRAM) travels like a penalty: one int in [0, 8] for the
 batch or one per request, kept by the request through every regrouping, handed on only when it is set (here or as
 `PipelineConfig.no_repeat_ngram_size`).
+`PipelineConfig.typical_p` / `epsilon_cutoff` / `eta_cutoff` (HF's warpers of those names; serving/stages.py, ENTROPY CUTS) are
+configuration only: a value that is set is handed to every stage's generate call as the keyword of that name, None is not passed.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -213,6 +215,11 @@ class PipelineConfig:
     # HF generate's no_repeat_ngram_size, handed to stage.generate(no_repeat_ngram_size=) unless the call names its own; None:
     # the keyword is not passed
     no_repeat_ngram_size: Optional[int] = None
+    # HF's typical_p / epsilon_cutoff / eta_cutoff, handed to stage.generate(typical_p=, epsilon_cutoff=, eta_cutoff=); None: the
+    # keyword is not passed (serving/stages.py, ENTROPY CUTS)
+    typical_p: Optional[float] = None
+    epsilon_cutoff: Optional[float] = None
+    eta_cutoff: Optional[float] = None
     # vLLM's prompt_logprobs (serving/stages.py, PROMPT LOG-PROBS), handed to every stage.generate(prompt_logprobs=): each
     # stage's entry then carries "prompt_logprobs" and "prompt_ranks"; not fed to the predictor.  None: the keyword is not passed
     prompt_logprobs: Optional[int] = None
@@ -253,6 +260,9 @@ class PipelineConfig:
             kw["stop_sequences"] = tuple(e if isinstance(e, str) else tuple(int(t) for t in e) for e in sec["stop_sequences"])
         if sec.get("no_repeat_ngram_size") is not None:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
+        for name in ("typical_p", "epsilon_cutoff", "eta_cutoff"):
+            if sec.get(name) is not None:
+                kw[name] = float(sec[name])
         if sec.get("prompt_logprobs") is not None:
             kw["prompt_logprobs"] = int(sec["prompt_logprobs"])
         if sec.get("token_stats") is not None:
@@ -607,6 +617,9 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["stop_sequences"] = list(cfg.stop_sequences)
                 if cfg.no_repeat_ngram_size is not None:                # (the call's own value, shared or per request, replaces it below)
                     stop_kw["no_repeat_ngram_size"] = int(cfg.no_repeat_ngram_size)
+                for name in ("typical_p", "epsilon_cutoff", "eta_cutoff"):      # the entropy cuts: only those that are set
+                    if getattr(cfg, name) is not None:
+                        stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:
                     stop_kw["prompt_logprobs"] = cfg.prompt_logprobs
                 if cfg.token_stats is not None:

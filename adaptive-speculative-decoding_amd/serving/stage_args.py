@@ -117,6 +117,37 @@ def _check_min_p(v, name: str = "min_p") -> float:
     return float(v)
 
 
+CUT_OFF, CUT_TYPICAL, CUT_EPSILON, CUT_ETA = 0, 1, 2, 3      # ASD_CUT_* of include/asd_hip.h: a row's mode (ENTROPY CUTS)
+
+
+def check_entropy_cuts(typical_p, epsilon_cutoff, eta_cutoff, n: int) -> List[Tuple[int, float]]:
+    """generate's `typical_p`, `epsilon_cutoff` and `eta_cutoff` (HF's warpers of those names): each one number for all `n`
+    prompts or a sequence of n numbers -> every row's (mode, value).  typical_p lies in [0, 1], 0 and 1 are off; the other two
+    lie in [0, 1), 0 is off.  A row has at most one mode.  A bool, a NaN, a value outside its range, the wrong length and a row
+    with two modes ("not built") raise ValueError."""
+    def number(name, top_closed):
+        def one(v):
+            ok = not isinstance(v, bool) and isinstance(v, _NUMBER) and (0.0 <= float(v) <= 1.0 if top_closed else 0.0 <= float(v) < 1.0)
+            if not ok:                                                           # (NaN included)
+                raise ValueError(f"{name} must be a number in [0, 1{']' if top_closed else ')'}, got {v!r}")
+            v = float(np.float32(v))                                             # the value the device record holds
+            return v if 0.0 < v < 1.0 else 0.0
+        return one
+    cols = []
+    for name, value, closed in (("typical_p", typical_p, True), ("epsilon_cutoff", epsilon_cutoff, False),
+                                ("eta_cutoff", eta_cutoff, False)):
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+        cols.append(_per_prompt(value, n, number(name, closed), f"{name} values"))
+    rows = []
+    for b, values in enumerate(zip(*cols)):
+        on = [(mode, v) for mode, v in zip((CUT_TYPICAL, CUT_EPSILON, CUT_ETA), values) if v > 0.0]
+        if len(on) > 1:
+            raise ValueError(f"prompt {b}: more than one of typical_p, epsilon_cutoff and eta_cutoff on one row is not built")
+        rows.append(on[0] if on else (CUT_OFF, 0.0))
+    return rows
+
+
 def _check_sampling_value(v, name: str):
     """One temperature / top_p / top_k / min_p value of generate (PER-REQUEST SAMPLING)."""
     if name == "top_k":

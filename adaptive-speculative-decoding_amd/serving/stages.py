@@ -360,6 +360,40 @@ against 67.3 us for asd_prompt_logprobs at N = 0 (ratio 1.15, more than that pas
 uniform in 0..K 52.9 / 45.1 us; plus one commit launch per step.  NOT BUILT: serving/hierarchy.py's loop; statistics of the
 draft model's rows.
 
+ENTROPY CUTS.  `generate(typical_p=, epsilon_cutoff=, eta_cutoff=)` are HF's TypicalLogitsWarper, EpsilonLogitsWarper and
+EtaLogitsWarper with min_tokens_to_keep = 1: the truncations that are no threshold on the sorted probabilities, because they
+need the row's entropy or its exact probabilities.  Each takes one number for the call or one per prompt; typical_p lies in
+[0, 1] and is off at 0 and 1, the other two lie in [0, 1) and are off at 0; None takes the configuration's value:
+StageConfig.typical_p / epsilon_cutoff / eta_cutoff are the stage's own draws at stage 0 and the proposals its model makes for
+the stage above, target_typical_p / target_epsilon_cutoff / target_eta_cutoff a verifying stage's own distribution -- the rule
+of min_p / target_min_p; all default to off.  A row has at most one of the three.  INPUT: p = softmax(x / T) of the row behind
+the mask, the automaton, the bad words, the n-gram rule, the edits and the penalties, at the row's temperature (its own on the
+rows route) and untruncated; a -inf element carries no mass and stays -inf.  With H = -sum p ln p:
+  typical_p = m       d_v = |-ln p_v - H|; d* is the smallest value with sum{p_v : d_v <= d*} >= m; token v is kept iff
+                      d_v <= d*.  Every tie at d* is kept; if the mass never reaches m everything is kept; the arg-max MAY be
+                      cut, which no other route here can express.
+  epsilon_cutoff = e  token v is cut iff p_v < e and x_v < x_max: every token that ties the maximum survives (HF's top-1 clause).
+  eta_cutoff = e      the same with min(e, sqrt(e) exp(-H)) in place of e.
+A cut token's logit becomes -inf in place; nothing else is written; a row with a NaN element or without a finite one is left as
+it is.  It is one more in-place pass of the form of the others (asd_entropy_cut_rows; the rows' {1 / T, mode, value} records are
+uploaded once per call and side through ops.pack_entropy_cut), and it runs LAST of them, directly ahead of the draw, propose or
+settle call, and so ahead of top.score and stat.score, which read the same tensor: the order is mask -> fsm -> bad words ->
+n-gram -> edit -> penalties -> ENTROPY CUT -> temperature -> top-k -> top-p -> min-p.  Top-k, top-p and min-p then act on the
+SURVIVORS.  THIS IS NOT HF's ORDER: HF runs Temperature -> TopK -> TopP -> MinP -> Typical -> Epsilon -> Eta; llama.cpp's
+default sampler chain places typical ahead of top-p, as this does.  With top-k, top-p and min-p off the kept set is HF's
+(tests/test_entropy_cut_ref.py holds the reference to transformers' three classes, and to HF's classes chained in this order).
+At a verifying stage the draft rows receive the DRAFT stage's configured cut and the target's [B, K+1, V] output the call's
+own, both with the row's temperature; the samplers, the verify, the residual draw and the commit are untouched and only ever
+see logits that already carry the cut, so the draft -> verify -> residual chain stays lossless against the cut target
+distribution by the argument of LOGIT EDITS.  As with every other pass the returned log-probs, the top-N tables and the token
+statistics describe the distribution behind the cut (unfillable table slots hold -1 / -inf, as under an allow-list).  Greedy
+decoding ignores all three, as it ignores min-p, and makes no call; a call whose every row is off makes exactly the ops calls it
+made before.  ValueError before any launch and before the prompts are encoded: a bool, a NaN, a value outside its range, the
+wrong length, two of the three on one row (NOT BUILT: HF applies them in sequence).  COST (profiles/entropy_cut.json: B = 32, K1 = 9,
+V = 152064, bf16, kernel time): epsilon mode 63.2 us and typical mode 175.0 us against 62.4 us for asd_token_stats with N = 0 on the
+same tensor (ratios 1.01, inside that pass's run-to-run spread of 0.10, and 2.81).  NOT
+BUILT beside that: per-request values of the DRAFT side, and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -381,7 +415,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_entropy_cuts, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -413,6 +447,13 @@ class StageConfig:
     target_top_k: int = 0
     min_p: float = 0.0                       # min-p of the stage's own draws, behind (top_k, top_p); 0: off (module docstring)
     target_min_p: float = 0.0                # min-p of a verifying stage's own distribution, behind (target_top_k, target_top_p)
+    # the entropy cuts (module docstring, ENTROPY CUTS), by the rule of min_p / target_min_p; at most one of the three per side
+    typical_p: float = 1.0                   # HF's typical_p of the stage's own draws and of its proposals; 0 and 1: off
+    epsilon_cutoff: float = 0.0              # HF's epsilon_cutoff of the same rows; 0: off
+    eta_cutoff: float = 0.0                  # HF's eta_cutoff of the same rows; 0: off
+    target_typical_p: float = 1.0            # the three of a verifying stage's own distribution
+    target_epsilon_cutoff: float = 0.0
+    target_eta_cutoff: float = 0.0
     draft_len: int = 8
     seed: int = 0
     sync_every: int = 4
@@ -460,6 +501,8 @@ class _Plan(NamedTuple):
     n_top: int
     n_prompt: Optional[int] = None           # prompt_logprobs: None off, else the table's N in [0, 8]
     token_stats: bool = False                # the per-token statistics and the predictor's feature batch (TOKEN STATS)
+    cut_rows: Optional[list] = None          # every row's (mode, value) of the stage's own entropy cut; None: every row off
+    cut_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, value) of the draft stage's configured cut
 
 
 class _EditState:
@@ -522,6 +565,22 @@ class _NgramState:
         if self.step_tok is None:
             return self.ops.no_repeat_ngram_rows(logits, self.packed, tokens, seq_len, self.cap)
         return self.ops.no_repeat_ngram_rows(logits, self.packed, tokens, seq_len, self.cap, self.step_tok, n_prev)
+
+
+class _CutState:
+    """What a generate call with an entropy cut keeps for one side (its own rows, or a verifying stage's draft rows): the
+    rows' {1 / temperature, mode, value} records on the device, uploaded once.  `apply` is the loops' one call per logits
+    tensor, the last one ahead of the draw, propose or settle call (module docstring, ENTROPY CUTS)."""
+
+    def __init__(self, ops, rows, inv_t: List[float], device):
+        self.ops = ops
+        self.packed = ops.pack_entropy_cut(inv_t, [m for m, _ in rows], [v for _, v in rows], device)
+
+    def apply(self, logits: torch.Tensor, keep: bool = False) -> Optional[torch.Tensor]:
+        """logits [B, V] or [B, K+1, V], cut in place.  keep: the tests' record -- a clone of the tensor as it entered."""
+        entered = logits.clone() if keep else None
+        self.ops.entropy_cut_rows(logits, self.packed)
+        return entered
 
 
 class _FsmState:
@@ -953,6 +1012,10 @@ class _CallState:
         self.stats = _StatsState(ops, self.top, plan.inv_t, B, P + plan.max_tokens, dev,
                                  self.sampler.table if plan.rows else None) if plan.token_stats else None
         self.prompt = _PromptState(ops, plan.n_prompt, ids, prompt_ids) if plan.n_prompt is not None else None
+        # the entropy cuts: `cut` on the stage's own rows, `cut_draft` on a verifying stage's draft rows; both with the rows' temperatures
+        inv_t = list(plan.rows[0]) if plan.rows else [plan.inv_t] * B
+        self.cut = _CutState(ops, plan.cut_rows, inv_t, dev) if plan.cut_rows else None
+        self.cut_draft = _CutState(ops, plan.cut_draft_rows, inv_t, dev) if plan.cut_draft_rows else None
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -982,6 +1045,8 @@ class Stage:
             raise ValueError("draft_len must be in [1, 64]")
         _check_min_p(config.min_p, "min_p")
         _check_min_p(config.target_min_p, "target_min_p")
+        check_entropy_cuts(config.typical_p, config.epsilon_cutoff, config.eta_cutoff, 1)
+        check_entropy_cuts(config.target_typical_p, config.target_epsilon_cutoff, config.target_eta_cutoff, 1)
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -1030,7 +1095,9 @@ class Stage:
                  guided_choice_per_prompt=None,
                  no_repeat_ngram_size=None,
                  prompt_logprobs: Optional[int] = None,
-                 token_stats: Optional[bool] = None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 token_stats: Optional[bool] = None,
+                 typical_p=None, epsilon_cutoff=None,
+                 eta_cutoff=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1127,14 +1194,27 @@ class Stage:
         stats["predictor_features"] (float32 [B, 256]: FeatureExtractor.extract_device on the two float arrays, formed on the
         device).  The distribution is the one the top-N table describes: processed, temperature-scaled, UNTRUNCATED.  Off: none
         of the five keys and no extra call.  Tokens, log-probs and tables keep their bits; anything but None or a bool raises
-        ValueError (module docstring, TOKEN STATS)."""
+        ValueError (module docstring, TOKEN STATS).
+        `typical_p`, `epsilon_cutoff`, `eta_cutoff` (HF's warpers of those names, min_tokens_to_keep = 1): None = the
+        configuration's (StageConfig.typical_p / epsilon_cutoff / eta_cutoff at stage 0, the target_* fields at a verifying
+        stage: the rule of `min_p`); one number for every prompt or one per prompt.  typical_p lies in [0, 1] (0 and 1: off),
+        the other two in [0, 1) (0: off); a row has at most one of the three.  They act on p = softmax(x / T) of the row behind
+        every other processor, at the row's temperature and untruncated, with its entropy H: typical_p = m keeps the tokens
+        whose |-ln p_v - H| is smallest until their mass reaches m (ties kept; the most likely token may be cut);
+        epsilon_cutoff = e cuts p_v < e; eta_cutoff = e cuts p_v < min(e, sqrt(e) exp(-H)); the last two keep every token
+        that ties the maximum.  The cut runs LAST of the processors and AHEAD of top-k, top-p and min-p, which act on the
+        survivors -- llama.cpp's order, not HF's (Temperature -> TopK -> TopP -> MinP -> Typical -> Epsilon -> Eta); with
+        those three off the kept set is HF's.  Log-probs, top-N tables and token statistics describe the distribution behind
+        the cut.  Greedy decoding ignores all three.  A bool, a NaN, a value outside its range, the wrong length and two of
+        them on one row raise ValueError (module docstring, ENTROPY CUTS)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
         plan = self._plan(prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
                           stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
                           repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
-                          guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats)
+                          guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats,
+                          typical_p, epsilon_cutoff, eta_cutoff)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1169,7 +1249,7 @@ class Stage:
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
               repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm=None,
               guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None,
-              token_stats=None) -> _Plan:
+              token_stats=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1230,6 +1310,11 @@ class Stage:
                      check_frequency_penalty(given(frequency_penalty, cfg.frequency_penalty), n))
         if all(r == 1.0 and p == 0.0 and f == 0.0 for r, p, f in zip(*penalties)):
             penalties = None                             # every row neutral: no state, no call
+        own_cuts = (cfg.typical_p, cfg.epsilon_cutoff, cfg.eta_cutoff) if self.draft is None else \
+            (cfg.target_typical_p, cfg.target_epsilon_cutoff, cfg.target_eta_cutoff)
+        cut_rows = check_entropy_cuts(*(given(v, d) for v, d in zip((typical_p, epsilon_cutoff, eta_cutoff), own_cuts)), n)
+        dcfg = None if self.draft is None else self.draft.config
+        cut_draft_rows = [] if dcfg is None else check_entropy_cuts(dcfg.typical_p, dcfg.epsilon_cutoff, dcfg.eta_cutoff, n)
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -1249,7 +1334,9 @@ class Stage:
                      stop=stop, row_seqs=row_seqs, finish_route=len(set(limits)) > 1 or bool(common) or any(own),
                      edit_rows=edit_rows, mask_rows=mask_rows, bad_rows=bad_rows, ngram_rows=ngram_rows,
                      penalties=penalties, fsm=fsm, seeds=seeds, n_top=n_top, n_prompt=n_prompt,
-                     token_stats=token_stats)
+                     token_stats=token_stats,
+                     cut_rows=cut_rows if not greedy and any(m for m, _ in cut_rows) else None,        # greedy ignores the cuts
+                     cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None)
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -1269,7 +1356,7 @@ class Stage:
         dev = ids.device
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram, stat = st.fsm, st.ngram, st.stats
+        fsm, ngram, stat, cut = st.fsm, st.ngram, st.stats, st.cut
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1293,8 +1380,11 @@ class Stage:
                 edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
             if pen is not None:
                 pen.apply(logits)                                        # the penalties last: mask -> edit -> penalties
+            cut_in = cut.apply(logits, self.keep_inputs) if cut is not None else None   # the entropy cut: behind every processor
             n_acc, tok, lp = sampler.draw(logits, step)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
+            if kept is not None and cut is not None:
+                kept["cut_in"] = cut_in
             if stat is not None:
                 stat.score(logits, None, n_acc, tok)                     # one pass: the statistics, and the table when it is on
             elif top is not None:
@@ -1338,7 +1428,7 @@ class Stage:
         Kd = cfg.draft_len
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram, stat = st.fsm, st.ngram, st.stats
+        fsm, ngram, stat, cut, cut_draft = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -1359,7 +1449,7 @@ class Stage:
             last2 = torch.stack([tokens[rows, L - 2], tokens[rows, L - 1]], 1).to(torch.int64)
             dl = draft.forward_ragged(last2, L - 2, window)[:, -1]
             sampler.start(steps)
-            toks = []
+            toks, cut_in_draft = [], []
             for k in range(Kd):
                 if sampler.dense:
                     dl = dl.contiguous()
@@ -1375,6 +1465,8 @@ class Stage:
                     edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
                 if pen is not None:
                     pen.apply(dl, k)                                    # ... and sees the proposals 0 .. k - 1 of this step
+                if cut_draft is not None:
+                    cut_in_draft.append(cut_draft.apply(dl, self.keep_inputs))   # the DRAFT stage's configured cut, last
                 toks.append(sampler.propose(dl, k))
                 if step_tok is not None:
                     step_tok[:, k] = toks[-1]
@@ -1396,8 +1488,14 @@ class Stage:
                 edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any slice
             if pen is not None:
                 pen.apply(t_out)                                        # row j sees the proposals 0 .. j - 1, as the draft's did
+            cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None    # the call's own cut on the K + 1 rows
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
+            if kept is not None and cut is not None:
+                kept["cut_in"] = cut_in
+            if kept is not None and cut_draft is not None:              # the draft rows as they entered and as they left the cut
+                kept["cut_in_draft"] = torch.stack(cut_in_draft, 1)
+                kept["cut_out_draft"] = torch.stack(sampler.dls, 1)
             if stat is not None:
                 stat.score(t_out, tok32, n_acc, drawn)                  # one pass: the statistics, and the table when it is on
             elif top is not None:

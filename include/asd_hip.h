@@ -718,6 +718,51 @@ int asd_no_repeat_ngram_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq,
                              const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Entropy cuts AHEAD of the samplers -- HF's TypicalLogitsWarper (`typical_p`), EpsilonLogitsWarper (`epsilon_cutoff`) and
+ * EtaLogitsWarper (`eta_cutoff`), each with min_tokens_to_keep = 1.  They are no threshold on the sorted probabilities: all
+ * three need the row's entropy or its exact probabilities, and typical-p may cut the arg-max.  One in-place pass, the last one
+ * ahead of the draw, applied alike to the draft's proposal rows and the target's K+1 rows; top-k, top-p and min-p then act on
+ * the survivors.
+ * logits: asd_no_repeat_ngram_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last
+ * stride, any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only.
+ * table: B records {float inv_t; int32 mode; float value} (asd_entropy_cut_rec, 12 bytes) on the device; all K1 rows of
+ * sequence b use record b.  The row's distribution is p = softmax(x * inv_t) of the row as it stands (whatever is -inf carries no
+ * mass and stays -inf), H = -sum p ln p its entropy in nats.
+ *   ASD_CUT_OFF (0): the row is not read.
+ *   ASD_CUT_TYPICAL (1), value = m in (0, 1): d_v = |-ln p_v - H|; d* is the smallest value with sum{p_v : d_v <= d*} >= m;
+ *     element v is cut iff d_v > d*.  Every tie at d* is kept; when the mass never reaches m nothing is cut; the arg-max may be.
+ *   ASD_CUT_EPSILON (2), value = e in (0, 1): element v is cut iff p_v < e and x_v < x_max (every element that ties the
+ *     maximum survives).
+ *   ASD_CUT_ETA (3), value = e in (0, 1): the same with min(e, sqrt(e) * exp(-H)) in place of e.
+ * A cut element becomes -inf of the dtype (0xFF80 bf16, 0xFC00 f16, -INFINITY f32); nothing else is written, and a 16-byte
+ * vector is stored only where a bit of it changes.  A row with a NaN or +inf element, or without a finite element, has no
+ * distribution and is left exactly as it is.  THE DATA CONTRACT: a record whose mode lies outside 0..3, whose value lies
+ * outside (0, 1) or whose inv_t is not a positive finite number skips its rows.
+ * Arithmetic: one workgroup of 1024 threads per (b, j).  The first sweep takes (m2, s, u) as asd_token_stats does (u: the
+ * entropy's running sum relative to the running maximum) and the exact maximum, merged lanes -> waves in a fixed order; then
+ * log2 p_v = fma(x_v, c2, -L.hi) - L.lo with c2 = float(log2(e) * inv_t) and L = m2 + log2 s in two floats.  Epsilon / eta:
+ * one more sweep compares log2 p_v with log2 of the bound.  Typical: the key of v is |fma(x_v, c2, -A.hi) - A.lo| with
+ * A = L - H / ln 2, and an ascending radix select (12 + 12 + 8 bits of the key's order-preserving integer) on the masses
+ * floor(p_v 2^40), summed in integer counters, finds the key at which the mass reaches floor(m 2^40); a last sweep cuts what lies
+ * above it.  The result depends on the row's bytes and its record only.  No workspace, no state.
+ * Status, in this order: negative B / K1 / V: invalid argument; B, K1 or V == 0: ASD_OK, nothing launched; unknown dtype,
+ * B*K1 > INT32_MAX, V * element size > INT32_MAX: unsupported; NULL logits / table, ld_row < V, ld_seq < K1*ld_row: invalid
+ * argument; logits not aligned to the element size, or table not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_CUT_OFF 0
+#define ASD_CUT_TYPICAL 1
+#define ASD_CUT_EPSILON 2
+#define ASD_CUT_ETA 3
+#define ASD_ENTROPY_CUT_REC_BYTES 12
+typedef struct asd_entropy_cut_rec {
+    float inv_t;   /* 1 / temperature of the sequence */
+    int32_t mode;  /* ASD_CUT_* */
+    float value;   /* typical_p, epsilon_cutoff or eta_cutoff */
+} asd_entropy_cut_rec;
+int asd_entropy_cut_rows(void* logits /*in/out*/, int dtype, int B, int K1, int V, int64_t ld_seq, int64_t ld_row,
+                         const asd_entropy_cut_rec* table /*[B]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /
  * structured-output back ends compile a set of answers, a regex or a schema to.  Inside a speculative step the mask of
  * position j depends on the proposals 0 .. j-1, which exist only on the device: so the state lives there, small kernels
