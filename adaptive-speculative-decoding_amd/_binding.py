@@ -26,6 +26,8 @@ MAX_STOP_SEQS, MAX_STOP_SEQ_LEN = 16, 8
 MAX_BAD_WORDS, MAX_BAD_WORD_LEN = 256, 8
 MAX_NGRAM, NGRAM_SLICE = 8, 2048
 ENTROPY_CUT_REC_BYTES = 12            # ASD_ENTROPY_CUT_REC_BYTES: one {inv_t f32, mode i32, value f32} record of asd_entropy_cut_rows
+DRY_MAX_MATCH, MAX_DRY_BREAKERS = 64, 32   # ASD_DRY_MAX_MATCH (CAP), ASD_MAX_DRY_BREAKERS
+DRY_REC_BYTES = 404                   # ASD_DRY_REC_BYTES: one asd_dry_rec {on, allowed_length, range, n_breakers, breakers[32], pen[65]}
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
@@ -120,6 +122,7 @@ SIGNATURES = {
     "asd_bad_words_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
     "asd_no_repeat_ngram_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
     "asd_entropy_cut_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp]),
+    "asd_dry_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
     "asd_fsm_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_advance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_commit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _vp, _i64, _vp, _vp, _i, _vp]),

@@ -551,6 +551,20 @@ class HipOps:
         logits tensor, behind penalty_rows and directly ahead of the draw, and only when some row of the call has a cut."""
         return self.K.entropy_cut_rows(logits, cut)
 
+    @traced("pack_dry")
+    def pack_dry(self, multipliers, bases, allowed_lengths, ranges, breakers, prompt_lens, P: int, device):
+        """Every row's DRY multiplier (0: off), base, allowed_length and range, the call's breaker ids and the rows' numbers of
+        real prompt ids, which end at index P of the token buffer -> the device arguments of dry_rows (kernels.pack_dry: the
+        records with their host-made penalty tables, one upload per generate call)."""
+        return self.K.pack_dry(multipliers, bases, allowed_lengths, ranges, breakers, prompt_lens, P, device)
+
+    @traced("dry_rows")
+    def dry_rows(self, logits, dry, tokens, seq_len, max_len, step_tok=None, n_prev: int = 0):
+        """The DRY repetition penalty ahead of the samplers (asd_dry_rows): logits [B, V] or [B, K1, V] (any row stride),
+        penalised in place; position j sees the row's real prompt ids, its committed tokens and the step's first n_prev + j
+        proposals."""
+        return self.K.dry_rows(logits, dry, tokens, seq_len, max_len, step_tok, n_prev)
+
     @traced("commit_step")
     def commit_step(self, tok, n_acc, drawn, seq_len, tokens, n_commit, max_len):
         self.K.commit_step(tok, n_acc, drawn, seq_len, tokens, n_commit, max_len=max_len)

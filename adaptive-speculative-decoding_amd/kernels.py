@@ -1868,3 +1868,116 @@ def entropy_cut_rows(logits: torch.Tensor, cut: EntropyCut) -> torch.Tensor:
                                      _dev(cut.table, "table", torch.uint8), _stream())
     B.check("asd_entropy_cut_rows", rc)
     return logits
+
+
+# ------------------------------------------------------------------------------- DRY (dry_multiplier / dry_base / dry_allowed_length / dry_range)
+_DRY_REC = np.dtype([("on", np.int32), ("allowed_length", np.int32), ("range", np.int32), ("n_breakers", np.int32),
+                     ("breakers", np.int32, (B.MAX_DRY_BREAKERS,)), ("pen", np.float32, (B.DRY_MAX_MATCH + 1,))])
+assert _DRY_REC.itemsize == B.DRY_REC_BYTES
+
+
+@dataclass
+class Dry:
+    """The per-row arguments of asd_dry_rows on the device (pack_dry): B records asd_dry_rec as a uint8 [B, 404] tensor;
+    row_start i32 [B], the index of every row's first real prompt id behind the left-padding, or None when no row has a
+    prompt id (row_start = P everywhere)."""
+    table: torch.Tensor
+    row_start: Optional[torch.Tensor]
+    P: int                                   # the padded prompt length the rows were packed for (`start` of the calls)
+    B: int                                   # rows the arguments were packed for
+
+
+def dry_penalties(multiplier: float, base: float, allowed_length: int) -> np.ndarray:
+    """pen[m], m = 0 .. DRY_MAX_MATCH, of one row: float32(multiplier * base ** (m - allowed_length)) from f64, 0 below
+    allowed_length; an overflow becomes +inf, which the kernel's clamp absorbs."""
+    pen = np.zeros(B.DRY_MAX_MATCH + 1, dtype=np.float64)
+    for m in range(int(allowed_length), B.DRY_MAX_MATCH + 1 if float(multiplier) > 0.0 else 0):
+        try:
+            pen[m] = float(multiplier) * float(base) ** (m - int(allowed_length))
+        except OverflowError:
+            pen[m] = np.inf
+    with np.errstate(over="ignore"):
+        return pen.astype(np.float32)
+
+
+def check_dry_rows(multipliers, bases, allowed_lengths, ranges, breakers, prompt_lens, P: int):
+    """The host side of pack_dry: every row's multiplier (finite, >= 0; 0: off), base (finite, >= 1), allowed_length (an int in
+    [1, DRY_MAX_MATCH]), range (an int in [0, 2^31); 0: the whole history) and number of real prompt ids in [0, P]; `breakers`:
+    at most MAX_DRY_BREAKERS distinct int32 token ids, shared by the rows -> (the records, a numpy structured array; the
+    row_start list with row_start[b] = P - prompt_lens[b])."""
+    cols = [list(c) for c in (multipliers, bases, allowed_lengths, ranges, prompt_lens)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("multipliers, bases, allowed_lengths, ranges and prompt_lens must describe the same rows")
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or not 0 <= int(P) < 2 ** 31:
+        raise ValueError(f"P must be an integer in [0, 2^31), got {P!r}")
+    ids = list(dict.fromkeys(breakers))
+    if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not -2 ** 31 <= int(t) < 2 ** 31 for t in ids):
+        raise ValueError(f"the breakers must be int32 token ids, got {breakers!r}")
+    if len(ids) > B.MAX_DRY_BREAKERS:
+        raise ValueError(f"{len(ids)} distinct breakers, at most {B.MAX_DRY_BREAKERS}")
+    rec = np.zeros(len(cols[0]), dtype=_DRY_REC)
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)   # noqa: E731
+    integer = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))                                        # noqa: E731
+    for b, (mul, base, allowed, rng, m) in enumerate(zip(*cols)):
+        if not number(mul) or float(mul) < 0.0:
+            raise ValueError(f"row {b}: the multiplier must be a finite number >= 0, got {mul!r}")
+        if not number(base) or float(base) < 1.0:
+            raise ValueError(f"row {b}: the base must be a finite number >= 1, got {base!r}")
+        if not integer(allowed) or not 1 <= int(allowed) <= B.DRY_MAX_MATCH:
+            raise ValueError(f"row {b}: allowed_length must be an integer in [1, {B.DRY_MAX_MATCH}], got {allowed!r}")
+        if not integer(rng) or not 0 <= int(rng) < 2 ** 31:
+            raise ValueError(f"row {b}: the range must be an integer in [0, 2^31), got {rng!r}")
+        if not integer(m) or not 0 <= int(m) <= int(P):
+            raise ValueError(f"row {b}: the prompt length must be an integer in [0, {int(P)}], got {m!r}")
+        rec[b]["on"], rec[b]["allowed_length"], rec[b]["range"], rec[b]["n_breakers"] = float(mul) > 0.0, int(allowed), int(rng), len(ids)
+        rec[b]["breakers"][:len(ids)] = ids
+        rec[b]["pen"] = dry_penalties(mul, base, allowed)
+    return rec, [int(P) - int(m) for m in cols[4]]
+
+
+def pack_dry(multipliers, bases, allowed_lengths, ranges, breakers, prompt_lens, P: int, device) -> Dry:
+    """The per-row arguments of dry_rows from host lists, checked BEFORE anything is uploaded (check_dry_rows): the records,
+    the pen tables included, and row_start.  One upload per generate call."""
+    rec, first = check_dry_rows(multipliers, bases, allowed_lengths, ranges, breakers, prompt_lens, P)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _DRY_REC.itemsize).copy()).to(device)
+    return Dry(table, None if all(f == int(P) for f in first) else torch.tensor(first, dtype=torch.int32).to(device), int(P), len(rec))
+
+
+def dry_rows(logits: torch.Tensor, dry: Dry, tokens: torch.Tensor, seq_len: torch.Tensor, max_len: int,
+             step_tok: Optional[torch.Tensor] = None, n_prev: int = 0) -> torch.Tensor:
+    """Penalise in place (asd_dry_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row stride
+    with unit stride along V.  With H = tokens[b, row_start[b]:seq_len[b]] ++ step_tok[b, :n_prev + j] (its last `range`
+    tokens), every token t that followed an earlier occurrence of H's last token loses pen[M_t] at position j, M_t the longest
+    backward match of such an occurrence with H's end (at most DRY_MAX_MATCH, cut at a breaker), where M_t >= allowed_length;
+    the result is clamped to the dtype's lowest finite value.  tokens i32 [B, >= max_len] contiguous; seq_len i32 [B]: the step's
+    lengths BEFORE its commit; step_tok i32 [B, n_tok] (unit stride along the proposals) or None."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    start = dry.P
+    if dry.B != Bv or tuple(seq_len.shape) != (Bv,):
+        raise ValueError(f"the DRY records were packed for {dry.B} rows and seq_len must be int32 [B]; logits have {Bv} rows")
+    if tokens.dim() != 2 or tokens.shape[0] != Bv or not 0 <= start <= int(max_len) <= tokens.shape[1]:
+        raise ValueError(f"tokens must be int32 [B, >= max_len] and 0 <= start <= max_len, got {tuple(tokens.shape)}, {start}, {max_len}")
+    ld_tok = n_tok = 0
+    if step_tok is None:
+        if n_prev != 0:
+            raise ValueError("n_prev must be 0 without step_tok")
+    else:
+        if not step_tok.is_cuda or step_tok.dtype != torch.int32 or step_tok.dim() != 2 or step_tok.shape[0] != Bv or \
+                (step_tok.shape[1] > 1 and step_tok.stride(1) != 1):
+            raise ValueError("step_tok must be a CUDA int32 [B, n_tok] tensor with unit stride along the proposals")
+        n_tok = step_tok.shape[1]
+        ld_tok = step_tok.stride(0) if Bv > 1 else n_tok
+        if not 0 <= int(n_prev) or int(n_prev) + K1 - 1 > n_tok or ld_tok < n_tok:
+            raise ValueError(f"position {K1 - 1} would see {int(n_prev) + K1 - 1} proposals; step_tok holds {n_tok}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_dry_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V, _dev(dry.table, "table", torch.uint8),
+                             _opt(dry.row_start, "row_start", torch.int32), _dev(tokens, "tokens", torch.int32), tokens.shape[1],
+                             _dev(seq_len, "seq_len", torch.int32), start, int(max_len),
+                             None if step_tok is None else step_tok.data_ptr(), ld_tok, n_tok, int(n_prev), _stream())
+    B.check("asd_dry_rows", rc)
+    return logits

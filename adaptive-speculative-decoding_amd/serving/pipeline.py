@@ -46,6 +46,8 @@ batch or one per request, kept by the request through every regrouping, handed o
 `PipelineConfig.no_repeat_ngram_size`).
 `PipelineConfig.typical_p` / `epsilon_cutoff` / `eta_cutoff` (HF's warpers of those names; serving/stages.py, ENTROPY CUTS) are
 configuration only: a value that is set is handed to every stage's generate call as the keyword of that name, None is not passed.
+`PipelineConfig.dry_multiplier` / `dry_base` / `dry_allowed_length` / `dry_range` / `dry_sequence_breakers` (the DRY sampler;
+serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -220,6 +222,13 @@ class PipelineConfig:
     typical_p: Optional[float] = None
     epsilon_cutoff: Optional[float] = None
     eta_cutoff: Optional[float] = None
+    # the DRY sampler's values, handed to stage.generate(dry_multiplier=, dry_base=, dry_allowed_length=, dry_range=,
+    # dry_sequence_breakers=); None: the keyword is not passed (serving/stages.py, DRY)
+    dry_multiplier: Optional[float] = None
+    dry_base: Optional[float] = None
+    dry_allowed_length: Optional[int] = None
+    dry_range: Optional[int] = None
+    dry_sequence_breakers: Optional[Sequence] = None
     # vLLM's prompt_logprobs (serving/stages.py, PROMPT LOG-PROBS), handed to every stage.generate(prompt_logprobs=): each
     # stage's entry then carries "prompt_logprobs" and "prompt_ranks"; not fed to the predictor.  None: the keyword is not passed
     prompt_logprobs: Optional[int] = None
@@ -263,6 +272,11 @@ class PipelineConfig:
         for name in ("typical_p", "epsilon_cutoff", "eta_cutoff"):
             if sec.get(name) is not None:
                 kw[name] = float(sec[name])
+        for name, kind in (("dry_multiplier", float), ("dry_base", float), ("dry_allowed_length", int), ("dry_range", int)):
+            if sec.get(name) is not None:
+                kw[name] = kind(sec[name])
+        if sec.get("dry_sequence_breakers") is not None:
+            kw["dry_sequence_breakers"] = tuple(e if isinstance(e, str) else int(e) for e in sec["dry_sequence_breakers"])
         if sec.get("prompt_logprobs") is not None:
             kw["prompt_logprobs"] = int(sec["prompt_logprobs"])
         if sec.get("token_stats") is not None:
@@ -617,7 +631,8 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["stop_sequences"] = list(cfg.stop_sequences)
                 if cfg.no_repeat_ngram_size is not None:                # (the call's own value, shared or per request, replaces it below)
                     stop_kw["no_repeat_ngram_size"] = int(cfg.no_repeat_ngram_size)
-                for name in ("typical_p", "epsilon_cutoff", "eta_cutoff"):      # the entropy cuts: only those that are set
+                for name in ("typical_p", "epsilon_cutoff", "eta_cutoff",       # the entropy cuts and DRY: only those that are set
+                             "dry_multiplier", "dry_base", "dry_allowed_length", "dry_range", "dry_sequence_breakers"):
                     if getattr(cfg, name) is not None:
                         stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:

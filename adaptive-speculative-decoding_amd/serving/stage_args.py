@@ -17,6 +17,8 @@ MAX_LOGIT_EDITS = 1024                       # ASD_MAX_LOGIT_EDITS: (id, bias, u
 MAX_BAD_WORDS = 256                          # ASD_MAX_BAD_WORDS: distinct words of one row (BAD WORDS)
 MAX_BAD_WORD_LEN = 8                         # ASD_MAX_BAD_WORD_LEN
 MAX_NGRAM = 8                                # ASD_MAX_NGRAM: the largest no_repeat_ngram_size (NO REPEAT N-GRAM)
+DRY_MAX_MATCH = 64                           # ASD_DRY_MAX_MATCH: the longest match DRY measures, and the largest dry_allowed_length (DRY)
+MAX_DRY_BREAKERS = 32                        # ASD_MAX_DRY_BREAKERS: distinct sequence-breaker ids of a call
 MAX_LOGIT_BIAS = 100.0                      # |bias| <= 100, the range OpenAI documents
 _EDIT_FOREVER = 2 ** 31 - 1                  # `until` of a permanent ban
 _NUMBER = (int, float, np.integer, np.floating)
@@ -292,6 +294,52 @@ def check_ngram_rows_keep_a_token(ngram_rows: List[int], prompt_lens: List[int],
             raise ValueError(f"prompt {b}: no_repeat_ngram_size can ban up to {bound} tokens (prompt {int(prompt_lens[b])} + "
                              f"max_tokens {int(limits[b])} + draft_len {int(draft_len)}), which may leave no token of its "
                              f"allowed_token_ids ({len(set(allowed[b]) - gone)} after its bans)")
+
+
+def check_dry(multiplier, base, allowed_length, dry_range, breakers, n: int, vocab: int, tokenizer):
+    """generate's `dry_multiplier` (a finite number >= 0; 0: off), `dry_base` (a finite number >= 1), `dry_allowed_length` (an
+    int in [1, DRY_MAX_MATCH]) and `dry_range` (an int >= 0; 0: the whole history), each one value for all `n` prompts or a
+    sequence of n values, and `dry_sequence_breakers`: ONE list for the call (or None), each entry a token id in [0, vocab) or
+    a string that the stage's tokenizer encodes (ids folded as a stop string's are) to exactly ONE id -> (n multipliers, n
+    bases, n allowed lengths, n ranges, the tuple of at most MAX_DRY_BREAKERS distinct breaker ids).  A bool, a NaN, a value
+    outside its range, the wrong length, more than MAX_DRY_BREAKERS ids and a string of 0 or several ids raise ValueError."""
+    def number(name, lo):
+        def one(v):
+            if isinstance(v, bool) or not isinstance(v, _NUMBER) or not lo <= float(v) < float("inf"):     # (NaN included)
+                raise ValueError(f"{name} must be a finite number >= {lo:g}, got {v!r}")
+            return float(v)
+        return one
+
+    def integer(name, lo, hi):
+        def one(v):
+            if not _is_int(v) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+            return int(v)
+        return one
+    cols = []
+    for name, value, one in (("dry_multiplier", multiplier, number("dry_multiplier", 0.0)), ("dry_base", base, number("dry_base", 1.0)),
+                             ("dry_allowed_length", allowed_length, integer("dry_allowed_length", 1, DRY_MAX_MATCH)),
+                             ("dry_range", dry_range, integer("dry_range", 0, 2 ** 31 - 1))):
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name} must be one value or one per prompt, got {value!r}")
+        cols.append(_per_prompt(value, n, one, f"{name} values"))
+    ids = []
+    if breakers is not None:
+        if not _is_seq(breakers):
+            raise ValueError(f"dry_sequence_breakers must be a list of token ids or strings, got {breakers!r}")
+        for e in breakers:
+            if isinstance(e, str):
+                got = [int(i) % vocab for i in tokenizer.encode(e, return_tensors=None)]
+                if len(got) != 1:
+                    raise ValueError(f"a dry_sequence_breakers string must come to exactly one token id, {e!r} gives {len(got)} "
+                                     "(multi-token breakers are not built)")
+                ids.append(got[0])
+            else:
+                ids.append(_check_token_id(e, vocab, "dry_sequence_breakers"))
+    ids = tuple(dict.fromkeys(ids))
+    if len(ids) > MAX_DRY_BREAKERS:
+        raise ValueError(f"{len(ids)} distinct dry_sequence_breakers, at most {MAX_DRY_BREAKERS}")
+    return (*cols, ids)
 
 
 def _check_bad_word_list(entries, vocab: int, tokenizer, what: str) -> List[Tuple[int, ...]]:

@@ -394,6 +394,42 @@ V = 152064, bf16, kernel time): epsilon mode 63.2 us and typical mode 175.0 us a
 same tensor (ratios 1.01, inside that pass's run-to-run spread of 0.10, and 2.81).  NOT
 BUILT beside that: per-request values of the DRAFT side, and serving/hierarchy.py's loop.
 
+DRY.  `generate(dry_multiplier=, dry_base=, dry_allowed_length=, dry_range=, dry_sequence_breakers=)` (or the StageConfig
+fields of those names; None takes the configuration's value) is the DRY ("don't repeat yourself") sampler of llama.cpp,
+koboldcpp, text-generation-webui, exllamav2 and Aphrodite: a token is penalised in proportion to the length of the repetition it
+would extend.  dry_multiplier is a finite number >= 0 (0, the default: off), dry_base a finite number >= 1 (1.75),
+dry_allowed_length an int in [1, 64] (2), dry_range an int >= 0 (0: the whole history) -- each one value for the call or one
+per prompt -- and dry_sequence_breakers ONE list for the call of at most 32 distinct entries, each a token id in [0, vocab) or
+a string that the tokenizer encodes (ids folded as a stop string's are) to exactly one id.  SEMANTICS, at every logits position:
+H is the history of NO REPEAT N-GRAM -- the row's real prompt ids (not the padding), its committed tokens and the step's own
+proposals in front of the position --, H' its last dry_range tokens (all of them at 0), len its length and last = H'[len-1].
+With len < 2, or `last` a breaker, nothing happens.  Otherwise every i in [0, len-2] with H'[i] == last names a candidate
+t = H'[i+1] (skipped when it is a breaker) whose match length m_i is the largest m in [1, min(i+1, CAP)] with
+H'[i-k] == H'[len-1-k] and H'[len-1-k] no breaker for every k < m; the matched region and the suffix may overlap.  CAP = 64
+(ASD_DRY_MAX_MATCH) is this build's choice: it bounds the walk per candidate and the exponent.  M_t is the largest m_i of
+token t, and where M_t >= dry_allowed_length
+    x_t <- x_t - dry_multiplier * dry_base ^ (M_t - dry_allowed_length)
+in f32, rounded to the logits' dtype to nearest even and clamped to the dtype's lowest FINITE value: DRY is a penalty and never
+creates -inf, so no "row keeps a token" check is needed and it composes with guided rows.  An element that is -inf (or NaN, or
++inf) is left as it is; a token is penalised ONCE, with its longest match.  The host forms the 65 penalties of a row in f64,
+rounds them to f32 and uploads them with the row's record (ops.pack_dry, once per call); the device evaluates no pow
+(asd_dry_rows: a workgroup per logits row, the suffix and the history tiles in LDS, the per-token maximum in an LDS hash table,
+one read-modify-write per penalised token).  ops.dry_rows runs directly behind the penalties and ahead of the entropy cut --
+llama.cpp's chain, penalties -> dry -> truncations: mask -> fsm -> bad words -> n-gram -> edit -> penalties -> DRY -> entropy
+cut -> temperature -> top-k -> top-p -> min-p -- on stage 0's [B, V] logits, on every draft row (position k sees the proposals
+0 .. k-1) and on the target's [B, K+1, V] output with the SAME records, one launch per logits tensor; the pass is a
+deterministic function of the row's history, so the draft -> verify -> residual chain stays lossless by the argument of LOGIT
+EDITS.  It runs under greedy decoding too: DRY is an edit, not a truncation.  Log-probs, top-N tables and token statistics
+describe the distribution behind the pass, as for the penalties.  A call whose every row has multiplier 0 makes exactly the ops
+calls it made before.  ValueError before any launch and before the prompts are encoded: a bool, a NaN, a negative or
+non-finite multiplier, a base below 1, an allowed length outside [1, 64], a negative range, the wrong length, more than 32
+breakers, a breaker string of 0 or several ids.  COST (profiles/dry.json: B = 32, K1 = 9, V = 152064, bf16, kernel time):
+natural-looking histories (random ids over 300 distinct tokens) of 128 / 2048 / 16384 tokens take 6.9 / 7.7 / 15.1 us against 3.5 / 5.1 /
+8.2 us for asd_no_repeat_ngram_rows (n = 3) on a copy of the same tensor with the same histories in the same run -- ratios 1.99 /
+1.51 / 1.83, that baseline's run-to-run spread being 0.03 to 0.24 --, and the all-equal worst case 11.3 / 30.3 / 197.8 us against
+3.4 / 7.3 / 12.4 us (ratios 3.3 / 4.1 / 16.0): every position is then a candidate and walks all 64 steps.  NOT BUILT: llama.cpp's multi-token breaker strings ("restart sequences"; breakers are single token ids),
+per-prompt breaker lists, separate draft-side values (the draft rows take the call's), and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -415,7 +451,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_entropy_cuts, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -469,6 +505,11 @@ class StageConfig:
     frequency_penalty: float = 0.0           # in [-2, 2]; 0: off
     bad_words: Sequence = ()                 # words (strings / sequences of 1..8 token ids) no row may produce (module docstring, BAD WORDS)
     no_repeat_ngram_size: int = 0            # in [0, 8]; 0: off (module docstring, NO REPEAT N-GRAM)
+    dry_multiplier: float = 0.0              # >= 0; 0: off (module docstring, DRY)
+    dry_base: float = 1.75                   # >= 1
+    dry_allowed_length: int = 2              # in [1, 64]: the shortest match that is penalised
+    dry_range: int = 0                       # >= 0: the last tokens of the history that count; 0: all of it
+    dry_sequence_breakers: Sequence = ()     # at most 32 token ids / one-token strings that reset a match
     guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
     guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
     prompt_logprobs: Optional[int] = None    # None: off; 0..8: the prompt tokens' log-probs and ranks, and a top-N table (PROMPT LOG-PROBS)
@@ -503,6 +544,7 @@ class _Plan(NamedTuple):
     token_stats: bool = False                # the per-token statistics and the predictor's feature batch (TOKEN STATS)
     cut_rows: Optional[list] = None          # every row's (mode, value) of the stage's own entropy cut; None: every row off
     cut_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, value) of the draft stage's configured cut
+    dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
 
 
 class _EditState:
@@ -565,6 +607,25 @@ class _NgramState:
         if self.step_tok is None:
             return self.ops.no_repeat_ngram_rows(logits, self.packed, tokens, seq_len, self.cap)
         return self.ops.no_repeat_ngram_rows(logits, self.packed, tokens, seq_len, self.cap, self.step_tok, n_prev)
+
+
+class _DryState:
+    """What a generate call with a DRY multiplier keeps: the rows' records (their penalty tables included) and the index of their
+    first real prompt id on the device (uploaded once), the size of the token buffer and, at a verifying stage, the call's
+    [B, draft_len] buffer of the step's proposals.  `apply` is the loops' one call per logits tensor, directly behind the
+    penalties' and ahead of the entropy cut's; nothing follows the commit: the operation reads `tokens` and keeps no state
+    (module docstring, DRY)."""
+
+    def __init__(self, ops, dry, prompt_ids, P: int, cap: int, step_tok: Optional[torch.Tensor], device):
+        self.ops, self.cap, self.step_tok = ops, int(cap), step_tok
+        self.packed = ops.pack_dry(*dry, [len(r) for r in prompt_ids], int(P), device)
+
+    def apply(self, logits: torch.Tensor, tokens: torch.Tensor, seq_len: torch.Tensor, n_prev: int = 0) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], penalised in place; seq_len: the step's lengths before its commit; position j sees the
+        step's first n_prev + j proposals behind the row's prompt and committed tokens."""
+        if self.step_tok is None:
+            return self.ops.dry_rows(logits, self.packed, tokens, seq_len, self.cap)
+        return self.ops.dry_rows(logits, self.packed, tokens, seq_len, self.cap, self.step_tok, n_prev)
 
 
 class _CutState:
@@ -996,7 +1057,7 @@ class _CallState:
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
         self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
-        history = any(plan.bad_rows) or any(plan.ngram_rows) or bool(plan.penalties) or plan.fsm is not None
+        history = any(plan.bad_rows) or any(plan.ngram_rows) or bool(plan.penalties) or plan.fsm is not None or plan.dry is not None
         self.step_tok = torch.zeros((B, stage.config.draft_len), dtype=torch.int32, device=dev) \
             if history and stage.draft is not None else None
         self.fsm = _FsmState(ops, plan.fsm, 1 if stage.draft is None else stage.config.draft_len + 1, self.step_tok, dev) \
@@ -1005,6 +1066,7 @@ class _CallState:
         self.ngram = _NgramState(ops, plan.ngram_rows, prompt_ids, P, P + plan.max_tokens, self.step_tok, dev) \
             if any(plan.ngram_rows) else None
         self.pen = _PenaltyState(ops, plan.penalties, prompt_ids, stage.shape.vocab, self.step_tok, dev) if plan.penalties else None
+        self.dry = _DryState(ops, plan.dry, prompt_ids, P, P + plan.max_tokens, self.step_tok, dev) if plan.dry is not None else None
         # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
         self.top = _TopState(ops, plan.n_top, plan.inv_t, B, P + plan.max_tokens, dev,
@@ -1097,7 +1159,9 @@ class Stage:
                  prompt_logprobs: Optional[int] = None,
                  token_stats: Optional[bool] = None,
                  typical_p=None, epsilon_cutoff=None,
-                 eta_cutoff=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 eta_cutoff=None,
+                 dry_multiplier=None, dry_base=None, dry_allowed_length=None, dry_range=None,
+                 dry_sequence_breakers=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1206,7 +1270,19 @@ class Stage:
         survivors -- llama.cpp's order, not HF's (Temperature -> TopK -> TopP -> MinP -> Typical -> Epsilon -> Eta); with
         those three off the kept set is HF's.  Log-probs, top-N tables and token statistics describe the distribution behind
         the cut.  Greedy decoding ignores all three.  A bool, a NaN, a value outside its range, the wrong length and two of
-        them on one row raise ValueError (module docstring, ENTROPY CUTS)."""
+        them on one row raise ValueError (module docstring, ENTROPY CUTS).
+        `dry_multiplier` (a finite number >= 0; 0: off), `dry_base` (a finite number >= 1), `dry_allowed_length` (an int in
+        [1, 64]) and `dry_range` (an int >= 0; 0: the whole history) are the DRY sampler's (llama.cpp, koboldcpp,
+        text-generation-webui, exllamav2, Aphrodite): None = the StageConfig field of that name; one value for every prompt or
+        one per prompt.  `dry_sequence_breakers`: None = StageConfig.dry_sequence_breakers; ONE list for the call of at most 32
+        token ids or strings that encode to exactly one id.  At every position a token t that followed an earlier occurrence of
+        the history's last token loses dry_multiplier * dry_base ^ (M - dry_allowed_length), M being the longest backward match
+        (at most 64 tokens, ended by a breaker) of such an occurrence with the end of the history -- prompt, generated tokens and
+        the step's own proposals in front of the position, its last dry_range tokens --, where M >= dry_allowed_length; the
+        result never falls below the dtype's lowest finite value.  Draft and target logits receive the same penalty, directly
+        behind the penalties above and ahead of the entropy cuts, under greedy decoding too, and log-probs, top-N tables and
+        token statistics are those of the penalised distribution.  A bool, a NaN, a value outside its range, the wrong length,
+        more than 32 breakers and a breaker string of 0 or several ids raise ValueError (module docstring, DRY)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1214,7 +1290,8 @@ class Stage:
                           stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
                           repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
                           guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats,
-                          typical_p, epsilon_cutoff, eta_cutoff)
+                          typical_p, epsilon_cutoff, eta_cutoff, dry_multiplier, dry_base, dry_allowed_length, dry_range,
+                          dry_sequence_breakers)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1249,7 +1326,8 @@ class Stage:
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
               repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm=None,
               guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None,
-              token_stats=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> _Plan:
+              token_stats=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, dry_multiplier=None, dry_base=None,
+              dry_allowed_length=None, dry_range=None, dry_sequence_breakers=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1315,6 +1393,9 @@ class Stage:
         cut_rows = check_entropy_cuts(*(given(v, d) for v, d in zip((typical_p, epsilon_cutoff, eta_cutoff), own_cuts)), n)
         dcfg = None if self.draft is None else self.draft.config
         cut_draft_rows = [] if dcfg is None else check_entropy_cuts(dcfg.typical_p, dcfg.epsilon_cutoff, dcfg.eta_cutoff, n)
+        dry = check_dry(given(dry_multiplier, cfg.dry_multiplier), given(dry_base, cfg.dry_base),
+                        given(dry_allowed_length, cfg.dry_allowed_length), given(dry_range, cfg.dry_range),
+                        given(dry_sequence_breakers, cfg.dry_sequence_breakers), n, V, self.tokenizer)
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -1336,7 +1417,8 @@ class Stage:
                      penalties=penalties, fsm=fsm, seeds=seeds, n_top=n_top, n_prompt=n_prompt,
                      token_stats=token_stats,
                      cut_rows=cut_rows if not greedy and any(m for m, _ in cut_rows) else None,        # greedy ignores the cuts
-                     cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None)
+                     cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
+                     dry=dry if any(m > 0.0 for m in dry[0]) else None)           # every row off: no state, no call
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -1356,7 +1438,7 @@ class Stage:
         dev = ids.device
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram, stat, cut = st.fsm, st.ngram, st.stats, st.cut
+        fsm, ngram, stat, cut, dry = st.fsm, st.ngram, st.stats, st.cut, st.dry
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1380,6 +1462,8 @@ class Stage:
                 edit.apply(logits, seq_len)                              # ahead of the draw and the top-N pass
             if pen is not None:
                 pen.apply(logits)                                        # the penalties last: mask -> edit -> penalties
+            if dry is not None:
+                dry.apply(logits, tokens, seq_len)                       # ... and DRY behind them, on the n-gram rule's history
             cut_in = cut.apply(logits, self.keep_inputs) if cut is not None else None   # the entropy cut: behind every processor
             n_acc, tok, lp = sampler.draw(logits, step)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
@@ -1428,7 +1512,7 @@ class Stage:
         Kd = cfg.draft_len
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram, stat, cut, cut_draft = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft
+        fsm, ngram, stat, cut, cut_draft, dry = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft, st.dry
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -1465,6 +1549,8 @@ class Stage:
                     edit.apply(dl, seq_len, k)                          # proposal k decides generated token L - P + k
                 if pen is not None:
                     pen.apply(dl, k)                                    # ... and sees the proposals 0 .. k - 1 of this step
+                if dry is not None:
+                    dry.apply(dl, tokens, seq_len, k)                   # DRY: the n-gram rule's history, behind the penalties
                 if cut_draft is not None:
                     cut_in_draft.append(cut_draft.apply(dl, self.keep_inputs))   # the DRAFT stage's configured cut, last
                 toks.append(sampler.propose(dl, k))
@@ -1488,6 +1574,8 @@ class Stage:
                 edit.apply(t_out, seq_len)                              # the same edit on the target's K + 1 rows, before any slice
             if pen is not None:
                 pen.apply(t_out)                                        # row j sees the proposals 0 .. j - 1, as the draft's did
+            if dry is not None:
+                dry.apply(t_out, tokens, seq_len)                       # the same records and history per row as the draft's rows had
             cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None    # the call's own cut on the K + 1 rows
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
             kept = sampler.kept(seq_len) if self.keep_inputs else None

@@ -58,6 +58,8 @@ typedef enum asd_dtype {
 #ifndef ASD_NGRAM_SLICE        /* (tools/bench_no_repeat_ngram.py builds the kernel once more with one slice for any history) */
 #define ASD_NGRAM_SLICE 2048   /* n-gram starts one workgroup of asd_no_repeat_ngram_rows scans */
 #endif
+#define ASD_DRY_MAX_MATCH 64   /* CAP of asd_dry_rows: the longest match that is measured, and the largest allowed_length */
+#define ASD_MAX_DRY_BREAKERS 32 /* sequence-breaker token ids one row may own in asd_dry_rows */
 #define ASD_MAX_STAGES 16      /* L: tiers in the DP rule */
 #define ASD_MAX_SPLITS 64      /* vocab splits per row inside one launch */
 #define ASD_MAX_MLP_DIM 1024   /* predictor input / hidden width */
@@ -761,6 +763,59 @@ typedef struct asd_entropy_cut_rec {
 } asd_entropy_cut_rec;
 int asd_entropy_cut_rows(void* logits /*in/out*/, int dtype, int B, int K1, int V, int64_t ld_seq, int64_t ld_row,
                          const asd_entropy_cut_rec* table /*[B]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The DRY ("don't repeat yourself") repetition penalty AHEAD of the samplers -- the sampler of that name in llama.cpp,
+ * koboldcpp, text-generation-webui, exllamav2 and Aphrodite: a token is penalised in proportion to the length of the repetition
+ * it would extend.  It is no fixed-n compare (every occurrence of the last token has its own backward match length) and no
+ * idempotent store (a token that followed several occurrences receives ONE subtraction, with the MAXIMUM match length).  A
+ * deterministic function of the row's history, applied alike to the draft's proposal rows and the target's K+1 rows: the
+ * draft -> verify -> residual chain stays lossless against the penalised target distribution.
+ * logits, tokens, ld_tokens, seq_len, start, max_len, row_start, step_tok, ld_tok, n_tok, n_prev: asd_no_repeat_ngram_rows'
+ * addressing and history,
+ *     H = tokens[b][row_start[b] .. L)  ++  step_tok[b][0 .. n_prev + j),      L = clamp(seq_len[b], start, max_len)
+ * recs: B records asd_dry_rec on the device; all K1 rows of sequence b use record b.  on == 0: the row is not read.
+ * With range > 0 only the last `range` tokens of H count: H', of length len; last = H'[len-1]; CAP = ASD_DRY_MAX_MATCH.
+ * Semantics: with len < 2, or `last` one of the record's breakers, nothing happens.  Otherwise every i in [0, len-2] with
+ * H'[i] == last names a candidate t = H'[i+1], skipped when t is a breaker or lies outside [0, V), with the match length
+ *     m_i = the largest m in [1, min(i+1, CAP)] with H'[i-k] == H'[len-1-k] and H'[len-1-k] no breaker for every k < m
+ * (the matched region and the suffix may overlap).  M_t = max m_i over the candidates of t, and where M_t >= allowed_length
+ *     x_t <- x_t - pen[M_t]
+ * in f32 from the element widened to f32, rounded to the dtype to nearest even, and clamped to the dtype's lowest FINITE value
+ * (0xFF7F bf16, 0xFBFF f16, -FLT_MAX f32): DRY never creates -inf, so a row keeps every token it had.  An element that is
+ * -inf, NaN or +inf is left as it is; every other element of the allocation keeps its bits.  pen[m], m = 0..CAP, is the
+ * HOST's table, float(multiplier * base^(m - allowed_length)) from double and 0 below allowed_length (+inf is allowed: the
+ * clamp absorbs it); the device evaluates no pow, so the result is reproducible bit for bit by a host reference.  Breakers are
+ * single token ids.  The operation keeps no state and `tokens` and `recs` are only read.
+ * THE DATA CONTRACT: seq_len[b] is clamped into [start, max_len], row_start[b] into [0, start], allowed_length into [1, CAP],
+ * n_breakers into [0, ASD_MAX_DRY_BREAKERS], a negative range counts as 0, and a history token outside [0, V) is compared as a
+ * plain integer but never used as an index.
+ * One launch: a workgroup of 1024 threads per (b, j).  The suffix lies in LDS in reverse order, cut at the first breaker; the
+ * history passes through LDS in tiles of 4096 positions (with a halo of CAP - 1), each lane compares H'[i] with `last` first
+ * and a hit walks backwards in LDS; the maximum per follower is formed in an LDS hash table of 2048 (token, m) slots (a slot
+ * claimed by compare-and-swap, the length merged by atomic max), and ONE lane per occupied slot does the one read-modify-write
+ * of that logit.  More than 1024 distinct penalised followers do not fit: such a pass writes nothing and is split by the low
+ * bits of the token id into two classes that scan the history again, recursively -- exact for any history, only slower.  The
+ * result does not depend on scheduling.  No workspace, no loop over the vocabulary, nothing waits on another workgroup.
+ * Status, in this order: negative B / K1 / V / n_tok / n_prev / start / max_len: invalid argument; B, K1 or V == 0: ASD_OK,
+ * nothing launched; unknown dtype, n_tok > ASD_MAX_DRAFT_LEN, B*K1 > INT32_MAX, max_len + n_tok > INT32_MAX - 4160:
+ * unsupported; NULL logits / recs / tokens / seq_len, ld_row < V, ld_seq < K1*ld_row, ld_tokens < max_len, start > max_len,
+ * step_tok == NULL with n_prev != 0, step_tok != NULL with n_prev + K1 - 1 > n_tok or ld_tok < n_tok: invalid argument; logits
+ * not aligned to the element size, or recs / row_start / tokens / seq_len / step_tok not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_DRY_REC_BYTES 404
+typedef struct asd_dry_rec {
+    int32_t on;                               /* 0: the sequence's rows are not read */
+    int32_t allowed_length;                   /* in [1, ASD_DRY_MAX_MATCH]: the shortest match that is penalised */
+    int32_t range;                            /* > 0: only the last `range` tokens of the history count; 0: all of it */
+    int32_t n_breakers;                       /* in [0, ASD_MAX_DRY_BREAKERS] */
+    int32_t breakers[ASD_MAX_DRY_BREAKERS];   /* the sequence-breaker token ids */
+    float pen[ASD_DRY_MAX_MATCH + 1];         /* pen[m]: what a match of length m subtracts; 0 below allowed_length */
+} asd_dry_rec;
+int asd_dry_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                 const asd_dry_rec* recs /*[B]*/, const int32_t* row_start /*[B], or NULL: start for every row*/,
+                 const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens, const int32_t* seq_len /*[B]*/, int start, int max_len,
+                 const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /

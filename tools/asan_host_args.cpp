@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_dry_rows, asd_entropy_cut_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -542,6 +542,69 @@ int main() {
         EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, off, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);        // seq_len
         EXPECT(NGRAM(p, BF16, K1 * V, V, B, K1, V, i32, 0, i32, i32, 32, i32, 4, 32, off, 4, 4, 0), ASD_ERR_ALIGNMENT);        // step_tok
 #undef NGRAM
+    }
+
+    // ---- asd_dry_rows: the n-gram launcher's checks with the records in place of (ngram_n, n_shared)
+    {
+#define DRY(x_, dt_, lds_, ldr_, B_, K1_, V_, rec_, rs_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_) \
+    asd_dry_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, rec_, rs_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_, nullptr)
+        const int K1 = 5;
+        const asd_dry_rec* rec = reinterpret_cast<const asd_dry_rec*>(rows);
+        const asd_dry_rec* rec_off = reinterpret_cast<const asd_dry_rec*>(rows + 2);
+        int32_t* off = reinterpret_cast<int32_t*>(rows + 2);
+        static_assert(sizeof(asd_dry_rec) == ASD_DRY_REC_BYTES, "the record the host packs");
+        EXPECT(DRY(p, BF16, K1 * V, V, -1, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(DRY(p, BF16, K1 * V, V, B, -1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, -1, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, -1, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // start
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, -1, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // max_len
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, -1, 0), ASD_ERR_INVALID_ARG);   // n_tok
+        EXPECT(DRY(p, BF16, K1 * V, V, 0, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);   // n_prev, before the empty batch
+        EXPECT(DRY(nullptr, 99, 0, 0, 0, K1, V, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // B == 0
+        EXPECT(DRY(nullptr, 99, 0, 0, B, 0, V, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);    // K1 == 0
+        EXPECT(DRY(nullptr, 99, 0, 0, B, K1, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // V == 0
+        EXPECT(DRY(nullptr, 99, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);  // dtype, before the NULL checks
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 65, ASD_MAX_DRAFT_LEN + 1, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, INT64_C(1) << 31, i32, 4, INT32_MAX - 4000, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);   // the scan counts in int32
+        EXPECT(DRY(nullptr, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, nullptr, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // recs
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, nullptr, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // tokens
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, nullptr, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // seq_len
+        EXPECT(DRY(p, BF16, K1 * V, V - 1, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // ld_row < V
+        EXPECT(DRY(p, BF16, K1 * V - 1, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // ld_seq < K1 ld_row
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 31, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);       // ld_tokens < max_len
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 33, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);      // start > max_len
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, nullptr, 0, 0, 1), ASD_ERR_INVALID_ARG);   // n_prev without step_tok
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 1), ASD_ERR_INVALID_ARG);       // position 4 would see 5 of 4
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 3, 4, 0), ASD_ERR_INVALID_ARG);       // ld_tok < n_tok
+        EXPECT(DRY(rows + 1, BF16, K1 * V, V - 1, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // ... before alignment
+        EXPECT(DRY(rows + 1, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);  // below the element size
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec_off, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);     // recs
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, off, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);         // row_start
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, off, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);         // tokens
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, off, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);         // seq_len
+        EXPECT(DRY(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, off, 4, 4, 0), ASD_ERR_ALIGNMENT);         // step_tok
+#undef DRY
+    }
+
+    // ---- asd_entropy_cut_rows: sizes, the empty batch, dtype and the int32 bounds, pointers and strides, alignment
+    {
+#define CUT(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_) asd_entropy_cut_rows(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, nullptr)
+        const int K1 = 5;
+        const asd_entropy_cut_rec* tab = reinterpret_cast<const asd_entropy_cut_rec*>(rows);
+        EXPECT(CUT(p, BF16, -1, K1, V, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CUT(p, BF16, B, -1, V, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CUT(p, BF16, B, K1, -1, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CUT(nullptr, 99, 0, K1, V, 0, 0, nullptr), ASD_OK);
+        EXPECT(CUT(nullptr, 99, B, K1, V, K1 * V, V, tab), ASD_ERR_UNSUPPORTED);                  // dtype, before the NULL checks
+        EXPECT(CUT(p, 0 /*f32*/, B, 1, INT32_MAX, INT32_MAX, INT32_MAX, tab), ASD_ERR_UNSUPPORTED);   // V * element size > INT32_MAX
+        EXPECT(CUT(nullptr, BF16, B, K1, V, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CUT(p, BF16, B, K1, V, K1 * V, V, nullptr), ASD_ERR_INVALID_ARG);
+        EXPECT(CUT(p, BF16, B, K1, V, K1 * V, V - 1, tab), ASD_ERR_INVALID_ARG);                  // ld_row < V
+        EXPECT(CUT(p, BF16, B, K1, V, K1 * V - 1, V, tab), ASD_ERR_INVALID_ARG);                  // ld_seq < K1 ld_row
+        EXPECT(CUT(rows + 1, BF16, B, K1, V, K1 * V, V, tab), ASD_ERR_ALIGNMENT);                 // below the element size
+        EXPECT(CUT(p, BF16, B, K1, V, K1 * V, V, reinterpret_cast<const asd_entropy_cut_rec*>(rows + 2)), ASD_ERR_ALIGNMENT);
+#undef CUT
     }
 
     // ---- asd_prompt_logprobs: the header's order (NULL outputs and the temperature, sizes, the empty batch, dtype, N / splits,
