@@ -551,6 +551,26 @@ class HipOps:
         logits tensor, behind penalty_rows and directly ahead of the draw, and only when some row of the call has a cut."""
         return self.K.entropy_cut_rows(logits, cut)
 
+    @traced("pack_mirostat")
+    def pack_mirostat(self, inv_t, taus, etas, device):
+        """Every row's 1 / temperature, tau (0: off) and eta -> the device records of mirostat_rows and the running target
+        mu = 2 * tau (kernels.pack_mirostat: one upload per generate call)."""
+        return self.K.pack_mirostat(inv_t, taus, etas, device)
+
+    @traced("mirostat_rows")
+    def mirostat_rows(self, logits, miro, step_tok=None):
+        """Mirostat v2 ahead of the samplers (asd_mirostat_rows): logits [B, V] or [B, K1, V] (any strides with a unit last
+        stride), cut in place against the running target, chained through the K1 rows by the surprise of the step's proposals
+        `step_tok` -> mu_path f32 [B, K1].  Two launches; a stage loop makes the call once per step on its OWN distribution,
+        the last pass ahead of the draw or settle call, and only when some row of the call is on."""
+        return self.K.mirostat_rows(logits, miro, step_tok)
+
+    @traced("mirostat_commit")
+    def mirostat_commit(self, miro, mu_path, n_acc, lp, seq_len, n_commit, mu_out):
+        """Behind the step's commit (asd_mirostat_commit): the mu in force at every committed token into mu_out [B, max_len],
+        and the running target moved by the surprise of the step's drawn token."""
+        return self.K.mirostat_commit(miro, mu_path, n_acc, lp, seq_len, n_commit, mu_out)
+
     @traced("pack_dry")
     def pack_dry(self, multipliers, bases, allowed_lengths, ranges, breakers, prompt_lens, P: int, device):
         """Every row's DRY multiplier (0: off), base, allowed_length and range, the call's breaker ids and the rows' numbers of

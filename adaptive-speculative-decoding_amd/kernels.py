@@ -1981,3 +1981,95 @@ def dry_rows(logits: torch.Tensor, dry: Dry, tokens: torch.Tensor, seq_len: torc
                              None if step_tok is None else step_tok.data_ptr(), ld_tok, n_tok, int(n_prev), _stream())
     B.check("asd_dry_rows", rc)
     return logits
+
+
+# ------------------------------------------------------------------------------- Mirostat v2 (mirostat_tau / mirostat_eta)
+_MIRO_REC = np.dtype([("inv_t", np.float32), ("tau", np.float32), ("eta", np.float32)])
+assert _MIRO_REC.itemsize == B.MIROSTAT_REC_BYTES
+
+
+@dataclass
+class Mirostat:
+    """What asd_mirostat_rows / asd_mirostat_commit keep on the device for one generate call (pack_mirostat): B records
+    {inv_t, tau, eta} f32 as a uint8 [B, 12] tensor; `mu` f32 [B], the running target, 2 * tau at the start; `taus`: the host's
+    copy of the rows' tau (0: off)."""
+    table: torch.Tensor
+    mu: torch.Tensor
+    taus: Tuple[float, ...]
+    B: int
+
+
+def check_mirostat_rows(inv_t, taus, etas) -> np.ndarray:
+    """The host side of pack_mirostat: every row's 1 / temperature (a positive finite number), tau (0: off, else in (0, 32])
+    and eta (in (0, 1] where the row is on) -> the records, a numpy structured array."""
+    inv_t, taus, etas = list(inv_t), list(taus), list(etas)
+    if not len(inv_t) == len(taus) == len(etas):
+        raise ValueError(f"{len(inv_t)} temperatures, {len(taus)} taus and {len(etas)} etas must describe the same rows")
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))   # noqa: E731
+    rec = np.zeros(len(taus), dtype=_MIRO_REC)
+    for b, (t, tau, eta) in enumerate(zip(inv_t, taus, etas)):
+        if not number(t) or not 0.0 < float(np.float32(t)) < 3.0e38:
+            raise ValueError(f"row {b}: 1 / temperature must be a positive finite number, got {t!r}")
+        if not number(tau) or not 0.0 <= float(tau) <= 32.0:
+            raise ValueError(f"row {b}: tau must be 0 (off) or a number in (0, 32], got {tau!r}")
+        on = float(np.float32(tau)) > 0.0
+        if on and (not number(eta) or not 0.0 < float(np.float32(eta)) <= 1.0):
+            raise ValueError(f"row {b}: eta of a row that is on must lie in (0, 1], got {eta!r}")
+        rec[b] = (np.float32(t), np.float32(tau) if on else 0.0, np.float32(eta) if on else 0.0)
+    return rec
+
+
+def pack_mirostat(inv_t, taus, etas, device) -> Mirostat:
+    """The records and the initial mu = 2 * tau of mirostat_rows from host lists, checked BEFORE anything is uploaded."""
+    rec = check_mirostat_rows(inv_t, taus, etas)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _MIRO_REC.itemsize).copy()).to(device)
+    mu = torch.from_numpy((np.float32(2.0) * rec["tau"]).astype(np.float32)).to(device)
+    return Mirostat(table, mu, tuple(float(t) for t in rec["tau"]), len(rec))
+
+
+def mirostat_rows(logits: torch.Tensor, miro: Mirostat, step_tok: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Cut in place (asd_mirostat_rows: two launches) and return mu_path f32 [B, K1], the mu in force at every row: logits
+    [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row stride with unit stride along V.  With p = softmax(x * inv_t) of
+    row (b, j) as it stands, token v becomes -inf iff -log2 p_v > mu_{b,j} and x_v < x_max; mu_{b,0} = miro.mu[b] and
+    mu_{b,j+1} = mu_{b,j} - eta (s^ - tau) with s^ the surprise of step_tok[b, j] under the cut, renormalised row; a proposal that
+    is cut ends the chain and the rows behind it stay untouched.  step_tok i32 [B, >= K1 - 1] (unit stride along the
+    proposals); None when K1 == 1.  miro.mu is not written: mirostat_commit moves it."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if miro.B != Bv:
+        raise ValueError(f"the Mirostat records were packed for {miro.B} rows; logits have {Bv}")
+    ld_tok = 0
+    if K1 > 1:
+        if step_tok is None or not step_tok.is_cuda or step_tok.dtype != torch.int32 or step_tok.dim() != 2 or \
+                step_tok.shape[0] != Bv or step_tok.shape[1] < K1 - 1 or (step_tok.shape[1] > 1 and step_tok.stride(1) != 1):
+            raise ValueError(f"step_tok must be a CUDA int32 [B, >= {K1 - 1}] tensor with unit stride along the proposals")
+        ld_tok = step_tok.stride(0) if Bv > 1 else step_tok.shape[1]
+    mu_path = torch.empty((Bv, K1), dtype=torch.float32, device=logits.device)
+    ws = torch.empty((max(Bv * K1, 1) * B.MIROSTAT_ROW_BYTES // 4,), dtype=torch.float32, device=logits.device)
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_mirostat_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], Bv, K1, V, ld_seq, ld_row,
+                                  _dev(miro.table, "table", torch.uint8), _dev(miro.mu, "mu", torch.float32),
+                                  None if K1 == 1 else step_tok.data_ptr(), ld_tok, mu_path.data_ptr(), ws.data_ptr(),
+                                  ws.numel() * 4, _stream())
+    B.check("asd_mirostat_rows", rc)
+    return mu_path
+
+
+def mirostat_commit(miro: Mirostat, mu_path: torch.Tensor, n_acc: torch.Tensor, lp: torch.Tensor, seq_len: torch.Tensor,
+                    n_commit: torch.Tensor, mu_out: torch.Tensor) -> None:
+    """Behind the step's commit (asd_mirostat_commit): mu_out[b, seq_len[b] - c + i] = mu_path[b, i] for the c = n_commit[b]
+    tokens the step committed, and miro.mu[b] = mu_path[b, n_acc[b]] - eta (-lp[b] / ln 2 - tau) where the step committed its
+    drawn token (lp f32 [B]: that token's log-prob); a finished sequence (n_commit == 0) keeps its mu.  mu_out f32
+    [B, max_len] contiguous; seq_len / n_commit i32 [B] as the commit left them."""
+    Bv, K1 = mu_path.shape
+    if miro.B != Bv or mu_out.dim() != 2 or mu_out.shape[0] != Bv or not mu_out.is_contiguous():
+        raise ValueError(f"mu_path [B, K1] and a contiguous mu_out [B, max_len] for the {miro.B} packed rows")
+    rc = _lib().asd_mirostat_commit(_dev(mu_path, "mu_path", torch.float32), Bv, K1, _dev(n_acc, "n_acc", torch.int32),
+                                    _dev(lp, "lp", torch.float32), _dev(seq_len, "seq_len", torch.int32),
+                                    _dev(n_commit, "n_commit", torch.int32), _dev(miro.table, "table", torch.uint8),
+                                    _dev(miro.mu, "mu", torch.float32), _dev(mu_out, "mu_out", torch.float32), mu_out.shape[1], _stream())
+    B.check("asd_mirostat_commit", rc)

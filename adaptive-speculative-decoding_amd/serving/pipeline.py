@@ -46,6 +46,7 @@ batch or one per request, kept by the request through every regrouping, handed o
 `PipelineConfig.no_repeat_ngram_size`).
 `PipelineConfig.typical_p` / `epsilon_cutoff` / `eta_cutoff` (HF's warpers of those names; serving/stages.py, ENTROPY CUTS) are
 configuration only: a value that is set is handed to every stage's generate call as the keyword of that name, None is not passed.
+`PipelineConfig.mirostat_tau` / `mirostat_eta` (llama.cpp's mirostat_v2; serving/stages.py, MIROSTAT) travel the same way.
 `PipelineConfig.dry_multiplier` / `dry_base` / `dry_allowed_length` / `dry_range` / `dry_sequence_breakers` (the DRY sampler;
 serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
 
@@ -222,6 +223,10 @@ class PipelineConfig:
     typical_p: Optional[float] = None
     epsilon_cutoff: Optional[float] = None
     eta_cutoff: Optional[float] = None
+    # llama.cpp's mirostat_v2, handed to stage.generate(mirostat_tau=, mirostat_eta=); None: the keyword is not passed
+    # (serving/stages.py, MIROSTAT)
+    mirostat_tau: Optional[float] = None
+    mirostat_eta: Optional[float] = None
     # the DRY sampler's values, handed to stage.generate(dry_multiplier=, dry_base=, dry_allowed_length=, dry_range=,
     # dry_sequence_breakers=); None: the keyword is not passed (serving/stages.py, DRY)
     dry_multiplier: Optional[float] = None
@@ -269,7 +274,7 @@ class PipelineConfig:
             kw["stop_sequences"] = tuple(e if isinstance(e, str) else tuple(int(t) for t in e) for e in sec["stop_sequences"])
         if sec.get("no_repeat_ngram_size") is not None:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
-        for name in ("typical_p", "epsilon_cutoff", "eta_cutoff"):
+        for name in ("typical_p", "epsilon_cutoff", "eta_cutoff", "mirostat_tau", "mirostat_eta"):
             if sec.get(name) is not None:
                 kw[name] = float(sec[name])
         for name, kind in (("dry_multiplier", float), ("dry_base", float), ("dry_allowed_length", int), ("dry_range", int)):
@@ -632,7 +637,8 @@ class AdaptiveSpeculativePipeline:
                 if cfg.no_repeat_ngram_size is not None:                # (the call's own value, shared or per request, replaces it below)
                     stop_kw["no_repeat_ngram_size"] = int(cfg.no_repeat_ngram_size)
                 for name in ("typical_p", "epsilon_cutoff", "eta_cutoff",       # the entropy cuts and DRY: only those that are set
-                             "dry_multiplier", "dry_base", "dry_allowed_length", "dry_range", "dry_sequence_breakers"):
+                             "dry_multiplier", "dry_base", "dry_allowed_length", "dry_range", "dry_sequence_breakers",
+                             "mirostat_tau", "mirostat_eta"):                    # ... and Mirostat
                     if getattr(cfg, name) is not None:
                         stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:

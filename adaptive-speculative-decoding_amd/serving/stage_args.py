@@ -150,6 +150,40 @@ def check_entropy_cuts(typical_p, epsilon_cutoff, eta_cutoff, n: int) -> List[Tu
     return rows
 
 
+def check_mirostat(tau, eta, n: int, eta_given: bool = False) -> List[Tuple[float, float]]:
+    """generate's `mirostat_tau` and `mirostat_eta` (llama.cpp's mirostat_v2): each one number for all `n` prompts or a sequence
+    of n numbers -> every row's (tau, eta), (0.0, 0.0) where the row is off.  tau lies in [0, 32] and is off at 0; eta lies in
+    (0, 1].  eta_given: the call named an eta of its own, which needs a row that is on.  A bool, a NaN, a value outside its
+    range, the wrong length and eta without tau raise ValueError."""
+    def number(name, lo_open, hi):
+        def one(v):
+            ok = not isinstance(v, bool) and isinstance(v, _NUMBER) and (0.0 < float(v) if lo_open else 0.0 <= float(v)) and float(v) <= hi
+            if not ok:                                                           # (NaN included)
+                raise ValueError(f"{name} must be a number in {'(' if lo_open else '['}0, {hi:g}], got {v!r}")
+            return float(np.float32(v))                                          # the value the device record holds
+        return one
+    for name, value in (("mirostat_tau", tau), ("mirostat_eta", eta)):
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+    taus = _per_prompt(tau, n, number("mirostat_tau", False, 32.0), "mirostat_tau values")
+    etas = _per_prompt(eta, n, number("mirostat_eta", True, 1.0), "mirostat_eta values")
+    if eta_given and not any(t > 0.0 for t in taus):
+        raise ValueError("mirostat_eta without mirostat_tau: no row of the call has Mirostat on")
+    return [(t, e) if t > 0.0 else (0.0, 0.0) for t, e in zip(taus, etas)]
+
+
+def check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows) -> None:
+    """A row with Mirostat on runs it IN PLACE of the truncation chain (llama.cpp): top-k, top-p, min-p, typical-p, epsilon or
+    eta on the same row and side raise ValueError.  top_k / top_p / min_p: one value or a list per row; cut_rows: every row's
+    (mode, value) of the entropy cut."""
+    n = len(miro_rows)
+    cols = [v if isinstance(v, list) else [v] * n for v in (top_k, top_p, min_p)]
+    for b, ((tau, _), k, p, m, (mode, _)) in enumerate(zip(miro_rows, *cols, cut_rows)):
+        if tau > 0.0 and (int(k) > 0 or 0.0 < float(p) < 1.0 or float(m) > 0.0 or mode != CUT_OFF):
+            raise ValueError(f"prompt {b}: Mirostat replaces top-k, top-p, min-p, typical-p, epsilon_cutoff and eta_cutoff; "
+                             "a row cannot have both")
+
+
 def _check_sampling_value(v, name: str):
     """One temperature / top_p / top_k / min_p value of generate (PER-REQUEST SAMPLING)."""
     if name == "top_k":

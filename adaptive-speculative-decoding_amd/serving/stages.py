@@ -430,6 +430,40 @@ natural-looking histories (random ids over 300 distinct tokens) of 128 / 2048 / 
 3.4 / 7.3 / 12.4 us (ratios 3.3 / 4.1 / 16.0): every position is then a candidate and walks all 64 steps.  NOT BUILT: llama.cpp's multi-token breaker strings ("restart sequences"; breakers are single token ids),
 per-prompt breaker lists, separate draft-side values (the draft rows take the call's), and serving/hierarchy.py's loop.
 
+MIROSTAT.  `generate(mirostat_tau=, mirostat_eta=)` is llama.cpp's `mirostat_v2`: a cut of every token whose surprise exceeds a
+running target mu, which then moves by the surprise of the token that was taken.  Each takes one number for the call or one per
+prompt; tau (bits) lies in (0, 32] and 0 switches the row off, eta lies in (0, 1]; None takes the configuration's value:
+StageConfig.mirostat_tau / mirostat_eta are the stage's own draws at stage 0, target_mirostat_tau / target_mirostat_eta a
+verifying stage's own distribution -- the rule of min_p / target_min_p; tau defaults to 0 (off), eta to 0.1.  STATE: one real
+number mu_b per sequence, 2 tau_b at the start of a call.  INPUT: a row x of the stage's OWN distribution behind the mask, the
+automaton, the bad words, the n-gram rule, the edits, the penalties and DRY, untruncated, at the row's temperature;
+p = softmax(x / T), s_v = -log2 p_v.  At position j of sequence b:
+  1. token v is cut, its logit set to -inf in place, iff s_v > mu_{b,j} and x_v < x_max: every token that ties the maximum
+     survives (llama.cpp's "keep at least one").  Nothing else is written.
+  2. a row with a NaN or +inf element or without a finite one is left as it is and mu passes through it.
+  3. with Z the kept mass, the surprise of a kept token t under the cut, renormalised distribution is s^ = s_t + log2 Z.
+  4. mu_{b,j+1} = mu_{b,j} - eta_b (s^(tok_{b,j}) - tau_b), tok_{b,j} the step's proposal at position j.  A proposal that is cut
+     or already -inf is rejected with certainty: the rows behind it can never commit, stay untouched, and keep mu_{b,j}.
+  5. a step commits n_acc proposals and one token drawn at row n_acc with the log-prob lp that generate returns (under this
+     stage's cut, renormalised distribution): mu_b = mu_{b,n_acc} - eta_b (-lp / ln 2 - tau_b).  Stage 0 has one row and
+     n_acc = 0.  A sequence that has ended keeps its mu.
+So inside a verifying step the K + 1 rows of a sequence are a DEPENDENT CHAIN, which no other pass here has; the proposals are
+on the device already, and asd_mirostat_rows walks the chain there: one launch sweeps all B (K + 1) rows for their normalisers
+(the HBM read), a second one, one workgroup per sequence, cuts row after row out of L2 and carries mu (include/asd_hip.h);
+asd_mirostat_commit moves mu behind the step's commit and writes the mu in force at every committed token into a [B, cap] buffer,
+which `stats["mirostat_mu"][i]` (float32 [n_i]; NaN on a row that is off) returns with no read-back inside the loop.  It is the
+LAST in-place pass, behind the entropy cut's place, and acts on the stage's OWN distribution only: stage 0's draws and a
+verifying stage's [B, K+1, V] target output; the draft rows of a verifying stage are not touched (the draft stage's configured
+Mirostat is not applied to its proposals: the proposal distribution is free).  LOSSLESS: the verify, the residual draw and the
+commit are untouched and only ever see logits that carry the cut, and mu_{b,j} is a function of the accepted prefix alone -- the
+proposals 0 .. j-1, which are exactly the tokens committed when row j is reached -- so row j's cut distribution is the one plain
+Mirostat decoding would have had behind the same prefix, and the draft -> verify -> residual chain stays lossless against the
+Mirostat target distribution by the argument of LOGIT EDITS.  llama.cpp runs Mirostat IN PLACE of its truncation chain: a row
+with Mirostat on and top-k, top-p, min-p, typical_p, epsilon_cutoff or eta_cutoff on the same side raises ValueError, as do a
+bool, a NaN, a value outside its range, the wrong length and eta without tau -- all before any launch.  Greedy decoding ignores
+Mirostat and makes no call; a call whose every row is off makes exactly the ops calls it made before.  NOT BUILT: Mirostat v1;
+serving/hierarchy.py's loop; Mirostat on a verifying stage's draft rows.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -451,7 +485,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_mirostat, check_mirostat_alone, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -490,6 +524,11 @@ class StageConfig:
     target_typical_p: float = 1.0            # the three of a verifying stage's own distribution
     target_epsilon_cutoff: float = 0.0
     target_eta_cutoff: float = 0.0
+    # Mirostat v2 (module docstring, MIROSTAT), by the rule of min_p / target_min_p; a side that has it has no truncation
+    mirostat_tau: float = 0.0                # the target surprise in bits of the stage's own draws at stage 0, in (0, 32]; 0: off
+    mirostat_eta: float = 0.1                # its learning rate, in (0, 1]
+    target_mirostat_tau: float = 0.0         # the two of a verifying stage's own distribution
+    target_mirostat_eta: float = 0.1
     draft_len: int = 8
     seed: int = 0
     sync_every: int = 4
@@ -544,6 +583,7 @@ class _Plan(NamedTuple):
     token_stats: bool = False                # the per-token statistics and the predictor's feature batch (TOKEN STATS)
     cut_rows: Optional[list] = None          # every row's (mode, value) of the stage's own entropy cut; None: every row off
     cut_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, value) of the draft stage's configured cut
+    miro_rows: Optional[list] = None         # every row's (tau, eta) of the stage's own Mirostat; None: every row off
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
 
 
@@ -642,6 +682,34 @@ class _CutState:
         entered = logits.clone() if keep else None
         self.ops.entropy_cut_rows(logits, self.packed)
         return entered
+
+
+class _MiroState:
+    """What a generate call with Mirostat on keeps (module docstring, MIROSTAT): the rows' {1 / temperature, tau, eta} records
+    and the running target mu (2 tau at the start) on the device, uploaded once; the step's mu_path; and the [B, cap] buffer
+    of the mu in force at every committed token, filled behind the commit like the log-prob buffer (NaN where nothing was
+    committed and on a row that is off).  `apply` is the loops' one call per step on the stage's OWN logits, the last one ahead
+    of the draw or settle call; `commit` runs behind the step's commit."""
+
+    def __init__(self, ops, rows, inv_t: List[float], B: int, cap: int, device):
+        self.ops = ops
+        self.packed = ops.pack_mirostat(inv_t, [t for t, _ in rows], [e for _, e in rows], device)
+        self.out = torch.full((B, cap), float("nan"), dtype=torch.float32, device=device)
+        self.path = None
+
+    def apply(self, logits: torch.Tensor, tok32: Optional[torch.Tensor] = None, keep: bool = False) -> Optional[torch.Tensor]:
+        """logits [B, V] or [B, K+1, V], cut in place; tok32: the step's proposals.  keep: the tests' record -- a clone of the
+        tensor as it entered."""
+        entered = logits.clone() if keep else None
+        self.path = self.ops.mirostat_rows(logits, self.packed, tok32)
+        return entered
+
+    def commit(self, n_acc: torch.Tensor, lp: torch.Tensor, seq_len: torch.Tensor, n_commit: torch.Tensor) -> None:
+        self.ops.mirostat_commit(self.packed, self.path, n_acc, lp, seq_len, n_commit, self.out)
+
+    def stats(self, P: int, n_tok) -> dict:
+        mu = self.out[:, P:].cpu().numpy()
+        return {"mirostat_mu": [np.ascontiguousarray(r[:n]) for r, n in zip(mu, n_tok)]}
 
 
 class _FsmState:
@@ -1078,6 +1146,7 @@ class _CallState:
         inv_t = list(plan.rows[0]) if plan.rows else [plan.inv_t] * B
         self.cut = _CutState(ops, plan.cut_rows, inv_t, dev) if plan.cut_rows else None
         self.cut_draft = _CutState(ops, plan.cut_draft_rows, inv_t, dev) if plan.cut_draft_rows else None
+        self.miro = _MiroState(ops, plan.miro_rows, inv_t, B, P + plan.max_tokens, dev) if plan.miro_rows else None
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -1109,6 +1178,8 @@ class Stage:
         _check_min_p(config.target_min_p, "target_min_p")
         check_entropy_cuts(config.typical_p, config.epsilon_cutoff, config.eta_cutoff, 1)
         check_entropy_cuts(config.target_typical_p, config.target_epsilon_cutoff, config.target_eta_cutoff, 1)
+        check_mirostat(config.mirostat_tau, config.mirostat_eta, 1)
+        check_mirostat(config.target_mirostat_tau, config.target_mirostat_eta, 1)
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -1161,7 +1232,8 @@ class Stage:
                  typical_p=None, epsilon_cutoff=None,
                  eta_cutoff=None,
                  dry_multiplier=None, dry_base=None, dry_allowed_length=None, dry_range=None,
-                 dry_sequence_breakers=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 dry_sequence_breakers=None,
+                 mirostat_tau=None, mirostat_eta=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1282,7 +1354,16 @@ class Stage:
         result never falls below the dtype's lowest finite value.  Draft and target logits receive the same penalty, directly
         behind the penalties above and ahead of the entropy cuts, under greedy decoding too, and log-probs, top-N tables and
         token statistics are those of the penalised distribution.  A bool, a NaN, a value outside its range, the wrong length,
-        more than 32 breakers and a breaker string of 0 or several ids raise ValueError (module docstring, DRY)."""
+        more than 32 breakers and a breaker string of 0 or several ids raise ValueError (module docstring, DRY).
+        `mirostat_tau`, `mirostat_eta` (llama.cpp's mirostat_v2): None = the configuration's (StageConfig.mirostat_tau /
+        mirostat_eta at stage 0, target_mirostat_tau / target_mirostat_eta at a verifying stage: the rule of `min_p`); one
+        number for every prompt or one per prompt.  tau, the target surprise in bits, lies in (0, 32], and 0 switches the row
+        off; eta lies in (0, 1].  Every token whose surprise -log2 p under softmax(x / T) of the processed row exceeds the
+        row's running target mu is cut (the maximum's ties stay); mu starts at 2 tau and moves by eta (tau - surprise of the
+        committed token under the cut distribution) per token, through the rows of a verifying step too.  It runs LAST, in
+        place of top-k, top-p, min-p and the entropy cuts: any of them on the same row raises ValueError, as do a bool, a NaN, a
+        value outside its range, the wrong length and eta without tau.  stats["mirostat_mu"][i]: float32 [n_i], the mu in
+        force when token i was drawn (NaN on a row that is off).  Greedy decoding ignores both (module docstring, MIROSTAT)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1291,7 +1372,7 @@ class Stage:
                           repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
                           guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats,
                           typical_p, epsilon_cutoff, eta_cutoff, dry_multiplier, dry_base, dry_allowed_length, dry_range,
-                          dry_sequence_breakers)
+                          dry_sequence_breakers, mirostat_tau, mirostat_eta)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1320,6 +1401,8 @@ class Stage:
             stats.update(state.stats.stats(P, n_tok, feats))
         if state.prompt is not None:
             stats.update(state.prompt.stats())
+        if state.miro is not None:
+            stats.update(state.miro.stats(P, n_tok))
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
@@ -1327,7 +1410,8 @@ class Stage:
               repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm=None,
               guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None,
               token_stats=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, dry_multiplier=None, dry_base=None,
-              dry_allowed_length=None, dry_range=None, dry_sequence_breakers=None) -> _Plan:
+              dry_allowed_length=None, dry_range=None, dry_sequence_breakers=None, mirostat_tau=None,
+              mirostat_eta=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1396,6 +1480,9 @@ class Stage:
         dry = check_dry(given(dry_multiplier, cfg.dry_multiplier), given(dry_base, cfg.dry_base),
                         given(dry_allowed_length, cfg.dry_allowed_length), given(dry_range, cfg.dry_range),
                         given(dry_sequence_breakers, cfg.dry_sequence_breakers), n, V, self.tokenizer)
+        own_miro = (cfg.mirostat_tau, cfg.mirostat_eta) if self.draft is None else (cfg.target_mirostat_tau, cfg.target_mirostat_eta)
+        miro_rows = check_mirostat(given(mirostat_tau, own_miro[0]), given(mirostat_eta, own_miro[1]), n, mirostat_eta is not None)
+        check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows)
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -1418,7 +1505,8 @@ class Stage:
                      token_stats=token_stats,
                      cut_rows=cut_rows if not greedy and any(m for m, _ in cut_rows) else None,        # greedy ignores the cuts
                      cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
-                     dry=dry if any(m > 0.0 for m in dry[0]) else None)           # every row off: no state, no call
+                     dry=dry if any(m > 0.0 for m in dry[0]) else None,           # every row off: no state, no call
+                     miro_rows=miro_rows if not greedy and any(t > 0.0 for t, _ in miro_rows) else None)    # greedy ignores Mirostat
 
     def _buffers(self, ids: torch.Tensor, cap: int):
         B, P = ids.shape
@@ -1438,7 +1526,7 @@ class Stage:
         dev = ids.device
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram, stat, cut, dry = st.fsm, st.ngram, st.stats, st.cut, st.dry
+        fsm, ngram, stat, cut, dry, miro = st.fsm, st.ngram, st.stats, st.cut, st.dry, st.miro
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1465,15 +1553,20 @@ class Stage:
             if dry is not None:
                 dry.apply(logits, tokens, seq_len)                       # ... and DRY behind them, on the n-gram rule's history
             cut_in = cut.apply(logits, self.keep_inputs) if cut is not None else None   # the entropy cut: behind every processor
+            miro_in = miro.apply(logits, None, self.keep_inputs) if miro is not None else None   # Mirostat: the LAST pass
             n_acc, tok, lp = sampler.draw(logits, step)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
             if kept is not None and cut is not None:
                 kept["cut_in"] = cut_in
+            if kept is not None and miro is not None:
+                kept.update(miro_in=miro_in, mu_path=miro.path.clone())
             if stat is not None:
                 stat.score(logits, None, n_acc, tok)                     # one pass: the statistics, and the table when it is on
             elif top is not None:
                 top.score(logits)
             end.commit(None, None, n_acc, tok, lp, seq_len, tokens, lps, n_commit, cap)
+            if miro is not None:
+                miro.commit(n_acc, lp, seq_len, n_commit)                # mu moves by the drawn token's surprise
             if top is not None:
                 top.commit(seq_len, n_commit)
             if stat is not None:
@@ -1512,7 +1605,7 @@ class Stage:
         Kd = cfg.draft_len
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram, stat, cut, cut_draft, dry = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft, st.dry
+        fsm, ngram, stat, cut, cut_draft, dry, miro = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft, st.dry, st.miro
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -1577,10 +1670,13 @@ class Stage:
             if dry is not None:
                 dry.apply(t_out, tokens, seq_len)                       # the same records and history per row as the draft's rows had
             cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None    # the call's own cut on the K + 1 rows
+            miro_in = miro.apply(t_out, tok32, self.keep_inputs) if miro is not None else None   # Mirostat, chained through the rows
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
             if kept is not None and cut is not None:
                 kept["cut_in"] = cut_in
+            if kept is not None and miro is not None:
+                kept.update(miro_in=miro_in, mu_path=miro.path.clone())
             if kept is not None and cut_draft is not None:              # the draft rows as they entered and as they left the cut
                 kept["cut_in_draft"] = torch.stack(cut_in_draft, 1)
                 kept["cut_out_draft"] = torch.stack(sampler.dls, 1)
@@ -1589,6 +1685,8 @@ class Stage:
             elif top is not None:
                 top.score(t_out)                                        # the [B, K+1, V] output as returned, not a copy
             end.commit(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            if miro is not None:
+                miro.commit(n_acc, lp_drawn, seq_len, n_commit)          # mu_{n_acc}, moved by the drawn token's surprise
             if top is not None:
                 top.commit(seq_len, n_commit)
             if stat is not None:

@@ -818,6 +818,64 @@ int asd_dry_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_
                  const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mirostat v2 AHEAD of the samplers -- llama.cpp's `mirostat_v2` sampler: every token whose surprise exceeds a running target
+ * mu is cut, and mu moves by the surprise of the token that was taken.  Unlike every other pass the state is a real number
+ * per sequence, and inside a verifying step the K1 rows of a sequence are a DEPENDENT CHAIN: the cut of row j+1 depends on the
+ * surprise of the proposal at row j under row j's cut, renormalised distribution.
+ * logits: asd_entropy_cut_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last
+ * stride, any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only.
+ * table: B records {float inv_t; float tau; float eta} (asd_mirostat_rec, 12 bytes) on the device.  tau == 0: sequence b is
+ * off, nothing of it is read or written (mu_path[b] included).  THE DATA CONTRACT: a record whose tau, eta or inv_t is not a
+ * positive finite number is off.
+ * mu[b]: the target in force at row 0, mu_{b,0} (2*tau at the start of a generation; asd_mirostat_commit moves it).
+ * tok [B, ld_tok]: the step's proposals, tok[b][j] scored by row j, j < K1-1; row K1-1 has none.  NULL when K1 == 1.
+ * For row (b, j) as it stands, p = softmax(x * inv_t), s_v = -log2 p_v:
+ *   1. v is cut -- its logit becomes -inf of the dtype -- iff s_v > mu_{b,j} and x_v < x_max: every element that ties the
+ *      maximum survives.  Nothing else is written; a 16-byte vector is stored only where a bit of it changes.
+ *   2. A row with a NaN or +inf element, or without a finite element, is left as it is and mu_{b,j+1} = mu_{b,j}.
+ *   3. Z_{b,j}: the kept mass.  The surprise of a kept token t under the cut, renormalised distribution: s^ = s_t + log2 Z.
+ *   4. mu_{b,j+1} = mu_{b,j} - eta * (s^(tok[b][j]) - tau).  If tok[b][j] is cut, already -inf or outside [0, V) (never
+ *      dereferenced), it is rejected with certainty: rows j+1 .. are left UNTOUCHED and mu_{b,j'} = mu_{b,j} for j' > j.
+ * mu_path [B, K1] out: mu_path[b][j] = mu_{b,j}, the target in force at row j (mu_path[b][0] = mu[b]).  mu is not written.
+ * Arithmetic: two launches.  k_mirostat_lse, grid (K1, B), 1024 threads per row: one sweep takes (m2, s) by the recurrences of
+ * asd_verify_accept and the exact maximum, merged lanes -> waves in a fixed order, and leaves {L.hi, L.lo, x_max, ok} per row
+ * in the workspace (L = m2 + log2 s in two floats).  k_mirostat_chain, grid (B), 1024 threads per sequence, rows in order: one
+ * sweep per row compares log2 p_v = fma(x_v, c2, -L.hi) - L.lo (c2 = float(log2(e) * inv_t)) with -mu_{b,j} in f32 and sums
+ * 2^(log2 p_v) of the kept elements in the same fixed order; s^ and the step of mu are formed in f64 and mu_{b,j+1} is rounded
+ * to f32.  The result depends on the bytes of the rows, the records, mu and tok only.
+ * workspace: at least B*K1*ASD_MIROSTAT_ROW_BYTES bytes, aligned to 16; no initialisation.
+ * Status, in this order: negative B / K1 / V: invalid argument; B, K1 or V == 0: ASD_OK, nothing launched; unknown dtype,
+ * B > 65535, K1 > ASD_MAX_DRAFT_LEN + 1, V * element size > INT32_MAX: unsupported; NULL logits / table / mu / mu_path /
+ * workspace, ld_row < V, ld_seq < K1*ld_row, K1 > 1 with NULL tok or ld_tok < K1-1, workspace_bytes too small: invalid
+ * argument; logits not aligned to the element size, table / mu / mu_path / tok not aligned to 4, workspace not to 16: alignment.
+ *
+ * asd_mirostat_commit: behind the step's commit kernel (asd_commit_step_lp / _stop / _finish, which left seq_len and n_commit).
+ * For a sequence that is on, with a = clamp(n_acc[b], 0, K1-1) and c = min(n_commit[b], a+1): c <= 0 (a finished sequence):
+ * nothing moves.  Else mu_out[b][seq_len[b] - c + i] = mu_path[b][i] for i < c (positions outside [0, max_len) are skipped):
+ * the mu in force when each committed token was drawn; and, when c == a+1 and lp[b] -- the log-prob of the step's last
+ * committed token under the cut, renormalised distribution, as the samplers return it -- is finite:
+ * mu[b] = float(mu_path[b][a] - eta * (-lp[b] / ln 2 - tau)) in f64.  A sequence that ended inside the accepted prefix keeps mu.
+ * mu_out: [B][max_len] float, contiguous.  One thread per sequence.
+ * Status: B < 0, K1 < 1, max_len < 1: invalid argument; B == 0: ASD_OK; a NULL pointer: invalid argument; a pointer not
+ * aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_MIROSTAT_REC_BYTES 12
+#define ASD_MIROSTAT_ROW_BYTES 16
+typedef struct asd_mirostat_rec {
+    float inv_t;   /* 1 / temperature of the sequence */
+    float tau;     /* the target surprise in bits; 0: off */
+    float eta;     /* the learning rate */
+} asd_mirostat_rec;
+int asd_mirostat_rows(void* logits /*in/out*/, int dtype, int B, int K1, int V, int64_t ld_seq, int64_t ld_row,
+                      const asd_mirostat_rec* table /*[B]*/, const float* mu /*[B]*/,
+                      const int32_t* tok /*[B, ld_tok], or NULL when K1 == 1*/, int64_t ld_tok, float* mu_path /*[B, K1] out*/,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int asd_mirostat_commit(const float* mu_path /*[B, K1]*/, int B, int K1, const int32_t* n_acc /*[B]*/, const float* lp /*[B]*/,
+                        const int32_t* seq_len /*[B]: AFTER the step's commit*/, const int32_t* n_commit /*[B]*/,
+                        const asd_mirostat_rec* table /*[B]*/, float* mu /*[B] in/out*/, float* mu_out /*[B, max_len]*/, int max_len,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /
  * structured-output back ends compile a set of answers, a regex or a schema to.  Inside a speculative step the mask of
  * position j depends on the proposals 0 .. j-1, which exist only on the device: so the state lives there, small kernels
