@@ -44,7 +44,8 @@ SOURCES = {
     "entropy_cut.hip": ["-ffp-contract=off"],     # token_stats.hip's (m2, s, u) recurrences, and keys a reference must be able to restate
     "dry.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # one f32 subtraction per penalised element: nothing to fuse, nothing to pack
     "mirostat.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # keys and sums a reference must be able to restate
-    "fsm.hip": [],                              # logit_mask.hip's write stream and integer searches: no floating-point arithmetic
+    "relative_cut.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # sums a reference must be able to bound term by term
+    "fsm.hip": [],                             # logit_mask.hip's write stream and integer searches: no floating-point arithmetic
     "penalty.hip": ["-ffp-contract=off"],         # y - freq * c must round twice, as the header and the numpy reference state it
     "lm_head_verify.hip": ["-ffp-contract=off"],  # ends in the same finish_row arithmetic as verify_accept.hip
     "decision.hip": ["-ffp-contract=off"],

@@ -11,10 +11,10 @@
 //   word 0  : the proposal uniform of slot k        -> r_draft[k][b]
 //   word 1  : the accept uniform of slot k          -> u[b][k]
 //   word 2  : the commit uniform, from k = 0 only   -> r_commit[b]
-//   word 3  : unused
+//   word 3  : the coin of slot k (asd_step_uniforms_ex only: XTC's per-position coin) -> coin[b][k]
 //   float   = float(x >> 8) * 2^-24                 exact, in [0, 1): torch.rand's range
 //
-// One thread per (b, k), k < max(K_draft, K_accept, 1); no LDS, no atomics, no workspace; plain vector stores.
+// One thread per (b, k), k < max(K_draft, K_accept, k_coin, 1); no LDS, no atomics, no workspace; plain vector stores.
 
 #include <hip/hip_runtime.h>
 
@@ -45,10 +45,11 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
 
 __device__ __forceinline__ float to_uniform(uint32_t x) { return static_cast<float>(x >> 8) * 0x1.0p-24f; }
 
+template <bool kCoin>
 __global__ __launch_bounds__(kThreads) void k_step_uniforms(const uint64_t* __restrict__ seeds, uint32_t step, uint32_t stage,
                                                             int B, int K_draft, int K_accept, int K_max,
                                                             float* __restrict__ r_draft, float* __restrict__ u,
-                                                            float* __restrict__ r_commit) {
+                                                            float* __restrict__ r_commit, float* __restrict__ coin, int k_coin) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
     if (idx >= static_cast<int64_t>(B) * K_max) return;
     const int b = static_cast<int>(idx / K_max);
@@ -59,6 +60,9 @@ __global__ __launch_bounds__(kThreads) void k_step_uniforms(const uint64_t* __re
     if (r_draft && k < K_draft) r_draft[static_cast<int64_t>(k) * B + b] = to_uniform(w.x);
     if (u && k < K_accept) u[static_cast<int64_t>(b) * K_accept + k] = to_uniform(w.y);
     if (r_commit && k == 0) r_commit[b] = to_uniform(w.z);
+    if constexpr (kCoin) {
+        if (k < k_coin) coin[static_cast<int64_t>(b) * k_coin + k] = to_uniform(w.w);
+    }
 }
 
 }  // namespace
@@ -74,7 +78,32 @@ ASD_EXPORT int asd_step_uniforms(const int64_t* seeds, uint32_t step, uint32_t s
     if (!aligned_to(seeds, 8) || !aligned_to(r_draft, 4) || !aligned_to(u, 4) || !aligned_to(r_commit, 4)) return ASD_ERR_ALIGNMENT;
     const int K_max = K_draft > K_accept ? (K_draft > 1 ? K_draft : 1) : (K_accept > 1 ? K_accept : 1);
     const int64_t blocks = (static_cast<int64_t>(B) * K_max + kThreads - 1) / kThreads;      // <= 2^31 * 64 / 256
-    hipLaunchKernelGGL(k_step_uniforms, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const uint64_t*>(seeds), step, stage, B, K_draft, K_accept, K_max, r_draft, u, r_commit);
+    hipLaunchKernelGGL(k_step_uniforms<false>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const uint64_t*>(seeds), step, stage, B, K_draft, K_accept, K_max, r_draft, u, r_commit,
+                       static_cast<float*>(nullptr), 0);
+    return launch_status();
+}
+
+ASD_EXPORT int asd_step_uniforms_ex(const int64_t* seeds, uint32_t step, uint32_t stage, int B, int K_draft, int K_accept,
+                                    float* r_draft, float* u, float* r_commit, float* coin, int k_coin, void* stream) {
+    if (B < 1 || K_draft < 0 || K_accept < 0 || K_draft > ASD_MAX_DRAFT_LEN || K_accept > ASD_MAX_DRAFT_LEN) return ASD_ERR_INVALID_ARG;
+    if (k_coin < 0 || k_coin > ASD_MAX_DRAFT_LEN + 1) return ASD_ERR_INVALID_ARG;
+    if (!seeds || (!r_draft && !u && !r_commit && !coin)) return ASD_ERR_INVALID_ARG;
+    if ((r_draft && K_draft < 1) || (u && K_accept < 1) || (coin != nullptr) != (k_coin > 0)) return ASD_ERR_INVALID_ARG;
+    if (!aligned_to(seeds, 8) || !aligned_to(r_draft, 4) || !aligned_to(u, 4) || !aligned_to(r_commit, 4) || !aligned_to(coin, 4))
+        return ASD_ERR_ALIGNMENT;
+    int K_max = K_draft > K_accept ? K_draft : K_accept;
+    K_max = K_max > k_coin ? K_max : k_coin;
+    K_max = K_max > 1 ? K_max : 1;
+    const int64_t blocks = (static_cast<int64_t>(B) * K_max + kThreads - 1) / kThreads;
+    const dim3 grid(static_cast<uint32_t>(blocks)), block(kThreads);
+    if (k_coin > 0)
+        hipLaunchKernelGGL(k_step_uniforms<true>, grid, block, 0, static_cast<hipStream_t>(stream),
+                           reinterpret_cast<const uint64_t*>(seeds), step, stage, B, K_draft, K_accept, K_max, r_draft, u, r_commit,
+                           coin, k_coin);
+    else
+        hipLaunchKernelGGL(k_step_uniforms<false>, grid, block, 0, static_cast<hipStream_t>(stream),
+                           reinterpret_cast<const uint64_t*>(seeds), step, stage, B, K_draft, K_accept, K_max, r_draft, u, r_commit,
+                           static_cast<float*>(nullptr), 0);
     return launch_status();
 }

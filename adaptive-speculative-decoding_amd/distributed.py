@@ -417,25 +417,31 @@ class HipOps:
         self.K.commit_top_logprobs(top_id, top_lp, seq_len, n_commit, out_id, out_lp, max_len=max_len)
 
     @traced("step_uniforms")
-    def step_uniforms(self, seeds, step, stage, K_draft, K_accept, commit: bool = True, out=None):
+    def step_uniforms(self, seeds, step, stage, K_draft, K_accept, commit: bool = True, out=None, k_coin: int = 0):
         """Every uniform of a seeded decoding step in ONE launch (asd_step_uniforms; Philox4x32-10 keyed by seeds[b] i64 [B],
         counter (step, k, stage, 0)) -> (r_draft f32 [K_draft, B] | None, u f32 [B, K_accept] | None, r_commit f32 [B] | None):
         r_draft[k] is the proposal uniform of slot k, u[:, k] the accept uniform of slot k.  An output whose K is 0 (and
         r_commit with commit=False) is None and not written.  The three are views of `out`, one f32 buffer of at least
         (K_draft + K_accept + 1) * B elements that a stage loop allocates once per generate call (None: a fresh one), so a
-        step's uniforms are valid until the next call on the same buffer (stream order)."""
+        step's uniforms are valid until the next call on the same buffer (stream order).  k_coin > 0 (asd_step_uniforms_ex):
+        a fourth result coin f32 [B, k_coin], word 3 of slot k -- XTC's coin of logits position k -- behind the three in
+        `out`, which then holds k_coin * B elements more; the three keep their bits.  k_coin == 0 is the call as it was."""
         Bv = seeds.shape[0]
-        Kd, Ka = int(K_draft), int(K_accept)
-        need = (Kd + Ka + 1) * Bv
+        Kd, Ka, Kc = int(K_draft), int(K_accept), int(k_coin)
+        need = (Kd + Ka + 1 + Kc) * Bv
         if out is None:
             out = torch.empty((need,), dtype=torch.float32, device=seeds.device)
         if out.dim() != 1 or out.numel() < need:
             raise ValueError(f"out must be a float32 vector of at least {need} elements")
         r_draft = out[:Kd * Bv].view(Kd, Bv) if Kd > 0 else None
         u = out[Kd * Bv:(Kd + Ka) * Bv].view(Bv, Ka) if Ka > 0 else None
-        r_commit = out[(Kd + Ka) * Bv:need] if commit else None
-        self.K.step_uniforms(seeds, step, stage, r_draft, u, r_commit)
-        return r_draft, u, r_commit
+        r_commit = out[(Kd + Ka) * Bv:(Kd + Ka + 1) * Bv] if commit else None
+        if Kc == 0:
+            self.K.step_uniforms(seeds, step, stage, r_draft, u, r_commit)
+            return r_draft, u, r_commit
+        coin = out[(Kd + Ka + 1) * Bv:need].view(Bv, Kc)
+        self.K.step_uniforms(seeds, step, stage, r_draft, u, r_commit, coin)
+        return r_draft, u, r_commit, coin
 
     def pack_logit_edits(self, rows, device):
         """One list of (id, bias, until) per batch row -> the device arrays of logit_edit_rows (kernels.pack_logit_edits: checked
@@ -550,6 +556,22 @@ class HipOps:
         from softmax(x / T) of the row as it stands.  One launch, no workspace, no state; a stage loop makes the call once per
         logits tensor, behind penalty_rows and directly ahead of the draw, and only when some row of the call has a cut."""
         return self.K.entropy_cut_rows(logits, cut)
+
+    @traced("pack_relative_cut")
+    def pack_relative_cut(self, inv_t, modes, a, b, device):
+        """Every row's 1 / temperature, mode (0 off, 1 top_n_sigma, 2 top_a, 3 XTC), a (n, a or xtc_threshold) and b
+        (xtc_probability) -> the device table of relative_cut_rows (kernels.pack_relative_cut: one upload per generate call
+        and side)."""
+        return self.K.pack_relative_cut(inv_t, modes, a, b, device)
+
+    @traced("relative_cut_rows")
+    def relative_cut_rows(self, logits, packed, coins=None):
+        """llama.cpp's top_n_sigma / XTC and koboldcpp's top_a ahead of the samplers (asd_relative_cut_rows): logits [B, V] or
+        [B, K1, V] (any strides with a unit last stride) -> the same tensor, with every token at -inf that the row's cut
+        removes; coins f32 [B, K1]: XTC's coin of every row, None when no row has XTC on.  One launch, no workspace, no state;
+        a stage loop makes the call once per logits tensor, directly behind dry_rows and ahead of entropy_cut_rows, and only
+        when some row of the call has a relative cut."""
+        return self.K.relative_cut_rows(logits, packed, coins)
 
     @traced("pack_mirostat")
     def pack_mirostat(self, inv_t, taus, etas, device):

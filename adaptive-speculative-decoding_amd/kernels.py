@@ -1250,11 +1250,13 @@ def commit_top_logprobs(top_id: torch.Tensor, top_lp: torch.Tensor, seq_len: tor
 
 # ------------------------------------------------------------------------------- per-request seeds (SamplingParams(seed=...))
 def step_uniforms(seeds: torch.Tensor, step: int, stage: int, r_draft: Optional[torch.Tensor] = None,
-                  u: Optional[torch.Tensor] = None, r_commit: Optional[torch.Tensor] = None) -> None:
+                  u: Optional[torch.Tensor] = None, r_commit: Optional[torch.Tensor] = None,
+                  coin: Optional[torch.Tensor] = None) -> None:
     """Every uniform of a decoding step in one launch (asd_step_uniforms): Philox4x32-10 with key seeds[b] (int64 [B], read as
     uint64) and counter (step, k, stage, 0).  r_draft f32 [K_draft, B]: the proposal uniform of slot k; u f32 [B, K_accept]: the
     accept uniform of slot k; r_commit f32 [B]: the commit uniform.  An output left None is not written; at least one is
-    given.  Values lie in [0, 1) and depend on (seeds[b], step, stage, k) alone."""
+    given.  Values lie in [0, 1) and depend on (seeds[b], step, stage, k) alone.  coin f32 [B, k_coin]: the coin of slot k (word
+    3 of the slot, which nothing else reads); given, the call goes to asd_step_uniforms_ex, else to asd_step_uniforms."""
     if seeds.dim() != 1:
         raise ValueError("seeds must be int64 [B]")
     Bv = seeds.shape[0]
@@ -1266,6 +1268,16 @@ def step_uniforms(seeds: torch.Tensor, step: int, stage: int, r_draft: Optional[
         raise ValueError("u must be float32 [B, K_accept]")
     if r_commit is not None and tuple(r_commit.shape) != (Bv,):
         raise ValueError("r_commit must be float32 [B]")
+    if coin is not None:
+        if coin.dim() != 2 or coin.shape[0] != Bv or coin.shape[1] < 1:
+            raise ValueError("coin must be float32 [B, k_coin] with k_coin >= 1")
+        rc = _lib().asd_step_uniforms_ex(_dev(seeds, "seeds", torch.int64), int(step), int(stage), Bv,
+                                         0 if r_draft is None else r_draft.shape[0], 0 if u is None else u.shape[1],
+                                         _opt(r_draft, "r_draft", torch.float32), _opt(u, "u", torch.float32),
+                                         _opt(r_commit, "r_commit", torch.float32), _dev(coin, "coin", torch.float32),
+                                         coin.shape[1], _stream())
+        B.check("asd_step_uniforms_ex", rc)
+        return
     rc = _lib().asd_step_uniforms(_dev(seeds, "seeds", torch.int64), int(step), int(stage), Bv,
                                   0 if r_draft is None else r_draft.shape[0], 0 if u is None else u.shape[1],
                                   _opt(r_draft, "r_draft", torch.float32), _opt(u, "u", torch.float32),
@@ -1867,6 +1879,82 @@ def entropy_cut_rows(logits: torch.Tensor, cut: EntropyCut) -> torch.Tensor:
     rc = _lib().asd_entropy_cut_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], Bv, K1, V, ld_seq, ld_row,
                                      _dev(cut.table, "table", torch.uint8), _stream())
     B.check("asd_entropy_cut_rows", rc)
+    return logits
+
+
+# ------------------------------------------------------------------------------- relative cuts (top_n_sigma / top_a / xtc_*)
+RELCUT_OFF, RELCUT_TOP_N_SIGMA, RELCUT_TOP_A, RELCUT_XTC = 0, 1, 2, 3
+_RELCUT_REC = np.dtype([("inv_t", np.float32), ("mode", np.int32), ("a", np.float32), ("b", np.float32)])
+
+
+@dataclass
+class RelativeCut:
+    """The table of asd_relative_cut_rows on the device (pack_relative_cut): B records {inv_t f32, mode i32, a f32, b f32} of
+    16 bytes, as a uint8 [B, 16] tensor; `modes`: the host's copy of the rows' modes."""
+    table: torch.Tensor
+    modes: Tuple[int, ...]
+    B: int
+
+
+def check_relative_cut_rows(inv_t, modes, a, b) -> np.ndarray:
+    """The host side of pack_relative_cut: every row's 1 / temperature (a positive finite number), mode (0 off, 1 top-n-sigma,
+    2 top-a, 3 XTC), a (n > 0 and finite; top_a or xtc_threshold in (0, 1]) and b (xtc_probability in (0, 1], mode 3 only)
+    -> the records, a numpy structured array."""
+    inv_t, modes, a, b = list(inv_t), list(modes), list(a), list(b)
+    if not len(inv_t) == len(modes) == len(a) == len(b):
+        raise ValueError(f"{len(inv_t)} temperatures, {len(modes)} modes, {len(a)} and {len(b)} values must describe the same rows")
+    rec = np.zeros(len(modes), dtype=_RELCUT_REC)
+    for i, (t, m, va, vb) in enumerate(zip(inv_t, modes, a, b)):
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (0, 1, 2, 3):
+            raise ValueError(f"row {i}: the mode must be 0 (off), 1 (top-n-sigma), 2 (top-a) or 3 (XTC), got {m!r}")
+        t32, a32, b32 = np.float32(t), np.float32(va), np.float32(vb)
+        if isinstance(t, bool) or not (t32 > 0.0 and t32 < np.float32(3.0e38)):
+            raise ValueError(f"row {i}: 1 / temperature must be a positive finite number, got {t!r}")
+        m = int(m)
+        if m == RELCUT_TOP_N_SIGMA and (isinstance(va, bool) or not 0.0 < float(a32) < float("inf")):
+            raise ValueError(f"row {i}: top-n-sigma's n must be a positive finite number, got {va!r}")
+        if m in (RELCUT_TOP_A, RELCUT_XTC) and (isinstance(va, bool) or not 0.0 < float(a32) <= 1.0):
+            raise ValueError(f"row {i}: top_a / xtc_threshold of a row that is on must lie in (0, 1], got {va!r}")
+        if m == RELCUT_XTC and (isinstance(vb, bool) or not 0.0 < float(b32) <= 1.0):
+            raise ValueError(f"row {i}: xtc_probability of a row that is on must lie in (0, 1], got {vb!r}")
+        rec[i] = (t32, m, a32 if m else np.float32(0.0), b32 if m == RELCUT_XTC else np.float32(0.0))
+    return rec
+
+
+def pack_relative_cut(inv_t, modes, a, b, device) -> RelativeCut:
+    """The table of relative_cut_rows from host lists, checked BEFORE anything is uploaded."""
+    rec = check_relative_cut_rows(inv_t, modes, a, b)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _RELCUT_REC.itemsize).copy()).to(device)
+    return RelativeCut(table, tuple(int(m) for m in rec["mode"]), len(rec))
+
+
+def relative_cut_rows(logits: torch.Tensor, cut: RelativeCut, coins: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Cut in place (asd_relative_cut_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  Row (b, j) under record b: top-n-sigma cuts x < x_max - n sigma(x) over the finite
+    elements; top-a cuts p < a p_max^2 under p = softmax(x * inv_t); XTC, when the row's coin coins[b, j] (f32 [B, K1], unit
+    last stride) lies under its probability, cuts every token with p >= t except the least likely of them (ties kept).  A
+    cut token becomes -inf.  `coins` is needed exactly when a row is in mode 3."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if cut.B != Bv:
+        raise ValueError(f"the cuts were packed for {cut.B} rows; logits have {Bv}")
+    if coins is None and RELCUT_XTC in cut.modes:
+        raise ValueError("a row has XTC on: coins [B, K1] must be given")
+    ld_coin = 0
+    if coins is not None:
+        if not coins.is_cuda or coins.dtype != torch.float32 or tuple(coins.shape) != (Bv, K1) or \
+                (K1 > 1 and coins.stride(1) != 1) or (Bv > 1 and coins.stride(0) < K1):
+            raise ValueError(f"coins must be a float32 CUDA (HIP) tensor [{Bv}, {K1}] with unit stride along K1")
+        ld_coin = int(coins.stride(0)) if Bv > 1 else K1
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_relative_cut_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], Bv, K1, V, ld_seq, ld_row,
+                                      _dev(cut.table, "table", torch.uint8), None if coins is None else coins.data_ptr(), ld_coin,
+                                      _stream())
+    B.check("asd_relative_cut_rows", rc)
     return logits
 
 

@@ -47,6 +47,7 @@ batch or one per request, kept by the request through every regrouping, handed o
 `PipelineConfig.typical_p` / `epsilon_cutoff` / `eta_cutoff` (HF's warpers of those names; serving/stages.py, ENTROPY CUTS) are
 configuration only: a value that is set is handed to every stage's generate call as the keyword of that name, None is not passed.
 `PipelineConfig.mirostat_tau` / `mirostat_eta` (llama.cpp's mirostat_v2; serving/stages.py, MIROSTAT) travel the same way.
+`PipelineConfig.top_n_sigma` / `top_a` / `xtc_threshold` / `xtc_probability` (serving/stages.py, RELATIVE CUTS) travel the same way.
 `PipelineConfig.dry_multiplier` / `dry_base` / `dry_allowed_length` / `dry_range` / `dry_sequence_breakers` (the DRY sampler;
 serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
 
@@ -227,6 +228,12 @@ class PipelineConfig:
     # (serving/stages.py, MIROSTAT)
     mirostat_tau: Optional[float] = None
     mirostat_eta: Optional[float] = None
+    # llama.cpp's top_n_sigma and XTC and koboldcpp's top_a, handed to stage.generate(top_n_sigma=, top_a=, xtc_threshold=,
+    # xtc_probability=); None: the keyword is not passed (serving/stages.py, RELATIVE CUTS)
+    top_n_sigma: Optional[float] = None
+    top_a: Optional[float] = None
+    xtc_threshold: Optional[float] = None
+    xtc_probability: Optional[float] = None
     # the DRY sampler's values, handed to stage.generate(dry_multiplier=, dry_base=, dry_allowed_length=, dry_range=,
     # dry_sequence_breakers=); None: the keyword is not passed (serving/stages.py, DRY)
     dry_multiplier: Optional[float] = None
@@ -274,7 +281,8 @@ class PipelineConfig:
             kw["stop_sequences"] = tuple(e if isinstance(e, str) else tuple(int(t) for t in e) for e in sec["stop_sequences"])
         if sec.get("no_repeat_ngram_size") is not None:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
-        for name in ("typical_p", "epsilon_cutoff", "eta_cutoff", "mirostat_tau", "mirostat_eta"):
+        for name in ("typical_p", "epsilon_cutoff", "eta_cutoff", "mirostat_tau", "mirostat_eta",
+                     "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability"):
             if sec.get(name) is not None:
                 kw[name] = float(sec[name])
         for name, kind in (("dry_multiplier", float), ("dry_base", float), ("dry_allowed_length", int), ("dry_range", int)):
@@ -638,7 +646,8 @@ class AdaptiveSpeculativePipeline:
                     stop_kw["no_repeat_ngram_size"] = int(cfg.no_repeat_ngram_size)
                 for name in ("typical_p", "epsilon_cutoff", "eta_cutoff",       # the entropy cuts and DRY: only those that are set
                              "dry_multiplier", "dry_base", "dry_allowed_length", "dry_range", "dry_sequence_breakers",
-                             "mirostat_tau", "mirostat_eta"):                    # ... and Mirostat
+                             "mirostat_tau", "mirostat_eta",                     # ... and Mirostat
+                             "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability"):    # ... and the relative cuts
                     if getattr(cfg, name) is not None:
                         stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:

@@ -172,16 +172,66 @@ def check_mirostat(tau, eta, n: int, eta_given: bool = False) -> List[Tuple[floa
     return [(t, e) if t > 0.0 else (0.0, 0.0) for t, e in zip(taus, etas)]
 
 
-def check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows) -> None:
+def check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows, rel_rows=None) -> None:
     """A row with Mirostat on runs it IN PLACE of the truncation chain (llama.cpp): top-k, top-p, min-p, typical-p, epsilon or
     eta on the same row and side raise ValueError.  top_k / top_p / min_p: one value or a list per row; cut_rows: every row's
-    (mode, value) of the entropy cut."""
+    (mode, value) of the entropy cut; rel_rows: every row's (mode, a, b) of the relative cut, which Mirostat excludes too."""
     n = len(miro_rows)
     cols = [v if isinstance(v, list) else [v] * n for v in (top_k, top_p, min_p)]
     for b, ((tau, _), k, p, m, (mode, _)) in enumerate(zip(miro_rows, *cols, cut_rows)):
         if tau > 0.0 and (int(k) > 0 or 0.0 < float(p) < 1.0 or float(m) > 0.0 or mode != CUT_OFF):
             raise ValueError(f"prompt {b}: Mirostat replaces top-k, top-p, min-p, typical-p, epsilon_cutoff and eta_cutoff; "
                              "a row cannot have both")
+        if tau > 0.0 and rel_rows is not None and rel_rows[b][0] != RELCUT_OFF:
+            raise ValueError(f"prompt {b}: top_n_sigma, top_a or XTC together with Mirostat on one row is not built")
+
+
+RELCUT_OFF, RELCUT_TOP_N_SIGMA, RELCUT_TOP_A, RELCUT_XTC = 0, 1, 2, 3    # ASD_RELCUT_* of include/asd_hip.h (RELATIVE CUTS)
+XTC_THRESHOLD_MAX = 0.5                  # above it A = {p >= t} holds two tokens only through an exact tie: the row is off
+
+
+def check_relative_cuts(top_n_sigma, top_a, xtc_threshold, xtc_probability, n: int,
+                        xtc_probability_given: bool = False) -> List[Tuple[int, float, float]]:
+    """generate's `top_n_sigma`, `top_a`, `xtc_threshold` and `xtc_probability` (llama.cpp's and koboldcpp's samplers of those
+    names): each one number for all `n` prompts or a sequence of n numbers -> every row's (mode, a, b).  top_n_sigma is a
+    finite number >= 0 (0: off); top_a and xtc_probability lie in [0, 1] (0: off); xtc_threshold lies in [0, 1] (None: 0.1),
+    and a row whose threshold is 0 or above 0.5 has XTC off.  xtc_probability_given: the call named a probability of its own,
+    which needs a row with a usable threshold.  A row has at most one mode.  A bool, a NaN, a value outside its range, the
+    wrong length and a row with two modes ("not built") raise ValueError."""
+    def number(name, hi):
+        def one(v):
+            ok = not isinstance(v, bool) and isinstance(v, _NUMBER) and 0.0 <= float(v) <= hi and float(v) < float("inf")
+            if not ok:                                                           # (NaN included)
+                raise ValueError(f"{name} must be a number in [0, {'1]' if hi == 1.0 else 'inf)'}, got {v!r}")
+            return float(np.float32(v))                                          # the value the device record holds
+        return one
+    named = (("top_n_sigma", top_n_sigma, float("inf")), ("top_a", top_a, 1.0),
+             ("xtc_threshold", 0.1 if xtc_threshold is None else xtc_threshold, 1.0), ("xtc_probability", xtc_probability, 1.0))
+    cols = []
+    for name, value, hi in named:
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+        cols.append(_per_prompt(value, n, number(name, hi), f"{name} values"))
+    usable = [0.0 < t <= XTC_THRESHOLD_MAX for t in cols[2]]
+    if xtc_probability_given and any(q > 0.0 for q in cols[3]) and not any(u and q > 0.0 for u, q in zip(usable, cols[3])):
+        raise ValueError("xtc_probability without a usable xtc_threshold (in (0, 0.5]): no row of the call has XTC on")
+    rows = []
+    for b, (sig, a, t, q) in enumerate(zip(*cols)):
+        on = [(RELCUT_TOP_N_SIGMA, sig, 0.0)] * (sig > 0.0) + [(RELCUT_TOP_A, a, 0.0)] * (a > 0.0) + \
+            [(RELCUT_XTC, t, q)] * (q > 0.0 and usable[b])
+        if len(on) > 1:
+            raise ValueError(f"prompt {b}: more than one of top_n_sigma, top_a and XTC on one row is not built")
+        rows.append(on[0] if on else (RELCUT_OFF, 0.0, 0.0))
+    return rows
+
+
+def check_relative_cut_alone(rel_rows, cut_rows) -> None:
+    """A row takes ONE cut: a relative cut together with typical_p, epsilon_cutoff or eta_cutoff on the same row and side is
+    not built and raises ValueError.  rel_rows: every row's (mode, a, b); cut_rows: every row's (mode, value)."""
+    for b, ((rel, _, _), (cut, _)) in enumerate(zip(rel_rows, cut_rows)):
+        if rel != RELCUT_OFF and cut != CUT_OFF:
+            raise ValueError(f"prompt {b}: top_n_sigma, top_a or XTC together with typical_p, epsilon_cutoff or eta_cutoff "
+                             "on one row is not built")
 
 
 def _check_sampling_value(v, name: str):

@@ -464,6 +464,46 @@ bool, a NaN, a value outside its range, the wrong length and eta without tau -- 
 Mirostat and makes no call; a call whose every row is off makes exactly the ops calls it made before.  NOT BUILT: Mirostat v1;
 serving/hierarchy.py's loop; Mirostat on a verifying stage's draft rows.
 
+RELATIVE CUTS.  `generate(top_n_sigma=, top_a=, xtc_threshold=, xtc_probability=)` are llama.cpp's `top_n_sigma`, koboldcpp's
+`top_a` and XTC ("exclude top choices", llama.cpp's `xtc_threshold` / `xtc_probability`, the DRY sampler's companion): three
+truncations that cut a row relative to its own statistics -- its maximum, its normaliser, its mean and deviation.  Each takes
+one number for the call or one per prompt; None takes the configuration's value: StageConfig.top_n_sigma / top_a /
+xtc_threshold / xtc_probability are the stage's own draws at stage 0, target_* a verifying stage's own distribution -- the
+rule of min_p / target_min_p.  top_n_sigma is a finite number >= 0 and off at 0; top_a and xtc_probability lie in [0, 1] and
+are off at 0; xtc_threshold lies in [0, 1], defaults to 0.1, and is off above 0.5, where two tokens can both reach it only
+through an exact tie.  INPUT: the row as every earlier pass left it (mask -> fsm -> bad words -> n-gram -> edit -> penalties
+-> DRY), the values the stored ones, fin the set of its finite elements; a -inf element carries no mass, stays -inf and is
+counted in no statistic; a row with a NaN or +inf element or without a finite one is left bit for bit as it is.
+  top_n_sigma = n     mu = the mean over fin, sigma = sqrt(sum_fin (x_v - mu)^2 / |fin|) (the population deviation, llama.cpp's);
+                      token v is cut iff x_v < x_max - n sigma.  The temperature plays no part; every tie at the maximum stays.
+  top_a = a           with p = softmax(x / T), token v is cut iff p_v < a p_max^2 and x_v < x_max.
+  XTC (t, q)          with a coin c in [0, 1) for this (sequence, position): c >= q: nothing happens.  Otherwise A = {v : p_v >= t};
+                      fewer than two tokens in A: nothing happens; else x_lo is the smallest stored value in A and v is cut iff v is
+                      in A and x_v > x_lo.  Every token that ties x_lo stays -- this build's rule for ties; llama.cpp keeps one, in
+                      sort order.  XTC can cut the arg-max: that is its purpose.  It never empties a row.
+A cut token's logit becomes -inf in place; nothing else is written.  It is one more in-place pass (asd_relative_cut_rows; the
+rows' {1 / T, mode, a, b} records are uploaded once per call and side through ops.pack_relative_cut) directly behind DRY and
+ahead of the entropy cut's place: mask -> fsm -> bad words -> n-gram -> edit -> penalties -> DRY -> RELATIVE CUT -> temperature
+-> top-k -> top-p -> min-p.  For top-n-sigma this is llama.cpp's position.  THIS IS NOT llama.cpp's ORDER FOR XTC: llama.cpp
+runs XTC BEHIND top-k / top-p / min-p, on their survivors; here XTC sees the untruncated distribution and the three act on what
+it leaves.  With top-k, top-p and min-p off the kept set is llama.cpp's, up to the tie rule.  ONE CUT PER ROW: a row takes at
+most one of the three, none together with typical_p / epsilon_cutoff / eta_cutoff and none together with Mirostat; each raises
+ValueError (NOT BUILT).  THE COIN: a seeded call takes the coins from word 3 of the step's Philox slots, which no other draw
+reads -- ops.step_uniforms(..., k_coin=K + 1) at a verifying stage (position j of the target's output uses slot j), k_coin = 1
+at stage 0, in the step's ONE launch -- so switching XTC on moves no draft, accept or commit uniform, and a position's coin is
+the same whichever route the step takes; an unseeded call draws one torch.rand((B, K1)) on the stage's generator at the top of
+the step, and only when a row has XTC on.  At a verifying stage the target's [B, K+1, V] output takes the call's own cut and
+the draft rows the DRAFT stage's configured top-n-sigma / top-a; the draft stage's configured XTC is NOT applied to its
+proposals (NOT BUILT) -- the verify, the residual draw and the commit only ever see logits that carry the cut, and the chain is
+lossless for any draft distribution.  Log-probs, top-N tables and token statistics describe the distribution behind the cut.
+Greedy decoding ignores all four and makes no call; a call whose every row is off makes exactly the ops calls it made before.
+ValueError before any launch and before the prompts are encoded: a bool, a NaN, a value outside its range, the wrong length,
+two modes on one row, xtc_probability without a usable threshold on any row.  COST (profiles/relative_cut.json: B = 32,
+V = 152064, bf16, kernel time, against asd_entropy_cut_rows in epsilon mode on a copy of the same tensor): K1 = 9: 56.2 / 48.0 /
+54.6 us for top-n-sigma / top-a / XTC with every coin under q against 63.4 us (ratios 0.89 / 0.76 / 0.86; that baseline's
+spread 0.03), 5.0 us with every coin above q; K1 = 1: 25.3 / 21.8 / 25.6 / 4.8 us against 28.3 us.  NOT BUILT beside the above:
+serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -485,7 +525,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_mirostat, check_mirostat_alone, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -529,6 +569,15 @@ class StageConfig:
     mirostat_eta: float = 0.1                # its learning rate, in (0, 1]
     target_mirostat_tau: float = 0.0         # the two of a verifying stage's own distribution
     target_mirostat_eta: float = 0.1
+    # the relative cuts (module docstring, RELATIVE CUTS), by the rule of min_p / target_min_p; at most one of the three per side
+    top_n_sigma: float = 0.0                 # llama.cpp's top_n_sigma of the stage's own draws and of its proposals; 0: off
+    top_a: float = 0.0                       # koboldcpp's top_a of the same rows; 0: off
+    xtc_threshold: float = 0.1               # XTC of the stage's own draws (never of its proposals); off above 0.5
+    xtc_probability: float = 0.0             # ... 0: off
+    target_top_n_sigma: float = 0.0          # the four of a verifying stage's own distribution
+    target_top_a: float = 0.0
+    target_xtc_threshold: float = 0.1
+    target_xtc_probability: float = 0.0
     draft_len: int = 8
     seed: int = 0
     sync_every: int = 4
@@ -584,6 +633,8 @@ class _Plan(NamedTuple):
     cut_rows: Optional[list] = None          # every row's (mode, value) of the stage's own entropy cut; None: every row off
     cut_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, value) of the draft stage's configured cut
     miro_rows: Optional[list] = None         # every row's (tau, eta) of the stage's own Mirostat; None: every row off
+    rel_rows: Optional[list] = None          # every row's (mode, a, b) of the stage's own relative cut; None: every row off
+    rel_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, a, b) of the draft stage's configured top-n-sigma / top-a
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
 
 
@@ -666,6 +717,25 @@ class _DryState:
         if self.step_tok is None:
             return self.ops.dry_rows(logits, self.packed, tokens, seq_len, self.cap)
         return self.ops.dry_rows(logits, self.packed, tokens, seq_len, self.cap, self.step_tok, n_prev)
+
+
+class _RelCutState:
+    """What a generate call with a relative cut keeps for one side (its own rows, or a verifying stage's draft rows): the rows'
+    {1 / temperature, mode, a, b} records on the device, uploaded once.  `apply` is the loops' one call per logits tensor,
+    directly behind DRY and ahead of the entropy cut (module docstring, RELATIVE CUTS); `xtc`: a row has XTC on, and the
+    sampler hands the step's coins."""
+
+    def __init__(self, ops, rows, inv_t: List[float], device):
+        self.ops = ops
+        self.xtc = any(m == RELCUT_XTC for m, _, _ in rows)
+        self.packed = ops.pack_relative_cut(inv_t, [m for m, _, _ in rows], [a for _, a, _ in rows], [b for _, _, b in rows], device)
+
+    def apply(self, logits: torch.Tensor, coins: Optional[torch.Tensor] = None, keep: bool = False) -> Optional[torch.Tensor]:
+        """logits [B, V] or [B, K+1, V], cut in place; coins [B, 1] or [B, K+1].  keep: the tests' record -- a clone of the
+        tensor as it entered."""
+        entered = logits.clone() if keep else None
+        self.ops.relative_cut_rows(logits, self.packed, coins if self.xtc else None)
+        return entered
 
 
 class _CutState:
@@ -962,6 +1032,9 @@ class _Greedy:
     def start(self, step: int) -> None:
         pass
 
+    def coins(self, step: int, B: int, device):
+        return None
+
     def draw(self, logits, step: int):
         self.read = logits, None
         out = self.out = self.ops.verify_greedy(logits, None, 1.0)
@@ -990,11 +1063,14 @@ class _Sampled:
     def __init__(self, stage: "Stage", plan: _Plan, B: int, device):
         self.ops, self.gen, self.inv_t, self.stage = stage.ops, stage.gen, plan.inv_t, stage.index
         self.K = 0 if stage.draft is None else stage.config.draft_len
+        # XTC on a row of the call: one coin per logits position of the step (RELATIVE CUTS), K + 1 at a verifying stage
+        self.k_coin = self.K + 1 if plan.rel_rows and any(m == RELCUT_XTC for m, _, _ in plan.rel_rows) else 0
+        self.coin, self.B = None, B
         self.seeds = None
         if plan.seeds is not None:               # uploaded once (two's-complement wrap above 2^63 - 1), with the one buffer every
             wrapped = [s - 2 ** 64 if s >= 2 ** 63 else s for s in plan.seeds]           # step's uniforms are written to
             self.seeds = torch.tensor(wrapped, dtype=torch.int64, device=device)
-            self.buf = torch.empty(((2 * max(self.K, 1) + 1) * B,), dtype=torch.float32, device=device)
+            self.buf = torch.empty(((2 * max(self.K, 1) + 1 + self.k_coin) * B,), dtype=torch.float32, device=device)
         self.own = plan.scalars
         # the proposals: stage 0's are its own draws; a verifying stage's come from the DRAFT stage's configured truncation
         dcfg = None if stage.draft is None else stage.draft.config
@@ -1007,12 +1083,29 @@ class _Sampled:
         return self.ops.step_uniforms(self.seeds, step, self.stage, k_draft, k_accept, commit=commit, out=self.buf)
 
     def start(self, step: int) -> None:
-        if self.seeds is not None:               # ONE launch for every uniform of the step
+        if self.seeds is not None and self.k_coin:          # ... and the K + 1 coins from the slots' unused word
+            self.rd, self.u, self.r, self.coin = self.ops.step_uniforms(self.seeds, step, self.stage, self.K, self.K, commit=True,
+                                                                        out=self.buf, k_coin=self.k_coin)
+        elif self.seeds is not None:             # ONE launch for every uniform of the step
             self.rd, self.u, self.r = self._uniforms(step, self.K, self.K, True)
+        elif self.k_coin:                        # unseeded: the step's coins first, one torch.rand on the stage's generator
+            self.coin = torch.rand((self.B, self.k_coin), generator=self.gen, device=self.gen.device)
         self.lpd, self.thrs, self.dls = [], [], []
 
+    def coins(self, step: int, B: int, device):
+        """Stage 0, at the top of a step and only with XTC on: the step's coin per row, [B, 1].  Seeded, this is the step's
+        one launch (the draw's uniform comes with it); unseeded, one torch.rand ahead of the draw's."""
+        if not self.k_coin:
+            return None
+        if self.seeds is not None:
+            self.rd, _, _, self.coin = self.ops.step_uniforms(self.seeds, step, self.stage, 1, 0, commit=False, out=self.buf,
+                                                              k_coin=1)
+        else:
+            self.coin = torch.rand((B, 1), generator=self.gen, device=device)
+        return self.coin
+
     def draw(self, logits, step: int):
-        if self.seeds is not None:               # stage 0's one uniform, behind the edit as it always was
+        if self.seeds is not None and not self.k_coin:      # stage 0's one uniform, behind the edit as it always was
             self.rd = self._uniforms(step, 1, 0, False)[0]
         r = torch.rand((logits.shape[0],), generator=self.gen, device=logits.device) if self.rd is None else self.rd[0]
         tok, lp, thr = self._draft_op(logits, r)         # (tok i32, log q(tok), threshold)
@@ -1147,6 +1240,9 @@ class _CallState:
         self.cut = _CutState(ops, plan.cut_rows, inv_t, dev) if plan.cut_rows else None
         self.cut_draft = _CutState(ops, plan.cut_draft_rows, inv_t, dev) if plan.cut_draft_rows else None
         self.miro = _MiroState(ops, plan.miro_rows, inv_t, B, P + plan.max_tokens, dev) if plan.miro_rows else None
+        # the relative cuts, by the same two sides; XTC's coins come from the sampler
+        self.rel = _RelCutState(ops, plan.rel_rows, inv_t, dev) if plan.rel_rows else None
+        self.rel_draft = _RelCutState(ops, plan.rel_draft_rows, inv_t, dev) if plan.rel_draft_rows else None
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -1180,6 +1276,9 @@ class Stage:
         check_entropy_cuts(config.target_typical_p, config.target_epsilon_cutoff, config.target_eta_cutoff, 1)
         check_mirostat(config.mirostat_tau, config.mirostat_eta, 1)
         check_mirostat(config.target_mirostat_tau, config.target_mirostat_eta, 1)
+        check_relative_cuts(config.top_n_sigma, config.top_a, config.xtc_threshold, config.xtc_probability, 1)
+        check_relative_cuts(config.target_top_n_sigma, config.target_top_a, config.target_xtc_threshold,
+                            config.target_xtc_probability, 1)
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -1233,7 +1332,9 @@ class Stage:
                  eta_cutoff=None,
                  dry_multiplier=None, dry_base=None, dry_allowed_length=None, dry_range=None,
                  dry_sequence_breakers=None,
-                 mirostat_tau=None, mirostat_eta=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 mirostat_tau=None, mirostat_eta=None,
+                 top_n_sigma=None, top_a=None, xtc_threshold=None,
+                 xtc_probability=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1363,7 +1464,19 @@ class Stage:
         committed token under the cut distribution) per token, through the rows of a verifying step too.  It runs LAST, in
         place of top-k, top-p, min-p and the entropy cuts: any of them on the same row raises ValueError, as do a bool, a NaN, a
         value outside its range, the wrong length and eta without tau.  stats["mirostat_mu"][i]: float32 [n_i], the mu in
-        force when token i was drawn (NaN on a row that is off).  Greedy decoding ignores both (module docstring, MIROSTAT)."""
+        force when token i was drawn (NaN on a row that is off).  Greedy decoding ignores both (module docstring, MIROSTAT).
+        `top_n_sigma`, `top_a`, `xtc_threshold`, `xtc_probability` (llama.cpp's top_n_sigma and XTC, koboldcpp's top_a): None =
+        the configuration's (StageConfig fields of those names at stage 0, the target_* fields at a verifying stage: the rule
+        of `min_p`); one number for every prompt or one per prompt.  top_n_sigma = n >= 0 (0: off) keeps the tokens with
+        x_v >= x_max - n sigma(x) of the raw processed logits, whatever the temperature; top_a in [0, 1] (0: off) cuts
+        p_v < a p_max^2; XTC, with probability xtc_probability in [0, 1] (0: off) per position, cuts every token with
+        p_v >= xtc_threshold except the least likely of them (ties kept; threshold in [0, 1], 0.1 unless set, off above 0.5)
+        -- it removes the most likely token on purpose.  The cut runs behind DRY and AHEAD of the temperature and top-k, top-p
+        and min-p, which act on the survivors (llama.cpp runs XTC behind them).  A row takes at most one of the three, and
+        none together with typical_p, epsilon_cutoff, eta_cutoff or Mirostat: ValueError, as for a bool, a NaN, a value
+        outside its range, the wrong length and xtc_probability without a usable threshold.  Log-probs, top-N tables and
+        token statistics describe the distribution behind the cut.  A seeded call takes XTC's coins from the seeded
+        generator's unused word: no other draw moves.  Greedy decoding ignores all four (module docstring, RELATIVE CUTS)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1372,7 +1485,8 @@ class Stage:
                           repetition_penalty, presence_penalty, frequency_penalty, bad_words, bad_words_per_prompt, guided_fsm,
                           guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats,
                           typical_p, epsilon_cutoff, eta_cutoff, dry_multiplier, dry_base, dry_allowed_length, dry_range,
-                          dry_sequence_breakers, mirostat_tau, mirostat_eta)
+                          dry_sequence_breakers, mirostat_tau, mirostat_eta, top_n_sigma, top_a, xtc_threshold,
+                          xtc_probability)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1411,7 +1525,7 @@ class Stage:
               guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None,
               token_stats=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, dry_multiplier=None, dry_base=None,
               dry_allowed_length=None, dry_range=None, dry_sequence_breakers=None, mirostat_tau=None,
-              mirostat_eta=None) -> _Plan:
+              mirostat_eta=None, top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1482,7 +1596,16 @@ class Stage:
                         given(dry_sequence_breakers, cfg.dry_sequence_breakers), n, V, self.tokenizer)
         own_miro = (cfg.mirostat_tau, cfg.mirostat_eta) if self.draft is None else (cfg.target_mirostat_tau, cfg.target_mirostat_eta)
         miro_rows = check_mirostat(given(mirostat_tau, own_miro[0]), given(mirostat_eta, own_miro[1]), n, mirostat_eta is not None)
-        check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows)
+        own_rel = (cfg.top_n_sigma, cfg.top_a, cfg.xtc_threshold, cfg.xtc_probability) if self.draft is None else \
+            (cfg.target_top_n_sigma, cfg.target_top_a, cfg.target_xtc_threshold, cfg.target_xtc_probability)
+        rel_rows = check_relative_cuts(*(given(v, d) for v, d in zip((top_n_sigma, top_a, xtc_threshold, xtc_probability), own_rel)),
+                                       n, xtc_probability is not None)
+        check_relative_cut_alone(rel_rows, cut_rows)
+        # the draft rows take the DRAFT stage's configured top-n-sigma / top-a; its XTC is never applied to proposals (NOT BUILT)
+        rel_draft_rows = [] if dcfg is None else check_relative_cuts(dcfg.top_n_sigma, dcfg.top_a, None, 0.0, n)
+        if cut_draft_rows:
+            check_relative_cut_alone(rel_draft_rows, cut_draft_rows)
+        check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows, rel_rows)
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -1506,6 +1629,8 @@ class Stage:
                      cut_rows=cut_rows if not greedy and any(m for m, _ in cut_rows) else None,        # greedy ignores the cuts
                      cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
                      dry=dry if any(m > 0.0 for m in dry[0]) else None,           # every row off: no state, no call
+                     rel_rows=rel_rows if not greedy and any(m for m, _, _ in rel_rows) else None,     # greedy ignores the cuts
+                     rel_draft_rows=rel_draft_rows if not greedy and any(m for m, _, _ in rel_draft_rows) else None,
                      miro_rows=miro_rows if not greedy and any(t > 0.0 for t, _ in miro_rows) else None)    # greedy ignores Mirostat
 
     def _buffers(self, ids: torch.Tensor, cap: int):
@@ -1526,7 +1651,7 @@ class Stage:
         dev = ids.device
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
-        fsm, ngram, stat, cut, dry, miro = st.fsm, st.ngram, st.stats, st.cut, st.dry, st.miro
+        fsm, ngram, stat, cut, dry, miro, rel = st.fsm, st.ngram, st.stats, st.cut, st.dry, st.miro, st.rel
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1536,6 +1661,7 @@ class Stage:
             self.prompt_inputs = st.prompt.score(logits[:, :P - 1], self.keep_inputs)
         logits = logits[:, -1]
         for step in range(max_tokens):
+            coins = sampler.coins(step, B, dev) if rel is not None else None       # XTC's coin per row: at the top of the step
             if sampler.dense:
                 logits = logits.contiguous()
             if mask is not None:
@@ -1552,12 +1678,15 @@ class Stage:
                 pen.apply(logits)                                        # the penalties last: mask -> edit -> penalties
             if dry is not None:
                 dry.apply(logits, tokens, seq_len)                       # ... and DRY behind them, on the n-gram rule's history
+            rel_in = rel.apply(logits, coins, self.keep_inputs) if rel is not None else None   # the relative cut: directly behind DRY
             cut_in = cut.apply(logits, self.keep_inputs) if cut is not None else None   # the entropy cut: behind every processor
             miro_in = miro.apply(logits, None, self.keep_inputs) if miro is not None else None   # Mirostat: the LAST pass
             n_acc, tok, lp = sampler.draw(logits, step)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
             if kept is not None and cut is not None:
                 kept["cut_in"] = cut_in
+            if kept is not None and rel is not None:
+                kept.update(rel_in=rel_in, rel_coins=None if coins is None else coins.clone())
             if kept is not None and miro is not None:
                 kept.update(miro_in=miro_in, mu_path=miro.path.clone())
             if stat is not None:
@@ -1606,6 +1735,7 @@ class Stage:
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         fsm, ngram, stat, cut, cut_draft, dry, miro = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft, st.dry, st.miro
+        rel, rel_draft = st.rel, st.rel_draft
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -1644,6 +1774,8 @@ class Stage:
                     pen.apply(dl, k)                                    # ... and sees the proposals 0 .. k - 1 of this step
                 if dry is not None:
                     dry.apply(dl, tokens, seq_len, k)                   # DRY: the n-gram rule's history, behind the penalties
+                if rel_draft is not None:
+                    rel_draft.apply(dl)                                 # the DRAFT stage's configured top-n-sigma / top-a
                 if cut_draft is not None:
                     cut_in_draft.append(cut_draft.apply(dl, self.keep_inputs))   # the DRAFT stage's configured cut, last
                 toks.append(sampler.propose(dl, k))
@@ -1669,12 +1801,15 @@ class Stage:
                 pen.apply(t_out)                                        # row j sees the proposals 0 .. j - 1, as the draft's did
             if dry is not None:
                 dry.apply(t_out, tokens, seq_len)                       # the same records and history per row as the draft's rows had
+            rel_in = rel.apply(t_out, sampler.coin, self.keep_inputs) if rel is not None else None   # the call's own relative cut; row j under coin j
             cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None    # the call's own cut on the K + 1 rows
             miro_in = miro.apply(t_out, tok32, self.keep_inputs) if miro is not None else None   # Mirostat, chained through the rows
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
             if kept is not None and cut is not None:
                 kept["cut_in"] = cut_in
+            if kept is not None and rel is not None:
+                kept.update(rel_in=rel_in, rel_coins=None if sampler.coin is None else sampler.coin.clone())
             if kept is not None and miro is not None:
                 kept.update(miro_in=miro_in, mu_path=miro.path.clone())
             if kept is not None and cut_draft is not None:              # the draft rows as they entered and as they left the cut

@@ -542,7 +542,7 @@ int asd_commit_top_logprobs(const int32_t* top_id /*[B,K1,N]*/, const float* top
  *   word 0 of counter (step, k, stage, 0): the proposal uniform of slot k   -> r_draft[k*B + b]   (k < K_draft)
  *   word 1:                                the accept uniform of slot k     -> u[b*K_accept + k]  (k < K_accept)
  *   word 2, from k == 0 only:              the commit uniform               -> r_commit[b]
- *   word 3: unused
+ *   word 3: the coin of slot k, written by asd_step_uniforms_ex only (below)
  *   float = (float)(x >> 8) * 2^-24: exact, in [0, 1) (torch.rand's range; 0 is possible, 1 is not)
  * A row's uniforms depend on (seeds[b], step, stage) alone: not on b, B, the other rows, K_draft / K_accept or earlier calls.
  * A NULL output is skipped.  One thread per (b, k), k < max(K_draft, K_accept, 1); no workspace, nothing waits.
@@ -553,6 +553,16 @@ int asd_commit_top_logprobs(const int32_t* top_id /*[B,K1,N]*/, const float* top
 int asd_step_uniforms(const int64_t* seeds /*[B], read as uint64*/, uint32_t step, uint32_t stage, int B, int K_draft,
                       int K_accept, float* r_draft /*[K_draft,B] out, may be NULL*/,
                       float* u /*[B,K_accept] out, may be NULL*/, float* r_commit /*[B] out, may be NULL*/, void* stream);
+/* asd_step_uniforms_ex: asd_step_uniforms plus the COIN of every slot -- word 3 of counter (step, k, stage, 0), by the same
+ * float conversion, -> coin[b*k_coin + k] for k < k_coin (XTC's coin of logits position k, asd_relative_cut_rows; a verifying
+ * step asks for k_coin = K + 1, stage 0 for 1).  Word 3 is read by nothing else, so the coins move no other uniform, and a
+ * position's coin is the same whichever route the step takes.  One thread per (b, k), k < max(K_draft, K_accept, k_coin, 1);
+ * with k_coin == 0 (and coin NULL) it writes the bytes asd_step_uniforms writes.
+ * Status: asd_step_uniforms' (an output among the four must be given), and k_coin outside [0, ASD_MAX_DRAFT_LEN + 1] or
+ * coin != NULL without k_coin > 0 (or the reverse): invalid argument; coin not 4-byte aligned: alignment. */
+int asd_step_uniforms_ex(const int64_t* seeds /*[B], read as uint64*/, uint32_t step, uint32_t stage, int B, int K_draft,
+                         int K_accept, float* r_draft, float* u, float* r_commit, float* coin /*[B,k_coin] out, or NULL*/,
+                         int k_coin, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Logit edits: a sparse in-place edit of a few logits per row AHEAD of the samplers -- OpenAI's `logit_bias`, vLLM's
@@ -874,6 +884,58 @@ int asd_mirostat_commit(const float* mu_path /*[B, K1]*/, int B, int K1, const i
                         const int32_t* seq_len /*[B]: AFTER the step's commit*/, const int32_t* n_commit /*[B]*/,
                         const asd_mirostat_rec* table /*[B]*/, float* mu /*[B] in/out*/, float* mu_out /*[B, max_len]*/, int max_len,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * RELATIVE CUTS ahead of the samplers -- llama.cpp's `top_n_sigma` and `xtc_threshold` / `xtc_probability` ("exclude top
+ * choices", the DRY sampler's companion) and koboldcpp's `top_a`: three truncations that cut a row relative to its own
+ * statistics (its maximum, its normaliser, its mean and deviation).  One in-place pass behind asd_dry_rows and ahead of
+ * asd_entropy_cut_rows, the temperature and top-k / top-p / min-p.
+ * logits: asd_entropy_cut_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only.
+ * table: B records {float inv_t; int32 mode; float a; float b} (asd_relative_cut_rec, 16 bytes) on the device; all K1 rows of
+ * sequence b use record b.  coins: f32, the coin of row (b, j) at b*ld_coin + j, read by mode 3 only; NULL when no row is in
+ * mode 3.
+ * The input is the row as every earlier pass left it, the values the stored ones, fin the set of its finite elements.  A -inf
+ * element carries no mass, stays -inf and is counted in no statistic.
+ *   ASD_RELCUT_OFF (0): the row is not read.
+ *   ASD_RELCUT_TOP_N_SIGMA (1), a = n in (0, inf): mu = the mean over fin, sigma = sqrt(sum_fin (x_v - mu)^2 / |fin|) (the
+ *     population deviation, llama.cpp's); element v is cut iff x_v < x_max - n * sigma.  inv_t is not used; every tie at the
+ *     maximum survives by construction.
+ *   ASD_RELCUT_TOP_A (2), a in (0, 1]: with p = softmax(x * inv_t), v is cut iff p_v < a * p_max^2 and x_v < x_max.
+ *   ASD_RELCUT_XTC (3), a = t in (0, 1], b = q in (0, 1], c the row's coin: c >= q (c == q included): nothing happens.
+ *     Otherwise A = {v : p_v >= t}; |A| < 2: nothing happens; else x_lo is the smallest stored value in A and v is cut iff
+ *     v is in A and x_v > x_lo.  Every element that ties x_lo stays (llama.cpp keeps one tie, in sort order).  XTC can cut the
+ *     arg-max -- that is its purpose -- and never empties a row.
+ * A cut element becomes -inf of the dtype; nothing else is written; a kept element keeps its bits; a 16-byte vector is stored
+ * only where a bit of it changes.  A row with a NaN or +inf element, or without a finite element, is left bit for bit as it is.
+ * THE DATA CONTRACT: a record whose mode lies outside 0..3, whose a or b lies outside the range above, whose inv_t is not a
+ * positive finite number, or a mode-3 record with coins == NULL skips its rows.
+ * Arithmetic: one workgroup of 1024 threads per (b, j); a lane meets its elements in ascending order, lanes merge by a fixed
+ * DPP sequence, waves in wave order: the result depends on the row's bytes, its record and its coin only.  Rows of at most
+ * 19 * 1024 16-byte vectors are read from memory once and kept in registers for the later sweeps; longer rows are re-read.
+ * top-n-sigma: two passes, the mean first (f32 sums; the count an integer; mu = float(sum / count)), then the squares;
+ * sigma and x_max - n * sigma in f64, rounded once to f32, compared with the stored values.  top-a / XTC:
+ * log2 p_v = fma(x_v, c2, -L.hi) - L.lo with c2 = float(log2(e) * inv_t) and L = m2 + log2 s in two floats; top-a compares it
+ * with float(log2 a + 2 (x_max c2 - L)), XTC's membership with float(log2 t); XTC's count is an integer and its minimum and
+ * the x_v > x_lo test are exact compares.  No workspace, no state.
+ * Status, in this order: negative B / K1 / V: invalid argument; B, K1 or V == 0: ASD_OK, nothing launched; unknown dtype,
+ * B*K1 > INT32_MAX, V * element size > INT32_MAX: unsupported; NULL logits / table, ld_row < V, ld_seq < K1*ld_row, coins with
+ * ld_coin < K1: invalid argument; logits not aligned to the element size, or table / coins not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_RELCUT_OFF 0
+#define ASD_RELCUT_TOP_N_SIGMA 1
+#define ASD_RELCUT_TOP_A 2
+#define ASD_RELCUT_XTC 3
+#define ASD_RELATIVE_CUT_REC_BYTES 16
+typedef struct asd_relative_cut_rec {
+    float inv_t;   /* 1 / temperature of the sequence (modes 2 and 3) */
+    int32_t mode;  /* ASD_RELCUT_* */
+    float a;       /* top_n_sigma, top_a or xtc_threshold */
+    float b;       /* xtc_probability */
+} asd_relative_cut_rec;
+int asd_relative_cut_rows(void* logits /*in/out*/, int dtype, int B, int K1, int V, int64_t ld_seq, int64_t ld_row,
+                          const asd_relative_cut_rec* table /*[B]*/, const float* coins /*[B, ld_coin], or NULL*/,
+                          int64_t ld_coin, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /

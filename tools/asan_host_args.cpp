@@ -607,6 +607,46 @@ int main() {
 #undef CUT
     }
 
+    // ---- asd_relative_cut_rows: asd_entropy_cut_rows' order, plus the coins' leading dimension and alignment
+    {
+#define REL(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, coin_, ldc_) asd_relative_cut_rows(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, coin_, ldc_, nullptr)
+        const int K1 = 5;
+        const asd_relative_cut_rec* tab = reinterpret_cast<const asd_relative_cut_rec*>(rows);
+        EXPECT(REL(p, BF16, -1, K1, V, K1 * V, V, tab, f32, K1), ASD_ERR_INVALID_ARG);
+        EXPECT(REL(p, BF16, B, -1, V, K1 * V, V, tab, f32, K1), ASD_ERR_INVALID_ARG);
+        EXPECT(REL(p, BF16, B, K1, -1, K1 * V, V, tab, f32, K1), ASD_ERR_INVALID_ARG);
+        EXPECT(REL(nullptr, 99, 0, K1, V, 0, 0, nullptr, nullptr, 0), ASD_OK);
+        EXPECT(REL(nullptr, 99, B, K1, V, K1 * V, V, tab, f32, K1), ASD_ERR_UNSUPPORTED);              // dtype, before the NULL checks
+        EXPECT(REL(p, 0 /*f32*/, B, 1, INT32_MAX, INT32_MAX, INT32_MAX, tab, f32, 1), ASD_ERR_UNSUPPORTED);
+        EXPECT(REL(nullptr, BF16, B, K1, V, K1 * V, V, tab, f32, K1), ASD_ERR_INVALID_ARG);
+        EXPECT(REL(p, BF16, B, K1, V, K1 * V, V, nullptr, f32, K1), ASD_ERR_INVALID_ARG);
+        EXPECT(REL(p, BF16, B, K1, V, K1 * V, V - 1, tab, f32, K1), ASD_ERR_INVALID_ARG);               // ld_row < V
+        EXPECT(REL(p, BF16, B, K1, V, K1 * V - 1, V, tab, f32, K1), ASD_ERR_INVALID_ARG);               // ld_seq < K1 ld_row
+        EXPECT(REL(p, BF16, B, K1, V, K1 * V, V, tab, f32, K1 - 1), ASD_ERR_INVALID_ARG);               // ld_coin < K1
+        EXPECT(REL(rows + 1, BF16, B, K1, V, K1 * V, V, tab, f32, K1), ASD_ERR_ALIGNMENT);              // below the element size
+        EXPECT(REL(p, BF16, B, K1, V, K1 * V, V, reinterpret_cast<const asd_relative_cut_rec*>(rows + 2), f32, K1), ASD_ERR_ALIGNMENT);
+        EXPECT(REL(p, BF16, B, K1, V, K1 * V, V, tab, reinterpret_cast<const float*>(rows + 2), K1), ASD_ERR_ALIGNMENT);
+#undef REL
+    }
+
+    // ---- asd_step_uniforms_ex: asd_step_uniforms' rejections, plus the coin and its count
+    {
+        const int64_t* seeds = reinterpret_cast<const int64_t*>(rows);
+#define UNX(seeds_, B_, Kd_, Ka_, rd_, u_, rc_, coin_, kc_) asd_step_uniforms_ex(seeds_, 0u, 0u, B_, Kd_, Ka_, rd_, u_, rc_, coin_, kc_, nullptr)
+        EXPECT(UNX(seeds, 0, 2, 2, f32, f32, f32, f32, 3), ASD_ERR_INVALID_ARG);                            // B < 1
+        EXPECT(UNX(seeds, B, ASD_MAX_DRAFT_LEN + 1, 2, f32, f32, f32, f32, 3), ASD_ERR_INVALID_ARG);
+        EXPECT(UNX(seeds, B, 2, 2, f32, f32, f32, f32, -1), ASD_ERR_INVALID_ARG);
+        EXPECT(UNX(seeds, B, 2, 2, f32, f32, f32, f32, ASD_MAX_DRAFT_LEN + 2), ASD_ERR_INVALID_ARG);
+        EXPECT(UNX(nullptr, B, 2, 2, f32, f32, f32, f32, 3), ASD_ERR_INVALID_ARG);                          // seeds
+        EXPECT(UNX(seeds, B, 2, 2, nullptr, nullptr, nullptr, nullptr, 0), ASD_ERR_INVALID_ARG);            // no output at all
+        EXPECT(UNX(seeds, B, 2, 2, f32, f32, f32, f32, 0), ASD_ERR_INVALID_ARG);                            // a coin without a slot
+        EXPECT(UNX(seeds, B, 2, 2, f32, f32, f32, nullptr, 3), ASD_ERR_INVALID_ARG);                        // slots without a coin
+        EXPECT(UNX(seeds, B, 0, 2, f32, f32, f32, f32, 3), ASD_ERR_INVALID_ARG);                            // r_draft without a slot
+        EXPECT(UNX(reinterpret_cast<const int64_t*>(rows + 4), B, 2, 2, f32, f32, f32, f32, 3), ASD_ERR_ALIGNMENT);
+        EXPECT(UNX(seeds, B, 2, 2, f32, f32, f32, reinterpret_cast<float*>(rows + 2), 3), ASD_ERR_ALIGNMENT);
+#undef UNX
+    }
+
     // ---- asd_prompt_logprobs: the header's order (NULL outputs and the temperature, sizes, the empty batch, dtype, N / splits,
     // pointers and strides, a 2 GiB row, alignment, the workspace) and the size query, which is sized for the splits in use
     {
