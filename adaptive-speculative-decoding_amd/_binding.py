@@ -30,6 +30,7 @@ DRY_MAX_MATCH, MAX_DRY_BREAKERS = 64, 32   # ASD_DRY_MAX_MATCH (CAP), ASD_MAX_DR
 DRY_REC_BYTES = 404                   # ASD_DRY_REC_BYTES: one asd_dry_rec {on, allowed_length, range, n_breakers, breakers[32], pen[65]}
 MIROSTAT_REC_BYTES, MIROSTAT_ROW_BYTES = 12, 16   # ASD_MIROSTAT_REC_BYTES ({inv_t, tau, eta} f32), ASD_MIROSTAT_ROW_BYTES (workspace per row)
 RELATIVE_CUT_REC_BYTES = 16           # ASD_RELATIVE_CUT_REC_BYTES: one {inv_t f32, mode i32, a f32, b f32} record of asd_relative_cut_rows
+LOGIT_SHAPE_REC_BYTES = 16            # ASD_LOGIT_SHAPE_REC_BYTES: one {mode i32, T f32, a f32, b f32} record of asd_logit_shape_rows
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
@@ -128,6 +129,7 @@ SIGNATURES = {
     "asd_mirostat_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "asd_mirostat_commit": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "asd_relative_cut_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "asd_logit_shape_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp]),
     "asd_step_uniforms_ex": (_i, [_vp, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "asd_fsm_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_advance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp]),

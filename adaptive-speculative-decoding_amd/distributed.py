@@ -573,6 +573,21 @@ class HipOps:
         when some row of the call has a relative cut."""
         return self.K.relative_cut_rows(logits, packed, coins)
 
+    @traced("pack_logit_shape")
+    def pack_logit_shape(self, temps, modes, a, b, device):
+        """Every row's temperature, mode (0 off, 1 dynatemp, 2 quadratic), a (dynatemp_range or smoothing_factor) and b
+        (dynatemp_exponent or smoothing_curve) -> the device table of logit_shape_rows (kernels.pack_logit_shape: one upload
+        per generate call and side)."""
+        return self.K.pack_logit_shape(temps, modes, a, b, device)
+
+    @traced("logit_shape_rows")
+    def logit_shape_rows(self, logits, packed):
+        """Dynamic temperature and quadratic smoothing ahead of the samplers (asd_logit_shape_rows): logits [B, V] or
+        [B, K1, V] (any strides with a unit last stride) -> the same tensor, every finite element of a row that is on
+        rewritten in place.  One launch, no workspace, no state; a stage loop makes the call once per logits tensor, behind
+        entropy_cut_rows and directly ahead of the draw, and only when some row of the call is on."""
+        return self.K.logit_shape_rows(logits, packed)
+
     @traced("pack_mirostat")
     def pack_mirostat(self, inv_t, taus, etas, device):
         """Every row's 1 / temperature, tau (0: off) and eta -> the device records of mirostat_rows and the running target

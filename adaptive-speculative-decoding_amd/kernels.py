@@ -1958,6 +1958,84 @@ def relative_cut_rows(logits: torch.Tensor, cut: RelativeCut, coins: Optional[to
     return logits
 
 
+# ------------------------------------------------------------------------------- shaping (dynatemp_* / smoothing_*)
+SHAPE_OFF, SHAPE_DYNATEMP, SHAPE_QUADRATIC = 0, 1, 2
+_SHAPE_REC = np.dtype([("mode", np.int32), ("T", np.float32), ("a", np.float32), ("b", np.float32)])
+
+
+@dataclass
+class LogitShape:
+    """The table of asd_logit_shape_rows on the device (pack_logit_shape): B records {mode i32, T f32, a f32, b f32} of 16
+    bytes, as a uint8 [B, 16] tensor; `modes`: the host's copy of the rows' modes."""
+    table: torch.Tensor
+    modes: Tuple[int, ...]
+    B: int
+
+
+def check_logit_shape_rows(temps, modes, a, b) -> np.ndarray:
+    """The host side of pack_logit_shape: every row's temperature, mode (0 off, 1 dynatemp, 2 quadratic), a (dynatemp_range in
+    (0, T) or smoothing_factor in (0, inf)) and b (dynatemp_exponent in (0, inf) or smoothing_curve in [1, 3]), each checked
+    as the f32 number the record holds -> the records, a numpy structured array.  A row that is off holds zeros."""
+    temps, modes, a, b = list(temps), list(modes), list(a), list(b)
+    if not len(temps) == len(modes) == len(a) == len(b):
+        raise ValueError(f"{len(temps)} temperatures, {len(modes)} modes, {len(a)} and {len(b)} values must describe the same rows")
+    rec = np.zeros(len(modes), dtype=_SHAPE_REC)
+    inf = float("inf")
+    for i, (t, m, va, vb) in enumerate(zip(temps, modes, a, b)):
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (0, 1, 2):
+            raise ValueError(f"row {i}: the mode must be 0 (off), 1 (dynatemp) or 2 (quadratic), got {m!r}")
+        m = int(m)
+        if m == SHAPE_OFF:
+            continue
+        if any(isinstance(v, bool) for v in (t, va, vb)):
+            raise ValueError(f"row {i}: the temperature and the two values must be numbers, got {(t, va, vb)!r}")
+        t32, a32, b32 = (float(np.float32(v)) for v in (t, va, vb))
+        if m == SHAPE_DYNATEMP:
+            if not 0.0 < t32 < inf:
+                raise ValueError(f"row {i}: the temperature of a dynatemp row must be a positive finite number, got {t!r}")
+            if not 0.0 < a32 < t32:
+                raise ValueError(f"row {i}: dynatemp_range must lie in (0, temperature = {t32}): a range that reaches "
+                                 f"temperature 0 is not built, got {va!r}")
+            if not 0.0 < b32 < inf:
+                raise ValueError(f"row {i}: dynatemp_exponent must be a positive finite number, got {vb!r}")
+        else:
+            if not 0.0 < a32 < inf:
+                raise ValueError(f"row {i}: smoothing_factor of a row that is on must be a positive finite number, got {va!r}")
+            if not 1.0 <= b32 <= 3.0:
+                raise ValueError(f"row {i}: smoothing_curve must lie in [1, 3], got {vb!r}")
+            t32 = 0.0                                                            # (not used)
+        rec[i] = (m, t32, a32, b32)
+    return rec
+
+
+def pack_logit_shape(temps, modes, a, b, device) -> LogitShape:
+    """The table of logit_shape_rows from host lists, checked BEFORE anything is uploaded."""
+    rec = check_logit_shape_rows(temps, modes, a, b)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _SHAPE_REC.itemsize).copy()).to(device)
+    return LogitShape(table, tuple(int(m) for m in rec["mode"]), len(rec))
+
+
+def logit_shape_rows(logits: torch.Tensor, packed: LogitShape) -> torch.Tensor:
+    """Reshape in place (asd_logit_shape_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row
+    stride with unit stride along V.  Row (b, j) under record b: dynatemp multiplies every finite element by
+    g = T / T_dyn with T_dyn = (T - r) + 2 r h^e and h the row's normalised entropy at temperature 1; quadratic maps it to
+    x_max - k d^2 + s d^3 with d = x - x_max, k = f (3 - c) / 2, s = f (c - 1) / 2.  Results are rounded to the dtype to
+    nearest even and clamped to its finite range; -inf stays -inf; a row with a NaN or +inf element is left as it is."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if packed.B != Bv:
+        raise ValueError(f"the records were packed for {packed.B} rows; logits have {Bv}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_logit_shape_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], Bv, K1, V, ld_seq, ld_row,
+                                     _dev(packed.table, "table", torch.uint8), _stream())
+    B.check("asd_logit_shape_rows", rc)
+    return logits
+
+
 # ------------------------------------------------------------------------------- DRY (dry_multiplier / dry_base / dry_allowed_length / dry_range)
 _DRY_REC = np.dtype([("on", np.int32), ("allowed_length", np.int32), ("range", np.int32), ("n_breakers", np.int32),
                      ("breakers", np.int32, (B.MAX_DRY_BREAKERS,)), ("pen", np.float32, (B.DRY_MAX_MATCH + 1,))])

@@ -48,6 +48,7 @@ batch or one per request, kept by the request through every regrouping, handed o
 configuration only: a value that is set is handed to every stage's generate call as the keyword of that name, None is not passed.
 `PipelineConfig.mirostat_tau` / `mirostat_eta` (llama.cpp's mirostat_v2; serving/stages.py, MIROSTAT) travel the same way.
 `PipelineConfig.top_n_sigma` / `top_a` / `xtc_threshold` / `xtc_probability` (serving/stages.py, RELATIVE CUTS) travel the same way.
+`PipelineConfig.dynatemp_range` / `dynatemp_exponent` / `smoothing_factor` / `smoothing_curve` (serving/stages.py, SHAPING) too.
 `PipelineConfig.dry_multiplier` / `dry_base` / `dry_allowed_length` / `dry_range` / `dry_sequence_breakers` (the DRY sampler;
 serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
 
@@ -234,6 +235,12 @@ class PipelineConfig:
     top_a: Optional[float] = None
     xtc_threshold: Optional[float] = None
     xtc_probability: Optional[float] = None
+    # dynamic temperature and quadratic sampling, handed to stage.generate(dynatemp_range=, dynatemp_exponent=,
+    # smoothing_factor=, smoothing_curve=); None: the keyword is not passed (serving/stages.py, SHAPING)
+    dynatemp_range: Optional[float] = None
+    dynatemp_exponent: Optional[float] = None
+    smoothing_factor: Optional[float] = None
+    smoothing_curve: Optional[float] = None
     # the DRY sampler's values, handed to stage.generate(dry_multiplier=, dry_base=, dry_allowed_length=, dry_range=,
     # dry_sequence_breakers=); None: the keyword is not passed (serving/stages.py, DRY)
     dry_multiplier: Optional[float] = None
@@ -282,7 +289,8 @@ class PipelineConfig:
         if sec.get("no_repeat_ngram_size") is not None:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
         for name in ("typical_p", "epsilon_cutoff", "eta_cutoff", "mirostat_tau", "mirostat_eta",
-                     "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability"):
+                     "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",
+                     "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve"):
             if sec.get(name) is not None:
                 kw[name] = float(sec[name])
         for name, kind in (("dry_multiplier", float), ("dry_base", float), ("dry_allowed_length", int), ("dry_range", int)):
@@ -647,7 +655,8 @@ class AdaptiveSpeculativePipeline:
                 for name in ("typical_p", "epsilon_cutoff", "eta_cutoff",       # the entropy cuts and DRY: only those that are set
                              "dry_multiplier", "dry_base", "dry_allowed_length", "dry_range", "dry_sequence_breakers",
                              "mirostat_tau", "mirostat_eta",                     # ... and Mirostat
-                             "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability"):    # ... and the relative cuts
+                             "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",     # ... and the relative cuts
+                             "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve"):   # ... and the shaping
                     if getattr(cfg, name) is not None:
                         stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:

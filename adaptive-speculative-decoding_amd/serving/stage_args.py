@@ -234,6 +234,59 @@ def check_relative_cut_alone(rel_rows, cut_rows) -> None:
                              "on one row is not built")
 
 
+SHAPE_OFF, SHAPE_DYNATEMP, SHAPE_QUADRATIC = 0, 1, 2     # ASD_SHAPE_* of include/asd_hip.h (SHAPING)
+
+
+def check_logit_shapes(dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve, n: int,
+                       exponent_given: bool = False, curve_given: bool = False) -> List[Tuple[int, float, float]]:
+    """generate's `dynatemp_range`, `dynatemp_exponent`, `smoothing_factor` and `smoothing_curve` (llama.cpp's / koboldcpp's
+    dynamic temperature; text-generation-webui's / koboldcpp's / Aphrodite's quadratic sampling): each one number for all `n`
+    prompts or a sequence of n numbers -> every row's (mode, a, b), the values the f32 numbers the device record holds.
+    dynatemp_range and smoothing_factor are finite numbers >= 0 (0: off); dynatemp_exponent is a finite number > 0;
+    smoothing_curve lies in [1, 3].  exponent_given / curve_given: the call named the value itself, which needs a row that
+    uses it (the mirostat_eta rule).  A row has at most one mode.  A bool, a NaN, a value outside its range, the wrong
+    length and a row with both modes ("not built") raise ValueError."""
+    inf = float("inf")
+
+    def number(name, ok, text):
+        def one(v):
+            if isinstance(v, bool) or not isinstance(v, _NUMBER) or not ok(float(np.float32(v))):     # (NaN included)
+                raise ValueError(f"{name} must be {text}, got {v!r}")
+            return float(np.float32(v))
+        return one
+    named = (("dynatemp_range", dynatemp_range, lambda v: 0.0 <= v < inf, "a finite number >= 0"),
+             ("dynatemp_exponent", dynatemp_exponent, lambda v: 0.0 < v < inf, "a finite number > 0"),
+             ("smoothing_factor", smoothing_factor, lambda v: 0.0 <= v < inf, "a finite number >= 0"),
+             ("smoothing_curve", smoothing_curve, lambda v: 1.0 <= v <= 3.0, "a number in [1, 3]"))
+    cols = []
+    for name, value, ok, text in named:
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+        cols.append(_per_prompt(value, n, number(name, ok, text), f"{name} values"))
+    if exponent_given and not any(r > 0.0 for r in cols[0]):
+        raise ValueError("dynatemp_exponent without a dynatemp_range > 0: no row of the call has dynamic temperature on")
+    if curve_given and not any(f > 0.0 for f in cols[2]):
+        raise ValueError("smoothing_curve without a smoothing_factor > 0: no row of the call has quadratic sampling on")
+    rows = []
+    for b, (r, e, f, c) in enumerate(zip(*cols)):
+        if r > 0.0 and f > 0.0:
+            raise ValueError(f"prompt {b}: dynamic temperature and quadratic sampling on one row is not built")
+        rows.append((SHAPE_DYNATEMP, r, e) if r > 0.0 else (SHAPE_QUADRATIC, f, c) if f > 0.0 else (SHAPE_OFF, 0.0, 0.0))
+    return rows
+
+
+def check_logit_shape_alone(shape_rows, miro_rows=None, temps=None, side: str = "") -> None:
+    """What a shaped row excludes: Mirostat on the same row (its carried mu is defined on the distribution it cut) is not built;
+    a dynatemp_range must lie strictly below the row's temperature (temps: every row's, None: a greedy call, which ignores the
+    values), so that T_dyn > 0 -- a range that reaches temperature 0 is not built.  ValueError for either."""
+    for b, (mode, a, _) in enumerate(shape_rows):
+        if mode != SHAPE_OFF and miro_rows is not None and miro_rows[b][0] > 0.0:
+            raise ValueError(f"prompt {b}: dynamic temperature or quadratic sampling together with Mirostat on one row is not built")
+        if mode == SHAPE_DYNATEMP and temps is not None and not a < float(np.float32(temps[b])):
+            raise ValueError(f"prompt {b}: {side}dynatemp_range {a} must lie strictly below the row's temperature {temps[b]}: "
+                             "a range that reaches temperature 0 is not built")
+
+
 def _check_sampling_value(v, name: str):
     """One temperature / top_p / top_k / min_p value of generate (PER-REQUEST SAMPLING)."""
     if name == "top_k":

@@ -504,6 +504,47 @@ V = 152064, bf16, kernel time, against asd_entropy_cut_rows in epsilon mode on a
 spread 0.03), 5.0 us with every coin above q; K1 = 1: 25.3 / 21.8 / 25.6 / 4.8 us against 28.3 us.  NOT BUILT beside the above:
 serving/hierarchy.py's loop.
 
+SHAPING.  `generate(dynatemp_range=, dynatemp_exponent=, smoothing_factor=, smoothing_curve=)` are llama.cpp's / koboldcpp's
+dynamic temperature and the quadratic ("smooth") sampling of text-generation-webui, koboldcpp and Aphrodite: the two samplers
+that RESHAPE a row's distribution instead of cutting it, the usual companions of DRY and XTC.  Each takes one number for the
+call or one per prompt; None takes the configuration's value: StageConfig.dynatemp_range / dynatemp_exponent /
+smoothing_factor / smoothing_curve are the stage's own draws at stage 0, target_* a verifying stage's own distribution -- the
+rule of min_p / target_min_p.  dynatemp_range is a finite number >= 0, off at 0, and STRICTLY BELOW the row's temperature where
+it is on; dynatemp_exponent is a finite number > 0 (default 1); smoothing_factor is a finite number >= 0, off at 0;
+smoothing_curve lies in [1, 3] (default 1).  INPUT: the row as every earlier pass left it, the values the stored ones, fin the
+set of its finite elements and n = |fin|; a -inf element stays -inf and enters no statistic; a row with a NaN or +inf element
+or with n == 0 is left bit for bit as it is.
+  dynatemp (T, r, e)     p = softmax(x) over fin at temperature 1 (llama.cpp measures the entropy of the raw logits),
+                         H = -sum p ln p, h = clamp(H / ln n, 0, 1), T_dyn = (T - r) + 2 r h^e, g = T / T_dyn; every finite
+                         element becomes x_v g, so that the sampler's unchanged x / T equals x / T_dyn: a flat row is sampled
+                         at T + r, a peaked one at T - r.  n < 2: nothing is written.
+  quadratic (f, c)       d_v = x_v - x_max, k = f (3 - c) / 2, s = f (c - 1) / 2; x_v <- x_max - k d_v^2 + s d_v^3.  c = 1 is
+                         the plain quadratic x_max - f d^2.  On [1, 3] k, s >= 0: the map is non-decreasing in d, the ranking
+                         and the arg-max are kept (ties may appear); above 3 it is not, hence the range.
+The f32 result is rounded to the logits' dtype to nearest even and clamped to the dtype's finite range (a finite element never
+becomes +-inf: DRY's rule).  It is one more in-place pass (asd_logit_shape_rows, the first that writes a whole row back; the
+rows' {mode, T, a, b} records are uploaded once per call and side through ops.pack_logit_shape) behind every cut and ahead of
+the temperature: mask -> fsm -> bad words -> n-gram -> edit -> penalties -> DRY -> relative cut -> entropy cut -> SHAPE ->
+temperature -> top-k -> top-p -> min-p.  This is the place llama.cpp gives its temperature stage relative to the cuts, acting on
+their survivors.  THIS IS NOT llama.cpp's ORDER FOR top-k / top-p / min-p: llama.cpp runs the three AHEAD of its temperature
+stage, so its entropy is that of their survivors; here they follow the pass and the entropy is taken over every finite element.
+With top-k, top-p and min-p off the two agree.  ONE MODE PER ROW: both on one row raise ValueError (NOT BUILT); either with
+Mirostat on the same row raises too (NOT BUILT: Mirostat's carried mu is defined on the distribution it cut).  At a verifying
+stage the target's [B, K+1, V] output takes the call's own values with the row's temperature and every draft tensor the DRAFT
+stage's configured values with that temperature; the pass is a deterministic function of the row, so the draft -> verify ->
+residual chain stays lossless by the LOGIT EDITS argument.  Log-probs, top-N tables and token statistics describe the
+distribution behind the pass.  Greedy decoding ignores all four and makes no call (both maps keep the arg-max); a call whose
+every row is off makes exactly the ops calls it made before.  ValueError before any launch and before the prompts are encoded:
+a bool, a NaN, a value outside its range, the wrong length, both modes on one row, either with Mirostat, a range that reaches
+the row's temperature, an exponent or curve named without a row that uses it (the mirostat_eta rule).  COST
+(profiles/logit_shape.json: B = 32, V = 152064, bf16, kernel time, against asd_relative_cut_rows in top-a mode on a copy of the
+same tensor): K1 = 9: 80.5 / 66.8 us for dynatemp / quadratic with every vector rewritten against 51.3 us (ratios 1.57 / 1.30;
+that baseline's spread 0.09), 40.6 us (0.79) for a dynatemp pass whose g is exactly 1 (the statistics sweep alone, no store
+issued), 61.1 us (1.19) for the quadratic on flat rows (both sweeps, no store issued); K1 = 1: 37.5 / 30.1 / 19.2 / 28.9 us
+against 23.0 us (1.63 / 1.31 / 0.83 / 1.25).  A full rewrite moves up to twice the baseline's bytes; both modes stay under 2,
+and the stores cost 6 us of the quadratic's 67.  NOT BUILT beside the above: a range that reaches temperature 0;
+serving/hierarchy.py's loop; per-request draft-side values.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -525,7 +566,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -578,6 +619,15 @@ class StageConfig:
     target_top_a: float = 0.0
     target_xtc_threshold: float = 0.1
     target_xtc_probability: float = 0.0
+    # shaping (module docstring, SHAPING), by the rule of min_p / target_min_p; at most one of the two modes per side
+    dynatemp_range: float = 0.0              # llama.cpp's dynatemp_range of the stage's own draws and of its proposals; 0: off
+    dynatemp_exponent: float = 1.0           # ... its exponent, > 0
+    smoothing_factor: float = 0.0            # quadratic sampling's factor of the same rows; 0: off
+    smoothing_curve: float = 1.0             # ... its curve, in [1, 3]
+    target_dynatemp_range: float = 0.0       # the four of a verifying stage's own distribution
+    target_dynatemp_exponent: float = 1.0
+    target_smoothing_factor: float = 0.0
+    target_smoothing_curve: float = 1.0
     draft_len: int = 8
     seed: int = 0
     sync_every: int = 4
@@ -635,6 +685,8 @@ class _Plan(NamedTuple):
     miro_rows: Optional[list] = None         # every row's (tau, eta) of the stage's own Mirostat; None: every row off
     rel_rows: Optional[list] = None          # every row's (mode, a, b) of the stage's own relative cut; None: every row off
     rel_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, a, b) of the draft stage's configured top-n-sigma / top-a
+    shape_rows: Optional[list] = None        # every row's (mode, T, a, b) of the stage's own shaping; None: every row off
+    shape_draft_rows: Optional[list] = None  # a verifying stage: every row's (mode, T, a, b) of the draft stage's configured shaping
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
 
 
@@ -735,6 +787,23 @@ class _RelCutState:
         tensor as it entered."""
         entered = logits.clone() if keep else None
         self.ops.relative_cut_rows(logits, self.packed, coins if self.xtc else None)
+        return entered
+
+
+class _ShapeState:
+    """What a generate call with dynamic temperature or quadratic sampling keeps for one side (its own rows, or a verifying
+    stage's draft rows): the rows' {mode, temperature, a, b} records on the device, uploaded once.  `apply` is the loops' one
+    call per logits tensor, behind the entropy cut and directly ahead of the draw (module docstring, SHAPING)."""
+
+    def __init__(self, ops, rows, device):
+        self.ops = ops
+        self.packed = ops.pack_logit_shape([t for _, t, _, _ in rows], [m for m, _, _, _ in rows], [a for _, _, a, _ in rows],
+                                           [b for _, _, _, b in rows], device)
+
+    def apply(self, logits: torch.Tensor, keep: bool = False) -> Optional[torch.Tensor]:
+        """logits [B, V] or [B, K+1, V], rewritten in place.  keep: the tests' record -- a clone of the tensor as it entered."""
+        entered = logits.clone() if keep else None
+        self.ops.logit_shape_rows(logits, self.packed)
         return entered
 
 
@@ -1243,6 +1312,9 @@ class _CallState:
         # the relative cuts, by the same two sides; XTC's coins come from the sampler
         self.rel = _RelCutState(ops, plan.rel_rows, inv_t, dev) if plan.rel_rows else None
         self.rel_draft = _RelCutState(ops, plan.rel_draft_rows, inv_t, dev) if plan.rel_draft_rows else None
+        # shaping, by the same two sides; the records carry the rows' temperatures themselves
+        self.shape = _ShapeState(ops, plan.shape_rows, dev) if plan.shape_rows else None
+        self.shape_draft = _ShapeState(ops, plan.shape_draft_rows, dev) if plan.shape_draft_rows else None
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -1279,6 +1351,9 @@ class Stage:
         check_relative_cuts(config.top_n_sigma, config.top_a, config.xtc_threshold, config.xtc_probability, 1)
         check_relative_cuts(config.target_top_n_sigma, config.target_top_a, config.target_xtc_threshold,
                             config.target_xtc_probability, 1)
+        check_logit_shapes(config.dynatemp_range, config.dynatemp_exponent, config.smoothing_factor, config.smoothing_curve, 1)
+        check_logit_shapes(config.target_dynatemp_range, config.target_dynatemp_exponent, config.target_smoothing_factor,
+                           config.target_smoothing_curve, 1)
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -1333,8 +1408,9 @@ class Stage:
                  dry_multiplier=None, dry_base=None, dry_allowed_length=None, dry_range=None,
                  dry_sequence_breakers=None,
                  mirostat_tau=None, mirostat_eta=None,
-                 top_n_sigma=None, top_a=None, xtc_threshold=None,
-                 xtc_probability=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None,
+                 dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None,
+                 smoothing_curve=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1476,7 +1552,19 @@ class Stage:
         none together with typical_p, epsilon_cutoff, eta_cutoff or Mirostat: ValueError, as for a bool, a NaN, a value
         outside its range, the wrong length and xtc_probability without a usable threshold.  Log-probs, top-N tables and
         token statistics describe the distribution behind the cut.  A seeded call takes XTC's coins from the seeded
-        generator's unused word: no other draw moves.  Greedy decoding ignores all four (module docstring, RELATIVE CUTS)."""
+        generator's unused word: no other draw moves.  Greedy decoding ignores all four (module docstring, RELATIVE CUTS).
+        `dynatemp_range`, `dynatemp_exponent`, `smoothing_factor`, `smoothing_curve` (llama.cpp's / koboldcpp's dynamic
+        temperature; text-generation-webui's / koboldcpp's / Aphrodite's quadratic sampling): None = the configuration's
+        (StageConfig fields of those names at stage 0, the target_* fields at a verifying stage: the rule of `min_p`); one
+        number for every prompt or one per prompt.  dynatemp_range = r >= 0 (0: off; strictly below the row's temperature T)
+        samples the row at T_dyn = (T - r) + 2 r h^e, h the normalised entropy of its processed logits at temperature 1 and
+        e = dynatemp_exponent > 0 (1 unless set); smoothing_factor = f >= 0 (0: off) bends the logits around their maximum,
+        x <- x_max - k d^2 + s d^3 with d = x - x_max, k = f (3 - c) / 2, s = f (c - 1) / 2 and c = smoothing_curve in
+        [1, 3] (1 unless set: the plain quadratic).  The pass runs behind every cut and AHEAD of the temperature and top-k,
+        top-p and min-p (llama.cpp runs those three ahead of its temperature stage).  A row takes one of the two, and neither
+        together with Mirostat: ValueError, as for a bool, a NaN, a value outside its range, the wrong length, a range that
+        reaches the row's temperature and an exponent or curve without a row that uses it.  Log-probs, top-N tables and token
+        statistics describe the distribution behind the pass.  Greedy decoding ignores all four (module docstring, SHAPING)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1486,7 +1574,7 @@ class Stage:
                           guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats,
                           typical_p, epsilon_cutoff, eta_cutoff, dry_multiplier, dry_base, dry_allowed_length, dry_range,
                           dry_sequence_breakers, mirostat_tau, mirostat_eta, top_n_sigma, top_a, xtc_threshold,
-                          xtc_probability)
+                          xtc_probability, dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1525,7 +1613,8 @@ class Stage:
               guided_choice=None, guided_choice_per_prompt=None, no_repeat_ngram_size=None, prompt_logprobs=None,
               token_stats=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, dry_multiplier=None, dry_base=None,
               dry_allowed_length=None, dry_range=None, dry_sequence_breakers=None, mirostat_tau=None,
-              mirostat_eta=None, top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None) -> _Plan:
+              mirostat_eta=None, top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None,
+              dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None, smoothing_curve=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1606,12 +1695,27 @@ class Stage:
         if cut_draft_rows:
             check_relative_cut_alone(rel_draft_rows, cut_draft_rows)
         check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows, rel_rows)
+        own_shape = (cfg.dynatemp_range, cfg.dynatemp_exponent, cfg.smoothing_factor, cfg.smoothing_curve) if self.draft is None else \
+            (cfg.target_dynatemp_range, cfg.target_dynatemp_exponent, cfg.target_smoothing_factor, cfg.target_smoothing_curve)
+        shape_rows = check_logit_shapes(*(given(v, d) for v, d in zip((dynatemp_range, dynatemp_exponent, smoothing_factor,
+                                                                       smoothing_curve), own_shape)),
+                                        n, dynatemp_exponent is not None, smoothing_curve is not None)
+        check_logit_shape_alone(shape_rows, miro_rows)
+        # the draft rows take the DRAFT stage's configured shaping (per-request draft-side values: NOT BUILT)
+        shape_draft_rows = [] if dcfg is None else check_logit_shapes(dcfg.dynatemp_range, dcfg.dynatemp_exponent,
+                                                                      dcfg.smoothing_factor, dcfg.smoothing_curve, n)
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
         if live and not isinstance(temperature, list) and not temperature >= 0.0:     # (NaN included)
             raise ValueError("temperature must be >= 0 (0: greedy decoding)")
         greedy = not live or (not isinstance(temperature, list) and temperature == 0.0)
+        if not greedy:                           # a range must stay under the row's temperature; the records carry T itself
+            row_t = temperature if isinstance(temperature, list) else [temperature] * n
+            check_logit_shape_alone(shape_rows, temps=row_t)
+            check_logit_shape_alone(shape_draft_rows, temps=row_t, side="the draft stage's configured ")
+            shape_rows = [(m, float(np.float32(t)), a, b) for (m, a, b), t in zip(shape_rows, row_t)]
+            shape_draft_rows = [(m, float(np.float32(t)), a, b) for (m, a, b), t in zip(shape_draft_rows, row_t)]
         scalars = rows = None
         if not greedy and any(isinstance(v, list) for v in (temperature, top_p, top_k, min_p)):
             # the rows route (module docstring, PER-REQUEST SAMPLING): every row's four values
@@ -1630,6 +1734,8 @@ class Stage:
                      cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
                      dry=dry if any(m > 0.0 for m in dry[0]) else None,           # every row off: no state, no call
                      rel_rows=rel_rows if not greedy and any(m for m, _, _ in rel_rows) else None,     # greedy ignores the cuts
+                     shape_rows=shape_rows if not greedy and any(r[0] for r in shape_rows) else None,  # ... and the shaping
+                     shape_draft_rows=shape_draft_rows if not greedy and any(r[0] for r in shape_draft_rows) else None,
                      rel_draft_rows=rel_draft_rows if not greedy and any(m for m, _, _ in rel_draft_rows) else None,
                      miro_rows=miro_rows if not greedy and any(t > 0.0 for t, _ in miro_rows) else None)    # greedy ignores Mirostat
 
@@ -1652,6 +1758,7 @@ class Stage:
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         fsm, ngram, stat, cut, dry, miro, rel = st.fsm, st.ngram, st.stats, st.cut, st.dry, st.miro, st.rel
+        shape = st.shape
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1680,6 +1787,7 @@ class Stage:
                 dry.apply(logits, tokens, seq_len)                       # ... and DRY behind them, on the n-gram rule's history
             rel_in = rel.apply(logits, coins, self.keep_inputs) if rel is not None else None   # the relative cut: directly behind DRY
             cut_in = cut.apply(logits, self.keep_inputs) if cut is not None else None   # the entropy cut: behind every processor
+            shape_in = shape.apply(logits, self.keep_inputs) if shape is not None else None   # shaping: behind the cuts, ahead of the temperature
             miro_in = miro.apply(logits, None, self.keep_inputs) if miro is not None else None   # Mirostat: the LAST pass
             n_acc, tok, lp = sampler.draw(logits, step)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
@@ -1687,6 +1795,8 @@ class Stage:
                 kept["cut_in"] = cut_in
             if kept is not None and rel is not None:
                 kept.update(rel_in=rel_in, rel_coins=None if coins is None else coins.clone())
+            if kept is not None and shape is not None:
+                kept["shape_in"] = shape_in
             if kept is not None and miro is not None:
                 kept.update(miro_in=miro_in, mu_path=miro.path.clone())
             if stat is not None:
@@ -1736,6 +1846,7 @@ class Stage:
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         fsm, ngram, stat, cut, cut_draft, dry, miro = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft, st.dry, st.miro
         rel, rel_draft = st.rel, st.rel_draft
+        shape, shape_draft = st.shape, st.shape_draft
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -1778,6 +1889,8 @@ class Stage:
                     rel_draft.apply(dl)                                 # the DRAFT stage's configured top-n-sigma / top-a
                 if cut_draft is not None:
                     cut_in_draft.append(cut_draft.apply(dl, self.keep_inputs))   # the DRAFT stage's configured cut, last
+                if shape_draft is not None:
+                    shape_draft.apply(dl)                               # the DRAFT stage's configured shaping, behind its cuts
                 toks.append(sampler.propose(dl, k))
                 if step_tok is not None:
                     step_tok[:, k] = toks[-1]
@@ -1803,6 +1916,7 @@ class Stage:
                 dry.apply(t_out, tokens, seq_len)                       # the same records and history per row as the draft's rows had
             rel_in = rel.apply(t_out, sampler.coin, self.keep_inputs) if rel is not None else None   # the call's own relative cut; row j under coin j
             cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None    # the call's own cut on the K + 1 rows
+            shape_in = shape.apply(t_out, self.keep_inputs) if shape is not None else None   # the call's own shaping on the K + 1 rows
             miro_in = miro.apply(t_out, tok32, self.keep_inputs) if miro is not None else None   # Mirostat, chained through the rows
             lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
             kept = sampler.kept(seq_len) if self.keep_inputs else None
@@ -1810,6 +1924,8 @@ class Stage:
                 kept["cut_in"] = cut_in
             if kept is not None and rel is not None:
                 kept.update(rel_in=rel_in, rel_coins=None if sampler.coin is None else sampler.coin.clone())
+            if kept is not None and shape is not None:
+                kept["shape_in"] = shape_in
             if kept is not None and miro is not None:
                 kept.update(miro_in=miro_in, mu_path=miro.path.clone())
             if kept is not None and cut_draft is not None:              # the draft rows as they entered and as they left the cut

@@ -938,6 +938,56 @@ int asd_relative_cut_rows(void* logits /*in/out*/, int dtype, int B, int K1, int
                           int64_t ld_coin, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SHAPING ahead of the samplers -- llama.cpp's / koboldcpp's dynamic temperature (`dynatemp_range`, `dynatemp_exponent`) and
+ * the quadratic "smooth" sampling of text-generation-webui, koboldcpp and Aphrodite (`smoothing_factor`, `smoothing_curve`):
+ * the two samplers that reshape a distribution instead of cutting it.  One in-place pass behind asd_entropy_cut_rows and ahead
+ * of the temperature and top-k / top-p / min-p; the only pass that writes a whole row back.
+ * logits: asd_relative_cut_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only.
+ * table: B records {int32 mode; float T; float a; float b} (asd_logit_shape_rec, 16 bytes) on the device; all K1 rows of
+ * sequence b use record b.
+ * The input is the row as every earlier pass left it, the values the stored ones, fin the set of its finite elements and
+ * n = |fin|.  A -inf element stays -inf and enters no statistic.  A row with a NaN or +inf element, or with n == 0, is left bit
+ * for bit as it is.
+ *   ASD_SHAPE_OFF (0): the row is not read.
+ *   ASD_SHAPE_DYNATEMP (1), T = the row's temperature, a = the range r in (0, T), b = the exponent e in (0, inf):
+ *     p = softmax(x) over fin at temperature 1 (llama.cpp measures the entropy of the raw logits), H = -sum p ln p,
+ *     h = clamp(H / ln n, 0, 1), T_dyn = (T - r) + 2 r h^e, g = T / T_dyn.  Every finite element becomes x_v * g, so that the
+ *     sampler's unchanged x / T equals x / T_dyn.  n < 2: nothing is written.  g is formed once per row in f64 from the f32
+ *     statistics and rounded once to f32; the product rounds once in f32.  A row whose g rounds to exactly 1 keeps its bits and
+ *     is not swept a second time.  A row whose f32 statistics overflow (f32 logits with |x| log2 e beyond f32's range), or
+ *     whose g is not a positive finite number, is left as it is.
+ *   ASD_SHAPE_QUADRATIC (2), a = the factor f in (0, inf), b = the curve c in [1, 3]: d_v = x_v - x_max,
+ *     k = f (3 - c) / 2, s = f (c - 1) / 2 (f64 products rounded once to f32), x_v <- (x_max - k d_v^2) + s d_v^3, every
+ *     operation rounding once in f32.  c = 1 is the plain quadratic x_max - f d^2.  k, s >= 0: the map is non-decreasing in d,
+ *     so the order of the elements is never inverted (ties may appear) and the arg-max keeps its bits.  T is not used.
+ * The f32 result is rounded to the dtype to nearest even and clamped to the dtype's finite range: a finite element never
+ * becomes +-inf.  A 16-byte vector is stored only where a bit of it changes; nothing outside a row's V elements is written.
+ * THE DATA CONTRACT: a record whose mode lies outside 0..2, or whose T / a / b lies outside the ranges above, skips its rows.
+ * Arithmetic: one workgroup of 1024 threads per (b, j); a lane meets its elements in ascending order, lanes merge by a fixed
+ * DPP sequence, waves in wave order: the result depends on the row's bytes and its record only.  Rows of at most 19 * 1024
+ * 16-byte vectors are read from memory once and rewritten from registers; longer rows are re-read.  Wave 0 merges the waves'
+ * partials and forms g once per row; the other waves take it from LDS behind a second barrier.  dynatemp: (m2, s, u)
+ * with c2 = float(log2 e), s * 2^m2 = sum exp(x_v), u = sum e_v (x_v c2 - m2); the count an integer;
+ * h = (log2 s - u / s) / log2 n with both logarithms by the same split evaluation.  No workspace, no state.
+ * Status, in this order: negative B / K1 / V: invalid argument; B, K1 or V == 0: ASD_OK, nothing launched; unknown dtype,
+ * B*K1 > INT32_MAX, V * element size > INT32_MAX: unsupported; NULL logits / table, ld_row < V, ld_seq < K1*ld_row: invalid
+ * argument; logits not aligned to the element size, or table not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_SHAPE_OFF 0
+#define ASD_SHAPE_DYNATEMP 1
+#define ASD_SHAPE_QUADRATIC 2
+#define ASD_LOGIT_SHAPE_REC_BYTES 16
+typedef struct asd_logit_shape_rec {
+    int32_t mode;  /* ASD_SHAPE_* */
+    float T;       /* the temperature of the sequence (mode 1) */
+    float a;       /* dynatemp_range or smoothing_factor */
+    float b;       /* dynatemp_exponent or smoothing_curve */
+} asd_logit_shape_rec;
+int asd_logit_shape_rows(void* logits /*in/out*/, int dtype, int B, int K1, int V, int64_t ld_seq, int64_t ld_row,
+                         const asd_logit_shape_rec* table /*[B]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /
  * structured-output back ends compile a set of answers, a regex or a schema to.  Inside a speculative step the mask of
  * position j depends on the proposals 0 .. j-1, which exist only on the device: so the state lives there, small kernels

@@ -629,6 +629,26 @@ int main() {
 #undef REL
     }
 
+    // ---- asd_logit_shape_rows: asd_relative_cut_rows' order without the coins
+    {
+#define SHP(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_) asd_logit_shape_rows(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, nullptr)
+        const int K1 = 5;
+        const asd_logit_shape_rec* tab = reinterpret_cast<const asd_logit_shape_rec*>(rows);
+        EXPECT(SHP(p, BF16, -1, K1, V, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(SHP(p, BF16, B, -1, V, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(SHP(p, BF16, B, K1, -1, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(SHP(nullptr, 99, 0, K1, V, 0, 0, nullptr), ASD_OK);
+        EXPECT(SHP(nullptr, 99, B, K1, V, K1 * V, V, tab), ASD_ERR_UNSUPPORTED);                       // dtype, before the NULL checks
+        EXPECT(SHP(p, 0 /*f32*/, B, 1, INT32_MAX, INT32_MAX, INT32_MAX, tab), ASD_ERR_UNSUPPORTED);
+        EXPECT(SHP(nullptr, BF16, B, K1, V, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(SHP(p, BF16, B, K1, V, K1 * V, V, nullptr), ASD_ERR_INVALID_ARG);
+        EXPECT(SHP(p, BF16, B, K1, V, K1 * V, V - 1, tab), ASD_ERR_INVALID_ARG);                        // ld_row < V
+        EXPECT(SHP(p, BF16, B, K1, V, K1 * V - 1, V, tab), ASD_ERR_INVALID_ARG);                        // ld_seq < K1 ld_row
+        EXPECT(SHP(rows + 1, BF16, B, K1, V, K1 * V, V, tab), ASD_ERR_ALIGNMENT);                       // below the element size
+        EXPECT(SHP(p, BF16, B, K1, V, K1 * V, V, reinterpret_cast<const asd_logit_shape_rec*>(rows + 2)), ASD_ERR_ALIGNMENT);
+#undef SHP
+    }
+
     // ---- asd_step_uniforms_ex: asd_step_uniforms' rejections, plus the coin and its count
     {
         const int64_t* seeds = reinterpret_cast<const int64_t*>(rows);
