@@ -31,6 +31,7 @@ DRY_REC_BYTES = 404                   # ASD_DRY_REC_BYTES: one asd_dry_rec {on, 
 MIROSTAT_REC_BYTES, MIROSTAT_ROW_BYTES = 12, 16   # ASD_MIROSTAT_REC_BYTES ({inv_t, tau, eta} f32), ASD_MIROSTAT_ROW_BYTES (workspace per row)
 RELATIVE_CUT_REC_BYTES = 16           # ASD_RELATIVE_CUT_REC_BYTES: one {inv_t f32, mode i32, a f32, b f32} record of asd_relative_cut_rows
 LOGIT_SHAPE_REC_BYTES = 16            # ASD_LOGIT_SHAPE_REC_BYTES: one {mode i32, T f32, a f32, b f32} record of asd_logit_shape_rows
+WATERMARK_REC_BYTES = 16              # ASD_WATERMARK_REC_BYTES: one {key_lo u32, key_hi u32, delta f32, thr | h << 16 u32} record of asd_watermark_rows / _score
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
@@ -130,6 +131,8 @@ SIGNATURES = {
     "asd_mirostat_commit": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "asd_relative_cut_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _i64, _vp]),
     "asd_logit_shape_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp]),
+    "asd_watermark_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
+    "asd_watermark_score": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "asd_step_uniforms_ex": (_i, [_vp, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "asd_fsm_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_advance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp]),

@@ -588,6 +588,25 @@ class HipOps:
         entropy_cut_rows and directly ahead of the draw, and only when some row of the call is on."""
         return self.K.logit_shape_rows(logits, packed)
 
+    @traced("pack_watermark")
+    def pack_watermark(self, keys, deltas, gammas, contexts, prompt_lens, P: int, device):
+        """Every row's watermark key (None: off), delta, gamma and context width and the rows' numbers of real prompt ids,
+        which end at index P of the token buffer -> the device arguments of watermark_rows and watermark_score
+        (kernels.pack_watermark: one upload per generate or detect call)."""
+        return self.K.pack_watermark(keys, deltas, gammas, contexts, prompt_lens, P, device)
+
+    @traced("watermark_rows")
+    def watermark_rows(self, logits, wm, tokens, seq_len, max_len, step_tok=None, n_prev: int = 0):
+        """The green-list watermark ahead of the samplers (asd_watermark_rows): logits [B, V] or [B, K1, V] (any row stride),
+        every finite green element raised by delta in place; position j sees the row's real prompt ids, its committed tokens
+        and the step's first n_prev + j proposals."""
+        return self.K.watermark_rows(logits, wm, tokens, seq_len, max_len, step_tok, n_prev)
+
+    @traced("watermark_score")
+    def watermark_score(self, tokens, wm, row_from, seq_len, max_len):
+        """The detector's counts (asd_watermark_score): int32 [B, 2], {n_scored, n_green} over tokens[b, row_from[b]:seq_len[b]]."""
+        return self.K.watermark_score(tokens, wm, row_from, seq_len, max_len)
+
     @traced("pack_mirostat")
     def pack_mirostat(self, inv_t, taus, etas, device):
         """Every row's 1 / temperature, tau (0: off) and eta -> the device records of mirostat_rows and the running target

@@ -2239,3 +2239,121 @@ def mirostat_commit(miro: Mirostat, mu_path: torch.Tensor, n_acc: torch.Tensor, 
                                     _dev(n_commit, "n_commit", torch.int32), _dev(miro.table, "table", torch.uint8),
                                     _dev(miro.mu, "mu", torch.float32), _dev(mu_out, "mu_out", torch.float32), mu_out.shape[1], _stream())
     B.check("asd_mirostat_commit", rc)
+
+
+# ------------------------------------------------------------------------------- the green-list watermark (watermark_key / _delta / _gamma / _context)
+_WATERMARK_REC = np.dtype([("key_lo", np.uint32), ("key_hi", np.uint32), ("delta", np.float32), ("thr_h", np.uint32)])
+assert _WATERMARK_REC.itemsize == B.WATERMARK_REC_BYTES
+
+
+@dataclass
+class Watermark:
+    """The per-row arguments of asd_watermark_rows / asd_watermark_score on the device (pack_watermark): B records
+    {key_lo, key_hi, delta, thr | h << 16} as a uint8 [B, 16] tensor; row_start i32 [B], the index of every row's first real
+    prompt id behind the left-padding, or None when no row has a prompt id; `thr`: the host's copy of the rows' thresholds
+    (0: off), from which a detector forms its z."""
+    table: torch.Tensor
+    row_start: Optional[torch.Tensor]
+    P: int                                   # the padded prompt length the rows were packed for (`start` of the calls)
+    B: int
+    thr: Tuple[int, ...]
+
+
+def watermark_threshold(gamma: float) -> int:
+    """The 16-bit threshold of a green ratio: round(gamma * 65536) clamped into 1..65535; the effective ratio is thr / 65536."""
+    return min(max(int(round(float(gamma) * 65536.0)), 1), 65535)
+
+
+def check_watermark_rows(keys, deltas, gammas, contexts, prompt_lens, P: int):
+    """The host side of pack_watermark: every row's key (an int in [0, 2^64), or None: the row is off), delta (finite, > 0, as
+    the f32 number the record holds), gamma (in (0, 1)), context width (1..3) and number of real prompt ids in [0, P] -> (the
+    records, a numpy structured array; the row_start list with row_start[b] = P - prompt_lens[b])."""
+    cols = [list(c) for c in (keys, deltas, gammas, contexts, prompt_lens)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("keys, deltas, gammas, contexts and prompt_lens must describe the same rows")
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or not 0 <= int(P) < 2 ** 31:
+        raise ValueError(f"P must be an integer in [0, 2^31), got {P!r}")
+    rec = np.zeros(len(cols[0]), dtype=_WATERMARK_REC)
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))   # noqa: E731
+    integer = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))                     # noqa: E731
+    for b, (key, delta, gamma, h, m) in enumerate(zip(*cols)):
+        if not integer(m) or not 0 <= int(m) <= int(P):
+            raise ValueError(f"row {b}: the prompt length must be an integer in [0, {int(P)}], got {m!r}")
+        if key is None:
+            continue
+        if not integer(key) or not 0 <= int(key) < 2 ** 64:
+            raise ValueError(f"row {b}: the key must be an integer in [0, 2^64) or None, got {key!r}")
+        if not number(delta) or not 0.0 < float(np.float32(delta)) < float("inf"):
+            raise ValueError(f"row {b}: delta must be a finite number > 0, got {delta!r}")
+        if not number(gamma) or not 0.0 < float(gamma) < 1.0:
+            raise ValueError(f"row {b}: gamma must lie in (0, 1), got {gamma!r}")
+        if not integer(h) or not 1 <= int(h) <= 3:
+            raise ValueError(f"row {b}: the context width must be 1, 2 or 3, got {h!r}")
+        rec[b] = (int(key) & 0xFFFFFFFF, int(key) >> 32, np.float32(delta), watermark_threshold(gamma) | int(h) << 16)
+    return rec, [int(P) - int(m) for m in cols[4]]
+
+
+def pack_watermark(keys, deltas, gammas, contexts, prompt_lens, P: int, device) -> Watermark:
+    """The per-row arguments of watermark_rows and watermark_score from host lists, checked BEFORE anything is uploaded
+    (check_watermark_rows).  One upload per generate or detect call."""
+    rec, first = check_watermark_rows(keys, deltas, gammas, contexts, prompt_lens, P)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _WATERMARK_REC.itemsize).copy()).to(device)
+    return Watermark(table, None if all(f == int(P) for f in first) else torch.tensor(first, dtype=torch.int32).to(device), int(P),
+                     len(rec), tuple(int(t) & 0xFFFF for t in rec["thr_h"]))
+
+
+def watermark_rows(logits: torch.Tensor, wm: Watermark, tokens: torch.Tensor, seq_len: torch.Tensor, max_len: int,
+                   step_tok: Optional[torch.Tensor] = None, n_prev: int = 0) -> torch.Tensor:
+    """Bias the green tokens in place (asd_watermark_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any
+    sequence / row stride with unit stride along V.  With H = tokens[b, row_start[b]:seq_len[b]] ++ step_tok[b, :n_prev + j],
+    token v is green at position j iff halfword v & 7 of philox4x32_10((v >> 3, H[-1], H[-2] | ~0, H[-3] | ~0), key) is < thr;
+    every finite green element gains delta in f32, rounded to the dtype to nearest even and clamped to its largest finite
+    value.  tokens i32 [B, >= max_len] contiguous; seq_len i32 [B]: the step's lengths BEFORE its commit; step_tok i32
+    [B, n_tok] (unit stride along the proposals) or None."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    start = wm.P
+    if wm.B != Bv or tuple(seq_len.shape) != (Bv,):
+        raise ValueError(f"the watermark records were packed for {wm.B} rows and seq_len must be int32 [B]; logits have {Bv} rows")
+    if tokens.dim() != 2 or tokens.shape[0] != Bv or not 0 <= start <= int(max_len) <= tokens.shape[1]:
+        raise ValueError(f"tokens must be int32 [B, >= max_len] and 0 <= start <= max_len, got {tuple(tokens.shape)}, {start}, {max_len}")
+    ld_tok = n_tok = 0
+    if step_tok is None:
+        if n_prev != 0:
+            raise ValueError("n_prev must be 0 without step_tok")
+    else:
+        if not step_tok.is_cuda or step_tok.dtype != torch.int32 or step_tok.dim() != 2 or step_tok.shape[0] != Bv or \
+                (step_tok.shape[1] > 1 and step_tok.stride(1) != 1):
+            raise ValueError("step_tok must be a CUDA int32 [B, n_tok] tensor with unit stride along the proposals")
+        n_tok = step_tok.shape[1]
+        ld_tok = step_tok.stride(0) if Bv > 1 else n_tok
+        if not 0 <= int(n_prev) or int(n_prev) + K1 - 1 > n_tok or ld_tok < n_tok:
+            raise ValueError(f"position {K1 - 1} would see {int(n_prev) + K1 - 1} proposals; step_tok holds {n_tok}")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_watermark_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], ld_seq, ld_row, Bv, K1, V, _dev(wm.table, "table", torch.uint8),
+                                   _opt(wm.row_start, "row_start", torch.int32), _dev(tokens, "tokens", torch.int32), tokens.shape[1],
+                                   _dev(seq_len, "seq_len", torch.int32), start, int(max_len),
+                                   None if step_tok is None else step_tok.data_ptr(), ld_tok, n_tok, int(n_prev), _stream())
+    B.check("asd_watermark_rows", rc)
+    return logits
+
+
+def watermark_score(tokens: torch.Tensor, wm: Watermark, row_from: torch.Tensor, seq_len: torch.Tensor, max_len: int) -> torch.Tensor:
+    """-> int32 [B, 2], {n_scored, n_green} per row (asd_watermark_score, one launch): over the positions i of tokens[b] in
+    [max(row_from[b], row_start[b] + h), seq_len[b]), position i scored under the context tokens[b, i - 1], [i - 2], [i - 3].
+    tokens i32 [B, >= max_len] contiguous; row_from, seq_len i32 [B]; a row that is off gives {0, 0}."""
+    Bv = wm.B
+    if tokens.dim() != 2 or tokens.shape[0] != Bv or not 0 <= int(max_len) <= tokens.shape[1]:
+        raise ValueError(f"tokens must be int32 [{Bv}, >= max_len], got {tuple(tokens.shape)}, {max_len}")
+    if tuple(row_from.shape) != (Bv,) or tuple(seq_len.shape) != (Bv,):
+        raise ValueError(f"row_from and seq_len must be int32 [{Bv}]")
+    out = torch.empty((Bv, 2), dtype=torch.int32, device=tokens.device)
+    rc = _lib().asd_watermark_score(_dev(tokens, "tokens", torch.int32), tokens.shape[1], _opt(wm.row_start, "row_start", torch.int32),
+                                    _dev(row_from, "row_from", torch.int32), _dev(seq_len, "seq_len", torch.int32), Bv, int(max_len),
+                                    _dev(wm.table, "table", torch.uint8), _dev(out, "out", torch.int32), _stream())
+    B.check("asd_watermark_score", rc)
+    return out

@@ -51,6 +51,8 @@ configuration only: a value that is set is handed to every stage's generate call
 `PipelineConfig.dynatemp_range` / `dynatemp_exponent` / `smoothing_factor` / `smoothing_curve` (serving/stages.py, SHAPING) too.
 `PipelineConfig.dry_multiplier` / `dry_base` / `dry_allowed_length` / `dry_range` / `dry_sequence_breakers` (the DRY sampler;
 serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
+`PipelineConfig.watermark_key` / `watermark_delta` / `watermark_gamma` / `watermark_context` (the green-list text watermark;
+serving/stages.py, WATERMARK) likewise: every stage then biases the same green lists, so accepted drafts stay watermarked.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -248,6 +250,12 @@ class PipelineConfig:
     dry_allowed_length: Optional[int] = None
     dry_range: Optional[int] = None
     dry_sequence_breakers: Optional[Sequence] = None
+    # the green-list watermark, handed to stage.generate(watermark_key=, watermark_delta=, watermark_gamma=, watermark_context=);
+    # None: the keyword is not passed (serving/stages.py, WATERMARK)
+    watermark_key: Optional[int] = None
+    watermark_delta: Optional[float] = None
+    watermark_gamma: Optional[float] = None
+    watermark_context: Optional[int] = None
     # vLLM's prompt_logprobs (serving/stages.py, PROMPT LOG-PROBS), handed to every stage.generate(prompt_logprobs=): each
     # stage's entry then carries "prompt_logprobs" and "prompt_ranks"; not fed to the predictor.  None: the keyword is not passed
     prompt_logprobs: Optional[int] = None
@@ -294,6 +302,9 @@ class PipelineConfig:
             if sec.get(name) is not None:
                 kw[name] = float(sec[name])
         for name, kind in (("dry_multiplier", float), ("dry_base", float), ("dry_allowed_length", int), ("dry_range", int)):
+            if sec.get(name) is not None:
+                kw[name] = kind(sec[name])
+        for name, kind in (("watermark_key", int), ("watermark_delta", float), ("watermark_gamma", float), ("watermark_context", int)):
             if sec.get(name) is not None:
                 kw[name] = kind(sec[name])
         if sec.get("dry_sequence_breakers") is not None:
@@ -656,7 +667,8 @@ class AdaptiveSpeculativePipeline:
                              "dry_multiplier", "dry_base", "dry_allowed_length", "dry_range", "dry_sequence_breakers",
                              "mirostat_tau", "mirostat_eta",                     # ... and Mirostat
                              "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",     # ... and the relative cuts
-                             "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve"):   # ... and the shaping
+                             "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve",    # ... and the shaping
+                             "watermark_key", "watermark_delta", "watermark_gamma", "watermark_context"):    # ... and the watermark
                     if getattr(cfg, name) is not None:
                         stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:

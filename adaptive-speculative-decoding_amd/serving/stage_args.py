@@ -601,6 +601,42 @@ def check_seeds(seed, n: int) -> Optional[List[int]]:
     return None if seed is None else _per_prompt(seed, n, one, "seeds")
 
 
+def check_watermark(key, delta, gamma, context, n: int, named: bool = False):
+    """generate's `watermark_key` (None: off; an int in [0, 2^64); or a sequence of n entries, each an int or None = that row
+    off), `watermark_delta` (a finite number in (0, 100], raw logit units: logit_bias' range), `watermark_gamma` (in (0, 1)) and
+    `watermark_context` (1, 2 or 3), each one value for all `n` prompts or a sequence of n values -> (n keys, n deltas, n
+    gammas, n context widths).  `named`: the call itself names a delta, gamma or context; without a key on any row that is an
+    error, as are a bool, a NaN, a value outside its range and the wrong length: ValueError."""
+    def one_key(v):
+        if v is not None and (not _is_int(v) or not 0 <= int(v) < 2 ** 64):
+            raise ValueError(f"watermark_key must be None or an integer in [0, 2^64), got {v!r}")
+        return None if v is None else int(v)
+
+    def one_delta(v):
+        if isinstance(v, bool) or not isinstance(v, _NUMBER) or not 0.0 < float(v) <= MAX_LOGIT_BIAS:      # (NaN included)
+            raise ValueError(f"watermark_delta must be a number in (0, {MAX_LOGIT_BIAS:g}], got {v!r}")
+        return float(v)
+
+    def one_gamma(v):
+        if isinstance(v, bool) or not isinstance(v, _NUMBER) or not 0.0 < float(v) < 1.0:
+            raise ValueError(f"watermark_gamma must be a number in (0, 1), got {v!r}")
+        return float(v)
+
+    def one_context(v):
+        if not _is_int(v) or not 1 <= int(v) <= 3:
+            raise ValueError(f"watermark_context must be 1, 2 or 3 (wider contexts are not built), got {v!r}")
+        return int(v)
+    cols = []
+    for name, value, one in (("watermark_key", key, one_key), ("watermark_delta", delta, one_delta),
+                             ("watermark_gamma", gamma, one_gamma), ("watermark_context", context, one_context)):
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name} must be one value or one per prompt, got {value!r}")
+        cols.append(_per_prompt(value, n, one, f"{name} values"))
+    if named and all(k is None for k in cols[0]):
+        raise ValueError("watermark_delta, watermark_gamma and watermark_context need a watermark_key on some row")
+    return tuple(cols)
+
+
 def merge_logit_edits(bias: List[Dict[int, float]], banned: List[Tuple[int, ...]], min_tokens: List[int],
                       row_seqs: List[List[Tuple[int, ...]]], vocab: int) -> List[List[Tuple[int, float, int]]]:
     """Per row, the distinct (id, bias, until) entries of asd_logit_edit_rows (LOGIT EDITS), sorted by id: a bias has until 0, a

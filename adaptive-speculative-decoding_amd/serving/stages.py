@@ -545,6 +545,34 @@ against 23.0 us (1.63 / 1.31 / 0.83 / 1.25).  A full rewrite moves up to twice t
 and the stores cost 6 us of the quadratic's 67.  NOT BUILT beside the above: a range that reaches temperature 0;
 serving/hierarchy.py's loop; per-request draft-side values.
 
+WATERMARK.  `generate(watermark_key=, watermark_delta=, watermark_gamma=, watermark_context=)` (or the StageConfig fields of
+those names; None takes the configuration's value) is the green-list text watermark of Kirchenbauer et al. 2023, which HF
+`generate` exposes as WatermarkingConfig(hashing_key, bias, greenlist_ratio, context_width).  watermark_key is None (off) or
+an int in [0, 2^64), watermark_delta a number in (0, 100] (2.0; raw logit units, logit_bias' range), watermark_gamma a number
+in (0, 1) (0.25) and watermark_context 1, 2 or 3 (1) -- each one value for the call or one per prompt; a None in a per-prompt
+list of keys switches that row off.  HF draws its green list from torch.randperm under a seeded generator, which no kernel
+restates, so THE PREDICATE is this library's own (include/asd_hip.h, WATERMARK): with thr = round(gamma * 65536) clamped into
+1..65535 and the history's last tokens a = H[-1], b = H[-2] (context >= 2), c = H[-3] (context 3), the missing ones
+0xFFFFFFFF, token v is green iff halfword v & 7 of philox4x32_10(counter = (v >> 3, a, b, c), key) is < thr.  H is the history
+of NO REPEAT N-GRAM: the row's real prompt ids (not the padding), its committed tokens and the step's own proposals in front
+of the position.  Every finite green logit gains delta in f32, rounded to the dtype to nearest even and clamped to its largest
+finite value; -inf, NaN and +inf stay, so the pass composes with every mask; a position with fewer than `context` tokens of
+history is left alone.  ops.watermark_rows (asd_watermark_rows: no reduction, no LDS; 256-lane workgroups on ranges of a
+row, one Philox call per eight token ids) runs directly behind DRY and ahead of the relative cut -- behind every processor,
+ahead of every warper, HF's position: mask -> fsm -> bad words -> n-gram -> edit -> penalties -> DRY -> WATERMARK -> relative
+cut -> entropy cut -> shaping -> temperature -> top-k -> top-p -> min-p -- on stage 0's [B, V] logits, on every draft row
+(position k sees the proposals 0 .. k-1) and on the target's [B, K+1, V] output with the SAME records, one launch per logits
+tensor: there is no target_* variant, the draft's and the target's logits receive the same edit from the same history, as
+with logit_bias, so the draft -> verify -> residual chain stays lossless against the watermarked target.  It runs under
+greedy decoding too: a bias moves the arg-max.  The pass keeps no state and needs no commit hook.  A call without a key on any
+row makes exactly the ops calls it made before.  RESULTS: stats["watermark"][i] = {"n_scored", "n_green", "z"} over the
+generated tokens of a watermarked row (one ops.watermark_score launch on the call's token buffer; z as below), None for a row
+that is off; without a key the entry is absent.  `Stage.detect_watermark(texts_or_ids, key, gamma, context, prompts)` scores
+texts the same way: z = (n_green - g n) / sqrt(n g (1 - g)) in f64 with g = thr / 65536, NaN for n = 0.  ValueError before
+any launch and before the prompts are encoded: a bool, a NaN, a value outside its range, the wrong length, and a delta, gamma
+or context named in a call that has no key on any row.  NOT BUILT: HF's `selfhash` seeding scheme, `ignore_repeated_ngrams`
+in detection, SynthID, context widths above 3, p-values, and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -566,7 +594,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -648,6 +676,10 @@ class StageConfig:
     dry_allowed_length: int = 2              # in [1, 64]: the shortest match that is penalised
     dry_range: int = 0                       # >= 0: the last tokens of the history that count; 0: all of it
     dry_sequence_breakers: Sequence = ()     # at most 32 token ids / one-token strings that reset a match
+    watermark_key: Optional[int] = None      # None: off; an int in [0, 2^64): the green-list watermark's key (module docstring, WATERMARK)
+    watermark_delta: float = 2.0             # in (0, 100]: what a green token's logit gains
+    watermark_gamma: float = 0.25            # in (0, 1): the green share of the vocabulary
+    watermark_context: int = 1               # 1..3: the tokens in front of a position that seed its green list
     guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
     guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
     prompt_logprobs: Optional[int] = None    # None: off; 0..8: the prompt tokens' log-probs and ranks, and a top-N table (PROMPT LOG-PROBS)
@@ -688,6 +720,7 @@ class _Plan(NamedTuple):
     shape_rows: Optional[list] = None        # every row's (mode, T, a, b) of the stage's own shaping; None: every row off
     shape_draft_rows: Optional[list] = None  # a verifying stage: every row's (mode, T, a, b) of the draft stage's configured shaping
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
+    watermark: Optional[tuple] = None        # every row's key (None: off), delta, gamma and context width; None: every row off
 
 
 class _EditState:
@@ -805,6 +838,37 @@ class _ShapeState:
         entered = logits.clone() if keep else None
         self.ops.logit_shape_rows(logits, self.packed)
         return entered
+
+
+class _WatermarkState:
+    """What a generate call with a watermark key keeps: the rows' records and the index of their first real prompt id on the
+    device (uploaded once), the size of the token buffer and, at a verifying stage, the call's [B, draft_len] buffer of the
+    step's proposals.  `apply` is the loops' one call per logits tensor, directly behind DRY's and ahead of the relative
+    cut's; nothing follows the commit: the pass reads `tokens` and keeps no state.  `stats` is the one scoring launch behind
+    the loop (module docstring, WATERMARK)."""
+
+    def __init__(self, ops, watermark, prompt_ids, P: int, cap: int, step_tok: Optional[torch.Tensor], device):
+        self.ops, self.cap, self.step_tok = ops, int(cap), step_tok
+        self.packed = ops.pack_watermark(*watermark, [len(r) for r in prompt_ids], int(P), device)
+
+    def apply(self, logits: torch.Tensor, tokens: torch.Tensor, seq_len: torch.Tensor, n_prev: int = 0) -> torch.Tensor:
+        """logits [B, V] or [B, K+1, V], biased in place; seq_len: the step's lengths before its commit; position j sees the
+        step's first n_prev + j proposals behind the row's prompt and committed tokens."""
+        if self.step_tok is None:
+            return self.ops.watermark_rows(logits, self.packed, tokens, seq_len, self.cap)
+        return self.ops.watermark_rows(logits, self.packed, tokens, seq_len, self.cap, self.step_tok, n_prev)
+
+    def stats(self, tokens: torch.Tensor, P: int, n_tok) -> Dict[str, object]:
+        """{"watermark": per row {"n_scored", "n_green", "z"} over its n_tok[i] generated tokens, None for a row that is off}."""
+        end = torch.tensor([P + int(n) for n in n_tok], dtype=torch.int32).to(tokens.device)
+        counts = self.ops.watermark_score(tokens, self.packed, torch.full_like(end, P), end, self.cap).cpu().numpy()
+        return {"watermark": [_watermark_entry(int(n), int(g), thr) if thr else None for (n, g), thr in zip(counts, self.packed.thr)]}
+
+
+def _watermark_entry(n: int, g: int, thr: int) -> Dict[str, object]:
+    """The detector's answer for one text: z = (g - gamma' n) / sqrt(n gamma' (1 - gamma')) in f64, gamma' = thr / 65536."""
+    gamma = thr / 65536.0
+    return {"n_scored": n, "n_green": g, "z": (g - gamma * n) / float(np.sqrt(n * gamma * (1.0 - gamma))) if n > 0 else float("nan")}
 
 
 class _CutState:
@@ -1287,7 +1351,8 @@ class _CallState:
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
         self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
-        history = any(plan.bad_rows) or any(plan.ngram_rows) or bool(plan.penalties) or plan.fsm is not None or plan.dry is not None
+        history = any(plan.bad_rows) or any(plan.ngram_rows) or bool(plan.penalties) or plan.fsm is not None or plan.dry is not None \
+            or plan.watermark is not None
         self.step_tok = torch.zeros((B, stage.config.draft_len), dtype=torch.int32, device=dev) \
             if history and stage.draft is not None else None
         self.fsm = _FsmState(ops, plan.fsm, 1 if stage.draft is None else stage.config.draft_len + 1, self.step_tok, dev) \
@@ -1297,6 +1362,8 @@ class _CallState:
             if any(plan.ngram_rows) else None
         self.pen = _PenaltyState(ops, plan.penalties, prompt_ids, stage.shape.vocab, self.step_tok, dev) if plan.penalties else None
         self.dry = _DryState(ops, plan.dry, prompt_ids, P, P + plan.max_tokens, self.step_tok, dev) if plan.dry is not None else None
+        self.wm = _WatermarkState(ops, plan.watermark, prompt_ids, P, P + plan.max_tokens, self.step_tok, dev) \
+            if plan.watermark is not None else None
         # greedy: no draws, no truncation, no table, a seed is ignored; else rows or scalars, decided here and nowhere else
         self.sampler = _Greedy(ops) if plan.greedy else (_SampledRows if plan.rows else _Sampled)(stage, plan, B, dev)
         self.top = _TopState(ops, plan.n_top, plan.inv_t, B, P + plan.max_tokens, dev,
@@ -1354,6 +1421,7 @@ class Stage:
         check_logit_shapes(config.dynatemp_range, config.dynatemp_exponent, config.smoothing_factor, config.smoothing_curve, 1)
         check_logit_shapes(config.target_dynatemp_range, config.target_dynatemp_exponent, config.target_smoothing_factor,
                            config.target_smoothing_curve, 1)
+        check_watermark(config.watermark_key, config.watermark_delta, config.watermark_gamma, config.watermark_context, 1)
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -1410,7 +1478,9 @@ class Stage:
                  mirostat_tau=None, mirostat_eta=None,
                  top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None,
                  dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None,
-                 smoothing_curve=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 smoothing_curve=None,
+                 watermark_key=None, watermark_delta=None, watermark_gamma=None,
+                 watermark_context=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1564,7 +1634,16 @@ class Stage:
         top-p and min-p (llama.cpp runs those three ahead of its temperature stage).  A row takes one of the two, and neither
         together with Mirostat: ValueError, as for a bool, a NaN, a value outside its range, the wrong length, a range that
         reaches the row's temperature and an exponent or curve without a row that uses it.  Log-probs, top-N tables and token
-        statistics describe the distribution behind the pass.  Greedy decoding ignores all four (module docstring, SHAPING)."""
+        statistics describe the distribution behind the pass.  Greedy decoding ignores all four (module docstring, SHAPING).
+        `watermark_key` (None = StageConfig.watermark_key; an int in [0, 2^64); in a per-prompt list None switches a row
+        off), `watermark_delta` (in (0, 100]), `watermark_gamma` (in (0, 1)) and `watermark_context` (1..3): the green-list
+        text watermark of Kirchenbauer et al. 2023 (HF's WatermarkingConfig), one value for every prompt or one per prompt.
+        At every position the tokens the key and the last `watermark_context` tokens of the history mark green -- a share
+        gamma of the vocabulary -- gain delta on their finite logits; draft and target logits receive the same bias from the
+        same history, directly behind DRY and ahead of every cut, under greedy decoding too, and log-probs, top-N tables and
+        token statistics describe the biased distribution.  stats["watermark"][i] = {"n_scored", "n_green", "z"} over row
+        i's generated tokens, None for a row without a key.  A bool, a NaN, a value outside its range, the wrong length, and
+        a delta, gamma or context named without a key on any row raise ValueError (module docstring, WATERMARK)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1574,7 +1653,8 @@ class Stage:
                           guided_choice, guided_choice_per_prompt, no_repeat_ngram_size, prompt_logprobs, token_stats,
                           typical_p, epsilon_cutoff, eta_cutoff, dry_multiplier, dry_base, dry_allowed_length, dry_range,
                           dry_sequence_breakers, mirostat_tau, mirostat_eta, top_n_sigma, top_a, xtc_threshold,
-                          xtc_probability, dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve)
+                          xtc_probability, dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve,
+                          watermark_key, watermark_delta, watermark_gamma, watermark_context)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1605,7 +1685,39 @@ class Stage:
             stats.update(state.prompt.stats())
         if state.miro is not None:
             stats.update(state.miro.stats(P, n_tok))
+        if state.wm is not None:
+            stats.update(state.wm.stats(tokens, P, n_tok))
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
+
+    @torch.no_grad()
+    def detect_watermark(self, texts_or_ids, key: int, gamma: float = 0.25, context: int = 1,
+                         prompts: Optional[Sequence[str]] = None) -> List[Dict[str, object]]:
+        """Score texts for the watermark of `key` -> per text {"n_scored", "n_green", "z"} (module docstring, WATERMARK).
+        texts_or_ids: generate's texts ("t12 t7 ...") or sequences of token ids.  With `prompts` (one per text, encoded as
+        generate encodes them) the prompt is the context of the first generated tokens, as it was during generation, and
+        every token of a text is scored; without, the first `context` tokens of a text are context only.  One
+        ops.watermark_score launch; z = (n_green - g n) / sqrt(n g (1 - g)) in f64 on the host, g = thr / 65536, NaN for
+        n = 0.  A malformed key, gamma or context and the wrong number of prompts raise ValueError."""
+        rows = [[int(w[1:]) for w in t.split()] if isinstance(t, str) else [int(i) for i in t] for t in texts_or_ids]
+        n = len(rows)
+        keys, _, gammas, contexts = check_watermark(key, 1.0, gamma, context, n)
+        if any(k is None for k in keys):
+            raise ValueError("detect_watermark needs a key")
+        if prompts is not None and len(prompts) != n:
+            raise ValueError(f"{len(prompts)} prompts for {n} texts")
+        if n == 0:
+            return []
+        real = [[] for _ in rows] if prompts is None else self._encode(prompts)[1]
+        P = max((len(r) for r in real), default=0)
+        cap = max(P + max(len(r) for r in rows), 1)
+        buf = np.zeros((n, cap), dtype=np.int32)
+        for b, (r, t) in enumerate(zip(real, rows)):
+            buf[b, P - len(r):P] = r
+            buf[b, P:P + len(t)] = t
+        packed = self.ops.pack_watermark(keys, [1.0] * n, gammas, contexts, [len(r) for r in real], P, self.device)
+        end = torch.tensor([P + len(t) for t in rows], dtype=torch.int32).to(self.device)
+        counts = self.ops.watermark_score(torch.from_numpy(buf).to(self.device), packed, torch.full_like(end, P), end, cap)
+        return [_watermark_entry(int(c), int(g), thr) for (c, g), thr in zip(counts.cpu().numpy(), packed.thr)]
 
     def _plan(self, prompts, max_tokens, temperature, top_p, stop_token_ids, logprobs, min_p, seed, stop_sequences,
               stop_sequences_per_prompt, top_k, logit_bias, banned_token_ids, min_tokens, allowed_token_ids,
@@ -1614,7 +1726,8 @@ class Stage:
               token_stats=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, dry_multiplier=None, dry_base=None,
               dry_allowed_length=None, dry_range=None, dry_sequence_breakers=None, mirostat_tau=None,
               mirostat_eta=None, top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None,
-              dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None, smoothing_curve=None) -> _Plan:
+              dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None, smoothing_curve=None,
+              watermark_key=None, watermark_delta=None, watermark_gamma=None, watermark_context=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1683,6 +1796,9 @@ class Stage:
         dry = check_dry(given(dry_multiplier, cfg.dry_multiplier), given(dry_base, cfg.dry_base),
                         given(dry_allowed_length, cfg.dry_allowed_length), given(dry_range, cfg.dry_range),
                         given(dry_sequence_breakers, cfg.dry_sequence_breakers), n, V, self.tokenizer)
+        watermark = check_watermark(given(watermark_key, cfg.watermark_key), given(watermark_delta, cfg.watermark_delta),
+                                    given(watermark_gamma, cfg.watermark_gamma), given(watermark_context, cfg.watermark_context), n,
+                                    any(v is not None for v in (watermark_delta, watermark_gamma, watermark_context)))
         own_miro = (cfg.mirostat_tau, cfg.mirostat_eta) if self.draft is None else (cfg.target_mirostat_tau, cfg.target_mirostat_eta)
         miro_rows = check_mirostat(given(mirostat_tau, own_miro[0]), given(mirostat_eta, own_miro[1]), n, mirostat_eta is not None)
         own_rel = (cfg.top_n_sigma, cfg.top_a, cfg.xtc_threshold, cfg.xtc_probability) if self.draft is None else \
@@ -1733,6 +1849,7 @@ class Stage:
                      cut_rows=cut_rows if not greedy and any(m for m, _ in cut_rows) else None,        # greedy ignores the cuts
                      cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
                      dry=dry if any(m > 0.0 for m in dry[0]) else None,           # every row off: no state, no call
+                     watermark=watermark if any(k is not None for k in watermark[0]) else None,   # no key: no state, no call
                      rel_rows=rel_rows if not greedy and any(m for m, _, _ in rel_rows) else None,     # greedy ignores the cuts
                      shape_rows=shape_rows if not greedy and any(r[0] for r in shape_rows) else None,  # ... and the shaping
                      shape_draft_rows=shape_draft_rows if not greedy and any(r[0] for r in shape_draft_rows) else None,
@@ -1758,7 +1875,7 @@ class Stage:
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         fsm, ngram, stat, cut, dry, miro, rel = st.fsm, st.ngram, st.stats, st.cut, st.dry, st.miro, st.rel
-        shape = st.shape
+        shape, wm = st.shape, st.wm
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = self.model
         m.reset()
@@ -1785,6 +1902,8 @@ class Stage:
                 pen.apply(logits)                                        # the penalties last: mask -> edit -> penalties
             if dry is not None:
                 dry.apply(logits, tokens, seq_len)                       # ... and DRY behind them, on the n-gram rule's history
+            if wm is not None:
+                wm.apply(logits, tokens, seq_len)                        # the watermark: behind every processor, ahead of every warper
             rel_in = rel.apply(logits, coins, self.keep_inputs) if rel is not None else None   # the relative cut: directly behind DRY
             cut_in = cut.apply(logits, self.keep_inputs) if cut is not None else None   # the entropy cut: behind every processor
             shape_in = shape.apply(logits, self.keep_inputs) if shape is not None else None   # shaping: behind the cuts, ahead of the temperature
@@ -1846,7 +1965,7 @@ class Stage:
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         fsm, ngram, stat, cut, cut_draft, dry, miro = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft, st.dry, st.miro
         rel, rel_draft = st.rel, st.rel_draft
-        shape, shape_draft = st.shape, st.shape_draft
+        shape, shape_draft, wm = st.shape, st.shape_draft, st.wm
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -1885,6 +2004,8 @@ class Stage:
                     pen.apply(dl, k)                                    # ... and sees the proposals 0 .. k - 1 of this step
                 if dry is not None:
                     dry.apply(dl, tokens, seq_len, k)                   # DRY: the n-gram rule's history, behind the penalties
+                if wm is not None:
+                    wm.apply(dl, tokens, seq_len, k)                    # the watermark: the green list behind the proposals 0 .. k - 1
                 if rel_draft is not None:
                     rel_draft.apply(dl)                                 # the DRAFT stage's configured top-n-sigma / top-a
                 if cut_draft is not None:
@@ -1914,6 +2035,8 @@ class Stage:
                 pen.apply(t_out)                                        # row j sees the proposals 0 .. j - 1, as the draft's did
             if dry is not None:
                 dry.apply(t_out, tokens, seq_len)                       # the same records and history per row as the draft's rows had
+            if wm is not None:
+                wm.apply(t_out, tokens, seq_len)                        # row j under the green list the draft's proposal j was drawn under
             rel_in = rel.apply(t_out, sampler.coin, self.keep_inputs) if rel is not None else None   # the call's own relative cut; row j under coin j
             cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None    # the call's own cut on the K + 1 rows
             shape_in = shape.apply(t_out, self.keep_inputs) if shape is not None else None   # the call's own shaping on the K + 1 rows

@@ -988,6 +988,58 @@ int asd_logit_shape_rows(void* logits /*in/out*/, int dtype, int B, int K1, int 
                          const asd_logit_shape_rec* table /*[B]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * WATERMARK: the green-list text watermark of Kirchenbauer et al. 2023 (HF generate's WatermarkingConfig: greenlist_ratio,
+ * bias, hashing_key, context_width) AHEAD of the samplers, and the counting half of its detector.  HF draws its green list
+ * from torch.randperm under a seeded generator, which no kernel restates; the predicate is this library's own and is stated
+ * exactly, so that generation, the scorer and a host reference agree bit for bit.
+ * THE PREDICATE.  A sequence has a 64-bit key (key_lo, key_hi), a context width h in 1..3 and a threshold thr in 1..65535
+ * (the effective green ratio is thr / 65536).  At a position with history H: a = H[-1], b = H[-2] if h >= 2 else 0xFFFFFFFF,
+ * c = H[-3] if h == 3 else 0xFFFFFFFF.  Token v is GREEN iff halfword v & 7 of philox4x32_10(counter = (v >> 3, a, b, c),
+ * key = (key_lo, key_hi)) is < thr -- asd_step_uniforms' generator; halfword i is word i >> 1, bits 0..15 for even i, bits
+ * 16..31 for odd i.  The green set depends on (key, h, thr, context, v) alone.
+ * asd_watermark_rows, in place: logits, tokens, ld_tokens, seq_len, start, max_len, row_start, step_tok, ld_tok, n_tok,
+ * n_prev are asd_dry_rows' addressing and history,
+ *     H = tokens[b][row_start[b] .. L)  ++  step_tok[b][0 .. n_prev + j),      L = clamp(seq_len[b], start, max_len)
+ * (the prompt's real ids count, the left-padding does not).  recs: B records asd_watermark_rec on the device; all K1 rows of
+ * sequence b use record b.  Every FINITE green element becomes fl32(x) + delta in f32, rounded to the dtype to nearest even;
+ * a result beyond the dtype's range becomes its largest finite value (0x7F7F bf16, 0x7BFF f16, FLT_MAX f32).  -inf, +inf and
+ * NaN elements, every element that is not green and the padding behind V keep their bits.  thr == 0: the row is off and is
+ * not read.  A position whose history is shorter than h is not written.
+ * THE DATA CONTRACT: seq_len[b] is clamped into [start, max_len] and row_start[b] into [0, start]; a record with h outside
+ * 1..3 or a delta that is not finite and positive skips its rows; history tokens are used as plain 32-bit numbers.
+ * One launch, no workspace, no LDS, no barrier, no atomics: workgroups of 256 lanes, each on a contiguous range of a row's
+ * 8-element units (one 16-byte vector in 16 bits, two adjacent ones in f32), four units per lane in flight; a row is cut into
+ * floor(8 * CUs / (B * K1)) ranges, at least 1 and at most ceil(V / 2048).  With a 16-byte aligned base and ld_seq and ld_row
+ * multiples of 16 bytes there is one Philox call per unit; otherwise two.  Both forms give the same bits.
+ * Status, in this order: negative B / K1 / V / n_tok / n_prev / start / max_len: invalid argument; B, K1 or V == 0: ASD_OK,
+ * nothing launched; unknown dtype, n_tok > ASD_MAX_DRAFT_LEN, B*K1 > INT32_MAX, max_len + n_tok > INT32_MAX, V * element size
+ * > INT32_MAX: unsupported; NULL logits / recs / tokens / seq_len, ld_row < V, ld_seq < K1*ld_row, ld_tokens < max_len,
+ * start > max_len, step_tok == NULL with n_prev != 0, step_tok != NULL with n_prev + K1 - 1 > n_tok or ld_tok < n_tok: invalid
+ * argument; logits not aligned to the element size, or recs / row_start / tokens / seq_len / step_tok not aligned to 4:
+ * alignment.
+ * asd_watermark_score: out[b] = {n_scored, n_green} (int32 [B, 2]) over the positions i of tokens[b] in
+ * [max(F, R + h), L), with L = clamp(seq_len[b], 0, max_len), R = clamp(row_start[b], 0, L) (NULL: 0) and
+ * F = clamp(row_from[b], R, L): position i is scored under the context tokens[b][i-1], [i-2], [i-3], and counts as green when
+ * tokens[b][i] is.  delta is not read; thr == 0 or h outside 1..3 gives {0, 0}.  One wave per sequence, no workspace.
+ * Status: negative B / max_len: invalid argument; B == 0: ASD_OK; NULL tokens / row_from / seq_len / recs / out,
+ * ld_tokens < max_len: invalid argument; a pointer not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_WATERMARK_REC_BYTES 16
+typedef struct asd_watermark_rec {
+    uint32_t key_lo, key_hi;  /* the sequence's 64-bit key */
+    float delta;              /* what a green token gains, in raw logit units: finite, > 0 */
+    uint32_t thr_h;           /* thr | h << 16; thr == 0: off */
+} asd_watermark_rec;
+int asd_watermark_rows(void* logits /*in/out*/, int dtype, int64_t ld_seq, int64_t ld_row, int B, int K1, int V,
+                       const asd_watermark_rec* recs /*[B]*/, const int32_t* row_start /*[B], or NULL: start for every row*/,
+                       const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens, const int32_t* seq_len /*[B]*/, int start,
+                       int max_len, const int32_t* step_tok /*[B, ld_tok], or NULL*/, int64_t ld_tok, int n_tok, int n_prev,
+                       void* stream);
+int asd_watermark_score(const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens, const int32_t* row_start /*[B], or NULL*/,
+                        const int32_t* row_from /*[B]*/, const int32_t* seq_len /*[B]*/, int B, int max_len,
+                        const asd_watermark_rec* recs /*[B]*/, int32_t* out /*[B, 2]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /
  * structured-output back ends compile a set of answers, a regex or a schema to.  Inside a speculative step the mask of
  * position j depends on the proposals 0 .. j-1, which exist only on the device: so the state lives there, small kernels

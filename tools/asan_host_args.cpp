@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_dry_rows, asd_entropy_cut_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_dry_rows, asd_watermark_rows, asd_watermark_score, asd_entropy_cut_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -647,6 +647,42 @@ int main() {
         EXPECT(SHP(rows + 1, BF16, B, K1, V, K1 * V, V, tab), ASD_ERR_ALIGNMENT);                       // below the element size
         EXPECT(SHP(p, BF16, B, K1, V, K1 * V, V, reinterpret_cast<const asd_logit_shape_rec*>(rows + 2)), ASD_ERR_ALIGNMENT);
 #undef SHP
+    }
+
+    // ---- asd_watermark_rows: asd_dry_rows' order with the 16-byte records; asd_watermark_score: sizes, pointers, alignment
+    {
+#define WM(x_, dt_, lds_, ldr_, B_, K1_, V_, rec_, rs_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_) \
+    asd_watermark_rows(x_, dt_, lds_, ldr_, B_, K1_, V_, rec_, rs_, tk_, ldk_, sl_, st_, ml_, tok_, ldt_, nt_, np_, nullptr)
+        const int K1 = 5;
+        const asd_watermark_rec* rec = reinterpret_cast<const asd_watermark_rec*>(rows);
+        const asd_watermark_rec* rec_off = reinterpret_cast<const asd_watermark_rec*>(rows + 2);
+        int32_t* off = reinterpret_cast<int32_t*>(rows + 2);
+        static_assert(sizeof(asd_watermark_rec) == ASD_WATERMARK_REC_BYTES, "the record the host packs");
+        EXPECT(WM(p, BF16, K1 * V, V, -1, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, -1, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);    // max_len
+        EXPECT(WM(p, BF16, K1 * V, V, 0, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, -1), ASD_ERR_INVALID_ARG);   // n_prev, before the empty batch
+        EXPECT(WM(nullptr, 99, 0, 0, B, K1, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0), ASD_OK);   // V == 0
+        EXPECT(WM(nullptr, 99, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);  // dtype, before the NULL checks
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 65, ASD_MAX_DRAFT_LEN + 1, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, INT64_C(1) << 31, i32, 4, INT32_MAX - 2, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);
+        EXPECT(WM(p, 0 /*f32*/, INT32_MAX, INT32_MAX, B, 1, INT32_MAX, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_UNSUPPORTED);   // V * 4 bytes
+        EXPECT(WM(nullptr, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, nullptr, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // recs
+        EXPECT(WM(p, BF16, K1 * V, V - 1, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // ld_row < V
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 33, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);      // start > max_len
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, nullptr, 0, 0, 1), ASD_ERR_INVALID_ARG);   // n_prev without step_tok
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 1), ASD_ERR_INVALID_ARG);       // position 4 would see 5 of 4
+        EXPECT(WM(rows + 1, BF16, K1 * V, V - 1, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_INVALID_ARG);   // ... before alignment
+        EXPECT(WM(rows + 1, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);  // below the element size
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec_off, i32, i32, 32, i32, 4, 32, i32, 4, 4, 0), ASD_ERR_ALIGNMENT);     // recs
+        EXPECT(WM(p, BF16, K1 * V, V, B, K1, V, rec, i32, i32, 32, i32, 4, 32, off, 4, 4, 0), ASD_ERR_ALIGNMENT);         // step_tok
+#undef WM
+        EXPECT(asd_watermark_score(i32, 32, i32, i32, i32, -1, 32, rec, i32, nullptr), ASD_ERR_INVALID_ARG);
+        EXPECT(asd_watermark_score(nullptr, 0, nullptr, nullptr, nullptr, 0, 32, nullptr, nullptr, nullptr), ASD_OK);    // B == 0
+        EXPECT(asd_watermark_score(i32, 32, nullptr, nullptr, i32, B, 32, rec, i32, nullptr), ASD_ERR_INVALID_ARG);      // row_from
+        EXPECT(asd_watermark_score(i32, 31, i32, i32, i32, B, 32, rec, i32, nullptr), ASD_ERR_INVALID_ARG);              // ld_tokens < max_len
+        EXPECT(asd_watermark_score(i32, 32, i32, i32, i32, B, 32, rec_off, i32, nullptr), ASD_ERR_ALIGNMENT);
+        EXPECT(asd_watermark_score(i32, 32, i32, i32, i32, B, 32, rec, off, nullptr), ASD_ERR_ALIGNMENT);                // out
     }
 
     // ---- asd_step_uniforms_ex: asd_step_uniforms' rejections, plus the coin and its count
