@@ -32,6 +32,7 @@ MIROSTAT_REC_BYTES, MIROSTAT_ROW_BYTES = 12, 16   # ASD_MIROSTAT_REC_BYTES ({inv
 RELATIVE_CUT_REC_BYTES = 16           # ASD_RELATIVE_CUT_REC_BYTES: one {inv_t f32, mode i32, a f32, b f32} record of asd_relative_cut_rows
 LOGIT_SHAPE_REC_BYTES = 16            # ASD_LOGIT_SHAPE_REC_BYTES: one {mode i32, T f32, a f32, b f32} record of asd_logit_shape_rows
 WATERMARK_REC_BYTES = 16              # ASD_WATERMARK_REC_BYTES: one {key_lo u32, key_hi u32, delta f32, thr | h << 16 u32} record of asd_watermark_rows / _score
+MAX_LOOKUP_TOKENS, MAX_LOOKUP_NGRAM, LOOKUP_TILE = 16, 8, 4096   # ASD_MAX_LOOKUP_TOKENS, ASD_MAX_LOOKUP_NGRAM, ASD_LOOKUP_TILE (asd_lookup_propose)
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
@@ -133,6 +134,7 @@ SIGNATURES = {
     "asd_logit_shape_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp]),
     "asd_watermark_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _i, _i, _vp]),
     "asd_watermark_score": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "asd_lookup_propose": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i64, _i64, _i, _vp]),
     "asd_step_uniforms_ex": (_i, [_vp, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "asd_fsm_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_advance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp]),

@@ -607,6 +607,15 @@ class HipOps:
         """The detector's counts (asd_watermark_score): int32 [B, 2], {n_scored, n_green} over tokens[b, row_from[b]:seq_len[b]]."""
         return self.K.watermark_score(tokens, wm, row_from, seq_len, max_len)
 
+    @traced("lookup_propose")
+    def lookup_propose(self, tokens, seq_len, start: int, max_len: int, tok, matched, max_ngram: int = 3, min_ngram: int = 1,
+                       row_start=None, counter=None, onehot=None):
+        """Prompt-lookup drafting (asd_lookup_propose, one launch): tok [B, K] <- what followed the most recent, longest earlier
+        occurrence (min_ngram .. max_ngram tokens) of the row's last tokens in tokens[b, row_start[b]:seq_len[b]], or the last
+        token; matched [B] <- the match length or 0, counter[b] += matched > 0; onehot [B, K, V]: the proposals' one-hot draft
+        rows, kept by two element stores per proposal."""
+        return self.K.lookup_propose(tokens, seq_len, start, max_len, tok, matched, max_ngram, min_ngram, row_start, counter, onehot)
+
     @traced("pack_mirostat")
     def pack_mirostat(self, inv_t, taus, etas, device):
         """Every row's 1 / temperature, tau (0: off) and eta -> the device records of mirostat_rows and the running target

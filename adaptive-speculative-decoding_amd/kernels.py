@@ -2357,3 +2357,43 @@ def watermark_score(tokens: torch.Tensor, wm: Watermark, row_from: torch.Tensor,
                                     _dev(wm.table, "table", torch.uint8), _dev(out, "out", torch.int32), _stream())
     B.check("asd_watermark_score", rc)
     return out
+
+
+# ------------------------------------------------------------------------------- prompt-lookup drafting (prompt_lookup_num_tokens)
+def lookup_propose(tokens: torch.Tensor, seq_len: torch.Tensor, start: int, max_len: int, tok: torch.Tensor, matched: torch.Tensor,
+                   max_ngram: int = 3, min_ngram: int = 1, row_start: Optional[torch.Tensor] = None,
+                   counter: Optional[torch.Tensor] = None, onehot: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The K = tok.shape[1] proposals of every row from its own history (asd_lookup_propose, one launch) -> `tok`.  With
+    H = tokens[b, row_start[b]:seq_len[b]] (row_start None: `start`; both clamped as the n-gram kernel clamps them) the winner
+    e* is the position in [1, len - 1] whose preceding tokens match the longest run (at most max_ngram) of H's last tokens, the
+    most recent among equals; where that run has at least min_ngram tokens, tok[b, i] = H[e* + i mod (len - e*)], otherwise
+    H[-1] (0 for an empty history).  matched i32 [B]: the winner's match length, or 0; counter i32 [B] or None:
+    counter[b] += matched[b] > 0.  tokens i32 [B, >= max_len] contiguous; tok i32 [B, K] with unit stride along K, read (with
+    `onehot`) and written.  onehot [B, K, V] bf16 / f16 / f32 with unit stride along V, or None: the launch stores -inf at
+    (b, i, the previous tok[b, i]) and 0 at (b, i, the new one), which keeps rows filled with -inf once (and a `tok` filled with
+    -1) the one-hot draft rows of the proposals."""
+    if tokens.dim() != 2 or not 0 <= int(start) <= int(max_len) <= tokens.shape[1]:
+        raise ValueError(f"tokens must be int32 [B, >= max_len] and 0 <= start <= max_len, got {tuple(tokens.shape)}, {start}, {max_len}")
+    Bv = tokens.shape[0]
+    if not tok.is_cuda or tok.dtype != torch.int32 or tok.dim() != 2 or tok.shape[0] != Bv or (tok.shape[1] > 1 and tok.stride(1) != 1):
+        raise ValueError("tok must be a CUDA int32 [B, K] tensor with unit stride along K")
+    Kp = tok.shape[1]
+    ld_tok = tok.stride(0) if Bv > 1 else Kp
+    for name, t in (("seq_len", seq_len), ("matched", matched), ("row_start", row_start), ("counter", counter)):
+        if t is not None and tuple(t.shape) != (Bv,):
+            raise ValueError(f"{name} must be int32 [{Bv}]")
+    dtype = ld_seq = ld_row = V = 0
+    if onehot is not None:
+        if not onehot.is_cuda or onehot.dtype not in _DTYPE_CODE or onehot.dim() != 3 or tuple(onehot.shape[:2]) != (Bv, Kp) or \
+                (onehot.shape[2] > 1 and onehot.stride(2) != 1):
+            raise ValueError("onehot must be a bf16 / f16 / f32 CUDA [B, K, V] tensor with unit stride along V")
+        V = onehot.shape[2]
+        ld_seq, ld_row = _logit_strides(onehot, Kp, "K")
+        dtype = _DTYPE_CODE[onehot.dtype]
+    rc = _lib().asd_lookup_propose(_dev(tokens, "tokens", torch.int32), tokens.shape[1], _opt(row_start, "row_start", torch.int32),
+                                   _dev(seq_len, "seq_len", torch.int32), Bv, int(start), int(max_len), Kp, int(max_ngram),
+                                   int(min_ngram), tok.data_ptr(), ld_tok, _dev(matched, "matched", torch.int32),
+                                   _opt(counter, "counter", torch.int32), None if onehot is None else onehot.data_ptr(), dtype,
+                                   ld_seq, ld_row, V, _stream())
+    B.check("asd_lookup_propose", rc)
+    return tok

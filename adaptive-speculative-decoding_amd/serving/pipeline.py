@@ -53,6 +53,8 @@ configuration only: a value that is set is handed to every stage's generate call
 serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
 `PipelineConfig.watermark_key` / `watermark_delta` / `watermark_gamma` / `watermark_context` (the green-list text watermark;
 serving/stages.py, WATERMARK) likewise: every stage then biases the same green lists, so accepted drafts stay watermarked.
+`PipelineConfig.prompt_lookup_num_tokens` / `prompt_lookup_max_ngram` / `prompt_lookup_min_ngram` (prompt-lookup drafting;
+serving/stages.py, PROMPT LOOKUP) likewise: every stage then speculates against itself and no stage runs the one below as a draft.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -256,6 +258,11 @@ class PipelineConfig:
     watermark_delta: Optional[float] = None
     watermark_gamma: Optional[float] = None
     watermark_context: Optional[int] = None
+    # prompt-lookup drafting, handed to stage.generate(prompt_lookup_num_tokens=, prompt_lookup_max_ngram=, prompt_lookup_min_ngram=);
+    # None: the keyword is not passed (serving/stages.py, PROMPT LOOKUP)
+    prompt_lookup_num_tokens: Optional[int] = None
+    prompt_lookup_max_ngram: Optional[int] = None
+    prompt_lookup_min_ngram: Optional[int] = None
     # vLLM's prompt_logprobs (serving/stages.py, PROMPT LOG-PROBS), handed to every stage.generate(prompt_logprobs=): each
     # stage's entry then carries "prompt_logprobs" and "prompt_ranks"; not fed to the predictor.  None: the keyword is not passed
     prompt_logprobs: Optional[int] = None
@@ -304,7 +311,8 @@ class PipelineConfig:
         for name, kind in (("dry_multiplier", float), ("dry_base", float), ("dry_allowed_length", int), ("dry_range", int)):
             if sec.get(name) is not None:
                 kw[name] = kind(sec[name])
-        for name, kind in (("watermark_key", int), ("watermark_delta", float), ("watermark_gamma", float), ("watermark_context", int)):
+        for name, kind in (("watermark_key", int), ("watermark_delta", float), ("watermark_gamma", float), ("watermark_context", int),
+                           ("prompt_lookup_num_tokens", int), ("prompt_lookup_max_ngram", int), ("prompt_lookup_min_ngram", int)):
             if sec.get(name) is not None:
                 kw[name] = kind(sec[name])
         if sec.get("dry_sequence_breakers") is not None:
@@ -668,7 +676,8 @@ class AdaptiveSpeculativePipeline:
                              "mirostat_tau", "mirostat_eta",                     # ... and Mirostat
                              "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",     # ... and the relative cuts
                              "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve",    # ... and the shaping
-                             "watermark_key", "watermark_delta", "watermark_gamma", "watermark_context"):    # ... and the watermark
+                             "watermark_key", "watermark_delta", "watermark_gamma", "watermark_context",     # ... and the watermark
+                             "prompt_lookup_num_tokens", "prompt_lookup_max_ngram", "prompt_lookup_min_ngram"):   # ... and prompt lookup
                     if getattr(cfg, name) is not None:
                         stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:

@@ -17,6 +17,7 @@ MAX_LOGIT_EDITS = 1024                       # ASD_MAX_LOGIT_EDITS: (id, bias, u
 MAX_BAD_WORDS = 256                          # ASD_MAX_BAD_WORDS: distinct words of one row (BAD WORDS)
 MAX_BAD_WORD_LEN = 8                         # ASD_MAX_BAD_WORD_LEN
 MAX_NGRAM = 8                                # ASD_MAX_NGRAM: the largest no_repeat_ngram_size (NO REPEAT N-GRAM)
+MAX_LOOKUP_TOKENS, MAX_LOOKUP_NGRAM = 16, 8  # ASD_MAX_LOOKUP_TOKENS, ASD_MAX_LOOKUP_NGRAM: prompt_lookup_num_tokens / _max_ngram (PROMPT LOOKUP)
 DRY_MAX_MATCH = 64                           # ASD_DRY_MAX_MATCH: the longest match DRY measures, and the largest dry_allowed_length (DRY)
 MAX_DRY_BREAKERS = 32                        # ASD_MAX_DRY_BREAKERS: distinct sequence-breaker ids of a call
 MAX_LOGIT_BIAS = 100.0                      # |bias| <= 100, the range OpenAI documents
@@ -635,6 +636,27 @@ def check_watermark(key, delta, gamma, context, n: int, named: bool = False):
     if named and all(k is None for k in cols[0]):
         raise ValueError("watermark_delta, watermark_gamma and watermark_context need a watermark_key on some row")
     return tuple(cols)
+
+
+def check_prompt_lookup(num_tokens, max_ngram, min_ngram, named: bool = False) -> Optional[Tuple[int, int, int]]:
+    """generate's `prompt_lookup_num_tokens` (K: an int in [0, MAX_LOOKUP_TOKENS], 0 = off), `prompt_lookup_max_ngram` (N: an int
+    in [1, MAX_LOOKUP_NGRAM]) and `prompt_lookup_min_ngram` (an int in [1, N]) -> (K, N, n0), or None when K is 0.  Each is ONE
+    value per call: K shapes the step.  `named`: the call itself names a max or min n-gram; with K == 0 that is an error, as
+    are a bool, a float, a sequence, a value outside its range and min above max: ValueError."""
+    out = []
+    for name, v, lo, hi in (("prompt_lookup_num_tokens", num_tokens, 0, MAX_LOOKUP_TOKENS),
+                            ("prompt_lookup_max_ngram", max_ngram, 1, MAX_LOOKUP_NGRAM),
+                            ("prompt_lookup_min_ngram", min_ngram, 1, MAX_LOOKUP_NGRAM)):
+        if not _is_int(v) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be one integer in [{lo}, {hi}] for the call, got {v!r}")
+        out.append(int(v))
+    if out[2] > out[1]:
+        raise ValueError(f"prompt_lookup_min_ngram ({out[2]}) must not exceed prompt_lookup_max_ngram ({out[1]})")
+    if out[0] == 0:
+        if named:
+            raise ValueError("prompt_lookup_max_ngram and prompt_lookup_min_ngram need prompt_lookup_num_tokens > 0")
+        return None
+    return tuple(out)
 
 
 def merge_logit_edits(bias: List[Dict[int, float]], banned: List[Tuple[int, ...]], min_tokens: List[int],

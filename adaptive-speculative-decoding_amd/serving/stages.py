@@ -573,6 +573,40 @@ any launch and before the prompts are encoded: a bool, a NaN, a value outside it
 or context named in a call that has no key on any row.  NOT BUILT: HF's `selfhash` seeding scheme, `ignore_repeated_ngrams`
 in detection, SynthID, context widths above 3, p-values, and serving/hierarchy.py's loop.
 
+PROMPT LOOKUP.  `generate(prompt_lookup_num_tokens=, prompt_lookup_max_ngram=, prompt_lookup_min_ngram=)` (or the StageConfig
+fields of those names; None takes the configuration's value) is HF generate's `prompt_lookup_num_tokens` and vLLM's `ngram`
+method: a proposer that needs no draft model.  K = prompt_lookup_num_tokens is 0 (off) or 1..16, N = prompt_lookup_max_ngram
+1..8 (3) and n0 = prompt_lookup_min_ngram 1..N (1) -- ONE value per call each, not one per prompt: K shapes the step.  THE RULE
+(include/asd_hip.h, PROMPT LOOKUP): for row b let H = tokens[b, row_start[b]:seq_len[b]] -- the real prompt ids without the
+left-padding, then the committed tokens -- and len = |H|.  For every e in [1, len - 1], m(e) is the number of
+k = 0, 1, .. < min(e, N) with H[e-1-k] == H[len-1-k], counted until the first failure: H[e] is the token that followed an
+earlier occurrence of the suffix, and e <= len - 1 keeps the suffix from matching itself.  The winner e* maximises (m(e), e):
+the longest match, then the most recent one; it is valid when m(e*) >= n0.  With a valid winner and p = len - e*, proposal i is
+H[e* + (i mod p)] for i < K -- an overlapping copy, so a loop of period p is proposed whole; without one every proposal is
+H[len-1] (token 0 for an empty history).  Every row always gets K proposals: speculative sampling is lossless for ANY
+deterministic proposal -- it is a draft distribution with mass 1 on one token, log q = 0 -- so padding costs nothing but a
+rejected slot.  THE LOOP is `_decode_lookup`, at any stage when K > 0 (stage 0 then no longer takes `_decode_plain`): it is
+`_decode_speculative` with this stage's own model as the target and NO draft model call -- a verifying stage does not run the
+stage below for the call.  The prefill covers all but the last prompt token; per step ONE ops.lookup_propose launch
+(asd_lookup_propose: a 1024-lane workgroup per row scans the history in 16-byte vectors straight from L2) writes the [B, K]
+proposals into `step_tok` and, on the sampled routes, keeps the [B, K, V] ONE-HOT DRAFT ROWS by two element stores per proposal
+(-inf at the previous proposal, 0 at the new one; filled with -inf once per call); the model scores [t_{L-1}, proposals] at L - 1
+in one pass; the target-side processors run on the K + 1 rows in `_decode_speculative`'s order from the same `step_tok` history
+(mask -> bad words -> n-gram -> edit -> penalties -> DRY -> watermark -> relative cut -> entropy cut -> shaping -> Mirostat); then
+`sampler.settle` and the commits.  The samplers' `lookup` stands where `propose` stood: greedy needs nothing; the sampled
+routes record lp_d = 0, thresholds of -inf (the whole draft row, an untruncated draft's) and the one-hot rows as the draft
+rows, so the existing verify and residual kernels serve the deterministic draft unchanged: u < p_t(tok) accepts, and a
+rejection draws from p_t with the proposal removed.  No draft uniform is consumed.  The draft-side processors (the draft
+stage's configured cuts and shaping) have no rows to act on and are off.  Buffers sized by draft_len elsewhere (`step_tok`, the
+seeded uniforms, XTC's coins) are sized by the call's K.  RESULTS: the text's distribution, log-probs, tables and statistics
+are those of the call without the keyword; stats["steps"] falls; stats["lookup_matched_steps"][i] is the kernel's counter for
+row i -- the steps in which its suffix had a valid match, counted over EVERY step the call ran, those behind the row's own end
+included; the key is absent when lookup is off.  ValueError in `_plan`, before any launch: a bool, a float or a sequence; a
+value outside its range; min above max; a max or min n-gram named while prompt_lookup_num_tokens resolves to 0; a guided row
+(guided_fsm / guided_choice) together with lookup -- the automaton's advance is only defined on tokens it allows.  NOT BUILT:
+guided rows with lookup, a per-prompt K, suffix-automaton or hash-indexed matching, lookup proposals combined with a draft
+model's in one step, and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -594,7 +628,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_prompt_lookup, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -680,6 +714,9 @@ class StageConfig:
     watermark_delta: float = 2.0             # in (0, 100]: what a green token's logit gains
     watermark_gamma: float = 0.25            # in (0, 1): the green share of the vocabulary
     watermark_context: int = 1               # 1..3: the tokens in front of a position that seed its green list
+    prompt_lookup_num_tokens: int = 0        # 0: off; 1..16: K proposals per step from the row's own history (module docstring, PROMPT LOOKUP)
+    prompt_lookup_max_ngram: int = 3         # 1..8: the longest suffix that is searched
+    prompt_lookup_min_ngram: int = 1         # 1..max: the shortest match that counts
     guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
     guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
     prompt_logprobs: Optional[int] = None    # None: off; 0..8: the prompt tokens' log-probs and ranks, and a top-N table (PROMPT LOG-PROBS)
@@ -721,6 +758,7 @@ class _Plan(NamedTuple):
     shape_draft_rows: Optional[list] = None  # a verifying stage: every row's (mode, T, a, b) of the draft stage's configured shaping
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
     watermark: Optional[tuple] = None        # every row's key (None: off), delta, gamma and context width; None: every row off
+    lookup: Optional[tuple] = None           # (K, max n-gram, min n-gram) of prompt-lookup drafting; None: off
 
 
 class _EditState:
@@ -869,6 +907,31 @@ def _watermark_entry(n: int, g: int, thr: int) -> Dict[str, object]:
     """The detector's answer for one text: z = (g - gamma' n) / sqrt(n gamma' (1 - gamma')) in f64, gamma' = thr / 65536."""
     gamma = thr / 65536.0
     return {"n_scored": n, "n_green": g, "z": (g - gamma * n) / float(np.sqrt(n * gamma * (1.0 - gamma))) if n > 0 else float("nan")}
+
+
+class _LookupState:
+    """What a generate call with prompt_lookup_num_tokens > 0 keeps: the index of every row's first real prompt id (uploaded
+    once), the call's [B, K] proposal buffer (`step_tok`, filled with -1 once), the match length of the last step, the per-row
+    counter of steps with a match and, on the sampled routes, the [B, K, V] one-hot draft rows (filled with -inf once).
+    `propose` is the loop's one launch per step (module docstring, PROMPT LOOKUP)."""
+
+    def __init__(self, ops, lookup, prompt_ids, P: int, cap: int, step_tok: torch.Tensor, V: int, dtype, device):
+        self.ops, self.P, self.cap, self.tok = ops, int(P), int(cap), step_tok
+        (self.K, self.max_ngram, self.min_ngram), B = lookup, step_tok.shape[0]
+        self.row_start = torch.tensor([P - len(r) for r in prompt_ids], dtype=torch.int32).to(device)
+        self.matched = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.counter = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.onehot = None if dtype is None else torch.full((B, self.K, V), float("-inf"), dtype=dtype, device=device)
+
+    def propose(self, tokens: torch.Tensor, seq_len: torch.Tensor) -> torch.Tensor:
+        """-> the step's proposals, int32 [B, K], from the real prompt ids and the committed tokens of every row."""
+        return self.ops.lookup_propose(tokens, seq_len, self.P, self.cap, self.tok, self.matched, self.max_ngram, self.min_ngram,
+                                       self.row_start, self.counter, self.onehot)
+
+    def stats(self) -> Dict[str, object]:
+        """{"lookup_matched_steps": per row, the steps of the call in which the row's suffix had a valid match} -- counted over
+        every step the call ran, the ones behind the row's own end included."""
+        return {"lookup_matched_steps": [int(c) for c in self.counter.cpu().numpy()]}
 
 
 class _CutState:
@@ -1176,6 +1239,9 @@ class _Greedy:
     def propose(self, dl, k: int):
         return self.ops.verify_greedy(dl, None, 1.0)[2]
 
+    def lookup(self, onehot):
+        pass                                     # (greedy keeps no draft rows: the proposals are compared with the arg-max)
+
     def settle(self, t_out, tok32):
         self.read = t_out, tok32
         out = self.out = self.ops.verify_greedy(t_out, tok32, 1.0)
@@ -1195,7 +1261,7 @@ class _Sampled:
 
     def __init__(self, stage: "Stage", plan: _Plan, B: int, device):
         self.ops, self.gen, self.inv_t, self.stage = stage.ops, stage.gen, plan.inv_t, stage.index
-        self.K = 0 if stage.draft is None else stage.config.draft_len
+        self.K = plan.lookup[0] if plan.lookup else 0 if stage.draft is None else stage.config.draft_len
         # XTC on a row of the call: one coin per logits position of the step (RELATIVE CUTS), K + 1 at a verifying stage
         self.k_coin = self.K + 1 if plan.rel_rows and any(m == RELCUT_XTC for m, _, _ in plan.rel_rows) else 0
         self.coin, self.B = None, B
@@ -1210,6 +1276,7 @@ class _Sampled:
         self.prop = plan.scalars if dcfg is None else (dcfg.top_k, dcfg.top_p, dcfg.min_p)
         self.none_accepted = torch.zeros((B,), dtype=torch.int32, device=device) if dcfg is None else None
         self.rd = self.u = self.r = None         # a seeded call: the step's uniforms (start)
+        self.look = self.look_const = None       # a lookup step: (lp_d, d_thr, the one-hot draft rows) (lookup)
 
     def _uniforms(self, step: int, k_draft: int, k_accept: int, commit: bool):
         """-> (r_draft [k_draft, B] | None, u [B, k_accept] | None, r_commit [B] | None), valid until the next step."""
@@ -1224,6 +1291,7 @@ class _Sampled:
         elif self.k_coin:                        # unseeded: the step's coins first, one torch.rand on the stage's generator
             self.coin = torch.rand((self.B, self.k_coin), generator=self.gen, device=self.gen.device)
         self.lpd, self.thrs, self.dls = [], [], []
+        self.look = None
 
     def coins(self, step: int, B: int, device):
         """Stage 0, at the top of a step and only with XTC on: the step's coin per row, [B, 1].  Seeded, this is the step's
@@ -1253,16 +1321,27 @@ class _Sampled:
         self.dls.append(dl)                      # kept (edited) for the residual distribution at a rejection
         return tok
 
+    def lookup(self, onehot):
+        """A step whose proposals are prompt lookups: a deterministic proposal is a draft distribution with mass 1 on one
+        token, so lp_d = 0, the thresholds keep the whole draft row (-inf, an untruncated draft's) and the draft rows are the
+        kernel's one-hot rows [B, K, V]; `settle` then runs as behind `propose`.  No draft uniform is consumed."""
+        if self.look_const is None:              # the step's constants, made once per call
+            B, Kd = onehot.shape[:2]
+            self.look_const = (torch.zeros((B, Kd), dtype=torch.float32, device=onehot.device),
+                               torch.full((B, Kd), float("-inf"), dtype=torch.float32, device=onehot.device), onehot)
+        self.look = self.look_const
+
     def settle(self, t_out, tok32):
         B, Kd = tok32.shape
-        lp_d = torch.stack(self.lpd, 1).contiguous()
-        d_thr = torch.stack(self.thrs, 1).contiguous()
+        lp_d, d_thr, d_rows = self.look if self.look is not None else \
+            (torch.stack(self.lpd, 1).contiguous(), torch.stack(self.thrs, 1).contiguous(), None)
         score = t_out[:, :Kd].contiguous()
         bonus = t_out[:, Kd].contiguous()
         u = torch.rand((B, Kd), generator=self.gen, device=t_out.device) if self.seeds is None else self.u
         lp_t, n_acc, t_thr = self._verify_op(score, tok32, lp_d, u)
         r = torch.rand((B,), generator=self.gen, device=t_out.device) if self.seeds is None else self.r
-        d_rows = torch.stack(self.dls, 1).to(score.dtype).contiguous()
+        if d_rows is None:
+            d_rows = torch.stack(self.dls, 1).to(score.dtype).contiguous()
         drawn, lp_drawn = self._residual_op(score, d_rows, n_acc, r, bonus, d_thr, t_thr)
         self.last = (score, bonus, tok32, lp_d, u, lp_t, n_acc, drawn, lp_drawn, t_thr)
         return lp_t, n_acc, drawn, lp_drawn
@@ -1353,10 +1432,11 @@ class _CallState:
         self.edit = _EditState(ops, plan.edit_rows, P, dev) if any(plan.edit_rows) else None
         history = any(plan.bad_rows) or any(plan.ngram_rows) or bool(plan.penalties) or plan.fsm is not None or plan.dry is not None \
             or plan.watermark is not None
-        self.step_tok = torch.zeros((B, stage.config.draft_len), dtype=torch.int32, device=dev) \
-            if history and stage.draft is not None else None
-        self.fsm = _FsmState(ops, plan.fsm, 1 if stage.draft is None else stage.config.draft_len + 1, self.step_tok, dev) \
-            if plan.fsm is not None else None
+        # a lookup call is shaped by its own K at every stage; its proposals are written to step_tok by the kernel itself
+        k_step = plan.lookup[0] if plan.lookup else 0 if stage.draft is None else stage.config.draft_len
+        self.step_tok = torch.zeros((B, k_step), dtype=torch.int32, device=dev) if history and k_step and not plan.lookup else \
+            torch.full((B, k_step), -1, dtype=torch.int32, device=dev) if plan.lookup else None
+        self.fsm = _FsmState(ops, plan.fsm, k_step + 1, self.step_tok, dev) if plan.fsm is not None else None
         self.bad = _BadWordState(ops, plan.bad_rows, P, P + plan.max_tokens, self.step_tok, dev) if any(plan.bad_rows) else None
         self.ngram = _NgramState(ops, plan.ngram_rows, prompt_ids, P, P + plan.max_tokens, self.step_tok, dev) \
             if any(plan.ngram_rows) else None
@@ -1382,6 +1462,8 @@ class _CallState:
         # shaping, by the same two sides; the records carry the rows' temperatures themselves
         self.shape = _ShapeState(ops, plan.shape_rows, dev) if plan.shape_rows else None
         self.shape_draft = _ShapeState(ops, plan.shape_draft_rows, dev) if plan.shape_draft_rows else None
+        self.lookup = _LookupState(ops, plan.lookup, prompt_ids, P, P + plan.max_tokens, self.step_tok, stage.shape.vocab,
+                                   None if plan.greedy else stage.config.dtype, dev) if plan.lookup else None
 
 
 def _shape_of(cfg: StageConfig) -> LMShape:
@@ -1422,6 +1504,7 @@ class Stage:
         check_logit_shapes(config.target_dynatemp_range, config.target_dynatemp_exponent, config.target_smoothing_factor,
                            config.target_smoothing_curve, 1)
         check_watermark(config.watermark_key, config.watermark_delta, config.watermark_gamma, config.watermark_context, 1)
+        check_prompt_lookup(config.prompt_lookup_num_tokens, config.prompt_lookup_max_ngram, config.prompt_lookup_min_ngram)
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -1480,7 +1563,8 @@ class Stage:
                  dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None,
                  smoothing_curve=None,
                  watermark_key=None, watermark_delta=None, watermark_gamma=None,
-                 watermark_context=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 watermark_context=None, prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None,
+                 prompt_lookup_min_ngram=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1643,7 +1727,18 @@ class Stage:
         same history, directly behind DRY and ahead of every cut, under greedy decoding too, and log-probs, top-N tables and
         token statistics describe the biased distribution.  stats["watermark"][i] = {"n_scored", "n_green", "z"} over row
         i's generated tokens, None for a row without a key.  A bool, a NaN, a value outside its range, the wrong length, and
-        a delta, gamma or context named without a key on any row raise ValueError (module docstring, WATERMARK)."""
+        a delta, gamma or context named without a key on any row raise ValueError (module docstring, WATERMARK).
+        `prompt_lookup_num_tokens` (None = StageConfig.prompt_lookup_num_tokens; 0 = off, 1..16), `prompt_lookup_max_ngram`
+        (1..8) and `prompt_lookup_min_ngram` (1..max), ONE value per call each: prompt-lookup drafting (HF's
+        prompt_lookup_num_tokens, vLLM's ngram method).  Every step proposes K = prompt_lookup_num_tokens tokens per row --
+        what followed the most recent, longest earlier occurrence of the row's last max_ngram .. min_ngram tokens in its
+        real prompt ids and committed tokens -- and THIS stage's model verifies them in one pass: stage 0 then commits up
+        to K + 1 tokens per model pass, and a verifying stage does not run its draft stage's model at all.  The text's
+        distribution, every log-prob, table and statistic stay those of the call without the keyword (lossless).
+        stats["lookup_matched_steps"][i]: the steps in which row i's suffix had a match, counted over EVERY step the call ran
+        (a row that ended early keeps being counted); absent when lookup is off.  A bool, a float, a sequence, a value
+        outside its range, min above max, an n-gram named while the number of tokens resolves to 0, and a guided row
+        together with lookup raise ValueError (module docstring, PROMPT LOOKUP)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1654,7 +1749,8 @@ class Stage:
                           typical_p, epsilon_cutoff, eta_cutoff, dry_multiplier, dry_base, dry_allowed_length, dry_range,
                           dry_sequence_breakers, mirostat_tau, mirostat_eta, top_n_sigma, top_a, xtc_threshold,
                           xtc_probability, dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve,
-                          watermark_key, watermark_delta, watermark_gamma, watermark_context)
+                          watermark_key, watermark_delta, watermark_gamma, watermark_context, prompt_lookup_num_tokens,
+                          prompt_lookup_max_ngram, prompt_lookup_min_ngram)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1662,10 +1758,10 @@ class Stage:
         P = ids.shape[1]
         if any(plan.ngram_rows):                 # (the one check that needs the prompts' lengths: host lists, nothing launched yet)
             check_ngram_rows_keep_a_token(plan.ngram_rows, [len(r) for r in prompt_ids], plan.limits,
-                                          0 if self.draft is None else self.config.draft_len, plan.mask_rows, plan.edit_rows,
+                                          plan.lookup[0] if plan.lookup else 0 if self.draft is None else self.config.draft_len, plan.mask_rows, plan.edit_rows,
                                           plan.bad_rows, self.shape.vocab)
         state = _CallState(self, plan, ids, prompt_ids)
-        decode = self._decode_plain if self.draft is None else self._decode_speculative
+        decode = self._decode_lookup if plan.lookup else self._decode_plain if self.draft is None else self._decode_speculative
         tokens, lps, seq_len = decode(ids, plan.max_tokens, state)
         self.ops.check_status()
         feats = None if state.stats is None else state.stats.features(P, seq_len, plan.prompts, self.index)   # before any read-back
@@ -1687,6 +1783,8 @@ class Stage:
             stats.update(state.miro.stats(P, n_tok))
         if state.wm is not None:
             stats.update(state.wm.stats(tokens, P, n_tok))
+        if state.lookup is not None:
+            stats.update(state.lookup.stats())
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     @torch.no_grad()
@@ -1727,7 +1825,8 @@ class Stage:
               dry_allowed_length=None, dry_range=None, dry_sequence_breakers=None, mirostat_tau=None,
               mirostat_eta=None, top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None,
               dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None, smoothing_curve=None,
-              watermark_key=None, watermark_delta=None, watermark_gamma=None, watermark_context=None) -> _Plan:
+              watermark_key=None, watermark_delta=None, watermark_gamma=None, watermark_context=None,
+              prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None, prompt_lookup_min_ngram=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1799,6 +1898,12 @@ class Stage:
         watermark = check_watermark(given(watermark_key, cfg.watermark_key), given(watermark_delta, cfg.watermark_delta),
                                     given(watermark_gamma, cfg.watermark_gamma), given(watermark_context, cfg.watermark_context), n,
                                     any(v is not None for v in (watermark_delta, watermark_gamma, watermark_context)))
+        lookup = check_prompt_lookup(given(prompt_lookup_num_tokens, cfg.prompt_lookup_num_tokens),
+                                     given(prompt_lookup_max_ngram, cfg.prompt_lookup_max_ngram),
+                                     given(prompt_lookup_min_ngram, cfg.prompt_lookup_min_ngram),
+                                     prompt_lookup_max_ngram is not None or prompt_lookup_min_ngram is not None)
+        if lookup is not None and fsm is not None:   # (the automaton's advance is only defined on tokens it allows)
+            raise ValueError("prompt_lookup_num_tokens > 0 is not built for a guided row (guided_fsm / guided_choice)")
         own_miro = (cfg.mirostat_tau, cfg.mirostat_eta) if self.draft is None else (cfg.target_mirostat_tau, cfg.target_mirostat_eta)
         miro_rows = check_mirostat(given(mirostat_tau, own_miro[0]), given(mirostat_eta, own_miro[1]), n, mirostat_eta is not None)
         own_rel = (cfg.top_n_sigma, cfg.top_a, cfg.xtc_threshold, cfg.xtc_probability) if self.draft is None else \
@@ -1820,6 +1925,8 @@ class Stage:
         # the draft rows take the DRAFT stage's configured shaping (per-request draft-side values: NOT BUILT)
         shape_draft_rows = [] if dcfg is None else check_logit_shapes(dcfg.dynatemp_range, dcfg.dynatemp_exponent,
                                                                       dcfg.smoothing_factor, dcfg.smoothing_curve, n)
+        if lookup is not None:                   # no draft rows: the draft stage's configured cuts and shaping have nothing to act on
+            cut_draft_rows, rel_draft_rows, shape_draft_rows = [], [], []
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -1850,6 +1957,7 @@ class Stage:
                      cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
                      dry=dry if any(m > 0.0 for m in dry[0]) else None,           # every row off: no state, no call
                      watermark=watermark if any(k is not None for k in watermark[0]) else None,   # no key: no state, no call
+                     lookup=lookup,
                      rel_rows=rel_rows if not greedy and any(m for m, _, _ in rel_rows) else None,     # greedy ignores the cuts
                      shape_rows=shape_rows if not greedy and any(r[0] for r in shape_rows) else None,  # ... and the shaping
                      shape_draft_rows=shape_draft_rows if not greedy and any(r[0] for r in shape_draft_rows) else None,
@@ -2070,6 +2178,94 @@ class Stage:
             if fsm is not None:
                 fsm.commit(tokens, seq_len, n_commit, cap)               # ... and move the automaton
             if kept is not None:                                        # tests: the record, with the top-N rows behind it
+                if top is not None:
+                    kept = dict(kept, **top.record(), n_commit=n_commit.clone())
+                self.step_inputs.append(kept if stat is None else dict(kept, **stat.record(), n_commit=n_commit.clone()))
+            steps += 1
+            if steps % cfg.sync_every == 0 and end.done(seq_len, cap):
+                break
+            if steps > max_tokens + cfg.sync_every:      # cannot happen: every step appends >= 1 token per unfinished row
+                raise RuntimeError("stage loop did not terminate")
+        self.last_steps = steps
+        return tokens, lps, seq_len
+
+
+    def _decode_lookup(self, ids: torch.Tensor, max_tokens: int, st: _CallState):
+        """Any stage with prompt_lookup_num_tokens = K > 0 (module docstring, PROMPT LOOKUP): _decode_speculative's step with
+        this stage's own model as the target and ops.lookup_propose in place of the draft model -- at a verifying stage the
+        draft stage's model is not run at all.
+
+        Invariant at the top of a step, L = seq_len[b]: tokens[b, :L] are committed and the model's KV is valid for positions
+        < L - 1, so it is fed [t_{L-1}, d_0 .. d_{K-1}] at position L - 1 (row i scores d_i, row K is the bonus row).  The
+        target-side processors run on the K + 1 rows in _decode_speculative's order with the proposals in `step_tok`; the
+        draft-side ones have no rows to act on."""
+        cfg, target, look = self.config, self.model, st.lookup
+        B, P = ids.shape
+        dev = ids.device
+        Kd = look.K
+        cap = P + max_tokens
+        end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
+        ngram, stat, cut, dry, miro, rel, shape, wm = st.ngram, st.stats, st.cut, st.dry, st.miro, st.rel, st.shape, st.wm
+        tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
+        target.reset()
+        target.alloc_ragged(B, cap + Kd + 2)
+        prefill = target.forward_ragged(ids[:, :P - 1], torch.zeros((B,), dtype=torch.int64, device=dev), P)   # all but the last prompt token
+        if st.prompt is not None:
+            self.prompt_inputs = st.prompt.score(prefill, self.keep_inputs)
+        del prefill
+        rows = torch.arange(B, device=dev)
+        steps = 0
+        while True:
+            L = seq_len.to(torch.int64)
+            window = min(P + steps * (Kd + 1) + Kd + 1, cap + Kd + 2)   # host-side bound on every position touched this step
+            sampler.start(steps)
+            tok32 = look.propose(tokens, seq_len)                       # ONE launch: step_tok, and the one-hot draft rows
+            sampler.lookup(look.onehot)
+            t_out = target.forward_ragged(torch.cat([tokens[rows, L - 1][:, None], tok32], 1).to(torch.int64), L - 1, window)   # [B, K+1, V]
+            if mask is not None:
+                mask.apply(t_out)
+            if bad is not None:
+                bad.apply(t_out, tokens, seq_len)                       # row j sees the proposals 0 .. j - 1
+            if ngram is not None:
+                ngram.apply(t_out, tokens, seq_len)
+            if edit is not None:
+                edit.apply(t_out, seq_len)
+            if pen is not None:
+                pen.apply(t_out)
+            if dry is not None:
+                dry.apply(t_out, tokens, seq_len)
+            if wm is not None:
+                wm.apply(t_out, tokens, seq_len)
+            rel_in = rel.apply(t_out, sampler.coin, self.keep_inputs) if rel is not None else None
+            cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None
+            shape_in = shape.apply(t_out, self.keep_inputs) if shape is not None else None
+            miro_in = miro.apply(t_out, tok32, self.keep_inputs) if miro is not None else None
+            lp_t, n_acc, drawn, lp_drawn = sampler.settle(t_out, tok32)
+            kept = sampler.kept(seq_len) if self.keep_inputs else None
+            if kept is not None:
+                kept.update(lookup_matched=look.matched.clone())
+                if cut is not None:
+                    kept["cut_in"] = cut_in
+                if rel is not None:
+                    kept.update(rel_in=rel_in, rel_coins=None if sampler.coin is None else sampler.coin.clone())
+                if shape is not None:
+                    kept["shape_in"] = shape_in
+                if miro is not None:
+                    kept.update(miro_in=miro_in, mu_path=miro.path.clone())
+            if stat is not None:
+                stat.score(t_out, tok32, n_acc, drawn)
+            elif top is not None:
+                top.score(t_out)
+            end.commit(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            if miro is not None:
+                miro.commit(n_acc, lp_drawn, seq_len, n_commit)
+            if top is not None:
+                top.commit(seq_len, n_commit)
+            if stat is not None:
+                stat.commit(seq_len, n_commit)
+            if pen is not None:
+                pen.commit(tokens, seq_len, n_commit, cap)
+            if kept is not None:
                 if top is not None:
                     kept = dict(kept, **top.record(), n_commit=n_commit.clone())
                 self.step_inputs.append(kept if stat is None else dict(kept, **stat.record(), n_commit=n_commit.clone()))

@@ -1040,6 +1040,50 @@ int asd_watermark_score(const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tok
                         const asd_watermark_rec* recs /*[B]*/, int32_t* out /*[B, 2]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PROMPT LOOKUP: the proposals of a speculative step WITHOUT a draft model -- HF generate's `prompt_lookup_num_tokens`, vLLM's
+ * `ngram` method.  The last tokens of a row are searched earlier in the row's own prompt and output, and what followed them
+ * there is proposed.  The proposal is a deterministic function of the history, so it is a draft distribution that puts mass 1
+ * on one token: log q = 0, and the verify / residual chain stays lossless against the target for ANY such proposal.
+ * History: H = tokens[b][row_start[b] .. L), L = clamp(seq_len[b], start, max_len), row_start[b] clamped into [0, start]
+ * (NULL: `start` for every row) -- asd_no_repeat_ngram_rows' history without proposals: the real prompt ids (not the
+ * left-padding), then the committed tokens.  tokens: int32 rows ld_tokens >= max_len elements apart, only read; nothing
+ * outside tokens[b][row_start[b] .. L) is read.
+ * THE RULE, with len = |H|, N = max_ngram (1..ASD_MAX_LOOKUP_NGRAM), n0 = min_ngram (1..N), K in 1..ASD_MAX_LOOKUP_TOKENS:
+ *     for every e in [1, len-1]:  m(e) = the number of k = 0, 1, .. < min(e, N) with H[e-1-k] == H[len-1-k], counted until
+ *     the first failure -- H[e] is the token that followed an earlier occurrence of the suffix; e <= len-1 keeps the suffix
+ *     from matching itself.
+ *     The winner e* maximises (m(e), e) in lexicographic order: the longest match, then the most recent one.  It is valid
+ *     when m(e*) >= n0.
+ *     With a valid winner and p = len - e*:  tok[b][i] = H[e* + (i mod p)] for i < K (an overlapping copy: a loop of period p
+ *     is proposed whole).  Without one:  tok[b][i] = H[len-1], or 0 when len == 0.  Every row always gets K proposals.
+ *     matched[b] = m(e*), or 0 without a valid winner; counter != NULL: counter[b] += (matched[b] > 0).
+ * THE ONE-HOT DRAFT ROWS (onehot != NULL): element (b, i, v) at b*ld_seq + i*ld_row + v, bf16 / f16 / f32 (`dtype`), [B, K, V].
+ * The launch reads old = tok[b][i] BEFORE it writes the new proposal, stores -inf at (b, i, old) when old is in [0, V), then
+ * stores 0 at (b, i, new) when new is in [0, V).  The caller fills onehot with -inf and tok with -1 once; from then on each
+ * row holds exactly one 0, softmax of it is exactly the one-hot distribution of the proposal, and a step costs 2 B K element
+ * stores.  onehot == NULL (greedy decoding): dtype, ld_seq, ld_row and V are not looked at, and tok is only written.
+ * THE DATA CONTRACT: seq_len[b] and row_start[b] are clamped as above; a token outside [0, V) is compared and proposed as a
+ * plain integer but never used as a store index.
+ * One launch, no workspace: one workgroup of 1024 lanes per row; the history is read in 16-byte vectors straight from L2, four
+ * candidates per lane, ASD_LOOKUP_TILE candidates per pass of the workgroup; a lane compares H[e-1] with the last token first
+ * and only a hit loads the two vectors in front of its own (the halo of N - 1 tokens) and walks backwards; the running best is
+ * one 64-bit key (m << 32) | e per lane, reduced inside each wave and once across the 16 waves through LDS.
+ * Status, in this order: negative B / start / max_len / V, K < 1, max_ngram < 1, min_ngram < 1, min_ngram > max_ngram: invalid
+ * argument; B == 0: ASD_OK, nothing launched; K > ASD_MAX_LOOKUP_TOKENS, max_ngram > ASD_MAX_LOOKUP_NGRAM, onehot with an
+ * unknown dtype, max_len > INT32_MAX - 2*ASD_LOOKUP_TILE: unsupported; NULL tokens / seq_len / tok / matched,
+ * ld_tokens < max_len, start > max_len, ld_tok < K, onehot with V < 1, ld_row < V or ld_seq < K*ld_row: invalid argument;
+ * tokens / row_start / seq_len / tok / matched / counter not aligned to 4, or onehot not aligned to the element size: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_MAX_LOOKUP_TOKENS 16  /* largest K of asd_lookup_propose */
+#define ASD_MAX_LOOKUP_NGRAM 8    /* largest max_ngram of asd_lookup_propose */
+#define ASD_LOOKUP_TILE 4096      /* candidate positions one pass of its workgroup covers: four per lane */
+int asd_lookup_propose(const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_tokens,
+                       const int32_t* row_start /*[B], or NULL: start for every row*/, const int32_t* seq_len /*[B]*/, int B,
+                       int start, int max_len, int K, int max_ngram, int min_ngram, int32_t* tok /*[B, ld_tok] in/out*/,
+                       int64_t ld_tok, int32_t* matched /*[B] out*/, int32_t* counter /*[B] in/out, or NULL*/,
+                       void* onehot /*[B, K, V] in/out, or NULL*/, int dtype, int64_t ld_seq, int64_t ld_row, int V, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /
  * structured-output back ends compile a set of answers, a regex or a schema to.  Inside a speculative step the mask of
  * position j depends on the proposals 0 .. j-1, which exist only on the device: so the state lives there, small kernels

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_dry_rows, asd_watermark_rows, asd_watermark_score, asd_entropy_cut_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_dry_rows, asd_watermark_rows, asd_watermark_score, asd_lookup_propose, asd_entropy_cut_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -811,6 +811,44 @@ int main() {
         EXPECT(STATS(rows + 2, BF16, VS, ldr, B, 1, VS, nullptr, 0, i32, i32, 1.0f, nullptr, NS, 1, i32, f32, i32, f32, p, 255), ASD_ERR_WORKSPACE);   // (K1 == 1: a NULL tok and any ld_tok are valid)
         EXPECT(STATS(p, BF16, static_cast<int64_t>(ASD_MAX_DRAFT_LEN + 1) * VS, ldr, 1 << 20, ASD_MAX_DRAFT_LEN + 1, VS, i32, ASD_MAX_DRAFT_LEN, i32, i32, 1.0f, nullptr, NS, ASD_MAX_SPLITS, i32, f32, i32, f32, p, ws64), ASD_ERR_UNSUPPORTED);   // B*K1*splits > INT32_MAX
 #undef STATS
+    }
+
+    // ---- asd_lookup_propose: sizes and ranges, the empty batch, the upper limits, null pointers, strides, alignment
+    {
+        const int KL = 4, VL = 64, ML = 128;
+        int32_t* odd = reinterpret_cast<int32_t*>(rows + 2);
+#define LOOK(tokens_, ldt_, rs_, seq_, B_, start_, max_len_, K_, N_, n0_, tok_, ldk_, m_, c_, oh_, dt_, lds_, ldr_, V_) \
+    asd_lookup_propose(tokens_, ldt_, rs_, seq_, B_, start_, max_len_, K_, N_, n0_, tok_, ldk_, m_, c_, oh_, dt_, lds_, ldr_, V_, nullptr)
+        EXPECT(LOOK(i32, ML, i32, i32, -1, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);
+        EXPECT(LOOK(i32, ML, i32, i32, B, -1, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, -1, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, 0, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);       // K < 1
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 0, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);      // N < 1
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 0, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);      // n0 < 1
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 4, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);      // n0 > N
+        EXPECT(LOOK(nullptr, 0, nullptr, nullptr, 0, 8, ML, ASD_MAX_LOOKUP_TOKENS + 1, 3, 1, nullptr, 0, nullptr, nullptr, nullptr, 99, 0, 0, 0), ASD_OK);   // B == 0
+        EXPECT(LOOK(nullptr, ML, i32, i32, B, 8, ML, ASD_MAX_LOOKUP_TOKENS + 1, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_UNSUPPORTED);   // K, before pointers
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, ASD_MAX_LOOKUP_NGRAM + 1, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_UNSUPPORTED);
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, 99, KL * VL, VL, VL), ASD_ERR_UNSUPPORTED);        // dtype
+        EXPECT(LOOK(i32, int64_t{1} << 31, i32, i32, B, 8, INT32_MAX, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_UNSUPPORTED);
+        EXPECT(LOOK(nullptr, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);  // tokens
+        EXPECT(LOOK(i32, ML, i32, nullptr, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);  // seq_len
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, nullptr, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);  // tok
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, nullptr, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);  // matched
+        EXPECT(LOOK(i32, ML - 1, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);  // ld_tokens < max_len
+        EXPECT(LOOK(i32, ML, i32, i32, B, ML + 1, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG); // start > max_len
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL - 1, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);  // ld_tok < K
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL - 1, VL), ASD_ERR_INVALID_ARG);  // ld_row < V
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL - 1, VL, VL), ASD_ERR_INVALID_ARG);  // ld_seq < K ld_row
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, 0, 0, 0), ASD_ERR_INVALID_ARG);              // one-hot rows with V == 0
+        EXPECT(LOOK(odd, ML - 1, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_INVALID_ARG);  // ... before alignment
+        EXPECT(LOOK(odd, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_ALIGNMENT);
+        EXPECT(LOOK(i32, ML, odd, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_ALIGNMENT);
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, odd, KL, i32, i32, p, BF16, KL * VL, VL, VL), ASD_ERR_ALIGNMENT);
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, odd, p, BF16, KL * VL, VL, VL), ASD_ERR_ALIGNMENT);
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, rows + 1, BF16, KL * VL, VL, VL), ASD_ERR_ALIGNMENT);
+        EXPECT(LOOK(i32, ML, i32, i32, B, 8, ML, KL, 3, 1, i32, KL, i32, i32, rows + 2, 0 /*f32*/, KL * VL, VL, VL), ASD_ERR_ALIGNMENT);
+#undef LOOK
     }
 
     std::printf(failures ? "asan_host_args: %d failure(s)\n" : "asan_host_args: ok\n", failures);
