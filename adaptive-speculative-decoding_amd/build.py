@@ -48,6 +48,7 @@ SOURCES = {
     "logit_shape.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # relative_cut.hip's flags: sums and a polynomial a reference must be able to bound term by term
     "watermark.hip": ["-ffp-contract=off"],      # integer rounds and one f32 add per green element: nothing to fuse
     "lookup.hip": [],                          # integer compares, a 64-bit max and stores of two constants: no floating-point arithmetic
+    "cfg.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # logit_shape.hip's flags: fl(fl(s c') + fl(t u')) rounds three times, as the header and the reference state it
     "fsm.hip": [],                             # logit_mask.hip's write stream and integer searches: no floating-point arithmetic
     "penalty.hip": ["-ffp-contract=off"],         # y - freq * c must round twice, as the header and the numpy reference state it
     "lm_head_verify.hip": ["-ffp-contract=off"],  # ends in the same finish_row arithmetic as verify_accept.hip

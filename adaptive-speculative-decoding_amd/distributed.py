@@ -616,6 +616,19 @@ class HipOps:
         rows, kept by two element stores per proposal."""
         return self.K.lookup_propose(tokens, seq_len, start, max_len, tok, matched, max_ngram, min_ngram, row_start, counter, onehot)
 
+    @traced("pack_cfg")
+    def pack_cfg(self, scales, uncond, device):
+        """Every row's guidance scale (1: off) and the index of its unconditional sequence (negative: off) -> the device table
+        of cfg_rows (kernels.pack_cfg: one upload per call)."""
+        return self.K.pack_cfg(scales, uncond, device)
+
+    @traced("cfg_rows")
+    def cfg_rows(self, cond, uncond, packed):
+        """Classifier-free guidance ahead of every other processor (asd_cfg_rows, one launch): cond [B, K1, V] <- u' + s (c' - u')
+        in place from the log-softmax of its own rows and of the rows of `uncond` [Bu, K1, V] the records name; `uncond` is only
+        read."""
+        return self.K.cfg_rows(cond, uncond, packed)
+
     @traced("pack_mirostat")
     def pack_mirostat(self, inv_t, taus, etas, device):
         """Every row's 1 / temperature, tau (0: off) and eta -> the device records of mirostat_rows and the running target

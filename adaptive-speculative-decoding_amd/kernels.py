@@ -2397,3 +2397,79 @@ def lookup_propose(tokens: torch.Tensor, seq_len: torch.Tensor, start: int, max_
                                    ld_seq, ld_row, V, _stream())
     B.check("asd_lookup_propose", rc)
     return tok
+
+
+# ------------------------------------------------------------------------------- classifier-free guidance (guidance_scale / negative_prompt)
+_CFG_REC = np.dtype([("scale", np.float32), ("uncond_seq", np.int32)])
+assert _CFG_REC.itemsize == B.CFG_REC_BYTES
+
+
+@dataclass
+class Cfg:
+    """The table of asd_cfg_rows on the device (pack_cfg): B records {scale f32, uncond_seq i32} of 8 bytes, as a uint8 [B, 8]
+    tensor; `uncond`: the host's copy of the rows' unconditional sequences (-1: off), Bu: how many sequences those index."""
+    table: torch.Tensor
+    uncond: Tuple[int, ...]
+    B: int
+    Bu: int
+
+
+def check_cfg_rows(scales, uncond) -> np.ndarray:
+    """The host side of pack_cfg: every row's guidance scale (a number in [0, MAX_GUIDANCE_SCALE] as the f32 the record holds)
+    and the index of its unconditional sequence (an int; negative: the row is off) -> the records, a numpy structured array.
+    A row whose scale is 1 is off and holds index -1 whatever was given."""
+    scales, uncond = list(scales), list(uncond)
+    if len(scales) != len(uncond):
+        raise ValueError(f"{len(scales)} scales and {len(uncond)} indices must describe the same rows")
+    rec = np.zeros(len(scales), dtype=_CFG_REC)
+    for i, (s, q) in enumerate(zip(scales, uncond)):
+        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)):
+            raise ValueError(f"row {i}: the guidance scale must be a number, got {s!r}")
+        s32 = float(np.float32(s))
+        if not 0.0 <= s32 <= B.MAX_GUIDANCE_SCALE:
+            raise ValueError(f"row {i}: the guidance scale must lie in [0, {B.MAX_GUIDANCE_SCALE:g}], got {s!r}")
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or int(q) >= 2 ** 31:
+            raise ValueError(f"row {i}: the unconditional sequence must be an int32 index (negative: off), got {q!r}")
+        rec[i] = (s32, -1 if s32 == 1.0 or int(q) < 0 else int(q))
+    return rec
+
+
+def pack_cfg(scales, uncond, device) -> Cfg:
+    """The table of cfg_rows from host lists, checked BEFORE anything is uploaded."""
+    rec = check_cfg_rows(scales, uncond)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _CFG_REC.itemsize).copy()).to(device)
+    idx = tuple(int(q) for q in rec["uncond_seq"])
+    return Cfg(table, idx, len(rec), max(idx, default=-1) + 1)
+
+
+def cfg_rows(cond: torch.Tensor, uncond: torch.Tensor, packed: Cfg) -> torch.Tensor:
+    """Classifier-free guidance in place over `cond` (asd_cfg_rows, one launch) and return it.  cond [B, V] or [B, K1, V],
+    uncond [Bu, V] or [Bu, K1, V]: bf16 / f16 / f32 of one dtype, any sequence / row strides of their own with unit stride
+    along V; they may be views of one tensor.  Row (b, j) with record {s, q}, q >= 0 and s != 1, becomes
+    fl(fl(s c') + fl(fl(1 - s) u')) with c' = fl(c - Lc), u' = fl(u - Lu) the rows' log-softmax values in f32 and u = row (q, j)
+    of `uncond`; a -inf of c stays, a -inf of u gives c'.  Results are rounded to the dtype to nearest even and clamped to its
+    finite range; a pair with a NaN or +inf element, or without a finite element in either row, is left as it is; `uncond` is
+    never written."""
+    for name, t in (("cond", cond), ("uncond", uncond)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in _DTYPE_CODE:
+            raise ValueError(f"{name} must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    if cond.dim() != uncond.dim() or cond.dtype != uncond.dtype:
+        raise ValueError("cond and uncond must have the same number of dimensions and the same dtype")
+    vc = cond[:, None] if cond.dim() == 2 else cond
+    vu = uncond[:, None] if uncond.dim() == 2 else uncond
+    for name, v in (("cond", vc), ("uncond", vu)):
+        if v.dim() != 3 or (v.shape[2] > 1 and v.stride(2) != 1):
+            raise ValueError(f"{name} must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = vc.shape
+    Bu = vu.shape[0]
+    if tuple(vu.shape[1:]) != (K1, V):
+        raise ValueError(f"uncond must hold rows of the same [K1, V] = [{K1}, {V}] as cond, got {tuple(vu.shape[1:])}")
+    if packed.B != Bv or packed.Bu > Bu:
+        raise ValueError(f"the records were packed for {packed.B} rows over {packed.Bu} unconditional sequences; "
+                         f"cond has {Bv} and uncond {Bu}")
+    ld_seq, ld_row = _logit_strides(vc, K1)
+    ld_useq, ld_urow = _logit_strides(vu, K1) if Bu else (K1 * V, V)
+    rc = _lib().asd_cfg_rows(vc.data_ptr(), _DTYPE_CODE[vc.dtype], Bv, K1, V, ld_seq, ld_row, vu.data_ptr() if Bu else None, Bu,
+                             ld_useq, ld_urow, _dev(packed.table, "table", torch.uint8), _stream())
+    B.check("asd_cfg_rows", rc)
+    return cond

@@ -55,6 +55,8 @@ serving/stages.py, DRY) travel the same way: configuration only, a set value is 
 serving/stages.py, WATERMARK) likewise: every stage then biases the same green lists, so accepted drafts stay watermarked.
 `PipelineConfig.prompt_lookup_num_tokens` / `prompt_lookup_max_ngram` / `prompt_lookup_min_ngram` (prompt-lookup drafting;
 serving/stages.py, PROMPT LOOKUP) likewise: every stage then speculates against itself and no stage runs the one below as a draft.
+`PipelineConfig.guidance_scale` / `negative_prompt` (classifier-free guidance; serving/stages.py, GUIDANCE) likewise: every
+stage's own model is then guided against the same negative prompt, and a verifying stage's draft model proposes unguided.
 
 What the reference's loop does per request (pipeline.py:165-286), and what this one keeps:
   for each stage i:  outputs, logprobs = stage.generate(prompts=[prompt_i], ..., return_logprobs=True)
@@ -263,6 +265,10 @@ class PipelineConfig:
     prompt_lookup_num_tokens: Optional[int] = None
     prompt_lookup_max_ngram: Optional[int] = None
     prompt_lookup_min_ngram: Optional[int] = None
+    # classifier-free guidance, handed to stage.generate(guidance_scale=, negative_prompt=); None: the keyword is not passed
+    # (serving/stages.py, GUIDANCE)
+    guidance_scale: Optional[float] = None
+    negative_prompt: Optional[str] = None
     # vLLM's prompt_logprobs (serving/stages.py, PROMPT LOG-PROBS), handed to every stage.generate(prompt_logprobs=): each
     # stage's entry then carries "prompt_logprobs" and "prompt_ranks"; not fed to the predictor.  None: the keyword is not passed
     prompt_logprobs: Optional[int] = None
@@ -312,7 +318,8 @@ class PipelineConfig:
             if sec.get(name) is not None:
                 kw[name] = kind(sec[name])
         for name, kind in (("watermark_key", int), ("watermark_delta", float), ("watermark_gamma", float), ("watermark_context", int),
-                           ("prompt_lookup_num_tokens", int), ("prompt_lookup_max_ngram", int), ("prompt_lookup_min_ngram", int)):
+                           ("prompt_lookup_num_tokens", int), ("prompt_lookup_max_ngram", int), ("prompt_lookup_min_ngram", int),
+                           ("guidance_scale", float), ("negative_prompt", str)):
             if sec.get(name) is not None:
                 kw[name] = kind(sec[name])
         if sec.get("dry_sequence_breakers") is not None:
@@ -677,7 +684,8 @@ class AdaptiveSpeculativePipeline:
                              "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",     # ... and the relative cuts
                              "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve",    # ... and the shaping
                              "watermark_key", "watermark_delta", "watermark_gamma", "watermark_context",     # ... and the watermark
-                             "prompt_lookup_num_tokens", "prompt_lookup_max_ngram", "prompt_lookup_min_ngram"):   # ... and prompt lookup
+                             "prompt_lookup_num_tokens", "prompt_lookup_max_ngram", "prompt_lookup_min_ngram",    # ... and prompt lookup
+                             "guidance_scale", "negative_prompt"):                           # ... and classifier-free guidance
                     if getattr(cfg, name) is not None:
                         stop_kw[name] = getattr(cfg, name)
                 if cfg.prompt_logprobs is not None:

@@ -18,6 +18,7 @@ MAX_BAD_WORDS = 256                          # ASD_MAX_BAD_WORDS: distinct words
 MAX_BAD_WORD_LEN = 8                         # ASD_MAX_BAD_WORD_LEN
 MAX_NGRAM = 8                                # ASD_MAX_NGRAM: the largest no_repeat_ngram_size (NO REPEAT N-GRAM)
 MAX_LOOKUP_TOKENS, MAX_LOOKUP_NGRAM = 16, 8  # ASD_MAX_LOOKUP_TOKENS, ASD_MAX_LOOKUP_NGRAM: prompt_lookup_num_tokens / _max_ngram (PROMPT LOOKUP)
+MAX_GUIDANCE_SCALE = 100.0                   # ASD_MAX_GUIDANCE_SCALE: the largest guidance_scale (GUIDANCE)
 DRY_MAX_MATCH = 64                           # ASD_DRY_MAX_MATCH: the longest match DRY measures, and the largest dry_allowed_length (DRY)
 MAX_DRY_BREAKERS = 32                        # ASD_MAX_DRY_BREAKERS: distinct sequence-breaker ids of a call
 MAX_LOGIT_BIAS = 100.0                      # |bias| <= 100, the range OpenAI documents
@@ -657,6 +658,32 @@ def check_prompt_lookup(num_tokens, max_ngram, min_ngram, named: bool = False) -
             raise ValueError("prompt_lookup_max_ngram and prompt_lookup_min_ngram need prompt_lookup_num_tokens > 0")
         return None
     return tuple(out)
+
+
+def check_guidance(scale, negative, n: int) -> Optional[Tuple[List[float], List[Optional[str]]]]:
+    """generate's `guidance_scale` (one finite number in [0, MAX_GUIDANCE_SCALE] for the call or one per prompt, held as f32;
+    1 = the row is off) and `negative_prompt` (None, one string for the call, or one string or None per prompt) ->
+    (scales, negatives) with one entry per prompt, or None when every row's scale is 1.  A bool, a NaN, a value out of range,
+    the wrong length, a negative prompt that is no string, and a negative prompt without a row whose scale differs from 1
+    (the mirostat_eta rule): ValueError."""
+    def one(v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not 0.0 <= float(np.float32(v)) <= MAX_GUIDANCE_SCALE:                   # (NaN fails both comparisons)
+            raise ValueError(f"guidance_scale must be a finite number in [0, {MAX_GUIDANCE_SCALE:g}] (1: off) for the call or "
+                             f"one per prompt, got {scale!r}")
+        return float(np.float32(v))
+
+    def text(v):
+        if v is not None and not isinstance(v, str):
+            raise ValueError(f"negative_prompt must be None, one string for the call, or one string or None per prompt, got {negative!r}")
+        return v
+    scales = _per_prompt(scale, n, one, "guidance_scale values")
+    negatives = _per_prompt(negative, n, text, "negative_prompt entries")
+    if all(s == 1.0 for s in scales):
+        if any(v is not None for v in negatives):
+            raise ValueError("negative_prompt needs a row whose guidance_scale differs from 1")
+        return None
+    return scales, negatives
 
 
 def merge_logit_edits(bias: List[Dict[int, float]], banned: List[Tuple[int, ...]], min_tokens: List[int],

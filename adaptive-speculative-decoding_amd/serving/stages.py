@@ -607,6 +607,32 @@ value outside its range; min above max; a max or min n-gram named while prompt_l
 guided rows with lookup, a per-prompt K, suffix-automaton or hash-indexed matching, lookup proposals combined with a draft
 model's in one step, and serving/hierarchy.py's loop.
 
+GUIDANCE.  `generate(guidance_scale=, negative_prompt=)` (StageConfig.guidance_scale is the call's default) is classifier-free
+guidance: HF generate's `guidance_scale` with `negative_prompt_ids`, llama.cpp's / koboldcpp's / ExLlamaV2's cfg-scale with a
+negative prompt.  Every step the stage's model scores the continuation under the prompt (c) and under a negative prompt (u), and
+its logits become g = u' + s (c' - u') with c' = log_softmax(c), u' = log_softmax(u) (include/asd_hip.h, CLASSIFIER-FREE
+GUIDANCE) AHEAD of every other processor.  guidance_scale: one finite number in [0, 100] for the call or one per prompt, held
+as f32; 1: the row is off -- not touched, bit for bit, and without an unconditional context; 0 gives the unconditional
+distribution, values above 1 the usual extrapolation.  negative_prompt: None, one string for the call, or one string or None per
+prompt; it is encoded as prompts are (ids folded into the vocabulary, the last P kept, left-padded with id 0) to the call's own
+P, which the prompts alone decide; None on a guided row: its unconditional context is its prompt's last token alone (HF's
+rule).  THE SECOND CONTEXT rides in the model's own passes: `_GuidedModel` wraps the stage's model behind the three methods the
+loops call -- alloc_ragged(B + Bg rows, Bg the guided rows), forward_ragged(cat(ids, ids_u)) at the guided rows' positions,
+where an unconditional row holds the negative prompt's id at every position below P and the guided row's own token behind it
+(KV roll-back is by position, so it follows the guided row through rejections for free) -- then ONE ops.cfg_rows launch
+(asd_cfg_rows: a 1024-lane workgroup per row pair, both rows out of HBM once, the conditional row held in registers) over the
+[B, K1, V] conditional rows in place, and the first B sequences are returned as a view.  The three loops take `st.model`; with
+guidance off that IS the stage's model and not one call changes.  WHERE IT SITS: the guided row replaces the model's logits, so
+everything downstream -- allow-list, automaton, bans, penalties, DRY, watermark, cuts, shaping, temperature, the draws, top-N
+tables, token statistics and the returned log-probs -- sees it; the history-based processors use the conditional row's history,
+which the committed tokens extend on both contexts alike.  Greedy, sampled, per-request rows, seeds and stop handling are
+unchanged.  At a verifying stage and under prompt lookup the stage's OWN model (the verifier, the lookup loop's target) is
+guided over all K + 1 rows of a pass and the draft model below proposes unguided: lossless either way, since verify and
+residual take whatever target distribution they are given.  ValueError in `_plan`, before any launch: a bool, a NaN, a value
+out of range, the wrong length, a negative prompt that is no string, and a negative prompt without a row whose scale differs
+from 1.  NOT BUILT (ValueError "... is not built"): prompt_logprobs together with guidance, a guided draft model (the draft
+stage's configured guidance_scale != 1); and serving/hierarchy.py's loop.
+
 PROMPTS.  `SimpleTokenizer` ids (folded into the model's vocabulary); each prompt keeps its LAST P ids, where P is the longest
 encoded prompt of the call, capped by `StageConfig.max_prompt_tokens` and at least 2; shorter prompts are LEFT-padded with id 0.
 The synthetic models have no attention mask, so the padding is attended like any other token: that is this build's choice, not
@@ -628,7 +654,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_prompt_lookup, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_guidance, check_prompt_lookup, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -717,6 +743,7 @@ class StageConfig:
     prompt_lookup_num_tokens: int = 0        # 0: off; 1..16: K proposals per step from the row's own history (module docstring, PROMPT LOOKUP)
     prompt_lookup_max_ngram: int = 3         # 1..8: the longest suffix that is searched
     prompt_lookup_min_ngram: int = 1         # 1..max: the shortest match that counts
+    guidance_scale: float = 1.0              # in [0, 100]; 1: off -- classifier-free guidance of the stage's own model (module docstring, GUIDANCE)
     guided_fsm: Optional[TokenFSM] = None    # the automaton every row follows (module docstring, GUIDED DECODING)
     guided_choice: Optional[Sequence] = None  # the choices (strings / sequences of 1..64 token ids) every row picks one of
     prompt_logprobs: Optional[int] = None    # None: off; 0..8: the prompt tokens' log-probs and ranks, and a top-N table (PROMPT LOG-PROBS)
@@ -759,6 +786,44 @@ class _Plan(NamedTuple):
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
     watermark: Optional[tuple] = None        # every row's key (None: off), delta, gamma and context width; None: every row off
     lookup: Optional[tuple] = None           # (K, max n-gram, min n-gram) of prompt-lookup drafting; None: off
+    guidance: Optional[tuple] = None         # every row's guidance scale and negative prompt (None: the prompt's last token); None: every row off
+
+
+class _GuidedModel:
+    """The stage's model under classifier-free guidance (module docstring, GUIDANCE): the three methods the loops call.  The Bg
+    guided rows' unconditional contexts ride in the same passes as batch rows B .. B + Bg - 1, at the guided rows' positions:
+    position p < P holds the negative prompt's id, every later one the guided row's own token.  `forward_ragged` guides the
+    conditional rows in place (ops.cfg_rows, one launch) and returns them as a view.  The first pass after `alloc_ragged` is the
+    prefill: its rows are read by prompt_logprobs alone, which is not built with guidance, so only its last row is guided, and
+    that only where the loop draws from it (`first_row`: stage 0's plain loop; the other two discard the prefill's output)."""
+
+    def __init__(self, ops, model, scales, neg_ids: torch.Tensor, device, first_row: bool):
+        guided = [b for b, s in enumerate(scales) if s != 1.0]
+        uncond = [-1] * len(scales)
+        for q, b in enumerate(guided):
+            uncond[b] = q
+        self.ops, self.model, self.neg, self.P = ops, model, neg_ids, neg_ids.shape[1]
+        self.rows = torch.tensor(guided, dtype=torch.int64).to(device)
+        self.packed = ops.pack_cfg(scales, uncond, device)
+        self.B, self.prefill, self.first_row = len(scales), True, first_row
+
+    def reset(self) -> None:
+        self.model.reset()
+
+    def alloc_ragged(self, batch: int, max_len: int) -> None:
+        self.model.alloc_ragged(batch + len(self.rows), max_len)
+        self.prefill = True
+
+    def forward_ragged(self, ids: torch.Tensor, pos: torch.Tensor, window: int) -> torch.Tensor:
+        B, pos = self.B, pos.to(torch.int64)
+        pos_u = pos[self.rows]
+        at = pos_u[:, None] + torch.arange(ids.shape[1], device=ids.device)
+        ids_u = torch.where(at < self.P, self.neg.gather(1, at.clamp(max=self.P - 1)), ids[self.rows])
+        out = self.model.forward_ragged(torch.cat([ids, ids_u], 0), torch.cat([pos, pos_u], 0), window)
+        first, self.prefill = (-1 if self.prefill else 0), False
+        if first == 0 or self.first_row:
+            self.ops.cfg_rows(out[:B, first:], out[B:, first:], self.packed)
+        return out[:B]
 
 
 class _EditState:
@@ -1426,6 +1491,10 @@ class _CallState:
 
     def __init__(self, stage: "Stage", plan: _Plan, ids: torch.Tensor, prompt_ids: List[List[int]]):
         (B, P), dev, ops = ids.shape, ids.device, stage.ops
+        # the model the loops run: the stage's own, or the same behind classifier-free guidance
+        self.model = stage.model if plan.guidance is None else \
+            _GuidedModel(ops, stage.model, plan.guidance[0], stage._encode_negative(plan.guidance, prompt_ids, P), dev,
+                         first_row=stage.draft is None and not plan.lookup)
         self.end = _StopSequences(ops, plan.row_seqs, plan.limits, P, dev) if plan.finish_route else \
             _StopIds(ops, plan.stop, B, dev) if plan.stop else _RunToLimit(ops)
         self.mask = _MaskState(ops, plan.mask_rows, stage.shape.vocab, dev) if any(r is not None for r in plan.mask_rows) else None
@@ -1505,6 +1574,7 @@ class Stage:
                            config.target_smoothing_curve, 1)
         check_watermark(config.watermark_key, config.watermark_delta, config.watermark_gamma, config.watermark_context, 1)
         check_prompt_lookup(config.prompt_lookup_num_tokens, config.prompt_lookup_max_ngram, config.prompt_lookup_min_ngram)
+        check_guidance(config.guidance_scale, None, 1)
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
         self.tokenizer = SimpleTokenizer()
@@ -1535,6 +1605,17 @@ class Stage:
         rows = [[0] * (P - len(r)) + r for r in real]
         return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), P).to(self.device), real
 
+    def _encode_negative(self, guidance, prompt_ids: List[List[int]], P: int) -> torch.Tensor:
+        """[Bg, P] int64: the unconditional contexts of the guided rows (scale != 1), in row order.  A negative prompt is
+        encoded as prompts are -- ids folded into the vocabulary, the last P kept, left-padded with id 0 -- to the call's own P;
+        None: the prompt's last token alone behind the padding (HF's rule)."""
+        V, rows = self.shape.vocab, []
+        for s, text, real in zip(*guidance, prompt_ids):
+            if s != 1.0:
+                r = list(real[-1:]) if text is None else [i % V for i in self.tokenizer.encode(text, return_tensors=None)][-P:]
+                rows.append([0] * (P - len(r)) + r)
+        return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), P).to(self.device)
+
     @staticmethod
     def decode_tokens(ids: Sequence[int]) -> str:
         return " ".join(f"t{int(i)}" for i in ids)
@@ -1564,7 +1645,8 @@ class Stage:
                  smoothing_curve=None,
                  watermark_key=None, watermark_delta=None, watermark_gamma=None,
                  watermark_context=None, prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None,
-                 prompt_lookup_min_ngram=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 prompt_lookup_min_ngram=None, guidance_scale=None,
+                 negative_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1738,7 +1820,17 @@ class Stage:
         stats["lookup_matched_steps"][i]: the steps in which row i's suffix had a match, counted over EVERY step the call ran
         (a row that ended early keeps being counted); absent when lookup is off.  A bool, a float, a sequence, a value
         outside its range, min above max, an n-gram named while the number of tokens resolves to 0, and a guided row
-        together with lookup raise ValueError (module docstring, PROMPT LOOKUP)."""
+        together with lookup raise ValueError (module docstring, PROMPT LOOKUP).
+        `guidance_scale` (None = StageConfig.guidance_scale; one finite number in [0, 100] for every prompt or one per prompt;
+        1: the row is off) and `negative_prompt` (None, one string for every prompt, or one string or None per prompt):
+        classifier-free guidance (HF's guidance_scale / negative_prompt_ids, llama.cpp's cfg-scale).  The model's logits of a
+        guided row become u' + s (c' - u'), c' and u' the log-softmax of its logits under the prompt and under the negative
+        prompt (encoded as prompts are, to the call's P; None: the prompt's last token alone), ahead of every other processor:
+        log-probs, top-N tables and token statistics describe the guided distribution.  0 gives the unconditional
+        distribution.  At a verifying stage and under prompt lookup this stage's own model is guided and the draft model
+        proposes unguided.  A bool, a NaN, a value out of range, the wrong length, a negative prompt without a row whose
+        scale differs from 1, prompt_logprobs together with guidance and a guided draft stage raise ValueError (module
+        docstring, GUIDANCE)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1750,7 +1842,7 @@ class Stage:
                           dry_sequence_breakers, mirostat_tau, mirostat_eta, top_n_sigma, top_a, xtc_threshold,
                           xtc_probability, dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve,
                           watermark_key, watermark_delta, watermark_gamma, watermark_context, prompt_lookup_num_tokens,
-                          prompt_lookup_max_ngram, prompt_lookup_min_ngram)
+                          prompt_lookup_max_ngram, prompt_lookup_min_ngram, guidance_scale, negative_prompt)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1826,7 +1918,8 @@ class Stage:
               mirostat_eta=None, top_n_sigma=None, top_a=None, xtc_threshold=None, xtc_probability=None,
               dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None, smoothing_curve=None,
               watermark_key=None, watermark_delta=None, watermark_gamma=None, watermark_context=None,
-              prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None, prompt_lookup_min_ngram=None) -> _Plan:
+              prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None, prompt_lookup_min_ngram=None,
+              guidance_scale=None, negative_prompt=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -1904,6 +1997,11 @@ class Stage:
                                      prompt_lookup_max_ngram is not None or prompt_lookup_min_ngram is not None)
         if lookup is not None and fsm is not None:   # (the automaton's advance is only defined on tokens it allows)
             raise ValueError("prompt_lookup_num_tokens > 0 is not built for a guided row (guided_fsm / guided_choice)")
+        guidance = check_guidance(given(guidance_scale, cfg.guidance_scale), negative_prompt, n)
+        if guidance is not None and n_prompt is not None:    # (the prompt's rows would have to be guided one by one: K1 = P - 1)
+            raise ValueError("prompt_logprobs together with guidance_scale != 1 is not built")
+        if dcfg is not None and lookup is None and dcfg.guidance_scale != 1.0:
+            raise ValueError("a guided draft model (the draft stage's configured guidance_scale != 1) is not built")
         own_miro = (cfg.mirostat_tau, cfg.mirostat_eta) if self.draft is None else (cfg.target_mirostat_tau, cfg.target_mirostat_eta)
         miro_rows = check_mirostat(given(mirostat_tau, own_miro[0]), given(mirostat_eta, own_miro[1]), n, mirostat_eta is not None)
         own_rel = (cfg.top_n_sigma, cfg.top_a, cfg.xtc_threshold, cfg.xtc_probability) if self.draft is None else \
@@ -1957,7 +2055,7 @@ class Stage:
                      cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
                      dry=dry if any(m > 0.0 for m in dry[0]) else None,           # every row off: no state, no call
                      watermark=watermark if any(k is not None for k in watermark[0]) else None,   # no key: no state, no call
-                     lookup=lookup,
+                     lookup=lookup, guidance=guidance,
                      rel_rows=rel_rows if not greedy and any(m for m, _, _ in rel_rows) else None,     # greedy ignores the cuts
                      shape_rows=shape_rows if not greedy and any(r[0] for r in shape_rows) else None,  # ... and the shaping
                      shape_draft_rows=shape_draft_rows if not greedy and any(r[0] for r in shape_draft_rows) else None,
@@ -1985,7 +2083,7 @@ class Stage:
         fsm, ngram, stat, cut, dry, miro, rel = st.fsm, st.ngram, st.stats, st.cut, st.dry, st.miro, st.rel
         shape, wm = st.shape, st.wm
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
-        m = self.model
+        m = st.model
         m.reset()
         m.alloc_ragged(B, cap + 1)
         logits = m.forward_ragged(ids, torch.zeros((B,), dtype=torch.int64, device=dev), P)
@@ -2065,7 +2163,7 @@ class Stage:
         < L - 1 and the draft's for positions < L - 2, so the target is fed [t_{L-1}, d_0 .. d_{K-1}] at position L - 1 (row i
         scores d_i, row K is the bonus row) and the draft first re-feeds the last two committed tokens."""
         cfg = self.config
-        draft, target = self.draft.model, self.model
+        draft, target = self.draft.model, st.model                       # (the draft proposes unguided; GUIDANCE)
         B, P = ids.shape
         dev = ids.device
         Kd = cfg.draft_len
@@ -2199,7 +2297,7 @@ class Stage:
         < L - 1, so it is fed [t_{L-1}, d_0 .. d_{K-1}] at position L - 1 (row i scores d_i, row K is the bonus row).  The
         target-side processors run on the K + 1 rows in _decode_speculative's order with the proposals in `step_tok`; the
         draft-side ones have no rows to act on."""
-        cfg, target, look = self.config, self.model, st.lookup
+        cfg, target, look = self.config, st.model, st.lookup
         B, P = ids.shape
         dev = ids.device
         Kd = look.K

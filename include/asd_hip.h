@@ -1084,6 +1084,52 @@ int asd_lookup_propose(const int32_t* tokens /*[B, ld_tokens]*/, int64_t ld_toke
                        void* onehot /*[B, K, V] in/out, or NULL*/, int dtype, int64_t ld_seq, int64_t ld_row, int V, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CLASSIFIER-FREE GUIDANCE -- HF generate's `guidance_scale` with `negative_prompt_ids`, llama.cpp's / koboldcpp's /
+ * ExLlamaV2's `cfg-scale` with a negative prompt.  The model scores the continuation under the prompt (the CONDITIONAL row c)
+ * and under a negative prompt (the UNCONDITIONAL row u), and its logits become
+ *     g = u' + s (c' - u'),    c' = log_softmax(c),  u' = log_softmax(u)
+ * AHEAD of every other pass.  One in-place launch over the conditional rows; unconditional rows are never written.
+ * cond: asd_logit_shape_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only.  uncond: Bu sequences of K1 rows in the
+ * same dtype from a base of its own, element (q, j, v) at q*ld_useq + j*ld_urow + v, under the same rules.  The two may be
+ * parts of one allocation; an unconditional row must not be a conditional row of a sequence that is on.
+ * table: B records {float scale; int32 uncond_seq} (asd_cfg_rec, 8 bytes) on the device; row (b, j) pairs with unconditional
+ * row (uncond_seq, j).  uncond_seq < 0 or scale == 1: the sequence is OFF, none of its rows is read.
+ * Per row pair, over the stored values, with Lc = float(ln sum_v exp c_v) and Lu = float(ln sum_v exp u_v) (a -inf element
+ * adds nothing), c'_v = fl(c_v - Lc), u'_v = fl(u_v - Lu), t = fl(1 - s), every operation rounding once in f32:
+ *     c_v == -inf                 ->  stays -inf
+ *     u_v == -inf, c_v finite     ->  c'_v: there is nothing to push against
+ *     otherwise                   ->  fl(fl(s c'_v) + fl(t u'_v))
+ * The f32 result is rounded to the dtype to nearest even and clamped to the dtype's finite range (asd_logit_shape_rows' rule).
+ * s == 0 gives the unconditional distribution on the conditional row's support.  A pair with a NaN or +inf element in either
+ * row, without a finite element in either row, or whose f32 sums leave f32's range (|x| log2 e beyond it, f32 / bf16 only) is
+ * left bit for bit as it is; nothing outside a row's V elements is written.
+ * THE DATA CONTRACT: a record whose scale is not a number in [0, 100], or whose uncond_seq is >= Bu, skips its rows.
+ * Arithmetic: one workgroup of 1024 threads per (b, j).  Both rows are cut at the same element indices -- the scalar head up
+ * to the CONDITIONAL row's first 16-byte boundary, 16-byte vectors, the scalar tail -- so a lane meets the same elements in
+ * the same ascending order at any pair of 16-byte phases; lanes merge by a fixed DPP sequence, waves in wave order: the result
+ * depends on the bytes of the pair and its record only.  (m2, s) per row with c2 = float(log2 e), s * 2^m2 = sum exp(x_v);
+ * L = float(ln 2 (m2 + log2 s)) with the split logarithm, formed once per row by wave 0.  Rows of at most
+ * ASD_CFG_RESIDENT_VECTORS 16-byte vectors (V <= ASD_CFG_RESIDENT_VECTORS * 16 / element size) are read from memory once: the
+ * conditional row is held in registers, the unconditional row is read a second time out of L2; longer rows re-read both.
+ * An unconditional vector is fetched by one 16-byte load where its address is a multiple of 4, and from the aligned dwords
+ * that hold its elements where a 16-bit row lies at 2 mod 4.  No workspace, no state.
+ * Status, in this order: negative B / K1 / V / Bu: invalid argument; B, K1 or V == 0: ASD_OK, nothing launched; unknown dtype,
+ * B*K1 > INT32_MAX, V * element size > INT32_MAX - 16: unsupported; NULL cond / table, NULL uncond with Bu > 0, ld_row < V,
+ * ld_seq < K1*ld_row, and with Bu > 0 ld_urow < V or ld_useq < K1*ld_urow: invalid argument; cond or uncond not aligned to
+ * the element size, or table not aligned to 4: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_CFG_REC_BYTES 8
+#define ASD_CFG_RESIDENT_VECTORS 19456  /* 19 * 1024: the 16-byte vectors of a row the resident kernel holds in registers */
+#define ASD_MAX_GUIDANCE_SCALE 100.0f
+typedef struct asd_cfg_rec {
+    float scale;         /* guidance_scale of the sequence; 1: off */
+    int32_t uncond_seq;  /* its sequence in `uncond`; < 0: off */
+} asd_cfg_rec;
+int asd_cfg_rows(void* cond /*in/out*/, int dtype, int B, int K1, int V, int64_t ld_seq, int64_t ld_row,
+                 const void* uncond, int Bu, int64_t ld_useq, int64_t ld_urow, const asd_cfg_rec* table /*[B]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Guided decoding: a token-level deterministic automaton (FSM) per sequence, AHEAD of the samplers -- what grammar /
  * structured-output back ends compile a set of answers, a regex or a schema to.  Inside a speculative step the mask of
  * position j depends on the proposals 0 .. j-1, which exist only on the device: so the state lives there, small kernels

@@ -1,5 +1,5 @@
 // Stand-alone host harness for `make asan-host-args`: calls the argument checks of the launchers behind asd_residual_sample_lp,
-// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_dry_rows, asd_watermark_rows, asd_watermark_score, asd_lookup_propose, asd_entropy_cut_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
+// asd_commit_step_lp, asd_commit_step_stop, asd_commit_step_finish, asd_verify_greedy, asd_top_logprobs, asd_commit_top_logprobs, asd_step_uniforms, asd_logit_edit_rows, asd_logit_mask_rows, asd_penalty_rows, asd_penalty_commit, asd_bad_words_rows, asd_fsm_mask_rows, asd_fsm_advance, asd_fsm_commit, asd_no_repeat_ngram_rows, asd_dry_rows, asd_watermark_rows, asd_watermark_score, asd_lookup_propose, asd_cfg_rows, asd_entropy_cut_rows, asd_prompt_logprobs and asd_token_stats in a library whose HOST code is built with AddressSanitizer + UBSan (build.py --asan).  Every call below is
 // rejected (or is the B == 0 no-op) before anything is launched, so no GPU is needed and no pointer is dereferenced.
 #include <cmath>
 #include <cstdint>
@@ -647,6 +647,32 @@ int main() {
         EXPECT(SHP(rows + 1, BF16, B, K1, V, K1 * V, V, tab), ASD_ERR_ALIGNMENT);                       // below the element size
         EXPECT(SHP(p, BF16, B, K1, V, K1 * V, V, reinterpret_cast<const asd_logit_shape_rec*>(rows + 2)), ASD_ERR_ALIGNMENT);
 #undef SHP
+    }
+
+    // ---- asd_cfg_rows: asd_logit_shape_rows' order with the second base pointer and its strides
+    {
+#define CFG(c_, dt_, B_, K1_, V_, lds_, ldr_, u_, Bu_, ldus_, ldur_, tab_) \
+    asd_cfg_rows(c_, dt_, B_, K1_, V_, lds_, ldr_, u_, Bu_, ldus_, ldur_, tab_, nullptr)
+        const int K1 = 5, Bu = 2;
+        const asd_cfg_rec* tab = reinterpret_cast<const asd_cfg_rec*>(rows);
+        EXPECT(CFG(p, BF16, -1, K1, V, K1 * V, V, p, Bu, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CFG(p, BF16, B, -1, V, K1 * V, V, p, Bu, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CFG(p, BF16, B, K1, -1, K1 * V, V, p, Bu, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V, p, -1, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CFG(nullptr, 99, 0, K1, V, 0, 0, nullptr, Bu, 0, 0, nullptr), ASD_OK);
+        EXPECT(CFG(nullptr, 99, B, K1, V, K1 * V, V, p, Bu, K1 * V, V, tab), ASD_ERR_UNSUPPORTED);       // dtype, before the NULL checks
+        EXPECT(CFG(p, 0 /*f32*/, B, 1, INT32_MAX, INT32_MAX, INT32_MAX, p, Bu, INT32_MAX, INT32_MAX, tab), ASD_ERR_UNSUPPORTED);
+        EXPECT(CFG(nullptr, BF16, B, K1, V, K1 * V, V, p, Bu, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V, nullptr, Bu, K1 * V, V, tab), ASD_ERR_INVALID_ARG);
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V, p, Bu, K1 * V, V, nullptr), ASD_ERR_INVALID_ARG);
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V - 1, p, Bu, K1 * V, V, tab), ASD_ERR_INVALID_ARG);       // ld_row < V
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V - 1, V, p, Bu, K1 * V, V, tab), ASD_ERR_INVALID_ARG);       // ld_seq < K1 ld_row
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V, p, Bu, K1 * V, V - 1, tab), ASD_ERR_INVALID_ARG);       // ld_urow < V
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V, p, Bu, K1 * V - 1, V, tab), ASD_ERR_INVALID_ARG);       // ld_useq < K1 ld_urow
+        EXPECT(CFG(rows + 1, BF16, B, K1, V, K1 * V, V, p, Bu, K1 * V, V, tab), ASD_ERR_ALIGNMENT);      // below the element size
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V, rows + 1, Bu, K1 * V, V, tab), ASD_ERR_ALIGNMENT);
+        EXPECT(CFG(p, BF16, B, K1, V, K1 * V, V, p, Bu, K1 * V, V, reinterpret_cast<const asd_cfg_rec*>(rows + 2)), ASD_ERR_ALIGNMENT);
+#undef CFG
     }
 
     // ---- asd_watermark_rows: asd_dry_rows' order with the 16-byte records; asd_watermark_score: sizes, pointers, alignment
