@@ -573,6 +573,22 @@ class HipOps:
         when some row of the call has a relative cut."""
         return self.K.relative_cut_rows(logits, packed, coins)
 
+    @traced("pack_tail_free")
+    def pack_tail_free(self, inv_t, z, device):
+        """Every row's 1 / temperature and tfs value (in (0, 1]; 1: off) -> the device table of tail_free_rows
+        (kernels.pack_tail_free: one upload per generate call and side)."""
+        return self.K.pack_tail_free(inv_t, z, device)
+
+    @traced("tail_free_rows")
+    def tail_free_rows(self, logits, packed, workspace=None):
+        """Tail-free sampling ahead of the samplers (asd_tail_free_rows): logits [B, V] or [B, K1, V] (any strides with a unit
+        last stride) -> the same tensor, with every token at -inf that lies behind the row's tail-free cut.  One launch: a
+        radix sort of every row's keys and a scan over the sorted row, in `workspace` (uint8, at least
+        kernels.tail_free_workspace_bytes(B, K1, V, dtype) bytes; None: allocated by the call).  A stage loop makes the call
+        once per logits tensor, directly behind relative_cut_rows and ahead of entropy_cut_rows, and only when some row of the
+        call has tfs below 1."""
+        return self.K.tail_free_rows(logits, packed, workspace)
+
     @traced("pack_logit_shape")
     def pack_logit_shape(self, temps, modes, a, b, device):
         """Every row's temperature, mode (0 off, 1 dynatemp, 2 quadratic), a (dynatemp_range or smoothing_factor) and b

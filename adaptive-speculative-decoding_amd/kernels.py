@@ -1958,6 +1958,80 @@ def relative_cut_rows(logits: torch.Tensor, cut: RelativeCut, coins: Optional[to
     return logits
 
 
+# ------------------------------------------------------------------------------- tail-free sampling (tfs)
+_TFS_REC = np.dtype([("inv_t", np.float32), ("z", np.float32)])
+assert _TFS_REC.itemsize == B.TAIL_FREE_REC_BYTES
+
+
+@dataclass
+class TailFree:
+    """The table of asd_tail_free_rows on the device (pack_tail_free): B records {inv_t f32, z f32} of 8 bytes, as a uint8
+    [B, 8] tensor; `z`: the host's copy of the rows' values (1: off); `workspace`: the key buffers tail_free_rows allocated
+    for these records' first call, reused by every later call that fits (a generate call allocates once per side)."""
+    table: torch.Tensor
+    z: Tuple[float, ...]
+    B: int
+    workspace: Optional[torch.Tensor] = None
+
+
+def check_tail_free_rows(inv_t, z) -> np.ndarray:
+    """The host side of pack_tail_free: every row's 1 / temperature (a positive finite number) and z (tfs, in (0, 1]; 1: off)
+    -> the records, a numpy structured array."""
+    inv_t, z = list(inv_t), list(z)
+    if len(inv_t) != len(z):
+        raise ValueError(f"{len(inv_t)} temperatures and {len(z)} tfs values must describe the same rows")
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))   # noqa: E731
+    rec = np.zeros(len(z), dtype=_TFS_REC)
+    for i, (t, v) in enumerate(zip(inv_t, z)):
+        if not number(t) or not 0.0 < float(np.float32(t)) < 3.0e38:
+            raise ValueError(f"row {i}: 1 / temperature must be a positive finite number, got {t!r}")
+        if not number(v) or not 0.0 < float(np.float32(v)) <= 1.0:                  # (NaN included)
+            raise ValueError(f"row {i}: tfs must lie in (0, 1] (1: off), got {v!r}")
+        rec[i] = (np.float32(t), np.float32(v))
+    return rec
+
+
+def pack_tail_free(inv_t, z, device) -> TailFree:
+    """The table of tail_free_rows from host lists, checked BEFORE anything is uploaded."""
+    rec = check_tail_free_rows(inv_t, z)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _TFS_REC.itemsize).copy()).to(device)
+    return TailFree(table, tuple(float(v) for v in rec["z"]), len(rec))
+
+
+def tail_free_workspace_bytes(Bv: int, K1: int, V: int, dtype: torch.dtype) -> int:
+    """asd_tail_free_workspace_bytes: two key buffers per row, each rounded up to 256 bytes."""
+    return int(_lib().asd_tail_free_workspace_bytes(int(Bv), int(K1), int(V), _DTYPE_CODE[dtype]))
+
+
+def tail_free_rows(logits: torch.Tensor, tfs: TailFree, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Cut in place (asd_tail_free_rows) and return `logits`: [B, V] or [B, K1, V], bf16 / f16 / f32, any sequence / row stride
+    with unit stride along V.  Row (b, j) under record b: with the finite elements sorted by value, descending, and
+    w = exp(inv_t (x - x_max)), d2_i = |(w_i - w_{i+1}) - (w_{i+1} - w_{i+2})| and i* the first i whose running sum of d2
+    exceeds z times their total, every token below the value at sorted position i* becomes -inf (ties at it stay).
+    workspace: a uint8 CUDA tensor of at least tail_free_workspace_bytes(B, K1, V, dtype) bytes, 256-byte aligned, which a
+    caller may hand in; None: tfs.workspace, allocated by the records' first call and kept.  Nothing it held is read."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    view = logits[:, None] if logits.dim() == 2 else logits
+    if view.dim() != 3 or (view.shape[2] > 1 and view.stride(2) != 1):
+        raise ValueError("logits must be [B, V] or [B, K1, V] with unit stride along V")
+    Bv, K1, V = view.shape
+    if tfs.B != Bv:
+        raise ValueError(f"the tfs records were packed for {tfs.B} rows; logits have {Bv}")
+    need = tail_free_workspace_bytes(Bv, K1, V, view.dtype)
+    if workspace is None:
+        if tfs.workspace is None or tfs.workspace.numel() < need or tfs.workspace.device != logits.device:
+            tfs.workspace = torch.empty((need,), dtype=torch.uint8, device=logits.device)
+        workspace = tfs.workspace
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.numel() < need:
+        raise ValueError(f"workspace must be a uint8 CUDA (HIP) vector of at least {need} bytes")
+    ld_seq, ld_row = _logit_strides(view, K1)
+    rc = _lib().asd_tail_free_rows(view.data_ptr(), _DTYPE_CODE[view.dtype], Bv, K1, V, ld_seq, ld_row,
+                                   _dev(tfs.table, "table", torch.uint8), workspace.data_ptr(), workspace.numel(), _stream())
+    B.check("asd_tail_free_rows", rc)
+    return logits
+
+
 # ------------------------------------------------------------------------------- shaping (dynatemp_* / smoothing_*)
 SHAPE_OFF, SHAPE_DYNATEMP, SHAPE_QUADRATIC = 0, 1, 2
 _SHAPE_REC = np.dtype([("mode", np.int32), ("T", np.float32), ("a", np.float32), ("b", np.float32)])

@@ -48,6 +48,9 @@ batch or one per request, kept by the request through every regrouping, handed o
 configuration only: a value that is set is handed to every stage's generate call as the keyword of that name, None is not passed.
 `PipelineConfig.mirostat_tau` / `mirostat_eta` (llama.cpp's mirostat_v2; serving/stages.py, MIROSTAT) travel the same way.
 `PipelineConfig.top_n_sigma` / `top_a` / `xtc_threshold` / `xtc_probability` (serving/stages.py, RELATIVE CUTS) travel the same way.
+`PipelineConfig.tfs` (tail-free sampling; serving/stages.py, TAIL-FREE) travels the same way: at stage 0 it is the stage's own
+draws, at a verifying stage the target's own distribution (StageConfig.target_tfs's place); a verifying stage's draft rows take
+the draft stage's StageConfig.tfs.
 `PipelineConfig.dynatemp_range` / `dynatemp_exponent` / `smoothing_factor` / `smoothing_curve` (serving/stages.py, SHAPING) too.
 `PipelineConfig.dry_multiplier` / `dry_base` / `dry_allowed_length` / `dry_range` / `dry_sequence_breakers` (the DRY sampler;
 serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
@@ -241,6 +244,8 @@ class PipelineConfig:
     top_a: Optional[float] = None
     xtc_threshold: Optional[float] = None
     xtc_probability: Optional[float] = None
+    # tail-free sampling, handed to stage.generate(tfs=); None: the keyword is not passed (serving/stages.py, TAIL-FREE)
+    tfs: Optional[float] = None
     # dynamic temperature and quadratic sampling, handed to stage.generate(dynatemp_range=, dynatemp_exponent=,
     # smoothing_factor=, smoothing_curve=); None: the keyword is not passed (serving/stages.py, SHAPING)
     dynatemp_range: Optional[float] = None
@@ -310,7 +315,7 @@ class PipelineConfig:
         if sec.get("no_repeat_ngram_size") is not None:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
         for name in ("typical_p", "epsilon_cutoff", "eta_cutoff", "mirostat_tau", "mirostat_eta",
-                     "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",
+                     "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability", "tfs",
                      "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve"):
             if sec.get(name) is not None:
                 kw[name] = float(sec[name])
@@ -682,6 +687,7 @@ class AdaptiveSpeculativePipeline:
                              "dry_multiplier", "dry_base", "dry_allowed_length", "dry_range", "dry_sequence_breakers",
                              "mirostat_tau", "mirostat_eta",                     # ... and Mirostat
                              "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",     # ... and the relative cuts
+                             "tfs",                                              # ... and tail-free sampling
                              "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve",    # ... and the shaping
                              "watermark_key", "watermark_delta", "watermark_gamma", "watermark_context",     # ... and the watermark
                              "prompt_lookup_num_tokens", "prompt_lookup_max_ngram", "prompt_lookup_min_ngram",    # ... and prompt lookup

@@ -236,6 +236,34 @@ def check_relative_cut_alone(rel_rows, cut_rows) -> None:
                              "on one row is not built")
 
 
+def check_tail_free(tfs, n: int) -> List[float]:
+    """generate's `tfs` (tail-free sampling: webui's / koboldcpp's / Aphrodite's `tfs`, llama.cpp's old `tfs_z`): one number
+    for all `n` prompts or a sequence of n numbers, each in (0, 1] (1: off) -> every row's value as the device record holds
+    it.  A bool, a NaN, 0, a value outside (0, 1] and the wrong length raise ValueError."""
+    def one(v):
+        ok = not isinstance(v, bool) and isinstance(v, _NUMBER) and 0.0 < float(np.float32(v)) <= 1.0   # (NaN included)
+        if not ok:
+            raise ValueError(f"tfs must be a number in (0, 1] (1: off), got {v!r}")
+        return float(np.float32(v))
+    if isinstance(tfs, (str, bytes)):
+        raise ValueError(f"tfs must be a number or one number per prompt, got {tfs!r}")
+    return _per_prompt(tfs, n, one, "tfs values")
+
+
+def check_tail_free_alone(tfs_rows, rel_rows, cut_rows, miro_rows=None, side: str = "") -> None:
+    """A row takes ONE cut: tfs below 1 together with a relative cut, an entropy cut or Mirostat on the same row and side is
+    not built and raises ValueError.  tfs_rows: every row's z; rel_rows: (mode, a, b); cut_rows: (mode, value); miro_rows:
+    (tau, eta)."""
+    for b, z in enumerate(tfs_rows):
+        if z >= 1.0:
+            continue
+        if (rel_rows and rel_rows[b][0] != RELCUT_OFF) or (cut_rows and cut_rows[b][0] != CUT_OFF):
+            raise ValueError(f"prompt {b}: {side}tfs together with top_n_sigma, top_a, XTC, typical_p, epsilon_cutoff or "
+                             "eta_cutoff on one row is not built")
+        if miro_rows is not None and miro_rows[b][0] > 0.0:
+            raise ValueError(f"prompt {b}: tfs together with Mirostat on one row is not built")
+
+
 SHAPE_OFF, SHAPE_DYNATEMP, SHAPE_QUADRATIC = 0, 1, 2     # ASD_SHAPE_* of include/asd_hip.h (SHAPING)
 
 

@@ -504,7 +504,38 @@ V = 152064, bf16, kernel time, against asd_entropy_cut_rows in epsilon mode on a
 spread 0.03), 5.0 us with every coin above q; K1 = 1: 25.3 / 21.8 / 25.6 / 4.8 us against 28.3 us.  NOT BUILT beside the above:
 serving/hierarchy.py's loop.
 
-SHAPING.  `generate(dynatemp_range=, dynatemp_exponent=, smoothing_factor=, smoothing_curve=)` are llama.cpp's / koboldcpp's
+TAIL-FREE.  `generate(tfs=)` is tail-free sampling: `tfs` of text-generation-webui, koboldcpp, KoboldAI and Aphrodite
+(TailFreeLogitsWarper with min_tokens_to_keep = 1), `tfs_z` of older llama.cpp -- the one truncation that is not a threshold on
+a row statistic: it needs the second differences of the probabilities IN SORTED ORDER.  It takes one number for the call or one
+per prompt, in (0, 1]; 1 is off and the default; None takes the configuration's value: StageConfig.tfs is the stage's own draws
+at stage 0 and its proposals for the stage above, target_tfs a verifying stage's own distribution -- the rule of min_p /
+target_min_p.  INPUT: the row as every earlier pass left it, the values the stored ones, fin the set of its finite elements and
+n = |fin|; a -inf element carries no mass, stays -inf and is in no statistic.
+  tfs = z             w_v = exp((x_v - x_max) / T), the finite elements sorted by value, descending: w_(0) >= ... >= w_(n-1);
+                      d1_i = w_(i) - w_(i+1), d2_i = |d1_i - d1_(i+1)| (i < n - 2), S = sum d2_i, c_i = d2_0 + ... + d2_i; i* is
+                      the first i with c_i > z S, x_cut the stored value at sorted position i*; token v is cut iff x_v < x_cut.
+                      Every tie at x_cut stays (this build's tie rule, XTC's), the arg-max is never cut, a row is never emptied.
+                      n < 3, S = 0 (a flat row), a NaN or +inf element: the row is left bit for bit.  llama.cpp's tfs_z keeps one
+                      token fewer: it resizes to i*, this rule keeps i* + 1.
+A cut token's logit becomes -inf in place; nothing else is written.  It is one more in-place pass (asd_tail_free_rows: a
+per-row radix sort of the row's keys and a scan over the sorted row in f64, in a workspace the call allocates once per side; the
+rows' {1 / T, z} records are uploaded once per call and side through ops.pack_tail_free) directly behind the relative cut and
+ahead of the entropy cut: mask -> fsm -> bad words -> n-gram -> edit -> penalties -> DRY -> watermark -> relative cut ->
+TAIL-FREE -> entropy cut -> shaping -> temperature -> top-k -> top-p -> min-p.  ONE CUT PER ROW: tfs below 1 on a row together
+with top_n_sigma / top_a / XTC / typical_p / epsilon_cutoff / eta_cutoff, or together with Mirostat, raises ValueError (NOT
+BUILT).  At a verifying stage the target's [B, K+1, V] output takes the call's own tfs and the draft rows the DRAFT stage's
+configured tfs (per-request values of the draft side: NOT BUILT); the verify, the residual draw and the commit only ever see
+logits that carry the cut, so the chain stays lossless by the LOGIT EDITS argument.  Log-probs, top-N tables and token
+statistics describe the distribution behind the cut.  Greedy decoding ignores tfs and makes no call; a call whose every row is
+off makes exactly the ops calls it made before.  ValueError before any launch and before the prompts are encoded: a bool, a
+NaN, 0 or anything outside (0, 1], the wrong length.  COST (profiles/tail_free.json: B = 32, V = 152064, bf16, kernel time,
+against asd_entropy_cut_rows in typical mode on a copy of the same tensor): K1 = 9: 1378.6 us against 175.6 us (ratio 7.85; that
+baseline's spread 0.011); K1 = 1: 464.9 us against 86.1 us (5.40) -- several times the costliest other cut; 64 sampled tokens
+at B = 8 at the Qwen2.5-7B shape: 1229.8 ms with tfs on against 1219.9 ms off (1.008); 54 VGPRs, 16776
+bytes of LDS, no scratch, a workspace of 175 MB / 19 MB; the phases were not timed apart.  NOT BUILT beside the above:
+serving/hierarchy.py's loop.
+
+SHAPING.`generate(dynatemp_range=, dynatemp_exponent=, smoothing_factor=, smoothing_curve=)` are llama.cpp's / koboldcpp's
 dynamic temperature and the quadratic ("smooth") sampling of text-generation-webui, koboldcpp and Aphrodite: the two samplers
 that RESHAPE a row's distribution instead of cutting it, the usual companions of DRY and XTC.  Each takes one number for the
 call or one per prompt; None takes the configuration's value: StageConfig.dynatemp_range / dynatemp_exponent /
@@ -654,7 +685,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_guidance, check_prompt_lookup, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_guidance, check_prompt_lookup, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_tail_free, check_tail_free_alone, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -707,6 +738,9 @@ class StageConfig:
     target_top_a: float = 0.0
     target_xtc_threshold: float = 0.1
     target_xtc_probability: float = 0.0
+    # tail-free sampling (module docstring, TAIL-FREE), by the rule of min_p / target_min_p
+    tfs: float = 1.0                         # tfs of the stage's own draws and of its proposals, in (0, 1]; 1: off
+    target_tfs: float = 1.0                  # ... of a verifying stage's own distribution
     # shaping (module docstring, SHAPING), by the rule of min_p / target_min_p; at most one of the two modes per side
     dynatemp_range: float = 0.0              # llama.cpp's dynatemp_range of the stage's own draws and of its proposals; 0: off
     dynatemp_exponent: float = 1.0           # ... its exponent, > 0
@@ -781,6 +815,8 @@ class _Plan(NamedTuple):
     miro_rows: Optional[list] = None         # every row's (tau, eta) of the stage's own Mirostat; None: every row off
     rel_rows: Optional[list] = None          # every row's (mode, a, b) of the stage's own relative cut; None: every row off
     rel_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, a, b) of the draft stage's configured top-n-sigma / top-a
+    tfs_rows: Optional[list] = None          # every row's z of the stage's own tail-free cut; None: every row off
+    tfs_draft_rows: Optional[list] = None    # a verifying stage: every row's z of the draft stage's configured tfs
     shape_rows: Optional[list] = None        # every row's (mode, T, a, b) of the stage's own shaping; None: every row off
     shape_draft_rows: Optional[list] = None  # a verifying stage: every row's (mode, T, a, b) of the draft stage's configured shaping
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
@@ -923,6 +959,23 @@ class _RelCutState:
         tensor as it entered."""
         entered = logits.clone() if keep else None
         self.ops.relative_cut_rows(logits, self.packed, coins if self.xtc else None)
+        return entered
+
+
+class _TailFreeState:
+    """What a generate call with tail-free sampling keeps for one side (its own rows, or a verifying stage's draft rows): the
+    rows' {1 / temperature, z} records on the device, uploaded once, and with them the sort's workspace, which the first call
+    allocates and every later one reuses.  `apply` is the loops' one call per logits tensor, directly behind the relative cut
+    and ahead of the entropy cut (module docstring, TAIL-FREE)."""
+
+    def __init__(self, ops, rows, inv_t: List[float], device):
+        self.ops = ops
+        self.packed = ops.pack_tail_free(inv_t, rows, device)
+
+    def apply(self, logits: torch.Tensor, keep: bool = False) -> Optional[torch.Tensor]:
+        """logits [B, V] or [B, K+1, V], cut in place.  keep: the tests' record -- a clone of the tensor as it entered."""
+        entered = logits.clone() if keep else None
+        self.ops.tail_free_rows(logits, self.packed)
         return entered
 
 
@@ -1528,6 +1581,9 @@ class _CallState:
         # the relative cuts, by the same two sides; XTC's coins come from the sampler
         self.rel = _RelCutState(ops, plan.rel_rows, inv_t, dev) if plan.rel_rows else None
         self.rel_draft = _RelCutState(ops, plan.rel_draft_rows, inv_t, dev) if plan.rel_draft_rows else None
+        # tail-free sampling, by the same two sides
+        self.tfs = _TailFreeState(ops, plan.tfs_rows, inv_t, dev) if plan.tfs_rows else None
+        self.tfs_draft = _TailFreeState(ops, plan.tfs_draft_rows, inv_t, dev) if plan.tfs_draft_rows else None
         # shaping, by the same two sides; the records carry the rows' temperatures themselves
         self.shape = _ShapeState(ops, plan.shape_rows, dev) if plan.shape_rows else None
         self.shape_draft = _ShapeState(ops, plan.shape_draft_rows, dev) if plan.shape_draft_rows else None
@@ -1569,6 +1625,8 @@ class Stage:
         check_relative_cuts(config.top_n_sigma, config.top_a, config.xtc_threshold, config.xtc_probability, 1)
         check_relative_cuts(config.target_top_n_sigma, config.target_top_a, config.target_xtc_threshold,
                             config.target_xtc_probability, 1)
+        check_tail_free(config.tfs, 1)
+        check_tail_free(config.target_tfs, 1)
         check_logit_shapes(config.dynatemp_range, config.dynatemp_exponent, config.smoothing_factor, config.smoothing_curve, 1)
         check_logit_shapes(config.target_dynatemp_range, config.target_dynatemp_exponent, config.target_smoothing_factor,
                            config.target_smoothing_curve, 1)
@@ -1646,7 +1704,7 @@ class Stage:
                  watermark_key=None, watermark_delta=None, watermark_gamma=None,
                  watermark_context=None, prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None,
                  prompt_lookup_min_ngram=None, guidance_scale=None,
-                 negative_prompt=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 negative_prompt=None, tfs=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1830,7 +1888,15 @@ class Stage:
         distribution.  At a verifying stage and under prompt lookup this stage's own model is guided and the draft model
         proposes unguided.  A bool, a NaN, a value out of range, the wrong length, a negative prompt without a row whose
         scale differs from 1, prompt_logprobs together with guidance and a guided draft stage raise ValueError (module
-        docstring, GUIDANCE)."""
+        docstring, GUIDANCE).
+        `tfs` (tail-free sampling: webui's / koboldcpp's / KoboldAI's / Aphrodite's `tfs`, llama.cpp's old `tfs_z`): None = the
+        configuration's (StageConfig.tfs at stage 0, target_tfs at a verifying stage: the rule of `min_p`); one number in
+        (0, 1] for every prompt or one per prompt; 1: off.  With the row's probabilities in descending order it cuts the tail
+        behind the point where the running sum of their absolute second differences passes tfs times the total (ties at the
+        cut stay, the arg-max always stays).  The cut runs behind the relative cut and ahead of the entropy cut.  A row takes
+        it alone: together with top_n_sigma, top_a, XTC, typical_p, epsilon_cutoff, eta_cutoff or Mirostat it raises
+        ValueError, as do a bool, a NaN, 0, a value outside (0, 1] and the wrong length.  Greedy decoding ignores it (module
+        docstring, TAIL-FREE)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1842,7 +1908,7 @@ class Stage:
                           dry_sequence_breakers, mirostat_tau, mirostat_eta, top_n_sigma, top_a, xtc_threshold,
                           xtc_probability, dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve,
                           watermark_key, watermark_delta, watermark_gamma, watermark_context, prompt_lookup_num_tokens,
-                          prompt_lookup_max_ngram, prompt_lookup_min_ngram, guidance_scale, negative_prompt)
+                          prompt_lookup_max_ngram, prompt_lookup_min_ngram, guidance_scale, negative_prompt, tfs)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1919,7 +1985,7 @@ class Stage:
               dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None, smoothing_curve=None,
               watermark_key=None, watermark_delta=None, watermark_gamma=None, watermark_context=None,
               prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None, prompt_lookup_min_ngram=None,
-              guidance_scale=None, negative_prompt=None) -> _Plan:
+              guidance_scale=None, negative_prompt=None, tfs=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -2014,6 +2080,10 @@ class Stage:
         if cut_draft_rows:
             check_relative_cut_alone(rel_draft_rows, cut_draft_rows)
         check_mirostat_alone(miro_rows, top_k, top_p, min_p, cut_rows, rel_rows)
+        tfs_rows = check_tail_free(given(tfs, cfg.tfs if self.draft is None else cfg.target_tfs), n)
+        check_tail_free_alone(tfs_rows, rel_rows, cut_rows, miro_rows)
+        # the draft rows take the DRAFT stage's configured tfs (per-request draft-side values: NOT BUILT)
+        tfs_draft_rows = [] if dcfg is None else check_tail_free(dcfg.tfs, n)
         own_shape = (cfg.dynatemp_range, cfg.dynatemp_exponent, cfg.smoothing_factor, cfg.smoothing_curve) if self.draft is None else \
             (cfg.target_dynatemp_range, cfg.target_dynatemp_exponent, cfg.target_smoothing_factor, cfg.target_smoothing_curve)
         shape_rows = check_logit_shapes(*(given(v, d) for v, d in zip((dynatemp_range, dynatemp_exponent, smoothing_factor,
@@ -2024,7 +2094,8 @@ class Stage:
         shape_draft_rows = [] if dcfg is None else check_logit_shapes(dcfg.dynatemp_range, dcfg.dynatemp_exponent,
                                                                       dcfg.smoothing_factor, dcfg.smoothing_curve, n)
         if lookup is not None:                   # no draft rows: the draft stage's configured cuts and shaping have nothing to act on
-            cut_draft_rows, rel_draft_rows, shape_draft_rows = [], [], []
+            cut_draft_rows, rel_draft_rows, shape_draft_rows, tfs_draft_rows = [], [], [], []
+        check_tail_free_alone(tfs_draft_rows, rel_draft_rows, cut_draft_rows, side="the draft stage's configured ")
         limits = max_tokens if isinstance(max_tokens, list) else [max_tokens] * n
         limit = max(limits, default=0)
         live = n > 0 and limit > 0               # (a call that returns at once never looked at a scalar temperature: it still does not)
@@ -2058,6 +2129,8 @@ class Stage:
                      lookup=lookup, guidance=guidance,
                      rel_rows=rel_rows if not greedy and any(m for m, _, _ in rel_rows) else None,     # greedy ignores the cuts
                      shape_rows=shape_rows if not greedy and any(r[0] for r in shape_rows) else None,  # ... and the shaping
+                     tfs_rows=tfs_rows if not greedy and any(z < 1.0 for z in tfs_rows) else None,      # ... and tail-free sampling
+                     tfs_draft_rows=tfs_draft_rows if not greedy and any(z < 1.0 for z in tfs_draft_rows) else None,
                      shape_draft_rows=shape_draft_rows if not greedy and any(r[0] for r in shape_draft_rows) else None,
                      rel_draft_rows=rel_draft_rows if not greedy and any(m for m, _, _ in rel_draft_rows) else None,
                      miro_rows=miro_rows if not greedy and any(t > 0.0 for t, _ in miro_rows) else None)    # greedy ignores Mirostat
@@ -2081,7 +2154,7 @@ class Stage:
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         fsm, ngram, stat, cut, dry, miro, rel = st.fsm, st.ngram, st.stats, st.cut, st.dry, st.miro, st.rel
-        shape, wm = st.shape, st.wm
+        shape, wm, tfs = st.shape, st.wm, st.tfs
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         m = st.model
         m.reset()
@@ -2111,6 +2184,7 @@ class Stage:
             if wm is not None:
                 wm.apply(logits, tokens, seq_len)                        # the watermark: behind every processor, ahead of every warper
             rel_in = rel.apply(logits, coins, self.keep_inputs) if rel is not None else None   # the relative cut: directly behind DRY
+            tfs_in = tfs.apply(logits, self.keep_inputs) if tfs is not None else None   # tail-free: behind the relative cut's place
             cut_in = cut.apply(logits, self.keep_inputs) if cut is not None else None   # the entropy cut: behind every processor
             shape_in = shape.apply(logits, self.keep_inputs) if shape is not None else None   # shaping: behind the cuts, ahead of the temperature
             miro_in = miro.apply(logits, None, self.keep_inputs) if miro is not None else None   # Mirostat: the LAST pass
@@ -2120,6 +2194,8 @@ class Stage:
                 kept["cut_in"] = cut_in
             if kept is not None and rel is not None:
                 kept.update(rel_in=rel_in, rel_coins=None if coins is None else coins.clone())
+            if kept is not None and tfs is not None:
+                kept["tfs_in"] = tfs_in
             if kept is not None and shape is not None:
                 kept["shape_in"] = shape_in
             if kept is not None and miro is not None:
@@ -2171,7 +2247,7 @@ class Stage:
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         fsm, ngram, stat, cut, cut_draft, dry, miro = st.fsm, st.ngram, st.stats, st.cut, st.cut_draft, st.dry, st.miro
         rel, rel_draft = st.rel, st.rel_draft
-        shape, shape_draft, wm = st.shape, st.shape_draft, st.wm
+        shape, shape_draft, wm, tfs, tfs_draft = st.shape, st.shape_draft, st.wm, st.tfs, st.tfs_draft
         step_tok = st.step_tok                                          # the step's proposals, for `fsm`, `bad`, `ngram` and `pen`; None: all off
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         for m in (draft, target):
@@ -2214,6 +2290,8 @@ class Stage:
                     wm.apply(dl, tokens, seq_len, k)                    # the watermark: the green list behind the proposals 0 .. k - 1
                 if rel_draft is not None:
                     rel_draft.apply(dl)                                 # the DRAFT stage's configured top-n-sigma / top-a
+                if tfs_draft is not None:
+                    tfs_draft.apply(dl)                                 # the DRAFT stage's configured tfs
                 if cut_draft is not None:
                     cut_in_draft.append(cut_draft.apply(dl, self.keep_inputs))   # the DRAFT stage's configured cut, last
                 if shape_draft is not None:
@@ -2244,6 +2322,7 @@ class Stage:
             if wm is not None:
                 wm.apply(t_out, tokens, seq_len)                        # row j under the green list the draft's proposal j was drawn under
             rel_in = rel.apply(t_out, sampler.coin, self.keep_inputs) if rel is not None else None   # the call's own relative cut; row j under coin j
+            tfs_in = tfs.apply(t_out, self.keep_inputs) if tfs is not None else None    # the call's own tail-free cut on the K + 1 rows
             cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None    # the call's own cut on the K + 1 rows
             shape_in = shape.apply(t_out, self.keep_inputs) if shape is not None else None   # the call's own shaping on the K + 1 rows
             miro_in = miro.apply(t_out, tok32, self.keep_inputs) if miro is not None else None   # Mirostat, chained through the rows
@@ -2253,6 +2332,8 @@ class Stage:
                 kept["cut_in"] = cut_in
             if kept is not None and rel is not None:
                 kept.update(rel_in=rel_in, rel_coins=None if sampler.coin is None else sampler.coin.clone())
+            if kept is not None and tfs is not None:
+                kept["tfs_in"] = tfs_in
             if kept is not None and shape is not None:
                 kept["shape_in"] = shape_in
             if kept is not None and miro is not None:
@@ -2304,6 +2385,7 @@ class Stage:
         cap = P + max_tokens
         end, mask, bad, edit, pen, top, sampler = st.end, st.mask, st.bad, st.edit, st.pen, st.top, st.sampler
         ngram, stat, cut, dry, miro, rel, shape, wm = st.ngram, st.stats, st.cut, st.dry, st.miro, st.rel, st.shape, st.wm
+        tfs = st.tfs
         tokens, lps, seq_len, n_commit = self._buffers(ids, cap)
         target.reset()
         target.alloc_ragged(B, cap + Kd + 2)
@@ -2335,6 +2417,7 @@ class Stage:
             if wm is not None:
                 wm.apply(t_out, tokens, seq_len)
             rel_in = rel.apply(t_out, sampler.coin, self.keep_inputs) if rel is not None else None
+            tfs_in = tfs.apply(t_out, self.keep_inputs) if tfs is not None else None
             cut_in = cut.apply(t_out, self.keep_inputs) if cut is not None else None
             shape_in = shape.apply(t_out, self.keep_inputs) if shape is not None else None
             miro_in = miro.apply(t_out, tok32, self.keep_inputs) if miro is not None else None
@@ -2346,6 +2429,8 @@ class Stage:
                     kept["cut_in"] = cut_in
                 if rel is not None:
                     kept.update(rel_in=rel_in, rel_coins=None if sampler.coin is None else sampler.coin.clone())
+                if tfs is not None:
+                    kept["tfs_in"] = tfs_in
                 if shape is not None:
                     kept["shape_in"] = shape_in
                 if miro is not None:

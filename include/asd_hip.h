@@ -938,6 +938,53 @@ int asd_relative_cut_rows(void* logits /*in/out*/, int dtype, int B, int K1, int
                           int64_t ld_coin, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * TAIL-FREE sampling ahead of the samplers -- `tfs` of text-generation-webui, koboldcpp, KoboldAI and Aphrodite
+ * (TailFreeLogitsWarper with min_tokens_to_keep = 1), `tfs_z` of older llama.cpp: the one truncation that needs the row in
+ * SORTED order.  One in-place pass behind asd_relative_cut_rows and ahead of asd_entropy_cut_rows.  llama.cpp's tfs_z keeps one
+ * token fewer: it resizes to i*, this rule keeps i* + 1.
+ * logits: asd_relative_cut_rows' addressing -- element (b, j, v) at b*ld_seq + j*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K1*ld_row, the base aligned to the element size only.
+ * table: B records {float inv_t; float z} (asd_tail_free_rec, 8 bytes) on the device; all K1 rows of sequence b use record b.
+ * The input is the row as every earlier pass left it, the values the stored ones, fin the set of its finite elements and
+ * n = |fin|.  A -inf element carries no mass, stays -inf and is in no statistic.
+ *   Weights: w_v = exp(inv_t * (x_v - x_max)) in f64, unnormalised (the normaliser cancels below: no log-sum-exp).  The finite
+ *     elements sorted by value, descending: w_(0) >= w_(1) >= ... >= w_(n-1).
+ *   Differences: d1_i = w_(i) - w_(i+1) for 0 <= i < n-1; d2_i = |d1_i - d1_(i+1)| for 0 <= i < n-2; S = sum d2_i;
+ *     c_i = d2_0 + ... + d2_i.
+ *   Cut: i* is the first i with c_i > z * S, the product formed in f64 from the f32 z.  x_cut is the stored value at sorted
+ *     position i*; element v is cut iff x_v < x_cut.  Every tie at x_cut stays (this build's tie rule, XTC's).  Equal values
+ *     give zero differences, so the result depends on the row's multiset of values only, not on how a sort orders ties or +-0.
+ *     The arg-max is never cut and a row is never emptied.
+ * Rows that are not changed: z == 1: off, the row is not read.  THE DATA CONTRACT: z outside (0, 1], or an inv_t that is not a
+ * positive finite number: the record is damaged and its rows are skipped.  n < 3, S == 0, or a NaN or +inf element: the row is
+ * left bit for bit.
+ * A cut element becomes -inf of the dtype; nothing else is written; a 16-byte vector is stored only where a bit of it changes.
+ * Arithmetic: one workgroup of 1024 threads per (b, j).  The finite elements' bits, under a transform that keeps their order
+ * (16-bit keys for bf16 / f16, 32-bit for f32), are sorted by an LSD radix sort of 8-bit digits between two key buffers of
+ * the row in the workspace.  Lane t then owns the d2_i of i in [t*C, (t+1)*C), C = ceil(n / 1024): x - x_max, the product
+ * with double(inv_t), the exp, both differences and every sum are f64, each operation rounding once, nothing fused.  ORDER of
+ * the additions: a lane adds its d2 in ascending i; inside a wave lane l adds the partial sums of lanes l-1, l-2, l-4, ... l-32
+ * in that order (an inclusive scan); the sixteen wave totals are added in wave order, which gives S and every lane's exclusive
+ * prefix P_t = (waves before) + (lanes before).  The first lane with P_t + s_t > z*S repeats its additions, and i* is the
+ * first i of its chunk with P_t + (d2 of the chunk up to i) > z*S.  The result depends on the row's bytes and its record only.
+ * workspace: >= asd_tail_free_workspace_bytes(B, K1, V, dtype) bytes -- per row two key buffers of V keys, each rounded up to
+ * 256 bytes; a multiple of 256; 256 for empty or invalid sizes -- aligned to 256; no initialisation, and nothing it held
+ * before a call is read.
+ * Status, in this order: negative B / K1 / V: invalid argument; B, K1 or V == 0: ASD_OK, nothing launched; unknown dtype,
+ * B*K1 > INT32_MAX, V * element size > INT32_MAX: unsupported; NULL logits / table / workspace, ld_row < V, ld_seq < K1*ld_row,
+ * workspace_bytes too small: invalid argument; logits not aligned to the element size, table not to 4, workspace not to 256:
+ * alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_TAIL_FREE_REC_BYTES 8
+typedef struct asd_tail_free_rec {
+    float inv_t;   /* 1 / temperature of the sequence */
+    float z;       /* tfs in (0, 1]; 1: off */
+} asd_tail_free_rec;
+size_t asd_tail_free_workspace_bytes(int B, int K1, int V, int dtype);
+int asd_tail_free_rows(void* logits /*in/out*/, int dtype, int B, int K1, int V, int64_t ld_seq, int64_t ld_row,
+                       const asd_tail_free_rec* table /*[B]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SHAPING ahead of the samplers -- llama.cpp's / koboldcpp's dynamic temperature (`dynatemp_range`, `dynatemp_exponent`) and
  * the quadratic "smooth" sampling of text-generation-webui, koboldcpp and Aphrodite (`smoothing_factor`, `smoothing_curve`):
  * the two samplers that reshape a distribution instead of cutting it.  One in-place pass behind asd_entropy_cut_rows and ahead

@@ -629,6 +629,35 @@ int main() {
 #undef REL
     }
 
+    // ---- asd_tail_free_rows: asd_relative_cut_rows' order with a workspace in the coins' place, and the size query
+    {
+#define TFS(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, ws_, wsb_) asd_tail_free_rows(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, ws_, wsb_, nullptr)
+        const int K1 = 5;
+        const asd_tail_free_rec* tab = reinterpret_cast<const asd_tail_free_rec*>(rows);
+        const size_t need = asd_tail_free_workspace_bytes(B, K1, V, BF16);
+        if (need != static_cast<size_t>(B) * K1 * 2 * 2048 || asd_tail_free_workspace_bytes(B, K1, 3, 0 /*f32*/) != static_cast<size_t>(B) * K1 * 2 * 256 ||
+            asd_tail_free_workspace_bytes(0, K1, V, BF16) != 256 || asd_tail_free_workspace_bytes(B, K1, V, 99) != 256) {
+            std::printf("FAIL tail-free workspace sizes %zu\n", need);
+            ++failures;
+        }
+        EXPECT(TFS(p, BF16, -1, K1, V, K1 * V, V, tab, p, need), ASD_ERR_INVALID_ARG);
+        EXPECT(TFS(p, BF16, B, -1, V, K1 * V, V, tab, p, need), ASD_ERR_INVALID_ARG);
+        EXPECT(TFS(p, BF16, B, K1, -1, K1 * V, V, tab, p, need), ASD_ERR_INVALID_ARG);
+        EXPECT(TFS(nullptr, 99, 0, K1, V, 0, 0, nullptr, nullptr, 0), ASD_OK);
+        EXPECT(TFS(nullptr, 99, B, K1, V, K1 * V, V, tab, p, need), ASD_ERR_UNSUPPORTED);               // dtype, before the NULL checks
+        EXPECT(TFS(p, 0 /*f32*/, B, 1, INT32_MAX, INT32_MAX, INT32_MAX, tab, p, need), ASD_ERR_UNSUPPORTED);
+        EXPECT(TFS(nullptr, BF16, B, K1, V, K1 * V, V, tab, p, need), ASD_ERR_INVALID_ARG);
+        EXPECT(TFS(p, BF16, B, K1, V, K1 * V, V, nullptr, p, need), ASD_ERR_INVALID_ARG);
+        EXPECT(TFS(p, BF16, B, K1, V, K1 * V, V, tab, nullptr, need), ASD_ERR_INVALID_ARG);
+        EXPECT(TFS(p, BF16, B, K1, V, K1 * V, V - 1, tab, p, need), ASD_ERR_INVALID_ARG);                // ld_row < V
+        EXPECT(TFS(p, BF16, B, K1, V, K1 * V - 1, V, tab, p, need), ASD_ERR_INVALID_ARG);                // ld_seq < K1 ld_row
+        EXPECT(TFS(p, BF16, B, K1, V, K1 * V, V, tab, p, need - 1), ASD_ERR_INVALID_ARG);                // workspace too small
+        EXPECT(TFS(rows + 1, BF16, B, K1, V, K1 * V, V, tab, p, need), ASD_ERR_ALIGNMENT);               // below the element size
+        EXPECT(TFS(p, BF16, B, K1, V, K1 * V, V, reinterpret_cast<const asd_tail_free_rec*>(rows + 2), p, need), ASD_ERR_ALIGNMENT);
+        EXPECT(TFS(p, BF16, B, K1, V, K1 * V, V, tab, rows + 8, need), ASD_ERR_ALIGNMENT);               // workspace below 256
+#undef TFS
+    }
+
     // ---- asd_logit_shape_rows: asd_relative_cut_rows' order without the coins
     {
 #define SHP(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_) asd_logit_shape_rows(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, nullptr)
