@@ -35,6 +35,7 @@ WATERMARK_REC_BYTES = 16              # ASD_WATERMARK_REC_BYTES: one {key_lo u32
 MAX_LOOKUP_TOKENS, MAX_LOOKUP_NGRAM, LOOKUP_TILE = 16, 8, 4096   # ASD_MAX_LOOKUP_TOKENS, ASD_MAX_LOOKUP_NGRAM, ASD_LOOKUP_TILE (asd_lookup_propose)
 CFG_REC_BYTES, CFG_RESIDENT_VECTORS, MAX_GUIDANCE_SCALE = 8, 19456, 100.0   # ASD_CFG_REC_BYTES ({scale f32, uncond_seq i32}), ASD_CFG_RESIDENT_VECTORS, ASD_MAX_GUIDANCE_SCALE (asd_cfg_rows)
 TAIL_FREE_REC_BYTES = 8               # ASD_TAIL_FREE_REC_BYTES: one {inv_t f32, z f32} record of asd_tail_free_rows
+TYPICAL_ACCEPT_REC_BYTES, TYPICAL_ACCEPT_MAX_K, TYPICAL_ACCEPT_MAX_SPLITS = 16, 16, 16   # ASD_TYPICAL_ACCEPT_*: one {inv_t, ln_eps, ln_alpha, pad} f32 record of asd_typical_accept, its K and splits limits
 MAX_MLP_DIM = 1024
 SAMPLING_ROW_BYTES = 32
 NUM_LP_STATS = 5
@@ -140,6 +141,8 @@ SIGNATURES = {
     "asd_cfg_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i64, _i64, _vp, _vp]),
     "asd_tail_free_rows": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asd_tail_free_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "asd_typical_accept": (_i, [_vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asd_typical_accept_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "asd_step_uniforms_ex": (_i, [_vp, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "asd_fsm_mask_rows": (_i, [_vp, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "asd_fsm_advance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _vp]),

@@ -46,6 +46,7 @@ SOURCES = {
     "mirostat.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # keys and sums a reference must be able to restate
     "relative_cut.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # sums a reference must be able to bound term by term
     "tail_free.hip": ["-ffp-contract=off"],       # f64 differences and sums that the header fixes operation by operation: nothing may fuse
+    "typical_accept.hip": ["-ffp-contract=off"],  # the three-term record's fmas are written out; nothing else may fuse
     "logit_shape.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],   # relative_cut.hip's flags: sums and a polynomial a reference must be able to bound term by term
     "watermark.hip": ["-ffp-contract=off"],      # integer rounds and one f32 add per green element: nothing to fuse
     "lookup.hip": [],                          # integer compares, a 64-bit max and stores of two constants: no floating-point arithmetic

@@ -589,6 +589,21 @@ class HipOps:
         call has tfs below 1."""
         return self.K.tail_free_rows(logits, packed, workspace)
 
+    @traced("pack_typical_accept")
+    def pack_typical_accept(self, inv_t, eps, alpha, device):
+        """Every row's 1 / temperature, hard threshold eps (in (0, 1]) and alpha (in (0, 100]) -> the device table of
+        typical_accept (kernels.pack_typical_accept: one upload per generate call)."""
+        return self.K.pack_typical_accept(inv_t, eps, alpha, device)
+
+    @traced("typical_accept")
+    def typical_accept(self, logits, tok, packed, workspace=None, splits=0):
+        """Typical acceptance, the lossy verify rule (asd_typical_accept): logits [B, K, V] (any strides with a unit last
+        stride), tok int32 [B, K] -> (lp_t [B, K], entropy [B, K], accept_bits int64 [B], n_acc int32 [B]): proposal k is accepted
+        when ln p_t(tok) > min(ln eps, ln alpha - H(p_t)); n_acc is the accepted prefix.  Two launches: a sweep over the rows and
+        a finish of one wave per sequence.  A stage loop makes the call in verify_accept's place, and only when the call has
+        typical acceptance on."""
+        return self.K.typical_accept(logits, tok, packed, workspace, splits)
+
     @traced("pack_logit_shape")
     def pack_logit_shape(self, temps, modes, a, b, device):
         """Every row's temperature, mode (0 off, 1 dynatemp, 2 quadratic), a (dynatemp_range or smoothing_factor) and b

@@ -2032,6 +2032,96 @@ def tail_free_rows(logits: torch.Tensor, tfs: TailFree, workspace: Optional[torc
     return logits
 
 
+# ------------------------------------------------------------------------------- typical acceptance (the lossy verify rule)
+_TYPICAL_REC = np.dtype([("inv_t", np.float32), ("ln_eps", np.float32), ("ln_alpha", np.float32), ("pad", np.float32)])
+assert _TYPICAL_REC.itemsize == B.TYPICAL_ACCEPT_REC_BYTES
+
+
+@dataclass
+class TypicalAccept:
+    """The table of asd_typical_accept on the device (pack_typical_accept): B records {inv_t, ln_eps, ln_alpha, pad} of 16
+    bytes, as a uint8 [B, 16] tensor; `workspace`: the slices' records typical_accept allocated for these records' first call,
+    reused by every later call that fits."""
+    table: torch.Tensor
+    B: int
+    workspace: Optional[torch.Tensor] = None
+
+
+def check_typical_accept_rows(inv_t, eps, alpha) -> np.ndarray:
+    """The host side of pack_typical_accept: every row's 1 / temperature (a positive finite number), eps (the hard threshold,
+    Medusa's posterior_threshold, in (0, 1]) and alpha (posterior_alpha, in (0, 100]) -> the records, a numpy structured array
+    that holds ln eps and ln alpha."""
+    inv_t, eps, alpha = list(inv_t), list(eps), list(alpha)
+    if not len(inv_t) == len(eps) == len(alpha):
+        raise ValueError(f"{len(inv_t)} temperatures, {len(eps)} thresholds and {len(alpha)} alphas must describe the same rows")
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))   # noqa: E731
+    rec = np.zeros(len(eps), dtype=_TYPICAL_REC)
+    for i, (t, e, a) in enumerate(zip(inv_t, eps, alpha)):
+        if not number(t) or not 0.0 < float(np.float32(t)) < 3.0e38:
+            raise ValueError(f"row {i}: 1 / temperature must be a positive finite number, got {t!r}")
+        if not number(e) or not 0.0 < float(e) <= 1.0:                               # (NaN included)
+            raise ValueError(f"row {i}: typical_acceptance_threshold must lie in (0, 1], got {e!r}")
+        if not number(a) or not 0.0 < float(a) <= 100.0:
+            raise ValueError(f"row {i}: typical_acceptance_alpha must lie in (0, 100], got {a!r}")
+        rec[i] = (np.float32(t), np.float32(np.log(float(e))), np.float32(np.log(float(a))), 0.0)
+    return rec
+
+
+def pack_typical_accept(inv_t, eps, alpha, device) -> TypicalAccept:
+    """The table of typical_accept from host lists, checked BEFORE anything is uploaded."""
+    rec = check_typical_accept_rows(inv_t, eps, alpha)
+    table = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), _TYPICAL_REC.itemsize).copy()).to(device)
+    return TypicalAccept(table, len(rec))
+
+
+def typical_accept_workspace_bytes(Bv: int, K: int, V: int, splits: int = 0) -> int:
+    """asd_typical_accept_workspace_bytes: B * K * splits records of 16 bytes (splits = 0: sized for 16), a multiple of 256."""
+    return int(_lib().asd_typical_accept_workspace_bytes(int(Bv), int(K), int(V), int(splits)))
+
+
+def typical_accept(logits: torch.Tensor, tok: torch.Tensor, packed: TypicalAccept, workspace: Optional[torch.Tensor] = None,
+                   splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Typical acceptance (asd_typical_accept) -> (lp_t f32 [B, K], entropy f32 [B, K], accept_bits int64 [B], n_acc int32 [B]).
+    logits: [B, K, V], bf16 / f16 / f32, any sequence / row stride with unit stride along V (a [:, :K] view of the target's
+    [B, K + 1, V] output is read where it lies); tok: int32 [B, K].  Row (b, k) under record b: with p = softmax(inv_t x) and H
+    its entropy, the proposal is accepted when ln p(tok) > min(ln eps, ln alpha - H); n_acc is the accepted prefix.  splits:
+    workgroups per row, 1 .. 16; 0: chosen from the device's compute-unit count.  workspace: a uint8 CUDA tensor of at least
+    typical_accept_workspace_bytes(B, K, V, splits) bytes; None: packed.workspace, allocated by the records' first call."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype not in _DTYPE_CODE:
+        raise ValueError("logits must be a bf16 / f16 / f32 CUDA (HIP) tensor; this package has no CPU path")
+    if logits.dim() != 3 or (logits.shape[2] > 1 and logits.stride(2) != 1):
+        raise ValueError("logits must be [B, K, V] with unit stride along V")
+    Bv, K, V = logits.shape
+    if not 1 <= K <= B.TYPICAL_ACCEPT_MAX_K or V < 1:
+        raise ValueError(f"typical acceptance takes 1 .. {B.TYPICAL_ACCEPT_MAX_K} proposals per sequence and V >= 1, got K = {K}, V = {V}")
+    if not 0 <= int(splits) <= B.TYPICAL_ACCEPT_MAX_SPLITS:
+        raise ValueError(f"splits must lie in [0, {B.TYPICAL_ACCEPT_MAX_SPLITS}], got {splits!r}")
+    if tuple(tok.shape) != (Bv, K):
+        raise ValueError(f"tok must be int32 [{Bv}, {K}], got {tuple(tok.shape)}")
+    if packed.B != Bv:
+        raise ValueError(f"the typical-acceptance records were packed for {packed.B} rows; logits have {Bv}")
+    need = typical_accept_workspace_bytes(Bv, K, V, splits)
+    if workspace is None:
+        if packed.workspace is None or packed.workspace.numel() < need or packed.workspace.device != logits.device:
+            packed.workspace = torch.empty((need,), dtype=torch.uint8, device=logits.device)
+        workspace = packed.workspace
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.numel() < need:
+        raise ValueError(f"workspace must be a uint8 CUDA (HIP) vector of at least {need} bytes")
+    lp_t = torch.empty((Bv, K), dtype=torch.float32, device=logits.device)
+    entropy = torch.empty((Bv, K), dtype=torch.float32, device=logits.device)
+    bits = torch.empty((Bv,), dtype=torch.int64, device=logits.device)
+    n_acc = torch.empty((Bv,), dtype=torch.int32, device=logits.device)
+    if Bv == 0:
+        return lp_t, entropy, bits, n_acc
+    ld_seq, ld_row = _logit_strides(logits, K, "K")
+    rc = _lib().asd_typical_accept(logits.data_ptr(), _DTYPE_CODE[logits.dtype], Bv, K, V, ld_seq, ld_row,
+                                   _dev(tok, "tok", torch.int32), _dev(packed.table, "table", torch.uint8), int(splits),
+                                   workspace.data_ptr(), lp_t.data_ptr(), entropy.data_ptr(), bits.data_ptr(), n_acc.data_ptr(),
+                                   _stream())
+    B.check("asd_typical_accept", rc)
+    return lp_t, entropy, bits, n_acc
+
+
 # ------------------------------------------------------------------------------- shaping (dynatemp_* / smoothing_*)
 SHAPE_OFF, SHAPE_DYNATEMP, SHAPE_QUADRATIC = 0, 1, 2
 _SHAPE_REC = np.dtype([("mode", np.int32), ("T", np.float32), ("a", np.float32), ("b", np.float32)])

@@ -51,6 +51,8 @@ configuration only: a value that is set is handed to every stage's generate call
 `PipelineConfig.tfs` (tail-free sampling; serving/stages.py, TAIL-FREE) travels the same way: at stage 0 it is the stage's own
 draws, at a verifying stage the target's own distribution (StageConfig.target_tfs's place); a verifying stage's draft rows take
 the draft stage's StageConfig.tfs.
+`PipelineConfig.typical_acceptance_threshold` / `typical_acceptance_alpha` (serving/stages.py, TYPICAL ACCEPTANCE) travel the
+same way; stage 0 ignores them.
 `PipelineConfig.dynatemp_range` / `dynatemp_exponent` / `smoothing_factor` / `smoothing_curve` (serving/stages.py, SHAPING) too.
 `PipelineConfig.dry_multiplier` / `dry_base` / `dry_allowed_length` / `dry_range` / `dry_sequence_breakers` (the DRY sampler;
 serving/stages.py, DRY) travel the same way: configuration only, a set value is handed on, None is not passed.
@@ -246,6 +248,10 @@ class PipelineConfig:
     xtc_probability: Optional[float] = None
     # tail-free sampling, handed to stage.generate(tfs=); None: the keyword is not passed (serving/stages.py, TAIL-FREE)
     tfs: Optional[float] = None
+    # typical acceptance, handed to stage.generate(typical_acceptance_threshold=, typical_acceptance_alpha=); None: the keyword
+    # is not passed (serving/stages.py, TYPICAL ACCEPTANCE)
+    typical_acceptance_threshold: Optional[float] = None
+    typical_acceptance_alpha: Optional[float] = None
     # dynamic temperature and quadratic sampling, handed to stage.generate(dynatemp_range=, dynatemp_exponent=,
     # smoothing_factor=, smoothing_curve=); None: the keyword is not passed (serving/stages.py, SHAPING)
     dynatemp_range: Optional[float] = None
@@ -316,6 +322,7 @@ class PipelineConfig:
             kw["no_repeat_ngram_size"] = int(sec["no_repeat_ngram_size"])
         for name in ("typical_p", "epsilon_cutoff", "eta_cutoff", "mirostat_tau", "mirostat_eta",
                      "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability", "tfs",
+                     "typical_acceptance_threshold", "typical_acceptance_alpha",
                      "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve"):
             if sec.get(name) is not None:
                 kw[name] = float(sec[name])
@@ -688,6 +695,7 @@ class AdaptiveSpeculativePipeline:
                              "mirostat_tau", "mirostat_eta",                     # ... and Mirostat
                              "top_n_sigma", "top_a", "xtc_threshold", "xtc_probability",     # ... and the relative cuts
                              "tfs",                                              # ... and tail-free sampling
+                             "typical_acceptance_threshold", "typical_acceptance_alpha",    # ... and typical acceptance
                              "dynatemp_range", "dynatemp_exponent", "smoothing_factor", "smoothing_curve",    # ... and the shaping
                              "watermark_key", "watermark_delta", "watermark_gamma", "watermark_context",     # ... and the watermark
                              "prompt_lookup_num_tokens", "prompt_lookup_max_ngram", "prompt_lookup_min_ngram",    # ... and prompt lookup

@@ -264,6 +264,54 @@ def check_tail_free_alone(tfs_rows, rel_rows, cut_rows, miro_rows=None, side: st
             raise ValueError(f"prompt {b}: tfs together with Mirostat on one row is not built")
 
 
+TYPICAL_ACCEPT_THRESHOLD, TYPICAL_ACCEPT_ALPHA = 0.09, 0.3     # Medusa's posterior_threshold / posterior_alpha defaults
+TYPICAL_ACCEPT_MAX_K = 16                                      # ASD_TYPICAL_ACCEPT_MAX_K of include/asd_hip.h
+
+
+def check_typical_accept(threshold, alpha, n: int) -> Optional[List[Tuple[float, float]]]:
+    """generate's `typical_acceptance_threshold` (eps, in (0, 1]) and `typical_acceptance_alpha` (in (0, 100]): each None (off),
+    one number for all `n` prompts or a sequence of n entries -> every row's (eps, alpha), or None when every row is off.  A row
+    is on when either of its two values is given; the one that is missing takes Medusa's default (0.09 / 0.3).  A bool, a NaN,
+    a value outside its range, the wrong length, and a list that mixes rows that are on with rows that are off ("not built")
+    raise ValueError."""
+    def number(name, hi):
+        def one(v):
+            if v is None:
+                return None
+            ok = not isinstance(v, bool) and isinstance(v, _NUMBER) and 0.0 < float(v) <= hi      # (NaN included)
+            if not ok:
+                raise ValueError(f"{name} must be a number in (0, {hi:g}] or None (off), got {v!r}")
+            return float(v)
+        return one
+    for name, value in (("typical_acceptance_threshold", threshold), ("typical_acceptance_alpha", alpha)):
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name} must be a number or one number per prompt, got {value!r}")
+    eps = _per_prompt(threshold, n, number("typical_acceptance_threshold", 1.0), "typical_acceptance_threshold values")
+    alphas = _per_prompt(alpha, n, number("typical_acceptance_alpha", 100.0), "typical_acceptance_alpha values")
+    on = [e is not None or a is not None for e, a in zip(eps, alphas)]
+    if not any(on):
+        return None
+    if not all(on):
+        raise ValueError("typical acceptance on some prompts and the lossless rule on others in one call is not built: "
+                         f"prompt {on.index(False)} has neither typical_acceptance_threshold nor typical_acceptance_alpha")
+    return [(TYPICAL_ACCEPT_THRESHOLD if e is None else e, TYPICAL_ACCEPT_ALPHA if a is None else a) for e, a in zip(eps, alphas)]
+
+
+def check_typical_accept_alone(rows, top_k, top_p, min_p, miro_rows, draft_len: int) -> None:
+    """Typical acceptance reads the target's whole processed row: target-side top-k, top-p or min-p, or Mirostat, on a row of
+    the call is not built and raises ValueError, as does a step of more than 16 proposals.  rows: check_typical_accept's (not
+    None); top_k / top_p / min_p: one value or a list per row; miro_rows: every row's (tau, eta)."""
+    n = len(rows)
+    if draft_len > TYPICAL_ACCEPT_MAX_K:
+        raise ValueError(f"typical acceptance verifies at most {TYPICAL_ACCEPT_MAX_K} proposals per step, got {draft_len}")
+    cols = [v if isinstance(v, list) else [v] * n for v in (top_k, top_p, min_p)]
+    for b, (k, p, m) in enumerate(zip(*cols)):
+        if int(k) > 0 or 0.0 < float(p) < 1.0 or float(m) > 0.0:
+            raise ValueError(f"prompt {b}: typical acceptance together with target-side top-k, top-p or min-p on one row is not built")
+        if miro_rows and miro_rows[b][0] > 0.0:
+            raise ValueError(f"prompt {b}: typical acceptance together with Mirostat on one row is not built")
+
+
 SHAPE_OFF, SHAPE_DYNATEMP, SHAPE_QUADRATIC = 0, 1, 2     # ASD_SHAPE_* of include/asd_hip.h (SHAPING)
 
 

@@ -535,6 +535,30 @@ at B = 8 at the Qwen2.5-7B shape: 1229.8 ms with tfs on against 1219.9 ms off (1
 bytes of LDS, no scratch, a workspace of 175 MB / 19 MB; the phases were not timed apart.  NOT BUILT beside the above:
 serving/hierarchy.py's loop.
 
+TYPICAL ACCEPTANCE.  `generate(typical_acceptance_threshold=, typical_acceptance_alpha=)` is Medusa's posterior_threshold /
+posterior_alpha and vLLM's TypicalAcceptanceSampler: the one LOSSY verify rule.  Every other verifying route is lossless (the
+sampled ones accept with log u <= lp_t - lp_d, the greedy one on arg-max equality); this one trades a bounded, tunable drift of
+the distribution for more tokens per target pass.  Each argument is None (the configuration's StageConfig field of the same
+name; off when that is None too), one number for the call or one per prompt: eps in (0, 1], alpha in (0, 100]; a row that
+names one of the two takes the other's Medusa default, 0.09 / 0.3.  At a verifying stage and under prompt lookup (both settle
+through the sampler), with p the softmax of the target's PROCESSED row at the row's temperature and H its entropy in nats:
+  accept proposal k       p(tok_k) > min(eps, alpha exp(-H))      -- no uniform is drawn, the draft's probability is not read
+  n_acc                   the accepted prefix
+  the token behind it     a plain draw from the target's own distribution at row n_acc (the bonus row when all K were accepted):
+                          the row is gathered on the device into [B, V] and handed to the stage's draft_sample op with the step's
+                          commit uniform; the op's log q(tok) is the committed token's reported log-prob
+  accepted tokens         report the kernel's lp_t = ln p(tok_k)
+Where the target is confident it demands the likely token; where it is spread out it lets any plausible proposal through.
+The verify op is ops.typical_accept (asd_typical_accept: a sweep over the K rows where they lie in the target's output and a
+finish of one wave per sequence) with each row's own 1 / T; the records are uploaded once per call through
+ops.pack_typical_accept.  Mask, automaton, bad words, n-gram, edits, penalties, DRY, watermark, the cuts, the shaping and
+guidance run ahead as always, so H and lp_t are those of the processed row.  NOT BUILT (ValueError): target-side top-k, top-p
+or min-p on the same row; Mirostat on the same row; a per-prompt list that mixes rows that are on with rows that are off; more
+than 16 proposals per step; serving/hierarchy.py's loop.  Greedy decoding and a stage with neither a draft nor lookup ignore
+the arguments; a call with the feature off makes exactly the ops calls it made before.  stats["typical_accepted"][i] and
+stats["typical_proposed"][i] count row i's accepted and made proposals over the steps in which the row committed a token; they
+accumulate on the device and are read once at the end.
+
 SHAPING.`generate(dynatemp_range=, dynatemp_exponent=, smoothing_factor=, smoothing_curve=)` are llama.cpp's / koboldcpp's
 dynamic temperature and the quadratic ("smooth") sampling of text-generation-webui, koboldcpp and Aphrodite: the two samplers
 that RESHAPE a row's distribution instead of cutting it, the usual companions of DRY and XTC.  Each takes one number for the
@@ -685,7 +709,7 @@ from .stage_args import (MAX_BAD_WORD_LEN, MAX_BAD_WORDS, MAX_LOGIT_EDITS, MAX_N
                          _check_logprobs, _check_min_p, _check_prompt_logprobs, _check_stop_ids, _check_stop_sequences, _check_token_stats,
                          _is_seq,
                          check_allowed_token_ids, check_bad_words, check_banned_token_ids, check_frequency_penalty, check_guided, check_logit_bias, check_max_tokens, check_min_tokens, check_ngram_rows_keep_a_token, check_no_repeat_ngram_size, check_per_prompt,
-                         check_dry, check_entropy_cuts, check_guidance, check_prompt_lookup, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_tail_free, check_tail_free_alone, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
+                         check_dry, check_entropy_cuts, check_guidance, check_prompt_lookup, check_watermark, check_mirostat, check_mirostat_alone, check_relative_cut_alone, check_relative_cuts, RELCUT_XTC, check_tail_free, check_tail_free_alone, check_typical_accept, check_typical_accept_alone, check_logit_shape_alone, check_logit_shapes, check_presence_penalty, check_repetition_penalty, check_rows_keep_a_token, check_seeds, merge_logit_edits)
 from .guided import MAX_FSM_EDGES, MAX_FSM_STATES, CompiledFsm, TokenFSM, check_guided_rows_keep_a_token, compile_rows  # noqa: F401
 from .synthetic_lm import QWEN25_SHAPES, LMShape, SyntheticLM
 
@@ -741,6 +765,9 @@ class StageConfig:
     # tail-free sampling (module docstring, TAIL-FREE), by the rule of min_p / target_min_p
     tfs: float = 1.0                         # tfs of the stage's own draws and of its proposals, in (0, 1]; 1: off
     target_tfs: float = 1.0                  # ... of a verifying stage's own distribution
+    # typical acceptance (module docstring, TYPICAL ACCEPTANCE): the lossy verify rule of a verifying or lookup call; None: off
+    typical_acceptance_threshold: Optional[float] = None     # eps, Medusa's posterior_threshold, in (0, 1]
+    typical_acceptance_alpha: Optional[float] = None         # Medusa's posterior_alpha, in (0, 100]
     # shaping (module docstring, SHAPING), by the rule of min_p / target_min_p; at most one of the two modes per side
     dynatemp_range: float = 0.0              # llama.cpp's dynatemp_range of the stage's own draws and of its proposals; 0: off
     dynatemp_exponent: float = 1.0           # ... its exponent, > 0
@@ -817,6 +844,7 @@ class _Plan(NamedTuple):
     rel_draft_rows: Optional[list] = None    # a verifying stage: every row's (mode, a, b) of the draft stage's configured top-n-sigma / top-a
     tfs_rows: Optional[list] = None          # every row's z of the stage's own tail-free cut; None: every row off
     tfs_draft_rows: Optional[list] = None    # a verifying stage: every row's z of the draft stage's configured tfs
+    typical_rows: Optional[list] = None      # a verifying or lookup call: every row's (eps, alpha) of typical acceptance; None: off
     shape_rows: Optional[list] = None        # every row's (mode, T, a, b) of the stage's own shaping; None: every row off
     shape_draft_rows: Optional[list] = None  # a verifying stage: every row's (mode, T, a, b) of the draft stage's configured shaping
     dry: Optional[tuple] = None              # every row's multiplier, base, allowed length and range, and the call's breaker ids; None: every row off
@@ -1339,6 +1367,7 @@ class _Greedy:
     it is the target row's arg-max and the token behind the accepted prefix is the arg-max of the next row, so the text is the
     target's own greedy continuation; log-probs are the model's at temperature 1."""
     dense = False
+    typical = None                               # (greedy decoding ignores typical acceptance)
 
     def __init__(self, ops):
         self.ops = ops
@@ -1394,6 +1423,13 @@ class _Sampled:
         self.prop = plan.scalars if dcfg is None else (dcfg.top_k, dcfg.top_p, dcfg.min_p)
         self.none_accepted = torch.zeros((B,), dtype=torch.int32, device=device) if dcfg is None else None
         self.rd = self.u = self.r = None         # a seeded call: the step's uniforms (start)
+        # typical acceptance (module docstring, TYPICAL ACCEPTANCE): the rows' records, uploaded once, and the two counters
+        self.typical = None
+        if plan.typical_rows:
+            inv_t = list(plan.rows[0]) if plan.rows else [plan.inv_t] * B
+            eps, alpha = zip(*plan.typical_rows)
+            self.typical = self.ops.pack_typical_accept(inv_t, list(eps), list(alpha), device)
+            self.typ_counts = torch.zeros((2, B), dtype=torch.int64, device=device)      # accepted, proposed
         self.look = self.look_const = None       # a lookup step: (lp_d, d_thr, the one-hot draft rows) (lookup)
 
     def _uniforms(self, step: int, k_draft: int, k_accept: int, commit: bool):
@@ -1401,11 +1437,12 @@ class _Sampled:
         return self.ops.step_uniforms(self.seeds, step, self.stage, k_draft, k_accept, commit=commit, out=self.buf)
 
     def start(self, step: int) -> None:
+        k_accept = 0 if self.typical is not None else self.K             # typical acceptance draws no accept uniform
         if self.seeds is not None and self.k_coin:          # ... and the K + 1 coins from the slots' unused word
-            self.rd, self.u, self.r, self.coin = self.ops.step_uniforms(self.seeds, step, self.stage, self.K, self.K, commit=True,
+            self.rd, self.u, self.r, self.coin = self.ops.step_uniforms(self.seeds, step, self.stage, self.K, k_accept, commit=True,
                                                                         out=self.buf, k_coin=self.k_coin)
         elif self.seeds is not None:             # ONE launch for every uniform of the step
-            self.rd, self.u, self.r = self._uniforms(step, self.K, self.K, True)
+            self.rd, self.u, self.r = self._uniforms(step, self.K, k_accept, True)
         elif self.k_coin:                        # unseeded: the step's coins first, one torch.rand on the stage's generator
             self.coin = torch.rand((self.B, self.k_coin), generator=self.gen, device=self.gen.device)
         self.lpd, self.thrs, self.dls = [], [], []
@@ -1449,7 +1486,34 @@ class _Sampled:
                                torch.full((B, Kd), float("-inf"), dtype=torch.float32, device=onehot.device), onehot)
         self.look = self.look_const
 
+    def _settle_typical(self, t_out, tok32):
+        """Typical acceptance: ops.typical_accept on the K score rows where they lie, then a plain draw of the token behind the
+        accepted prefix from the target's own row n_acc[b] (the bonus row when all K were accepted), gathered on the device."""
+        B, Kd = tok32.shape
+        lp_t, entropy, bits, n_acc = self.ops.typical_accept(t_out[:, :Kd], tok32, self.typical)
+        r = torch.rand((B,), generator=self.gen, device=t_out.device) if self.seeds is None else self.r
+        row = t_out[torch.arange(B, device=t_out.device), n_acc.to(torch.int64)].contiguous()      # [B, V], no read-back
+        drawn, lp_drawn, _ = self._commit_op(row, r)
+        self.last = (t_out[:, :Kd], t_out[:, Kd], tok32, lp_t, entropy, bits, n_acc, row, r, drawn, lp_drawn)
+        return lp_t, n_acc, drawn, lp_drawn
+
+    def _commit_op(self, row, r):
+        """The draw behind a typical-acceptance prefix: the stage's own distribution, which carries no truncation."""
+        return self.ops.draft_sample(row, r, self.inv_t, 1.0)
+
+    def typical_count(self, n_acc, n_commit) -> None:
+        """Behind the commit: a row that committed something this step proposed K tokens and had n_acc accepted."""
+        live = (n_commit > 0).to(torch.int64)
+        self.typ_counts[0] += n_acc.to(torch.int64) * live
+        self.typ_counts[1] += self.K * live
+
+    def typical_stats(self) -> dict:
+        acc, prop = self.typ_counts.cpu().numpy()                        # the one read-back, at the end of the call
+        return {"typical_accepted": [int(v) for v in acc], "typical_proposed": [int(v) for v in prop]}
+
     def settle(self, t_out, tok32):
+        if self.typical is not None:
+            return self._settle_typical(t_out, tok32)
         B, Kd = tok32.shape
         lp_d, d_thr, d_rows = self.look if self.look is not None else \
             (torch.stack(self.lpd, 1).contiguous(), torch.stack(self.thrs, 1).contiguous(), None)
@@ -1466,6 +1530,9 @@ class _Sampled:
 
     def kept(self, seq_len) -> dict:
         seeded = self.rd is not None             # only a seeded call records the uniforms it was handed
+        if self.K and self.typical is not None:
+            names = ("logits", "bonus", "tok", "lp_t", "entropy", "accept_bits", "n_acc", "commit_row", "r_commit", "drawn", "lp_drawn")
+            return _clones(**dict(zip(names, self.last)), seq_len=seq_len)
         if self.K:
             names = ("logits", "bonus", "tok", "lp_d", "u", "lp_t", "n_acc", "drawn", "lp_drawn", "t_thr")
             last = dict(zip(names, self.last), seq_len=seq_len)
@@ -1528,6 +1595,9 @@ class _SampledRows(_Sampled):
     def _verify_op(self, score, tok32, lp_d, u):
         lp_t, _, n_acc, _, t_thr, _ = self.ops.verify_accept_rows(score, tok32, lp_d, u, self.table)
         return lp_t, n_acc, t_thr
+
+    def _commit_op(self, row, r):
+        return self.ops.draft_sample_rows(row, r, self.table)
 
     def _residual_op(self, score, d_rows, n_acc, r, bonus, d_thr, t_thr):
         return self.ops.residual_sample_lp_rows(score, d_rows, n_acc, r, bonus, self.table, d_threshold=d_thr, t_threshold=t_thr)
@@ -1627,6 +1697,7 @@ class Stage:
                             config.target_xtc_probability, 1)
         check_tail_free(config.tfs, 1)
         check_tail_free(config.target_tfs, 1)
+        check_typical_accept(config.typical_acceptance_threshold, config.typical_acceptance_alpha, 1)
         check_logit_shapes(config.dynatemp_range, config.dynatemp_exponent, config.smoothing_factor, config.smoothing_curve, 1)
         check_logit_shapes(config.target_dynatemp_range, config.target_dynatemp_exponent, config.target_smoothing_factor,
                            config.target_smoothing_curve, 1)
@@ -1704,7 +1775,8 @@ class Stage:
                  watermark_key=None, watermark_delta=None, watermark_gamma=None,
                  watermark_context=None, prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None,
                  prompt_lookup_min_ngram=None, guidance_scale=None,
-                 negative_prompt=None, tfs=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
+                 negative_prompt=None, tfs=None, typical_acceptance_threshold=None,
+                 typical_acceptance_alpha=None) -> Tuple[List[str], Optional[List[np.ndarray]], Dict[str, object]]:
         """-> (texts, logprobs, {"generation_time_ms": ...}).  texts[i]: the committed token ids as space-joined token strings
         ("t123 t7 ..."; len(text.split()) is the token count, as the reference counts it); logprobs[i]: float32 [n_i], log-prob
         of every committed token under THIS stage's (truncated, renormalised) distribution.  `top_p` overrides the nucleus of that
@@ -1896,7 +1968,16 @@ class Stage:
         cut stay, the arg-max always stays).  The cut runs behind the relative cut and ahead of the entropy cut.  A row takes
         it alone: together with top_n_sigma, top_a, XTC, typical_p, epsilon_cutoff, eta_cutoff or Mirostat it raises
         ValueError, as do a bool, a NaN, 0, a value outside (0, 1] and the wrong length.  Greedy decoding ignores it (module
-        docstring, TAIL-FREE)."""
+        docstring, TAIL-FREE).
+        `typical_acceptance_threshold` (eps, in (0, 1]) and `typical_acceptance_alpha` (in (0, 100]) switch a verifying or
+        lookup call to typical acceptance (Medusa's posterior_threshold / posterior_alpha, vLLM's TypicalAcceptanceSampler):
+        a proposal is accepted when the target gives it more than min(eps, alpha exp(-H)) of its mass, H the entropy of the
+        target's processed row -- LOSSY, no accept uniform.  Each is None (the configuration's; off when that is None too),
+        one number for the call or one per prompt; giving one takes the other's Medusa default (0.09 / 0.3).  The token
+        behind the accepted prefix is a plain draw from the target's row.  Target-side top-k / top-p / min-p or Mirostat on
+        the same row, a list that mixes on and off rows, more than 16 proposals per step, a bool, a NaN and a value out of
+        range raise ValueError.  Greedy decoding and a stage with neither a draft nor lookup ignore them.
+        stats["typical_accepted"] / ["typical_proposed"]: per row (module docstring, TYPICAL ACCEPTANCE)."""
         t0 = time.perf_counter()
         self.step_inputs = []
         self.prompt_inputs = None
@@ -1908,7 +1989,8 @@ class Stage:
                           dry_sequence_breakers, mirostat_tau, mirostat_eta, top_n_sigma, top_a, xtc_threshold,
                           xtc_probability, dynatemp_range, dynatemp_exponent, smoothing_factor, smoothing_curve,
                           watermark_key, watermark_delta, watermark_gamma, watermark_context, prompt_lookup_num_tokens,
-                          prompt_lookup_max_ngram, prompt_lookup_min_ngram, guidance_scale, negative_prompt, tfs)
+                          prompt_lookup_max_ngram, prompt_lookup_min_ngram, guidance_scale, negative_prompt, tfs,
+                          typical_acceptance_threshold, typical_acceptance_alpha)
         if not plan.prompts or plan.max_tokens <= 0:
             return ["" for _ in plan.prompts], ([np.zeros(0, np.float32) for _ in plan.prompts] if return_logprobs else None), \
                 {"generation_time_ms": 0.0}
@@ -1943,6 +2025,8 @@ class Stage:
             stats.update(state.wm.stats(tokens, P, n_tok))
         if state.lookup is not None:
             stats.update(state.lookup.stats())
+        if plan.typical_rows:
+            stats.update(state.sampler.typical_stats())
         return texts, ([np.ascontiguousarray(r[:n]) for r, n in zip(lp_h, n_tok)] if return_logprobs else None), stats
 
     @torch.no_grad()
@@ -1985,7 +2069,8 @@ class Stage:
               dynatemp_range=None, dynatemp_exponent=None, smoothing_factor=None, smoothing_curve=None,
               watermark_key=None, watermark_delta=None, watermark_gamma=None, watermark_context=None,
               prompt_lookup_num_tokens=None, prompt_lookup_max_ngram=None, prompt_lookup_min_ngram=None,
-              guidance_scale=None, negative_prompt=None, tfs=None) -> _Plan:
+              guidance_scale=None, negative_prompt=None, tfs=None, typical_acceptance_threshold=None,
+              typical_acceptance_alpha=None) -> _Plan:
         """generate's arguments -> the call's _Plan: every check (ValueError before any launch and before encode_prompts), every
         `None = the configuration's` default -- a stage's own side is (top_k, top_p, min_p) at stage 0 and (target_top_k,
         target_top_p, target_min_p) at a verifying stage -- and the choice of route."""
@@ -2102,6 +2187,12 @@ class Stage:
         if live and not isinstance(temperature, list) and not temperature >= 0.0:     # (NaN included)
             raise ValueError("temperature must be >= 0 (0: greedy decoding)")
         greedy = not live or (not isinstance(temperature, list) and temperature == 0.0)
+        typical_rows = check_typical_accept(given(typical_acceptance_threshold, cfg.typical_acceptance_threshold),
+                                            given(typical_acceptance_alpha, cfg.typical_acceptance_alpha), n)
+        if greedy or (self.draft is None and lookup is None):
+            typical_rows = None                  # greedy decoding and a stage that verifies nothing ignore it
+        if typical_rows is not None:
+            check_typical_accept_alone(typical_rows, top_k, top_p, min_p, miro_rows, lookup[0] if lookup else cfg.draft_len)
         if not greedy:                           # a range must stay under the row's temperature; the records carry T itself
             row_t = temperature if isinstance(temperature, list) else [temperature] * n
             check_logit_shape_alone(shape_rows, temps=row_t)
@@ -2126,7 +2217,7 @@ class Stage:
                      cut_draft_rows=cut_draft_rows if not greedy and any(m for m, _ in cut_draft_rows) else None,
                      dry=dry if any(m > 0.0 for m in dry[0]) else None,           # every row off: no state, no call
                      watermark=watermark if any(k is not None for k in watermark[0]) else None,   # no key: no state, no call
-                     lookup=lookup, guidance=guidance,
+                     lookup=lookup, guidance=guidance, typical_rows=typical_rows,
                      rel_rows=rel_rows if not greedy and any(m for m, _, _ in rel_rows) else None,     # greedy ignores the cuts
                      shape_rows=shape_rows if not greedy and any(r[0] for r in shape_rows) else None,  # ... and the shaping
                      tfs_rows=tfs_rows if not greedy and any(z < 1.0 for z in tfs_rows) else None,      # ... and tail-free sampling
@@ -2346,6 +2437,8 @@ class Stage:
             elif top is not None:
                 top.score(t_out)                                        # the [B, K+1, V] output as returned, not a copy
             end.commit(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            if sampler.typical is not None:
+                sampler.typical_count(n_acc, n_commit)
             if miro is not None:
                 miro.commit(n_acc, lp_drawn, seq_len, n_commit)          # mu_{n_acc}, moved by the drawn token's surprise
             if top is not None:
@@ -2440,6 +2533,8 @@ class Stage:
             elif top is not None:
                 top.score(t_out)
             end.commit(tok32, lp_t, n_acc, drawn, lp_drawn, seq_len, tokens, lps, n_commit, cap)
+            if sampler.typical is not None:
+                sampler.typical_count(n_acc, n_commit)
             if miro is not None:
                 miro.commit(n_acc, lp_drawn, seq_len, n_commit)
             if top is not None:

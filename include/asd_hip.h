@@ -985,6 +985,61 @@ int asd_tail_free_rows(void* logits /*in/out*/, int dtype, int B, int K1, int V,
                        const asd_tail_free_rec* table /*[B]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * TYPICAL ACCEPTANCE -- Medusa's `posterior_threshold` / `posterior_alpha`, vLLM's TypicalAcceptanceSampler: the LOSSY verify
+ * rule.  It stands in asd_verify_accept's place behind every in-place pass: no uniform is drawn and the draft's probability is
+ * not read.  Proposal k of sequence b is accepted when
+ *     p_t(tok) > min(eps, alpha * exp(-H(p_t)))      p_t = softmax(inv_t * logits[b][k]), H its entropy in nats
+ * logits: asd_logit_shape_rows' addressing -- element (b, k, v) at b*ld_seq + k*ld_row + v, bf16 / f16 / f32, unit last stride,
+ * any ld_row >= V, any ld_seq >= K*ld_row, a row's first element aligned to the element size only; never written.
+ * tok: int32 [B, K], dense.  table: B records {inv_t, ln_eps, ln_alpha, pad} (asd_typical_accept_rec, 16 bytes) on the device;
+ * all K rows of sequence b use record b; ln_eps = ln(eps), ln_alpha = ln(alpha), formed by the host.
+ * Per row, with y_v = x_v * inv_t over the row's finite elements (a -inf element carries no mass and is in no sum):
+ *     L = ln sum exp y      H = L - (sum y e^y) / (sum e^y), not below 0      lp_t = y_tok - L
+ *     accept = lp_t > min(ln_eps, ln_alpha - H)
+ *     accept_bits[b] = sum_k accept(b, k) << k      n_acc[b] = the number of trailing one bits of accept_bits[b] (<= K)
+ * lp_t and entropy are float [B, K], dense; accept_bits uint64 [B]; n_acc int32 [B].
+ * Special cases.  The row's conditions come first:
+ *   a NaN or +inf element in the row, or an element whose x * log2(e) * inv_t leaves f32's range upwards:
+ *                                                                        lp_t = entropy = NaN, the row rejects
+ *   no finite element in the row (elements with y below -1e30 log 2 count as -inf):      lp_t = entropy = NaN, the row rejects
+ *   tok outside [0, V), or the token's element at -inf:                  lp_t = -inf, entropy as the row gives it, rejects
+ *   THE DATA CONTRACT: a record whose inv_t is not a positive finite number (inv_t <= 0, NaN, inf), or whose ln_eps or
+ *   ln_alpha is not finite: damaged; its K rows are not read, lp_t = entropy = NaN, accept_bits = 0, n_acc = 0.
+ * A row's result never depends on another row.
+ * Arithmetic: two stream-ordered launches and nothing else between workgroups (no barrier across the grid, no atomic).  The
+ * sweep, one workgroup of 1024 threads per (b, k, slice), keeps per lane the record m = max y2, s = sum 2^(y2 - m),
+ * w = sum (y2 - m) 2^(y2 - m) in f32 with y2 = x * c2, c2 = float(log2(e) * double(inv_t)); when m moves by d, w becomes
+ * (w + d s) 2^d beside s 2^d.  Lanes merge by a fixed DPP sequence, waves in wave order, and each slice writes {m, s, w} to the
+ * workspace.  The finish, one wave per sequence, merges a row's slices in slice order in f64, forms L = ln2 (m + log2 s),
+ * H = ln2 (log2 s - w / s), lp_t = ln2 (x_tok c2 - m - log2 s) and the threshold in f64, and ballots.  A result is a function of
+ * the row's bytes, its record and `splits`: the same call gives the same bits.
+ * splits: workgroups per row in [1, ASD_TYPICAL_ACCEPT_MAX_SPLITS]; 0 = heuristic (asd_top_logprobs'), from the device's
+ * compute-unit count.  K <= ASD_TYPICAL_ACCEPT_MAX_K.
+ * workspace: >= asd_typical_accept_workspace_bytes(B, K, V, splits) bytes -- B*K*splits records of 16 bytes, for splits = 0 sized
+ * for ASD_TYPICAL_ACCEPT_MAX_SPLITS; a multiple of 256; 256 for empty or invalid sizes -- aligned to 16; no initialisation,
+ * nothing it held before a call is read.
+ * Status, in this order: negative B / K / V: invalid argument; K > ASD_TYPICAL_ACCEPT_MAX_K, splits outside
+ * [0, ASD_TYPICAL_ACCEPT_MAX_SPLITS]: unsupported; B == 0: ASD_OK, nothing launched; K == 0 or V == 0: invalid argument; unknown
+ * dtype, B*K*16 > INT32_MAX, V * element size > INT32_MAX - 16: unsupported; a NULL pointer, ld_row < V, ld_seq < K*ld_row:
+ * invalid argument; logits not aligned to the element size, tok / lp_t / entropy / n_acc not to 4, accept_bits not to 8, table /
+ * workspace not to 16: alignment.
+ * ---------------------------------------------------------------------------------------- */
+#define ASD_TYPICAL_ACCEPT_REC_BYTES 16
+#define ASD_TYPICAL_ACCEPT_MAX_K 16
+#define ASD_TYPICAL_ACCEPT_MAX_SPLITS 16
+typedef struct asd_typical_accept_rec {
+    float inv_t;      /* 1 / temperature of the sequence */
+    float ln_eps;     /* ln of the hard threshold eps (Medusa's posterior_threshold), eps in (0, 1] */
+    float ln_alpha;   /* ln of alpha (Medusa's posterior_alpha), alpha in (0, 100] */
+    float pad;
+} asd_typical_accept_rec;
+size_t asd_typical_accept_workspace_bytes(int B, int K, int V, int splits);
+int asd_typical_accept(const void* logits, int dtype, int B, int K, int V, int64_t ld_seq, int64_t ld_row,
+                       const int32_t* tok /*[B, K]*/, const asd_typical_accept_rec* table /*[B]*/, int splits, void* workspace,
+                       float* lp_t /*[B, K]*/, float* entropy /*[B, K]*/, uint64_t* accept_bits /*[B]*/, int32_t* n_acc /*[B]*/,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * SHAPING ahead of the samplers -- llama.cpp's / koboldcpp's dynamic temperature (`dynatemp_range`, `dynatemp_exponent`) and
  * the quadratic "smooth" sampling of text-generation-webui, koboldcpp and Aphrodite (`smoothing_factor`, `smoothing_curve`):
  * the two samplers that reshape a distribution instead of cutting it.  One in-place pass behind asd_entropy_cut_rows and ahead

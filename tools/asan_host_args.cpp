@@ -658,6 +658,50 @@ int main() {
 #undef TFS
     }
 
+    // ---- asd_typical_accept: sizes first, B == 0 before everything that needs a row, then dtype, NULLs, strides, alignment
+    {
+#define TYP(x_, dt_, B_, K_, V_, lds_, ldr_, tok_, tab_, s_, ws_, lp_, h_, bits_, n_) \
+    asd_typical_accept(x_, dt_, B_, K_, V_, lds_, ldr_, tok_, tab_, s_, ws_, lp_, h_, bits_, n_, nullptr)
+        const asd_typical_accept_rec* tab = reinterpret_cast<const asd_typical_accept_rec*>(rows);
+        const int32_t* tk = reinterpret_cast<const int32_t*>(rows);
+        float* f = reinterpret_cast<float*>(rows);
+        uint64_t* bits = reinterpret_cast<uint64_t*>(rows);
+        int32_t* na = reinterpret_cast<int32_t*>(rows);
+        if (asd_typical_accept_workspace_bytes(B, K, V, 0) != static_cast<size_t>(B) * K * 16 * 16 ||
+            asd_typical_accept_workspace_bytes(B, K, V, 3) != 1536 || asd_typical_accept_workspace_bytes(1, 1, V, 1) != 256 ||
+            asd_typical_accept_workspace_bytes(0, K, V, 0) != 256 || asd_typical_accept_workspace_bytes(B, 17, V, 0) != 256 ||
+            asd_typical_accept_workspace_bytes(B, K, V, 17) != 256) {
+            std::printf("FAIL typical-accept workspace sizes\n");
+            ++failures;
+        }
+        EXPECT(TYP(p, BF16, -1, K, V, K * V, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, -1, V, K * V, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, -1, K * V, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, 17, V, 17 * V, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_UNSUPPORTED);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, -1, p, f, f, bits, na), ASD_ERR_UNSUPPORTED);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 17, p, f, f, bits, na), ASD_ERR_UNSUPPORTED);
+        EXPECT(TYP(nullptr, 99, 0, K, V, 0, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr), ASD_OK);
+        EXPECT(TYP(p, BF16, B, 0, V, 0, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, 0, 0, 0, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(nullptr, 99, B, K, V, K * V, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_UNSUPPORTED);     // dtype, before the NULL checks
+        EXPECT(TYP(p, 0 /*f32*/, B, 1, INT32_MAX, INT32_MAX, INT32_MAX, tk, tab, 1, p, f, f, bits, na), ASD_ERR_UNSUPPORTED);
+        EXPECT(TYP(nullptr, BF16, B, K, V, K * V, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, nullptr, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, nullptr, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 1, nullptr, f, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 1, p, nullptr, f, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 1, p, f, nullptr, bits, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 1, p, f, f, nullptr, na), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 1, p, f, f, bits, nullptr), ASD_ERR_INVALID_ARG);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V - 1, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);     // ld_row < V
+        EXPECT(TYP(p, BF16, B, K, V, K * V - 1, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_INVALID_ARG);     // ld_seq < K ld_row
+        EXPECT(TYP(rows + 1, BF16, B, K, V, K * V, V, tk, tab, 1, p, f, f, bits, na), ASD_ERR_ALIGNMENT);    // below the element size
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, reinterpret_cast<const asd_typical_accept_rec*>(rows + 8), 1, p, f, f, bits, na), ASD_ERR_ALIGNMENT);
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 1, rows + 8, f, f, bits, na), ASD_ERR_ALIGNMENT);    // workspace below 16
+        EXPECT(TYP(p, BF16, B, K, V, K * V, V, tk, tab, 1, p, f, f, reinterpret_cast<uint64_t*>(rows + 4), na), ASD_ERR_ALIGNMENT);
+#undef TYP
+    }
+
     // ---- asd_logit_shape_rows: asd_relative_cut_rows' order without the coins
     {
 #define SHP(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_) asd_logit_shape_rows(x_, dt_, B_, K1_, V_, lds_, ldr_, tab_, nullptr)
