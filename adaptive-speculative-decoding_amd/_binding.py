@@ -102,6 +102,10 @@ SIGNATURES = {
     "asd_linear_ex": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _sz, _vp]),
     "asd_linear_partial": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _sz, _vp, _vp]),
     "asd_linear_slices": (_i, [_i, _i, _i]),
+    "asd_fp8_image_bytes": (_sz, [_i, _i]),
+    "asd_fp8_quantize_weights": (_i, [_vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
+    "asd_linear_fp8_workspace_bytes": (_sz, [_i, _i, _i]),
+    "asd_linear_fp8": (_i, [_vp, _i64, _vp, _sz, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _sz, _vp]),
     "asd_rmsnorm": (_i, [_vp, _i64, _vp, _f, _i, _i, _i, _vp, _i64, _vp]),
     "asd_rope_kv_store": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "asd_attn_ragged": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),

@@ -31,6 +31,7 @@ SOURCES = {
     "draft_sample.hip": [],
     "verify_nucleus.hip": [],     # shares draft_sample.hip's select (sample_device.hpp) and its flags: the same bits
     "decoder.hip": [],
+    "linear_fp8.hip": ["-ffp-contract=off"],      # the row scale is ONE f32 multiply ahead of the bias: it must not fuse into an fma
     "commit.hip": [],
     "greedy.hip": ["-ffp-contract=off"],          # lp_argmax / lp_target end in finish_row's arithmetic, as verify_accept.hip's do
     "top_logprobs.hip": ["-ffp-contract=off"],    # greedy.hip's (m2, s) stream and row_logprob: slot 0 has lp_argmax's bits

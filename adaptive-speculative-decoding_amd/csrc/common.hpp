@@ -35,6 +35,12 @@ int current_device_cus();
 // top_logprobs.hip): R rows of V elements of esz bytes on `cus` compute units
 int choose_splits(int64_t R, int V, int esz, int cus);
 
+// asd_linear_fp8 (linear_fp8.hip) with asd_linear_partial's contract, for asd_decoder_forward: k_slices_out != NULL and
+// *k_slices_out > 1 on return means y was not written and the scaled f32 partials lie in `workspace` as [k_slices][M][N]
+int linear_fp8_run(const void* x, int64_t ld_x, const void* image, size_t image_bytes, const void* bias, const void* residual,
+                   int64_t ld_res, int dtype, int M, int N, int D, void* y, int64_t ld_y, void* workspace,
+                   size_t workspace_bytes, void* stream, int* k_slices_out);
+
 // ---- shared by the launchers of the sampling steps, the verify step (verify_accept.hip) and the lm_head / linear kernels ----
 
 // f(std::integral_constant<int, ASD_DTYPE_*>{}): the kernels take the element type as a template argument.  Whatever is not

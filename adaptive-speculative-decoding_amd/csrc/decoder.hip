@@ -503,6 +503,11 @@ Scratch scratch_layout(const asd_decoder_shape_t& s, int M) {
     lin = lin > asd_linear_workspace_bytes(M, s.hidden, s.hidden) ? lin : asd_linear_workspace_bytes(M, s.hidden, s.hidden);
     lin = lin > asd_linear_workspace_bytes(M, 2 * s.intermediate, s.hidden) ? lin : asd_linear_workspace_bytes(M, 2 * s.intermediate, s.hidden);
     lin = lin > asd_linear_workspace_bytes(M, s.hidden, s.intermediate) ? lin : asd_linear_workspace_bytes(M, s.hidden, s.intermediate);
+    // ... and of the FP8 products (layers with weights_packed == 2; 0 where a width is no multiple of 256)
+    auto fp8 = [&](size_t n, size_t d) { return asd_linear_fp8_workspace_bytes(M, static_cast<int>(n), static_cast<int>(d)); };
+    for (size_t need : {fp8(s.hidden + 2 * kv, s.hidden), fp8(s.hidden, s.hidden), fp8(2 * static_cast<size_t>(s.intermediate), s.hidden),
+                        fp8(s.hidden, s.intermediate)})
+        lin = lin > need ? lin : need;
     z.lin = take(lin);
     z.total = off;
     return z;
@@ -558,16 +563,24 @@ ASD_EXPORT int asd_decoder_forward(const asd_layer_t* layers, int n_layers, cons
         if (!L.ln1_w || !L.qkv_w || !L.o_w || !L.ln2_w || !L.gate_up_w || !L.down_w || !L.k_cache || !L.vt_cache) return ASD_ERR_INVALID_ARG;
         int ks = 1;
         const int64_t ldw_h = L.weights_packed ? 0 : s.hidden, ldw_i = L.weights_packed ? 0 : s.intermediate;   // 0: tile-major image
+        // weights_packed == 2: the matrix is an FP8 image (asd_linear_fp8); its sliced plans leave SCALED partials, so the slab
+        // consumers below are the same
+        auto project = [&](const void* in, int64_t ld_in, const void* w, int64_t ld_w, const void* bias, const void* res, int64_t ld_res,
+                           int N, int D, void* y, int64_t ld_y) {
+            if (L.weights_packed == 2)
+                return linear_fp8_run(in, ld_in, w, asd_fp8_image_bytes(N, D), bias, res, ld_res, dt, M, N, D, y, ld_y, lin, lin_bytes, stream, &ks);
+            return asd_linear_partial(in, ld_in, w, ld_w, bias, res, ld_res, dt, M, N, D, y, ld_y, lin, lin_bytes, stream, &ks);
+        };
         if (!have_hn) rc = rmsnorm_run(x, ld_x, L.ln1_w, s.rms_eps, dt, M, s.hidden, hn, s.hidden, stream, Slabs{});
-        if (rc == ASD_OK) rc = asd_linear_partial(hn, s.hidden, L.qkv_w, ldw_h, L.qkv_b, nullptr, 0, dt, M, qkv_w, s.hidden, qkv, qkv_w, lin, lin_bytes, stream, &ks);
+        if (rc == ASD_OK) rc = project(hn, s.hidden, L.qkv_w, ldw_h, L.qkv_b, nullptr, 0, qkv_w, s.hidden, qkv, qkv_w);
         if (rc == ASD_OK) rc = rope_kv_run(qkv, qkv_w, pos, rows, s.inv_freq, dt, B, T, s.heads, s.kv_heads, s.head_dim, L.k_cache, L.vt_cache, s.t_max, stream,
                                            slabs_of(lin, ks, M, qkv_w), L.qkv_b);
         if (rc == ASD_OK) rc = asd_attn_ragged(qkv, qkv_w, L.k_cache, L.vt_cache, pos, rows, dt, B, T, s.heads, s.kv_heads, s.head_dim, s.t_max, attn, s.hidden, stream);
-        if (rc == ASD_OK) rc = asd_linear_partial(attn, s.hidden, L.o_w, ldw_h, nullptr, x, ld_x, dt, M, s.hidden, s.hidden, x, ld_x, lin, lin_bytes, stream, &ks);
+        if (rc == ASD_OK) rc = project(attn, s.hidden, L.o_w, ldw_h, nullptr, x, ld_x, s.hidden, s.hidden, x, ld_x);
         if (rc == ASD_OK) rc = rmsnorm_run(x, ld_x, L.ln2_w, s.rms_eps, dt, M, s.hidden, hn, s.hidden, stream, slabs_of(lin, ks, M, s.hidden));
-        if (rc == ASD_OK) rc = asd_linear_partial(hn, s.hidden, L.gate_up_w, ldw_h, nullptr, nullptr, 0, dt, M, 2 * s.intermediate, s.hidden, gu, gu_w, lin, lin_bytes, stream, &ks);
+        if (rc == ASD_OK) rc = project(hn, s.hidden, L.gate_up_w, ldw_h, nullptr, nullptr, 0, 2 * s.intermediate, s.hidden, gu, gu_w);
         if (rc == ASD_OK) rc = silu_mul_run(gu, gu_w, dt, M, s.intermediate, act, s.intermediate, stream, slabs_of(lin, ks, M, 2 * s.intermediate));
-        if (rc == ASD_OK) rc = asd_linear_partial(act, s.intermediate, L.down_w, ldw_i, nullptr, x, ld_x, dt, M, s.hidden, s.intermediate, x, ld_x, lin, lin_bytes, stream, &ks);
+        if (rc == ASD_OK) rc = project(act, s.intermediate, L.down_w, ldw_i, nullptr, x, ld_x, s.hidden, s.intermediate, x, ld_x);
         if (rc != ASD_OK) break;
         // the norm that follows the down projection: the next layer's ln1, or the final norm
         const bool last = l + 1 == n_layers;

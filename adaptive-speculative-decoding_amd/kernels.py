@@ -417,8 +417,8 @@ class LinearWorkspace:
         self.buf: Optional[torch.Tensor] = None
         self.on_grow = on_grow
 
-    def ensure(self, M: int, N: int, D: int) -> Tuple[int, int]:
-        need = int(_lib().asd_linear_workspace_bytes(M, N, D))
+    def ensure(self, M: int, N: int, D: int, fp8: bool = False) -> Tuple[int, int]:
+        need = int((_lib().asd_linear_fp8_workspace_bytes if fp8 else _lib().asd_linear_workspace_bytes)(M, N, D))
         if self.buf is None or self.buf.numel() < need:
             if self.buf is not None and self.on_grow is not None:
                 self.on_grow()
@@ -453,6 +453,52 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
                               0 if residual is None else residual.stride(0), _DTYPE_CODE[x.dtype], M, N, D, out.data_ptr(),
                               out.stride(0), ws_ptr, ws_bytes, _stream())
     B.check("asd_linear_ex", rc)
+    return out.view(*x.shape[:-1], N)
+
+
+def quantize_fp8(weight: torch.Tensor) -> torch.Tensor:
+    """X3, weight-only FP8: a [N, D] bf16 / f16 CUDA matrix (N % 256 == 0, D % 64 == 0) -> its asd_fp8_quantize_weights image,
+    a uint8 CUDA tensor of N * D + 4 * N bytes: E4M3 codes in the order asd_linear_fp8 streams them, then the N f32 row scales
+    (include/asd_hip.h states the layout).  Runs on the device; the matrix never passes through host memory."""
+    if weight.dim() != 2 or weight.dtype not in (torch.bfloat16, torch.float16) or not weight.is_cuda or weight.stride(1) != 1:
+        raise ValueError("weight must be a [N, D] bf16 or f16 CUDA tensor with contiguous rows")
+    N, D = weight.shape
+    nbytes = int(_lib().asd_fp8_image_bytes(N, D))
+    if nbytes == 0:
+        raise ValueError(f"quantize_fp8: shape ({N}, {D}) unsupported (N % 256 == 0 and D % 64 == 0)")
+    image = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    B.check("asd_fp8_quantize_weights", _lib().asd_fp8_quantize_weights(weight.data_ptr(), weight.stride(0), _DTYPE_CODE[weight.dtype],
+                                                                        N, D, image.data_ptr(), nbytes, _stream()))
+    return image
+
+
+def linear_fp8(x: torch.Tensor, image: torch.Tensor, N: int, bias: Optional[torch.Tensor] = None, *, workspace: LinearWorkspace,
+               out: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """X3: y = (x @ codes.T) * scale (+ bias) (+ residual) through asd_linear_fp8.  x [..., D] bf16 or f16, image: quantize_fp8 of
+    the [N, D] matrix; bias / out / residual as in `linear`."""
+    if image.dtype != torch.uint8 or not image.is_cuda or not image.is_contiguous():
+        raise ValueError("image must be a contiguous uint8 CUDA tensor (quantize_fp8)")
+    if x.dtype not in (torch.bfloat16, torch.float16) or not x.is_cuda:
+        raise ValueError("x must be a bf16 or f16 CUDA tensor")
+    D = x.shape[-1]
+    x2 = x.reshape(-1, D)
+    if x2.stride(1) != 1:
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    elif out.shape != (M, N) or out.dtype != x.dtype or out.stride(1) != 1:
+        raise ValueError("out must be a [M, N] tensor of the operands' type with contiguous rows")
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous [N] tensor of the operands' type")
+    if residual is not None and (residual.shape != (M, N) or residual.dtype != x.dtype or residual.stride(1) != 1):
+        raise ValueError("residual must be a [M, N] tensor of the operands' type with contiguous rows")
+    ws_ptr, ws_bytes = workspace.ensure(M, N, D, fp8=True)
+    rc = _lib().asd_linear_fp8(x2.data_ptr(), x2.stride(0), image.data_ptr(), image.numel(),
+                               None if bias is None else bias.data_ptr(), None if residual is None else residual.data_ptr(),
+                               0 if residual is None else residual.stride(0), _DTYPE_CODE[x.dtype], M, N, D, out.data_ptr(),
+                               out.stride(0), ws_ptr, ws_bytes, _stream())
+    B.check("asd_linear_fp8", rc)
     return out.view(*x.shape[:-1], N)
 
 

@@ -997,8 +997,8 @@ def build_rank_roles(rank: int, placement: Placement, shapes: Sequence, cfg: Hie
                      max_new_tokens: int, predictor, ops=None, dtype: torch.dtype = torch.bfloat16,
                      heads: Sequence[str] = ("logits", "fused"), logit_scale: float = 1.0, seeds: Sequence[int] = (1, 2, 3),
                      keep_inputs: bool = False, weight_noise: Sequence[float] = (0.0, 0.0, 0.0), share_seed: Optional[int] = None,
-                     hip_layers: Optional[bool] = None, pack_weights: bool = False, backend: Optional[str] = None
-                     ) -> Tuple[Optional[DraftRole], Dict[int, VerifyRole]]:
+                     hip_layers: Optional[bool] = None, pack_weights: bool = False, backend: Optional[str] = None,
+                     weights: str = "bf16") -> Tuple[Optional[DraftRole], Dict[int, VerifyRole]]:
     """The roles `rank` hosts under `placement`: tier 0 + verify tiers, models built on prompt_ids.device.
     shapes: one synthetic_lm.LMShape per tier.  heads[s-1]: "logits" (lm_head GEMM + asd_verify_accept), "fused"
     (asd_lm_head_verify from hidden states); a tier placed on several ranks gets a ShardedHead over those ranks
@@ -1008,6 +1008,8 @@ def build_rank_roles(rank: int, placement: Placement, shapes: Sequence, cfg: Hie
     hip_layers: run the models' passes through asd_decoder_forward (serving/hip_decoder.py) instead of torch modules.  None:
     wherever the stack supports the model (CUDA, bf16, head_dim 128 -- every Qwen2.5 shape); True: required (raises
     otherwise); False: torch modules.  `model.execution` on every role's model says which one it got.
+    weights: "fp8" runs every tier's layers on weight-only FP8 images (HipDecoder(weights="fp8")); it requires the HIP stack
+    (hip_layers must not be False) and cannot be combined with pack_weights.
     backend: the backend of the process group a vocab-sharded tier creates ("nccl" when the job's default group is a gloo
     control group and the data path is RCCL); None = the default group's."""
     from .synthetic_lm import SyntheticLM
@@ -1024,7 +1026,11 @@ def build_rank_roles(rank: int, placement: Placement, shapes: Sequence, cfg: Hie
         # anything else instead of raising at the first pass; hip_layers=True keeps raising
         can = (dev.type == "cuda" and dtype == torch.bfloat16 and sh.head_dim == 128 and sh.hidden == sh.heads * sh.head_dim
                and sh.hidden % 64 == 0 and sh.intermediate % 64 == 0 and sh.hidden <= 8192 and sh.heads % sh.kv_heads == 0)
-        if hip_layers or (hip_layers is None and can):
+        if weights == "fp8":
+            if hip_layers is False or pack_weights:
+                raise ValueError("weights='fp8' needs the HIP decoder stack (hip_layers is False) and excludes pack_weights")
+            m.enable_hip_layers(weights="fp8")
+        elif hip_layers or (hip_layers is None and can):
             # pack_weights: the projection matrices re-laid tile-major in place (HipDecoder) where every row count allows it
             packable = pack_weights and all(n % 256 == 0 for n in (shapes[i].hidden, shapes[i].hidden + 2 * shapes[i].kv_heads * shapes[i].head_dim,
                                                                   2 * shapes[i].intermediate))

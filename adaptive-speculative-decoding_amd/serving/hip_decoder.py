@@ -19,8 +19,13 @@ from .. import kernels as K
 
 
 class HipDecoder:
-    def __init__(self, lm, pack_weights: bool = False):
-        """pack_weights: re-lay every projection matrix tile-major IN ITS OWN STORAGE (asd_lm_head_pack_weights: a column block's
+    def __init__(self, lm, pack_weights: bool = False, weights: str = "bf16"):
+        """weights="fp8": quantise the four projection matrices of every layer (fused q|k|v, o, gate|up, down) to weight-only
+        FP8 images (K.quantize_fp8: E4M3 codes, one f32 scale per row) and run them through asd_linear_fp8 -- half the weight
+        bytes per pass.  The bf16 storage of each matrix is RELEASED as soon as its image exists (peak memory is the model plus
+        one matrix), so the torch modules cannot run this model any more (SyntheticLM refuses).  Needs every matrix's row count
+        to be a multiple of 256 and its depth a multiple of 64.  The embedding, lm_head and KV cache stay bf16.
+        pack_weights: re-lay every projection matrix tile-major IN ITS OWN STORAGE (asd_lm_head_pack_weights: a column block's
         64-deep reduction step becomes one contiguous 32 KiB run instead of 256 strided lines; same results bit for bit, 3-7 %
         less time per projection).  Needs every matrix's row count to be a multiple of 256 (all Qwen2.5 shapes); the torch
         modules of this model then hold re-laid bytes and must not be used any more (SyntheticLM refuses)."""
@@ -30,6 +35,10 @@ class HipDecoder:
         s = lm.shape
         if s.head_dim != 128:
             raise RuntimeError(f"HipDecoder: head_dim {s.head_dim} unsupported (128 only)")
+        if weights not in ("bf16", "fp8"):
+            raise ValueError(f"HipDecoder: weights must be 'bf16' or 'fp8', not {weights!r}")
+        if weights == "fp8" and pack_weights:
+            raise ValueError("HipDecoder: weights='fp8' has its own image layout; it cannot be combined with pack_weights=True")
         self.lm = lm
         self.lib = B.load_library()
         self.device = p.device
@@ -62,6 +71,10 @@ class HipDecoder:
                 self.packed = True
             else:
                 raise RuntimeError("HipDecoder(pack_weights=True): a projection's row count is not a multiple of 256")
+        self.weights = weights
+        self._images = []                          # weights == "fp8": per layer (qkv, o, gate|up, down) images
+        if weights == "fp8":
+            self._quantize(lm)
         self.t_max = 0
         self.k_cache = []
         self.vt_cache = []
@@ -69,6 +82,30 @@ class HipDecoder:
         self._shape = None
         self._scratch: Optional[torch.Tensor] = None
         self._lin_ws = K.LinearWorkspace(dev, on_grow=self._drop_graphs)
+
+    def _quantize(self, lm) -> None:
+        """Layer by layer: image of a matrix, then its bf16 storage is dropped (the modules' parameters become empty tensors)."""
+        s = lm.shape
+        widths = (s.hidden + 2 * s.kv_heads * s.head_dim, s.hidden, 2 * s.intermediate)
+        if any(n % 256 for n in widths) or s.hidden % 64 or s.intermediate % 64:
+            raise RuntimeError(f"HipDecoder(weights='fp8'): a projection of {s} has a row count that is no multiple of 256 or a depth that is no multiple of 64")
+        empty = torch.empty(0, dtype=torch.bfloat16, device=self.device)
+
+        def take(mat, mods):
+            img = K.quantize_fp8(mat)
+            for m in mods:
+                m.weight.data = empty              # the last references to the bf16 matrix are the caller's and `mat`
+            return img
+        with torch.no_grad():
+            for i, blk in enumerate(lm.blocks):
+                qkv_w, qkv_b, gu_w = self._fused[i]
+                self._fused[i] = (None, qkv_b, None)
+                qkv_i = take(qkv_w, (blk.q, blk.k, blk.v))
+                del qkv_w
+                o_i = take(blk.o.weight.data, (blk.o,))
+                gu_i = take(gu_w, (blk.gate, blk.up))
+                del gu_w
+                self._images.append((qkv_i, o_i, gu_i, take(blk.down.weight.data, (blk.down,))))
 
     def _drop_graphs(self) -> None:
         """A buffer whose ADDRESS captured hipGraphs hold (KV caches, the decoder scratch, the linear workspace) is about to be
@@ -90,9 +127,13 @@ class HipDecoder:
         arr = (B.Layer * s.layers)()
         for i, blk in enumerate(self.lm.blocks):
             qkv_w, qkv_b, gu_w = self._fused[i]
-            arr[i] = B.Layer(blk.ln1.weight.data_ptr(), qkv_w.data_ptr(), qkv_b.data_ptr(), blk.o.weight.data_ptr(),
-                             blk.ln2.weight.data_ptr(), gu_w.data_ptr(), blk.down.weight.data_ptr(),
-                             self.k_cache[i].data_ptr(), self.vt_cache[i].data_ptr(), 1 if self.packed else 0)
+            if self.weights == "fp8":
+                mats, mode = self._images[i], 2
+            else:
+                mats, mode = (qkv_w, blk.o.weight, gu_w, blk.down.weight), (1 if self.packed else 0)
+            arr[i] = B.Layer(blk.ln1.weight.data_ptr(), mats[0].data_ptr(), qkv_b.data_ptr(), mats[1].data_ptr(),
+                             blk.ln2.weight.data_ptr(), mats[2].data_ptr(), mats[3].data_ptr(),
+                             self.k_cache[i].data_ptr(), self.vt_cache[i].data_ptr(), mode)
         self._layers = arr
         self._shape = B.DecoderShape(s.hidden, s.heads, s.kv_heads, s.head_dim, s.intermediate, float(s.rms_eps),
                                      self.inv_freq.data_ptr(), self.t_max)

@@ -724,7 +724,7 @@ class StageConfig:
     model_size: str = "8b"                   # the stage's name: StageManager.get_stage(model_size)
     tensor_parallel_size: int = 1            # recorded only (multi-rank stages are out of scope)
     gpu_memory_utilization: float = 0.8      # recorded only
-    quantized: bool = False                  # recorded only
+    quantized: bool = False                  # True: the layers' projection weights are FP8 (E4M3) images on the HIP decoder stack
     cost_per_token: float = 1.0
     # -- build extensions
     shape: Optional[LMShape] = None          # None: QWEN25_SHAPES by model_size
@@ -1704,8 +1704,19 @@ class Stage:
         check_watermark(config.watermark_key, config.watermark_delta, config.watermark_gamma, config.watermark_context, 1)
         check_prompt_lookup(config.prompt_lookup_num_tokens, config.prompt_lookup_max_ngram, config.prompt_lookup_min_ngram)
         check_guidance(config.guidance_scale, None, 1)
+        if config.quantized:
+            # weight-only FP8 runs on the HIP decoder stack alone (serving/hip_decoder.py): refuse here what it cannot serve
+            sh = self.shape
+            if self.device.type != "cuda" or config.dtype != torch.bfloat16:
+                raise ValueError("StageConfig.quantized=True needs a CUDA device and dtype=torch.bfloat16")
+            if sh.head_dim != 128 or sh.hidden != sh.heads * sh.head_dim or sh.hidden > 8192 or any(
+                    n % 256 for n in (sh.hidden, sh.hidden + 2 * sh.kv_heads * sh.head_dim, 2 * sh.intermediate)) or sh.intermediate % 64:
+                raise ValueError(f"StageConfig.quantized=True: shape {sh.name} unsupported (head_dim 128, hidden = heads * 128 <= 8192, "
+                                 "projection row counts multiples of 256)")
         self.model = SyntheticLM(self.shape, dtype=config.dtype, device=self.device, seed=config.model_seed,
                                  logit_scale=config.logit_scale)
+        if config.quantized:
+            self.model.enable_hip_layers(weights="fp8")
         self.tokenizer = SimpleTokenizer()
         self.gen = torch.Generator(device=self.device).manual_seed(int(config.seed))
         self.keep_inputs = False                         # tests: keep every step's inputs and draws in `step_inputs`
@@ -1718,7 +1729,8 @@ class Stage:
         return {"name": self.model_name, "size": self.model_size, "stage": self.index, "shape": self.shape.name,
                 "parameters": self.shape.param_count(), "vocab": self.shape.vocab, "cost_per_token": self.cost_per_token,
                 "draft": None if self.draft is None else self.draft.model_size, "draft_len": c.draft_len,
-                "tensor_parallel_size": c.tensor_parallel_size, "quantized": c.quantized, "device": str(self.device)}
+                "tensor_parallel_size": c.tensor_parallel_size, "quantized": c.quantized, "weight_dtype": "fp8_e4m3" if c.quantized else "bfloat16",
+                "device": str(self.device)}
 
     # ------------------------------------------------------------------------------------------ prompts / text
     def encode_prompts(self, prompts: Sequence[str]) -> torch.Tensor:

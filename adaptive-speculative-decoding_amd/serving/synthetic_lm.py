@@ -209,16 +209,19 @@ class SyntheticLM(nn.Module):
         self._graphs = {} if on else None
         self._max_graphs = int(max_graphs)
 
-    def enable_hip_layers(self, on: bool = True, pack_weights: bool = False) -> None:
+    def enable_hip_layers(self, on: bool = True, pack_weights: bool = False, weights: str = "bf16") -> None:
         """Run forward_ragged through asd_decoder_forward (X3: csrc/decoder.hip + asd_linear; nine launches per layer, one host
         call per pass) instead of the torch modules.  CUDA + bf16 + head_dim 128 only; raises otherwise -- no fallback.  Call
-        before alloc_ragged.  The lock-step `forward` / `truncate` cache keeps the torch modules."""
+        before alloc_ragged.  The lock-step `forward` / `truncate` cache keeps the torch modules.
+        weights="fp8": the layers' projection matrices become weight-only FP8 images (HipDecoder) and their bf16 storage is freed."""
         if getattr(self, "_weights_relaid", False) and not on:
-            raise RuntimeError("this model's projection matrices were re-laid tile-major for the HIP decoder stack: the torch modules cannot run it any more")
+            raise RuntimeError("this model's projection matrices were re-laid (tile-major or FP8) for the HIP decoder stack: the torch modules cannot run it any more")
+        if on and self._hip is not None and self._hip.weights == "fp8":
+            raise RuntimeError("this model's projection matrices are FP8 images already and their bf16 storage is gone: build a new model to change the layout")
         if on:
             from .hip_decoder import HipDecoder
-            self._hip = HipDecoder(self, pack_weights=pack_weights)
-            self._weights_relaid = self._hip.packed
+            self._hip = HipDecoder(self, pack_weights=pack_weights, weights=weights)
+            self._weights_relaid = self._hip.packed or self._hip.weights == "fp8"
         else:
             self._hip = None
         self._ragged = None

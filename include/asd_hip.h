@@ -244,6 +244,36 @@ int asd_linear_partial(const void* x, int64_t ld_x, const void* w, int64_t ld_w,
 int asd_linear_slices(int M, int N, int D);
 
 /* ------------------------------------------------------------------------------------------
+ * X3, weight-only FP8 (W8A16): the same projections on HALF the weight bytes.
+ *   y[m][n] = round( scale[n] * sum_d x[m][d] * code[n][d]  + bias[n] + residual[m][n] )
+ * code: OCP E4M3 ("fn": bias 7, max 448, no infinities), scale: one f32 per weight row; x, bias, residual, y all bf16 or all
+ * f16 (dtype); the codes are widened exactly to the activations' type in the wave, f32 MFMA accumulation, ONE f32 multiply by
+ * the row scale, then bias, then residual, ONE rounding.  Shapes: N % 256 == 0 and D % 64 == 0 (ASD_ERR_UNSUPPORTED otherwise).
+ *
+ * asd_fp8_quantize_weights, per row n of w [N][ld_w] (bf16 / f16), on the device:
+ *   amax = max_d |w[n][d]|;  scale[n] = amax / 448 (f32, correctly rounded; 1 when amax == 0);
+ *   code[n][d] = E4M3 nearest-even of f32(w[n][d]) / scale[n] (correctly rounded f32 division), saturated at +-448: no NaN code
+ * and writes ONE image of asd_fp8_image_bytes(N, D) = N * D + 4 * N bytes (0: unsupported shape), 16-byte aligned:
+ *   codes   [N / 256][D / 64][8][2][64][16] bytes: a column block's 64-deep reduction step ("superstage") is one contiguous
+ *           16 KiB run; in it wave w (weight rows 32 w .. 32 w + 31 of the block) finds, for quarter q = 0, 1 and lane
+ *           l = 32 h + r, the 16 codes of row r at reduction columns 32 h + 16 q .. + 15.  Code (n, d) is byte
+ *             ((n / 256) * (D / 64) + d / 64) * 16384 + ((n % 256) / 32) * 2048 + ((d % 32) / 16) * 1024
+ *                 + (((d % 64) / 32) * 32 + n % 32) * 16 + d % 16
+ *   scales  [N] f32 at byte N * D.
+ * asd_linear_fp8: argument rules of asd_linear_ex (x 16-byte aligned with ld_x % 8 == 0, y 8-byte aligned with ld_y % 4 == 0,
+ * residual may alias y); image_bytes < asd_fp8_image_bytes(N, D) is ASD_ERR_INVALID_ARG.  M <= 64 is the memory-bound form
+ * the kernel is built for; M > 64 runs as row blocks of 64 in the same launch (correct, not fast).  Narrow matrices are cut
+ * into reduction slices whose SCALED f32 partials meet in `workspace` (asd_linear_fp8_workspace_bytes(M, N, D) bytes, no
+ * initialisation needed) and are added in slice order: the same bits on every call. */
+size_t asd_fp8_image_bytes(int N, int D);
+int asd_fp8_quantize_weights(const void* weight, int64_t ld_w, int dtype, int N, int D, void* image /*out*/, size_t image_bytes,
+                             void* stream);
+size_t asd_linear_fp8_workspace_bytes(int M, int N, int D);
+int asd_linear_fp8(const void* x, int64_t ld_x, const void* image, size_t image_bytes, const void* bias, const void* residual,
+                   int64_t ld_res, int dtype, int M, int N, int D, void* y /*[M][ld_y] out*/, int64_t ld_y, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * X3, continued: the rest of a decoder layer around the projections, for the M = B * T positions a tier is fed in one pass
  * (row m = b * T + t), over a per-sequence KV cache.  bf16 only; head_dim 128 (every Qwen2.5 shape).
  *   asd_rmsnorm        out = x * rsqrt(mean(x^2) + eps) * weight, f32 arithmetic, one rounding; D % 4 == 0, D <= 8192
@@ -274,7 +304,8 @@ typedef struct asd_layer {
     const void* down_w;     /* [hidden][intermediate] */
     void* k_cache;
     void* vt_cache;
-    int weights_packed;     /* != 0: the four matrices are tile-major images (asd_lm_head_pack_weights of each, see asd_linear) */
+    int weights_packed;     /* 1: the four matrices are tile-major images (asd_lm_head_pack_weights of each, see asd_linear);
+                             * 2: they are FP8 images (asd_fp8_quantize_weights of each, see asd_linear_fp8) */
 } asd_layer_t;
 typedef struct asd_decoder_shape {
     int hidden, heads, kv_heads, head_dim, intermediate;
